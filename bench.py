@@ -12,8 +12,14 @@ over those 10k reads per GPU: conv -> 5 x (projection + GRU) -> softmax ->
 Viterbi -> backtrace on device, D2H of paths, homopolymer correction + k-mer
 stitching on the host.
 
-Three timed regions, each K steps between barriers (only the first one is the
-contract's `value`; the other two are extra fields of the same JSON line):
+A plain run sets up, warms up, times K steps and prints the JSON line: its `value`,
+`ms_per_step`, stage times and roofline all come from that one timed region.
+--dump-outputs DIR also writes the calls of the last timed step (dump_calls()).
+
+--full adds the records beside the headline, as further fields of the same line: two
+more timed regions, each K steps between barriers, and the batch64, exact_fp32,
+per_read_surface, cli_end_to_end and cpu_baseline records (--no-extra / --no-cpu-baseline
+leave parts of them out):
   1. `value`: inputs resident in HBM when the timed region starts (bench contract).
   2. `host_to_host`: SURVEY 8(d)'s definition -- normalised signal in pageable host
      memory to base strings in host memory through scrappie_hip_basecall_batch
@@ -25,7 +31,7 @@ contract's `value`; the other two are extra fields of the same JSON line):
      random weights decode to ~5 bases per read: S1 + Viterbi (k_ff_viterbi) -> D2H ->
      homopolymer -> overlapper then run on ~400-base calls; bases are COUNTED.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 For N > 1 launch with torch.distributed.run (one rank per GPU); reads are
 sharded across ranks, no data-path collective, weak scaling (10k reads/GPU).
@@ -75,6 +81,33 @@ def make_reads(first_index, n_reads, n_samples, seed, events=False):
         mad = np.median(np.abs(sig - med)) * 1.4826
         flat[i] = (sig - med) / mad
     return flat.ravel(), [flat[i] for i in range(min(n_reads, 64))]
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_calls(out_dir, calls, n):
+    """--dump-outputs: the calls of one launch group as a caller of the timed path receives them (scrappie_hip_collect), as .npy
+    files: score (float32), nblock and basecall_length (float64), called (1 where the read got a call), bases (every read's bases
+    in read order, A C G T = 0 1 2 3, float32) and read_index (float64: which reads the other arrays hold).  Above 64 MB in all,
+    a fixed seeded sample of the reads is written instead of all of them."""
+    from scrappie_amd import _Call
+    raw = np.frombuffer(calls, dtype=np.uint64).reshape(n, C.sizeof(_Call) // 8)
+    score = np.array([calls[i].score for i in range(n)], dtype=np.float32)
+    nblock = raw[:, 1].astype(np.float64)
+    length = raw[:, 3].astype(np.float64)
+    called = (raw[:, 2] != 0).astype(np.float32)
+    idx = np.arange(n)
+    while len(idx) and len(idx) * 32 + 4 * length[idx].sum() > DUMP_LIMIT_BYTES:
+        keep = int(len(idx) * DUMP_LIMIT_BYTES / (len(idx) * 32 + 4 * length[idx].sum()))
+        idx = np.sort(np.random.default_rng(0).choice(n, size=min(keep, len(idx) - 1), replace=False))
+    code = np.full(256, -1.0, np.float32)
+    code[np.frombuffer(b"ACGT", np.uint8)] = np.arange(4, dtype=np.float32)
+    seqs = b"".join(C.string_at(calls[i].basecall, int(length[i])) for i in idx if called[i])
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (("read_index", idx.astype(np.float64)), ("called", called[idx]), ("score", score[idx]),
+                    ("nblock", nblock[idx]), ("basecall_length", length[idx]), ("bases", code[np.frombuffer(seqs, np.uint8)])):
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def csrc_tree_hash():
@@ -305,9 +338,18 @@ def main():
     ap.add_argument("--reads", type=int, default=10000, help="reads per GPU per step")
     ap.add_argument("--samples", type=int, default=4000)
     ap.add_argument("--model", default="rgrgr_r94")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the host-to-host and HMM-posterior regions")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the records beside the headline: host-to-host, batch64, HMM-posterior and exact-fp32 regions, "
+                         "per-read surface, command line end to end, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip every record but the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the calls of the last step (rank 0's reads) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    extra = args.full and not args.no_extra
+    cpu_base = args.full and not args.no_cpu_baseline
 
     # HIP gives a process 4 hardware queues by default and maps its streams onto them round robin; an engine owns 4
     # streams, torch and RCCL bring their own, and two of the engine's streams on one queue serialise work that is
@@ -379,9 +421,17 @@ def main():
     def enqueue():
         eng.run_device(d_sig, off, ln, run_model[0], params)
 
-    def finish():
-        """collect the OLDEST launch group in flight + the stage timings its events recorded"""
-        nb = eng.collect(n, params, raw=True)
+    def finish(keep=None):
+        """collect the OLDEST launch group in flight + the stage timings its events recorded; with `keep` (a list) the group's
+        calls are appended to it instead of freed (the caller frees them)"""
+        if keep is None:
+            nb = eng.collect(n, params, raw=True)
+        else:
+            calls = (sa._Call * n)()
+            if sa.lib().scrappie_hip_collect(eng._h, C.byref(params), calls, n) != 0:
+                raise RuntimeError("collect: " + sa.last_error())
+            nb = int(np.frombuffer(calls, dtype=np.uint64).reshape(n, C.sizeof(sa._Call) // 8)[:, 3].sum()) if n else 0
+            keep.append(calls)
         return nb, eng.timing()
 
     rank_dt = [None]            # the last timed region's wall time on every rank (a SCALE run should show skew, not just the maximum)
@@ -400,10 +450,11 @@ def main():
             return float(t.item()), float(b.item())
         return dt, float(nb)
 
-    def device_resident_region(steps, acc=None):
+    def device_resident_region(steps, acc=None, keep_last=None):
         """K steps, software pipelined: the engine holds two launch groups, so step k+1's kernels are
         enqueued before the host waits for / stitches step k.  Everything of all K steps (enqueue,
-        kernels, D2H, stitching) happens between the barriers."""
+        kernels, D2H, stitching) happens between the barriers.  keep_last (a list): receives the last
+        step's calls, freed by the caller."""
         nbases = 0
         marks = []
         barrier()
@@ -413,7 +464,7 @@ def main():
         for k in range(steps):
             if k + 1 < steps:
                 enqueue()
-            nb, tm = finish()
+            nb, tm = finish(keep_last if k + 1 == steps else None)
             nbases += nb
             if acc is not None:
                 acc(tm)
@@ -439,14 +490,19 @@ def main():
             stage[key] = stage.get(key, 0.0) + tm[key]
 
     # ---- region 1: the contract's timed region (inputs resident in HBM)
-    dt, nbases = device_resident_region(args.steps, acc)
+    last_calls = [] if args.dump_outputs else None
+    dt, nbases = device_resident_region(args.steps, acc, last_calls)
     value_rank_dt = list(rank_dt[0])
     eng.set_profiling(False)
+    if last_calls:
+        if rank == 0:
+            dump_calls(args.dump_outputs, last_calls[0], n)
+        sa.lib().scrappie_hip_free_calls(last_calls[0], n)
     gru_ms, gru_launches, gru_flops = gru
 
     # ---- region 2: SURVEY 8(d) host -> host: pageable host signals in, base strings out
     h2h = None
-    if not args.no_extra and not events and args.steps > 0:
+    if extra and not events and args.steps > 0:
         L = sa.lib()
         G = max(1, min(args.steps, 40))                          # launch groups (= steps' worth of reads) in the one call: all K steps
         host_sig = np.tile(flat, G)                              # ordinary pageable memory, G x the step's reads
@@ -486,7 +542,7 @@ def main():
     # ---- BASELINE config 2 AS WRITTEN ("batch=64"): the same reads handed over 64 at a time through scrappie_hip_basecall_batch, from one
     # host thread and from 64 (the reference's `#pragma omp parallel for schedule(dynamic)`, scrappie_raw.c:355,387, with a batched body)
     b64 = None
-    if not args.no_extra and not events and args.steps > 0 and world == 1:
+    if extra and not events and args.steps > 0 and world == 1:
         import threading
         L = sa.lib()
         per = 64
@@ -598,7 +654,7 @@ def main():
 
     # ---- region 3: realistic calls through the default kernels (decode driven by HMM-like posteriors)
     hmm = None
-    if not args.no_extra and not events and model.model_dims(weights)["NS"] == 1025 and model.model_dims(weights)["S"] >= 21 and args.steps > 0:
+    if extra and not events and model.model_dims(weights)["NS"] == 1025 and model.model_dims(weights)["S"] >= 21 and args.steps > 0:
         from scrappie_amd import synth
         d_ = model.model_dims(weights)
         nblk = (args.samples + weights["stride"] - 1) // weights["stride"]
@@ -631,7 +687,7 @@ def main():
     # ---- region 4: the same step with the five recurrent layers on the exact-fp32 kernels (v_mfma_f32_16x16x4_f32 throughout:
     # k_affine<.., F32> + k_gru_lanes), the path a layer with |w| >= 255 takes: the like-for-like reading of "fp32 peak"
     f32r = None
-    if not args.no_extra and not events and weights["arch"] in ("rgrgr", "rnnrf") and args.steps > 0:
+    if extra and not events and weights["arch"] in ("rgrgr", "rnnrf") and args.steps > 0:
         eng.debug_option("force_f32_layers", 1)
         eng.load_model("exact_fp32", weights)
         eng.debug_option("force_f32_layers", 0)
@@ -670,7 +726,7 @@ def main():
 
     # ---- the per-read reference surface from many host threads (the reference's own loop body, scrappie_raw.c:265-315): not the metric, a record
     prs = None
-    if not args.no_extra and not events and rank == 0 and world == 1 and weights["arch"] == "rgrgr" and args.model in sa._model_fn_ and args.steps > 0 \
+    if extra and not events and rank == 0 and world == 1 and weights["arch"] == "rgrgr" and args.model in sa._model_fn_ and args.steps > 0 \
             and model.model_dims(weights)["NS"] == 1025:
         from concurrent.futures import ThreadPoolExecutor
         try:
@@ -849,7 +905,7 @@ def main():
     eng.free(d_sig)
     eng.close()
     if rank == 0:
-        if not args.no_extra and not events and world == 1 and weights["arch"] in ("rgrgr", "rnnrf") and args.steps > 0 and args.samples >= 1000:
+        if extra and not events and world == 1 and weights["arch"] in ("rgrgr", "rnnrf") and args.steps > 0 and args.samples >= 1000:
             # the command line end to end, with the GPU to itself (this process's engine is gone)
             # on the one input format the reference reads (fast5), and on headerless float32 files; same reads, so the same sequences
             e5 = cli_end_to_end(weights, args.model, 40 * args.reads, args.samples, "fast5")
@@ -863,7 +919,7 @@ def main():
                     e5["same_sequences_as_f32_input"] = e5["sequences_md5"] == e32["sequences_md5"]
             else:
                 out["cli_end_to_end"], out["cli_end_to_end_fast5"] = e32, e5
-        if not args.no_cpu_baseline and world == 1 and not events:
+        if cpu_base and world == 1 and not events:
             out["cpu_baseline"] = cpu_baseline(weights, base)
         print(json.dumps(out))
     if distributed:

@@ -9,6 +9,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
+if GOLDEN not in sys.path:
+    sys.path.append(GOLDEN)
 
 
 def pytest_configure(config):
@@ -26,3 +28,13 @@ def orc():
     import oracle
     oracle.lib()
     return oracle
+
+
+@pytest.fixture(scope="session")
+def fast5_dir(tmp_path_factory):
+    """tests/golden/fast5 as a directory of whole files: the fixtures above 1 MB are committed in parts (tests/golden/provenance.py)"""
+    import provenance
+    d = tmp_path_factory.mktemp("fast5")
+    for f in provenance.fixture_files("fast5/*.fast5"):
+        (d / os.path.basename(f)).write_bytes(provenance.fixture_bytes(f))
+    return str(d)

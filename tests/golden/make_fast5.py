@@ -6,7 +6,8 @@ storage forms the built-in reader (scrappie_amd/csrc/sh_h5mini.c) supports or mu
     variant_shuf_gzip_c256.fast5   chunks of 256 samples (114 chunks: a two-level chunk B-tree), shuffle + deflate
     variant_latest.fast5           written with --latest (superblock v2, new-style groups): must be REFUSED with a message
 
-Needs the build container (/root/reference and /opt/conda/bin/h5repack); the files are committed."""
+Needs the reference checkout and libhdf5's h5repack (see REPACK); the files are committed, those above 1 MB in parts
+(provenance.split_large)."""
 import glob
 import os
 import shutil
@@ -24,4 +25,6 @@ if __name__ == "__main__":
     subprocess.run([REPACK, "-f", "SHUF", "-f", "GZIP=5", "-l", "CHUNK=256", small, os.path.join(OUT, "variant_shuf_gzip_c256.fast5")], check=True)
     subprocess.run([REPACK, "--latest", small, os.path.join(OUT, "variant_latest.fast5")], check=True)
     import provenance
+    for f in glob.glob(os.path.join(OUT, "*.fast5")):
+        provenance.split_large(f)
     print(provenance.write())

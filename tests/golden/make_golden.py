@@ -184,6 +184,33 @@ def events_fixtures(rf):
     np.savez_compressed(os.path.join(HERE, "ref_events.npz"), **out)
 
 
+def live_fixtures(rd, rp):
+    """tests/test_oracle_golden.py::test_live_against_compiled_reference: the reference's decode_transducer, homopolymer_path and
+    overlapper on the test's own 12 seeded posteriors (ref_live.npz), what the test checks the oracle against where oracle/_ref
+    is not built"""
+    sys.path.insert(0, os.path.dirname(HERE))
+    from test_oracle_golden import live_cases
+    PM = C.POINTER(oracle.Mat)
+    ip = C.POINTER(C.c_int)
+    rd.decode_transducer.restype = C.c_float
+    rd.decode_transducer.argtypes = [PM, C.c_float, C.c_float, C.c_float, ip, C.c_bool]
+    rp.homopolymer_path.restype = C.c_int
+    rp.homopolymer_path.argtypes = [PM, ip, C.c_int]
+    rd.overlapper.restype = C.c_void_p
+    rd.overlapper.argtypes = [ip, C.c_size_t, C.c_int, ip]
+    out = {}
+    for i, (post, stay, skip, local, slip) in enumerate(live_cases()):
+        score, seq = oracle.decode_transducer(post, stay, skip, local, slip, fn=rd.decode_transducer)
+        rc, hseq = oracle.homopolymer_path(post, seq, fn=rp.homopolymer_path)
+        bases, _ = oracle.overlapper(hseq, 1024, fn=rd.overlapper)
+        out["score_%d" % i] = np.float32(score)
+        out["seq_%d" % i] = seq
+        out["hp_seq_%d" % i] = hseq
+        if bases is not None:
+            out["bases_%d" % i] = np.array(bases)
+    np.savez_compressed(os.path.join(HERE, "ref_live.npz"), **out)
+
+
 def bundled_reads():
     """BASELINE config 1: the three fast5 files bundled with the reference
     (reads/*.fast5), re-encoded as int16 DAC counts + (offset, range,
@@ -222,6 +249,7 @@ def main():
     math_fixtures(rp)
     signal_fixtures(rp)
     decode_fixtures(rd, rp)
+    live_fixtures(rd, rp)
     rf = oracle.ref_features()
     assert rf is not None, "oracle/_ref/libref_features.so not built"
     events_fixtures(rf)

@@ -27,6 +27,7 @@ SOURCES = {
     "ref_math.npz": PURE,
     "ref_signal_prep.npz": PURE + ["src/test/raw_signal.crp"],
     "ref_decode.npz": DECODE + ["src/homopolymer.c", "src/scrappie_seq_helpers.c"],
+    "ref_live.npz": DECODE + ["src/homopolymer.c", "src/scrappie_seq_helpers.c"],
     "ref_events.npz": ["src/nnfeatures.c", "src/nnfeatures.h", "src/util.h", "src/sse_mathfun.h", "src/scrappie_structures.h"],
     "reads/*.i16": ["reads/*.fast5"],
     "fast5/*.fast5": ["reads/*.fast5"],
@@ -34,18 +35,49 @@ SOURCES = {
 }
 
 
+# a fixture larger than this is committed as <name>.part0, <name>.part1, ... (no committed file exceeds 1 MiB); the tests read
+# it through fixture_bytes() / fixture_files() and see the whole file
+PART_BYTES = 1000000
+
+
+def _parts(path):
+    return sorted(glob.glob(glob.escape(path) + ".part*"), key=lambda f: int(f.rsplit(".part", 1)[1]))
+
+
+def fixture_bytes(path):
+    """the bytes of fixture `path`, joined from its parts where it is committed in parts"""
+    if os.path.exists(path):
+        return open(path, "rb").read()
+    parts = _parts(path)
+    assert parts, path
+    return b"".join(open(f, "rb").read() for f in parts)
+
+
+def fixture_files(pattern):
+    """the fixtures whose path matches `pattern` (absolute, or relative to tests/golden), those committed in parts included"""
+    pattern = os.path.join(HERE, pattern)
+    return sorted(set(glob.glob(pattern)) | {f.rsplit(".part", 1)[0] for f in glob.glob(pattern + ".part*")})
+
+
+def split_large(path):
+    """commit form of a generated fixture: above PART_BYTES, the file is replaced by its parts"""
+    data = open(path, "rb").read()
+    for f in _parts(path):
+        os.unlink(f)
+    if len(data) > PART_BYTES:
+        for k in range(0, len(data), PART_BYTES):
+            open("%s.part%d" % (path, k // PART_BYTES), "wb").write(data[k:k + PART_BYTES])
+        os.unlink(path)
+
+
 def sha(path):
-    h = hashlib.sha256()
-    with open(path, "rb") as fh:
-        for chunk in iter(lambda: fh.read(1 << 20), b""):
-            h.update(chunk)
-    return h.hexdigest()
+    return hashlib.sha256(fixture_bytes(path)).hexdigest()
 
 
 def collect():
     out = {}
     for pat, srcs in sorted(SOURCES.items()):
-        files = sorted(glob.glob(os.path.join(HERE, pat)))
+        files = fixture_files(pat)
         assert files, pat
         ref = {}
         for s in srcs:

@@ -56,10 +56,11 @@ def test_i16_fixtures_match_survey_probe():
     assert sorted(m["n"] for m in META.values()) == [29150, 64395, 81106]
 
 
-def test_fast5_reader_equals_fixture():
-    files = sorted(glob.glob("/root/reference/reads/*.fast5"))
-    if not files or not _reader().scrappie_hip_have_hdf5():
-        pytest.skip("needs the reference's bundled fast5 files and an HDF5 library (build container only)")
+def test_fast5_reader_equals_fixture(fast5_dir):
+    """read_raw() through libhdf5 on the reference's three bundled reads (tests/golden/fast5: byte-for-byte copies) equals the .i16 fixtures"""
+    if not _reader().scrappie_hip_have_hdf5():
+        pytest.skip("no HDF5 library on this box")
+    files = [os.path.join(fast5_dir, name + ".fast5") for name in sorted(META)]
     for f in files:
         name = os.path.basename(f)[:-6]
         a, uuid = _read(f)
@@ -68,15 +69,12 @@ def test_fast5_reader_equals_fixture():
         assert uuid.decode() == META[name]["uuid"]
 
 
-FAST5 = os.path.join(ROOT, "tests", "golden", "fast5")
-
-
 @pytest.fixture
 def own_reader(monkeypatch):
     monkeypatch.setenv("SCRAPPIE_FAST5_READER", "own")          # read by the library at every call
 
 
-def test_builtin_fast5_reader_equals_fixture(own_reader):
+def test_builtin_fast5_reader_equals_fixture(own_reader, fast5_dir):
     """the reader of the HDF5 subset fast5 files use (csrc/sh_h5mini.c: no libhdf5) on the reference's three bundled reads
     (contiguous Signal; chunked + deflate Signal) and on a re-encoding with 114 shuffled + deflated chunks (two-level chunk
     B-tree): samples in pA bit-equal to read_raw()'s (fast5_interface.c:130-217), read_id, offset / range / digitisation"""
@@ -88,23 +86,23 @@ def test_builtin_fast5_reader_equals_fixture(own_reader):
         hdr = np.fromfile(os.path.join(READS, name + ".i16"), dtype="<f4", count=3)
         variants = [name + ".fast5"] + (["variant_shuf_gzip_c256.fast5"] if name == "read_ch228_file118" else [])
         for v in variants:
-            a, uuid = _read(os.path.join(FAST5, v))
+            a, uuid = _read(os.path.join(fast5_dir, v))
             assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), v
             assert uuid.decode() == m["uuid"]
             sc = (C.c_float * 3)()
-            assert _reader().scrappie_hip_fast5_scaling(os.fsencode(os.path.join(FAST5, v)), sc) == 0
+            assert _reader().scrappie_hip_fast5_scaling(os.fsencode(os.path.join(fast5_dir, v)), sc) == 0
             assert np.array_equal(np.array(sc, dtype=np.float32), hdr)
-            counts, _ = _read(os.path.join(FAST5, v), scale=False)        # DAC counts, as read_raw(..., false) gives them
+            counts, _ = _read(os.path.join(fast5_dir, v), scale=False)        # DAC counts, as read_raw(..., false) gives them
             assert np.array_equal(counts, np.round(counts)) and np.array_equal((counts + hdr[0]) * (hdr[1] / hdr[2]), b)
     # the deflate-compressed chunks (MinKNOW's level 1, chunks of 20 000 samples; 114 shuffled chunks) went through the built-in inflater
     # (sh_inflate.c): zlib, its safety net, was not consulted once
     assert fallbacks() == before
 
 
-def test_builtin_fast5_reader_equals_libhdf5(monkeypatch):
+def test_builtin_fast5_reader_equals_libhdf5(monkeypatch, fast5_dir):
     if not _reader().scrappie_hip_have_hdf5():
         pytest.skip("no HDF5 library on this box")
-    for f in sorted(glob.glob(os.path.join(FAST5, "*.fast5"))):
+    for f in sorted(glob.glob(os.path.join(fast5_dir, "*.fast5"))):
         if "latest" in f:
             continue
         monkeypatch.setenv("SCRAPPIE_FAST5_READER", "hdf5")
@@ -114,7 +112,7 @@ def test_builtin_fast5_reader_equals_libhdf5(monkeypatch):
         assert np.array_equal(a.view(np.uint32), b.view(np.uint32)) and ua == ub
 
 
-def test_builtin_fast5_reader_under_address_sanitizer(tmp_path):
+def test_builtin_fast5_reader_under_address_sanitizer(tmp_path, fast5_dir):
     """sh_h5mini.c + sh_inflate.c parse untrusted files.  150 damaged copies (1-4 overwritten bytes, every other time inside the first 4 KiB of structure; one in
     five truncated) of each bundled fast5 through the reader built with -fsanitize=address,undefined: no report; the intact files still read."""
     import shutil
@@ -129,7 +127,7 @@ def test_builtin_fast5_reader_under_address_sanitizer(tmp_path):
         pytest.skip("no AddressSanitizer runtime in this toolchain")
     assert b.returncode == 0, b.stderr[-2000:]
     rng = np.random.default_rng(11)
-    srcs = [f for f in sorted(glob.glob(os.path.join(FAST5, "*.fast5"))) if "latest" not in f]
+    srcs = [f for f in sorted(glob.glob(os.path.join(fast5_dir, "*.fast5"))) if "latest" not in f]
     files = []
     for s in srcs:
         good = open(s, "rb").read()
@@ -148,14 +146,14 @@ def test_builtin_fast5_reader_under_address_sanitizer(tmp_path):
     assert n == len(srcs) + len(files) and ok >= len(srcs)
 
 
-def test_builtin_fast5_reader_refuses_what_it_does_not_parse(own_reader, tmp_path, capfd):
+def test_builtin_fast5_reader_refuses_what_it_does_not_parse(own_reader, tmp_path, capfd, fast5_dir):
     """a file written with the newer format (superblock v2, new-style groups) is refused with a message, never misread; a
     truncated or damaged file gives no read (and no crash)"""
-    rt = _reader().scrappie_hip_read_raw(os.fsencode(os.path.join(FAST5, "variant_latest.fast5")), True)
+    rt = _reader().scrappie_hip_read_raw(os.fsencode(os.path.join(fast5_dir, "variant_latest.fast5")), True)
     assert not rt.raw and rt.n == 0
     assert "needs libhdf5" in capfd.readouterr().err
-    good = open(os.path.join(FAST5, "variant_shuf_gzip_c256.fast5"), "rb").read()
-    want, _ = _read(os.path.join(FAST5, "variant_shuf_gzip_c256.fast5"))
+    good = open(os.path.join(fast5_dir, "variant_shuf_gzip_c256.fast5"), "rb").read()
+    want, _ = _read(os.path.join(fast5_dir, "variant_shuf_gzip_c256.fast5"))
     rng = np.random.default_rng(5)
     f = str(tmp_path / "damaged.fast5")
     n_ok = 0
@@ -191,7 +189,7 @@ def test_cli_plumbing_without_gpu(cli):
 
 
 @pytest.mark.gpu
-def test_config1_from_the_fast5_files_themselves(cli, tmp_path):
+def test_config1_from_the_fast5_files_themselves(cli, tmp_path, fast5_dir):
     """BASELINE config 1 on the reference's bundled fast5 files as they are (no libhdf5 needed: built-in reader), against the
     run on their .i16 re-encodings that test_config1_bundled_reads_vs_oracle checks against the oracle: identical calls,
     scores and trims; --uuid names the records by read_id (scrappie_raw.c:285-300)"""
@@ -200,7 +198,7 @@ def test_config1_from_the_fast5_files_themselves(cli, tmp_path):
     model.save_model(w, mfile)
     base = [cli, "raw", "--model", "rgrgr_r94", "--model-file", mfile, "--local", "150"]
     env = dict(os.environ, SCRAPPIE_FAST5_READER="own")
-    files = [os.path.join(FAST5, n + ".fast5") for n in META]
+    files = [os.path.join(fast5_dir, n + ".fast5") for n in META]
     a = subprocess.run(base + ["--uuid"] + files, capture_output=True, text=True, env=env)
     b = subprocess.run(base + [os.path.join(READS, n + ".i16") for n in META], capture_output=True, text=True, env=env)
     assert a.returncode == 0 and b.returncode == 0, a.stderr + b.stderr
@@ -214,7 +212,7 @@ def test_config1_from_the_fast5_files_themselves(cli, tmp_path):
         assert ga[3:] == gb[3:]                              # score, nblock, length, blocks per base, nsample, trim
         assert ga[0] == m["uuid"] and ga[2] == m["uuid"]
     # a directory argument means dir/*.fast5: the five files there, one of which the built-in reader refuses
-    d = subprocess.run(base + [FAST5], capture_output=True, text=True, env=env)
+    d = subprocess.run(base + [fast5_dir], capture_output=True, text=True, env=env)
     assert d.returncode == 0 and d.stdout.count(">") == 4 and "needs libhdf5" in d.stderr
 
 
@@ -383,7 +381,7 @@ def test_bench_two_ranks_on_one_gpu():
     env = dict(os.environ, BENCH_BACKEND="gloo", BENCH_DEVICE="0", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29533", os.path.join(root, "bench.py"),
-           "--gpus", "2", "--steps", "1", "--warmup", "1", "--reads", "400", "--samples", "2000", "--no-cpu-baseline"]
+           "--gpus", "2", "--steps", "1", "--warmup", "1", "--reads", "400", "--samples", "2000", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -317,18 +317,8 @@ def test_reference_path_fixture_loads(golden):
 
 
 # ---------------------------------------------------------------- live vs _ref
-def test_live_against_compiled_reference(orc):
-    rd, rp = orc.ref_decode(), orc.ref_pure()
-    if rd is None or rp is None:
-        pytest.skip("oracle/_ref not built (no /root/reference on this box)")
-    PM = C.POINTER(orc.Mat)
-    ip = C.POINTER(C.c_int)
-    rd.decode_transducer.restype = C.c_float
-    rd.decode_transducer.argtypes = [PM, C.c_float, C.c_float, C.c_float, ip, C.c_bool]
-    rp.homopolymer_path.restype = C.c_int
-    rp.homopolymer_path.argtypes = [PM, ip, C.c_int]
-    rd.overlapper.restype = C.c_void_p
-    rd.overlapper.argtypes = [ip, C.c_size_t, C.c_int, ip]
+def live_cases():
+    """(posterior, stay, skip, local penalty, slip) of the live comparison; tests/golden/make_golden.py records the reference's results on them"""
     rng = np.random.RandomState(0)
     for i in range(12):
         T = int(rng.randint(3, 260))
@@ -337,13 +327,37 @@ def test_live_against_compiled_reference(orc):
         post, _ = synth.simulated_posterior(T, 1000 + i, plant_homopolymers=3)
         if i % 3 == 0:      # heavy floor -> many exactly-tied scores (tie-break order, quirk Q7)
             post = np.maximum(post, np.float32(np.log(np.float32(1e-5) * 4))).astype(np.float32)
-        a = orc.decode_transducer(post, pens[0], pens[1], max(pens[2], 0.5), slip)
-        b = orc.decode_transducer(post, pens[0], pens[1], max(pens[2], 0.5), slip, fn=rd.decode_transducer)
-        assert a[0] == b[0] and np.array_equal(a[1], b[1])
+        yield post, pens[0], pens[1], max(pens[2], 0.5), slip
+
+
+def test_live_against_compiled_reference(orc, golden):
+    """decode_transducer, homopolymer_path and overlapper of the oracle against the reference's own on 12 seeded posteriors: against
+    the reference's results recorded in tests/golden/ref_live.npz always, and live against oracle/_ref where it is built."""
+    g = golden["ref_live"]
+    rd, rp = orc.ref_decode(), orc.ref_pure()
+    if rd is not None and rp is not None:
+        PM = C.POINTER(orc.Mat)
+        ip = C.POINTER(C.c_int)
+        rd.decode_transducer.restype = C.c_float
+        rd.decode_transducer.argtypes = [PM, C.c_float, C.c_float, C.c_float, ip, C.c_bool]
+        rp.homopolymer_path.restype = C.c_int
+        rp.homopolymer_path.argtypes = [PM, ip, C.c_int]
+        rd.overlapper.restype = C.c_void_p
+        rd.overlapper.argtypes = [ip, C.c_size_t, C.c_int, ip]
+    for i, (post, stay, skip, local, slip) in enumerate(live_cases()):
+        a = orc.decode_transducer(post, stay, skip, local, slip)
         ha = orc.homopolymer_path(post, a[1])
+        bases = orc.overlapper(ha[1], 1024)[0]
+        assert np.float32(a[0]) == g["score_%d" % i] and np.array_equal(a[1], g["seq_%d" % i]), i
+        assert np.array_equal(ha[1], g["hp_seq_%d" % i]), i
+        assert bases == (str(g["bases_%d" % i]) if "bases_%d" % i in g.files else None), i
+        if rd is None or rp is None:
+            continue
+        b = orc.decode_transducer(post, stay, skip, local, slip, fn=rd.decode_transducer)
+        assert a[0] == b[0] and np.array_equal(a[1], b[1])
         hb = orc.homopolymer_path(post, a[1], fn=rp.homopolymer_path)
         assert np.array_equal(ha[1], hb[1])
-        assert orc.overlapper(ha[1], 1024)[0] == orc.overlapper(ha[1], 1024, fn=rd.overlapper)[0]
+        assert bases == orc.overlapper(ha[1], 1024, fn=rd.overlapper)[0]
 
 
 # ---------------------------------------------------------------------------
@@ -413,19 +427,19 @@ def test_fixture_provenance():
     file it was derived from.  Keeps "pinned by the reference's own code / data" a checkable statement."""
     import hashlib
     import json
+    from provenance import fixture_bytes, fixture_files       # (fixtures above 1 MB are committed in parts: hashed as the whole file)
     here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
     rec = json.load(open(os.path.join(here, "PROVENANCE.json")))
 
     def sha(path):
-        return hashlib.sha256(open(path, "rb").read()).hexdigest()
+        return hashlib.sha256(fixture_bytes(path)).hexdigest()
     seen = set()
     for pat, d in rec.items():
         assert d["fixtures"] and d["reference_files"], pat
         for f, h in d["fixtures"].items():
             assert sha(os.path.join(here, f)) == h, "fixture %s is not the one PROVENANCE.json records: regenerate both" % f
             seen.add(f)
-    import glob
-    have = {os.path.relpath(f, here) for f in glob.glob(os.path.join(here, "*.npz")) + glob.glob(os.path.join(here, "reads", "*.i16")) + glob.glob(os.path.join(here, "fast5", "*.fast5"))}
+    have = {os.path.relpath(f, here) for f in fixture_files("*.npz") + fixture_files("reads/*.i16") + fixture_files("fast5/*.fast5")}
     assert have <= seen, "fixtures without a provenance record: %s" % sorted(have - seen)
     ref = "/root/reference"
     if os.path.isdir(os.path.join(ref, "src")):

@@ -177,3 +177,34 @@ def test_committed_bench_line_keeps_the_contract():
     assert d["cli_end_to_end"]["input"] == "fast5" and d["cli_end_to_end"]["same_sequences_as_f32_input"] is True
     assert "openmp" in d["batch64"] and d["ms_per_step_per_rank"]["max"] >= d["ms_per_step_per_rank"]["min"] > 0
 
+
+
+def test_bench_dump_outputs_format(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the calls of a launch group as float32 / float64 .npy files (bases coded A C G T = 0 1 2 3, read by read
+    after basecall_length), and above the size limit a fixed seeded sample of the reads with their indices"""
+    import ctypes as C
+    import bench
+    import scrappie_amd as sa
+    seqs = [b"ACGT", None, b"TTGA", b"CAT", b"G"]
+    calls = (sa._Call * len(seqs))()
+    keep = []
+    for i, s in enumerate(seqs):
+        calls[i].score, calls[i].nblock = -1.5 * i, 10 + i
+        if s is not None:
+            keep.append(C.create_string_buffer(s))
+            calls[i].basecall, calls[i].basecall_length = C.cast(keep[-1], C.c_void_p), len(s)
+    bench.dump_calls(str(tmp_path / "all"), calls, len(seqs))
+    d = {f[:-4]: np.load(str(tmp_path / "all" / f)) for f in os.listdir(str(tmp_path / "all"))}
+    assert sorted(d) == ["basecall_length", "bases", "called", "nblock", "read_index", "score"]
+    assert all(a.dtype in (np.float32, np.float64) for a in d.values())
+    assert list(d["read_index"]) == [0, 1, 2, 3, 4] and list(d["called"]) == [1, 0, 1, 1, 1] and list(d["nblock"]) == [10, 11, 12, 13, 14]
+    assert np.array_equal(d["score"], np.float32([0, -1.5, -3, -4.5, -6])) and list(d["basecall_length"]) == [4, 0, 4, 3, 1]
+    assert list(d["bases"]) == [0, 1, 2, 3, 3, 3, 2, 0, 1, 0, 3, 2]
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 100)
+    for k in range(2):
+        bench.dump_calls(str(tmp_path / ("part%d" % k)), calls, len(seqs))
+    a = {f[:-4]: np.load(str(tmp_path / "part0" / f)) for f in os.listdir(str(tmp_path / "part0"))}
+    b = {f[:-4]: np.load(str(tmp_path / "part1" / f)) for f in os.listdir(str(tmp_path / "part1"))}
+    assert 0 < len(a["read_index"]) < len(seqs) and sum(x.nbytes for x in a.values()) <= 100
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert np.array_equal(a["nblock"], 10 + a["read_index"])
