@@ -151,6 +151,25 @@ scrappie_matrix make_scrappie_matrix(size_t nr, size_t nc);
 scrappie_matrix mat_from_array(const float *x, size_t nr, size_t nc);
 scrappie_matrix free_scrappie_matrix(scrappie_matrix mat);
 
+/* Block-based mapping of a transducer log-posterior to a sequence (src/decode.c:1420, :1547, :1638, :1706, :1844;
+ * python/pyscrap.h:41-58).  Same signatures and NULL/NAN conventions; the DP runs on the process-default engine (one
+ * launch per call: calls from several threads serialise on the engine).  Viterbi scores and paths are bit-identical to
+ * the reference's; forward agrees to float rounding.  Where the reference is undefined (seqlen == 0, a seq
+ * code outside [0, nr - 1), a banded call with seqlen < 3, a posterior of no blocks, seqlen above 65536) these return NAN
+ * and set scrappie_hip_last_error().  path: nblock int32 positions, -1 in START / END (decode.c:1519-1523). */
+bool are_bounds_sane(size_t const *low, size_t const *high, size_t nblock, size_t seqlen);
+float map_to_sequence_forward(const_scrappie_matrix logpost, float stay_pen, float skip_pen, float local_pen,
+                              int const *seq, size_t seqlen);
+float map_to_sequence_forward_banded(const_scrappie_matrix logpost, float stay_pen, float skip_pen, float local_pen,
+                                     int const *seq, size_t seqlen, size_t const *poslow, size_t const *poshigh);
+float map_to_sequence_viterbi(const_scrappie_matrix logpost, float stay_pen, float skip_pen, float local_pen,
+                              int const *seq, size_t seqlen, int *path);
+float map_to_sequence_viterbi_banded(const_scrappie_matrix logpost, float stay_pen, float skip_pen, float local_pen,
+                                     int const *seq, size_t seqlen, size_t const *poslow, size_t const *poshigh);
+/* src/scrappie_seq_helpers.c:53 (python/pyscrap.h:61): n - state_len + 1 codes, calloc'd; NULL on a base outside
+ * ACGT/acgt and (the reference is undefined there) when n < state_len */
+int *encode_bases_to_integers(char const *seq, size_t n, size_t state_len);
+
 /* ------------------------------------------------------------------------
  * (2) Batched engine surface (additive)
  * ---------------------------------------------------------------------- */
@@ -366,6 +385,27 @@ int scrappie_hip_collect(scrappie_hip_engine *e, const scrappie_hip_params *p,
                          scrappie_hip_call *out, size_t n);
 
 void scrappie_hip_free_calls(scrappie_hip_call *calls, size_t n);
+
+/* Block-based mapping, batched (sh_eng_map.inc): the network and S1 of a transducer model (not a CRF model) run as
+ * for scrappie_hip_posterior, the posterior stays on the device, k_map maps every read to its target and only scores
+ * and paths return.  reads[i] is mapped to targets[i]; out[i] belongs to reads[i].  seq holds state codes (as
+ * encode_bases_to_integers makes them with the model's k-mer length); poslow / poshigh NULL: unbanded, else one entry
+ * per block of the read (scrappie_hip_read_blocks).  Parameters: min_prob, tempW, tempb, stay_pen, skip_pen, local_pen
+ * of p.  viterbi 0: forward scores.  want_path: the Viterbi path of every unbanded read (malloc'd nblock int32, -1 in
+ * START / END); banded reads and forward scores have none.  A read that cannot be mapped (too short, out of the
+ * operand range, a bad sequence or band, longer than the limits of DESIGN.md) gets score NAN and path NULL; the others
+ * are untouched.  Returns 0, or -1 with scrappie_hip_last_error() when the call as a whole fails.  Takes the engine's
+ * call lock, as scrappie_hip_basecall_batch does: calls on one engine run one at a time. */
+typedef struct { const int *seq; size_t seqlen; const size_t *poslow, *poshigh; } scrappie_hip_map_target;
+typedef struct { float score; size_t nblock; int32_t *path; } scrappie_hip_map_result;
+int scrappie_hip_read_blocks(scrappie_hip_engine *e, int model, size_t nsample);   /* posterior columns of a read of nsample samples (0: below the minimum) */
+int scrappie_hip_model_states(scrappie_hip_engine *e, int model);                  /* posterior rows (4^k + 1 for a transducer), -1: no such model */
+int scrappie_hip_map_batch(scrappie_hip_engine *e, int model, const raw_table *reads, const scrappie_hip_map_target *targets,
+                           size_t n, const scrappie_hip_params *p, int viterbi, int want_path, scrappie_hip_map_result *out);
+void scrappie_hip_free_map_results(scrappie_hip_map_result *r, size_t n);
+/* the last scrappie_hip_map_batch call's time, milliseconds summed over its launch groups: [0] network + S1, [1] k_map,
+ * [2] k_map_walk + results to the host (host clock, the stream drained between the stages) */
+void scrappie_hip_map_timing(scrappie_hip_engine *e, double out[3]);
 
 /* Measurement / test hook for SURVEY.md 8(d) "decode driven by HMM-simulated posteriors" (synthetic
  * weights decode to a handful of bases per read, which leaves the decode -> D2H -> homopolymer ->

@@ -52,6 +52,15 @@ class _Call(C.Structure):
                 ("basecall_length", C.c_size_t), ("pos", C.POINTER(C.c_int))]
 
 
+class _MapTarget(C.Structure):
+    _fields_ = [("seq", C.POINTER(C.c_int)), ("seqlen", C.c_size_t), ("poslow", C.POINTER(C.c_size_t)),
+                ("poshigh", C.POINTER(C.c_size_t))]
+
+
+class _MapResult(C.Structure):
+    _fields_ = [("score", C.c_float), ("nblock", C.c_size_t), ("path", C.POINTER(C.c_int32))]
+
+
 class Timing(C.Structure):
     _fields_ = [("conv_ms", C.c_float), ("affine_ms", C.c_float), ("gru_ms", C.c_float),
                 ("ff_ms", C.c_float), ("decode_ms", C.c_float), ("backtrace_ms", C.c_float),
@@ -201,6 +210,24 @@ def lib():
     L.scrappie_hip_prep_timing.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double)]
     L.get_raw_model_stride_from_string.argtypes = [C.c_char_p]
     L.get_raw_model.argtypes = [C.c_char_p]
+    sp = C.POINTER(C.c_size_t)
+    L.are_bounds_sane.restype = C.c_bool
+    L.are_bounds_sane.argtypes = [sp, sp, C.c_size_t, C.c_size_t]
+    L.map_to_sequence_viterbi.restype = C.c_float
+    L.map_to_sequence_viterbi.argtypes = [PM, C.c_float, C.c_float, C.c_float, ip, C.c_size_t, ip]
+    L.map_to_sequence_forward.restype = C.c_float
+    L.map_to_sequence_forward.argtypes = [PM, C.c_float, C.c_float, C.c_float, ip, C.c_size_t]
+    for nm in ("map_to_sequence_viterbi_banded", "map_to_sequence_forward_banded"):
+        getattr(L, nm).restype = C.c_float
+        getattr(L, nm).argtypes = [PM, C.c_float, C.c_float, C.c_float, ip, C.c_size_t, sp, sp]
+    L.encode_bases_to_integers.restype = C.c_void_p
+    L.encode_bases_to_integers.argtypes = [C.c_char_p, C.c_size_t, C.c_size_t]
+    L.scrappie_hip_read_blocks.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
+    L.scrappie_hip_model_states.argtypes = [C.c_void_p, C.c_int]
+    L.scrappie_hip_map_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(_RawTable), C.POINTER(_MapTarget), C.c_size_t,
+                                         C.POINTER(Params), C.c_int, C.c_int, C.POINTER(_MapResult)]
+    L.scrappie_hip_free_map_results.argtypes = [C.POINTER(_MapResult), C.c_size_t]
+    L.scrappie_hip_map_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     _lib = L
     return L
 
@@ -429,6 +456,85 @@ def basecall_raw(data, model='rgrgr_r94', with_base_probs=False, **kwargs):
 # ---------------------------------------------------------------------------
 # batched engine (additive; the fast path)
 # ---------------------------------------------------------------------------
+def _gsp():
+    """python/scrappy/__init__.py:25-44: alphabet size and k-mer length from a transducer's state count"""
+    import itertools
+    pairs = [(a, k) for a, k in itertools.product(range(4, 8), range(1, 10))]
+    lookup = {a ** k: (a, k) for a, k in pairs}
+    assert len(lookup) == len(pairs)
+
+    def guess_state_properties(nstate):
+        return lookup[nstate - 1]
+    return guess_state_properties
+
+
+guess_state_properties = _gsp()
+
+
+def encode_bases(sequence, kmer_len):
+    """encode_bases_to_integers: the state codes of `sequence`'s k-mers as an int32 array (ValueError on a base outside ACGT)."""
+    b = sequence.encode()
+    n = len(b) - kmer_len + 1
+    ptr = lib().encode_bases_to_integers(b, len(b), kmer_len)
+    if not ptr:
+        raise ValueError("cannot encode sequence: " + last_error())
+    out = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_int)), shape=(n,)).copy()
+    _libc.free(ptr)
+    return out
+
+
+def diagonal_bands(bands, nblock, seq_len):
+    """python/scrappy/__init__.py:550-558: the (low, high) uintp arrays of a diagonal band of half-width `bands` * seq_len / nblock."""
+    gradient = seq_len / nblock
+    bands = 2 * bands * gradient
+    hband = bands / 2
+    return [np.ascontiguousarray(np.array(x, dtype=np.uintp)) for x in (
+        [(max(0, x * gradient - hband)) for x in range(nblock)],
+        [(min(seq_len, x * gradient + hband)) for x in range(nblock)])]
+
+
+def map_post_to_sequence(post, sequence, stay_pen=0, skip_pen=0, local_pen=4.0, viterbi=False, path=False, bands=None):
+    """python/scrappy/__init__.py:492-578: block-based local-global alignment of a posterior (a `ScrappyMatrix` of
+    log-probabilities, as from `calc_post`) to a base sequence, Viterbi or forward, full or banded; the DP runs on the
+    GPU.  `bands`: None, an int (diagonal band) or a (low, high) pair.  Returns (score, path or None)."""
+    if path and not viterbi:
+        raise ValueError('Cannot calulate path with `viterbi==False`.')
+    if not isinstance(post, ScrappyMatrix):
+        raise TypeError('`post` should be a ScrappyMatrix.')
+    nblock, nstate = post.shape
+    alpha_len, kmer_len = guess_state_properties(nstate)
+    seq_len = len(sequence) - kmer_len + 1
+    ptr = lib().encode_bases_to_integers(sequence.encode(), len(sequence), kmer_len)
+    if not ptr:
+        raise RuntimeError('An unknown error occurred whilst encoding sequence.')
+    try:
+        p_seq = C.cast(ptr, C.POINTER(C.c_int))
+        path_data = np.zeros(nblock, dtype=np.int32) if (viterbi and path) else None
+        p_path = path_data.ctypes.data_as(C.POINTER(C.c_int)) if path_data is not None else None
+        if bands is None:
+            if viterbi:
+                score = lib().map_to_sequence_viterbi(post.data(), stay_pen, skip_pen, local_pen, p_seq, seq_len, p_path)
+            else:
+                score = lib().map_to_sequence_forward(post.data(), stay_pen, skip_pen, local_pen, p_seq, seq_len)
+        else:
+            if isinstance(bands, int):
+                bands = diagonal_bands(bands, nblock, seq_len)
+            elif len(bands) == 2:
+                bands = [np.ascontiguousarray(x, dtype=np.uintp) for x in bands]
+            else:
+                raise ValueError('`bands` should be `None`, an integer, or length 2.')
+            p_lo, p_hi = (x.ctypes.data_as(C.POINTER(C.c_size_t)) for x in bands)
+            if not lib().are_bounds_sane(p_lo, p_hi, nblock, seq_len):
+                raise ValueError('Supplied banding structure is not valid.')
+            func = lib().map_to_sequence_viterbi_banded if viterbi else lib().map_to_sequence_forward_banded
+            score = func(post.data(), stay_pen, skip_pen, local_pen, p_seq, seq_len, p_lo, p_hi)
+    finally:
+        _libc.free(ptr)
+    if np.isnan(score):
+        raise RuntimeError('An unknown error occurred during alignment: ' + last_error())
+    return score, path_data
+
+
 def plan_tail(lengths, stride, max_long_blocks=0):
     """scrappie_hip_plan_tail (host only): boolean array, True for the chain-bound reads a call runs beside the others"""
     ln = np.ascontiguousarray(lengths, dtype=np.uint32)
@@ -806,6 +912,65 @@ class Engine(object):
         if not m:
             raise RuntimeError("posterior: " + last_error())
         return ScrappyMatrix(m).data(as_numpy=True, sloika=False)
+
+    def read_blocks(self, model, nsample):
+        """posterior columns (blocks) of a read of `nsample` samples; 0 below the model's minimum"""
+        return lib().scrappie_hip_read_blocks(self._h, self._models[model], nsample)
+
+    def map_to_sequence(self, signals, sequences, model='rgrgr_r94', viterbi=True, path=False, bands=None, stay_pen=0.0,
+                        skip_pen=0.0, local_pen=4.0, min_prob=1e-5, tempW=1.0, tempb=1.0):
+        """Block-based mapping of each read (trimmed, normalised float32 signal) to its base sequence, batched: the
+        network and S1 run as for `posterior`, the posterior stays on the device, only scores and paths return
+        (scrappie_hip_map_batch).  `bands`: None, an int (scrappy's diagonal band, per read) or a list with a
+        (low, high) pair or None per read.  Returns [(score, path or None)] in input order; score NaN where a read
+        cannot be mapped (too short, a bad sequence or band)."""
+        n = len(signals)
+        if len(sequences) != n:
+            raise ValueError("one sequence per signal")
+        if path and not viterbi:
+            raise ValueError('Cannot calulate path with `viterbi==False`.')
+        h = self._models[model]
+        kmer_len = guess_state_properties(lib().scrappie_hip_model_states(self._h, h))[1]
+        keep = []
+        rts = (_RawTable * n)()
+        tgs = (_MapTarget * n)()
+        for i, (x, sq) in enumerate(zip(signals, sequences)):
+            x = np.ascontiguousarray(x, dtype=ftype)
+            try:
+                codes = encode_bases(sq, kmer_len)
+            except ValueError:
+                codes = np.zeros(0, dtype=np.int32)      # mapped to NaN by the library (empty sequence)
+            keep += [x, codes]
+            rts[i] = _RawTable(None, len(x), 0, len(x), x.ctypes.data_as(C.POINTER(C.c_float)))
+            tgs[i].seq = codes.ctypes.data_as(C.POINTER(C.c_int))
+            tgs[i].seqlen = len(codes)
+            b = bands if (bands is None or isinstance(bands, int)) else bands[i]
+            if isinstance(b, int):
+                nblock = self.read_blocks(model, len(x))
+                b = diagonal_bands(b, nblock, len(codes)) if nblock > 0 and len(codes) > 0 else None
+            if b is not None:
+                lo, hi = (np.ascontiguousarray(v, dtype=np.uintp) for v in b)
+                keep += [lo, hi]
+                tgs[i].poslow = lo.ctypes.data_as(C.POINTER(C.c_size_t))
+                tgs[i].poshigh = hi.ctypes.data_as(C.POINTER(C.c_size_t))
+        p = self.default_params(min_prob=min_prob, tempW=tempW, tempb=tempb, stay_pen=stay_pen, skip_pen=skip_pen,
+                                local_pen=local_pen)
+        out = (_MapResult * n)()
+        if lib().scrappie_hip_map_batch(self._h, h, rts, tgs, n, C.byref(p), 1 if viterbi else 0, 1 if path else 0, out) != 0:
+            raise RuntimeError("map_batch: " + last_error())
+        res = []
+        for i in range(n):
+            r = out[i]
+            pth = np.ctypeslib.as_array(r.path, shape=(r.nblock,)).copy() if r.path else None
+            res.append((float(r.score), pth))
+        lib().scrappie_hip_free_map_results(out, n)
+        return res
+
+    def map_timing(self):
+        """the last map_to_sequence call's time (ms, summed over launch groups): network + S1, k_map, walk + results"""
+        t = (C.c_double * 3)()
+        lib().scrappie_hip_map_timing(self._h, t)
+        return dict(network_ms=t[0], map_ms=t[1], walk_ms=t[2])
 
     def trunk(self, signal, model='rgrgr_r94', upto=5):
         rt = RawTable(signal)

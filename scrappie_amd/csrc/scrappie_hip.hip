@@ -34,6 +34,7 @@
  *   sh_eng_batch.inc     helper engine for chain-bound reads, host-signal entry points, several GPUs
  *   sh_eng_debug.inc     measurement / test hooks
  *   sh_eng_surface.inc   the reference's per-read functions
+ *   sh_eng_map.inc       block-based mapping of posteriors to sequences (per-read and batched)
  * Separate translation units: sh_p0.hip (signal preparation, k_p0), sh_host.c / sh_fast5.c / sh_h5mini.c (host C);
  * sh_coalesce.h (the per-read functions' queue) and sh_dev.h are plain C++ headers.
  */
@@ -64,6 +65,7 @@
 #include "sh_sched.h"
 #include "sh_dev.h"
 #include "sh_coalesce.h"
+#include "sh_map.h"
 
 /* function attributes (dynamic LDS limit) are per device: remember for which devices a kernel has had its attribute set
  * (engines on several GPUs may share one process).  A real once per device: the thread that finds the attribute unset holds
@@ -162,6 +164,12 @@ int sh_set_err_v(const char *fmt, va_list ap) {
     return -1;
 }
 extern "C" const char *scrappie_hip_last_error(void) { return g_err; }
+extern "C" void sh_set_error(const char *fmt, ...) {       /* (sh_host.c: the host C sets the same text) */
+    va_list ap;
+    va_start(ap, fmt);
+    (void)sh_set_err_v(fmt, ap);
+    va_end(ap);
+}
 
 #include "sh_eng_weights.inc"      /* weights as the device wants them: MFMA fragments, fp16 pieces, bias tables; the Model */
 /* ------------------------------------------------------------------ */
@@ -318,6 +326,8 @@ struct scrappie_hip_engine {
     double dbg_tail_free_frac = 0;   /* test hook (debug option "tail_free_frac", in 1/1000): the free share the helper's creation sees */
     BatchCoalescer batch_co;         /* this engine's queue of small scrappie_hip_basecall_batch calls, and the threads seen inside them lately */
     ShPresence batch_presence;
+    DBuf d_map[10]; HBuf h_map;      /* block-based mapping (sh_eng_map.inc): per-read tables, codes, bands, traceback, scratch, scores, paths, posterior */
+    double map_ms[3] = {0, 0, 0};    /* scrappie_hip_map_batch: network + S1, k_map, k_map_walk + results, summed over the last call's launch groups */
     std::mutex call_mu;              /* scrappie_hip_basecall_batch: one call at a time inside the engine (concurrent small calls share one: sh_eng_batch.inc) */
 };
 
@@ -441,6 +451,8 @@ extern "C" void scrappie_hip_engine_destroy(scrappie_hip_engine *e) {
                     &e->d_edge[0], &e->d_edge[1], &e->d_pos[0], &e->d_pos[1], &e->d_bases[0], &e->d_bases[1], &e->d_blen[0], &e->d_blen[1], &e->d_redo[0], &e->d_redo[1]}) b->release();
     for (int k = 0; k < 2; k++) for (HBuf *b : {&e->h_meta[k], &e->h_seq[k], &e->h_score[k], &e->h_hp[k], &e->h_pos[k], &e->h_bases[k], &e->h_blen[k], &e->h_redo[k]}) b->release();
     e->h_edge[0].release(); e->h_edge[1].release();
+    for (DBuf &b : e->d_map) b.release();
+    e->h_map.release();
     e->h_sig[0].release(); e->h_sig[1].release(); e->h_err[0].release(); e->h_err[1].release(); e->h_bad[0].release(); e->h_bad[1].release();
     if (e->ev_ok) { for (auto &row : e->ev) for (auto &x : row) (void)hipEventDestroy(x); for (auto &x : e->done) (void)hipEventDestroy(x); for (auto &x : e->kdone) (void)hipEventDestroy(x); for (auto &x : e->hdone) (void)hipEventDestroy(x); for (auto &x : e->pdone) (void)hipEventDestroy(x); for (auto &x : e->up) (void)hipEventDestroy(x); }
     (void)hipStreamDestroy(e->stream);
@@ -465,3 +477,4 @@ extern "C" scrappie_hip_params scrappie_hip_default_params(void) {
 #include "sh_eng_batch.inc"      /* chain-bound reads on a helper engine, host-signal entry points, several GPUs */
 #include "sh_eng_debug.inc"      /* measurement / test hooks: decoder and trunk inputs, debug_option / debug_fetch / debug_stitch */
 #include "sh_eng_surface.inc"      /* the reference's per-read functions: posterior / trunk on an explicit engine, the process-default engine, decode_transducer, decode_crf; all three coalesced (sh_coalesce.h) */
+#include "sh_eng_map.inc"      /* block-based mapping (sh_map.h): map_to_sequence_* on the process-default engine, scrappie_hip_map_batch */

@@ -1,0 +1,348 @@
+/* sh_eng_map.inc -- part of scrappie_hip.hip (one translation unit, included from there in this order; not compiled alone):
+ * block-based mapping of transducer posteriors to sequences (sh_map.h).  The reference's map_to_sequence_* on the
+ * process-default engine (the caller's host posterior uploaded, one launch), and scrappie_hip_map_batch: the network and S1
+ * of a launch group (run_pipeline to STOP_POST), k_map on the posterior where S1 left it, k_map_walk; scores and paths back. */
+
+/* host side of one k_map launch: the reads' tables, their codes and bands laid end to end, traceback / scratch offsets */
+struct MapPlan {
+    std::vector<ShMapRead> rd;
+    std::vector<int> seq, band;
+    std::vector<long long> path_off;      /* per read, -1: no path */
+    long long tb_words = 0, scr_floats = 0, path_len = 0;
+    size_t lds = 0;
+};
+
+static size_t map_lds_bytes(size_t L) { return (2 * (L + 2) + L) * 4; }
+/* code words (4 ceil(L / 64) per block) + END bits (one word per 32 blocks), rounded to whole 16-byte pieces */
+static long long map_tb_words(size_t L, size_t nblock) {
+    return (long long)nblock * (long long)(4 * ((L + 63) / 64)) + (long long)(((nblock + 31) / 32 + 3) & ~(size_t)3);
+}
+/* device bytes one read adds to a launch (traceback, scratch, path, codes, bands) */
+static size_t map_read_bytes(size_t L, size_t nblock, bool band, bool path) {
+    size_t b = L * 4 + sizeof(ShMapRead) + 64;
+    if (band) b += nblock * 8;
+    if (path) b += (size_t)map_tb_words(L, nblock) * 4 + nblock * 4;
+    if (map_lds_bytes(L) > SH_MAP_LDS) b += (2 * (L + 2) + 4) * 4;
+    return b;
+}
+
+static void plan_add(MapPlan &pl, long long post, int lane, size_t nblock, const int *seq, size_t L, const size_t *lo, const size_t *hi, bool path) {
+    ShMapRead r{};
+    r.post = post; r.lane = lane; r.nblock = (int)nblock; r.seqlen = (int)L; r.ok = 1;
+    r.seq = (long long)pl.seq.size();
+    pl.seq.insert(pl.seq.end(), seq, seq + L);
+    r.band = -1;
+    if (lo) {
+        r.band = (long long)pl.band.size();
+        for (size_t i = 0; i < nblock; i++) pl.band.push_back((int)lo[i]);
+        for (size_t i = 0; i < nblock; i++) pl.band.push_back((int)hi[i]);
+    }
+    r.tb = -1;
+    if (path) {
+        r.tb = pl.tb_words; pl.tb_words += map_tb_words(L, nblock);
+        pl.path_off.push_back(pl.path_len); pl.path_len += (long long)nblock;
+    } else pl.path_off.push_back(-1);
+    if (map_lds_bytes(L) <= SH_MAP_LDS) { r.scr = -1; pl.lds = std::max(pl.lds, map_lds_bytes(L)); }
+    else { r.scr = pl.scr_floats; pl.scr_floats += (long long)((2 * (L + 2) + 3) & ~(size_t)3); }
+    pl.rd.push_back(r);
+}
+
+template <bool VIT, bool BAND, bool TILED>
+static void map_launch_k(hipStream_t s, const ShMapArgs &a, size_t n_lds, size_t n, size_t lds) {
+    if (n_lds) hipLaunchKernelGGL((k_map<VIT, BAND, TILED, true>), dim3((unsigned)n_lds), dim3(SH_MAP_NTH), lds, s, a);
+    if (n > n_lds) {                     /* the reads whose rows live in scratch: the tables' tail */
+        ShMapArgs b = a;
+        b.rd += n_lds; b.score += n_lds; b.final_state += n_lds;
+        hipLaunchKernelGGL((k_map<VIT, BAND, TILED, false>), dim3((unsigned)(n - n_lds)), dim3(SH_MAP_NTH), 0, s, b);
+    }
+}
+
+/* one plan (all banded or all unbanded) through k_map (+ k_map_walk): scores into score[], paths into paths[i] (malloc'd,
+ * only where the plan holds a path).  a: the posterior, its shape and the penalties.  t[0] += k_map, t[1] += walk + copies. */
+static int map_run(scrappie_hip_engine *e, MapPlan &pl, ShMapArgs a, bool vit, bool band, bool tiled, float *score, int32_t **paths, double *t) {
+    const size_t n = pl.rd.size();
+    if (n == 0) return 0;
+    hipStream_t s = e->stream;
+    DBuf *d = e->d_map;          /* 0 reads, 1 codes, 2 bands, 3 traceback, 4 scratch, 5 scores, 6 final states, 7 path offsets, 8 paths */
+    const bool walk = vit && !band && pl.path_len > 0;
+    /* device order: the reads whose rows fit LDS first (one launch), then those in scratch (another) */
+    std::vector<size_t> perm(n);
+    std::iota(perm.begin(), perm.end(), (size_t)0);
+    std::stable_partition(perm.begin(), perm.end(), [&](size_t i) { return pl.rd[i].scr < 0; });
+    size_t n_lds = 0;
+    while (n_lds < n && pl.rd[perm[n_lds]].scr < 0) n_lds++;
+    std::vector<ShMapRead> rd(n);
+    std::vector<long long> poff(n);
+    for (size_t k = 0; k < n; k++) { rd[k] = pl.rd[perm[k]]; poff[k] = pl.path_off[perm[k]]; }
+    if (d[0].ensure(n * sizeof(ShMapRead)) || d[1].ensure(pl.seq.size() * 4 + 16) || d[2].ensure(pl.band.size() * 4 + 16) ||
+        d[3].ensure((size_t)pl.tb_words * 4 + 16) || d[4].ensure((size_t)pl.scr_floats * 4 + 16) || d[5].ensure(n * 4) ||
+        d[6].ensure(n * 4) || d[7].ensure(n * 8) || d[8].ensure((size_t)pl.path_len * 4 + 16) ||
+        e->h_map.ensure(n * 4 + (size_t)pl.path_len * 4)) return -1;
+    HIPCHK(hipMemcpyAsync(d[0].p, rd.data(), n * sizeof(ShMapRead), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d[1].p, pl.seq.data(), pl.seq.size() * 4, hipMemcpyHostToDevice, s));
+    if (!pl.band.empty()) HIPCHK(hipMemcpyAsync(d[2].p, pl.band.data(), pl.band.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d[7].p, poff.data(), n * 8, hipMemcpyHostToDevice, s));
+    a.rd = d[0].as<ShMapRead>(); a.seq = d[1].as<int>(); a.band = d[2].as<int>(); a.tb = d[3].as<unsigned>(); a.scr = d[4].as<float>();
+    a.score = d[5].as<float>(); a.final_state = d[6].as<int>();
+    const auto t0 = std::chrono::steady_clock::now();
+    const int k = (vit ? 4 : 0) | (band ? 2 : 0) | (tiled ? 1 : 0);
+    switch (k) {
+    case 0: map_launch_k<false, false, false>(s, a, n_lds, n, pl.lds); break;
+    case 1: map_launch_k<false, false, true>(s, a, n_lds, n, pl.lds); break;
+    case 2: map_launch_k<false, true, false>(s, a, n_lds, n, pl.lds); break;
+    case 3: map_launch_k<false, true, true>(s, a, n_lds, n, pl.lds); break;
+    case 4: map_launch_k<true, false, false>(s, a, n_lds, n, pl.lds); break;
+    case 5: map_launch_k<true, false, true>(s, a, n_lds, n, pl.lds); break;
+    case 6: map_launch_k<true, true, false>(s, a, n_lds, n, pl.lds); break;
+    default: map_launch_k<true, true, true>(s, a, n_lds, n, pl.lds); break;
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(sh_stream_wait(s));
+    const auto t1 = std::chrono::steady_clock::now();
+    if (walk) {
+        hipLaunchKernelGGL(k_map_walk, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, (const ShMapRead *)d[0].p, (int)n, (const unsigned *)d[3].p,
+                           (const int *)d[6].p, (const long long *)d[7].p, d[8].as<int>());
+        HIPCHK(hipGetLastError());
+    }
+    float *hs = e->h_map.as<float>();
+    int32_t *hp = (int32_t *)(hs + n);
+    HIPCHK(hipMemcpyAsync(hs, d[5].p, n * 4, hipMemcpyDeviceToHost, s));
+    if (walk) HIPCHK(hipMemcpyAsync(hp, d[8].p, (size_t)pl.path_len * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(sh_stream_wait(s));
+    for (size_t k = 0; k < n; k++) {
+        const size_t i = perm[k];
+        score[i] = hs[k];
+        if (!paths) continue;
+        paths[i] = nullptr;
+        if (!walk || pl.path_off[i] < 0) continue;
+        const size_t nb = (size_t)pl.rd[i].nblock;
+        paths[i] = (int32_t *)malloc(nb * 4);
+        if (!paths[i]) return set_err("out of host memory");
+        memcpy(paths[i], hp + pl.path_off[i], nb * 4);
+    }
+    if (t) {
+        t[0] += std::chrono::duration<double, std::milli>(t1 - t0).count();
+        t[1] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+    }
+    return 0;
+}
+
+/* the checks every target passes before it reaches a kernel; nr: posterior rows; 0 or -1 with the reason */
+static int map_target_ok(const char *fn, size_t nr, size_t nblock, const int *seq, size_t L, const size_t *lo, const size_t *hi, bool band) {
+    if (nr < 2) return set_err("%s: a posterior of %zu states (at least 2: one k-mer and stay)", fn, nr);
+    if (nblock == 0) return set_err("%s: a posterior of no blocks", fn);
+    if (nblock > (size_t)INT32_MAX / 2) return set_err("%s: %zu blocks is too many", fn, nblock);
+    if (L == 0) return set_err("%s: an empty sequence", fn);
+    if (L > SH_MAP_MAX_SEQ) return set_err("%s: a sequence of %zu states is longer than the %d this build maps", fn, L, SH_MAP_MAX_SEQ);
+    for (size_t i = 0; i < L; i++)
+        if (seq[i] < 0 || (size_t)seq[i] >= nr - 1) return set_err("%s: sequence state %d at %zu is not one of the posterior's %zu k-mers", fn, seq[i], i, nr - 1);
+    if (band) {
+        if (L < 3) return set_err("%s: a banded mapping needs a sequence of at least 3 states (got %zu)", fn, L);
+        if (!sh_bounds_sane(lo, hi, nblock, L, 0)) return set_err("%s: the bands are not valid (are_bounds_sane)", fn);
+    }
+    return 0;
+}
+
+/* ------------------------------------------------------------------ */
+/* per-read reference surface (decode.c:1420-1964)                      */
+/* ------------------------------------------------------------------ */
+static float map_one(const char *fn, const_scrappie_matrix lp, float stay_pen, float skip_pen, float local_pen, const int *seq, size_t L,
+                     const size_t *lo, const size_t *hi, bool band, bool vit, int *path) {
+    if (!lp || !seq) return NAN;                                       /* RETURN_NULL_IF, decode.c:1423-1424 */
+    if (band && (!lo || !hi)) return NAN;
+    if (band && L >= 3 && !are_bounds_sane(lo, hi, lp->nc, L)) { set_err("%s: the bands are not valid (are_bounds_sane)", fn); return NAN; }
+    if (map_target_ok(fn, lp->nr, lp->nc, seq, L, lo, hi, band)) return NAN;
+    scrappie_hip_engine *e = default_engine();
+    if (!e) return NAN;
+    (void)hipSetDevice(e->device);
+    std::lock_guard<std::mutex> lk(e->mu);
+    MapPlan pl;
+    const bool want_path = vit && !band && path;
+    plan_add(pl, 0, 0, lp->nc, seq, L, band ? lo : nullptr, band ? hi : nullptr, want_path);
+    DBuf &dpost = e->d_map[9];
+    const size_t pbytes = lp->nc * lp->stride * 4;
+    if (dpost.ensure(pbytes)) return NAN;
+    if (hipMemcpyAsync(dpost.p, lp->data.f, pbytes, hipMemcpyHostToDevice, e->stream) != hipSuccess) { set_err("%s: upload failed", fn); return NAN; }
+    ShMapArgs a{};
+    a.post = dpost.as<float>(); a.pstride = (long long)lp->stride; a.nr = (int)lp->nr;
+    a.stay_pen = stay_pen; a.skip_pen = skip_pen; a.local_pen = local_pen;
+    float score = NAN;
+    int32_t *p = nullptr;
+    if (map_run(e, pl, a, vit, band, false, &score, want_path ? &p : nullptr, nullptr)) { (void)hipGetLastError(); return NAN; }
+    if (want_path) {
+        if (!p) return NAN;
+        memcpy(path, p, lp->nc * 4);
+        free(p);
+    }
+    return score;
+}
+
+extern "C" float map_to_sequence_viterbi(const_scrappie_matrix logpost, float stay_pen, float skip_pen, float local_pen,
+                                         int const *seq, size_t seqlen, int *path) {
+    return map_one("map_to_sequence_viterbi", logpost, stay_pen, skip_pen, local_pen, seq, seqlen, nullptr, nullptr, false, true, path);
+}
+extern "C" float map_to_sequence_forward(const_scrappie_matrix logpost, float stay_pen, float skip_pen, float local_pen,
+                                         int const *seq, size_t seqlen) {
+    return map_one("map_to_sequence_forward", logpost, stay_pen, skip_pen, local_pen, seq, seqlen, nullptr, nullptr, false, false, nullptr);
+}
+extern "C" float map_to_sequence_viterbi_banded(const_scrappie_matrix logpost, float stay_pen, float skip_pen, float local_pen,
+                                                int const *seq, size_t seqlen, size_t const *poslow, size_t const *poshigh) {
+    return map_one("map_to_sequence_viterbi_banded", logpost, stay_pen, skip_pen, local_pen, seq, seqlen, poslow, poshigh, true, true, nullptr);
+}
+extern "C" float map_to_sequence_forward_banded(const_scrappie_matrix logpost, float stay_pen, float skip_pen, float local_pen,
+                                                int const *seq, size_t seqlen, size_t const *poslow, size_t const *poshigh) {
+    return map_one("map_to_sequence_forward_banded", logpost, stay_pen, skip_pen, local_pen, seq, seqlen, poslow, poshigh, true, false, nullptr);
+}
+
+/* ------------------------------------------------------------------ */
+/* batched: network + S1 -> k_map -> k_map_walk per launch group        */
+/* ------------------------------------------------------------------ */
+static size_t map_read_nsample(const Model *m, const raw_table &rt) {
+    const size_t nf = (rt.raw && rt.end > rt.start) ? rt.end - rt.start : 0;
+    return m->arch == 3 ? nf / (size_t)m->nfeat : nf;            /* events: raw holds [nevent][12] features */
+}
+static size_t map_blocks(const Model *m, size_t ns) {
+    return ns >= m->min_samples ? (ns + (size_t)m->stride - 1) / (size_t)m->stride : 0;       /* build_group */
+}
+
+extern "C" int scrappie_hip_read_blocks(scrappie_hip_engine *e, int model, size_t nsample) {
+    Model *m = get_model(e, model);
+    if (!m) return -1;
+    const size_t ns = m->arch == 3 ? nsample / (size_t)m->nfeat : nsample;
+    return (int)std::min<size_t>(map_blocks(m, ns), (size_t)INT32_MAX);
+}
+
+extern "C" int scrappie_hip_model_states(scrappie_hip_engine *e, int model) {
+    Model *m = get_model(e, model);
+    return m ? m->NS : -1;
+}
+
+extern "C" void scrappie_hip_map_timing(scrappie_hip_engine *e, double out[3]) {
+    for (int k = 0; k < 3; k++) out[k] = e ? e->map_ms[k] : 0.0;
+}
+
+extern "C" void scrappie_hip_free_map_results(scrappie_hip_map_result *r, size_t n) {
+    if (!r) return;
+    for (size_t i = 0; i < n; i++) { free(r[i].path); r[i].path = nullptr; }
+}
+
+/* one launch group: reads idx[0..cnt) of the call */
+static int map_group(scrappie_hip_engine *e, Model *m, const raw_table *reads, const scrappie_hip_map_target *tg, const std::vector<size_t> &idx,
+                     const scrappie_hip_params *p, bool vit, bool want_path, scrappie_hip_map_result *out, std::vector<std::string> &why) {
+    std::lock_guard<std::mutex> lk(e->mu);
+    const size_t cnt = idx.size();
+    std::vector<uint64_t> off(cnt);
+    std::vector<uint32_t> len(cnt);
+    size_t total = 0;
+    for (size_t k = 0; k < cnt; k++) {
+        const raw_table &rt = reads[idx[k]];
+        off[k] = total; len[k] = (uint32_t)map_read_nsample(m, rt);
+        total += rt.end - rt.start;
+    }
+    if (e->h_sig[0].ensure(total * 4) || e->d_signal[0].ensure(total * 4)) return -1;
+    float *hs = e->h_sig[0].as<float>();
+    for (size_t k = 0; k < cnt; k++) { const raw_table &rt = reads[idx[k]]; memcpy(hs + off[k], rt.raw + rt.start, (rt.end - rt.start) * 4); }
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(hipMemcpyAsync(e->d_signal[0].p, hs, total * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(sh_stream_wait(e->stream));        /* (the group's prologue runs on another stream: the signals must be there first) */
+    RunOut ro;
+    if (run_pipeline(e, m, e->d_signal[0].as<float>(), off.data(), len.data(), cnt, p, STOP_POST, 5, &ro)) return -1;
+    const LaunchGroup &lg = e->lgs[e->cur];
+    std::vector<unsigned> bad(lg.npad, 0);
+    HIPCHK(hipMemcpyAsync(bad.data(), e->d_bad[e->cur].p, lg.npad * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(sh_stream_wait(e->stream));
+    e->map_ms[0] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    std::vector<long long> tile_boff(lg.ntile, 0);
+    { long long ncb = 0; for (size_t t = 0; t < lg.ntile; t++) { int tt = 0; for (int b = 0; b < 16; b++) tt = std::max(tt, lg.rT[t * 16 + b]); tile_boff[t] = ncb; ncb += tt; } }
+    MapPlan plan[2];                       /* unbanded, banded */
+    std::vector<size_t> who[2];
+    for (size_t i = 0; i < lg.npad; i++) {
+        const int o = lg.order[i];
+        if (o < 0 || lg.rT[i] <= 0) continue;
+        const size_t r = idx[(size_t)o];
+        if (bad[i]) {
+            why[r] = "the read holds values outside the supported range (is the signal trimmed and med/MAD-normalised?)";
+            continue;
+        }
+        const scrappie_hip_map_target &t = tg[r];
+        const bool band = t.poslow != nullptr;
+        plan_add(plan[band], tile_boff[i >> 4], (int)(i & 15), (size_t)lg.rT[i], t.seq, t.seqlen, t.poslow, t.poshigh, want_path && vit && !band);
+        who[band].push_back(r);
+    }
+    ShMapArgs a{};
+    a.E = ro.E; a.sums = ro.sums; a.nr = m->NS; a.nchunk = m->ff_mtiles; a.min_prob = p->min_prob;
+    a.stay_pen = p->stay_pen; a.skip_pen = p->skip_pen; a.local_pen = p->local_pen;
+    for (int b = 0; b < 2; b++) {
+        const size_t n = who[b].size();
+        if (!n) continue;
+        std::vector<float> sc(n, NAN);
+        std::vector<int32_t *> paths(n, nullptr);
+        const int rc = map_run(e, plan[b], a, vit, b == 1, true, sc.data(), paths.data(), e->map_ms + 1);
+        for (size_t k = 0; k < n; k++) {
+            scrappie_hip_map_result &res = out[who[b][k]];
+            if (rc) { free(paths[k]); continue; }
+            res.score = sc[k]; res.nblock = (size_t)plan[b].rd[k].nblock; res.path = paths[k];
+        }
+        if (rc) return -1;
+    }
+    return 0;
+}
+
+extern "C" int scrappie_hip_map_batch(scrappie_hip_engine *e, int model, const raw_table *reads, const scrappie_hip_map_target *targets,
+                                      size_t n, const scrappie_hip_params *p, int viterbi, int want_path, scrappie_hip_map_result *out) {
+    if (!e || (n && (!reads || !targets || !out))) return set_err("map_batch: null argument");
+    std::lock_guard<std::mutex> call(e->call_mu);
+    Model *m = get_model(e, model);
+    if (!m) return -1;
+    if (m->arch == 1) return set_err("map_batch: model '%s' is a CRF (flip-flop) model: block-based mapping needs a transducer posterior", m->name.c_str());
+    {   /* NS = 4^k + 1 */
+        int nk = m->NS - 1;
+        while (nk > 1 && nk % 4 == 0) nk /= 4;
+        if (nk != 1) return set_err("map_batch: model '%s' has %d states, not 4^k + 1", m->name.c_str(), m->NS);
+    }
+    scrappie_hip_params dp = scrappie_hip_default_params();
+    if (!p) p = &dp;
+    (void)hipSetDevice(e->device);
+    for (double &x : e->map_ms) x = 0.0;
+    for (size_t i = 0; i < n; i++) { out[i].score = NAN; out[i].nblock = 0; out[i].path = nullptr; }
+    const bool vit = viterbi != 0, wp = want_path != 0;
+    std::vector<std::string> why(n);
+    /* launch groups in input order, bounded by reads and by device memory: the materialised posterior and the arena of the network
+     * (bytes_per_block with the posterior: ~66 KB per column block of 16 reads for 4^5 + 1 states), plus each read's traceback */
+    const size_t bpb = bytes_per_block(m, true);
+    const size_t budget = e->max_launch_blocks ? e->max_launch_blocks * bpb : (size_t)(e->mem_frac * (double)e->total_mem);
+    std::vector<size_t> grp;
+    size_t sumT = 0, maxT = 0, extra = 0;
+    int rc = 0;
+    auto flush = [&]() {
+        if (grp.empty() || rc) return;
+        if (map_group(e, m, reads, targets, grp, p, vit, wp, out, why)) {
+            rc = -1;
+            const std::string keep = g_err;
+            (void)hipGetLastError();
+            (void)sh_stream_wait(e->pstream); (void)sh_stream_wait(e->stream); (void)sh_stream_wait(e->cstream);
+            set_err("%s", keep.c_str());
+        }
+        grp.clear(); sumT = maxT = extra = 0;
+    };
+    for (size_t i = 0; i < n && !rc; i++) {
+        const scrappie_hip_map_target &t = targets[i];
+        const size_t T = map_blocks(m, map_read_nsample(m, reads[i]));
+        if (T == 0) { why[i] = "read too short for the model (or empty)"; continue; }
+        const bool band = t.poslow != nullptr || t.poshigh != nullptr;
+        if (!t.seq || map_target_ok("map_batch", (size_t)m->NS, T, t.seq, t.seqlen, t.poslow, t.poshigh, band) || (band && !t.poslow)) {
+            why[i] = t.seq ? g_err : "no sequence";
+            continue;
+        }
+        const size_t rb = map_read_bytes(t.seqlen, T, band, vit && wp && !band);
+        auto cost = [&](size_t sT, size_t mT, size_t ex) { return (sT / 16 + mT + 1) * bpb + ex; };
+        if (cost(T, T, rb) > budget) { why[i] = "read and sequence too long for one launch group on this device"; continue; }
+        if (!grp.empty() && (grp.size() >= e->max_launch_reads || cost(sumT + T, std::max(maxT, T), extra + rb) > budget)) flush();
+        grp.push_back(i); sumT += T; maxT = std::max(maxT, T); extra += rb;
+    }
+    flush();
+    if (rc) { scrappie_hip_free_map_results(out, n); for (size_t i = 0; i < n; i++) { out[i].score = NAN; out[i].nblock = 0; } return -1; }
+    for (size_t i = 0; i < n; i++)
+        if (!why[i].empty()) { set_err("map_batch: read %zu: %s", i, why[i].c_str()); break; }
+    return 0;
+}

@@ -12,7 +12,9 @@
 #include "scrappie_hip.h"
 #include "sh_internal.h"
 
+#include <err.h>
 #include <math.h>
+#include <stdbool.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -478,4 +480,86 @@ int scrappie_hip_event_features(const event_table et, float *out) {
         }
     free(f);
     return 0;
+}
+
+/* ------------------------------------------------------------------ */
+/* block-based mapping: band checks and sequence encoding              */
+/* (decode.c:1638-1689, scrappie_seq_helpers.c:30-74)                   */
+/* ------------------------------------------------------------------ */
+/* A band is [low[i], high[i]) per block: starts at 0, ends at seqlen, inside [0, seqlen], never empty the wrong way round,
+ * monotone, and each block reaches back to the one before (low[i] == high[i-1] allowed: a step but no stay).  Every rule is
+ * checked and reported (verbose) so that a caller sees all that is wrong at once, as the reference does. */
+int sh_bounds_sane(const size_t *low, const size_t *high, size_t nblock, size_t seqlen, int verbose) {
+#define SH_BAND_BAD(...) do { if (verbose) warnx(__VA_ARGS__); ok = 0; } while (0)
+    if (!low || !high) {
+        if (verbose) warnx("One or more bounds are NULL");
+        return 0;
+    }
+    if (nblock == 0) {
+        if (verbose) warnx("No blocks to bound");
+        return 0;
+    }
+    int ok = 1;
+    if (low[0] != 0) SH_BAND_BAD("First bound must include 0 (got %zu)", low[0]);
+    if (high[nblock - 1] != seqlen) SH_BAND_BAD("Last bound must equal seqlen %zu (got %zu)", seqlen, high[nblock - 1]);
+    for (size_t i = 0; i < nblock; i++) {
+        if (low[i] > seqlen) SH_BAND_BAD("Low bound for block %zu exceeds length of sequence (got %zu but seqlen is %zu)", i, low[i], seqlen);
+        if (high[i] > seqlen) SH_BAND_BAD("High bound for block %zu exceeds length of sequence (got %zu but seqlen is %zu)", i, high[i], seqlen);
+        if (low[i] > high[i]) SH_BAND_BAD("Low bound for block %zu exceeds high bound [%zu , %zu).", i, low[i], high[i]);
+        if (i == 0) continue;
+        if (low[i] > high[i - 1])
+            SH_BAND_BAD("Blocks %zu and %zu don't overlap [%zu , %zu) -> [%zu , %zu)", i - 1, i, low[i - 1], high[i - 1], low[i], high[i]);
+        if (low[i] < low[i - 1])
+            SH_BAND_BAD("Low bounds for blocks %zu and %zu aren't monotonic [%zu , %zu) -> [%zu , %zu)", i - 1, i, low[i - 1], high[i - 1], low[i], high[i]);
+        if (high[i] < high[i - 1])
+            SH_BAND_BAD("High bounds for blocks %zu and %zu aren't monotonic [%zu , %zu) -> [%zu , %zu)", i - 1, i, low[i - 1], high[i - 1], low[i], high[i]);
+    }
+#undef SH_BAND_BAD
+    return ok;
+}
+
+bool are_bounds_sane(size_t const *low, size_t const *high, size_t nblock, size_t seqlen) {
+    return sh_bounds_sane(low, high, nblock, seqlen, 1) != 0;
+}
+
+/* the library defines it (scrappie_hip.hip); weak, so that this file also links into the host-only builds of the tests */
+void sh_set_error(const char *fmt, ...) __attribute__((weak, format(printf, 1, 2)));
+#define SH_ERR(...) do { if (sh_set_error) sh_set_error(__VA_ARGS__); } while (0)
+
+static int base_code(char b) {
+    switch (b) {
+    case 'A': case 'a': return 0;
+    case 'C': case 'c': return 1;
+    case 'G': case 'g': return 2;
+    case 'T': case 't': return 3;
+    default: return -1;
+    }
+}
+
+/* the state code of every window of state_len bases (oldest base most significant), n - state_len + 1 of them, calloc'd.
+ * One pass: a window's code is the previous one without its oldest base, times four, plus the new base -- in unsigned
+ * arithmetic, which wraps exactly as the reference's int products do for long windows.  NULL (and the reason in
+ * scrappie_hip_last_error) on a base outside ACGT / acgt, or when there is no whole window. */
+int *encode_bases_to_integers(char const *seq, size_t n, size_t state_len) {
+    if (!seq || state_len == 0) { SH_ERR("encode_bases_to_integers: no sequence or a zero state length"); return NULL; }
+    if (n < state_len) { SH_ERR("encode_bases_to_integers: %zu bases hold no window of %zu", n, state_len); return NULL; }
+    for (size_t i = 0; i < n; i++)
+        if (base_code(seq[i]) < 0) {
+            warnx("Unrecognised base %d in read", seq[i]);
+            SH_ERR("encode_bases_to_integers: unrecognised base %d at %zu", seq[i], i);
+            return NULL;
+        }
+    const size_t nstate = n - state_len + 1;
+    int *codes = calloc(nstate, sizeof(int));
+    if (!codes) { SH_ERR("encode_bases_to_integers: out of memory"); return NULL; }
+    unsigned top = 1;                        /* weight of the oldest base: 4^(state_len - 1), mod 2^32 */
+    for (size_t j = 1; j < state_len; j++) top *= 4u;
+    unsigned code = 0;
+    for (size_t j = 0; j < state_len; j++) code = code * 4u + (unsigned)base_code(seq[j]);
+    codes[0] = (int)code;
+    for (size_t i = 1; i < nstate; i++) {
+        code = (code - (unsigned)base_code(seq[i - 1]) * top) * 4u + (unsigned)base_code(seq[i + state_len - 1]);
+        codes[i] = (int)code;
+    }
+    return codes;
 }

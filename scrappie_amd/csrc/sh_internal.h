@@ -14,6 +14,8 @@ int sh_homopolymer_side(const float *side, int *path, int nblock, int nstate);
 /* sh_inflate.c: what zlib's uncompress() does (zlib stream -> dst[0 .. cap), *outlen bytes; 0 on success), built for streams of literals */
 int sh_zlib_inflate(unsigned char *dst, size_t cap, size_t *outlen, const unsigned char *src, size_t srclen);
 unsigned long sh_h5mini_zlib_fallbacks(void);      /* chunks the built-in inflater refused and zlib decoded (expected: 0) */
+/* block-based mapping (sh_host.c): are_bounds_sane with its warnings on or off (1 / 0: sane / not) */
+int sh_bounds_sane(const size_t *low, const size_t *high, size_t nblock, size_t seqlen, int verbose);
 #ifdef __cplusplus
 }
 #endif

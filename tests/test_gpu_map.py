@@ -1,0 +1,222 @@
+"""Block-based mapping on the GPU (sh_map.h): the per-read map_to_sequence_* against the reference's compiled
+decode.c (oracle/_ref/libref_decode.so) and the numpy restatement of tests/test_map_cpu.py; the batched
+Engine.map_to_sequence against the reference run on the engine's own posterior; `scrappie seqmappy` on the bundled
+reads.  Viterbi scores and paths must be bit-identical; forward within 2x the reference's own error + 1e-5 |score|."""
+import ctypes as C
+import hashlib
+import os
+import subprocess
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import pytest
+
+import scrappie_amd as sa
+from scrappie_amd import model, synth
+from test_map_cpu import band_sets, call_map, map_cases, np_map, ref_decode_lib
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CLI = os.path.join(ROOT, "scrappie_amd", "scrappie")
+READS = os.path.join(ROOT, "tests", "golden", "reads")
+FA_SHA256 = {
+    "MINICOL228_20161012_FNFAB42578_MN17976_mux_scan_HG_52221_ch174_read172_strand":
+        "0dcf90a5b480a0765f5090e4c888a946330a956aad9cc2596f53e474ad0a2786",
+    "MINICOL228_20161012_FNFAB42578_MN17976_mux_scan_HG_52221_ch271_read66_strand":
+        "e56d9dc82d910b61ed30656ebb6035fefc029da2a675025eaa0f90b7a7e7e6b4",
+}
+PM = C.POINTER(sa._Mat)
+
+
+@pytest.fixture(scope="module")
+def ref():
+    R = ref_decode_lib()
+    assert R is not None, "oracle/_ref/libref_decode.so is required (build() makes it and it travels with the tree)"
+    return R
+
+
+def _forward_ok(got, want_ref, post, seq, pens, bands=None):
+    """|gpu - f64| <= 2 |ref - f64| + 1e-5 |score|; returns the ratio |gpu - f64| / (|ref - f64| + 1e-5 |score|)"""
+    lo, hi = (None, None) if bands is None else bands
+    exact = float(np_map(post, seq, *pens, viterbi=False, low=lo, high=hi, dtype=np.float64)[0])
+    eg, er = abs(float(got) - exact), abs(float(want_ref) - exact)
+    assert eg <= 2 * er + 1e-5 * abs(exact), (got, want_ref, exact)
+    return eg / (er + 1e-5 * abs(exact) + 1e-30)
+
+
+def test_per_read_against_reference(ref):
+    L = sa.lib()
+    rng = np.random.default_rng(21)
+    worst = 0.0
+    n_band = 0
+    for name, post, seq, pens in map_cases():
+        want_s, want_p = call_map(ref, post, seq, pens, True)
+        got_s, got_p = call_map(L, post, seq, pens, True, cast=PM)
+        assert got_s.tobytes() == want_s.tobytes(), (name, got_s, want_s)
+        assert np.array_equal(got_p, want_p), name
+        np_s, np_p = np_map(post, seq, *pens)
+        assert np.float32(np_s).tobytes() == got_s.tobytes() and np.array_equal(np_p, got_p), name
+        want_f, _ = call_map(ref, post, seq, pens, False)
+        got_f, _ = call_map(L, post, seq, pens, False, cast=PM)
+        worst = max(worst, _forward_ok(got_f, want_f, post, seq, pens))
+        if len(seq) < 3 or post.shape[0] > 2000:
+            continue
+        for bname, bands in band_sets(post.shape[0], len(seq), rng):
+            lo, hi = bands
+            if not ref.are_bounds_sane(lo.ctypes.data_as(C.POINTER(C.c_size_t)), hi.ctypes.data_as(C.POINTER(C.c_size_t)),
+                                       post.shape[0], len(seq)):
+                got_s, _ = call_map(L, post, seq, pens, True, bands, cast=PM)
+                assert np.isnan(got_s), (name, bname)
+                continue
+            n_band += 1
+            want_s, _ = call_map(ref, post, seq, pens, True, bands)
+            got_s, _ = call_map(L, post, seq, pens, True, bands, cast=PM)
+            assert got_s.tobytes() == want_s.tobytes(), (name, bname, got_s, want_s)
+            want_f, _ = call_map(ref, post, seq, pens, False, bands)
+            got_f, _ = call_map(L, post, seq, pens, False, bands, cast=PM)
+            worst = max(worst, _forward_ok(got_f, want_f, post, seq, pens, bands))
+    assert n_band > 100
+    print("forward: worst |gpu - f64| / (|ref - f64| + 1e-5 |score|) = %.3f" % worst)
+
+
+def test_undefined_cases_give_nan():
+    L = sa.lib()
+    post, _ = synth.simulated_posterior(50, 3, klen=3)
+    seq = np.arange(10, dtype=np.int32)
+    assert np.isnan(call_map(L, post, seq[:0], (0.0, 0.0, 4.0), True, cast=PM)[0])
+    assert "empty" in sa.last_error()
+    bad = seq.copy(); bad[4] = 64                                      # nr - 1 = 64 k-mers
+    assert np.isnan(call_map(L, post, bad, (0.0, 0.0, 4.0), False, cast=PM)[0])
+    short = seq[:2]
+    bands = (np.zeros(50, dtype=np.uintp), np.full(50, 2, dtype=np.uintp))
+    assert np.isnan(call_map(L, post, short, (0.0, 0.0, 4.0), True, bands, cast=PM)[0])
+    bands = (np.ones(50, dtype=np.uintp), np.full(50, 10, dtype=np.uintp))   # low[0] != 0
+    assert np.isnan(call_map(L, post, seq, (0.0, 0.0, 4.0), True, bands, cast=PM)[0])
+
+
+def test_true_sequence_outscores_random():
+    post, tpath = synth.simulated_posterior(800, 8, klen=5)
+    true = np.array([x for x in tpath if x >= 0], dtype=np.int32)
+    rnd = np.random.default_rng(2).integers(0, 1024, len(true)).astype(np.int32)
+    L = sa.lib()
+    for vit in (True, False):
+        assert call_map(L, post, true, (0.0, 0.0, 4.0), vit, cast=PM)[0] > call_map(L, post, rnd, (0.0, 0.0, 4.0), vit, cast=PM)[0]
+
+
+def test_scrappy_style_map_post_to_sequence(ref):
+    post, tpath = synth.simulated_posterior(300, 4, klen=4)
+    bases = "".join(np.random.default_rng(4).choice(list("ACGT"), 200))
+    m = sa.ScrappyMatrix.from_numpy(post, sloika=False)
+    codes = sa.encode_bases(bases, 4)
+    s, p = sa.map_post_to_sequence(m, bases, viterbi=True, path=True)
+    ws, wp = call_map(ref, post, codes, (0.0, 0.0, 4.0), True)
+    assert np.float32(s).tobytes() == ws.tobytes() and np.array_equal(p, wp)
+    s, p = sa.map_post_to_sequence(m, bases, viterbi=True, bands=5)
+    ws, _ = call_map(ref, post, codes, (0.0, 0.0, 4.0), True, sa.diagonal_bands(5, 300, len(codes)))
+    assert p is None and np.float32(s).tobytes() == ws.tobytes()
+
+
+@pytest.fixture(scope="module")
+def eng():
+    w = model.synthetic_model("rgrgr_r94", seed=1)
+    e = sa.Engine(0)
+    e.load_model("rgrgr_r94", w)
+    yield e
+    e.close()
+
+
+def _bases(n, rng):
+    return "".join(rng.choice(list("ACGT"), n))
+
+
+def test_engine_map_to_sequence(eng, ref):
+    rng = np.random.default_rng(31)
+    lens = [int(x) for x in rng.integers(600, 6000, 40)]
+    lens[3] = 5                                            # below the model's minimum
+    sigs = [synth.medmad_normalise(synth.synthetic_signal(n, 200 + i)) for i, n in enumerate(lens)]
+    seqs = [_bases(int(rng.integers(8, 700)), rng) for _ in lens]
+    seqs[7] = seqs[7][:20] + "N" + seqs[7][21:]          # a bad sequence
+    eng.set_max_launch_reads(16)                           # >= 3 launch groups
+    try:
+        for vit in (True, False):
+            for bands in (None, 4):
+                res = eng.map_to_sequence(sigs, seqs, viterbi=vit, path=vit and bands is None, bands=bands, stay_pen=0.5,
+                                          skip_pen=1.0, local_pen=4.0, min_prob=1e-5)
+                assert len(res) == len(sigs)
+                for i, (x, sq) in enumerate(zip(sigs, seqs)):
+                    sc, pth = res[i]
+                    if i in (3, 7):
+                        assert np.isnan(sc) and pth is None, i
+                        continue
+                    post = eng.posterior(x, min_prob=1e-5)
+                    codes = sa.encode_bases(sq, 5)
+                    bb = None if bands is None else sa.diagonal_bands(bands, post.shape[0], len(codes))
+                    if bb is not None and not ref.are_bounds_sane(bb[0].ctypes.data_as(C.POINTER(C.c_size_t)),
+                                                                  bb[1].ctypes.data_as(C.POINTER(C.c_size_t)), post.shape[0], len(codes)):
+                        assert np.isnan(sc), i
+                        continue
+                    ws, wp = call_map(ref, post, codes, (0.5, 1.0, 4.0), vit, bb)
+                    if vit:
+                        assert np.float32(sc).tobytes() == ws.tobytes(), (i, sc, ws)
+                        if bands is None:
+                            assert np.array_equal(pth, wp), i
+                    else:
+                        _forward_ok(sc, ws, post, codes, (0.5, 1.0, 4.0), bb)
+    finally:
+        eng.set_max_launch_reads(16384)
+
+
+def _fasta(name):
+    path = os.path.join(READS, name + ".fa")
+    data = open(path, "rb").read()
+    assert hashlib.sha256(data).hexdigest() == FA_SHA256[name]
+    return "".join(l.strip() for l in data.decode().splitlines()[1:])
+
+
+def _prepared(path):
+    L = sa.lib()
+    L.scrappie_hip_read_raw.restype = sa._RawTable
+    L.scrappie_hip_read_raw.argtypes = [C.c_char_p, C.c_bool]
+    rt = L.scrappie_hip_read_raw(os.fsencode(path), True)
+    rt = L.trim_and_segment_raw(rt, 200, 10, 100, 0.0)
+    x = np.ctypeslib.as_array(rt.raw, shape=(rt.n,))[rt.start:rt.end].copy()
+    sa._libc.free(C.cast(rt.raw, C.c_void_p))
+    L.medmad_normalise_array(x.ctypes.data_as(C.POINTER(C.c_float)), len(x))
+    return x
+
+
+def test_seqmappy_bundled_reads(eng, ref, tmp_path):
+    w = model.synthetic_model("rgrgr_r94", seed=1)
+    mfile = str(tmp_path / "rgrgr_r94.scrm")
+    model.save_model(w, mfile)
+    want = {}
+    for name in FA_SHA256:
+        fa, f5 = os.path.join(READS, name + ".fa"), os.path.join(READS, name + ".i16")
+        codes = sa.encode_bases(_fasta(name), 5)
+        post = eng.posterior(_prepared(f5), min_prob=1e-5)
+        s, path = call_map(ref, post, codes, (0.0, 0.0, 4.0), True)
+        nb = post.shape[0]
+        per = np.float32(-s) / np.float32(nb)
+        txt = "# %s to %s -- score %f over %d blocks (%f per block)\nblock\tpos\n" % (f5, fa, -s, nb, per)
+        txt += "".join("%d\t%d\n" % (i, p) for i, p in enumerate(path))
+        want[name] = (fa, f5, txt)
+    names = list(FA_SHA256)
+    one = subprocess.run([CLI, "seqmappy", "--model-file", mfile, want[names[0]][0], want[names[0]][1]],
+                         capture_output=True, text=True, timeout=600)
+    assert one.returncode == 0, one.stderr
+    assert one.stdout == want[names[0]][2]
+    two = subprocess.run([CLI, "seqmappy", "--model-file", mfile, want[names[1]][0], want[names[1]][1], want[names[0]][0], want[names[0]][1]],
+                         capture_output=True, text=True, timeout=600)
+    assert two.returncode == 0, two.stderr
+    assert two.stdout == want[names[1]][2] + want[names[0]][2]
+
+
+def test_per_read_threads():
+    cases = [c for c in map_cases(big=False) if c[1].shape[0] == 800][:16]
+    L = sa.lib()
+    alone = [call_map(L, post, seq, pens, True, cast=PM) for _, post, seq, pens in cases]
+    with ThreadPoolExecutor(16) as ex:
+        together = list(ex.map(lambda c: call_map(L, c[1], c[2], c[3], True, cast=PM), cases))
+    for (a_s, a_p), (t_s, t_p) in zip(alone, together):
+        assert a_s.tobytes() == t_s.tobytes() and np.array_equal(a_p, t_p)
