@@ -239,10 +239,10 @@ int scrappie_hip_register_model(const char *name, const char *path);
 /* The per-read network functions above may be called from many host threads at once, as the reference's OpenMP loop over reads does
  * (scrappie_raw.c:355,387): calls that arrive while the device is busy, or while the leader waits for company -- windows of SCRAPPIE_HIP_COALESCE_US (default 500)
  * microseconds until three quarters of the threads seen lately have joined or a window passes with no arrival, SCRAPPIE_HIP_COALESCE_MAX_US
- * (default 10000) in all (scrappie_amd/csrc/sh_coalesce.h) -- run as ONE launch group and every caller gets its own matrix -- bit for bit the one it would get alone.  SCRAPPIE_HIP_COALESCE=0: one
- * read per launch, as in earlier rounds.  out[0..2] = launch groups run this way, reads in them, the largest group (tests, tools). */
+ * (default 10000) in all (scrappie_amd/csrc/sh_coalesce.h) -- run as ONE launch group and every caller gets its own matrix -- bit for bit the one it would get alone.  SCRAPPIE_HIP_COALESCE=0: no
+ * queue -- one read per launch, calls serialised on the engine (the same code with a batch of one; so is a call on an explicit engine).  out[0..2] = launch groups run this way, reads in them, the largest group (tests, tools). */
 void scrappie_hip_coalescer_stats(unsigned long long out[3]);
-/* decode_transducer is coalesced the same way (one workgroup per waiting call, each the single-read form: same path, same score) */
+/* decode_transducer is coalesced the same way (one workgroup per waiting call, as for a call alone: same path, same score) */
 void scrappie_hip_decode_coalescer_stats(unsigned long long out[3]);
 /* ... and decode_crf (a thread per waiting call) */
 void scrappie_hip_crf_coalescer_stats(unsigned long long out[3]);

@@ -33,7 +33,7 @@
  *   sh_eng_groups.inc    run_device / collect / stitching, a call cut into launch groups
  *   sh_eng_batch.inc     helper engine for chain-bound reads, host-signal entry points, several GPUs
  *   sh_eng_debug.inc     measurement / test hooks
- *   sh_eng_surface.inc   the reference's per-read functions
+ *   sh_eng_surface.inc   the reference's per-read functions: one batch function per family, run by the queue or with a batch of one
  *   sh_eng_map.inc       block-based mapping of posteriors to sequences (per-read and batched)
  * Separate translation units: sh_p0.hip (signal preparation, k_p0), sh_host.c / sh_fast5.c / sh_h5mini.c (host C);
  * sh_coalesce.h (the per-read functions' queue) and sh_dev.h are plain C++ headers.
@@ -217,6 +217,10 @@ struct BatchReq {
 };
 struct BatchCoalescer : ShCoalescer<BatchReq> { BatchCoalescer() { target_pct = 100; window_mul = 4; } };      /* a leader waits for every thread seen inside lately (sh_coalesce.h) */
 
+/* the posteriors of a launch of the per-read functions in pinned memory: every caller copies its own matrix out after the engine's lock is released
+ * (all at once) and counts itself off `users`; the buffer is written again only when nobody is left (sh_eng_surface.inc) */
+struct PostStage { HBuf h; DBuf d; std::atomic<int> users{0}; };
+
 struct scrappie_hip_engine {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -326,6 +330,12 @@ struct scrappie_hip_engine {
     double dbg_tail_free_frac = 0;   /* test hook (debug option "tail_free_frac", in 1/1000): the free share the helper's creation sees */
     BatchCoalescer batch_co;         /* this engine's queue of small scrappie_hip_basecall_batch calls, and the threads seen inside them lately */
     ShPresence batch_presence;
+    /* staging of the per-read functions (sh_eng_surface.inc), touched under mu only (a PostStage's pinned half: see above), grow-only and kept between
+     * calls.  They belong to the engine, not to the queue in front of it: a call with the queue off, or on an engine of its own, runs the same batch
+     * functions with nobody but mu to keep two callers apart. */
+    PostStage post_stage[2]; unsigned post_turn = 0;     /* posterior_batch: two in turn, so that a batch seldom waits for the last one's callers */
+    HBuf h_dec_in, h_dec_out; DBuf d_dec[7];             /* decode_batch: posteriors in (a lone call; the queue's members fill the queue's own), paths + scores out */
+    HBuf h_crf_in, h_crf_out; DBuf d_crf[4];             /* crf_batch */
     DBuf d_map[10]; HBuf h_map;      /* block-based mapping (sh_eng_map.inc): per-read tables, codes, bands, traceback, scratch, scores, paths, posterior */
     double map_ms[3] = {0, 0, 0};    /* scrappie_hip_map_batch: network + S1, k_map, k_map_walk + results, summed over the last call's launch groups */
     std::mutex call_mu;              /* scrappie_hip_basecall_batch: one call at a time inside the engine (concurrent small calls share one: sh_eng_batch.inc) */
@@ -453,6 +463,10 @@ extern "C" void scrappie_hip_engine_destroy(scrappie_hip_engine *e) {
     e->h_edge[0].release(); e->h_edge[1].release();
     for (DBuf &b : e->d_map) b.release();
     e->h_map.release();
+    for (PostStage &ps : e->post_stage) { ps.h.release(); ps.d.release(); }
+    for (DBuf &b : e->d_dec) b.release();
+    for (DBuf &b : e->d_crf) b.release();
+    for (HBuf *b : {&e->h_dec_in, &e->h_dec_out, &e->h_crf_in, &e->h_crf_out}) b->release();
     e->h_sig[0].release(); e->h_sig[1].release(); e->h_err[0].release(); e->h_err[1].release(); e->h_bad[0].release(); e->h_bad[1].release();
     if (e->ev_ok) { for (auto &row : e->ev) for (auto &x : row) (void)hipEventDestroy(x); for (auto &x : e->done) (void)hipEventDestroy(x); for (auto &x : e->kdone) (void)hipEventDestroy(x); for (auto &x : e->hdone) (void)hipEventDestroy(x); for (auto &x : e->pdone) (void)hipEventDestroy(x); for (auto &x : e->up) (void)hipEventDestroy(x); }
     (void)hipStreamDestroy(e->stream);

@@ -18,6 +18,10 @@
  * (target 1).
  *
  * Req needs:  int phase  (0 queued, 1 asked to copy its input, 2 copied, 3 done).
+ *
+ * What a launch takes is the same walk at every queue (take_compatible): the front request, then every waiting request that may
+ * share its launch, up to a count and a cost.  What the launch itself runs is the caller's business; the per-read functions run
+ * the same batch function for a lone call (queue off: a batch of one, no waiting) as for a launch the queue has assembled.
  */
 #pragma once
 #include <algorithm>
@@ -56,6 +60,21 @@ struct ShCoalesceTuning {
         return t;
     }
 };
+
+/* A leader's take: move the front request of `queue`, and every later one with same(front, c), into `batch`, in queue order, until the
+ * batch holds max_reqs requests or its summed cost(c) would pass max_cost.  The front request is always taken, whatever it costs alone. */
+template <class Req, class Cost, class Same, class CostOf>
+void take_compatible(std::deque<Req *> &queue, std::vector<Req *> &batch, size_t max_reqs, Cost max_cost, Same same, CostOf cost) {
+    if (queue.empty()) return;
+    const Req *front = queue.front();
+    Cost total = 0;
+    for (auto it = queue.begin(); it != queue.end() && batch.size() < max_reqs;) {
+        Req *c = *it;
+        const Cost w = (Cost)cost(c);
+        if (same(front, c) && (batch.empty() || total + w <= max_cost)) { batch.push_back(c); total += w; it = queue.erase(it); }
+        else ++it;
+    }
+}
 
 template <class Req>
 class ShCoalescer {

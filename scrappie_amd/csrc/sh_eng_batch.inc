@@ -338,7 +338,7 @@ extern "C" long scrappie_hip_deferred_collect(scrappie_hip_engine *e, long ticke
  * is decided by how many calls share a group: 157 calls of 64 from one thread run one after the other (nothing to share them with; the
  * streaming entry points are the single-thread answer), from 64 threads they run as three groups.  Calls of SH_BATCH_COALESCE_MAX reads or
  * more fill the device by themselves and go straight in.  Either way the engine sees one call at a time (call_mu), which also makes this entry
- * point safe to call from several threads.  SCRAPPIE_HIP_COALESCE=0 or SCRAPPIE_HIP_BATCH_COALESCE=0: every call alone, as before round 6. */
+ * point safe to call from several threads.  SCRAPPIE_HIP_COALESCE=0 or SCRAPPIE_HIP_BATCH_COALESCE=0: every call alone. */
 #ifndef SH_BATCH_COALESCE_MAX
 #define SH_BATCH_COALESCE_MAX 4096
 #endif
@@ -366,14 +366,9 @@ extern "C" int scrappie_hip_basecall_batch(scrappie_hip_engine *e, int model, co
     r.e = e; r.model = model; r.reads = reads; r.n = n; r.p = p ? *p : scrappie_hip_default_params(); r.out = out;
     e->batch_co.run(r, e->batch_presence, MAX_CALLS, false,
         [&](std::deque<BatchReq *> &q, std::vector<BatchReq *> &batch) {
-            const BatchReq *f = q.front();
-            size_t tot = 0;
-            for (auto it = q.begin(); it != q.end() && batch.size() < MAX_CALLS;) {
-                BatchReq *c = *it;
-                if (c->e == f->e && c->model == f->model && memcmp(&c->p, &f->p, sizeof f->p) == 0 && (batch.empty() || tot + c->n <= MAX_READS)) {
-                    batch.push_back(c); tot += c->n; it = q.erase(it);
-                } else ++it;
-            }
+            take_compatible(q, batch, MAX_CALLS, MAX_READS,
+                            [](const BatchReq *f, const BatchReq *c) { return c->e == f->e && c->model == f->model && memcmp(&c->p, &f->p, sizeof f->p) == 0; },
+                            [](const BatchReq *c) { return c->n; });
         },
         [](std::vector<BatchReq *> &) { return true; }, [](BatchReq &) {},
         [&](std::vector<BatchReq *> &batch) {

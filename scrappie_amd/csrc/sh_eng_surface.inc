@@ -1,76 +1,22 @@
 /* sh_eng_surface.inc -- part of scrappie_hip.hip (one translation unit, included from there in this order; not compiled alone):
- * the reference's per-read functions: posterior / trunk on an explicit engine, the process-default engine, decode_transducer, decode_crf; all three coalesced (sh_coalesce.h). */
+ * the reference's per-read functions: posterior / trunk on an explicit engine, the process-default engine, decode_transducer, decode_crf.
+ * Each family has ONE implementation, a batch function (posterior_batch, decode_batch, crf_batch): the queue (sh_coalesce.h) hands it the calls that were
+ * waiting, a call by itself -- explicit engine, or SCRAPPIE_HIP_COALESCE=0 -- hands it a batch of one.  The batch functions take the engine's lock and stage
+ * through buffers the engine owns, so callers that come in without the queue are kept apart by that lock alone. */
 
 /* ------------------------------------------------------------------ */
-/* single-read surface on an explicit engine                            */
+/* the network: posterior / trunk of the reads of one launch group      */
 /* ------------------------------------------------------------------ */
-static scrappie_matrix gather_to_host(scrappie_hip_engine *e, const float *src, const float *sums, int T, int nr,
-                                      int nchunk, int finalize, int want_log, float min_prob) {
-    scrappie_matrix M = make_scrappie_matrix((size_t)nr, (size_t)T);
-    if (!M) { set_err("out of host memory"); return nullptr; }
-    DBuf tmp;
-    const size_t bytes = (size_t)T * M->stride * 4;
-    if (tmp.ensure(bytes)) { free_scrappie_matrix(M); return nullptr; }
-    bool ok = hipMemsetAsync(tmp.p, 0, bytes, e->stream) == hipSuccess;
-    const long long tot = (long long)T * nr;
-    hipLaunchKernelGGL(k_gather_read, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, e->stream, src, sums, 0LL, 0, T, nr, nchunk,
-                       (int)M->stride, finalize, want_log, min_prob, tmp.as<float>());
-    ok = ok && hipMemcpyAsync(M->data.f, tmp.p, bytes, hipMemcpyDeviceToHost, e->stream) == hipSuccess;
-    ok = ok && sh_stream_wait(e->stream) == hipSuccess;
-    tmp.release();
-    if (!ok) { set_err("gather failed: %s", hipGetErrorString(hipGetLastError())); return free_scrappie_matrix(M); }
-    return M;
-}
-
-/* single-read surface: did the read of the launch group just run leave the split products' operand range? */
-static bool read_out_of_range(scrappie_hip_engine *e) {
-    unsigned flag = 0;
-    if (hipMemcpyAsync(&flag, e->d_bad[e->cur].p, 4, hipMemcpyDeviceToHost, e->stream) != hipSuccess || sh_stream_wait(e->stream) != hipSuccess) {
-        set_err("reading the range flag failed: %s", hipGetErrorString(hipGetLastError()));
-        return true;
-    }
-    if (flag) set_err("the read holds values outside the supported range (|activation| >= %g after the first layer, or non-finite): "
-                      "is the signal trimmed and med/MAD-normalised?", (double)SH_ACT_LIMIT);
-    return flag != 0;
-}
-
-static int stage_one(scrappie_hip_engine *e, const raw_table &signal, uint64_t &off, uint32_t &len) {
-    if (signal.n == 0 || !signal.raw || signal.end <= signal.start) return set_err("empty read");
-    const size_t ns = signal.end - signal.start;
-    if (e->d_signal[0].ensure(ns * 4)) return -1;
-    HIPCHK(hipMemcpyAsync(e->d_signal[0].p, signal.raw + signal.start, ns * 4, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(sh_stream_wait(e->stream));   /* source is pageable caller memory */
-    off = 0; len = (uint32_t)ns;
-    return 0;
-}
-
-extern "C" scrappie_matrix scrappie_hip_posterior(scrappie_hip_engine *e, int model, const raw_table signal, float min_prob,
-                                                  float tempW, float tempb, bool return_log) {
-    Model *m = get_model(e, model);
-    if (!m) return nullptr;
-    (void)hipSetDevice(e->device);
-    std::lock_guard<std::mutex> lk(e->mu);
-    uint64_t off; uint32_t len;
-    if (stage_one(e, signal, off, len)) return nullptr;
-    if (m->arch == 3) len /= (uint32_t)m->nfeat;          /* events: raw holds [nevent][12] features */
-    if (len < m->min_samples) { set_err("read of %u samples is below the model minimum %zu", len, m->min_samples); return nullptr; }
-    scrappie_hip_params p = scrappie_hip_default_params();
-    p.min_prob = min_prob; p.tempW = tempW; p.tempb = tempb;
-    RunOut ro;
-    if (run_pipeline(e, m, e->d_signal[0].as<float>(), &off, &len, 1, &p, STOP_POST, 5, &ro)) return nullptr;
-    if (read_out_of_range(e)) return nullptr;
-    const int T = e->lgs[e->cur].rT[0];
-    if (m->arch != 1) return gather_to_host(e, ro.E, ro.sums, T, m->NS, m->ff_mtiles, 1, return_log ? 1 : 0, min_prob);
-    return gather_to_host(e, ro.E, nullptr, T, m->NS, m->ff_mtiles, 0, 0, 0.f);
-}
-
-/* Posteriors of several reads in one launch group (the per-read reference surface called from several host threads at once: the coalescer below).
- * Every request gets its own host matrix or its own error text; a read's posterior does not depend on what it was batched with. */
+/* Posteriors of several reads in one launch group: what the queue below assembles from the calls of several host threads, and -- as a batch of one --
+ * a call on an explicit engine or with the queue off.  Every request gets its own host matrix or its own error text; a read's posterior does not
+ * depend on what it was batched with.  The requests of a batch share model, temperatures and stopping point. */
 struct PostReq {
     int model = -1;
     raw_table sig{};
     float min_prob = 0.f, tempW = 1.f, tempb = 1.f;
     bool want_log = true;
+    StopAt stop = STOP_POST;         /* STOP_TRUNK: the activations after layer `upto` instead of the posterior (scrappie_hip_trunk) */
+    int upto = 5;
     scrappie_matrix out = nullptr;
     size_t nr = 0, nc = 0;           /* shape of the matrix to make */
     const float *src = nullptr;      /* the matrix's bytes in the batch's pinned buffer: the caller makes the matrix and copies them itself (all callers at once) */
@@ -79,19 +25,20 @@ struct PostReq {
     int phase = 0;                   /* sh_coalesce.h: 0 queued ... 3 done */
     char err[256] = "";
 };
-struct PostStage { HBuf h; DBuf d; std::atomic<int> users{0}; };
 static void post_fail(PostReq *r, const char *fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(r->err, sizeof r->err, fmt, ap);
     va_end(ap);
 }
-static void posterior_batch(scrappie_hip_engine *e, std::vector<PostReq *> &reqs, PostStage *stage) {
+static void posterior_batch(scrappie_hip_engine *e, std::vector<PostReq *> &reqs) {
     if (reqs.empty()) return;
     Model *m = get_model(e, reqs[0]->model);
     if (!m) { for (PostReq *r : reqs) post_fail(r, "%s", g_err); return; }
+    const bool trunk = reqs[0]->stop == STOP_TRUNK;
     (void)hipSetDevice(e->device);
     std::lock_guard<std::mutex> lk(e->mu);
+    PostStage *stage = &e->post_stage[e->post_turn++ & 1];
     std::vector<PostReq *> live;
     std::vector<uint64_t> off;
     std::vector<uint32_t> len;
@@ -100,7 +47,11 @@ static void posterior_batch(scrappie_hip_engine *e, std::vector<PostReq *> &reqs
         const raw_table &sg = r->sig;
         if (sg.n == 0 || !sg.raw || sg.end <= sg.start) { post_fail(r, "empty read"); continue; }
         const size_t nf = sg.end - sg.start, ns = m->arch == 3 ? nf / (size_t)m->nfeat : nf;      /* events: raw holds [nevent][12] features */
-        if (ns < m->min_samples) { post_fail(r, "read of %zu samples is below the model minimum %zu", ns, m->min_samples); continue; }
+        if (ns < m->min_samples) {
+            if (trunk) post_fail(r, "read too short");
+            else post_fail(r, "read of %zu samples is below the model minimum %zu", ns, m->min_samples);
+            continue;
+        }
         live.push_back(r); off.push_back(total); len.push_back((uint32_t)ns);
         total += nf;
     }
@@ -116,7 +67,11 @@ static void posterior_batch(scrappie_hip_engine *e, std::vector<PostReq *> &reqs
     scrappie_hip_params p = scrappie_hip_default_params();
     p.tempW = live[0]->tempW; p.tempb = live[0]->tempb;
     RunOut ro;
-    if (run_pipeline(e, m, e->d_signal[0].as<float>(), off.data(), len.data(), live.size(), &p, STOP_POST, 5, &ro)) { fail_all(); return; }
+    if (run_pipeline(e, m, e->d_signal[0].as<float>(), off.data(), len.data(), live.size(), &p, live[0]->stop, live[0]->upto, &ro)) { fail_all(); return; }
+    /* what is gathered: the posterior where S1 left it (finalised here for the transducers; the CRF's transitions are final), or the trunk's activations */
+    const float *src = trunk ? ro.act : ro.E;
+    const int nr = trunk ? ro.act_units : m->NS, nchunk = trunk ? ro.act_units / 16 : m->ff_mtiles;
+    const bool tr = !trunk && m->arch != 1;
     const LaunchGroup &lg = e->lgs[e->cur];
     std::vector<unsigned> bad(lg.npad, 0);
     if (hipMemcpyAsync(bad.data(), e->d_bad[e->cur].p, lg.npad * 4, hipMemcpyDeviceToHost, e->stream) != hipSuccess || sh_stream_wait(e->stream) != hipSuccess) {
@@ -127,14 +82,14 @@ static void posterior_batch(scrappie_hip_engine *e, std::vector<PostReq *> &reqs
     /* one staging buffer for the whole group, one synchronisation */
     std::vector<size_t> toff(lg.npad, 0);
     size_t tbytes = 0;
-    const size_t mstride = (size_t)((m->NS + 3) / 4) * 4;      /* scrappie_matrix.c:11-42: rows padded to whole vectors */
+    const size_t mstride = (size_t)((nr + 3) / 4) * 4;      /* scrappie_matrix.c:11-42: rows padded to whole vectors */
     for (size_t i = 0; i < lg.npad; i++) {
         const int o = lg.order[i];
         if (o < 0 || lg.rT[i] <= 0) continue;
         PostReq *r = live[(size_t)o];
         if (bad[i]) { post_fail(r, "the read holds values outside the supported range (|activation| >= %g after the first layer, or non-finite): is the signal trimmed and med/MAD-normalised?", (double)SH_ACT_LIMIT); continue; }
         /* (the matrix itself -- 3.3 MB to allocate and clear for a read of 4000 samples -- is made by the caller, beside all the others) */
-        r->nr = m->NS; r->nc = lg.rT[i];
+        r->nr = (size_t)nr; r->nc = lg.rT[i];
         toff[i] = tbytes; tbytes += (size_t)lg.rT[i] * mstride * 4;
     }
     DBuf &tmp = stage->d;            /* (grow-only, kept between launch groups) */
@@ -148,11 +103,10 @@ static void posterior_batch(scrappie_hip_engine *e, std::vector<PostReq *> &reqs
         if (o < 0 || lg.rT[i] <= 0 || live[(size_t)o]->nc == 0) continue;
         PostReq *r = live[(size_t)o];
         const int T = lg.rT[i];
-        const long long tot = (long long)T * m->NS;
+        const long long tot = (long long)T * nr;
         float *dst = (float *)((char *)tmp.p + toff[i]);
-        const bool tr = m->arch != 1;
-        hipLaunchKernelGGL(k_gather_read, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, e->stream, ro.E, tr ? ro.sums : nullptr, tile_boff[i >> 4], (int)(i & 15), T, m->NS,
-                           m->ff_mtiles, (int)mstride, tr ? 1 : 0, tr && r->want_log ? 1 : 0, tr ? r->min_prob : 0.f, dst);
+        hipLaunchKernelGGL(k_gather_read, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, e->stream, src, tr ? ro.sums : nullptr, tile_boff[i >> 4], (int)(i & 15), T, nr,
+                           nchunk, (int)mstride, tr ? 1 : 0, tr && r->want_log ? 1 : 0, tr ? r->min_prob : 0.f, dst);
     }
     /* one copy into pinned memory at the link's rate; the callers take their matrices out of it themselves, all at once */
     ok = ok && (tbytes == 0 || hipMemcpyAsync(stage->h.p, tmp.p, tbytes, hipMemcpyDeviceToHost, e->stream) == hipSuccess);
@@ -175,41 +129,9 @@ static void posterior_batch(scrappie_hip_engine *e, std::vector<PostReq *> &reqs
     stage->users.store(nuse, std::memory_order_release);
 }
 
-/* The reference calls its network functions from an OpenMP loop over reads (scrappie_raw.c:355,387), one read per call.  One read cannot fill the
- * device -- its five recurrent layers are a serial chain of T steps each -- so calls that arrive while the device is busy (or within a short window
- * of the first) are run as ONE launch group: whoever finds no batch running becomes its leader, takes every waiting request for the same model and
- * temperatures, runs them, hands the matrices out and wakes the others.  SCRAPPIE_HIP_COALESCE=0: every call runs alone, as before;
- * SCRAPPIE_HIP_COALESCE_US / _MAX_US: the leader's waiting windows (defaults 500 / 10000 microseconds); the queue itself is sh_coalesce.h. */
-/* how many host threads are inside the coalesced functions (either of them), and the most seen lately: a process that calls from ONE thread must not
- * wait for company that cannot come, one that calls from many should */
-static ShPresence g_presence;           /* threads inside the per-read functions: how much company a leader waits for (sh_coalesce.h) */
-struct Coalescer : ShCoalescer<PostReq> { PostStage stage[2]; };
-static Coalescer g_co;
-static bool coalesce_on(char which = 'p') {       /* SCRAPPIE_HIP_COALESCE: 0 neither, p the network calls only, d decode_transducer only; default both */
-    static const int on = [] { const char *v = getenv("SCRAPPIE_HIP_COALESCE"); return !v ? 3 : v[0] == '0' ? 0 : v[0] == 'p' ? 1 : v[0] == 'd' ? 2 : 3; }();
-    return (on & (which == 'd' ? 2 : 1)) != 0;
-}
-static scrappie_matrix coalesced_posterior(scrappie_hip_engine *e, int model, const raw_table signal, float min_prob, float tempW, float tempb, bool return_log) {
-    constexpr size_t MAX_READS = 4096, MAX_BLOCKS = 200000;          /* per launch group: the posterior is materialised (66 KB per block of 16 reads) */
-    ShInside inside(g_presence);
-    PostReq r;
-    r.model = model; r.sig = signal; r.min_prob = min_prob; r.tempW = tempW; r.tempb = tempb; r.want_log = return_log;
-    PostStage *stage = nullptr;
-    g_co.run(r, g_presence, MAX_READS, false,
-        [&](std::deque<PostReq *> &q, std::vector<PostReq *> &batch) {
-            const PostReq *f = q.front();
-            size_t blocks = 0;
-            for (auto it = q.begin(); it != q.end() && batch.size() < MAX_READS;) {
-                PostReq *c = *it;
-                const size_t b = (c->sig.end > c->sig.start ? c->sig.end - c->sig.start : 0) / 4 + 1;
-                if (c->model == f->model && c->tempW == f->tempW && c->tempb == f->tempb && (batch.empty() || blocks + b <= MAX_BLOCKS)) {
-                    batch.push_back(c); blocks += b; it = q.erase(it);
-                } else ++it;
-            }
-            stage = &g_co.stage[g_co.n_batches & 1];
-        },
-        [](std::vector<PostReq *> &) { return true; }, [](PostReq &) {},
-        [&](std::vector<PostReq *> &batch) { posterior_batch(e, batch, stage); });
+/* the caller's half of a batch, on its own thread with the engine's lock released: its matrix, made here and filled from the batch's pinned buffer
+ * (3.3 MB to allocate, clear and copy for a read of 4000 samples: the callers of a batch do it all at once), or its error text */
+static scrappie_matrix post_result(PostReq &r) {
     if (r.src) {
         r.out = make_scrappie_matrix(r.nr, r.nc);
         if (r.out) memcpy(r.out->data.f, r.src, r.nbytes);
@@ -219,27 +141,60 @@ static scrappie_matrix coalesced_posterior(scrappie_hip_engine *e, int model, co
     if (!r.out && r.err[0]) set_err("%s", r.err);
     return r.out;
 }
+/* a call by itself (explicit engine, or the queue off): a batch of one, run at once; calls are serialised on the engine */
+static scrappie_matrix posterior_alone(scrappie_hip_engine *e, PostReq &r) {
+    std::vector<PostReq *> one{&r};
+    posterior_batch(e, one);
+    return post_result(r);
+}
+
+extern "C" scrappie_matrix scrappie_hip_posterior(scrappie_hip_engine *e, int model, const raw_table signal, float min_prob,
+                                                  float tempW, float tempb, bool return_log) {
+    PostReq r;
+    r.model = model; r.sig = signal; r.min_prob = min_prob; r.tempW = tempW; r.tempb = tempb; r.want_log = return_log;
+    return posterior_alone(e, r);
+}
+
+extern "C" scrappie_matrix scrappie_hip_trunk(scrappie_hip_engine *e, int model, const raw_table signal, int upto) {
+    PostReq r;
+    r.model = model; r.sig = signal; r.stop = STOP_TRUNK; r.upto = upto;
+    return posterior_alone(e, r);
+}
+
+/* The reference calls its network functions from an OpenMP loop over reads (scrappie_raw.c:355,387), one read per call.  One read cannot fill the
+ * device -- its five recurrent layers are a serial chain of T steps each -- so calls that arrive while the device is busy (or within a short window
+ * of the first) are run as ONE launch group: whoever finds no batch running becomes its leader, takes every waiting request for the same model and
+ * temperatures, runs them, hands the matrices out and wakes the others.  SCRAPPIE_HIP_COALESCE=0: no queue -- every call runs the batch function
+ * with its one request, one read per launch, calls serialised on the engine;
+ * SCRAPPIE_HIP_COALESCE_US / _MAX_US: the leader's waiting windows (defaults 500 / 10000 microseconds); the queue itself is sh_coalesce.h. */
+/* how many host threads are inside the coalesced functions (either of them), and the most seen lately: a process that calls from ONE thread must not
+ * wait for company that cannot come, one that calls from many should */
+static ShPresence g_presence;           /* threads inside the per-read functions: how much company a leader waits for (sh_coalesce.h) */
+static ShCoalescer<PostReq> g_co;
+static bool coalesce_on(char which = 'p') {       /* SCRAPPIE_HIP_COALESCE: 0 neither, p the network calls only, d decode_transducer only; default both */
+    static const int on = [] { const char *v = getenv("SCRAPPIE_HIP_COALESCE"); return !v ? 3 : v[0] == '0' ? 0 : v[0] == 'p' ? 1 : v[0] == 'd' ? 2 : 3; }();
+    return (on & (which == 'd' ? 2 : 1)) != 0;
+}
+static scrappie_matrix coalesced_posterior(scrappie_hip_engine *e, int model, const raw_table signal, float min_prob, float tempW, float tempb, bool return_log) {
+    constexpr size_t MAX_READS = 4096, MAX_BLOCKS = 200000;          /* per launch group: the posterior is materialised (66 KB per block of 16 reads) */
+    ShInside inside(g_presence);
+    PostReq r;
+    r.model = model; r.sig = signal; r.min_prob = min_prob; r.tempW = tempW; r.tempb = tempb; r.want_log = return_log;
+    g_co.run(r, g_presence, MAX_READS, false,
+        [&](std::deque<PostReq *> &q, std::vector<PostReq *> &batch) {
+            take_compatible(q, batch, MAX_READS, MAX_BLOCKS,
+                            [](const PostReq *f, const PostReq *c) { return c->model == f->model && c->tempW == f->tempW && c->tempb == f->tempb; },
+                            [](const PostReq *c) { return (c->sig.end > c->sig.start ? c->sig.end - c->sig.start : 0) / 4 + 1; });
+        },
+        [](std::vector<PostReq *> &) { return true; }, [](PostReq &) {},
+        [&](std::vector<PostReq *> &batch) { posterior_batch(e, batch); });
+    return post_result(r);
+}
 /* (tests, tools) launch groups the coalescer has run, reads in them, the largest group */
 extern "C" void scrappie_hip_coalescer_stats(unsigned long long out[3]) {
     std::lock_guard<std::mutex> lk(g_co.mu);
     out[0] = g_co.n_batches; out[1] = g_co.n_reads; out[2] = g_co.max_batch;
     if (getenv("SCRAPPIE_HIP_COALESCE_TIMES")) fprintf(stderr, "posterior coalescer: %llu launch groups took %.1f ms in all\n", g_co.n_batches, g_co.service_us / 1e3);
-}
-
-extern "C" scrappie_matrix scrappie_hip_trunk(scrappie_hip_engine *e, int model, const raw_table signal, int upto) {
-    Model *m = get_model(e, model);
-    if (!m) return nullptr;
-    (void)hipSetDevice(e->device);
-    std::lock_guard<std::mutex> lk(e->mu);
-    uint64_t off; uint32_t len;
-    if (stage_one(e, signal, off, len)) return nullptr;
-    if (m->arch == 3) len /= (uint32_t)m->nfeat;
-    if (len < m->min_samples) { set_err("read too short"); return nullptr; }
-    scrappie_hip_params p = scrappie_hip_default_params();
-    RunOut ro;
-    if (run_pipeline(e, m, e->d_signal[0].as<float>(), &off, &len, 1, &p, STOP_TRUNK, upto, &ro)) return nullptr;
-    if (read_out_of_range(e)) return nullptr;
-    return gather_to_host(e, ro.act, nullptr, e->lgs[e->cur].rT[0], ro.act_units, ro.act_units / 16, 0, 0, 0.f);
 }
 
 /* ------------------------------------------------------------------ */
@@ -359,10 +314,10 @@ extern "C" int get_raw_model_stride_from_string(const char *modelstr) {      /* 
     return get_raw_model_stride(t);
 }
 
-/* decode_transducer from many host threads at once (the other half of the reference's per-read loop body, scrappie_raw.c:279-287): the calls that are
- * waiting run as one launch -- one workgroup per read, each exactly the single-read form below (a tile whose lanes alias the read's columns), so a call's
- * path and score are the ones it gets alone.  The posteriors are 3.3 MB per read of 4000 samples: every caller copies its own into pinned memory (all at
- * once), one transfer takes them to the device. */
+/* decode_transducer (decode.c:123 on host posteriors; the other half of the reference's per-read loop body, scrappie_raw.c:279-287), from many host threads
+ * at once: the calls that are waiting run as one launch -- one workgroup per read, a tile whose 16 lanes all alias that read's columns (strideB = 0), so a
+ * call's path and score do not depend on its company; a call with the queue off is the same launch with one read.  The posteriors are 3.3 MB per read of
+ * 4000 samples: every caller of the queue copies its own into pinned memory (all at once), one transfer takes them to the device. */
 struct DecReq {
     const_scrappie_matrix post = nullptr;
     float stay_pen = 0.f, skip_pen = 0.f, local_pen = 0.f;
@@ -372,14 +327,13 @@ struct DecReq {
     int phase = 0;                  /* 0 queued, 1 asked to copy its posterior to `dst`, 2 copied, 3 done */
     float *dst = nullptr;
 };
-struct DecCoalescer : ShCoalescer<DecReq> {
-    HBuf stage, hseq;
-    DBuf d[7];
-};
+/* the queue's pinned input buffer: sized by the leader, filled by the members of the launch in preparation (one leader at a time), read by that launch */
+struct DecCoalescer : ShCoalescer<DecReq> { HBuf stage; };
 static DecCoalescer g_dc;
 
-/* the batch's posteriors are in g_dc.stage (concatenated, read k at column offset boff[k]); results into the requests */
-static void decode_batch(scrappie_hip_engine *e, std::vector<DecReq *> &reqs, const std::vector<long long> &boff, long long ncb) {
+/* The requests share shape and penalties.  `staged`: their posteriors concatenated in pinned memory, read k at the column offset the reads before it add up
+ * to (the queue's members have put them there); nullptr: they are copied into the engine's own staging buffer here, under its lock.  Results into the requests. */
+static void decode_batch(scrappie_hip_engine *e, std::vector<DecReq *> &reqs, const float *staged) {
     const size_t n = reqs.size();
     const DecReq *f = reqs[0];
     const int NH = (int)f->post->nr - 1, NQ = NH / 4;
@@ -388,28 +342,36 @@ static void decode_batch(scrappie_hip_engine *e, std::vector<DecReq *> &reqs, co
     std::lock_guard<std::mutex> lk(e->mu);
     hipStream_t s = e->stream;
     const size_t npad = 16 * n;
+    long long ncb = 0;
+    for (const DecReq *r : reqs) ncb += (long long)r->post->nc;
     /* metadata: sig_off[npad] | seq_off[npad] | (unused)[npad] | tile_boff[n] | rN[npad] | rT[npad] | tile_T[n] */
     std::vector<char> hm(npad * 24 + n * 8 + npad * 8 + n * 4, 0);
     long long *seq_off = (long long *)(hm.data() + npad * 8);
     long long *tboff = (long long *)(hm.data() + npad * 24);
     int *rN = (int *)(hm.data() + npad * 24 + n * 8), *rT = rN + npad, *tT = rT + npad;
-    long long nseq = 0;
+    long long nseq = 0, boff = 0;
     for (size_t k = 0; k < n; k++) {
         const int T = (int)reqs[k]->post->nc;
-        tboff[k] = boff[k]; tT[k] = T;
-        /* every lane of the tile reads the same columns (strideB = 0) and runs the read, as in the single-read form; lane 0's path is walked back */
+        tboff[k] = boff; tT[k] = T;
+        /* every lane of the tile reads the same columns (strideB = 0) and runs the read; lane 0's path is walked back */
         for (int b = 0; b < 16; b++) { rN[k * 16 + b] = 1; rT[k * 16 + b] = T; seq_off[k * 16 + b] = nseq; }
-        nseq += T + 1;
+        nseq += T + 1; boff += T;
     }
     /* (grow-only, kept between launches: seven hipMalloc / hipFree pairs per launch cost more than the transfer) */
-    DBuf &dmeta = g_dc.d[0], &dpost = g_dc.d[1], &dtb = g_dc.d[2], &dtbe = g_dc.d[3], &dfs = g_dc.d[4], &dfsc = g_dc.d[5], &dseq = g_dc.d[6];
+    DBuf &dmeta = e->d_dec[0], &dpost = e->d_dec[1], &dtb = e->d_dec[2], &dtbe = e->d_dec[3], &dfs = e->d_dec[4], &dfsc = e->d_dec[5], &dseq = e->d_dec[6];
     bool ok = false;
     do {
         const size_t pbytes = (size_t)ncb * stride * 4;
         if (dmeta.ensure(hm.size()) || dpost.ensure(pbytes) || dtb.ensure((size_t)ncb * NQ * 16 * 4) || dtbe.ensure((size_t)ncb * 16 * 4) ||
-            dfs.ensure(npad * 4) || dfsc.ensure(npad * 4) || dseq.ensure((size_t)nseq * 4) || g_dc.hseq.ensure((size_t)nseq * 4 + npad * 4)) break;
+            dfs.ensure(npad * 4) || dfsc.ensure(npad * 4) || dseq.ensure((size_t)nseq * 4) || e->h_dec_out.ensure((size_t)nseq * 4 + npad * 4)) break;
+        if (!staged) {
+            if (e->h_dec_in.ensure(pbytes)) break;
+            float *h = e->h_dec_in.as<float>();
+            for (size_t k = 0; k < n; k++) memcpy(h + (size_t)tboff[k] * stride, reqs[k]->post->data.f, (size_t)reqs[k]->post->nc * stride * 4);
+            staged = h;
+        }
         if (hipMemcpyAsync(dmeta.p, hm.data(), hm.size(), hipMemcpyHostToDevice, s) != hipSuccess) break;
-        if (hipMemcpyAsync(dpost.p, g_dc.stage.p, pbytes, hipMemcpyHostToDevice, s) != hipSuccess) break;
+        if (hipMemcpyAsync(dpost.p, staged, pbytes, hipMemcpyHostToDevice, s) != hipSuccess) break;
         char *d = dmeta.as<char>();
         ShMeta md;
         md.sig_off = (const unsigned long long *)d;
@@ -430,7 +392,7 @@ static void decode_batch(scrappie_hip_engine *e, std::vector<DecReq *> &reqs, co
         /* lane 0 of every tile: the other lanes hold the same path */
         hipLaunchKernelGGL(k_backtrace_lane0, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, dtb.as<unsigned>(), dtbe.as<int>(), dfs.as<int>(), md,
                            (const long long *)(d + npad * 8), dseq.as<int>(), (int)n, NQ);
-        int *hseq = g_dc.hseq.as<int>();
+        int *hseq = e->h_dec_out.as<int>();
         if (hipMemcpyAsync(hseq, dseq.p, (size_t)nseq * 4, hipMemcpyDeviceToHost, s) != hipSuccess) break;
         if (hipMemcpyAsync(hseq + nseq, dfsc.p, npad * 4, hipMemcpyDeviceToHost, s) != hipSuccess) break;
         if (sh_stream_wait(s) != hipSuccess) break;
@@ -450,29 +412,26 @@ static float coalesced_decode(scrappie_hip_engine *e, const_scrappie_matrix logp
     ShInside inside(g_presence);
     DecReq r;
     r.post = logpost; r.stay_pen = stay_pen; r.skip_pen = skip_pen; r.local_pen = local_pen; r.slip = allow_slip; r.seq = seq;
-    std::vector<long long> boff;
-    long long ncb = 0;
     g_dc.run(r, g_presence, MAX_READS, true,
         [&](std::deque<DecReq *> &q, std::vector<DecReq *> &batch) {
-            const DecReq *f = q.front();
-            boff.clear(); ncb = 0;
-            for (auto it = q.begin(); it != q.end() && batch.size() < MAX_READS;) {
-                DecReq *c = *it;
-                const bool same = c->post->nr == f->post->nr && c->post->stride == f->post->stride && c->stay_pen == f->stay_pen && c->skip_pen == f->skip_pen &&
-                                  c->local_pen == f->local_pen && c->slip == f->slip;
-                if (same && (batch.empty() || ncb + (long long)c->post->nc <= MAX_BLOCKS)) {
-                    batch.push_back(c); boff.push_back(ncb); ncb += (long long)c->post->nc; it = q.erase(it);
-                } else ++it;
-            }
+            take_compatible(q, batch, MAX_READS, MAX_BLOCKS,
+                            [](const DecReq *f, const DecReq *c) {
+                                return c->post->nr == f->post->nr && c->post->stride == f->post->stride && c->stay_pen == f->stay_pen && c->skip_pen == f->skip_pen &&
+                                       c->local_pen == f->local_pen && c->slip == f->slip;
+                            },
+                            [](const DecReq *c) { return (long long)c->post->nc; });
         },
         [&](std::vector<DecReq *> &batch) {      /* every member copies its own posterior into the launch's pinned buffer, all at once */
             const size_t stride = batch[0]->post->stride;
-            if (g_dc.stage.ensure((size_t)ncb * stride * 4) != 0) return false;
-            for (size_t k = 0; k < batch.size(); k++) batch[k]->dst = g_dc.stage.as<float>() + (size_t)boff[k] * stride;
+            size_t ncb = 0;
+            for (const DecReq *c : batch) ncb += c->post->nc;
+            if (g_dc.stage.ensure(ncb * stride * 4) != 0) return false;
+            float *at = g_dc.stage.as<float>();
+            for (DecReq *c : batch) { c->dst = at; at += c->post->nc * stride; }
             return true;
         },
         [](DecReq &c) { memcpy(c.dst, c.post->data.f, (size_t)c.post->nc * c.post->stride * 4); },
-        [&](std::vector<DecReq *> &batch) { decode_batch(e, batch, boff, ncb); });
+        [&](std::vector<DecReq *> &batch) { decode_batch(e, batch, g_dc.stage.as<float>()); });
     return r.score;
 }
 extern "C" void scrappie_hip_decode_coalescer_stats(unsigned long long out[3]) {
@@ -481,8 +440,6 @@ extern "C" void scrappie_hip_decode_coalescer_stats(unsigned long long out[3]) {
     if (getenv("SCRAPPIE_HIP_COALESCE_TIMES")) fprintf(stderr, "decode coalescer: %llu launches took %.1f ms in all\n", g_dc.n_batches, g_dc.service_us / 1e3);
 }
 
-/* decode.c:123 on a host posterior: one read = one tile, every lane of the tile
- * aliases the same column data (strideB = 0). */
 extern "C" float decode_transducer(const_scrappie_matrix logpost, float stay_pen, float skip_pen, float local_pen, int *seq, bool allow_slip) {
     if (!logpost || !seq) return NAN;
     scrappie_hip_engine *e = default_engine();
@@ -491,85 +448,15 @@ extern "C" float decode_transducer(const_scrappie_matrix logpost, float stay_pen
     if (NH % 64 != 0 || (allow_slip && NH % 256 != 0) || T <= 0) return NAN;
     if (NH != 64 && NH != 256 && NH != 1024) return NAN;
     if (coalesce_on('d')) return coalesced_decode(e, logpost, stay_pen, skip_pen, local_pen, seq, allow_slip);
-    (void)hipSetDevice(e->device);
-    std::lock_guard<std::mutex> lk(e->mu);
-    hipStream_t s = e->stream;
-    const int NQ = NH / 4;
-    const size_t pbytes = (size_t)T * logpost->stride * 4;
-    /* metadata for one tile whose 16 lanes all run the same read */
-    const size_t npad = 16;
-    std::vector<char> hm(npad * 8 * 3 + 8 + npad * 4 * 2 + 4, 0);
-    long long *seq_off = (long long *)(hm.data() + npad * 8);
-    int *rN = (int *)(hm.data() + npad * 24 + 8), *rT = rN + npad, *tT = rT + npad;
-    for (size_t i = 0; i < npad; i++) { rN[i] = 1; rT[i] = T; seq_off[i] = 0; }
-    *tT = T;
-    DBuf dmeta, dpost, dtb, dtbe, dfs, dfsc, dseq;
-    float score = NAN;
-    do {
-        if (dmeta.ensure(hm.size()) || dpost.ensure(pbytes) || dtb.ensure((size_t)T * NQ * 16 * 4) || dtbe.ensure((size_t)T * 16 * 4) ||
-            dfs.ensure(64) || dfsc.ensure(64) || dseq.ensure(((size_t)T + 1) * 4)) break;
-        if (hipMemcpyAsync(dmeta.p, hm.data(), hm.size(), hipMemcpyHostToDevice, s) != hipSuccess) break;
-        if (hipMemcpyAsync(dpost.p, logpost->data.f, pbytes, hipMemcpyHostToDevice, s) != hipSuccess) break;
-        char *d = dmeta.as<char>();
-        ShMeta md;
-        md.sig_off = (const unsigned long long *)d;
-        md.tile_boff = (const long long *)(d + npad * 24);
-        md.rN = (const int *)(d + npad * 24 + 8);
-        md.rT = md.rN + npad;
-        md.tile_T = md.rT + npad;
-        ShVitArgs va;
-        va.E = dpost.as<float>(); va.sums = nullptr;
-        va.strideT = (long long)logpost->stride; va.strideQ = 4; va.strideB = 0;
-        va.want_log = 0; va.min_prob = 0.f;
-        va.stay_pen = stay_pen; va.skip_pen = skip_pen; va.local_pen = local_pen; va.use_slip = allow_slip ? 1 : 0;
-        va.tb = dtb.as<unsigned>(); va.tb_end = dtbe.as<int>();
-        va.final_state = dfs.as<int>(); va.final_score = dfsc.as<float>();
-        va.hp_side = nullptr; va.hp_off = nullptr; va.dbg = nullptr; va.dump_final = 0;
-        va.seg = nullptr; va.vstate = nullptr; va.flag = nullptr; va.err = nullptr;   /* one workgroup, the whole tile */
-        if (launch_viterbi(s, NH, va, md, 1)) break;
-        hipLaunchKernelGGL(k_backtrace, dim3(1), dim3(64), 0, s, dtb.as<unsigned>(), dtbe.as<int>(), dfs.as<int>(), md,
-                           (const long long *)(d + npad * 8), dseq.as<int>(), 1, NQ, 1);
-        if (hipMemcpyAsync(seq, dseq.p, ((size_t)T + 1) * 4, hipMemcpyDeviceToHost, s) != hipSuccess) break;
-        float sc = NAN;
-        if (hipMemcpyAsync(&sc, dfsc.p, 4, hipMemcpyDeviceToHost, s) != hipSuccess) break;
-        if (sh_stream_wait(s) != hipSuccess) break;
-        score = sc;
-    } while (0);
-    for (DBuf *b : {&dmeta, &dpost, &dtb, &dtbe, &dfs, &dfsc, &dseq}) b->release();
-    return score;
+    DecReq r;
+    r.post = logpost; r.stay_pen = stay_pen; r.skip_pen = skip_pen; r.local_pen = local_pen; r.slip = allow_slip; r.seq = seq;
+    std::vector<DecReq *> one{&r};
+    decode_batch(e, one, nullptr);
+    return r.score;
 }
 
-/* decode.c:836 on a host transition matrix.  The kernel works on the chunked
- * layout, so the 25 rows are re-laid on the host first. */
-__global__ void k_crf_viterbi_only(const float *__restrict__ trans, int stride, int T, unsigned *__restrict__ tbbuf,
-                                   int *__restrict__ path, float *__restrict__ score) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    float prev[5] = {0.f, 0.f, 0.f, 0.f, 0.f}, curr[5];
-    for (int t = 0; t < T; t++) {
-        const float *tr = trans + (long long)t * stride;
-        unsigned pack = 0;
-        for (int to = 0; to < 5; to++) {
-            float best = tr[to * 5] + prev[0];
-            unsigned from = 0;
-            for (int fr = 1; fr < 5; fr++) {
-                const float sc = tr[to * 5 + fr] + prev[fr];
-                if (sc > best) { best = sc; from = fr; }
-            }
-            curr[to] = best;
-            pack |= from << (3 * to);
-        }
-        tbbuf[t] = pack;
-        for (int i = 0; i < 5; i++) prev[i] = curr[i];
-    }
-    float best = prev[0];
-    int arg = 0;
-    for (int i = 1; i < 5; i++) if (prev[i] > best) { best = prev[i]; arg = i; }
-    *score = best;
-    path[T] = arg;
-    for (int blk = T; blk > 0; blk--) { arg = (tbbuf[blk - 1] >> (3 * arg)) & 7u; path[blk - 1] = arg; }
-}
-
-/* the same recursion for many reads at once, a thread per read (decode_crf from many host threads: coalesced like decode_transducer) */
+/* decode_crf (decode.c:836 on host transition matrices): the serial recursion of a read on one thread, a thread per read -- the waiting calls of many host
+ * threads in one launch (coalesced like decode_transducer), or one call with the queue off */
 __global__ void k_crf_viterbi_batch(const float *__restrict__ trans, int stride, const long long *__restrict__ coff, const int *__restrict__ Ts, int n,
                                     unsigned *__restrict__ tbbuf, int *__restrict__ path, float *__restrict__ score) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -604,11 +491,7 @@ __global__ void k_crf_viterbi_batch(const float *__restrict__ trans, int stride,
 }
 
 struct CrfReq { const_scrappie_matrix trans = nullptr; int *path = nullptr; float score = NAN; int phase = 0; };
-struct CrfCoalescer : ShCoalescer<CrfReq> {
-    HBuf hin, hout;
-    DBuf d[4];
-};
-static CrfCoalescer g_cc;
+static ShCoalescer<CrfReq> g_cc;
 
 static void crf_batch(scrappie_hip_engine *e, std::vector<CrfReq *> &reqs) {
     const size_t n = reqs.size(), stride = reqs[0]->trans->stride;
@@ -618,12 +501,12 @@ static void crf_batch(scrappie_hip_engine *e, std::vector<CrfReq *> &reqs) {
     const size_t fbytes = (size_t)ncol * stride * 4, in_bytes = fbytes + n * 8 + n * 4;
     (void)hipSetDevice(e->device);
     std::lock_guard<std::mutex> lk(e->mu);
-    DBuf &din = g_cc.d[0], &dtb = g_cc.d[1], &dpath = g_cc.d[2], &dsc = g_cc.d[3];
+    DBuf &din = e->d_crf[0], &dtb = e->d_crf[1], &dpath = e->d_crf[2], &dsc = e->d_crf[3];
     bool ok = false;
     do {
-        if (g_cc.hin.ensure(in_bytes) || g_cc.hout.ensure(((size_t)ncol + n) * 4 + n * 4) || din.ensure(in_bytes) || dtb.ensure((size_t)ncol * 4) ||
+        if (e->h_crf_in.ensure(in_bytes) || e->h_crf_out.ensure(((size_t)ncol + n) * 4 + n * 4) || din.ensure(in_bytes) || dtb.ensure((size_t)ncol * 4) ||
             dpath.ensure(((size_t)ncol + n) * 4) || dsc.ensure(n * 4)) break;
-        char *h = g_cc.hin.as<char>();
+        char *h = e->h_crf_in.as<char>();
         long long *coff = (long long *)(h + fbytes);
         int *Ts = (int *)(h + fbytes + n * 8);
         long long c = 0;
@@ -637,7 +520,7 @@ static void crf_batch(scrappie_hip_engine *e, std::vector<CrfReq *> &reqs) {
         const char *d = din.as<char>();
         hipLaunchKernelGGL(k_crf_viterbi_batch, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, (const float *)d, (int)stride, (const long long *)(d + fbytes),
                            (const int *)(d + fbytes + n * 8), (int)n, dtb.as<unsigned>(), dpath.as<int>(), dsc.as<float>());
-        int *hp = g_cc.hout.as<int>();
+        int *hp = e->h_crf_out.as<int>();
         if (hipMemcpyAsync(hp, dpath.p, ((size_t)ncol + n) * 4, hipMemcpyDeviceToHost, s) != hipSuccess) break;
         if (hipMemcpyAsync(hp + ncol + n, dsc.p, n * 4, hipMemcpyDeviceToHost, s) != hipSuccess) break;
         if (sh_stream_wait(s) != hipSuccess) break;
@@ -659,13 +542,8 @@ static float coalesced_decode_crf(scrappie_hip_engine *e, const_scrappie_matrix 
     r.trans = trans; r.path = path;
     g_cc.run(r, g_presence, MAX_READS, false,
         [&](std::deque<CrfReq *> &q, std::vector<CrfReq *> &batch) {
-            long long cols = 0;
-            const size_t stride = q.front()->trans->stride;
-            for (auto it = q.begin(); it != q.end() && batch.size() < MAX_READS;) {
-                CrfReq *c = *it;
-                if (c->trans->stride == stride && (batch.empty() || cols + (long long)c->trans->nc <= MAX_COLS)) { batch.push_back(c); cols += (long long)c->trans->nc; it = q.erase(it); }
-                else ++it;
-            }
+            take_compatible(q, batch, MAX_READS, MAX_COLS, [](const CrfReq *f, const CrfReq *c) { return c->trans->stride == f->trans->stride; },
+                            [](const CrfReq *c) { return (long long)c->trans->nc; });
         },
         [](std::vector<CrfReq *> &) { return true; }, [](CrfReq &) {},
         [&](std::vector<CrfReq *> &batch) { crf_batch(e, batch); });
@@ -682,23 +560,9 @@ extern "C" float decode_crf(const_scrappie_matrix trans, int *path) {
     scrappie_hip_engine *e = default_engine();
     if (!e) return NAN;
     if (coalesce_on('d')) return coalesced_decode_crf(e, trans, path);
-    (void)hipSetDevice(e->device);
-    std::lock_guard<std::mutex> lk(e->mu);
-    const int T = (int)trans->nc;
-    DBuf dtr, dtb, dpath, dsc;
-    float score = NAN;
-    do {
-        const size_t bytes = (size_t)T * trans->stride * 4;
-        if (dtr.ensure(bytes) || dtb.ensure((size_t)T * 4) || dpath.ensure(((size_t)T + 1) * 4) || dsc.ensure(4)) break;
-        if (hipMemcpyAsync(dtr.p, trans->data.f, bytes, hipMemcpyHostToDevice, e->stream) != hipSuccess) break;
-        hipLaunchKernelGGL(k_crf_viterbi_only, dim3(1), dim3(64), 0, e->stream, dtr.as<float>(), (int)trans->stride, T, dtb.as<unsigned>(),
-                           dpath.as<int>(), dsc.as<float>());
-        float sc = NAN;
-        if (hipMemcpyAsync(path, dpath.p, ((size_t)T + 1) * 4, hipMemcpyDeviceToHost, e->stream) != hipSuccess) break;
-        if (hipMemcpyAsync(&sc, dsc.p, 4, hipMemcpyDeviceToHost, e->stream) != hipSuccess) break;
-        if (sh_stream_wait(e->stream) != hipSuccess) break;
-        score = sc;
-    } while (0);
-    for (DBuf *b : {&dtr, &dtb, &dpath, &dsc}) b->release();
-    return score;
+    CrfReq r;
+    r.trans = trans; r.path = path;
+    std::vector<CrfReq *> one{&r};
+    crf_batch(e, one);
+    return r.score;
 }

@@ -32,10 +32,7 @@ static std::vector<uint32_t> g_stage;          /* the two-phase queue's staging 
 static std::atomic<unsigned long long> g_served{0};
 
 static void take_same_kind(std::deque<Req *> &q, std::vector<Req *> &batch, size_t max_reqs) {
-    const int kind = q.front()->kind;
-    for (auto it = q.begin(); it != q.end() && batch.size() < max_reqs;) {
-        if ((*it)->kind == kind) { batch.push_back(*it); it = q.erase(it); } else ++it;
-    }
+    take_compatible(q, batch, max_reqs, (size_t)-1, [](const Req *f, const Req *c) { return c->kind == f->kind; }, [](const Req *) { return (size_t)0; });
 }
 
 static uint64_t call_plain(Req &r) {

@@ -1660,6 +1660,22 @@ def test_per_read_calls_from_many_threads_share_launch_groups(models):
 
 
 @pytest.mark.gpu
+def test_explicit_engine_and_default_engine_posteriors_are_the_same_bits(eng, models):
+    """scrappie_hip_posterior on an explicit engine (Engine.posterior: a batch of one, no queue) and the reference's per-read function on the
+    process-default engine (calc_post: the same batch function behind the queue) are one code path reached two ways: on the same weights they
+    return the same bits -- two transducers and the CRF model, log and probability outputs, lengths from the model's minimum up."""
+    for name in ("rgrgr_r94", "rgrgr_r10", "rnnrf_r94"):
+        for k, n in enumerate((eng.min_samples(name), 303, 2003, 6001)):
+            x = sig(n, 7300 + k)
+            for log, mp in ((True, 1e-5), (False, 1e-3)):
+                if name == "rnnrf_r94" and not log:
+                    continue
+                a = eng.posterior(x, name, min_prob=mp, log=log)
+                b = sa.calc_post(sa.RawTable(x), name, min_prob=mp, log=log).data(as_numpy=True, sloika=False)
+                assert a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32)), (name, n, log)
+
+
+@pytest.mark.gpu
 def test_per_read_decode_from_many_threads_is_the_single_read_decode(models, orc):
     """decode_transducer (decode.h:13) from many host threads at once runs as one launch, one workgroup per call: path and score of every call are the
     ones it gets alone, and the oracle's (decode.c:123-365 restated) -- posteriors of different lengths, two parameter sets, 3-mer and 5-mer models."""

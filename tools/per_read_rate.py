@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Rate of the per-read reference surface (nanonet_rgrgr_r94_posterior: one read per call, a host matrix per call) driven from
-T host threads, as the reference's OpenMP loop drives it (scrappie_raw.c:355,387).  SCRAPPIE_HIP_COALESCE=0: every call alone.
+T host threads, as the reference's OpenMP loop drives it (scrappie_raw.c:355,387).  SCRAPPIE_HIP_COALESCE=0: no queue, every call a batch of one.
 usage: python tools/per_read_rate.py [threads] [reads] [samples]"""
 import ctypes as C, os, sys, tempfile, time
 from concurrent.futures import ThreadPoolExecutor
