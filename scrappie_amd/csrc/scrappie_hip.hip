@@ -25,18 +25,18 @@
  *
  * The translation unit in parts (round 5; the kernels are templates in headers and are instantiated where they are launched, so
  * the engine stays ONE translation unit -- the parts are files of their own for reading, included below in this order):
- *   this file            switches, the engine's state, create / destroy
+ *   this file            switches, the engine's state (struct Slot: what exists once per launch group in flight), create / destroy
  *   sh_eng_weights.inc   weights as the device wants them; the Model
  *   sh_eng_load.inc      .scrm container -> Model, settings, the ABI's planning functions
  *   sh_eng_launch.inc    launch-group construction, kernel dispatch helpers
- *   sh_eng_pipeline.inc  run_pipeline: one launch group through its kernels
+ *   sh_eng_pipeline.inc  run_pipeline: one launch group through its kernels, a function per stage
  *   sh_eng_groups.inc    run_device / collect / stitching, a call cut into launch groups
  *   sh_eng_batch.inc     helper engine for chain-bound reads, host-signal entry points, several GPUs
  *   sh_eng_debug.inc     measurement / test hooks
  *   sh_eng_surface.inc   the reference's per-read functions: one batch function per family, run by the queue or with a batch of one
  *   sh_eng_map.inc       block-based mapping of posteriors to sequences (per-read and batched)
  * Separate translation units: sh_p0.hip (signal preparation, k_p0), sh_host.c / sh_fast5.c / sh_h5mini.c (host C);
- * sh_coalesce.h (the per-read functions' queue) and sh_dev.h are plain C++ headers.
+ * sh_coalesce.h (the per-read functions' queue) and sh_dev.h (DBuf / HBuf: buffers that own their memory) are plain C++ headers.
  */
 #include <hip/hip_runtime.h>
 #include <sched.h>
@@ -221,66 +221,107 @@ struct BatchCoalescer : ShCoalescer<BatchReq> { BatchCoalescer() { target_pct = 
  * (all at once) and counts itself off `users`; the buffer is written again only when nobody is left (sh_eng_surface.inc) */
 struct PostStage { HBuf h; DBuf d; std::atomic<int> users{0}; };
 
+/* fields of scrappie_hip_timing (and two figures of SH_HOST_STAMP) that a span between two profiling marks adds to: resolve_spans (sh_eng_load.inc) */
+enum SpanField { F_CONV = 0, F_AFFINE, F_GRU, F_FF, F_DECODE, F_BACKTRACE, F_TOTAL, F_FUSED, F_STITCH,
+                 F_WAIT, F_LEAD,      /* how long the main stream waited for the prologue; how long before that the convolution had ended */
+                 F_COUNT };
+
+/* Everything that exists once per launch group in flight.  The engine keeps two, so group k+1 can be enqueued while the host is still stitching
+ * group k: its metadata, staged signals, convolution output, the device buffers the host reads back (a second stream copies them out while the
+ * next group computes) and their pinned twins, its completion events and its profiling marks.  What is NOT here is shared by the two groups
+ * (scrappie_hip_engine, "shared between the slots"). */
+struct Slot {
+    LaunchGroup lg;
+    bool pending = false;            /* taken: from run_pipeline until scrappie_hip_collect picks the group up */
+    /* profiling: events are only RECORDED while a launch group runs (no host synchronisation inside the timed region); elapsed times are
+     * read back by resolve_spans after the group's done event */
+    hipEvent_t ev[48] = {};
+    int nev = 0;                     /* events of ev[] the group has recorded */
+    struct Span { int field, i, j; };
+    std::vector<Span> spans;
+    scrappie_hip_timing timing{};
+    hipEvent_t done = nullptr;       /* results are in pinned memory (cstream) */
+    hipEvent_t kdone = nullptr;      /* kernels of the slot finished (stream) -> copies may start (cstream) */
+    hipEvent_t hdone = nullptr;      /* traceback walk + k_stitch of the slot finished (cstream) */
+    hipEvent_t pdone = nullptr;      /* prologue finished (pstream) -> the main stream may go on */
+    hipEvent_t up = nullptr;         /* upload into d_signal finished */
+    DBuf d_meta, d_signal, d_gflag;
+    DBuf d_conv;                     /* convolution output (the layers' ping-pong buffers belong to the group that is running) */
+    DBuf d_bad;                      /* [npad]: read whose input left the split products' operand range (k_conv_act, k_feat_in) */
+    DBuf d_edge;                     /* k_gru_conv: where each read's convolution windows end (ShConvFuse::edge) */
+    DBuf d_fscore, d_seq, d_hp;
+    DBuf d_pos, d_bases, d_blen, d_redo;     /* k_stitch: pos / bases / lengths / host-decides flags */
+    HBuf h_meta, h_sig, h_err, h_bad, h_edge, h_seq, h_score, h_hp, h_pos, h_bases, h_blen, h_redo;
+    size_t pinned_bytes() const {
+        size_t tot = 0;
+        for (const HBuf *h : {&h_meta, &h_sig, &h_err, &h_bad, &h_edge, &h_seq, &h_score, &h_hp, &h_pos, &h_bases, &h_blen, &h_redo}) tot += h->cap;
+        return tot;
+    }
+    bool create_events() {
+        bool ok = true;
+        for (auto &x : ev) ok &= hipEventCreate(&x) == hipSuccess;
+        for (hipEvent_t *x : {&done, &kdone, &hdone, &pdone, &up}) ok &= hipEventCreateWithFlags(x, hipEventDisableTiming) == hipSuccess;
+        return ok;
+    }
+    ~Slot() {      /* (with the engine: its device current, its streams drained) */
+        for (auto &x : ev) if (x) (void)hipEventDestroy(x);
+        for (hipEvent_t x : {done, kdone, hdone, pdone, up}) if (x) (void)hipEventDestroy(x);
+    }
+};
+
+/* Caller-supplied data in place of a stage's output (measurement / test hooks, set while nothing is in flight): where each read of a call starts in
+ * it, and what its image in a launch group's layout was last built for -- once per launch-group shape (inject_alt, sh_eng_pipeline.inc). */
+struct AltInput {
+    const float *data = nullptr;
+    std::vector<uint64_t> off;
+    DBuf d_off;
+    uint64_t key = 0; bool valid = false;
+    explicit operator bool() const { return data != nullptr; }
+    int set(const char *who, const float *d, const uint64_t *o, size_t n) {
+        valid = false;
+        if (!d) { data = nullptr; off.clear(); return 0; }
+        if (!o || n == 0) return set_err("%s: no offsets", who);
+        data = d; off.assign(o, o + n);
+        return 0;
+    }
+};
+
 struct scrappie_hip_engine {
     int device = 0;
     hipStream_t stream = nullptr;
     hipStream_t cstream = nullptr;   /* results -> host, so that the copy overlaps the next group's kernels */
     hipStream_t ustream = nullptr;   /* host signals -> device (scrappie_hip_basecall_batch), same reason */
     hipStream_t pstream = nullptr;   /* prologue of a launch group: metadata upload, flag clears, convolution -- runs under the PREVIOUS group's
-                                        recurrent layers (k_conv_act fits beside k_gru_proj's waves), the main stream waits for pdone[slot] */
-    hipEvent_t pdone[2];
-    DBuf d_conv[2];                  /* convolution output per slot (the layers' ping-pong buffers belong to the group that is running) */
-    hipEvent_t up[2];                /* upload into d_signal[k] finished */
+                                        recurrent layers (k_conv_act fits beside k_gru_proj's waves), the main stream waits for the slot's pdone */
     size_t total_mem = (size_t)64 << 30;
     size_t max_launch_blocks = 0;    /* column blocks (16 reads x 1 block) per launch group; 0 = from device memory */
     std::vector<Model *> models;
     size_t max_launch_reads = 16384;
     bool profiling = false;
     scrappie_hip_timing timing{};
-    /* profiling: events are only RECORDED while a launch group runs (no host
-     * synchronisation inside the timed region); elapsed times are read back in
-     * scrappie_hip_get_timing after the stream has drained. */
-    /* Two launch-group slots: group k+1 can be enqueued while the host is still
-     * stitching group k (its metadata, pinned result buffers, completion event and
-     * profiling events are per slot, and so are the device buffers the host reads back, which a
-     * second stream copies out while the next group computes; all other device buffers are shared,
-     * ordered by the stream). */
-    hipEvent_t ev[2][48];
-    hipEvent_t done[2];
-    hipEvent_t kdone[2];         /* kernels of the slot finished (stream) -> copies may start (cstream) */
-    hipEvent_t hdone[2];         /* traceback walk + k_stitch of the slot finished (cstream) */
     bool ev_ok = false;
-    int evn = 0;
-    struct Span { int field, i, j; };
-    std::vector<Span> spans[2];
+    Slot slots[2];               /* the two launch groups in flight */
     int cur = 0;                 /* slot of the most recent run_pipeline */
-    bool pending[2] = {false, false};
     int oldest = 0;              /* next slot collect() will take */
-    /* arena */
-    DBuf d_hstate, d_gflag[2], d_vstate, d_vflag;
-    DBuf d_bad[2];                /* [npad] per slot: read whose input left the split products' operand range (k_conv_act, k_feat_in) */
-    HBuf h_err[2], h_bad[2];
-    DBuf d_pos[2], d_bases[2], d_blen[2], d_redo[2];     /* k_stitch: pos / bases / lengths / host-decides flags per slot */
-    DBuf d_edge[2]; HBuf h_edge[2];                      /* k_gru_conv: where each read's convolution windows end (ShConvFuse::edge) */
-    HBuf h_pos[2], h_bases[2], h_blen[2], h_redo[2];
+    Slot &current() { return slots[cur]; }
+    Slot &other(const Slot &sl) { return slots[&sl == &slots[0] ? 1 : 0]; }
+    int index(const Slot &sl) const { return (int)(&sl - slots); }
+    bool any_pending() const { return slots[0].pending || slots[1].pending; }
+    void drain() {                /* after a failure: nothing left in flight, nothing left to collect */
+        (void)sh_stream_wait(pstream); (void)sh_stream_wait(stream); (void)sh_stream_wait(cstream);
+        slots[0].pending = slots[1].pending = false;
+    }
+    /* shared between the slots: the buffers only the kernels of ONE group touch at a time.  The main stream runs the groups' kernels one group
+     * after the other, which orders the layers' buffers (d_act[1..2], d_xaff), S1's (d_E, d_sums) and the hand-over state (d_hstate, d_vstate,
+     * d_vflag).  The traceback (d_tb, d_tbend, d_fstate) is read by the walk back on the copy stream: a group's decoder waits for the other
+     * slot's done event before it overwrites them (run_pipeline).  The alt_* images further down belong to hooks that run with nothing in flight. */
+    DBuf d_hstate, d_vstate, d_vflag;
+    DBuf d_act[3];                /* ([0] is unused: the convolution's output is the slot's d_conv) */
+    DBuf d_xaff, d_E, d_sums, d_tb, d_tbend, d_fstate;
     int ncu = 256;
     bool handover = true;         /* cut tiles between lanes / into pieces (SCRAPPIE_HIP_HANDOVER=0: whole tiles only) */
-    DBuf d_meta[2], d_signal[2], d_act[3], d_xaff, d_E, d_sums, d_tb, d_tbend, d_fstate, d_fscore[2], d_seq[2], d_hp[2];
-    HBuf h_meta[2], h_seq[2], h_score[2], h_hp[2], h_sig[2];
-    LaunchGroup lgs[2];
-    scrappie_hip_timing slot_timing[2];
-    /* scrappie_hip_set_decoder_input: caller-supplied probabilities in place of the S1 output */
-    const float *alt_prob = nullptr;
-    std::vector<uint64_t> alt_off;
-    DBuf d_Ealt, d_sums_alt, d_altoff;
-    uint64_t alt_key = 0;
-    bool alt_valid = false;
-    /* scrappie_hip_set_trunk_input: caller-supplied trunk activations in front of S1 */
-    const float *alt_trunk = nullptr;
-    std::vector<uint64_t> trk_off;
-    DBuf d_act_alt, d_trkoff;
-    uint64_t trk_key = 0;
-    bool trk_valid = false;
+    AltInput alt_prob; DBuf d_Ealt, d_sums_alt;      /* scrappie_hip_set_decoder_input: probabilities in place of the S1 output, their decoder image */
+    AltInput alt_trunk; DBuf d_act_alt;              /* scrappie_hip_set_trunk_input: trunk activations in front of S1, their chunk-layout image */
     /* scrappie_hip_debug_option */
     bool dbg_ff_separate = false;    /* S1 and the decoder as two kernels (as SH_FF_SEPARATE, per engine) */
     bool dbg_fv_single = false;      /* S1 inside the decoder on k_ff_viterbi's eight do-everything waves (as SH_FV_SINGLE, per engine) */
@@ -339,6 +380,11 @@ struct scrappie_hip_engine {
     DBuf d_map[10]; HBuf h_map;      /* block-based mapping (sh_eng_map.inc): per-read tables, codes, bands, traceback, scratch, scores, paths, posterior */
     double map_ms[3] = {0, 0, 0};    /* scrappie_hip_map_batch: network + S1, k_map, k_map_walk + results, summed over the last call's launch groups */
     std::mutex call_mu;              /* scrappie_hip_basecall_batch: one call at a time inside the engine (concurrent small calls share one: sh_eng_batch.inc) */
+    /* (scrappie_hip_engine_destroy has made the device current and drained the streams; the slots and the buffers go after this body) */
+    ~scrappie_hip_engine() {
+        for (Model *m : models) delete m;
+        for (hipStream_t st : {stream, cstream, ustream, pstream}) if (st) (void)hipStreamDestroy(st);
+    }
 };
 
 static int pick_mt(int mtiles) {
@@ -427,12 +473,7 @@ extern "C" scrappie_hip_engine *scrappie_hip_engine_create(int device) {
         return nullptr;
     }
     e->ev_ok = true;
-    for (auto &row : e->ev) for (auto &x : row) if (hipEventCreate(&x) != hipSuccess) e->ev_ok = false;
-    for (auto &x : e->done) if (hipEventCreateWithFlags(&x, hipEventDisableTiming) != hipSuccess) e->ev_ok = false;
-    for (auto &x : e->kdone) if (hipEventCreateWithFlags(&x, hipEventDisableTiming) != hipSuccess) e->ev_ok = false;
-    for (auto &x : e->hdone) if (hipEventCreateWithFlags(&x, hipEventDisableTiming) != hipSuccess) e->ev_ok = false;
-    for (auto &x : e->pdone) if (hipEventCreateWithFlags(&x, hipEventDisableTiming) != hipSuccess) e->ev_ok = false;
-    for (auto &x : e->up) if (hipEventCreateWithFlags(&x, hipEventDisableTiming) != hipSuccess) e->ev_ok = false;
+    for (Slot &sl : e->slots) if (!sl.create_events()) e->ev_ok = false;
     return e;
 }
 
@@ -450,30 +491,8 @@ extern "C" void scrappie_hip_engine_destroy(scrappie_hip_engine *e) {
     if (e->tail) { scrappie_hip_engine_destroy(e->tail); e->tail = nullptr; }
     if (e->tail2) { scrappie_hip_engine_destroy(e->tail2); e->tail2 = nullptr; }
     (void)hipSetDevice(e->device);
-    (void)sh_stream_wait(e->stream);
-    if (e->cstream) (void)sh_stream_wait(e->cstream);
-    if (e->ustream) (void)sh_stream_wait(e->ustream);
-    if (e->pstream) (void)sh_stream_wait(e->pstream);
-    for (Model *m : e->models) { m->release(); delete m; }
-    for (DBuf *b : {&e->d_meta[0], &e->d_meta[1], &e->d_signal[0], &e->d_signal[1], &e->d_act[0], &e->d_act[1], &e->d_act[2], &e->d_xaff, &e->d_E, &e->d_sums,
-                    &e->d_tb, &e->d_tbend, &e->d_fstate, &e->d_fscore[0], &e->d_seq[0], &e->d_hp[0], &e->d_fscore[1], &e->d_seq[1], &e->d_hp[1],
-                    &e->d_hstate, &e->d_gflag[0], &e->d_gflag[1], &e->d_vstate, &e->d_vflag, &e->d_Ealt, &e->d_sums_alt, &e->d_altoff, &e->d_act_alt, &e->d_trkoff, &e->d_bad[0], &e->d_bad[1], &e->d_conv[0], &e->d_conv[1],
-                    &e->d_edge[0], &e->d_edge[1], &e->d_pos[0], &e->d_pos[1], &e->d_bases[0], &e->d_bases[1], &e->d_blen[0], &e->d_blen[1], &e->d_redo[0], &e->d_redo[1]}) b->release();
-    for (int k = 0; k < 2; k++) for (HBuf *b : {&e->h_meta[k], &e->h_seq[k], &e->h_score[k], &e->h_hp[k], &e->h_pos[k], &e->h_bases[k], &e->h_blen[k], &e->h_redo[k]}) b->release();
-    e->h_edge[0].release(); e->h_edge[1].release();
-    for (DBuf &b : e->d_map) b.release();
-    e->h_map.release();
-    for (PostStage &ps : e->post_stage) { ps.h.release(); ps.d.release(); }
-    for (DBuf &b : e->d_dec) b.release();
-    for (DBuf &b : e->d_crf) b.release();
-    for (HBuf *b : {&e->h_dec_in, &e->h_dec_out, &e->h_crf_in, &e->h_crf_out}) b->release();
-    e->h_sig[0].release(); e->h_sig[1].release(); e->h_err[0].release(); e->h_err[1].release(); e->h_bad[0].release(); e->h_bad[1].release();
-    if (e->ev_ok) { for (auto &row : e->ev) for (auto &x : row) (void)hipEventDestroy(x); for (auto &x : e->done) (void)hipEventDestroy(x); for (auto &x : e->kdone) (void)hipEventDestroy(x); for (auto &x : e->hdone) (void)hipEventDestroy(x); for (auto &x : e->pdone) (void)hipEventDestroy(x); for (auto &x : e->up) (void)hipEventDestroy(x); }
-    (void)hipStreamDestroy(e->stream);
-    if (e->cstream) (void)hipStreamDestroy(e->cstream);
-    if (e->ustream) (void)hipStreamDestroy(e->ustream);
-    if (e->pstream) (void)hipStreamDestroy(e->pstream);
-    delete e;
+    for (hipStream_t st : {e->stream, e->cstream, e->ustream, e->pstream}) if (st) (void)sh_stream_wait(st);
+    delete e;      /* (events, streams, models and every buffer: ~scrappie_hip_engine, ~Slot, ~DBuf / ~HBuf) */
 }
 
 extern "C" scrappie_hip_params scrappie_hip_default_params(void) {
@@ -486,7 +505,7 @@ extern "C" scrappie_hip_params scrappie_hip_default_params(void) {
 
 #include "sh_eng_load.inc"      /* the .scrm container -> Model, engine settings, the planning functions of the ABI */
 #include "sh_eng_launch.inc"      /* launch-group construction (tiles, metadata, schedules) and the kernel dispatch helpers */
-#include "sh_eng_pipeline.inc"      /* run_pipeline: one launch group through its kernels */
+#include "sh_eng_pipeline.inc"      /* run_pipeline: one launch group through its kernels, a function per stage */
 #include "sh_eng_groups.inc"      /* run_device / collect / stitching, a call cut into launch groups, device-resident entry points */
 #include "sh_eng_batch.inc"      /* chain-bound reads on a helper engine, host-signal entry points, several GPUs */
 #include "sh_eng_debug.inc"      /* measurement / test hooks: decoder and trunk inputs, debug_option / debug_fetch / debug_stitch */

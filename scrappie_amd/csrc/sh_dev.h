@@ -1,5 +1,5 @@
 /* sh_dev.h -- what the HIP translation units of libscrappie_hip.so share (not part of the ABI): the error text behind
- * scrappie_hip_last_error(), HIPCHK, grow-only device and pinned host buffers. */
+ * scrappie_hip_last_error(), HIPCHK, grow-only device and pinned host buffers that own their memory. */
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdarg>
@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <ctime>
+#include <utility>
 #include "sh_numa.h"
 
 int sh_set_err_v(const char *fmt, va_list ap);      /* scrappie_hip.hip: thread-local text; returns -1 */
@@ -50,9 +51,15 @@ static inline hipError_t sh_stream_wait(hipStream_t s) {
     for (;;) { const hipError_t r = hipStreamQuery(s); if (r != hipErrorNotReady) return sh_wait_done(r); nanosleep(&nap, nullptr); }
 }
 
-struct DBuf {   /* device buffer, grow-only */
+/* device buffer, grow-only.  Owns its memory: move-only, freed by the destructor -- on whichever device is current then, so an owner sets its device
+ * (and drains its streams) before it lets go.  No object with static storage may hold one: its destructor would call HIP while the process exits. */
+struct DBuf {
     void *p = nullptr;
     size_t cap = 0;
+    DBuf() = default;
+    DBuf(DBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }      /* (move-only: no copies) */
+    DBuf &operator=(DBuf &&o) noexcept { if (this != &o) { release(); std::swap(p, o.p); std::swap(cap, o.cap); } return *this; }
+    ~DBuf() { release(); }
     int ensure(size_t bytes) {
         if (bytes <= cap) return 0;
         if (p) (void)hipFree(p);
@@ -70,9 +77,14 @@ struct DBuf {   /* device buffer, grow-only */
     template <typename T> T *as() const { return (T *)p; }
 };
 
-struct HBuf {   /* pinned host buffer, grow-only */
+/* pinned host buffer, grow-only; owns its memory like DBuf */
+struct HBuf {
     void *p = nullptr;
     size_t cap = 0;
+    HBuf() = default;
+    HBuf(HBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }      /* (move-only: no copies) */
+    HBuf &operator=(HBuf &&o) noexcept { if (this != &o) { release(); std::swap(p, o.p); std::swap(cap, o.cap); } return *this; }
+    ~HBuf() { release(); }
     int ensure(size_t bytes) {
         if (bytes <= cap) return 0;
         if (p) (void)hipHostFree(p);

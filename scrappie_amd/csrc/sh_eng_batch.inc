@@ -466,12 +466,13 @@ static int basecall_batch_one(scrappie_hip_engine *e, int model, const raw_table
     bool used[2] = {false, false};
     return run_groups(e, model, m, len.data(), n, p, out, [&](int k, const uint32_t *idx, size_t cnt, GroupArgs &a) {
         /* staging buffer k was last read by the upload of group g-2 */
-        if (used[k] && e->ev_ok) HIPCHK(sh_event_wait(e->up[k]));
+        Slot &st = e->slots[k];
+        if (used[k] && e->ev_ok) HIPCHK(sh_event_wait(st.up));
         off[k].resize(cnt); glen[k].resize(cnt);
         size_t total = 0;
         for (size_t i = 0; i < cnt; i++) { glen[k][i] = len[idx[i]]; off[k][i] = total; total += (size_t)glen[k][i] * per; }
-        if (e->h_sig[k].ensure(std::max<size_t>(total, 1) * 4) || e->d_signal[k].ensure(std::max<size_t>(total, 1) * 4)) return -1;
-        float *hs = e->h_sig[k].as<float>();
+        if (st.h_sig.ensure(std::max<size_t>(total, 1) * 4) || st.d_signal.ensure(std::max<size_t>(total, 1) * 4)) return -1;
+        float *hs = st.h_sig.as<float>();
         {   /* gather into the pinned staging buffer on several host threads (160 MB per 10 000 x 4000-sample group: 20 ms on one) */
             const unsigned nthr = (total * 4 > ((size_t)8 << 20)) ? std::max(1u, std::min(host_threads(), 8u)) : 1u;
             auto part = [&](size_t a, size_t b) {
@@ -487,11 +488,11 @@ static int basecall_batch_one(scrappie_hip_engine *e, int model, const raw_table
             }
         }
         hipStream_t us = e->ev_ok ? e->ustream : e->stream;
-        HIPCHK(hipMemcpyAsync(e->d_signal[k].p, hs, total * 4, hipMemcpyHostToDevice, us));
-        if (e->ev_ok) { HIPCHK(hipEventRecord(e->up[k], us)); HIPCHK(hipStreamWaitEvent(e->stream, e->up[k], 0)); HIPCHK(hipStreamWaitEvent(e->pstream, e->up[k], 0)); }
+        HIPCHK(hipMemcpyAsync(st.d_signal.p, hs, total * 4, hipMemcpyHostToDevice, us));
+        if (e->ev_ok) { HIPCHK(hipEventRecord(st.up, us)); HIPCHK(hipStreamWaitEvent(e->stream, st.up, 0)); HIPCHK(hipStreamWaitEvent(e->pstream, st.up, 0)); }
         else HIPCHK(sh_stream_wait(e->stream));
         used[k] = true;
-        a.d = e->d_signal[k].as<float>(); a.off = off[k].data(); a.len = glen[k].data();
+        a.d = st.d_signal.as<float>(); a.off = off[k].data(); a.len = glen[k].data();
         return 0;
     });
 }
@@ -533,7 +534,7 @@ extern "C" int scrappie_hip_basecall_batch_multi(scrappie_hip_engine *const *eng
         if (!ms[k]) return -1;
         if (ms[k]->stride != ms[0]->stride || ms[k]->arch != ms[0]->arch || ms[k]->NS != ms[0]->NS)
             return set_err("basecall_batch_multi: the engines hold different models");
-        if (engines[k]->pending[0] || engines[k]->pending[1]) return set_err("basecall_batch_multi: launch groups are already in flight on engine %zu", k);
+        if (engines[k]->any_pending()) return set_err("basecall_batch_multi: launch groups are already in flight on engine %zu", k);
     }
     for (size_t i = 0; i < n; i++) { out[i].score = NAN; out[i].nblock = 0; out[i].basecall = nullptr; out[i].basecall_length = 0; out[i].pos = nullptr; }
     if (n == 0) return 0;
@@ -574,38 +575,33 @@ extern "C" int scrappie_hip_basecall_batch_multi(scrappie_hip_engine *const *eng
             if (g >= ng) break;
             Flight &f = fl[nf & 1];
             const size_t lo = starts[(size_t)g], cnt = starts[(size_t)g + 1] - lo;
-            const int kbuf = nf & 1;
-            /* staging buffer kbuf was last read by the upload of this engine's group nf - 2 */
+            Slot &st = e->slots[nf & 1];
+            /* its staging buffer was last read by the upload of this engine's group nf - 2 */
             int rc = 0;
-            if (nf >= 2 && e->ev_ok && sh_event_wait(e->up[kbuf]) != hipSuccess) rc = set_err("hipEventSynchronize failed");
+            if (nf >= 2 && e->ev_ok && sh_event_wait(st.up) != hipSuccess) rc = set_err("hipEventSynchronize failed");
             f.g = g; f.off.resize(cnt); f.len.resize(cnt); f.calls.assign(cnt, scrappie_hip_call{});
             size_t total = 0;
             for (size_t i = 0; i < cnt; i++) { f.len[i] = len[order[lo + i]]; f.off[i] = total; total += (size_t)f.len[i] * per; }
-            if (!rc && (e->h_sig[kbuf].ensure(std::max<size_t>(total, 1) * 4) || e->d_signal[kbuf].ensure(std::max<size_t>(total, 1) * 4))) rc = -1;
+            if (!rc && (st.h_sig.ensure(std::max<size_t>(total, 1) * 4) || st.d_signal.ensure(std::max<size_t>(total, 1) * 4))) rc = -1;
             if (!rc) {
-                float *hs = e->h_sig[kbuf].as<float>();
+                float *hs = st.h_sig.as<float>();
                 for (size_t i = 0; i < cnt; i++) {
                     const raw_table &rt = reads[order[lo + i]];
                     if (f.len[i]) memcpy(hs + f.off[i], rt.raw + rt.start, (size_t)f.len[i] * per * 4);
                 }
                 hipStream_t us = e->ev_ok ? e->ustream : e->stream;
-                if (hipMemcpyAsync(e->d_signal[kbuf].p, hs, total * 4, hipMemcpyHostToDevice, us) != hipSuccess) rc = set_err("hipMemcpyAsync (signals) failed");
-                if (!rc && e->ev_ok && (hipEventRecord(e->up[kbuf], us) != hipSuccess || hipStreamWaitEvent(e->stream, e->up[kbuf], 0) != hipSuccess || hipStreamWaitEvent(e->pstream, e->up[kbuf], 0) != hipSuccess)) rc = set_err("event failed");
+                if (hipMemcpyAsync(st.d_signal.p, hs, total * 4, hipMemcpyHostToDevice, us) != hipSuccess) rc = set_err("hipMemcpyAsync (signals) failed");
+                if (!rc && e->ev_ok && (hipEventRecord(st.up, us) != hipSuccess || hipStreamWaitEvent(e->stream, st.up, 0) != hipSuccess || hipStreamWaitEvent(e->pstream, st.up, 0) != hipSuccess)) rc = set_err("event failed");
                 if (!rc && !e->ev_ok && sh_stream_wait(e->stream) != hipSuccess) rc = set_err("sync failed");
             }
-            if (!rc && scrappie_hip_run_device(e, models[k], e->d_signal[kbuf].as<float>(), f.off.data(), f.len.data(), cnt, p) < 0) rc = -1;
+            if (!rc && scrappie_hip_run_device(e, models[k], st.d_signal.as<float>(), f.off.data(), f.len.data(), cnt, p) < 0) rc = -1;
             if (!rc) nf++;
             if (!rc && prev >= 0 && collect_one(fl[(nf - 2) & 1])) rc = -1;      /* the older group, while the new one runs */
             if (rc) { errs[k] = scrappie_hip_last_error(); failed.store(1); break; }
             prev = g;
         }
         if (!failed.load() && prev >= 0 && collect_one(fl[(nf - 1) & 1])) { errs[k] = scrappie_hip_last_error(); failed.store(1); }
-        if (failed.load()) {       /* leave the engine drained */
-            (void)sh_stream_wait(e->pstream);
-            (void)sh_stream_wait(e->stream);
-            (void)sh_stream_wait(e->cstream);
-            e->pending[0] = e->pending[1] = false;
-        }
+        if (failed.load()) e->drain();
     };
     /* the engines of one call share the host: each stitches with its share of the CPUs this process may use */
     for (size_t k = 0; k < nengine; k++) engines[k]->host_thread_budget = std::max(1u, host_threads() / (unsigned)nengine);

@@ -3,31 +3,21 @@
 
 extern "C" int scrappie_hip_set_decoder_input(scrappie_hip_engine *e, const float *d_prob, const uint64_t *prob_off, size_t n_prob) {
     if (!e) return set_err("set_decoder_input: null engine");
-    if (e->pending[0] || e->pending[1]) return set_err("set_decoder_input: launch groups are in flight");
-    e->alt_valid = false;
-    if (!d_prob) { e->alt_prob = nullptr; e->alt_off.clear(); return 0; }
-    if (!prob_off || n_prob == 0) return set_err("set_decoder_input: no offsets");
-    e->alt_prob = d_prob;
-    e->alt_off.assign(prob_off, prob_off + n_prob);
-    return 0;
+    if (e->any_pending()) return set_err("set_decoder_input: launch groups are in flight");
+    return e->alt_prob.set("set_decoder_input", d_prob, prob_off, n_prob);
 }
 
 extern "C" int scrappie_hip_set_trunk_input(scrappie_hip_engine *e, const float *d_trunk, const uint64_t *trunk_off, size_t n_trunk) {
     if (!e) return set_err("set_trunk_input: null engine");
-    if (e->pending[0] || e->pending[1]) return set_err("set_trunk_input: launch groups are in flight");
-    e->trk_valid = false;
-    if (!d_trunk) { e->alt_trunk = nullptr; e->trk_off.clear(); return 0; }
-    if (!trunk_off || n_trunk == 0) return set_err("set_trunk_input: no offsets");
-    e->alt_trunk = d_trunk;
-    e->trk_off.assign(trunk_off, trunk_off + n_trunk);
-    return 0;
+    if (e->any_pending()) return set_err("set_trunk_input: launch groups are in flight");
+    return e->alt_trunk.set("set_trunk_input", d_trunk, trunk_off, n_trunk);
 }
 
 /* Test hooks.  Options: "ff_separate" (S1 and the decoder as two kernels on this engine, whatever the shape),
  * "dump_final" (the decoders leave every tile's final scores, start and end state in the hand-over buffer). */
 extern "C" int scrappie_hip_debug_option(scrappie_hip_engine *e, const char *name, int value) {
     if (!e || !name) return set_err("debug_option: null argument");
-    if (e->pending[0] || e->pending[1]) return set_err("debug_option: launch groups are in flight");
+    if (e->any_pending()) return set_err("debug_option: launch groups are in flight");
     if (!strcmp(name, "ff_separate")) e->dbg_ff_separate = value != 0;
     else if (!strcmp(name, "fv_single")) e->dbg_fv_single = value != 0;
     else if (!strcmp(name, "dump_final")) e->dbg_dump_final = value != 0;
@@ -58,8 +48,7 @@ extern "C" long long scrappie_hip_debug_fetch(scrappie_hip_engine *e, const char
     (void)hipSetDevice(e->device);
     HIPCHK(sh_stream_wait(e->stream));
     HIPCHK(sh_stream_wait(e->cstream));
-    const int slot = e->cur;
-    const LaunchGroup &lg = e->lgs[slot];
+    const Slot &sl = e->current(); const LaunchGroup &lg = sl.lg;
     if (!lg.valid) return set_err("debug_fetch: no launch group has run");
     Model *m = get_model(e, lg.model);
     if (!m) return -1;
@@ -70,7 +59,7 @@ extern "C" long long scrappie_hip_debug_fetch(scrappie_hip_engine *e, const char
     if (!strcmp(what, "tb")) { src = e->d_tb.p; have = (size_t)lg.ncb * NH * 16; }
     else if (!strcmp(what, "tb_end")) { src = e->d_tbend.p; have = (size_t)lg.ncb * 16 * 4; }
     else if (!strcmp(what, "final_state")) { src = e->d_fstate.p; have = lg.npad * 4; }
-    else if (!strcmp(what, "final_score")) { src = e->d_fscore[slot].p; have = lg.npad * 4; }
+    else if (!strcmp(what, "final_score")) { src = sl.d_fscore.p; have = lg.npad * 4; }
     else if (!strcmp(what, "final_scores")) { src = e->d_vstate.p; have = lg.ntile * (NH * 16 + 32) * 4; }
     else if (!strcmp(what, "order")) { src = lg.order.data(); have = lg.npad * 4; host = true; }
     else if (!strcmp(what, "tile_boff")) {
@@ -84,10 +73,7 @@ extern "C" long long scrappie_hip_debug_fetch(scrappie_hip_engine *e, const char
     else if (!strcmp(what, "gru_tiles")) { src = &gru_tiles; have = 4; host = true; }
     else if (!strcmp(what, "pinned_bytes")) {      /* pinned host memory this engine holds (staging, results, metadata; both slots) */
         static thread_local unsigned long long tot;
-        tot = 0;
-        for (int k = 0; k < 2; k++)
-            for (const HBuf *h : {&e->h_err[k], &e->h_bad[k], &e->h_edge[k], &e->h_pos[k], &e->h_bases[k], &e->h_blen[k], &e->h_redo[k], &e->h_meta[k],
-                                  &e->h_seq[k], &e->h_score[k], &e->h_hp[k], &e->h_sig[k]}) tot += h->cap;
+        tot = e->slots[0].pinned_bytes() + e->slots[1].pinned_bytes();
         src = &tot; have = 8; host = true;
     }
     else return set_err("debug_fetch: unknown buffer '%s'", what);
@@ -111,47 +97,42 @@ extern "C" long scrappie_hip_debug_stitch(scrappie_hip_engine *e, const int *pat
     (void)hipSetDevice(e->device);
     std::lock_guard<std::mutex> lk(e->mu);
     const size_t T = nblock, npad = 64, bcap = 5 * (T + 1) + 8;
-    DBuf dmeta, dseq, dhp, dpos, dbases, dblen, dredo;
-    long rc = -2;
-    do {
-        /* metadata of a group of one read: [seq_off | hp_off | bases_off] (long long x npad each), rT (int x npad) */
-        std::vector<char> hm(npad * 8 * 3 + npad * 4, 0);
-        int *rT = (int *)(hm.data() + npad * 24);
-        rT[0] = (int)T;
-        if (dmeta.ensure(hm.size()) || dseq.ensure((T + 1) * 4) || dpos.ensure((T + 1) * 4) || dbases.ensure(bcap) ||
-            dblen.ensure(npad * 4) || dredo.ensure(npad * 4) || (side && dhp.ensure(T * 5 * 4))) break;
-        hipStream_t s = e->stream;
-        if (hipMemcpyAsync(dmeta.p, hm.data(), hm.size(), hipMemcpyHostToDevice, s) != hipSuccess) break;
-        if (hipMemcpyAsync(dseq.p, path, (T + 1) * 4, hipMemcpyHostToDevice, s) != hipSuccess) break;
-        if (side && hipMemcpyAsync(dhp.p, side, T * 5 * 4, hipMemcpyHostToDevice, s) != hipSuccess) break;
-        if (hipMemsetAsync(dredo.p, 0, npad * 4, s) != hipSuccess) break;
-        if (sh_stream_wait(s) != hipSuccess) break;                 /* sources are pageable caller memory */
-        char *d = dmeta.as<char>();
-        ShMeta md{};
-        md.rT = (const int *)(d + npad * 24);
-        ShStitchArgs sa;
-        sa.seq = dseq.as<int>(); sa.seq_off = (const long long *)d;
-        sa.hp = side ? dhp.as<float>() : nullptr; sa.hp_off = (const long long *)(d + npad * 8);
-        sa.pos = pos ? dpos.as<int>() : nullptr;
-        sa.bases = dbases.as<char>(); sa.bases_off = (const long long *)(d + npad * 16);
-        sa.blen = dblen.as<int>(); sa.redo = dredo.as<unsigned>();
-        sa.npad = 1; sa.nstate = nstate; sa.crf = crf; sa.sstride = 1;
-        hipLaunchKernelGGL(k_stitch, dim3(1), dim3(64), 0, s, sa, md);
-        int len = -1; unsigned rd = 0;
-        if (hipMemcpyAsync(&len, dblen.p, 4, hipMemcpyDeviceToHost, s) != hipSuccess) break;
-        if (hipMemcpyAsync(&rd, dredo.p, 4, hipMemcpyDeviceToHost, s) != hipSuccess) break;
-        if (sh_stream_wait(s) != hipSuccess) { set_err("debug_stitch: %s", hipGetErrorString(hipGetLastError())); break; }
-        if (redo) *redo = (int)rd;
-        if (len >= 0) {
-            if ((size_t)len + 1 > cap) { set_err("debug_stitch: %d bases do not fit %zu bytes", len, cap); break; }
-            if (len && hipMemcpy(bases, dbases.p, (size_t)len, hipMemcpyDeviceToHost) != hipSuccess) break;
-            bases[len] = 0;
-            if (pos && !crf && hipMemcpy(pos, dpos.p, (T + 1) * 4, hipMemcpyDeviceToHost) != hipSuccess) break;
-        }
-        rc = len;
-    } while (0);
-    for (DBuf *b : {&dmeta, &dseq, &dhp, &dpos, &dbases, &dblen, &dredo}) b->release();
-    return rc;
+    DBuf dmeta, dseq, dhp, dpos, dbases, dblen, dredo;      /* (freed on every way out) */
+    /* metadata of a group of one read: [seq_off | hp_off | bases_off] (long long x npad each), rT (int x npad) */
+    std::vector<char> hm(npad * 8 * 3 + npad * 4, 0);
+    int *rT = (int *)(hm.data() + npad * 24);
+    rT[0] = (int)T;
+    if (dmeta.ensure(hm.size()) || dseq.ensure((T + 1) * 4) || dpos.ensure((T + 1) * 4) || dbases.ensure(bcap) ||
+        dblen.ensure(npad * 4) || dredo.ensure(npad * 4) || (side && dhp.ensure(T * 5 * 4))) return -2;
+    hipStream_t s = e->stream;
+    if (hipMemcpyAsync(dmeta.p, hm.data(), hm.size(), hipMemcpyHostToDevice, s) != hipSuccess) return -2;
+    if (hipMemcpyAsync(dseq.p, path, (T + 1) * 4, hipMemcpyHostToDevice, s) != hipSuccess) return -2;
+    if (side && hipMemcpyAsync(dhp.p, side, T * 5 * 4, hipMemcpyHostToDevice, s) != hipSuccess) return -2;
+    if (hipMemsetAsync(dredo.p, 0, npad * 4, s) != hipSuccess) return -2;
+    if (sh_stream_wait(s) != hipSuccess) return -2;                 /* sources are pageable caller memory */
+    char *d = dmeta.as<char>();
+    ShMeta md{};
+    md.rT = (const int *)(d + npad * 24);
+    ShStitchArgs sa;
+    sa.seq = dseq.as<int>(); sa.seq_off = (const long long *)d;
+    sa.hp = side ? dhp.as<float>() : nullptr; sa.hp_off = (const long long *)(d + npad * 8);
+    sa.pos = pos ? dpos.as<int>() : nullptr;
+    sa.bases = dbases.as<char>(); sa.bases_off = (const long long *)(d + npad * 16);
+    sa.blen = dblen.as<int>(); sa.redo = dredo.as<unsigned>();
+    sa.npad = 1; sa.nstate = nstate; sa.crf = crf; sa.sstride = 1;
+    hipLaunchKernelGGL(k_stitch, dim3(1), dim3(64), 0, s, sa, md);
+    int len = -1; unsigned rd = 0;
+    if (hipMemcpyAsync(&len, dblen.p, 4, hipMemcpyDeviceToHost, s) != hipSuccess) return -2;
+    if (hipMemcpyAsync(&rd, dredo.p, 4, hipMemcpyDeviceToHost, s) != hipSuccess) return -2;
+    if (sh_stream_wait(s) != hipSuccess) { set_err("debug_stitch: %s", hipGetErrorString(hipGetLastError())); return -2; }
+    if (redo) *redo = (int)rd;
+    if (len >= 0) {
+        if ((size_t)len + 1 > cap) { set_err("debug_stitch: %d bases do not fit %zu bytes", len, cap); return -2; }
+        if (len && hipMemcpy(bases, dbases.p, (size_t)len, hipMemcpyDeviceToHost) != hipSuccess) return -2;
+        bases[len] = 0;
+        if (pos && !crf && hipMemcpy(pos, dpos.p, (T + 1) * 4, hipMemcpyDeviceToHost) != hipSuccess) return -2;
+    }
+    return len;
 }
 
 extern "C" void scrappie_hip_free_calls(scrappie_hip_call *calls, size_t n) {

@@ -12,10 +12,10 @@ extern "C" long scrappie_hip_run_device(scrappie_hip_engine *e, int model, const
     if (!p) p = &dp;
     if (n > e->max_launch_reads) { set_err("run_device: %zu reads exceed max_launch_reads %zu", n, e->max_launch_reads); return -1; }
     if (e->dbg_fail_run > 0 && --e->dbg_fail_run == 0) { set_err("run_device: injected failure (debug option fail_run)"); return -1; }
-    const auto hs0 = std::chrono::steady_clock::now();
+    const HostStamp stamp;
     if (run_pipeline(e, m, d_signal, offsets, lengths, n, p, STOP_NONE, 5, nullptr)) return -1;
-    if (tun().host_stamp) fprintf(stderr, "host stamp: run_device %.2f ms on the host\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - hs0).count());
-    return (long)e->lgs[e->cur].ncb;
+    stamp("run_device", " on the host");
+    return (long)e->current().lg.ncb;
 }
 
 /* D2 + D3 of one read on the host (sh_host.c): what k_stitch does on the device.  `path` (T + 1 entries) is consumed. */
@@ -34,11 +34,11 @@ static void host_stitch_read(const Model *m, bool hp_on, const float *side, int 
     if (want_pos && bases) c.pos = pos; else { free(pos); c.pos = nullptr; }
 }
 
-static void stitch_range(scrappie_hip_engine *e, int slot, const Model *m, const scrappie_hip_params *p, scrappie_hip_call *out,
+static void stitch_range(const scrappie_hip_engine *e, const Slot &sl, const Model *m, const scrappie_hip_params *p, scrappie_hip_call *out,
                          size_t lo, size_t hi) {
-    const LaunchGroup &lg = e->lgs[slot];
-    const float *scores = e->h_score[slot].as<float>();
-    const unsigned *bad = e->h_bad[slot].as<unsigned>();
+    const LaunchGroup &lg = sl.lg;
+    const float *scores = sl.h_score.as<float>();
+    const unsigned *bad = sl.h_bad.as<unsigned>();
     for (size_t i = lo; i < hi; i++) {
         const int o = lg.order[i];
         if (o < 0) continue;
@@ -52,19 +52,19 @@ static void stitch_range(scrappie_hip_engine *e, int slot, const Model *m, const
         if (lg.dev_stitch) {
             /* bases (and pos) were made by k_stitch: copy them out of the pinned buffers.  Reads whose homopolymer
              * mean sat on a rounding boundary (redo) are left to stitch_group. */
-            if (e->h_redo[slot].as<unsigned>()[i] || e->dbg_redo_all) continue;
-            const int len = e->h_blen[slot].as<int>()[i];
+            if (sl.h_redo.as<unsigned>()[i] || e->dbg_redo_all) continue;
+            const int len = sl.h_blen.as<int>()[i];
             if (len < 0) continue;                                   /* every entry a stay: no call (overlapper returns NULL) */
             char *bases = (char *)malloc((size_t)len + 1);
             if (!bases) continue;
-            memcpy(bases, e->h_bases[slot].as<char>() + lg.bases_off[i], (size_t)len);
+            memcpy(bases, sl.h_bases.as<char>() + lg.bases_off[i], (size_t)len);
             bases[len] = 0;
             c.basecall = bases;
             c.basecall_length = (size_t)len;
             if (p->want_pos) {
                 int *pos = (int *)malloc(((size_t)T + 1) * sizeof(int));
                 if (pos) {
-                    if (lg.dev_pos) { const int *src = e->h_pos[slot].as<int>() + lg.seq_off[i]; for (int t = 0; t <= T; t++) pos[t] = src[(size_t)t * SH_SEQ_STRIDE]; }
+                    if (lg.dev_pos) { const int *src = sl.h_pos.as<int>() + lg.seq_off[i]; for (int t = 0; t <= T; t++) pos[t] = src[(size_t)t * SH_SEQ_STRIDE]; }
                     else memset(pos, 0, ((size_t)T + 1) * sizeof(int));             /* CRF: crfpath_to_basecall leaves pos untouched (Q11) */
                 }
                 c.pos = pos;
@@ -73,13 +73,13 @@ static void stitch_range(scrappie_hip_engine *e, int slot, const Model *m, const
         }
         int *path = (int *)malloc(((size_t)T + 1) * sizeof(int));
         if (!path) continue;
-        { const int *src = e->h_seq[slot].as<int>() + lg.seq_off[i]; for (int t = 0; t <= T; t++) path[t] = src[(size_t)t * SH_SEQ_STRIDE]; }
-        host_stitch_read(m, lg.hp_on, lg.hp_on ? e->h_hp[slot].as<float>() + lg.hp_off[i] * 5 : nullptr, path, T, p->want_pos != 0, c);
+        { const int *src = sl.h_seq.as<int>() + lg.seq_off[i]; for (int t = 0; t <= T; t++) path[t] = src[(size_t)t * SH_SEQ_STRIDE]; }
+        host_stitch_read(m, lg.hp_on, lg.hp_on ? sl.h_hp.as<float>() + lg.hp_off[i] * 5 : nullptr, path, T, p->want_pos != 0, c);
         free(path);
     }
 }
 
-static int stitch_group(scrappie_hip_engine *e, int slot, Model *m, const scrappie_hip_params *p, scrappie_hip_call *out, size_t n);
+static int stitch_group(scrappie_hip_engine *e, Slot &sl, Model *m, const scrappie_hip_params *p, scrappie_hip_call *out, size_t n);
 
 /* Host threads for stitching a launch group: the CPUs this process may actually use -- its affinity mask and its
  * cgroup CPU quota (a GPU box may report 256 CPUs and grant 16), shared with the other ranks of a torchrun job
@@ -116,24 +116,24 @@ extern "C" int scrappie_hip_collect(scrappie_hip_engine *e, const scrappie_hip_p
     if (!e || !out) return set_err("collect: null argument");
     scrappie_hip_params dp = scrappie_hip_default_params();
     if (!p) p = &dp;
-    if (!e->pending[0] && !e->pending[1]) return set_err("collect: no launch group in flight");
-    const int slot = e->pending[e->oldest] ? e->oldest : (e->oldest ^ 1);
-    LaunchGroup &lg = e->lgs[slot];
+    if (!e->any_pending()) return set_err("collect: no launch group in flight");
+    Slot &sl = e->slots[e->oldest].pending ? e->slots[e->oldest] : e->other(e->slots[e->oldest]);
+    LaunchGroup &lg = sl.lg;
     if (!lg.valid || lg.n != n) return set_err("collect: oldest launch group has %zu reads, asked for %zu", lg.n, n);
     (void)hipSetDevice(e->device);
     const auto hs0 = std::chrono::steady_clock::now();
-    if (e->ev_ok) HIPCHK(sh_event_wait(e->done[slot]));
+    if (e->ev_ok) HIPCHK(sh_event_wait(sl.done));
     else HIPCHK(sh_stream_wait(e->stream));
     const auto hs1 = std::chrono::steady_clock::now();
     struct StampOut { std::chrono::steady_clock::time_point a, b; bool on; ~StampOut() { if (on) fprintf(stderr, "host stamp: collect waited %.2f ms, then %.2f ms of host work\n", std::chrono::duration<double, std::milli>(b - a).count(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - b).count()); } } stamp_out{hs0, hs1, tun().host_stamp};
-    e->pending[slot] = false;
-    e->oldest = slot ^ 1;
-    if (!e->spans[slot].empty() && resolve_spans(e, slot)) return -1;
+    sl.pending = false;
+    e->oldest = e->index(e->other(sl));
+    if (!sl.spans.empty() && resolve_spans(e, sl)) return -1;
     Model *m = get_model(e, lg.model);
     if (!m) return -1;
     static std::atomic<bool> fake_once{false};
     const bool faked = tun().fake_timeout && e->handover && lg.ncb > 0 && !fake_once.exchange(true);
-    if (lg.ncb > 0 && e->h_err[slot].p && (*e->h_err[slot].as<unsigned>() != 0 || faked)) {
+    if (lg.ncb > 0 && sl.h_err.p && (*sl.h_err.as<unsigned>() != 0 || faked)) {
         /* a state hand-over between workgroups timed out (sh_wait_flag): the results of this group are
          * invalid.  Run it again scheduled on whole tiles (no inter-workgroup waits at all), behind whatever
          * else is in flight, and stitch that. */
@@ -147,24 +147,24 @@ extern "C" int scrappie_hip_collect(scrappie_hip_engine *e, const scrappie_hip_p
         const int rc = run_pipeline(e, m, dsig, off.data(), len.data(), n, &pp, STOP_NONE, 5, nullptr);
         e->handover = true;
         if (rc) return -1;
-        const int rs = e->cur;
-        if (e->ev_ok) HIPCHK(sh_event_wait(e->done[rs])); else HIPCHK(sh_stream_wait(e->stream));
-        e->pending[rs] = false;
+        Slot &rs = e->current();
+        if (e->ev_ok) HIPCHK(sh_event_wait(rs.done)); else HIPCHK(sh_stream_wait(e->stream));
+        rs.pending = false;
         e->oldest = other_oldest;
-        if (!e->spans[rs].empty() && resolve_spans(e, rs)) return -1;
-        if (*e->h_err[rs].as<unsigned>() != 0) return set_err("launch group failed on the device even on whole tiles");
+        if (!rs.spans.empty() && resolve_spans(e, rs)) return -1;
+        if (*rs.h_err.as<unsigned>() != 0) return set_err("launch group failed on the device even on whole tiles");
         fprintf(stderr, "scrappie_hip: a state hand-over between workgroups timed out; launch group of %zu reads re-run on whole tiles\n", n);
         return stitch_group(e, rs, m, p, out, n);
     }
-    return stitch_group(e, slot, m, p, out, n);
+    return stitch_group(e, sl, m, p, out, n);
 }
 
-static int stitch_group(scrappie_hip_engine *e, int slot, Model *m, const scrappie_hip_params *p, scrappie_hip_call *out, size_t n) {
-    LaunchGroup &lg = e->lgs[slot];
+static int stitch_group(scrappie_hip_engine *e, Slot &sl, Model *m, const scrappie_hip_params *p, scrappie_hip_call *out, size_t n) {
+    LaunchGroup &lg = sl.lg;
     for (size_t i = 0; i < n; i++) { out[i].score = NAN; out[i].nblock = 0; out[i].basecall = nullptr; out[i].basecall_length = 0; out[i].pos = nullptr; }
     if (lg.ncb == 0) return 0;
     {   /* reads whose input left the operand range of the split products (k_conv_act / k_feat_in): no call, said aloud */
-        const unsigned *bad = e->h_bad[slot].as<unsigned>();
+        const unsigned *bad = sl.h_bad.as<unsigned>();
         size_t nbad = 0; long first = -1;
         for (size_t i = 0; i < lg.npad; i++) if (bad[i] && lg.order[i] >= 0) { if (!nbad || lg.order[i] < first) first = lg.order[i]; nbad++; }
         if (nbad) {
@@ -175,39 +175,39 @@ static int stitch_group(scrappie_hip_engine *e, int slot, Model *m, const scrapp
     }
     if (lg.dev_stitch && p->want_pos && !lg.dev_pos && m->arch != 1) {
         /* pos[] was not asked for when the group was enqueued: fetch the paths (and side rows) after all and stitch on the host */
-        if (e->h_seq[slot].ensure((size_t)std::max<long long>(lg.nseq, 1) * 4) || (lg.hp_on && e->h_hp[slot].ensure((size_t)std::max<long long>(lg.nhp, 1) * 5 * 4))) return -1;
-        HIPCHK(hipMemcpy(e->h_seq[slot].p, e->d_seq[slot].p, (size_t)lg.nseq * 4, hipMemcpyDeviceToHost));
-        if (lg.hp_on) HIPCHK(hipMemcpy(e->h_hp[slot].p, e->d_hp[slot].p, (size_t)lg.nhp * 5 * 4, hipMemcpyDeviceToHost));
+        if (sl.h_seq.ensure((size_t)std::max<long long>(lg.nseq, 1) * 4) || (lg.hp_on && sl.h_hp.ensure((size_t)std::max<long long>(lg.nhp, 1) * 5 * 4))) return -1;
+        HIPCHK(hipMemcpy(sl.h_seq.p, sl.d_seq.p, (size_t)lg.nseq * 4, hipMemcpyDeviceToHost));
+        if (lg.hp_on) HIPCHK(hipMemcpy(sl.h_hp.p, sl.d_hp.p, (size_t)lg.nhp * 5 * 4, hipMemcpyDeviceToHost));
         lg.dev_stitch = false;
     }
     unsigned nthr = host_threads();
     if (e->host_thread_budget) nthr = std::min(nthr, e->host_thread_budget);
     if (lg.dev_stitch) nthr = std::min(nthr, 4u);             /* copying strings out of pinned memory: a few ms on one thread */
     if (lg.npad < 256) nthr = 1;
-    if (nthr == 1) stitch_range(e, slot, m, p, out, 0, lg.npad);
+    if (nthr == 1) stitch_range(e, sl, m, p, out, 0, lg.npad);
     else {
         std::vector<std::thread> th;
         const size_t per = (lg.npad + nthr - 1) / nthr;
         for (unsigned t = 0; t < nthr; t++) {
             const size_t lo = t * per, hi = std::min(lg.npad, lo + per);
             if (lo >= hi) break;
-            th.emplace_back(stitch_range, e, slot, m, p, out, lo, hi);
+            th.emplace_back(stitch_range, e, std::cref(sl), m, p, out, lo, hi);
         }
         for (auto &x : th) x.join();
     }
     if (lg.dev_stitch) {
         /* reads k_stitch would not decide (a homopolymer run's posterior-mean count within rounding noise of a boundary):
          * their path and side rows are still on the device; the host code decides */
-        const unsigned *redo = e->h_redo[slot].as<unsigned>();
-        const unsigned *bad = e->h_bad[slot].as<unsigned>();
+        const unsigned *redo = sl.h_redo.as<unsigned>();
+        const unsigned *bad = sl.h_bad.as<unsigned>();
         size_t nredo = 0;
         for (size_t i = 0; i < lg.npad; i++) {
             const int o = lg.order[i], T = lg.rT[i];
             if (o < 0 || T <= 0 || bad[i] || !(redo[i] || e->dbg_redo_all)) continue;
             std::vector<int> path((size_t)T + 1);
             std::vector<float> side(lg.hp_on ? (size_t)T * 5 : 0);
-            HIPCHK(hipMemcpy2D(path.data(), 4, e->d_seq[slot].as<int>() + lg.seq_off[i], (size_t)SH_SEQ_STRIDE * 4, 4, (size_t)T + 1, hipMemcpyDeviceToHost));
-            if (lg.hp_on) HIPCHK(hipMemcpy(side.data(), e->d_hp[slot].as<float>() + lg.hp_off[i] * 5, (size_t)T * 5 * 4, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy2D(path.data(), 4, sl.d_seq.as<int>() + lg.seq_off[i], (size_t)SH_SEQ_STRIDE * 4, 4, (size_t)T + 1, hipMemcpyDeviceToHost));
+            if (lg.hp_on) HIPCHK(hipMemcpy(side.data(), sl.d_hp.as<float>() + lg.hp_off[i] * 5, (size_t)T * 5 * 4, hipMemcpyDeviceToHost));
             host_stitch_read(m, lg.hp_on, side.data(), path.data(), T, p->want_pos != 0, out[o]);
             nredo++;
         }
@@ -244,7 +244,7 @@ static int run_groups(scrappie_hip_engine *e, int model, const Model *m, const u
     scrappie_hip_params dp = scrappie_hip_default_params();
     if (!p) p = &dp;
     if (!stream && e->carry.live && collect_carry(e)) return -1;      /* an ordinary call behind a streaming one: that one's last group first */
-    const int inflight = (e->pending[0] ? 1 : 0) + (e->pending[1] ? 1 : 0);
+    const int inflight = (e->slots[0].pending ? 1 : 0) + (e->slots[1].pending ? 1 : 0);
     if (inflight > (e->carry.live ? 1 : 0)) return set_err("launch groups are already in flight on this engine: collect them first");
     if (n == 0) return 0;
     const int unit = m->arch == 3 ? 1 : std::max(m->stride, 1);    /* events models: lengths already count blocks */
@@ -262,10 +262,7 @@ static int run_groups(scrappie_hip_engine *e, int model, const Model *m, const u
     auto blank = [&]() { for (size_t i = 0; i < n; i++) { scrappie_hip_call &c = at(i); c.score = NAN; c.nblock = 0; c.basecall = nullptr; c.basecall_length = 0; c.pos = nullptr; } };
     blank();
     auto fail = [&]() {   /* leave the engine drained; a failed call returns nothing: release the calls already stitched */
-        (void)sh_stream_wait(e->pstream);
-        (void)sh_stream_wait(e->stream);
-        (void)sh_stream_wait(e->cstream);
-        e->pending[0] = e->pending[1] = false;
+        e->drain();
         e->carry.live = false;                 /* (a carried group's reads keep their blank entries: the stream has failed) */
         const std::string keep = g_err;
         for (size_t i = 0; i < n; i++) scrappie_hip_free_calls(&at(i), 1);
@@ -306,9 +303,9 @@ static int run_groups(scrappie_hip_engine *e, int model, const Model *m, const u
     return 0;
 }
 
-extern "C" int scrappie_hip_basecall_device(scrappie_hip_engine *e, int model, const float *d_signal, const uint64_t *offsets,
-                                            const uint32_t *lengths, size_t n, const scrappie_hip_params *p, scrappie_hip_call *out) {
-    if (!e || !out) return set_err("basecall_device: null argument");
+static int basecall_device(scrappie_hip_engine *e, int model, const float *d_signal, const uint64_t *offsets, const uint32_t *lengths, size_t n,
+                           const scrappie_hip_params *p, scrappie_hip_call *out, bool stream) {
+    if (!e || !out) return set_err("basecall_device%s: null argument", stream ? "_stream" : "");
     Model *m = get_model(e, model);
     if (!m) return -1;
     std::vector<uint64_t> off[2];
@@ -318,7 +315,11 @@ extern "C" int scrappie_hip_basecall_device(scrappie_hip_engine *e, int model, c
         for (size_t i = 0; i < cnt; i++) { off[k][i] = offsets[idx[i]]; len[k][i] = lengths[idx[i]]; }
         a.d = d_signal; a.off = off[k].data(); a.len = len[k].data();
         return 0;
-    });
+    }, stream);
+}
+extern "C" int scrappie_hip_basecall_device(scrappie_hip_engine *e, int model, const float *d_signal, const uint64_t *offsets,
+                                            const uint32_t *lengths, size_t n, const scrappie_hip_params *p, scrappie_hip_call *out) {
+    return basecall_device(e, model, d_signal, offsets, lengths, n, p, out, false);
 }
 
 /* scrappie_hip_basecall_device that returns while its LAST launch group is still running.  That group's calls are delivered -- into the
@@ -328,17 +329,7 @@ extern "C" int scrappie_hip_basecall_device(scrappie_hip_engine *e, int model, c
  * carried group first.  A failure loses the carried group's calls too (their entries stay blank): the stream has failed. */
 extern "C" int scrappie_hip_basecall_device_stream(scrappie_hip_engine *e, int model, const float *d_signal, const uint64_t *offsets,
                                                    const uint32_t *lengths, size_t n, const scrappie_hip_params *p, scrappie_hip_call *out) {
-    if (!e || !out) return set_err("basecall_device_stream: null argument");
-    Model *m = get_model(e, model);
-    if (!m) return -1;
-    std::vector<uint64_t> off[2];
-    std::vector<uint32_t> len[2];
-    return run_groups(e, model, m, lengths, n, p, out, [&](int k, const uint32_t *idx, size_t cnt, GroupArgs &a) {
-        off[k].resize(cnt); len[k].resize(cnt);
-        for (size_t i = 0; i < cnt; i++) { off[k][i] = offsets[idx[i]]; len[k][i] = lengths[idx[i]]; }
-        a.d = d_signal; a.off = off[k].data(); a.len = len[k].data();
-        return 0;
-    }, true);
+    return basecall_device(e, model, d_signal, offsets, lengths, n, p, out, true);
 }
 extern "C" int scrappie_hip_stream_flush(scrappie_hip_engine *e) {
     if (!e) return set_err("stream_flush: null engine");
@@ -346,8 +337,7 @@ extern "C" int scrappie_hip_stream_flush(scrappie_hip_engine *e) {
     (void)hipSetDevice(e->device);
     if (collect_carry(e)) {
         const std::string keep = g_err;
-        (void)sh_stream_wait(e->pstream); (void)sh_stream_wait(e->stream); (void)sh_stream_wait(e->cstream);
-        e->pending[0] = e->pending[1] = false;
+        e->drain();
         return set_err("%s", keep.c_str());
     }
     return 0;

@@ -6,9 +6,9 @@
 /* ------------------------------------------------------------------ */
 struct MetaPtrs { ShMeta md; const long long *seq_off, *hp_off, *bases_off; ShGruLanes lanes, lanes1; ShGruPairs pairs, pairs2; const ShGruSegD *vseg; };
 
-static int build_group(scrappie_hip_engine *e, Model *m, const uint64_t *offsets, const uint32_t *lengths,
+static int build_group(scrappie_hip_engine *e, Slot &sl, Model *m, const uint64_t *offsets, const uint32_t *lengths,
                        size_t n, bool hp_on, MetaPtrs &mp) {
-    LaunchGroup &lg = e->lgs[e->cur];
+    LaunchGroup &lg = sl.lg;
     lg.valid = false;
     lg.n = n; lg.hp_on = hp_on;
     lg.ntile = (n + 15) / 16; lg.npad = lg.ntile * 16;
@@ -90,8 +90,8 @@ static int build_group(scrappie_hip_engine *e, Model *m, const uint64_t *offsets
     const size_t b_loff32b = sched32b.lane_off.size() * 4, b_seg32b = sched32b.seg.size() * sizeof(ShGruSeg);
     const size_t total = 4 * b_u64 + lg.ntile * 8 + 2 * b_i32 + lg.ntile * 4 + 16 + b_seg + b_loff + b_wit + 16 + b_vseg + b_vloff + 16 + b_seg1 + b_loff1 +
                          16 + b_seg32 + b_loff32 + b_pt + 16 + b_seg32b + b_loff32b;
-    if (e->h_meta[e->cur].ensure(total + 16) || e->d_meta[e->cur].ensure(total + 16)) return -1;
-    char *h = e->h_meta[e->cur].as<char>();
+    if (sl.h_meta.ensure(total + 16) || sl.d_meta.ensure(total + 16)) return -1;
+    char *h = sl.h_meta.as<char>();
     size_t o = 0;
     memcpy(h + o, sig_off.data(), b_u64); const size_t o_sig = o; o += b_u64;
     memcpy(h + o, lg.seq_off.data(), b_u64); const size_t o_seq = o; o += b_u64;
@@ -120,9 +120,9 @@ static int build_group(scrappie_hip_engine *e, Model *m, const uint64_t *offsets
     hipStream_t ps = e->ev_ok ? e->pstream : e->stream;      /* prologue stream: see run_pipeline */
     if (e->ev_ok) {
         const long long n16 = (long long)((total + 15) / 16);
-        hipLaunchKernelGGL(k_upload_words, dim3((unsigned)std::min<long long>((n16 + 255) / 256, 64)), dim3(256), 0, ps, (const u32x4 *)h, e->d_meta[e->cur].as<u32x4>(), n16);
-    } else HIPCHK(hipMemcpyAsync(e->d_meta[e->cur].p, h, total, hipMemcpyHostToDevice, ps));
-    char *d = e->d_meta[e->cur].as<char>();
+        hipLaunchKernelGGL(k_upload_words, dim3((unsigned)std::min<long long>((n16 + 255) / 256, 64)), dim3(256), 0, ps, (const u32x4 *)h, sl.d_meta.as<u32x4>(), n16);
+    } else HIPCHK(hipMemcpyAsync(sl.d_meta.p, h, total, hipMemcpyHostToDevice, ps));
+    char *d = sl.d_meta.as<char>();
     mp.md.sig_off = (const unsigned long long *)(d + o_sig);
     mp.seq_off = (const long long *)(d + o_seq);
     mp.hp_off = (const long long *)(d + o_hp);
@@ -137,12 +137,12 @@ static int build_group(scrappie_hip_engine *e, Model *m, const uint64_t *offsets
     mp.lanes.wg_iter = (const int *)(d + o_wit);
     mp.lanes.ntile = (int)lg.ntile;
     mp.vseg = (const ShGruSegD *)(d + o_vseg);
-    if (e->d_hstate.ensure(std::max<size_t>(lg.ntile, 1) * 12 * 256 * 4) || e->d_gflag[e->cur].ensure((lg.ntile + 1) * 4)) return -1;
+    if (e->d_hstate.ensure(std::max<size_t>(lg.ntile, 1) * 12 * 256 * 4) || sl.d_gflag.ensure((lg.ntile + 1) * 4)) return -1;
     mp.lanes.hstate = e->d_hstate.as<float>();
-    mp.lanes.flag = e->d_gflag[e->cur].as<unsigned>();
-    HIPCHK(hipMemsetAsync(e->d_gflag[e->cur].p, 0, (lg.ntile + 1) * 4, ps));
-    if (e->d_bad[e->cur].ensure(lg.npad * 4)) return -1;
-    HIPCHK(hipMemsetAsync(e->d_bad[e->cur].p, 0, lg.npad * 4, ps));
+    mp.lanes.flag = sl.d_gflag.as<unsigned>();
+    HIPCHK(hipMemsetAsync(sl.d_gflag.p, 0, (lg.ntile + 1) * 4, ps));
+    if (sl.d_bad.ensure(lg.npad * 4)) return -1;
+    HIPCHK(hipMemsetAsync(sl.d_bad.p, 0, lg.npad * 4, ps));
     mp.lanes1 = mp.lanes;
     mp.lanes1.seg = (const ShGruSegD *)(d + o_seg1);
     mp.lanes1.lane_off = (const int *)(d + o_loff1);

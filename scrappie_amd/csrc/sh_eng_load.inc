@@ -72,12 +72,12 @@ static int load_model_mem_one(scrappie_hip_engine *e, const char *name, const vo
             const int I = (l < 2) ? m->nfeat : m->S;
             if (!mi || !ms || !mb || !mpp || mi->nr != I || mi->nc != 4 * m->S || ms->nr != m->S || ms->nc != 4 * m->S ||
                 mb->nr * mb->nc != 4 * m->S || mpp->nr * mpp->nc != 3 * m->S) {
-                m->release(); delete m;
+                delete m;
                 return set_err("model '%s': LSTM layer %d has wrong shapes", name, l);
             }
             for (const HostMat *x : {mi, ms}) if (!in_split_range(*x)) {
                 const float mx = max_abs(*x);
-                m->release(); delete m;
+                delete m;
                 return set_err("model '%s': LSTM layer %d has a weight of magnitude %g, outside the split products' range (< %g); "
                                "there is no exact-fp32 LSTM kernel", name, l, mx, (double)SH_W_LIMIT);
             }
@@ -91,7 +91,7 @@ static int load_model_mem_one(scrappie_hip_engine *e, const char *name, const vo
             int mt, mtp;
             int mt_s;
             if (upload(m->iW[l], make_frags(*src, mt)) || upload(m->ib[l], make_bias_frags(*mb, mt)) ||
-                upload(m->sW[l], make_frags(*ms, mt_s))) { m->release(); delete m; return -1; }
+                upload(m->sW[l], make_frags(*ms, mt_s))) { delete m; return -1; }
             HostMat padded32;                                /* ... and to one 32-wide k step for the split products of k_lstm_proj */
             const HostMat *psrc = src;
             if (src->nr % 32 != 0) {
@@ -99,10 +99,10 @@ static int load_model_mem_one(scrappie_hip_engine *e, const char *name, const vo
                 for (int c = 0; c < mi->nc; c++) for (int r = 0; r < I; r++) padded32.v[(size_t)c * 32 + r] = mi->v[(size_t)c * I + r];
                 psrc = &padded32;
             }
-            if (upload_u32(m->iWp[l], make_piece_frags(*psrc)) || upload(m->ibs[l], scaled(make_bias_frags(*mb, mt), SH_OSCALE))) { m->release(); delete m; return -1; }
-            if (upload_u32(m->sWp[l], make_piece_frags(*ms))) { m->release(); delete m; return -1; }
+            if (upload_u32(m->iWp[l], make_piece_frags(*psrc)) || upload(m->ibs[l], scaled(make_bias_frags(*mb, mt), SH_OSCALE))) { delete m; return -1; }
+            if (upload_u32(m->sWp[l], make_piece_frags(*ms))) { delete m; return -1; }
             mtp = 3 * m->S / 16;
-            if (upload(m->lp[l], make_bias_frags(*mpp, mtp))) { m->release(); delete m; return -1; }
+            if (upload(m->lp[l], make_bias_frags(*mpp, mtp))) { delete m; return -1; }
         }
     } else {
     if (!cw || !cb || !fw || !fb) { delete m; return set_err("model '%s': missing conv/ff matrices", name); }
@@ -118,7 +118,7 @@ static int load_model_mem_one(scrappie_hip_engine *e, const char *name, const vo
     {   /* conv taps as [WL][F] so 4 consecutive filters load as one vector */
         std::vector<float> w((size_t)m->WL * m->F);
         for (int f = 0; f < m->F; f++) for (int t = 0; t < m->WL; t++) w[(size_t)t * m->F + f] = cw->v[(size_t)f * m->WL + t];
-        if (upload(m->conv_W, w) || upload(m->conv_b, cb->v)) { m->release(); delete m; return -1; }
+        if (upload(m->conv_W, w) || upload(m->conv_b, cb->v)) { delete m; return -1; }
     }
     const int ngru = (m->arch == 2) ? 4 : 5;
     for (int l = 0; l < ngru; l++) {
@@ -131,14 +131,14 @@ static int load_model_mem_one(scrappie_hip_engine *e, const char *name, const vo
         const int I = (m->arch == 2) ? (l < 2 ? m->F : m->S) : ((l == 0) ? m->F : m->S);
         if (!mi || !ms || !ms2 || !mb || mi->nr != I || mi->nc != 3 * m->S || ms->nr != m->S || ms->nc != 2 * m->S ||
             ms2->nr != m->S || ms2->nc != m->S || mb->nr * mb->nc != 3 * m->S) {
-            m->release(); delete m;
+            delete m;
             return set_err("model '%s': GRU layer %d has wrong shapes", name, l);
         }
         /* a weight the fp16 pieces cannot hold (|w| >= 255): this layer runs on the exact-fp32 kernels
          * (k_affine<.., F32> + k_gru_lanes / k_gru) instead -- slower, same results as the reference's fp32 */
         m->layer_f32[l] = !(in_split_range(*mi) && in_split_range(*ms) && in_split_range(*ms2)) || e->dbg_force_f32;
         if (m->layer_f32[l] && !(std::isfinite(max_abs(*mi)) && std::isfinite(max_abs(*ms)) && std::isfinite(max_abs(*ms2)))) {
-            m->release(); delete m;
+            delete m;
             return set_err("model '%s': GRU layer %d holds a non-finite weight", name, l);
         }
         if (m->layer_f32[l] && !e->dbg_force_f32)
@@ -147,13 +147,13 @@ static int load_model_mem_one(scrappie_hip_engine *e, const char *name, const vo
         int mt, mt_s;
         std::vector<float> ifr = make_frags(*mi, mt);
         if (upload(m->iW[l], ifr) || upload(m->ib[l], make_bias_frags(*mb, mt)) ||
-            upload(m->sW[l], make_frags(*ms, mt_s)) || upload(m->sW2[l], make_frags(*ms2, mt_s))) { m->release(); delete m; return -1; }
+            upload(m->sW[l], make_frags(*ms, mt_s)) || upload(m->sW2[l], make_frags(*ms2, mt_s))) { delete m; return -1; }
         if ((mi->nr % 32 == 0 && (upload_u32(m->iWp[l], make_piece_frags(*mi)) || upload(m->ibs[l], scaled(make_bias_frags(*mb, mt), SH_OSCALE)))) ||
-            (m->S % 32 == 0 && (upload_u32(m->sWp[l], make_piece_frags(*ms)) || upload_u32(m->sW2p[l], make_piece_frags(*ms2))))) { m->release(); delete m; return -1; }
+            (m->S % 32 == 0 && (upload_u32(m->sWp[l], make_piece_frags(*ms)) || upload_u32(m->sW2p[l], make_piece_frags(*ms2))))) { delete m; return -1; }
 #ifdef SH_EXPERIMENTS
         if (m->S == 96 && I == 96 && !m->layer_f32[l]) {      /* k_gru_proj32 */
             if (upload_u32(m->iWp32[l], make_piece_frags32(*mi)) || upload_u32(m->sWp32[l], make_piece_frags32(*ms)) ||
-                upload_u32(m->sW2p32[l], make_piece_frags32(*ms2)) || upload(m->ib32[l], make_bias32(*mb))) { m->release(); delete m; return -1; }
+                upload_u32(m->sW2p32[l], make_piece_frags32(*ms2)) || upload(m->ib32[l], make_bias32(*mb))) { delete m; return -1; }
             m->has32 = true;
         }
 #endif
@@ -167,24 +167,24 @@ static int load_model_mem_one(scrappie_hip_engine *e, const char *name, const vo
             snprintf(nm, sizeof nm, "ff%d_Wb", k + 1); wb = find_mat(mats, nm);
             snprintf(nm, sizeof nm, "ff%d_b", k + 1); bb = find_mat(mats, nm);
             if (!wf || !wb || !bb || wf->nr != m->S || wb->nr != m->S || wf->nc != m->S || wb->nc != m->S || bb->nr * bb->nc != m->S) {
-                m->release(); delete m;
+                delete m;
                 return set_err("model '%s': FF%d has wrong shapes (need S x S)", name, k + 1);
             }
             for (const HostMat *x : {wf, wb}) if (!in_split_range(*x)) {
                 const float mx = max_abs(*x);
-                m->release(); delete m;
+                delete m;
                 return set_err("model '%s': FF%d has a weight of magnitude %g, outside the split products' range (< %g); "
                                "there is no exact-fp32 kernel for this layer", name, k + 1, mx, (double)SH_W_LIMIT);
             }
             const int mt = (m->S + 15) / 16;
             /* as fp16 pieces (split products), the bias in accumulator units */
             if (upload_u32(m->ff2W[k][0], make_piece_frags(*wf)) || upload_u32(m->ff2W[k][1], make_piece_frags(*wb)) ||
-                upload(m->ff2b[k], scaled(make_bias_frags(*bb, mt), SH_OSCALE))) { m->release(); delete m; return -1; }
+                upload(m->ff2b[k], scaled(make_bias_frags(*bb, mt), SH_OSCALE))) { delete m; return -1; }
         }
     }
     if (m->S % 32 == 0 && !in_split_range(*fw)) {
         const float mx = max_abs(*fw);
-        m->release(); delete m;
+        delete m;
         return set_err("model '%s': the output layer has a weight of magnitude %g, outside the split products' range (< %g); "
                        "there is no exact-fp32 kernel for this layer", name, mx, (double)SH_W_LIMIT);
     }
@@ -200,8 +200,8 @@ static int load_model_mem_one(scrappie_hip_engine *e, const char *name, const vo
         }
         m->ff_no_clamp = worst < 88.0;
     }
-    if (upload(m->ffW, make_frags(*fw, m->ff_mtiles)) || upload(m->ffb, make_bias_frags(*fb, m->ff_mtiles))) { m->release(); delete m; return -1; }
-    if (m->S % 32 == 0 && (upload_u32(m->ffWp, make_piece_frags(*fw)) || upload(m->ffbs, scaled(make_bias_frags(*fb, m->ff_mtiles), SH_OSCALE)))) { m->release(); delete m; return -1; }
+    if (upload(m->ffW, make_frags(*fw, m->ff_mtiles)) || upload(m->ffb, make_bias_frags(*fb, m->ff_mtiles))) { delete m; return -1; }
+    if (m->S % 32 == 0 && (upload_u32(m->ffWp, make_piece_frags(*fw)) || upload(m->ffbs, scaled(make_bias_frags(*fb, m->ff_mtiles), SH_OSCALE)))) { delete m; return -1; }
     if (m->arch == 3) {
         m->min_samples = 2;                       /* lstm_forward needs two columns (layers.c:697) */
     } else {
@@ -215,7 +215,7 @@ static int load_model_mem_one(scrappie_hip_engine *e, const char *name, const vo
     }
     std::lock_guard<std::mutex> lk(e->mu);
     for (size_t i = 0; i < e->models.size(); i++)
-        if (e->models[i]->name == name) { e->models[i]->release(); delete e->models[i]; e->models[i] = m; return (int)i; }
+        if (e->models[i]->name == name) { delete e->models[i]; e->models[i] = m; return (int)i; }
     e->models.push_back(m);
     return (int)e->models.size() - 1;
 }
@@ -255,17 +255,18 @@ extern "C" int scrappie_hip_model_stride(scrappie_hip_engine *e, int model) {
     return m ? m->stride : -1;
 }
 extern "C" void scrappie_hip_set_profiling(scrappie_hip_engine *e, int on) { if (e) e->profiling = on != 0; }
-static int resolve_spans(scrappie_hip_engine *e, int slot) {
-    /* all events of `slot` have completed (caller waited on its done event or drained the stream) */
-    scrappie_hip_timing &tm = e->slot_timing[slot];
+static int resolve_spans(scrappie_hip_engine *e, Slot &sl) {
+    /* all events of the slot have completed (caller waited on its done event or drained the stream) */
+    scrappie_hip_timing &tm = sl.timing;
     float dbg_wait = 0.f, dbg_lead = 0.f;
-    float *fields[] = {&tm.conv_ms, &tm.affine_ms, &tm.gru_ms, &tm.ff_ms, &tm.decode_ms, &tm.backtrace_ms, &tm.total_ms, &tm.fused_ms, &tm.stitch_ms, &dbg_wait, &dbg_lead};
-    for (auto &sp : e->spans[slot]) {
+    float *fields[F_COUNT] = {&tm.conv_ms, &tm.affine_ms, &tm.gru_ms, &tm.ff_ms, &tm.decode_ms, &tm.backtrace_ms, &tm.total_ms, &tm.fused_ms, &tm.stitch_ms,
+                              &dbg_wait, &dbg_lead};      /* in the order of SpanField */
+    for (auto &sp : sl.spans) {
         float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, e->ev[slot][sp.i], e->ev[slot][sp.j]));
+        HIPCHK(hipEventElapsedTime(&ms, sl.ev[sp.i], sl.ev[sp.j]));
         *fields[sp.field] += ms;
     }
-    e->spans[slot].clear();
+    sl.spans.clear();
     if (tun().host_stamp) fprintf(stderr, "host stamp: main stream waited %.2f ms for the prologue; the convolution had ended %.2f ms before the main stream got there (negative: after)\n", dbg_wait, dbg_lead);
     e->timing = tm;
     return 0;
@@ -276,9 +277,10 @@ static int resolve_spans(scrappie_hip_engine *e, int slot) {
 extern "C" int scrappie_hip_get_timing(scrappie_hip_engine *e, scrappie_hip_timing *t) {
     if (!e || !t) return -1;
     (void)hipSetDevice(e->device);
-    if (!e->spans[e->cur].empty() && !e->pending[e->cur]) {
+    Slot &sl = e->current();
+    if (!sl.spans.empty() && !sl.pending) {
         HIPCHK(sh_stream_wait(e->stream));
-        if (resolve_spans(e, e->cur)) return -1;
+        if (resolve_spans(e, sl)) return -1;
     }
     *t = e->timing;
     return 0;

@@ -239,17 +239,18 @@ static int map_group(scrappie_hip_engine *e, Model *m, const raw_table *reads, c
         off[k] = total; len[k] = (uint32_t)map_read_nsample(m, rt);
         total += rt.end - rt.start;
     }
-    if (e->h_sig[0].ensure(total * 4) || e->d_signal[0].ensure(total * 4)) return -1;
-    float *hs = e->h_sig[0].as<float>();
+    Slot &st = e->slots[0];                /* staged in the first slot's buffers (nothing else is in flight under mu) */
+    if (st.h_sig.ensure(total * 4) || st.d_signal.ensure(total * 4)) return -1;
+    float *hs = st.h_sig.as<float>();
     for (size_t k = 0; k < cnt; k++) { const raw_table &rt = reads[idx[k]]; memcpy(hs + off[k], rt.raw + rt.start, (rt.end - rt.start) * 4); }
     const auto t0 = std::chrono::steady_clock::now();
-    HIPCHK(hipMemcpyAsync(e->d_signal[0].p, hs, total * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(st.d_signal.p, hs, total * 4, hipMemcpyHostToDevice, e->stream));
     HIPCHK(sh_stream_wait(e->stream));        /* (the group's prologue runs on another stream: the signals must be there first) */
     RunOut ro;
-    if (run_pipeline(e, m, e->d_signal[0].as<float>(), off.data(), len.data(), cnt, p, STOP_POST, 5, &ro)) return -1;
-    const LaunchGroup &lg = e->lgs[e->cur];
+    if (run_pipeline(e, m, st.d_signal.as<float>(), off.data(), len.data(), cnt, p, STOP_POST, 5, &ro)) return -1;
+    const Slot &sl = e->current(); const LaunchGroup &lg = sl.lg;
     std::vector<unsigned> bad(lg.npad, 0);
-    HIPCHK(hipMemcpyAsync(bad.data(), e->d_bad[e->cur].p, lg.npad * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(bad.data(), sl.d_bad.p, lg.npad * 4, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(sh_stream_wait(e->stream));
     e->map_ms[0] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     std::vector<long long> tile_boff(lg.ntile, 0);

@@ -57,24 +57,25 @@ static void posterior_batch(scrappie_hip_engine *e, std::vector<PostReq *> &reqs
     }
     if (live.empty()) return;
     auto fail_all = [&]() { for (PostReq *r : live) if (!r->src) post_fail(r, "%s", g_err); };
-    if (e->h_sig[0].ensure(total * 4) || e->d_signal[0].ensure(total * 4)) { fail_all(); return; }
-    float *hs = e->h_sig[0].as<float>();
+    Slot &st = e->slots[0];                /* staged in the first slot's buffers (nothing else is in flight under mu) */
+    if (st.h_sig.ensure(total * 4) || st.d_signal.ensure(total * 4)) { fail_all(); return; }
+    float *hs = st.h_sig.as<float>();
     for (size_t i = 0; i < live.size(); i++) memcpy(hs + off[i], live[i]->sig.raw + live[i]->sig.start, (live[i]->sig.end - live[i]->sig.start) * 4);
     /* (the group's prologue -- the convolution -- runs on another stream: the signals must be there before it is enqueued) */
-    if (hipMemcpyAsync(e->d_signal[0].p, hs, total * 4, hipMemcpyHostToDevice, e->stream) != hipSuccess || sh_stream_wait(e->stream) != hipSuccess) {
+    if (hipMemcpyAsync(st.d_signal.p, hs, total * 4, hipMemcpyHostToDevice, e->stream) != hipSuccess || sh_stream_wait(e->stream) != hipSuccess) {
         set_err("upload failed: %s", hipGetErrorString(hipGetLastError())); fail_all(); return;
     }
     scrappie_hip_params p = scrappie_hip_default_params();
     p.tempW = live[0]->tempW; p.tempb = live[0]->tempb;
     RunOut ro;
-    if (run_pipeline(e, m, e->d_signal[0].as<float>(), off.data(), len.data(), live.size(), &p, live[0]->stop, live[0]->upto, &ro)) { fail_all(); return; }
+    if (run_pipeline(e, m, st.d_signal.as<float>(), off.data(), len.data(), live.size(), &p, live[0]->stop, live[0]->upto, &ro)) { fail_all(); return; }
     /* what is gathered: the posterior where S1 left it (finalised here for the transducers; the CRF's transitions are final), or the trunk's activations */
     const float *src = trunk ? ro.act : ro.E;
     const int nr = trunk ? ro.act_units : m->NS, nchunk = trunk ? ro.act_units / 16 : m->ff_mtiles;
     const bool tr = !trunk && m->arch != 1;
-    const LaunchGroup &lg = e->lgs[e->cur];
+    const Slot &sl = e->current(); const LaunchGroup &lg = sl.lg;
     std::vector<unsigned> bad(lg.npad, 0);
-    if (hipMemcpyAsync(bad.data(), e->d_bad[e->cur].p, lg.npad * 4, hipMemcpyDeviceToHost, e->stream) != hipSuccess || sh_stream_wait(e->stream) != hipSuccess) {
+    if (hipMemcpyAsync(bad.data(), sl.d_bad.p, lg.npad * 4, hipMemcpyDeviceToHost, e->stream) != hipSuccess || sh_stream_wait(e->stream) != hipSuccess) {
         set_err("reading the range flags failed: %s", hipGetErrorString(hipGetLastError())); fail_all(); return;
     }
     std::vector<long long> tile_boff(lg.ntile, 0);
@@ -327,8 +328,10 @@ struct DecReq {
     int phase = 0;                  /* 0 queued, 1 asked to copy its posterior to `dst`, 2 copied, 3 done */
     float *dst = nullptr;
 };
-/* the queue's pinned input buffer: sized by the leader, filled by the members of the launch in preparation (one leader at a time), read by that launch */
-struct DecCoalescer : ShCoalescer<DecReq> { HBuf stage; };
+/* the queue's pinned input buffer: sized by the leader, filled by the members of the launch in preparation (one leader at a time), read by that launch.
+ * The queue has static storage and an HBuf frees its memory when it is destroyed, so the buffer lives behind a reference to an object that is never
+ * deleted: no HIP call while the process exits (the process-default engine is never destroyed for the same reason).  g_co and g_cc hold no buffer. */
+struct DecCoalescer : ShCoalescer<DecReq> { HBuf &stage = *new HBuf; };
 static DecCoalescer g_dc;
 
 /* The requests share shape and penalties.  `staged`: their posteriors concatenated in pinned memory, read k at the column offset the reads before it add up

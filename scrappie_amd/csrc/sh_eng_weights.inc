@@ -37,14 +37,6 @@ struct Model {
     DBuf lp[4];                          /* events: LSTM peepholes [update | forget | output] in accumulator layout */
     int nfeat = 0;                       /* events: input features per event (12), padded to F = 16 */
     bool layer_f32[5] = {false, false, false, false, false};   /* GRU layer has a weight outside the split products' range: exact-fp32 kernels */
-    void release() {
-        conv_W.release(); conv_b.release(); ffW.release(); ffb.release();
-        for (int l = 0; l < 5; l++) { iW[l].release(); ib[l].release(); sW[l].release(); sW2[l].release(); iWp[l].release(); sWp[l].release(); sW2p[l].release(); }
-        ffWp.release(); ffbs.release();
-        for (int l = 0; l < 5; l++) { ibs[l].release(); iWp32[l].release(); sWp32[l].release(); sW2p32[l].release(); ib32[l].release(); }
-        for (int k = 0; k < 2; k++) { ff2W[k][0].release(); ff2W[k][1].release(); ff2b[k].release(); }
-        for (int l = 0; l < 4; l++) lp[l].release();
-    }
 };
 
 /* MFMA A fragments of an (M x K) weight matrix given as rows m (output unit)

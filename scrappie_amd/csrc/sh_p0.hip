@@ -50,13 +50,9 @@ extern "C" void scrappie_hip_prep_destroy(scrappie_hip_prep *p) {
     if (!p) return;
     (void)hipSetDevice(p->device);
     (void)sh_stream_wait(p->stream);
-    for (auto &s : p->slot) {
-        s.h_sig.release(); s.h_meta.release(); s.h_win.release();
-        s.d_sig.release(); s.d_scratch.release(); s.d_meta.release(); s.d_win.release();
-    }
     if (p->ev_ok) for (auto &e : p->ev) (void)hipEventDestroy(e);
     (void)hipStreamDestroy(p->stream);
-    delete p;
+    delete p;      /* (the slots' buffers go with it) */
 }
 
 extern "C" void *scrappie_hip_prep_begin(scrappie_hip_prep *p, int slot, size_t capacity_samples) {
@@ -139,8 +135,7 @@ extern "C" int scrappie_hip_prep_run(scrappie_hip_prep *p, int slot, const raw_t
         HBuf nb;
         if (nb.ensure(std::max<size_t>(total, 1) * 4)) return -1;
         if (used && hs0) memcpy(nb.p, hs0, used * 4);
-        S.h_sig.release();
-        S.h_sig = nb;
+        S.h_sig = std::move(nb);
     }
     S.total = total;
     *d_signal = S.d_sig.as<float>();
