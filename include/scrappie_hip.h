@@ -170,6 +170,19 @@ float map_to_sequence_viterbi_banded(const_scrappie_matrix logpost, float stay_p
  * ACGT/acgt and (the reference is undefined there) when n < state_len */
 int *encode_bases_to_integers(char const *seq, size_t n, size_t state_len);
 
+/* Mapping of a raw signal to a predicted squiggle (src/decode.c:1035, :1262; python/pyscrap.h:33-39).  Same signatures; the
+ * dynamic programme runs on the process-default engine as a batch of one (sh_squig.h; calls from several threads
+ * serialise on the engine).  params: the reference's predicted squiggle, nc = npos columns of (mean, log sd, dwell logit).
+ * signal: trimmed and normalised, mapped over [start, end); path_padded: signal.n int32, -1 outside [start, end) and in
+ * the START / END states, positions elsewhere.  The Viterbi score and path are bit-identical to the reference's; forward
+ * agrees to float rounding.  Where the reference asserts or is undefined (rate <= 0, prob_back outside [0, 1],
+ * start >= end, end > n, a squiggle of no positions, NULL arguments) these return NAN, set scrappie_hip_last_error() and
+ * launch nothing.  The squiggle itself (squiggle_r94 and its relatives) is not built: it is an input here. */
+float squiggle_match_viterbi(const raw_table signal, float rate, const_scrappie_matrix params, float prob_back, float local_pen,
+                             float skip_pen, float minscore, int32_t *path_padded);
+float squiggle_match_forward(const raw_table signal, float rate, const_scrappie_matrix params, float prob_back, float local_pen,
+                             float skip_pen, float minscore);
+
 /* ------------------------------------------------------------------------
  * (2) Batched engine surface (additive)
  * ---------------------------------------------------------------------- */
@@ -406,6 +419,27 @@ void scrappie_hip_free_map_results(scrappie_hip_map_result *r, size_t n);
 /* the last scrappie_hip_map_batch call's time, milliseconds summed over its launch groups: [0] network + S1, [1] k_map,
  * [2] k_map_walk + results to the host (host clock, the stream drained between the stages) */
 void scrappie_hip_map_timing(scrappie_hip_engine *e, double out[3]);
+
+/* Squiggle matching, batched (sh_eng_squig.inc): reads[i] (trimmed, normalised; mapped over [start, end)) against
+ * targets[i], a predicted squiggle of npos columns of stride >= 3 floats (mean, log sd, dwell logit); out[i] belongs to
+ * reads[i].  No network runs and no model is needed.  viterbi 0: forward scores.  want_path (Viterbi only): out[i].path
+ * is the reference's path_padded, malloc'd, out[i].n = reads[i].n int32.  The call is cut into launches whose
+ * traceback (samples x positions / 2 bytes per read) and scratch fit half of the device memory that is free; a single
+ * read that does not fit gets NAN and an error text, as does one the per-read functions refuse, and the others are
+ * untouched.  p NULL: scrappie_hip_default_squiggle_params() (scrappy's defaults); an invalid rate or prob_back fails the
+ * call.  Returns 0, or -1 with scrappie_hip_last_error() when the call as a whole fails.  A launch holds the engine's lock. */
+typedef struct { const float *params; size_t npos, stride; } scrappie_hip_squiggle_target;
+typedef struct { float rate, prob_back, local_pen, skip_pen, minscore; } scrappie_hip_squiggle_params;
+typedef struct { float score; size_t n; int32_t *path; } scrappie_hip_squiggle_result;
+scrappie_hip_squiggle_params scrappie_hip_default_squiggle_params(void);
+int scrappie_hip_squiggle_match_batch(scrappie_hip_engine *e, const raw_table *reads, const scrappie_hip_squiggle_target *targets, size_t n,
+                                      const scrappie_hip_squiggle_params *p, int viterbi, int want_path, scrappie_hip_squiggle_result *out);
+void scrappie_hip_free_squiggle_results(scrappie_hip_squiggle_result *r, size_t n);
+/* the last scrappie_hip_squiggle_match_batch call's time, milliseconds summed over its launches: [0] tables on the host +
+ * uploads, [1] k_squig, [2] k_squig_walk + results to the host (host clock, the stream drained between the stages) */
+void scrappie_hip_squiggle_timing(scrappie_hip_engine *e, double out[3]);
+/* positions up to which k_squig keeps its score rows and tables in LDS; longer squiggles keep the rows in device scratch */
+size_t scrappie_hip_squiggle_lds_max_pos(void);
 
 /* Measurement / test hook for SURVEY.md 8(d) "decode driven by HMM-simulated posteriors" (synthetic
  * weights decode to a handful of bases per read, which leaves the decode -> D2H -> homopolymer ->

@@ -61,6 +61,19 @@ class _MapResult(C.Structure):
     _fields_ = [("score", C.c_float), ("nblock", C.c_size_t), ("path", C.POINTER(C.c_int32))]
 
 
+class _SquigTarget(C.Structure):
+    _fields_ = [("params", C.POINTER(C.c_float)), ("npos", C.c_size_t), ("stride", C.c_size_t)]
+
+
+class _SquigParams(C.Structure):
+    _fields_ = [("rate", C.c_float), ("prob_back", C.c_float), ("local_pen", C.c_float), ("skip_pen", C.c_float),
+                ("minscore", C.c_float)]
+
+
+class _SquigResult(C.Structure):
+    _fields_ = [("score", C.c_float), ("n", C.c_size_t), ("path", C.POINTER(C.c_int32))]
+
+
 class Timing(C.Structure):
     _fields_ = [("conv_ms", C.c_float), ("affine_ms", C.c_float), ("gru_ms", C.c_float),
                 ("ff_ms", C.c_float), ("decode_ms", C.c_float), ("backtrace_ms", C.c_float),
@@ -228,6 +241,15 @@ def lib():
                                          C.POINTER(Params), C.c_int, C.c_int, C.POINTER(_MapResult)]
     L.scrappie_hip_free_map_results.argtypes = [C.POINTER(_MapResult), C.c_size_t]
     L.scrappie_hip_map_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    L.squiggle_match_viterbi.restype = C.c_float
+    L.squiggle_match_viterbi.argtypes = [_RawTable, C.c_float, PM, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_int32)]
+    L.squiggle_match_forward.restype = C.c_float
+    L.squiggle_match_forward.argtypes = [_RawTable, C.c_float, PM, C.c_float, C.c_float, C.c_float, C.c_float]
+    L.scrappie_hip_squiggle_match_batch.argtypes = [C.c_void_p, C.POINTER(_RawTable), C.POINTER(_SquigTarget), C.c_size_t,
+                                                    C.POINTER(_SquigParams), C.c_int, C.c_int, C.POINTER(_SquigResult)]
+    L.scrappie_hip_free_squiggle_results.argtypes = [C.POINTER(_SquigResult), C.c_size_t]
+    L.scrappie_hip_squiggle_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    L.scrappie_hip_squiggle_lds_max_pos.restype = C.c_size_t
     _lib = L
     return L
 
@@ -533,6 +555,51 @@ def map_post_to_sequence(post, sequence, stay_pen=0, skip_pen=0, local_pen=4.0, 
     if np.isnan(score):
         raise RuntimeError('An unknown error occurred during alignment: ' + last_error())
     return score, path_data
+
+
+def _squiggle_matrix(squiggle):
+    """a predicted squiggle as a ScrappyMatrix of npos columns (mean, log sd, dwell logit): one as it is, an (npos, 3)
+    array converted; a base sequence would need the squiggle-predicting network, which is not built"""
+    if isinstance(squiggle, str):
+        raise NotImplementedError("squiggle prediction (sequence_to_squiggle) is not built: pass the predicted squiggle, "
+                                  "a ScrappyMatrix or an (npos, 3) array of (mean, log sd, dwell logit)")
+    if isinstance(squiggle, ScrappyMatrix):
+        return squiggle
+    a = np.asarray(squiggle, dtype=ftype)
+    if a.ndim != 2 or a.shape[1] != 3 or a.shape[0] == 0:
+        raise ValueError("`squiggle` should be a ScrappyMatrix or an (npos, 3) array.")
+    return ScrappyMatrix.from_numpy(a, sloika=False)
+
+
+def squiggle_match(rt, squiggle, rate=1.0, back_prob=0.0, local_pen=2.0, skip_pen=5000.0, min_score=5.0, viterbi=True,
+                   path=True):
+    """squiggle_match_viterbi / squiggle_match_forward (decode.c:1035, :1262) on the GPU: the `RawTable` rt as it is (no
+    trimming), mapped over [rt.start, rt.end), against a predicted squiggle.  Returns (score, path or None); the path has
+    rt's full length, -1 outside the window and in the START / END states."""
+    if path and not viterbi:
+        raise ValueError('Cannot calulate path with `viterbi==False`.')
+    if not isinstance(rt, RawTable):
+        raise TypeError('`rt` should be a RawTable.')
+    sq = _squiggle_matrix(squiggle)
+    if viterbi:
+        path_data = np.zeros(rt._rt.n, dtype=np.int32)
+        score = lib().squiggle_match_viterbi(rt.data(), rate, sq.data(), back_prob, local_pen, skip_pen, min_score,
+                                             path_data.ctypes.data_as(C.POINTER(C.c_int32)))
+    else:
+        path_data = None
+        score = lib().squiggle_match_forward(rt.data(), rate, sq.data(), back_prob, local_pen, skip_pen, min_score)
+    if np.isnan(score):
+        raise RuntimeError('An unknown error occurred during alignment: ' + last_error())
+    return score, (path_data if path else None)
+
+
+def map_signal_to_squiggle(data, squiggle, rate=1.0, back_prob=0.0, local_pen=2.0, skip_pen=5000.0, min_score=5.0):
+    """python/scrappy/__init__.py:462-489 with the predicted squiggle (a `ScrappyMatrix` or an (npos, 3) array) in place
+    of (sequence, model): trim -> scale -> squiggle_match_viterbi.  Returns (score, path over the whole of `data`)."""
+    sq = _squiggle_matrix(squiggle)
+    raw = RawTable(data)
+    raw.trim().scale()
+    return squiggle_match(raw, sq, rate, back_prob, local_pen, skip_pen, min_score, viterbi=True, path=True)
 
 
 def plan_tail(lengths, stride, max_long_blocks=0):
@@ -971,6 +1038,52 @@ class Engine(object):
         t = (C.c_double * 3)()
         lib().scrappie_hip_map_timing(self._h, t)
         return dict(network_ms=t[0], map_ms=t[1], walk_ms=t[2])
+
+    def match_squiggle(self, signals, squiggles, viterbi=True, path=False, rate=1.0, back_prob=0.0, local_pen=2.0,
+                       skip_pen=5000.0, min_score=5.0):
+        """Each signal (trimmed, normalised float32 array, or a `RawTable` with its window) against its predicted squiggle
+        (an (npos, 3) array of mean, log sd, dwell logit), batched (scrappie_hip_squiggle_match_batch).  Returns
+        [(score, path or None)] in input order; score NaN where a read cannot be mapped."""
+        n = len(signals)
+        if len(squiggles) != n:
+            raise ValueError("one squiggle per signal")
+        if path and not viterbi:
+            raise ValueError('Cannot calulate path with `viterbi==False`.')
+        keep = []
+        rts = (_RawTable * n)()
+        tgs = (_SquigTarget * n)()
+        for i, (x, sq) in enumerate(zip(signals, squiggles)):
+            if isinstance(x, RawTable):
+                keep.append(x)
+                rts[i] = x.data()
+            else:
+                x = np.ascontiguousarray(x, dtype=ftype)
+                keep.append(x)
+                rts[i] = _RawTable(None, len(x), 0, len(x), x.ctypes.data_as(C.POINTER(C.c_float)))
+            if isinstance(sq, str):
+                _squiggle_matrix(sq)
+            sq = np.ascontiguousarray(sq, dtype=ftype)
+            if sq.ndim != 2 or sq.shape[1] < 3:
+                raise ValueError("a squiggle should be an (npos, 3) array")
+            keep.append(sq)
+            tgs[i] = _SquigTarget(sq.ctypes.data_as(C.POINTER(C.c_float)), sq.shape[0], sq.shape[1])
+        p = _SquigParams(rate, back_prob, local_pen, skip_pen, min_score)
+        out = (_SquigResult * n)()
+        if lib().scrappie_hip_squiggle_match_batch(self._h, rts, tgs, n, C.byref(p), 1 if viterbi else 0, 1 if path else 0, out) != 0:
+            raise RuntimeError("squiggle_match_batch: " + last_error())
+        res = []
+        for i in range(n):
+            r = out[i]
+            pth = np.ctypeslib.as_array(r.path, shape=(r.n,)).copy() if r.path else None
+            res.append((float(r.score), pth))
+        lib().scrappie_hip_free_squiggle_results(out, n)
+        return res
+
+    def squiggle_timing(self):
+        """the last match_squiggle call's time (ms, summed over launches): tables + uploads, k_squig, walk + results"""
+        t = (C.c_double * 3)()
+        lib().scrappie_hip_squiggle_timing(self._h, t)
+        return dict(tables_ms=t[0], match_ms=t[1], walk_ms=t[2])
 
     def trunk(self, signal, model='rgrgr_r94', upto=5):
         rt = RawTable(signal)

@@ -35,6 +35,7 @@
  *   sh_eng_debug.inc     measurement / test hooks
  *   sh_eng_surface.inc   the reference's per-read functions: one batch function per family, run by the queue or with a batch of one
  *   sh_eng_map.inc       block-based mapping of posteriors to sequences (per-read and batched)
+ *   sh_eng_squig.inc     mapping of raw signals to predicted squiggles (per-read and batched)
  * Separate translation units: sh_p0.hip (signal preparation, k_p0), sh_host.c / sh_fast5.c / sh_h5mini.c (host C);
  * sh_coalesce.h (the per-read functions' queue) and sh_dev.h (DBuf / HBuf: buffers that own their memory) are plain C++ headers.
  */
@@ -66,6 +67,7 @@
 #include "sh_dev.h"
 #include "sh_coalesce.h"
 #include "sh_map.h"
+#include "sh_squig.h"
 
 /* function attributes (dynamic LDS limit) are per device: remember for which devices a kernel has had its attribute set
  * (engines on several GPUs may share one process).  A real once per device: the thread that finds the attribute unset holds
@@ -379,6 +381,9 @@ struct scrappie_hip_engine {
     HBuf h_crf_in, h_crf_out; DBuf d_crf[4];             /* crf_batch */
     DBuf d_map[10]; HBuf h_map;      /* block-based mapping (sh_eng_map.inc): per-read tables, codes, bands, traceback, scratch, scores, paths, posterior */
     double map_ms[3] = {0, 0, 0};    /* scrappie_hip_map_batch: network + S1, k_map, k_map_walk + results, summed over the last call's launch groups */
+    DBuf d_sq[9]; HBuf h_sq;         /* squiggle matching (sh_eng_squig.inc): records, signals, tables, traceback, scratch, scores, final states, path offsets, paths */
+    double squig_ms[3] = {0, 0, 0};  /* scrappie_hip_squiggle_match_batch: tables + uploads, k_squig, k_squig_walk + results, summed over the last call's launches */
+    size_t dbg_squig_budget = 0;     /* device bytes one squiggle-matching launch may hold (debug option "squiggle_budget_kb"; 0: half of the free memory) */
     std::mutex call_mu;              /* scrappie_hip_basecall_batch: one call at a time inside the engine (concurrent small calls share one: sh_eng_batch.inc) */
     /* (scrappie_hip_engine_destroy has made the device current and drained the streams; the slots and the buffers go after this body) */
     ~scrappie_hip_engine() {
@@ -511,3 +516,4 @@ extern "C" scrappie_hip_params scrappie_hip_default_params(void) {
 #include "sh_eng_debug.inc"      /* measurement / test hooks: decoder and trunk inputs, debug_option / debug_fetch / debug_stitch */
 #include "sh_eng_surface.inc"      /* the reference's per-read functions: posterior / trunk on an explicit engine, the process-default engine, decode_transducer, decode_crf; all three coalesced (sh_coalesce.h) */
 #include "sh_eng_map.inc"      /* block-based mapping (sh_map.h): map_to_sequence_* on the process-default engine, scrappie_hip_map_batch */
+#include "sh_eng_squig.inc"      /* squiggle matching (sh_squig.h): squiggle_match_* on the process-default engine, scrappie_hip_squiggle_match_batch */

@@ -1,0 +1,260 @@
+/* sh_eng_squig.inc -- part of scrappie_hip.hip (one translation unit, included from there in this order; not compiled alone):
+ * mapping of raw signals to predicted squiggles (sh_squig.h).  scrappie_hip_squiggle_match_batch cuts a call into launches
+ * whose traceback and scratch fit a share of the free device memory; a launch is tables on the host (sh_host.c) -> uploads
+ * -> k_squig -> k_squig_walk -> scores and paths back.  The reference's squiggle_match_viterbi / _forward are a batch of one
+ * on the process-default engine.  No network runs and no model is needed. */
+
+/* host side of one launch: the reads' records, their signals and tables laid end to end, traceback / scratch offsets */
+struct SquigPlan {
+    std::vector<ShSquigRead> rd;
+    std::vector<size_t> who;              /* index of each read in the call */
+    std::vector<long long> path_off;      /* per read, -1: no path */
+    long long sig_floats = 0, tab_floats = 0, tb_words = 0, scr_floats = 0, path_len = 0;
+    size_t lds = SH_SQ_LDS_HEAD * 4;
+    size_t bytes = 0;                     /* device bytes the launch holds so far */
+    void clear() { *this = SquigPlan(); }
+};
+
+static size_t squig_lds_bytes(size_t npos) { return (SH_SQ_LDS_HEAD + 2 * (2 * npos + 1) + 5 * npos + 4) * 4; }
+/* code words (8 ceil(npos / 64) per sample) + END's source (one int32 per sample), rounded to whole 16-byte pieces */
+static long long squig_tb_words(size_t npos, size_t nsample) {
+    return (long long)nsample * sh_squig_words((int)npos) + (long long)((nsample + 3) & ~(size_t)3);
+}
+static long long squig_scr_floats(size_t npos) { return (long long)((2 * (2 * npos + 1) + 3) & ~(size_t)3); }
+/* device bytes one read adds to a launch (signal, tables, traceback, path, scratch) */
+static size_t squig_read_bytes(size_t npos, size_t nsample, bool path) {
+    size_t b = nsample * 4 + (5 * npos + 4) * 4 + sizeof(ShSquigRead) + 64;
+    if (path) b += (size_t)squig_tb_words(npos, nsample) * 4 + nsample * 4;
+    if (npos > SH_SQ_LDS_MAX_POS) b += (size_t)squig_scr_floats(npos) * 4;
+    return b;
+}
+
+static void squig_plan_add(SquigPlan &pl, size_t who, size_t nsample, size_t npos, bool path) {
+    ShSquigRead r{};
+    r.nsample = (int)nsample; r.npos = (int)npos; r.ok = 1;
+    r.sig = pl.sig_floats; pl.sig_floats += (long long)nsample;
+    r.tab = pl.tab_floats; pl.tab_floats += (long long)(5 * npos + 4);
+    r.tb = -1;
+    if (path) {
+        r.tb = pl.tb_words; pl.tb_words += squig_tb_words(npos, nsample);
+        pl.path_off.push_back(pl.path_len); pl.path_len += (long long)nsample;
+    } else pl.path_off.push_back(-1);
+    if (npos <= SH_SQ_LDS_MAX_POS) { r.scr = -1; pl.lds = std::max(pl.lds, squig_lds_bytes(npos)); }
+    else { r.scr = pl.scr_floats; pl.scr_floats += squig_scr_floats(npos); }
+    pl.rd.push_back(r);
+    pl.who.push_back(who);
+    pl.bytes += squig_read_bytes(npos, nsample, path);
+}
+
+template <bool VIT>
+static void squig_launch_k(hipStream_t s, const ShSquigArgs &a, size_t n_lds, size_t n, size_t lds) {
+    if (n_lds) hipLaunchKernelGGL((k_squig<VIT, true>), dim3((unsigned)n_lds), dim3(SH_SQ_NTH), lds, s, a);
+    if (n > n_lds) {                     /* the reads whose rows live in scratch: the records' tail */
+        ShSquigArgs b = a;
+        b.rd += n_lds; b.score += n_lds; b.final_state += n_lds;
+        hipLaunchKernelGGL((k_squig<VIT, false>), dim3((unsigned)(n - n_lds)), dim3(SH_SQ_NTH), SH_SQ_LDS_HEAD * 4, s, b);
+    }
+}
+
+/* one launch: out[who] gets its score and, where the plan holds a path, its padded path (malloc'd, signal.n long) */
+static int squig_run(scrappie_hip_engine *e, SquigPlan &pl, const raw_table *reads, const scrappie_hip_squiggle_target *tg,
+                     const scrappie_hip_squiggle_params *p, bool vit, scrappie_hip_squiggle_result *out) {
+    const size_t n = pl.rd.size();
+    if (n == 0) return 0;
+    std::lock_guard<std::mutex> lk(e->mu);
+    hipStream_t s = e->stream;
+    DBuf *d = e->d_sq;           /* 0 reads, 1 signals, 2 tables, 3 traceback, 4 scratch, 5 scores, 6 final states, 7 path offsets, 8 paths */
+    const bool walk = vit && pl.path_len > 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    /* device order: the reads whose rows fit LDS first (one launch), then those in scratch (another) */
+    std::vector<size_t> perm(n);
+    std::iota(perm.begin(), perm.end(), (size_t)0);
+    std::stable_partition(perm.begin(), perm.end(), [&](size_t i) { return pl.rd[i].scr < 0; });
+    size_t n_lds = 0;
+    while (n_lds < n && pl.rd[perm[n_lds]].scr < 0) n_lds++;
+    const size_t up_floats = ((size_t)pl.sig_floats + (size_t)pl.tab_floats + 1) & ~(size_t)1;      /* (the records behind them are 8-byte aligned) */
+    if (d[0].ensure(n * sizeof(ShSquigRead)) || d[1].ensure((size_t)pl.sig_floats * 4 + 16) || d[2].ensure((size_t)pl.tab_floats * 4 + 16) ||
+        d[3].ensure((size_t)pl.tb_words * 4 + 16) || d[4].ensure((size_t)pl.scr_floats * 4 + 16) || d[5].ensure(n * 4) ||
+        d[6].ensure(n * 4) || d[7].ensure(n * 8) || d[8].ensure((size_t)pl.path_len * 4 + 16) ||
+        e->h_sq.ensure(std::max(up_floats * 4 + n * (sizeof(ShSquigRead) + 8), n * 4 + (size_t)pl.path_len * 4))) return -1;
+    /* staging (pinned): signals | tables | records | path offsets */
+    float *hsig = e->h_sq.as<float>(), *htab = hsig + pl.sig_floats;
+    ShSquigRead *hrd = (ShSquigRead *)(hsig + up_floats);
+    long long *hoff = (long long *)(hrd + n);
+    float pens[2] = {0.0f, 0.0f};
+    for (size_t k = 0; k < n; k++) {
+        const size_t i = perm[k];
+        const ShSquigRead &r = pl.rd[i];
+        const raw_table &rt = reads[pl.who[i]];
+        const scrappie_hip_squiggle_target &t = tg[pl.who[i]];
+        memcpy(hsig + r.sig, rt.raw + rt.start, (size_t)r.nsample * 4);
+        sh_squiggle_tables(t.params, t.npos, t.stride, p->rate, p->prob_back, htab + r.tab, pens);
+        hrd[k] = r; hoff[k] = pl.path_off[i];
+    }
+    HIPCHK(hipMemcpyAsync(d[1].p, hsig, (size_t)pl.sig_floats * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d[2].p, htab, (size_t)pl.tab_floats * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d[0].p, hrd, n * sizeof(ShSquigRead), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d[7].p, hoff, n * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(sh_stream_wait(s));
+    ShSquigArgs a{};
+    a.rd = d[0].as<ShSquigRead>(); a.sig = d[1].as<float>(); a.tab = d[2].as<float>(); a.tb = d[3].as<unsigned>(); a.scr = d[4].as<float>();
+    a.score = d[5].as<float>(); a.final_state = d[6].as<int>();
+    a.move_back_pen = pens[0]; a.half_pen = pens[1];
+    a.local_pen = p->local_pen; a.skip_pen = p->skip_pen; a.minscore = p->minscore;
+    const auto t1 = std::chrono::steady_clock::now();
+    if (vit) squig_launch_k<true>(s, a, n_lds, n, pl.lds); else squig_launch_k<false>(s, a, n_lds, n, pl.lds);
+    HIPCHK(hipGetLastError());
+    HIPCHK(sh_stream_wait(s));
+    const auto t2 = std::chrono::steady_clock::now();
+    if (walk) {
+        hipLaunchKernelGGL(k_squig_walk, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, (const ShSquigRead *)d[0].p, (int)n, (const unsigned *)d[3].p,
+                           (const int *)d[6].p, (const long long *)d[7].p, d[8].as<int>());
+        HIPCHK(hipGetLastError());
+    }
+    float *hs = e->h_sq.as<float>();
+    int32_t *hp = (int32_t *)(hs + n);
+    HIPCHK(hipMemcpyAsync(hs, d[5].p, n * 4, hipMemcpyDeviceToHost, s));
+    if (walk) HIPCHK(hipMemcpyAsync(hp, d[8].p, (size_t)pl.path_len * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(sh_stream_wait(s));
+    for (size_t k = 0; k < n; k++) {
+        const size_t i = perm[k];
+        scrappie_hip_squiggle_result &res = out[pl.who[i]];
+        const raw_table &rt = reads[pl.who[i]];
+        res.score = hs[k];
+        res.n = rt.n;
+        if (!walk || pl.path_off[i] < 0) continue;
+        res.path = (int32_t *)malloc(std::max<size_t>(rt.n, 1) * 4);
+        if (!res.path) return set_err("out of host memory");
+        for (size_t j = 0; j < rt.n; j++) res.path[j] = -1;
+        memcpy(res.path + rt.start, hp + pl.path_off[i], (size_t)pl.rd[i].nsample * 4);
+    }
+    const auto t3 = std::chrono::steady_clock::now();
+    e->squig_ms[0] += std::chrono::duration<double, std::milli>(t1 - t0).count();
+    e->squig_ms[1] += std::chrono::duration<double, std::milli>(t2 - t1).count();
+    e->squig_ms[2] += std::chrono::duration<double, std::milli>(t3 - t2).count();
+    return 0;
+}
+
+/* the checks a read and its squiggle pass before they reach a kernel; 0 or -1 with the reason */
+static int squig_read_ok(const char *fn, const raw_table &rt, const scrappie_hip_squiggle_target &t) {
+    if (!rt.raw) return set_err("%s: no signal", fn);
+    if (!t.params) return set_err("%s: no squiggle", fn);
+    if (rt.start >= rt.end) return set_err("%s: an empty signal window [%zu, %zu)", fn, rt.start, rt.end);
+    if (rt.end > rt.n) return set_err("%s: the signal window ends at %zu, past its %zu samples", fn, rt.end, rt.n);
+    if (rt.end - rt.start > (size_t)INT32_MAX / 2) return set_err("%s: %zu samples is too many", fn, rt.end - rt.start);
+    if (t.npos == 0) return set_err("%s: a squiggle of no positions", fn);
+    if (t.npos > SH_SQ_MAX_POS) return set_err("%s: a squiggle of %zu positions is longer than the %d this build maps", fn, t.npos, SH_SQ_MAX_POS);
+    if (t.stride < 3) return set_err("%s: a squiggle column holds %zu floats (3: mean, log sd, dwell logit)", fn, t.stride);
+    return 0;
+}
+static int squig_params_ok(const char *fn, const scrappie_hip_squiggle_params *p) {
+    if (!(p->rate > 0.0f)) return set_err("%s: rate %g is not positive", fn, (double)p->rate);
+    if (!(p->prob_back >= 0.0f && p->prob_back <= 1.0f)) return set_err("%s: prob_back %g is outside [0, 1]", fn, (double)p->prob_back);
+    return 0;
+}
+
+extern "C" scrappie_hip_squiggle_params scrappie_hip_default_squiggle_params(void) {
+    scrappie_hip_squiggle_params p;
+    p.rate = 1.0f; p.prob_back = 0.0f; p.local_pen = 2.0f; p.skip_pen = 5000.0f; p.minscore = 5.0f;       /* scrappy's map_signal_to_squiggle */
+    return p;
+}
+
+extern "C" size_t scrappie_hip_squiggle_lds_max_pos(void) { return SH_SQ_LDS_MAX_POS; }
+
+extern "C" void scrappie_hip_squiggle_timing(scrappie_hip_engine *e, double out[3]) {
+    for (int k = 0; k < 3; k++) out[k] = e ? e->squig_ms[k] : 0.0;
+}
+
+extern "C" void scrappie_hip_free_squiggle_results(scrappie_hip_squiggle_result *r, size_t n) {
+    if (!r) return;
+    for (size_t i = 0; i < n; i++) { free(r[i].path); r[i].path = nullptr; }
+}
+
+extern "C" int scrappie_hip_squiggle_match_batch(scrappie_hip_engine *e, const raw_table *reads, const scrappie_hip_squiggle_target *targets,
+                                                 size_t n, const scrappie_hip_squiggle_params *p, int viterbi, int want_path,
+                                                 scrappie_hip_squiggle_result *out) {
+    if (!e || (n && (!reads || !targets || !out))) return set_err("squiggle_match_batch: null argument");
+    for (size_t i = 0; i < n; i++) { out[i].score = NAN; out[i].n = 0; out[i].path = nullptr; }
+    const scrappie_hip_squiggle_params dp = scrappie_hip_default_squiggle_params();
+    if (!p) p = &dp;
+    if (squig_params_ok("squiggle_match_batch", p)) return -1;
+    (void)hipSetDevice(e->device);
+    { std::lock_guard<std::mutex> lk(e->mu); for (double &x : e->squig_ms) x = 0.0; }
+    const bool vit = viterbi != 0, path = vit && want_path != 0;
+    /* what a launch may hold: half of the device memory that is free now (the engine's own arena stays where it is) */
+    size_t budget = e->dbg_squig_budget;
+    if (!budget) {
+        size_t fr = 0, tot = 0;
+        budget = hipMemGetInfo(&fr, &tot) == hipSuccess ? fr / 2 : e->total_mem / 4;
+    }
+    std::vector<std::string> why(n);
+    SquigPlan pl;
+    int rc = 0;
+    auto flush = [&]() {
+        if (pl.rd.empty() || rc) return;
+        if (squig_run(e, pl, reads, targets, p, vit, out)) {
+            rc = -1;
+            const std::string keep = g_err;
+            (void)hipGetLastError();
+            (void)sh_stream_wait(e->stream);
+            set_err("%s", keep.c_str());
+        }
+        pl.clear();
+    };
+    for (size_t i = 0; i < n && !rc; i++) {
+        if (squig_read_ok("squiggle_match_batch", reads[i], targets[i])) { why[i] = g_err; continue; }
+        const size_t ns = reads[i].end - reads[i].start, npos = targets[i].npos;
+        const size_t rb = squig_read_bytes(npos, ns, path);
+        if (rb > budget) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "squiggle_match_batch: %zu samples against %zu positions need %zu bytes on the device, more than one launch may take (%zu)", ns, npos, rb, budget);
+            why[i] = msg;
+            continue;
+        }
+        if (!pl.rd.empty() && (pl.bytes + rb > budget || pl.rd.size() >= 65535)) flush();
+        squig_plan_add(pl, i, ns, npos, path);
+    }
+    flush();
+    if (rc) {
+        scrappie_hip_free_squiggle_results(out, n);
+        for (size_t i = 0; i < n; i++) { out[i].score = NAN; out[i].n = 0; }
+        return -1;
+    }
+    for (size_t i = 0; i < n; i++)
+        if (!why[i].empty()) { set_err("%s (read %zu of the call)", why[i].c_str(), i); break; }
+    return 0;
+}
+
+/* ------------------------------------------------------------------ */
+/* per-read reference surface (decode.c:1035, :1262)                    */
+/* ------------------------------------------------------------------ */
+static float squig_one(const char *fn, const raw_table signal, float rate, const_scrappie_matrix params, float prob_back, float local_pen,
+                       float skip_pen, float minscore, bool vit, int32_t *path_padded) {
+    if (!signal.raw) { set_err("%s: no signal", fn); return NAN; }                   /* RETURN_NULL_IF, decode.c:1038-1040 */
+    if (!params || !params->data.f) { set_err("%s: no squiggle", fn); return NAN; }
+    if (vit && !path_padded) { set_err("%s: no path to write to", fn); return NAN; }
+    scrappie_hip_squiggle_params p;
+    p.rate = rate; p.prob_back = prob_back; p.local_pen = local_pen; p.skip_pen = skip_pen; p.minscore = minscore;
+    scrappie_hip_squiggle_target t;
+    t.params = params->data.f; t.npos = params->nc; t.stride = params->stride;
+    if (squig_params_ok(fn, &p) || squig_read_ok(fn, signal, t)) return NAN;          /* the reference's asserts, and npos == 0 */
+    scrappie_hip_engine *e = default_engine();
+    if (!e) return NAN;
+    scrappie_hip_squiggle_result res;
+    if (scrappie_hip_squiggle_match_batch(e, &signal, &t, 1, &p, vit ? 1 : 0, vit ? 1 : 0, &res)) return NAN;
+    if (vit) {
+        if (!res.path) return NAN;
+        memcpy(path_padded, res.path, signal.n * 4);
+        free(res.path);
+    }
+    return res.score;
+}
+
+extern "C" float squiggle_match_viterbi(const raw_table signal, float rate, const_scrappie_matrix params, float prob_back, float local_pen,
+                                        float skip_pen, float minscore, int32_t *path_padded) {
+    return squig_one("squiggle_match_viterbi", signal, rate, params, prob_back, local_pen, skip_pen, minscore, true, path_padded);
+}
+extern "C" float squiggle_match_forward(const raw_table signal, float rate, const_scrappie_matrix params, float prob_back, float local_pen,
+                                        float skip_pen, float minscore) {
+    return squig_one("squiggle_match_forward", signal, rate, params, prob_back, local_pen, skip_pen, minscore, false, nullptr);
+}

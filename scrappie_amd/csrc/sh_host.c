@@ -563,3 +563,39 @@ int *encode_bases_to_integers(char const *seq, size_t n, size_t state_len) {
     }
     return codes;
 }
+
+/* ------------------------------------------------------------------ */
+/* squiggle matching: the per-position tables (decode.c:1055-1099)      */
+/* ------------------------------------------------------------------ */
+/* What squiggle_match_viterbi / _forward compute before their sample loop, with the reference's expressions and its
+ * summation order, from the same libm: tab = loc[npos] | scale[npos] | logsc[npos] | move_pen[npos + 2] | stay_pen[npos + 2]
+ * (the means in the START and END slots); pens = { logf(prob_back), logf(0.5f) }.  params: npos columns of ldp floats
+ * (mean, log sd, dwell logit). */
+void sh_squiggle_tables(const float *params, size_t npos, size_t ldp, float rate, float prob_back, float *tab, float pens[2]) {
+    float *loc = tab, *scale = tab + npos, *logsc = tab + 2 * npos, *move_pen = tab + 3 * npos, *stay_pen = tab + 4 * npos + 2;
+    const size_t nfstate = npos + 2;
+    pens[0] = logf(prob_back);
+    pens[1] = logf(0.5f);
+    for (size_t pos = 0; pos < npos; pos++) {
+        loc[pos] = params[pos * ldp + 0];
+        logsc[pos] = params[pos * ldp + 1];
+        scale[pos] = expf(params[pos * ldp + 1]);
+    }
+    const float lograte = logf(rate);
+    float mean_move_pen = 0.0f;
+    float mean_stay_pen = 0.0f;
+    for (size_t pos = 0; pos < npos; pos++) {
+        const float x = params[pos * ldp + 2] + lograte;
+        const float mp = (1.0f - prob_back) * (0.5f * (1.0f + tanhf(x / 2.0f)));      /* plogisticf, util.h:110-112 */
+        move_pen[pos + 1] = logf(mp);
+        stay_pen[pos + 1] = log1pf(-mp - prob_back);
+        mean_move_pen += move_pen[pos + 1];
+        mean_stay_pen += stay_pen[pos + 1];
+    }
+    mean_move_pen /= npos;
+    mean_stay_pen /= npos;
+    move_pen[0] = mean_move_pen;
+    move_pen[nfstate - 1] = mean_move_pen;
+    stay_pen[0] = mean_stay_pen;
+    stay_pen[nfstate - 1] = mean_stay_pen;
+}

@@ -16,6 +16,8 @@ int sh_zlib_inflate(unsigned char *dst, size_t cap, size_t *outlen, const unsign
 unsigned long sh_h5mini_zlib_fallbacks(void);      /* chunks the built-in inflater refused and zlib decoded (expected: 0) */
 /* block-based mapping (sh_host.c): are_bounds_sane with its warnings on or off (1 / 0: sane / not) */
 int sh_bounds_sane(const size_t *low, const size_t *high, size_t nblock, size_t seqlen, int verbose);
+/* squiggle matching (sh_host.c): the tables of decode.c:1055-1099 from the host's libm; tab holds 5 npos + 4 floats */
+void sh_squiggle_tables(const float *params, size_t npos, size_t ldp, float rate, float prob_back, float *tab, float pens[2]);
 #ifdef __cplusplus
 }
 #endif

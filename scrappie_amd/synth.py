@@ -13,6 +13,8 @@ fast5 data, and the bundled reads need HDF5).
   posteriors decode to an all-stay path (SURVEY.md section 8c fixture note).
   Homopolymer runs with ambiguous stay/repeat mass can be planted to exercise the
   homopolymer correction (homopolymer.c:175).
+* `simulated_squiggle` -- a predicted squiggle (mean, log sd, dwell logit per position) and a
+  signal that dwells along it, for squiggle matching (decode.c:1016-1401).
 """
 import numpy as np
 
@@ -227,3 +229,21 @@ def synthetic_events(n, seed, mean_dwell=9.0):
     ev["pos"] = -1
     ev["state"] = -1
     return ev
+
+
+def simulated_squiggle(npos, seed, mean_dwell=8.0, noise=0.15):
+    """(params[npos, 3] float32, signal float32, true position per sample): means ~N(0, 1) per position, log sd near
+    log(noise), dwell logits near logit(1 / mean_dwell) -- the per-sample probability of moving on that
+    squiggle_match turns into its move penalty -- and a signal that stays Geometric(that probability) samples at each
+    position in turn, with Laplace noise of the position's scale.  Deterministic per seed."""
+    rng = np.random.RandomState(seed)
+    params = np.zeros((npos, 3), dtype=np.float32)
+    params[:, 0] = rng.normal(0.0, 1.0, size=npos)
+    params[:, 1] = np.log(noise) + rng.normal(0.0, 0.05, size=npos)
+    p_move = 1.0 / mean_dwell
+    params[:, 2] = np.log(p_move / (1.0 - p_move)) + rng.normal(0.0, 0.1, size=npos)
+    p = 1.0 / (1.0 + np.exp(-params[:, 2].astype(np.float64)))
+    dwell = rng.geometric(p)
+    truth = np.repeat(np.arange(npos, dtype=np.int32), dwell)
+    sig = params[truth, 0] + rng.laplace(0.0, 1.0, size=len(truth)) * np.exp(params[truth, 1])
+    return params, sig.astype(np.float32), truth

@@ -1,0 +1,171 @@
+"""Squiggle matching on the GPU (sh_squig.h): the per-read squiggle_match_viterbi / _forward and the batched
+Engine.match_squiggle against the reference's compiled decode.c (oracle/_ref/libref_decode.so) and the numpy restatement
+of tests/test_squiggle_cpu.py.  Viterbi scores and padded paths must be bit-identical; forward within 2x the reference's
+own error + 1e-5 |score| (the criterion of tests/test_gpu_map.py)."""
+import ctypes as C
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import pytest
+
+import scrappie_amd as sa
+from scrappie_amd import synth
+from test_squiggle_cpu import PENS, call_squig, lds_threshold, np_squiggle_match, ref_squiggle_lib, squig_cases
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def ref():
+    R = ref_squiggle_lib()
+    assert R is not None, "oracle/_ref/libref_decode.so is required (build() makes it and it travels with the tree)"
+    return R
+
+
+@pytest.fixture(scope="module")
+def cases(ref):
+    """every case with what the reference and the restatement give for it, computed once"""
+    out = []
+    for name, sig, start, end, params, pens in squig_cases(lds_threshold()):
+        c = dict(name=name, sig=sig, start=start, end=end, params=params, pens=pens)
+        c["ref_v"] = call_squig(ref, sig, start, end, params, pens, True)
+        c["ref_f"] = call_squig(ref, sig, start, end, params, pens, False)[0]
+        c["np_v"] = np_squiggle_match(sig[start:end], params, *pens, viterbi=True)
+        c["f64"] = float(np_squiggle_match(sig[start:end], params, *pens, viterbi=False, dtype=np.float64)[0])
+        out.append(c)
+    return out
+
+
+def _forward_ok(got, want_ref, exact, name):
+    """|gpu - f64| <= 2 |ref - f64| + 1e-5 |score|; returns the ratio |gpu - f64| / (|ref - f64| + 1e-5 |score|)"""
+    eg, er = abs(float(got) - exact), abs(float(want_ref) - exact)
+    print("forward %s: gpu %r ref %r f64 %r" % (name, float(got), float(want_ref), exact))
+    assert eg <= 2 * er + 1e-5 * abs(exact), (name, got, want_ref, exact)
+    return eg / (er + 1e-5 * abs(exact) + 1e-30)
+
+
+def test_per_read_against_reference(cases):
+    L = sa.lib()
+    worst = 0.0
+    for c in cases:
+        want_s, want_p = c["ref_v"]
+        got_s, got_p = call_squig(L, c["sig"], c["start"], c["end"], c["params"], c["pens"], True, gpu=True)
+        assert got_s.tobytes() == want_s.tobytes(), (c["name"], got_s, want_s)
+        assert np.array_equal(got_p, want_p), c["name"]
+        np_s, np_p = c["np_v"]
+        assert np.float32(np_s).tobytes() == got_s.tobytes() and np.array_equal(np_p, got_p[c["start"]:c["end"]]), c["name"]
+        got_f, _ = call_squig(L, c["sig"], c["start"], c["end"], c["params"], c["pens"], False, gpu=True)
+        worst = max(worst, _forward_ok(got_f, c["ref_f"], c["f64"], c["name"]))
+    print("forward: worst |gpu - f64| / (|ref - f64| + 1e-5 |score|) = %.3f" % worst)
+
+
+@pytest.fixture(scope="module")
+def eng():
+    e = sa.Engine(0)
+    yield e
+    e.close()
+
+
+def test_engine_all_cases_in_one_call(eng, ref, cases):
+    """every case in ONE call per parameter set: LDS and scratch homes mixed, several launches (a 1 MB budget), windows"""
+    rts = []
+    for c in cases:
+        rt = sa.RawTable(c["sig"])
+        rt._rt.start, rt._rt.end = c["start"], c["end"]
+        rts.append(rt)
+    sqs = [c["params"] for c in cases]
+    eng.debug_option("squiggle_budget_kb", 1024)
+    try:
+        for pens in PENS:
+            kw = dict(rate=pens[0], back_prob=pens[1], local_pen=pens[2], skip_pen=pens[3], min_score=pens[4])
+            res = eng.match_squiggle(rts, sqs, viterbi=True, path=True, **kw)
+            fwd = eng.match_squiggle(rts, sqs, viterbi=False, **kw)
+            assert len(res) == len(cases) == len(fwd)
+            for c, (sc, pth), (fs, fp) in zip(cases, res, fwd):
+                own = c["pens"] is pens
+                want_s, want_p = c["ref_v"] if own else call_squig(ref, c["sig"], c["start"], c["end"], c["params"], pens, True)
+                assert np.float32(sc).tobytes() == want_s.tobytes(), (c["name"], pens, sc, want_s)
+                assert pth is not None and np.array_equal(pth, want_p), (c["name"], pens)
+                assert fp is None
+                if own:
+                    np_s, np_p = c["np_v"]
+                    assert np.float32(np_s).tobytes() == np.float32(sc).tobytes(), c["name"]
+                    assert np.array_equal(np_p, pth[c["start"]:c["end"]]), c["name"]
+                    _forward_ok(fs, c["ref_f"], c["f64"], c["name"])
+            t = eng.squiggle_timing()
+            assert t["match_ms"] > 0 and t["walk_ms"] > 0
+        # a read whose traceback cannot fit a launch: NAN for it and a text, the others as before
+        eng.debug_option("squiggle_budget_kb", 256)
+        res = eng.match_squiggle(rts, sqs, viterbi=True, path=True)
+        big = [i for i, c in enumerate(cases) if (c["end"] - c["start"]) * ((len(c["params"]) + 63) // 64) * 32 > 256 * 1024]
+        assert big and "more than one launch may take" in sa.last_error()
+        for i, (c, (sc, pth)) in enumerate(zip(cases, res)):
+            if i in big:
+                assert np.isnan(sc) and pth is None
+            elif c["pens"] is PENS[0]:
+                assert np.float32(sc).tobytes() == c["ref_v"][0].tobytes() and np.array_equal(pth, c["ref_v"][1]), c["name"]
+    finally:
+        eng.debug_option("squiggle_budget_kb", 0)
+
+
+def test_path_follows_the_simulated_squiggle(ref):
+    params, sig, truth = synth.simulated_squiggle(400, 12)
+    pens = PENS[0]
+    want_s, want_p = call_squig(ref, sig, 0, len(sig), params, pens, True)
+    agree_ref = float(np.mean(want_p == truth))
+    L = sa.lib()
+    got_s, got_p = call_squig(L, sig, 0, len(sig), params, pens, True, gpu=True)
+    agree_gpu = float(np.mean(got_p == truth))
+    print("agreement with the true positions: reference %.4f, gpu %.4f over %d samples" % (agree_ref, agree_gpu, len(sig)))
+    assert agree_gpu == agree_ref and got_s.tobytes() == want_s.tobytes()
+    assert agree_ref > 0.5
+    perm = params[np.random.RandomState(3).permutation(len(params))]
+    for vit in (True, False):
+        true_s = call_squig(L, sig, 0, len(sig), params, pens, vit, gpu=True)[0]
+        perm_s = call_squig(L, sig, 0, len(sig), perm, pens, vit, gpu=True)[0]
+        assert true_s > perm_s, (vit, true_s, perm_s)
+
+
+def test_map_signal_to_squiggle_on_raw_data(ref):
+    params, sig, _ = synth.simulated_squiggle(300, 21)
+    body = 90.0 + 12.0 * sig
+    rng = np.random.RandomState(4)
+    data = np.concatenate([90.0 + rng.normal(0, 1.0, 400), body, 90.0 + rng.normal(0, 1.0, 150)])
+    data = np.round(data).astype(np.int16)                  # raw DAC-like values
+    score, path = sa.map_signal_to_squiggle(data, params)
+    rt = sa.RawTable(data).trim().scale()
+    assert rt.start > 0 and rt.end < len(data) and rt.end > rt.start
+    want_s, want_p = call_squig(ref, rt._data, rt.start, rt.end, params, PENS[0], True)
+    assert np.float32(score).tobytes() == want_s.tobytes()
+    assert len(path) == len(data) and np.array_equal(path, want_p)
+    assert np.all(path[:rt.start] == -1) and np.all(path[rt.end:] == -1) and np.any(path >= 0)
+    m = sa.ScrappyMatrix.from_numpy(params, sloika=False)
+    score2, path2 = sa.map_signal_to_squiggle(data, m)
+    assert np.float32(score2).tobytes() == want_s.tobytes() and np.array_equal(path2, want_p)
+    fs, fp = sa.squiggle_match(rt, m, viterbi=False, path=False)
+    assert fp is None and fs >= score - 1e-3 * abs(score)
+
+
+def test_a_sequence_needs_the_predictor():
+    with pytest.raises(NotImplementedError):
+        sa.map_signal_to_squiggle(np.zeros(2000, dtype=np.float32), "ACGTACGTACGTACGT")
+    e = sa.Engine(0)
+    try:
+        with pytest.raises(NotImplementedError):
+            e.match_squiggle([np.zeros(100, dtype=np.float32)], ["ACGTACGT"])
+    finally:
+        e.close()
+
+
+def test_per_read_threads(cases):
+    L = sa.lib()
+    some = [c for c in cases if 60 <= len(c["params"]) <= 300][:8]
+    assert len(some) == 8
+
+    def one(c):
+        return call_squig(L, c["sig"], c["start"], c["end"], c["params"], c["pens"], True, gpu=True)
+    alone = [one(c) for c in some]
+    with ThreadPoolExecutor(8) as ex:
+        together = list(ex.map(one, some))
+    for (a_s, a_p), (t_s, t_p) in zip(alone, together):
+        assert a_s.tobytes() == t_s.tobytes() and np.array_equal(a_p, t_p)
