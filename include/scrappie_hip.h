@@ -419,6 +419,8 @@ void scrappie_hip_free_map_results(scrappie_hip_map_result *r, size_t n);
 /* the last scrappie_hip_map_batch call's time, milliseconds summed over its launch groups: [0] network + S1, [1] k_map,
  * [2] k_map_walk + results to the host (host clock, the stream drained between the stages) */
 void scrappie_hip_map_timing(scrappie_hip_engine *e, double out[3]);
+/* states up to which k_map keeps its score rows and the codes in LDS; longer sequences keep the rows in device scratch */
+size_t scrappie_hip_map_lds_max_seq(void);
 
 /* Squiggle matching, batched (sh_eng_squig.inc): reads[i] (trimmed, normalised; mapped over [start, end)) against
  * targets[i], a predicted squiggle of npos columns of stride >= 3 floats (mean, log sd, dwell logit); out[i] belongs to
@@ -440,6 +442,16 @@ void scrappie_hip_free_squiggle_results(scrappie_hip_squiggle_result *r, size_t 
 void scrappie_hip_squiggle_timing(scrappie_hip_engine *e, double out[3]);
 /* positions up to which k_squig keeps its score rows and tables in LDS; longer squiggles keep the rows in device scratch */
 size_t scrappie_hip_squiggle_lds_max_pos(void);
+/* The planners' scratch arithmetic on the host, no device (for the tests): reads of seqlen[i] states / npos[i] positions laid
+ * out in this order in one launch; off[i] = float offset of read i's two score rows in the launch's scratch allocation (-1: the
+ * rows live in LDS); returns the floats allocated for all of them.  k_map touches 2 (seqlen + 2) floats from its offset,
+ * k_squig 2 (2 npos + 1). */
+long long scrappie_hip_map_plan_scratch(const size_t *seqlen, const size_t *nblock, size_t n, long long *off);
+long long scrappie_hip_squiggle_plan_scratch(const size_t *npos, const size_t *nsample, size_t n, long long *off);
+/* Launches of each kernel form since the process started, all engines together (the per-read functions run on the
+ * process-default engine).  map_forms[(viterbi ? 8 : 0) | (banded ? 4 : 0) | (tiled ? 2 : 0) | (scratch ? 1 : 0)] for k_map,
+ * squig_forms[(viterbi ? 2 : 0) | (scratch ? 1 : 0)] for k_squig; either may be NULL.  Host counters only: no device work. */
+void scrappie_hip_launch_form_counts(uint64_t map_forms[16], uint64_t squig_forms[4]);
 
 /* Measurement / test hook for SURVEY.md 8(d) "decode driven by HMM-simulated posteriors" (synthetic
  * weights decode to a handful of bases per read, which leaves the decode -> D2H -> homopolymer ->

@@ -250,6 +250,13 @@ def lib():
     L.scrappie_hip_free_squiggle_results.argtypes = [C.POINTER(_SquigResult), C.c_size_t]
     L.scrappie_hip_squiggle_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     L.scrappie_hip_squiggle_lds_max_pos.restype = C.c_size_t
+    L.scrappie_hip_map_lds_max_seq.restype = C.c_size_t
+    L.scrappie_hip_map_lds_max_seq.argtypes = []
+    for nm in ("scrappie_hip_map_plan_scratch", "scrappie_hip_squiggle_plan_scratch"):
+        getattr(L, nm).restype = C.c_longlong
+        getattr(L, nm).argtypes = [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(C.c_longlong)]
+    L.scrappie_hip_launch_form_counts.restype = None
+    L.scrappie_hip_launch_form_counts.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     _lib = L
     return L
 
@@ -260,6 +267,28 @@ _libc.free.argtypes = [C.c_void_p]
 
 def last_error():
     return lib().scrappie_hip_last_error().decode()
+
+
+def plan_scratch(kind, sizes, counts):
+    """The planner's scratch layout of one launch of reads in this order (host arithmetic, no device): kind 'map' with
+    sizes = states and counts = blocks per read, or 'squig' with positions and samples.  Returns (off, total): the float
+    offset of each read's two score rows (-1: in LDS) and the floats allocated for all of them."""
+    fn = {"map": lib().scrappie_hip_map_plan_scratch, "squig": lib().scrappie_hip_squiggle_plan_scratch}[kind]
+    a = np.ascontiguousarray(sizes, dtype=np.uintp)
+    b = np.ascontiguousarray(counts, dtype=np.uintp)
+    off = np.zeros(len(a), dtype=np.longlong)
+    sp = C.POINTER(C.c_size_t)
+    total = fn(a.ctypes.data_as(sp), b.ctypes.data_as(sp), len(a), off.ctypes.data_as(C.POINTER(C.c_longlong)))
+    return off, int(total)
+
+
+def launch_form_counts():
+    """Launches of each kernel form in this process so far (scrappie_hip_launch_form_counts): {'map': {(viterbi, banded,
+    tiled, scratch): n} for the 16 forms of k_map, 'squig': {(viterbi, scratch): n} for the 4 of k_squig}."""
+    m, q = (C.c_uint64 * 16)(), (C.c_uint64 * 4)()
+    lib().scrappie_hip_launch_form_counts(m, q)
+    return dict(map={(bool(k & 8), bool(k & 4), bool(k & 2), bool(k & 1)): int(m[k]) for k in range(16)},
+                squig={(bool(k & 2), bool(k & 1)): int(q[k]) for k in range(4)})
 
 
 def _take_string(ptr):

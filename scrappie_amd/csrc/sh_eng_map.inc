@@ -13,6 +13,11 @@ struct MapPlan {
 };
 
 static size_t map_lds_bytes(size_t L) { return (2 * (L + 2) + L) * 4; }
+/* the longest sequence whose rows and codes stay in LDS (map_lds_bytes is linear in L) */
+extern "C" size_t scrappie_hip_map_lds_max_seq(void) {
+    const size_t per = map_lds_bytes(1) - map_lds_bytes(0);
+    return (SH_MAP_LDS - map_lds_bytes(0)) / per;
+}
 /* code words (4 ceil(L / 64) per block) + END bits (one word per 32 blocks), rounded to whole 16-byte pieces */
 static long long map_tb_words(size_t L, size_t nblock) {
     return (long long)nblock * (long long)(4 * ((L + 63) / 64)) + (long long)(((nblock + 31) / 32 + 3) & ~(size_t)3);
@@ -47,8 +52,29 @@ static void plan_add(MapPlan &pl, long long post, int lane, size_t nblock, const
     pl.rd.push_back(r);
 }
 
+/* The scratch part of the plan plan_add makes of reads of seqlen[i] states and nblock[i] blocks, in this order in one launch
+ * (no traceback, no bands): off[i] = the float offset of read i's two score rows in the scratch allocation, -1 where they live
+ * in LDS; returns the floats the launch allocates for them all.  Host arithmetic only, no device: for the tests, which hold
+ * it against what k_map touches (2 (L + 2) floats from off[i]). */
+extern "C" long long scrappie_hip_map_plan_scratch(const size_t *seqlen, const size_t *nblock, size_t n, long long *off) {
+    MapPlan pl;
+    std::vector<int> codes;
+    for (size_t i = 0; i < n; i++) {
+        codes.assign(seqlen[i], 0);
+        plan_add(pl, 0, 0, nblock[i], codes.data(), seqlen[i], nullptr, nullptr, false);
+        if (off) off[i] = pl.rd[i].scr;
+    }
+    return pl.scr_floats;
+}
+
+/* launches of each k_map form in this process: index (vit ? 8 : 0) | (band ? 4 : 0) | (tiled ? 2 : 0) | (scratch ? 1 : 0) */
+static std::atomic<uint64_t> g_map_forms[16];
+
 template <bool VIT, bool BAND, bool TILED>
 static void map_launch_k(hipStream_t s, const ShMapArgs &a, size_t n_lds, size_t n, size_t lds) {
+    const int form = (VIT ? 8 : 0) | (BAND ? 4 : 0) | (TILED ? 2 : 0);
+    if (n_lds) g_map_forms[form].fetch_add(1, std::memory_order_relaxed);
+    if (n > n_lds) g_map_forms[form | 1].fetch_add(1, std::memory_order_relaxed);
     if (n_lds) hipLaunchKernelGGL((k_map<VIT, BAND, TILED, true>), dim3((unsigned)n_lds), dim3(SH_MAP_NTH), lds, s, a);
     if (n > n_lds) {                     /* the reads whose rows live in scratch: the tables' tail */
         ShMapArgs b = a;

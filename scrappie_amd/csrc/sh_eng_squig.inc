@@ -46,8 +46,26 @@ static void squig_plan_add(SquigPlan &pl, size_t who, size_t nsample, size_t npo
     pl.bytes += squig_read_bytes(npos, nsample, path);
 }
 
+/* The scratch part of the plan squig_plan_add makes of reads of npos[i] positions and nsample[i] samples, in this order in one
+ * launch (no traceback): off[i] = the float offset of read i's two score rows in the scratch allocation, -1 where they live in
+ * LDS; returns the floats the launch allocates for them all.  Host arithmetic only: for the tests, which hold it against what
+ * k_squig touches (2 (2 npos + 1) floats from off[i]). */
+extern "C" long long scrappie_hip_squiggle_plan_scratch(const size_t *npos, const size_t *nsample, size_t n, long long *off) {
+    SquigPlan pl;
+    for (size_t i = 0; i < n; i++) {
+        squig_plan_add(pl, i, nsample[i], npos[i], false);
+        if (off) off[i] = pl.rd[i].scr;
+    }
+    return pl.scr_floats;
+}
+
+/* launches of each k_squig form in this process: index (vit ? 2 : 0) | (scratch ? 1 : 0) */
+static std::atomic<uint64_t> g_squig_forms[4];
+
 template <bool VIT>
 static void squig_launch_k(hipStream_t s, const ShSquigArgs &a, size_t n_lds, size_t n, size_t lds) {
+    if (n_lds) g_squig_forms[VIT ? 2 : 0].fetch_add(1, std::memory_order_relaxed);
+    if (n > n_lds) g_squig_forms[(VIT ? 2 : 0) | 1].fetch_add(1, std::memory_order_relaxed);
     if (n_lds) hipLaunchKernelGGL((k_squig<VIT, true>), dim3((unsigned)n_lds), dim3(SH_SQ_NTH), lds, s, a);
     if (n > n_lds) {                     /* the reads whose rows live in scratch: the records' tail */
         ShSquigArgs b = a;
@@ -160,6 +178,11 @@ extern "C" scrappie_hip_squiggle_params scrappie_hip_default_squiggle_params(voi
 }
 
 extern "C" size_t scrappie_hip_squiggle_lds_max_pos(void) { return SH_SQ_LDS_MAX_POS; }
+
+extern "C" void scrappie_hip_launch_form_counts(uint64_t map_forms[16], uint64_t squig_forms[4]) {
+    for (int k = 0; k < 16; k++) if (map_forms) map_forms[k] = g_map_forms[k].load(std::memory_order_relaxed);
+    for (int k = 0; k < 4; k++) if (squig_forms) squig_forms[k] = g_squig_forms[k].load(std::memory_order_relaxed);
+}
 
 extern "C" void scrappie_hip_squiggle_timing(scrappie_hip_engine *e, double out[3]) {
     for (int k = 0; k < 3; k++) out[k] = e ? e->squig_ms[k] : 0.0;

@@ -13,7 +13,7 @@ import pytest
 
 import scrappie_amd as sa
 from scrappie_amd import model, synth
-from test_map_cpu import band_sets, call_map, map_cases, np_map, ref_decode_lib
+from test_map_cpu import band_sets, call_map, lds_max_seq, map_cases, map_form, map_scratch_cases, np_map, ref_decode_lib
 
 pytestmark = pytest.mark.gpu
 
@@ -36,10 +36,21 @@ def ref():
     return R
 
 
-def _forward_ok(got, want_ref, post, seq, pens, bands=None):
-    """|gpu - f64| <= 2 |ref - f64| + 1e-5 |score|; returns the ratio |gpu - f64| / (|ref - f64| + 1e-5 |score|)"""
+@pytest.fixture(scope="module", autouse=True)
+def forms_at_start():
+    """k_map launches per form before this module's first test (test_every_map_form_was_launched)"""
+    return sa.launch_form_counts()["map"]
+
+
+def _f64(post, seq, pens, bands=None):
     lo, hi = (None, None) if bands is None else bands
-    exact = float(np_map(post, seq, *pens, viterbi=False, low=lo, high=hi, dtype=np.float64)[0])
+    return float(np_map(post, seq, *pens, viterbi=False, low=lo, high=hi, dtype=np.float64)[0])
+
+
+def _forward_ok(got, want_ref, post, seq, pens, bands=None, exact=None):
+    """|gpu - f64| <= 2 |ref - f64| + 1e-5 |score|; returns the ratio |gpu - f64| / (|ref - f64| + 1e-5 |score|)"""
+    if exact is None:
+        exact = _f64(post, seq, pens, bands)
     eg, er = abs(float(got) - exact), abs(float(want_ref) - exact)
     assert eg <= 2 * er + 1e-5 * abs(exact), (got, want_ref, exact)
     return eg / (er + 1e-5 * abs(exact) + 1e-30)
@@ -78,6 +89,80 @@ def test_per_read_against_reference(ref):
             worst = max(worst, _forward_ok(got_f, want_f, post, seq, pens, bands))
     assert n_band > 100
     print("forward: worst |gpu - f64| / (|ref - f64| + 1e-5 |score|) = %.3f" % worst)
+
+
+def _sane_ref(ref, bands, nblock, L):
+    sp = C.POINTER(C.c_size_t)
+    return bool(ref.are_bounds_sane(bands[0].ctypes.data_as(sp), bands[1].ctypes.data_as(sp), nblock, L))
+
+
+@pytest.fixture(scope="module")
+def scratch_cases(ref):
+    """map_scratch_cases with what the reference and the restatement give for each, computed once: unbanded
+    (ref_v, ref_f, np_v, f64); per band set (name, bands, sane, ref_v, ref_f, f64)"""
+    out = []
+    for name, post, seq, pens, bsets in map_scratch_cases():
+        c = dict(name=name, post=post, seq=seq, pens=pens, bands=None)
+        if bsets is None:
+            c["ref_v"] = call_map(ref, post, seq, pens, True)
+            c["ref_f"] = call_map(ref, post, seq, pens, False)[0]
+            c["np_v"] = np_map(post, seq, *pens)
+            c["f64"] = _f64(post, seq, pens)
+        else:
+            c["bands"] = []
+            for bname, bands in bsets:
+                b = dict(name=bname, bands=bands, sane=_sane_ref(ref, bands, post.shape[0], len(seq)))
+                if b["sane"]:
+                    b["ref_v"] = call_map(ref, post, seq, pens, True, bands)[0]
+                    b["ref_f"] = call_map(ref, post, seq, pens, False, bands)[0]
+                    b["f64"] = _f64(post, seq, pens, bands)
+                c["bands"].append(b)
+        out.append(c)
+    return out
+
+
+def test_per_read_scratch_cases(scratch_cases):
+    """the scratch home (and its control at the last LDS length) through the per-read surface: unbanded Viterbi score and
+    path byte for byte against the reference and the restatement, banded Viterbi against the reference, forward by
+    _forward_ok, NaN where are_bounds_sane refuses"""
+    L = sa.lib()
+    M = lds_max_seq()
+    worst = {False: 0.0, True: 0.0}                      # by home: scratch?
+    n_band = 0
+    ran = set()
+    before = sa.launch_form_counts()["map"]
+    for c in scratch_cases:
+        name, post, seq, pens = c["name"], c["post"], c["seq"], c["pens"]
+        scr = len(seq) > M
+        if c["bands"] is None:
+            want_s, want_p = c["ref_v"]
+            got_s, got_p = call_map(L, post, seq, pens, True, cast=PM)
+            assert got_s.tobytes() == want_s.tobytes(), (name, got_s, want_s)
+            assert np.array_equal(got_p, want_p), name
+            np_s, np_p = c["np_v"]
+            assert np.float32(np_s).tobytes() == got_s.tobytes() and np.array_equal(np_p, got_p), name
+            got_f, _ = call_map(L, post, seq, pens, False, cast=PM)
+            worst[scr] = max(worst[scr], _forward_ok(got_f, c["ref_f"], post, seq, pens, exact=c["f64"]))
+            ran |= {map_form(post, seq, None, v, M=M) for v in (True, False)}
+            continue
+        for b in c["bands"]:
+            bands = b["bands"]
+            got_s, _ = call_map(L, post, seq, pens, True, bands, cast=PM)
+            if not b["sane"]:
+                assert np.isnan(got_s), (name, b["name"])
+                continue
+            n_band += scr
+            assert got_s.tobytes() == b["ref_v"].tobytes(), (name, b["name"], got_s, b["ref_v"])
+            got_f, _ = call_map(L, post, seq, pens, False, bands, cast=PM)
+            worst[scr] = max(worst[scr], _forward_ok(got_f, b["ref_f"], post, seq, pens, bands, exact=b["f64"]))
+            ran |= {map_form(post, seq, bands, v, M=M) for v in (True, False)}
+    after = sa.launch_form_counts()["map"]
+    assert n_band >= 12
+    assert ran == {(v, b, False, h) for v in (True, False) for b in (True, False) for h in (True, False)}
+    for k in after:
+        assert (after[k] > before[k]) == (k in ran), (k, before[k], after[k])       # the forms the shapes imply are the forms launched
+    print("sane banded scratch cases: %d" % n_band)
+    print("forward: worst |gpu - f64| / (|ref - f64| + 1e-5 |score|) = %.3f in LDS (the control), %.3f in scratch" % (worst[False], worst[True]))
 
 
 def test_undefined_cases_give_nan():
@@ -167,6 +252,76 @@ def test_engine_map_to_sequence(eng, ref):
         eng.set_max_launch_reads(16384)
 
 
+def test_engine_tiled_scratch_forms(eng, ref):
+    """Engine.map_to_sequence on reads whose sequences are longer than the LDS home takes -- k_map on the tiled posterior
+    with its rows in device scratch -- mixed with short ones in one call of two launch groups; one sequence of exactly M
+    states (the last LDS length) and one of M + 1.  Three more scratch reads have signals of 121 to 140 blocks only: their
+    sequences cannot be reached, so their scores are what START and END hold at the last block, the floats at the very
+    end of a read's scratch rows, next to the first positions of the neighbouring read's rows in the same allocation.
+    The reference runs on the engine's own posterior."""
+    M = lds_max_seq()
+    rng = np.random.default_rng(41)
+    nstate = [M, M + 1, M + 600, M + 2]
+    lens = [int(x) for x in rng.integers(600, 3000, 20)]
+    long_at = [0, 2, 5, 17]                                # launch groups of 16 reads: two scratch reads side by side in the first, one in the second
+    for i, n in zip(long_at, (28000, 28500, 29000, 28200)):
+        lens[i] = n
+    brief_at = [8, 9, 10]                                  # scratch reads of few blocks, neighbours in the first group
+    for i, n in zip(brief_at, (605, 700, 655)):
+        lens[i] = n
+    sigs = [synth.medmad_normalise(synth.synthetic_signal(n, 300 + i)) for i, n in enumerate(lens)]
+    seqs = [_bases(int(rng.integers(8, 300)), rng) for _ in lens]
+    for i, ns in zip(long_at, nstate):
+        seqs[i] = _bases(ns + 4, rng)                      # k = 5: n - 4 states
+    for i, ns in zip(brief_at, (M + 1, M + 4, M + 3)):     # odd and even: the rows' rounding to 16 bytes differs
+        seqs[i] = _bases(ns + 4, rng)
+    codes = [sa.encode_bases(sq, 5) for sq in seqs]
+    assert [len(codes[i]) for i in long_at] == nstate
+    posts = [eng.posterior(x, min_prob=1e-5) for x in sigs]
+    assert all(5600 <= posts[i].shape[0] <= 6000 for i in long_at)
+    assert [posts[i].shape[0] for i in brief_at] == [121, 140, 131]
+    # (the engine cuts a call into launch groups of consecutive reads, max_launch_reads at a time while memory allows:
+    # read i is in group i // 16.  The launch counts asserted at the end depend on that policy.)
+    scratch_groups = {i // 16 for i, c in enumerate(codes) if len(c) > M}
+    assert len(scratch_groups) == 2
+    pens = (0.5, 1.0, 4.0)
+    eng.set_max_launch_reads(16)                           # two launch groups, a scratch read in each
+    before = sa.launch_form_counts()["map"]
+    worst = {False: 0.0, True: 0.0}
+    try:
+        for bands in (None, 4):
+            bbs = [None if bands is None else sa.diagonal_bands(bands, p.shape[0], len(c)) for p, c in zip(posts, codes)]
+            sane = [bb is None or _sane_ref(ref, bb, p.shape[0], len(c)) for bb, p, c in zip(bbs, posts, codes)]
+            if bands is not None:
+                assert sum(sane[i] for i in long_at if len(codes[i]) > M) >= 2
+            exact = [_f64(p, c, pens, bb) if ok else None for p, c, bb, ok in zip(posts, codes, bbs, sane)]
+            for vit in (True, False):
+                res = eng.map_to_sequence(sigs, seqs, viterbi=vit, path=vit and bands is None, bands=bands, stay_pen=pens[0],
+                                          skip_pen=pens[1], local_pen=pens[2], min_prob=1e-5)
+                assert len(res) == len(sigs)
+                for i, (sc, pth) in enumerate(res):
+                    if not sane[i]:
+                        assert np.isnan(sc), i
+                        continue
+                    ws, wp = call_map(ref, posts[i], codes[i], pens, vit, bbs[i])
+                    if vit:
+                        assert np.float32(sc).tobytes() == ws.tobytes(), (i, bands, sc, ws)
+                        if bands is None:
+                            assert np.array_equal(pth, wp), i
+                    else:
+                        scr = len(codes[i]) > M
+                        worst[scr] = max(worst[scr], _forward_ok(sc, ws, posts[i], codes[i], pens, bbs[i], exact=exact[i]))
+    finally:
+        eng.set_max_launch_reads(16384)
+    after = sa.launch_form_counts()["map"]
+    for v in (True, False):
+        for b in (True, False):
+            for h in (True, False):
+                assert after[(v, b, True, h)] - before[(v, b, True, h)] >= 1, (v, b, h)
+            assert after[(v, b, True, True)] - before[(v, b, True, True)] == len(scratch_groups), (v, b)      # one scratch launch per group that holds such reads
+    print("forward, tiled: worst |gpu - f64| / (|ref - f64| + 1e-5 |score|) = %.3f in LDS, %.3f in scratch" % (worst[False], worst[True]))
+
+
 def _fasta(name):
     path = os.path.join(READS, name + ".fa")
     data = open(path, "rb").read()
@@ -220,3 +375,12 @@ def test_per_read_threads():
         together = list(ex.map(lambda c: call_map(L, c[1], c[2], c[3], True, cast=PM), cases))
     for (a_s, a_p), (t_s, t_p) in zip(alone, together):
         assert a_s.tobytes() == t_s.tobytes() and np.array_equal(a_p, t_p)
+
+
+def test_every_map_form_was_launched(forms_at_start):
+    """the last test of the module: each of the 16 k_map instantiations (Viterbi / forward x full / banded x dense / tiled
+    x LDS / scratch) has been launched by the tests above"""
+    now = sa.launch_form_counts()["map"]
+    ran = {k: now[k] - forms_at_start[k] for k in now}
+    print("k_map launches by (viterbi, banded, tiled, scratch): %r" % sorted(ran.items()))
+    assert len(ran) == 16 and all(v > 0 for v in ran.values()), ran

@@ -242,6 +242,93 @@ def _sane(lo, hi, nblock, L):
 
 
 # ---------------------------------------------------------------------------
+# the scratch home: sequences of more than M states, whose rows live in device scratch and whose codes are read from
+# global memory (sh_map.h).  map_cases reaches it with two dense unbanded reads only.
+# ---------------------------------------------------------------------------
+SCRATCH_NBLOCK = (1, 2, 3, 40, 41)
+SCRATCH_NBLOCK_PAIRS = ((1, 2), (3, 40), (41, 2), (40, 1), (2, 3), (41, 40), (1, 40))      # one of each parity per length
+SCRATCH_BAND_NBLOCK = 5600
+RIDE_NBLOCK = 14000          # the simulated posterior emits a state in about 45 % of its blocks: more than M + 1 states
+
+
+def lds_max_seq():
+    return int(sa.lib().scrappie_hip_map_lds_max_seq())
+
+
+def scratch_seqlens(M):
+    """M (the last LDS size: the control), M + 1, M + 2; the next multiple of 64 and one past it; one past the next
+    multiple of 256 (a chunk of the kernel's 256 threads more); about 1.5 M.  For M = 5460: 5460, 5461, 5462, 5504, 5505,
+    5633, 8000."""
+    r64 = (M + 3 + 63) // 64 * 64
+    r256 = (r64 + 2 + 255) // 256 * 256
+    return (M, M + 1, M + 2, r64, r64 + 1, r256 + 1, M * 3 // 2 // 1000 * 1000)
+
+
+def map_form(post, seq, bands, viterbi, tiled=False, M=None):
+    """the k_map instantiation a case runs in: (viterbi, banded, tiled, scratch) -- the key of sa.launch_form_counts()"""
+    M = lds_max_seq() if M is None else M
+    return (bool(viterbi), bands is not None, bool(tiled), len(seq) > M)
+
+
+def _fit(seq, L, rng, nk):
+    """seq cut or padded with random codes to L states"""
+    seq = np.asarray(seq, dtype=np.int32)[:L]
+    return np.concatenate([seq, rng.integers(0, nk, L - len(seq)).astype(np.int32)])
+
+
+def map_scratch_cases():
+    """(name, post, seq, pens, band sets) for k = 3 posteriors (65 states).  Unbanded (band sets None): every length of
+    scratch_seqlens with two of the block counts 1, 2, 3, 40, 41 -- both ping-pong parities, the END-bit word of a short
+    read -- and one read of SCRATCH_BAND_NBLOCK blocks at M + 1, whose path crosses thousands of positions.  Banded: the
+    SCRATCH_BAND_NBLOCK posterior against true, mutated and random sequences of every length, with band_sets."""
+    M = lds_max_seq()
+    rng = np.random.default_rng(17)
+    nk = 64
+    out = []
+    posts = {nb: synth.simulated_posterior(nb, 500 + nb, klen=3)[0] for nb in SCRATCH_NBLOCK}
+    for j, L in enumerate(scratch_seqlens(M)):
+        for i, nb in enumerate(SCRATCH_NBLOCK_PAIRS[j]):
+            out.append(("scr_L%d_T%d" % (L, nb), posts[nb], rng.integers(0, nk, L).astype(np.int32), PENS[(2 * j + i) % 3], None))
+    post, tpath = synth.simulated_posterior(SCRATCH_BAND_NBLOCK, 501, klen=3)
+    true = _true_seq(tpath, nk, rng)
+    mut = true.copy()
+    idx = rng.random(len(mut)) < 0.15
+    mut[idx] = rng.integers(0, nk, int(idx.sum()))
+    kinds = [("true", true), ("mutated", mut), ("random", np.zeros(0, dtype=np.int32))]
+    out.append(("scr_L%d_T%d_true" % (M + 1, SCRATCH_BAND_NBLOCK), post, _fit(true, M + 1, rng, nk), PENS[1], None))
+    for j, L in enumerate(scratch_seqlens(M)):
+        kind, base = kinds[j % 3]
+        seq = _fit(base, L, rng, nk)
+        out.append(("scr_band_L%d_%s" % (L, kind), post, seq, PENS[(j + 1) % 3], band_sets(SCRATCH_BAND_NBLOCK, L, rng)))
+    # bands whose LOW edge is the true path of a posterior simulated from the sequence itself: the best path enters a
+    # block through the band's lowest cell whenever it moves on, by the step whose range starts at
+    # max(low[blk], low[blk - 1] + 1) -- a cell the other bands leave to worse paths.  The alignment has to beat the
+    # banded forms' START -> END of block 0, so the sequence is the true one throughout and END costs 4 per block
+    # (PENS[0]).  One in each home.
+    for L in (M, M + 1):
+        out.append(riding_case(L))
+    return out
+
+
+def riding_case(L, widths=(3, 40)):
+    """(name, post, seq, PENS[0], [(name, (low, high))]): a k = 3 posterior simulated until its true sequence has L states,
+    that sequence, and bands low[blk] = the true position at blk (0 before the first), high = low + w"""
+    post, tpath = synth.simulated_posterior(RIDE_NBLOCK, 502, klen=3)
+    emit = np.asarray(tpath) >= 0
+    assert np.all(np.asarray(tpath) >= -1) and int(emit.sum()) > L
+    nb = int(np.nonzero(np.cumsum(emit) == L)[0][0]) + 1
+    post, emit = post[:nb], emit[:nb]
+    seq = np.asarray(tpath)[:nb][emit].astype(np.int32)
+    low = np.maximum(np.cumsum(emit) - 1, 0)
+    bsets = []
+    for w in widths:
+        high = np.minimum(low + w, L)
+        high[-1] = L
+        bsets.append(("ride%d" % w, (low.astype(np.uintp), high.astype(np.uintp))))
+    return ("scr_band_L%d_ride" % L, np.ascontiguousarray(post), seq, PENS[0], bsets)
+
+
+# ---------------------------------------------------------------------------
 # tests
 # ---------------------------------------------------------------------------
 def test_encode_bases_matches_reference():
@@ -312,6 +399,112 @@ def test_restatement_equals_reference(viterbi):
         if len(seq) < 3:
             continue
         for bname, bands in band_sets(post.shape[0], len(seq), rng):
+            if not _sane(bands[0], bands[1], post.shape[0], len(seq)):
+                continue
+            want_s, _ = call_map(R, post, seq, pens, viterbi, bands)
+            got_s, _ = np_map(post, seq, *pens, viterbi=viterbi, low=bands[0], high=bands[1])
+            if viterbi:
+                assert np.float32(got_s).tobytes() == want_s.tobytes(), (name, bname)
+            else:
+                assert abs(float(got_s) - float(want_s)) <= 1e-5 * abs(float(want_s)) + 1e-4, (name, bname)
+
+
+def test_scratch_cases_cover_the_scratch_home(capfd):
+    R = ref_decode_lib()
+    if R is None:
+        pytest.skip("oracle/_ref/libref_decode.so not built")
+    M = lds_max_seq()
+    assert 256 < M < 65536
+    if M == 5460:
+        assert scratch_seqlens(M) == (5460, 5461, 5462, 5504, 5505, 5633, 8000)
+    lens = scratch_seqlens(M)
+    assert len(set(lens)) == 7 and lens[3] % 64 == 0 and lens[4] == lens[3] + 1 and (lens[5] - 1) % 256 == 0
+    assert lens[5] > lens[4] and 1.4 * M < lens[6] < 1.6 * M
+    cases = map_scratch_cases()
+    assert len({c[0] for c in cases}) == len(cases)
+    forms = set()
+    n_sane = 0
+    for name, post, seq, pens, bsets in cases:
+        assert post.shape[1] == 65 and len(seq) >= M, name
+        if bsets is None:
+            forms |= {map_form(post, seq, None, v, M=M) for v in (True, False)}
+            continue
+        for bname, (lo, hi) in bsets:
+            if R.are_bounds_sane(_sp(lo), _sp(hi), post.shape[0], len(seq)):
+                forms |= {map_form(post, seq, (lo, hi), v, M=M) for v in (True, False)}
+                n_sane += len(seq) > M
+    capfd.readouterr()
+    # every dense form, both homes (the control at M is the LDS one); the tiled forms need the engine
+    assert forms == {(v, b, False, h) for v in (True, False) for b in (True, False) for h in (True, False)}
+    print("sane banded scratch cases: %d" % n_sane)
+    assert n_sane >= 12
+    free = [c for c in cases if c[4] is None]
+    band = [c for c in cases if c[4] is not None]
+    for L in lens:
+        nbs = [c[1].shape[0] for c in free if len(c[2]) == L and c[1].shape[0] <= 41]
+        assert len(nbs) == 2 and (nbs[0] + nbs[1]) % 2 == 1, L                   # both ping-pong parities
+        assert any(len(c[2]) == L for c in band), L
+    assert {c[1].shape[0] for c in free} == set(SCRATCH_NBLOCK) | {SCRATCH_BAND_NBLOCK}
+    assert {c[3] for c in free} == set(PENS) and {c[3] for c in band} == set(PENS)
+    assert any(len(c[2]) == M + 1 and c[1].shape[0] > M // 2 for c in free)       # a long walk just above the threshold
+    ride = [c for c in cases if c[0].endswith("_ride")]
+    assert sorted(len(c[2]) for c in ride) == [M, M + 1]
+    for name, post, seq, pens, bsets in ride:
+        for bname, (lo, hi) in bsets:
+            assert R.are_bounds_sane(_sp(lo), _sp(hi), post.shape[0], len(seq)), (name, bname)
+            assert int(np.sum(np.diff(lo.astype(np.int64)) == 1)) == len(seq) - 1       # every move is a step into the lowest cell
+            # the alignment sets the score, not the banded forms' START -> END of block 0 and END from there on
+            chain = -pens[2] + float(np.sum(np.maximum(-pens[2], post[1:, -1].astype(np.float64))))
+            assert float(call_map(R, post, seq, pens, True, (lo, hi))[0]) > chain + 1000, (name, bname)
+    capfd.readouterr()
+
+
+def check_scratch_plan(kind, sizes, counts, in_lds, need):
+    """the planner's scratch layout of one launch (sa.plan_scratch): LDS reads take none; every other read's rows,
+    need(size) floats from its offset, start on a 16-byte boundary, lie behind the previous read's and inside the
+    allocation"""
+    off, total = sa.plan_scratch(kind, sizes, counts)
+    end = 0
+    for i, (n, o) in enumerate(zip(sizes, off)):
+        if in_lds(n):
+            assert o == -1, (kind, i, n, o)
+            continue
+        assert o >= end and o % 4 == 0, (kind, i, n, int(o), end)
+        end = int(o) + need(n)
+    assert end <= total and total % 4 == 0, (kind, end, total)
+    assert total <= end + 3 * sum(1 for n in sizes if not in_lds(n)), (kind, end, total)      # rounding only, no more
+
+
+def test_scratch_plan_keeps_neighbours_apart():
+    """plan_add: k_map touches 2 (L + 2) floats from a read's scratch offset (both rows with START and END).  Odd and even
+    L just above the threshold and every length of scratch_seqlens, LDS reads between them, several orders."""
+    M = lds_max_seq()
+    lens = [M + 1, M + 2, 7, M + 3, M + 4, M, M + 1] + list(scratch_seqlens(M)) + [M - 1, M + 5, M + 6, 65536]
+    rng = np.random.default_rng(23)
+    for order in (np.arange(len(lens)), np.arange(len(lens))[::-1], rng.permutation(len(lens)), rng.permutation(len(lens))):
+        L = [lens[i] for i in order]
+        check_scratch_plan("map", L, [1 + (i % 41) for i in range(len(L))], lambda n: n <= M, lambda n: 2 * (n + 2))
+    for L in (M + 1, M + 2, M + 3, M + 4):                    # a lone read: the allocation covers it
+        check_scratch_plan("map", [L], [40], lambda n: n <= M, lambda n: 2 * (n + 2))
+
+
+@pytest.mark.parametrize("viterbi", [True, False])
+def test_restatement_equals_reference_scratch_cases(viterbi):
+    """as test_restatement_equals_reference on map_scratch_cases"""
+    R = ref_decode_lib()
+    if R is None:
+        pytest.skip("oracle/_ref/libref_decode.so not built")
+    for name, post, seq, pens, bsets in map_scratch_cases():
+        if bsets is None:
+            want_s, want_p = call_map(R, post, seq, pens, viterbi)
+            got_s, got_p = np_map(post, seq, *pens, viterbi=viterbi)
+            if viterbi:
+                assert np.float32(got_s).tobytes() == want_s.tobytes(), name
+                assert np.array_equal(got_p, want_p), name
+            else:
+                assert abs(float(got_s) - float(want_s)) <= 1e-5 * abs(float(want_s)) + 1e-4, name
+            continue
+        for bname, bands in bsets:
             if not _sane(bands[0], bands[1], post.shape[0], len(seq)):
                 continue
             want_s, _ = call_map(R, post, seq, pens, viterbi, bands)

@@ -227,8 +227,136 @@ def lds_threshold():
 
 
 # ---------------------------------------------------------------------------
+# the scratch home: squiggles of more than T positions, whose rows live in device scratch and whose tables are read from
+# global memory (sh_squig.h).  squig_cases reaches it at T + 1 only, with the two uninformative penalty sets.
+# ---------------------------------------------------------------------------
+SCRATCH_NSAMPLE = (1, 2, 3, 64, 65, 257, 400)
+
+
+def scratch_npos(T):
+    """T + 1; the next multiple of 64 and one past it; the next multiple of 256 (a chunk of the kernel's 256 threads more)
+    -1 / 0 / +1; about 2.25 T.  For T = 1818: 1819, 1856, 1857, 2047, 2048, 2049, 4100."""
+    r64 = (T + 2 + 63) // 64 * 64
+    r256 = (r64 + 2 + 255) // 256 * 256
+    return (T + 1, r64, r64 + 1, r256 - 1, r256, r256 + 1, (9 * T // 4 + 99) // 100 * 100)
+
+
+def scratch_grid(T):
+    """(npos, nsample, index into PENS): two sample counts of opposite parity per npos, every count and every set used"""
+    n = scratch_npos(T)
+    return [(n[0], 1, 0), (n[0], 64, 1), (n[1], 2, 2), (n[1], 65, 0), (n[2], 3, 2), (n[2], 400, 1), (n[3], 64, 2),
+            (n[3], 257, 1), (n[4], 65, 1), (n[4], 400, 0), (n[5], 257, 2), (n[5], 2, 0), (n[6], 400, 1), (n[6], 3, 2)]
+
+
+def _wandering_inputs(npos, ns, seed):
+    """simulated_squiggle's parameters and a signal that walks them from position 0 with what PENS[1] keeps alive: skipped
+    positions and excursions one position back (k + 1, k, k + 1: through back state k), two samples at each stop so that
+    the excursion pays for its two penalties"""
+    params, _, _ = synth.simulated_squiggle(npos, seed, mean_dwell=2.0)
+    rng = np.random.RandomState(seed + 1)
+    walk = []
+    pos = 0
+    while len(walk) < ns:
+        walk += [pos, pos]
+        r = rng.rand()
+        if r < 0.15 and pos >= 1:
+            walk += [pos - 1, pos - 1, pos, pos]
+        pos = min(pos + (2 if 0.15 <= r < 0.30 else 1), npos - 1)
+    walk = np.array(walk[:ns])
+    sig = params[walk, 0] + rng.laplace(0.0, 1.0, size=ns) * np.exp(params[walk, 1])
+    return params, sig.astype(np.float32)
+
+
+def squig_scratch_cases(T):
+    """(name, padded signal, start, end, params, pens): scratch_grid, and a window inside a longer read"""
+    out = []
+    for j, (npos, ns, k) in enumerate(scratch_grid(T)):
+        params, sig = _wandering_inputs(npos, ns, 3000 + j) if k == 1 else _case_inputs(npos, ns, PENS[k], 3000 + j)
+        out.append(("scr_p%d_s%d_set%d" % (npos, ns, k), sig, 0, ns, params, PENS[k]))
+    npos = scratch_npos(T)[5]
+    params, sig = _wandering_inputs(npos, 257, 3077)
+    pad = np.random.RandomState(5).normal(0.0, 1.0, size=500).astype(np.float32)
+    pad[70:327] = sig
+    out.append(("scr_window_p%d" % npos, pad, 70, 327, params, PENS[1]))
+    return out
+
+
+def path_moves(path):
+    """(backward steps, skips) of a recoded Viterbi path: position differences < 0 and == 2 between mapped samples"""
+    d = np.diff(path[path >= 0])
+    return int(np.sum(d < 0)), int(np.sum(d == 2))
+
+
+# ---------------------------------------------------------------------------
 # tests
 # ---------------------------------------------------------------------------
+def test_scratch_cases_cover_the_scratch_home():
+    T = lds_threshold()
+    grid = scratch_grid(T)
+    npos = scratch_npos(T)
+    assert len(set(grid)) == len(grid) and len(set(npos)) == 7 and all(n > T for n in npos)
+    if T == 1818:
+        assert npos == (1819, 1856, 1857, 2047, 2048, 2049, 4100)
+    assert npos[0] == T + 1 and npos[1] % 64 == 0 and npos[2] == npos[1] + 1
+    assert npos[4] % 256 == 0 and npos[3] == npos[4] - 1 and npos[5] == npos[4] + 1       # the chunk boundary of 256 threads
+    assert (npos[3] + 255) // 256 + 1 == (npos[5] + 255) // 256
+    assert 2.2 * T < npos[6] < 2.3 * T and (npos[6] + 255) // 256 >= 2 * ((npos[0] + 255) // 256)
+    for n in npos:
+        ss = [s for p, s, k in grid if p == n]
+        assert len(ss) == 2 and (ss[0] + ss[1]) % 2 == 1, n                      # both ping-pong parities
+    assert {s for p, s, k in grid} == set(SCRATCH_NSAMPLE)
+    for k in range(3):
+        assert sum(1 for g in grid if g[2] == k) >= 2, k
+    assert sum(1 for g in grid if g[2] == 1) >= 3 and (npos[6], 400, 1) in grid
+    for p, s, k in grid:
+        assert s * (2 * p + 2) * 4 < 50e6                                         # the reference's traceback
+    cases = squig_scratch_cases(T)
+    assert len(cases) == len(grid) + 1 and len({c[0] for c in cases}) == len(cases)
+    for name, sig, start, end, params, pens in cases:
+        assert len(params) > T and sig.dtype == np.float32 and params.dtype == np.float32, name      # every one is the scratch form
+    wins = [c for c in cases if c[2] > 0 and c[3] < len(c[1])]
+    assert len(wins) == 1 and wins[0][5] is PENS[1]
+    assert {c[5] for c in cases} == set(PENS)
+
+
+def test_scratch_plan_keeps_neighbours_apart():
+    """squig_plan_add: k_squig touches 2 (2 npos + 1) floats from a read's scratch offset (both rows: START, the positions
+    and the back states).  The sizes of scratch_npos, T + 1 ... T + 5, LDS reads between them, several orders."""
+    from test_map_cpu import check_scratch_plan
+    T = lds_threshold()
+    npos = [T + 1, T + 2, 5, T + 3, T, T + 4, T + 5] + list(scratch_npos(T)) + [T - 1, T + 1, 1 << 20]
+    rng = np.random.default_rng(29)
+    for order in (np.arange(len(npos)), np.arange(len(npos))[::-1], rng.permutation(len(npos)), rng.permutation(len(npos))):
+        P = [npos[i] for i in order]
+        check_scratch_plan("squig", P, [SCRATCH_NSAMPLE[i % 7] for i in range(len(P))], lambda n: n <= T, lambda n: 2 * (2 * n + 1))
+    for n in (T + 1, T + 2, T + 3, T + 4):
+        check_scratch_plan("squig", [n], [64], lambda m: m <= T, lambda m: 2 * (2 * m + 1))
+
+
+@pytest.mark.parametrize("viterbi", [True, False])
+def test_restatement_equals_reference_scratch_cases(viterbi):
+    """as test_restatement_equals_reference on squig_scratch_cases; and some PENS[1] path there goes through a back state,
+    some through a skip"""
+    R = ref_squiggle_lib()
+    if R is None:
+        pytest.skip("oracle/_ref/libref_decode.so not built")
+    nback = nskip = 0
+    for name, sig, start, end, params, pens in squig_scratch_cases(lds_threshold()):
+        want_s, want_p = call_squig(R, sig, start, end, params, pens, viterbi)
+        got_s, got_p = np_squiggle_match(sig[start:end], params, *pens, viterbi=viterbi)
+        if viterbi:
+            assert np.float32(got_s).tobytes() == want_s.tobytes(), (name, got_s, want_s)
+            assert np.all(want_p[:start] == -1) and np.all(want_p[end:] == -1), name
+            assert np.array_equal(got_p, want_p[start:end]), name
+            if pens is PENS[1]:
+                b, k = path_moves(want_p)
+                nback += b; nskip += k
+        else:
+            assert abs(float(got_s) - float(want_s)) <= 1e-5 * abs(float(want_s)) + 1e-3, (name, got_s, want_s)
+    if viterbi:
+        assert nback > 0 and nskip > 0, (nback, nskip)
+
+
 def test_case_grid_covers_the_sizes():
     T = lds_threshold()
     assert 256 < T < 65536
