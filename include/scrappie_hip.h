@@ -177,11 +177,24 @@ int *encode_bases_to_integers(char const *seq, size_t n, size_t state_len);
  * the START / END states, positions elsewhere.  The Viterbi score and path are bit-identical to the reference's; forward
  * agrees to float rounding.  Where the reference asserts or is undefined (rate <= 0, prob_back outside [0, 1],
  * start >= end, end > n, a squiggle of no positions, NULL arguments) these return NAN, set scrappie_hip_last_error() and
- * launch nothing.  The squiggle itself (squiggle_r94 and its relatives) is not built: it is an input here. */
+ * launch nothing.  The squiggle comes from squiggle_r94 and its relatives below, or from anywhere else. */
 float squiggle_match_viterbi(const raw_table signal, float rate, const_scrappie_matrix params, float prob_back, float local_pen,
                              float skip_pen, float minscore, int32_t *path_padded);
 float squiggle_match_forward(const raw_table signal, float rate, const_scrappie_matrix params, float prob_back, float local_pen,
                              float skip_pen, float minscore);
+
+/* Prediction of a squiggle from a base sequence (src/networks.c:397, :454, :511; python/pyscrap.h:29-31).  Same signatures:
+ * sequence holds n bases coded 0..3 (encode_bases_to_integers(seq, n, 1)); the result has n columns of (mean, log sd, dwell
+ * logit), nr 3, stride 4, pad lane 0, malloc'd, freed by free_scrappie_matrix.  transform_units: column 1 <- expf(x),
+ * column 2 <- expf(-x), on the host with libm.  The network (an embedding and six convolutions, sh_sqnet.h) runs on the
+ * process-default engine as a batch of one; its weights are the model registered under the function's name
+ * (scrappie_hip_register_model, or <name>.scrm under SCRAPPIE_MODEL_DIR).  The output agrees with the reference's to float
+ * rounding (another summation order).  Where the reference is undefined or asserts (a NULL sequence, fewer than WL - 1
+ * bases -- WL 9, for squiggle_r94_rna 7: the edge products of `convolution` read outside their input --, a code outside
+ * 0..3) and for an unregistered model these return NULL, set scrappie_hip_last_error() and launch nothing. */
+scrappie_matrix squiggle_r94(int const *sequence, size_t n, bool transform_units);
+scrappie_matrix squiggle_r94_rna(int const *sequence, size_t n, bool transform_units);
+scrappie_matrix squiggle_r10(int const *sequence, size_t n, bool transform_units);
 
 /* ------------------------------------------------------------------------
  * (2) Batched engine surface (additive)
@@ -424,7 +437,8 @@ size_t scrappie_hip_map_lds_max_seq(void);
 
 /* Squiggle matching, batched (sh_eng_squig.inc): reads[i] (trimmed, normalised; mapped over [start, end)) against
  * targets[i], a predicted squiggle of npos columns of stride >= 3 floats (mean, log sd, dwell logit); out[i] belongs to
- * reads[i].  No network runs and no model is needed.  viterbi 0: forward scores.  want_path (Viterbi only): out[i].path
+ * reads[i].  No network runs and no model is needed (the squiggles are an input here: scrappie_hip_squiggle_predict_batch
+ * makes them).  viterbi 0: forward scores.  want_path (Viterbi only): out[i].path
  * is the reference's path_padded, malloc'd, out[i].n = reads[i].n int32.  The call is cut into launches whose
  * traceback (samples x positions / 2 bytes per read) and scratch fit half of the device memory that is free; a single
  * read that does not fit gets NAN and an error text, as does one the per-read functions refuse, and the others are
@@ -448,6 +462,22 @@ size_t scrappie_hip_squiggle_lds_max_pos(void);
  * k_squig 2 (2 npos + 1). */
 long long scrappie_hip_map_plan_scratch(const size_t *seqlen, const size_t *nblock, size_t n, long long *off);
 long long scrappie_hip_squiggle_plan_scratch(const size_t *npos, const size_t *nsample, size_t n, long long *off);
+/* Squiggle prediction, batched (sh_eng_sqnet.inc): seqs[i] holds n[i] bases coded 0..3; out[i] becomes a matrix as
+ * squiggle_r94 returns it (free_scrappie_matrix), predicted with `model`, a squiggle model loaded on e under that name.
+ * The accepted sequences are laid end to end: one upload, one k_sqnet launch over all their tiles, one download; the call
+ * is cut into several such launches where codes and outputs (13 bytes per base) exceed half of the device memory that is
+ * free.  A sequence the per-read functions refuse, or one that alone exceeds a launch, gets out[i] = NULL and an error
+ * text, and the others are untouched.  Returns 0, or -1 with scrappie_hip_last_error() when the call as a whole fails
+ * (then every out[i] is NULL).  A launch holds the engine's lock. */
+int scrappie_hip_squiggle_predict_batch(scrappie_hip_engine *e, const char *model, const int *const *seqs, const size_t *n, size_t count,
+                                        int transform_units, scrappie_matrix *out);
+/* the last scrappie_hip_squiggle_predict_batch call's time, milliseconds summed over its launches: [0] staging + upload,
+ * [1] k_sqnet, [2] download + transform (host clock, the stream drained between the stages) */
+void scrappie_hip_sqnet_timing(scrappie_hip_engine *e, double out[3]);
+/* output positions per workgroup of k_sqnet (host only, no device): sequences longer than this span several tiles */
+size_t scrappie_hip_sqnet_tile(void);
+/* launches of k_sqnet since the process started, all engines together (a host counter) */
+uint64_t scrappie_hip_sqnet_launch_count(void);
 /* Launches of each kernel form since the process started, all engines together (the per-read functions run on the
  * process-default engine).  map_forms[(viterbi ? 8 : 0) | (banded ? 4 : 0) | (tiled ? 2 : 0) | (scratch ? 1 : 0)] for k_map,
  * squig_forms[(viterbi ? 2 : 0) | (scratch ? 1 : 0)] for k_squig; either may be NULL.  Host counters only: no device work. */

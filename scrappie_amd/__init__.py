@@ -255,6 +255,15 @@ def lib():
     for nm in ("scrappie_hip_map_plan_scratch", "scrappie_hip_squiggle_plan_scratch"):
         getattr(L, nm).restype = C.c_longlong
         getattr(L, nm).argtypes = [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(C.c_longlong)]
+    for nm in ("squiggle_r94", "squiggle_r94_rna", "squiggle_r10"):
+        getattr(L, nm).restype = PM
+        getattr(L, nm).argtypes = [ip, C.c_size_t, C.c_bool]
+    L.scrappie_hip_squiggle_predict_batch.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(ip), sp, C.c_size_t, C.c_int, C.POINTER(PM)]
+    L.scrappie_hip_sqnet_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    L.scrappie_hip_sqnet_tile.restype = C.c_size_t
+    L.scrappie_hip_sqnet_tile.argtypes = []
+    L.scrappie_hip_sqnet_launch_count.restype = C.c_uint64
+    L.scrappie_hip_sqnet_launch_count.argtypes = []
     L.scrappie_hip_launch_form_counts.restype = None
     L.scrappie_hip_launch_form_counts.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     _lib = L
@@ -586,12 +595,47 @@ def map_post_to_sequence(post, sequence, stay_pen=0, skip_pen=0, local_pen=4.0, 
     return score, path_data
 
 
-def _squiggle_matrix(squiggle):
+_squiggle_fn_ = {
+    'squiggle_r94': 'squiggle_r94',
+    'squiggle_r94_rna': 'squiggle_r94_rna',
+    'squiggle_r10': 'squiggle_r10',
+}
+
+
+def _base_codes(sequence):
+    """the bases of `sequence` coded 0..3 as an int32 array (encode_bases_to_integers with a state of one base)"""
+    return encode_bases(sequence, 1).astype(np.int32)
+
+
+def sequence_to_squiggle(sequence, model='squiggle_r94', rescale=False):
+    """python/scrappy/__init__.py:433-459: the squiggle a base sequence is predicted to give, a `ScrappyMatrix` of
+    len(sequence) columns of (mean, log sd, dwell logit); with rescale, (mean, sd, expected dwell).  The network runs on
+    the GPU; `model` must have been registered (`register_model`): no weights are compiled in."""
+    try:
+        fn = getattr(lib(), _squiggle_fn_[model])
+    except KeyError:
+        raise KeyError("Squiggle model '{}' not recognised.".format(model))
+    ptr = lib().encode_bases_to_integers(sequence.encode(), len(sequence), 1)
+    if not ptr:
+        raise RuntimeError('An unknown error occurred whilst encoding sequence: ' + last_error())
+    try:
+        squiggle = fn(C.cast(ptr, C.POINTER(C.c_int)), len(sequence), rescale)
+    finally:
+        _libc.free(ptr)
+    if not squiggle:
+        raise RuntimeError('An unknown error occurred whilst generating squiggle: ' + last_error())
+    return ScrappyMatrix(squiggle)
+
+
+def _squiggle_matrix(squiggle, model=None):
     """a predicted squiggle as a ScrappyMatrix of npos columns (mean, log sd, dwell logit): one as it is, an (npos, 3)
-    array converted; a base sequence would need the squiggle-predicting network, which is not built"""
+    array converted, a base sequence predicted with the squiggle model `model`"""
     if isinstance(squiggle, str):
-        raise NotImplementedError("squiggle prediction (sequence_to_squiggle) is not built: pass the predicted squiggle, "
-                                  "a ScrappyMatrix or an (npos, 3) array of (mean, log sd, dwell logit)")
+        if model is None:
+            raise NotImplementedError("a base sequence needs the name of a registered squiggle model (model='squiggle_r94', "
+                                      "...; no weights are compiled in); or pass the predicted squiggle, a ScrappyMatrix or "
+                                      "an (npos, 3) array of (mean, log sd, dwell logit)")
+        return sequence_to_squiggle(squiggle, model=model, rescale=False)
     if isinstance(squiggle, ScrappyMatrix):
         return squiggle
     a = np.asarray(squiggle, dtype=ftype)
@@ -622,10 +666,11 @@ def squiggle_match(rt, squiggle, rate=1.0, back_prob=0.0, local_pen=2.0, skip_pe
     return score, (path_data if path else None)
 
 
-def map_signal_to_squiggle(data, squiggle, rate=1.0, back_prob=0.0, local_pen=2.0, skip_pen=5000.0, min_score=5.0):
-    """python/scrappy/__init__.py:462-489 with the predicted squiggle (a `ScrappyMatrix` or an (npos, 3) array) in place
-    of (sequence, model): trim -> scale -> squiggle_match_viterbi.  Returns (score, path over the whole of `data`)."""
-    sq = _squiggle_matrix(squiggle)
+def map_signal_to_squiggle(data, squiggle, rate=1.0, back_prob=0.0, local_pen=2.0, skip_pen=5000.0, min_score=5.0, model=None):
+    """python/scrappy/__init__.py:462-489: `squiggle` is a base sequence, predicted with the registered squiggle model
+    `model`, or the predicted squiggle itself (a `ScrappyMatrix` or an (npos, 3) array); then trim -> scale ->
+    squiggle_match_viterbi.  Returns (score, path over the whole of `data`)."""
+    sq = _squiggle_matrix(squiggle, model)
     raw = RawTable(data)
     raw.trim().scale()
     return squiggle_match(raw, sq, rate, back_prob, local_pen, skip_pen, min_score, viterbi=True, path=True)
@@ -1106,6 +1151,46 @@ class Engine(object):
             pth = np.ctypeslib.as_array(r.path, shape=(r.n,)).copy() if r.path else None
             res.append((float(r.score), pth))
         lib().scrappie_hip_free_squiggle_results(out, n)
+        return res
+
+    def predict_squiggle(self, sequences, model='squiggle_r94', rescale=False):
+        """The predicted squiggle of each base sequence (a str over ACGT, or an int array of codes 0..3), batched
+        (scrappie_hip_squiggle_predict_batch): a list of (npos, 3) float32 arrays of (mean, log sd, dwell logit) -- with
+        rescale (mean, sd, expected dwell) -- in input order, None where a sequence is refused (`last_error()` says why).
+        `model`: a squiggle model loaded on this engine."""
+        n = len(sequences)
+        ip = C.POINTER(C.c_int)
+        codes = [_base_codes(x) if isinstance(x, str) else np.ascontiguousarray(x, dtype=np.int32) for x in sequences]
+        ptrs = (ip * max(n, 1))(*[c.ctypes.data_as(ip) for c in codes])
+        lens = (C.c_size_t * max(n, 1))(*[len(c) for c in codes])
+        out = (C.POINTER(_Mat) * max(n, 1))()
+        if lib().scrappie_hip_squiggle_predict_batch(self._h, model.encode(), ptrs, lens, n, 1 if rescale else 0, out) != 0:
+            raise RuntimeError("squiggle_predict_batch: " + last_error())
+        res = []
+        for i in range(n):
+            res.append(ScrappyMatrix(out[i]).data(as_numpy=True, sloika=False) if out[i] else None)
+        return res
+
+    def sqnet_timing(self):
+        """the last predict_squiggle call's time (ms, summed over launches): upload, k_sqnet, download + transform"""
+        t = (C.c_double * 3)()
+        lib().scrappie_hip_sqnet_timing(self._h, t)
+        return dict(upload_ms=t[0], net_ms=t[1], download_ms=t[2])
+
+    def mappy(self, signals, sequences, model='squiggle_r94', rate=1.0, back_prob=0.0, local_pen=2.0, skip_pen=5000.0,
+              min_score=5.0):
+        """Each signal (trimmed, normalised float32 array, or a `RawTable` with its window) against the squiggle predicted
+        for its base sequence: one batched prediction, then one batched Viterbi match of the downloaded squiggles.
+        Returns [(score, path)] in input order; (nan, None) where a sequence or a read is refused."""
+        if len(signals) != len(sequences):
+            raise ValueError("one sequence per signal")
+        sqs = self.predict_squiggle(sequences, model=model, rescale=False)
+        keep = [i for i, sq in enumerate(sqs) if sq is not None]
+        got = self.match_squiggle([signals[i] for i in keep], [sqs[i] for i in keep], viterbi=True, path=True, rate=rate,
+                                  back_prob=back_prob, local_pen=local_pen, skip_pen=skip_pen, min_score=min_score)
+        res = [(float("nan"), None)] * len(signals)
+        for i, r in zip(keep, got):
+            res[i] = r
         return res
 
     def squiggle_timing(self):

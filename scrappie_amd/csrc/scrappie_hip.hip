@@ -36,6 +36,7 @@
  *   sh_eng_surface.inc   the reference's per-read functions: one batch function per family, run by the queue or with a batch of one
  *   sh_eng_map.inc       block-based mapping of posteriors to sequences (per-read and batched)
  *   sh_eng_squig.inc     mapping of raw signals to predicted squiggles (per-read and batched)
+ *   sh_eng_sqnet.inc     prediction of squiggles from base sequences (per-read and batched)
  * Separate translation units: sh_p0.hip (signal preparation, k_p0), sh_host.c / sh_fast5.c / sh_h5mini.c (host C);
  * sh_coalesce.h (the per-read functions' queue) and sh_dev.h (DBuf / HBuf: buffers that own their memory) are plain C++ headers.
  */
@@ -68,6 +69,7 @@
 #include "sh_coalesce.h"
 #include "sh_map.h"
 #include "sh_squig.h"
+#include "sh_sqnet.h"
 
 /* function attributes (dynamic LDS limit) are per device: remember for which devices a kernel has had its attribute set
  * (engines on several GPUs may share one process).  A real once per device: the thread that finds the attribute unset holds
@@ -383,6 +385,9 @@ struct scrappie_hip_engine {
     double map_ms[3] = {0, 0, 0};    /* scrappie_hip_map_batch: network + S1, k_map, k_map_walk + results, summed over the last call's launch groups */
     DBuf d_sq[9]; HBuf h_sq;         /* squiggle matching (sh_eng_squig.inc): records, signals, tables, traceback, scratch, scores, final states, path offsets, paths */
     double squig_ms[3] = {0, 0, 0};  /* scrappie_hip_squiggle_match_batch: tables + uploads, k_squig, k_squig_walk + results, summed over the last call's launches */
+    DBuf d_sqn[2]; HBuf h_sqn;       /* squiggle prediction (sh_eng_sqnet.inc): tiles | codes, outputs */
+    double sqnet_ms[3] = {0, 0, 0};  /* scrappie_hip_squiggle_predict_batch: upload, k_sqnet, download + transform, summed over the last call's launches */
+    size_t dbg_sqnet_budget = 0;     /* device bytes one squiggle-predicting launch may hold (debug option "sqnet_budget_kb"; 0: half of the free memory) */
     size_t dbg_squig_budget = 0;     /* device bytes one squiggle-matching launch may hold (debug option "squiggle_budget_kb"; 0: half of the free memory) */
     std::mutex call_mu;              /* scrappie_hip_basecall_batch: one call at a time inside the engine (concurrent small calls share one: sh_eng_batch.inc) */
     /* (scrappie_hip_engine_destroy has made the device current and drained the streams; the slots and the buffers go after this body) */
@@ -517,3 +522,4 @@ extern "C" scrappie_hip_params scrappie_hip_default_params(void) {
 #include "sh_eng_surface.inc"      /* the reference's per-read functions: posterior / trunk on an explicit engine, the process-default engine, decode_transducer, decode_crf; all three coalesced (sh_coalesce.h) */
 #include "sh_eng_map.inc"      /* block-based mapping (sh_map.h): map_to_sequence_* on the process-default engine, scrappie_hip_map_batch */
 #include "sh_eng_squig.inc"      /* squiggle matching (sh_squig.h): squiggle_match_* on the process-default engine, scrappie_hip_squiggle_match_batch */
+#include "sh_eng_sqnet.inc"      /* squiggle prediction (sh_sqnet.h): squiggle_r94 and its relatives on the process-default engine, scrappie_hip_squiggle_predict_batch */

@@ -1,0 +1,302 @@
+/* scrappie_squiggle.c -- the `scrappie squiggle` and `scrappie mappy` command lines over libscrappie_hip.so
+ * (src/scrappie_squiggle.c, src/scrappie_mappy.c).
+ *
+ * Same options, defaults and output as the reference's subcommands.  squiggle: the predicted squiggle of every record of
+ * every FASTA file, all of them in ONE scrappie_hip_squiggle_predict_batch call, written in input order; a record the
+ * network refuses (a base outside ACGT, fewer bases than the window needs) is skipped, as the reference skips a NULL
+ * squiggle.  mappy: the first record's squiggle, then squiggle_match_viterbi of the read against it.  Added: --model-file /
+ * --device as `scrappie raw` takes them (the weights are data: default $SCRAPPIE_MODEL_DIR/<model>.scrm).
+ */
+#define _GNU_SOURCE
+#include <getopt.h>
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <sys/types.h>
+
+#include "scrappie_hip.h"
+
+int main_squiggle(int argc, char **argv);
+int main_mappy(int argc, char **argv);
+
+struct fa_rec { char *name, *seq; size_t n; };
+
+/* the records of a FASTA file appended to *recs (at most `limit` in all, 0: no limit): the name is the header up to the first
+ * blank, the sequence its lines joined; -1 if the file cannot be opened */
+static int read_fasta(const char *path, struct fa_rec **recs, size_t *nrec, size_t limit) {
+    FILE *fh = fopen(path, "r");
+    if (!fh) return -1;
+    char *line = NULL;
+    size_t cap = 0, scap = 0;
+    ssize_t got;
+    struct fa_rec *cur = NULL;
+    while ((got = getline(&line, &cap, fh)) != -1) {
+        while (got > 0 && (line[got - 1] == '\n' || line[got - 1] == '\r')) line[--got] = '\0';
+        if (line[0] == '>') {
+            if (limit && *nrec >= limit) break;
+            struct fa_rec *grown = realloc(*recs, (*nrec + 1) * sizeof **recs);
+            if (!grown) break;
+            *recs = grown;
+            cur = &grown[(*nrec)++];
+            cur->name = strndup(line + 1, strcspn(line + 1, " \t"));
+            cur->seq = calloc(1, 1); cur->n = 0; scap = 1;
+            continue;
+        }
+        if (!cur || got == 0 || !cur->seq) continue;
+        if (cur->n + (size_t)got + 1 > scap) {
+            scap = 2 * (cur->n + (size_t)got + 1);
+            char *s = realloc(cur->seq, scap);
+            if (!s) break;
+            cur->seq = s;
+        }
+        memcpy(cur->seq + cur->n, line, (size_t)got); cur->n += (size_t)got; cur->seq[cur->n] = '\0';
+    }
+    free(line);
+    fclose(fh);
+    return 0;
+}
+
+static void free_recs(struct fa_rec *recs, size_t n) {
+    for (size_t i = 0; i < n; i++) { free(recs[i].name); free(recs[i].seq); }
+    free(recs);
+}
+
+static int squiggle_model_ok(const char *name) {      /* scrappie_stdlib.h: get_squiggle_model */
+    return !strcmp(name, "squiggle_r94") || !strcmp(name, "squiggle_r94_rna") || !strcmp(name, "squiggle_r10");
+}
+
+/* engine + model as the options name them; NULL with the reason on stderr */
+static scrappie_hip_engine *open_model(int device, const char *model, const char *model_file) {
+    char *mpath = NULL;
+    if (model_file) mpath = strdup(model_file);
+    else if (getenv("SCRAPPIE_MODEL_DIR")) { if (asprintf(&mpath, "%s/%s.scrm", getenv("SCRAPPIE_MODEL_DIR"), model) < 0) mpath = NULL; }
+    if (!mpath) { fprintf(stderr, "scrappie: no weights for model %s: give --model-file or set SCRAPPIE_MODEL_DIR\n", model); return NULL; }
+    scrappie_hip_engine *e = scrappie_hip_engine_create(device);
+    if (!e) { fprintf(stderr, "scrappie: %s\n", scrappie_hip_last_error()); free(mpath); return NULL; }
+    const int h = scrappie_hip_load_model(e, model, mpath);
+    free(mpath);
+    if (h < 0) { fprintf(stderr, "scrappie: %s\n", scrappie_hip_last_error()); scrappie_hip_engine_destroy(e); return NULL; }
+    return e;
+}
+
+static void squiggle_usage(FILE *fh) {
+    fputs("Usage: scrappie squiggle [OPTION...] fasta [fasta ...]\n"
+          "Scrappie squiggler\n\n"
+          "  -l, --limit=nreads         Maximum number of reads to call (0 is unlimited)\n"
+          "  -m, --model=name           Squiggle model to use: \"squiggle_r94\", \"squiggle_r94_rna\", \"squiggle_r10\"\n"
+          "  -o, --output=filename      Write to file rather than stdout\n"
+          "  -p, --prefix=string        Prefix to append to name of each read\n"
+          "      --rescale, --no-rescale   Rescale network output (default) or don't\n"
+          "      --licence, --license   Print licensing information\n"
+          "      --model-file=path      Weight container (.scrm); default $SCRAPPIE_MODEL_DIR/<model>.scrm\n"
+          "      --device=N             GPU to run on (default 0)\n"
+          "All records of all files are predicted in one batched engine call and written in input order.\n", fh);
+}
+
+int main_squiggle(int argc, char **argv) {
+    enum { O_RESCALE = 256, O_NORESCALE, O_LIC, O_MFILE, O_DEV };
+    static const struct option lo[] = {
+        {"model", 1, 0, 'm'}, {"limit", 1, 0, 'l'}, {"output", 1, 0, 'o'}, {"prefix", 1, 0, 'p'}, {"rescale", 0, 0, O_RESCALE},
+        {"no-rescale", 0, 0, O_NORESCALE}, {"licence", 0, 0, O_LIC}, {"license", 0, 0, O_LIC}, {"model-file", 1, 0, O_MFILE},
+        {"device", 1, 0, O_DEV}, {"help", 0, 0, '?'}, {0, 0, 0, 0}};
+    /* defaults: scrappie_squiggle.c:47-54 */
+    const char *model = "squiggle_r94", *model_file = NULL;
+    FILE *out = stdout;
+    int limit = 0, rescale = 1, device = 0, c;
+    optind = 1;
+    while ((c = getopt_long(argc, argv, "m:l:o:p:", lo, NULL)) != -1) {
+        switch (c) {
+        case 'm':
+            if (!squiggle_model_ok(optarg)) { fprintf(stderr, "scrappie: Invalid squiggle model name \"%s\"\n", optarg); return EXIT_FAILURE; }
+            model = optarg;
+            break;
+        case 'l':
+            limit = atoi(optarg);
+            if (limit < 0) { fprintf(stderr, "scrappie: --limit wants a count\n"); return EXIT_FAILURE; }
+            break;
+        case 'o':
+            out = fopen(optarg, "w");
+            if (!out) { fprintf(stderr, "scrappie: Failed to open \"%s\" for output.\n", optarg); return EXIT_FAILURE; }
+            break;
+        case 'p': break;                 /* accepted; the reference's squiggle never prints it */
+        case O_RESCALE: rescale = 1; break;
+        case O_NORESCALE: rescale = 0; break;
+        case O_LIC: puts("Mozilla Public License 2.0 applies to the reference interface this build follows."); exit(EXIT_SUCCESS);
+        case O_MFILE: model_file = optarg; break;
+        case O_DEV: device = atoi(optarg); break;
+        default: squiggle_usage(stderr); return EXIT_FAILURE;
+        }
+    }
+    if (argc - optind <= 0) { squiggle_usage(stderr); return EXIT_FAILURE; }
+    scrappie_hip_engine *e = open_model(device, model, model_file);
+    if (!e) return EXIT_FAILURE;
+
+    struct fa_rec *recs = NULL;
+    size_t nrec = 0;
+    for (int fn = optind; fn < argc; fn++) {
+        if (limit > 0 && nrec >= (size_t)limit) break;
+        if (read_fasta(argv[fn], &recs, &nrec, (size_t)limit)) fprintf(stderr, "scrappie: Failed to open \"%s\" for input.\n\n", argv[fn]);
+    }
+    int rc = EXIT_SUCCESS;
+    int **codes = calloc(nrec ? nrec : 1, sizeof *codes);
+    size_t *lens = calloc(nrec ? nrec : 1, sizeof *lens);
+    scrappie_matrix *sq = calloc(nrec ? nrec : 1, sizeof *sq);
+    for (size_t i = 0; i < nrec; i++) {
+        codes[i] = recs[i].seq ? encode_bases_to_integers(recs[i].seq, recs[i].n, 1) : NULL;      /* NULL: refused below, like a NULL sequence */
+        lens[i] = recs[i].n;
+    }
+    if (scrappie_hip_squiggle_predict_batch(e, model, (const int *const *)codes, lens, nrec, rescale, sq) != 0) {
+        fprintf(stderr, "scrappie: %s\n", scrappie_hip_last_error());
+        rc = EXIT_FAILURE;
+    } else {
+        for (size_t i = 0; i < nrec; i++) {
+            if (!sq[i]) continue;
+            /* scrappie_squiggle.c:157-164 */
+            fprintf(out, "#%s\n", recs[i].name ? recs[i].name : "");
+            fprintf(out, "pos\tbase\tcurrent\tsd\tdwell\n");
+            for (size_t k = 0; k < sq[i]->nc; k++) {
+                const float *col = sq[i]->data.f + k * sq[i]->stride;
+                fprintf(out, "%zu\t%c\t%3.6f\t%3.6f\t%3.6f\n", k, recs[i].seq[k], col[0], col[1], col[2]);
+            }
+        }
+    }
+    for (size_t i = 0; i < nrec; i++) { free(codes[i]); free_scrappie_matrix(sq[i]); }
+    free(codes); free(lens); free(sq);
+    free_recs(recs, nrec);
+    if (out != stdout) fclose(out);
+    scrappie_hip_engine_destroy(e);
+    return rc;
+}
+
+static void mappy_usage(FILE *fh) {
+    fputs("Usage: scrappie mappy [OPTION...] fasta fast5\n"
+          "Scrappie squiggler\n\n"
+          "  -b, --backprob=probability Probability of backwards movement\n"
+          "  -k, --skippen=float        Penalty for skipping position\n"
+          "  -l, --localpen=float       Penalty for local matching\n"
+          "  -m, --minscore=float       Minimum possible score for matching emission\n"
+          "      --model=name           Squiggle model to use: \"squiggle_r94\", \"squiggle_r94_rna\" or \"squiggle_r10\"\n"
+          "  -o, --output=filename      Write to file rather than stdout\n"
+          "  -p, --prefix=string        Prefix to append to name of read\n"
+          "  -r, --rate=float           Translocation rate of read relative to standard squiggle\n"
+          "  -s, --segmentation=chunk:percentile\n"
+          "                             Chunk size and percentile for variance based segmentation\n"
+          "  -t, --trim=start:end       Number of samples to trim, as start:end\n"
+          "      --licence, --license   Print licensing information\n"
+          "      --model-file=path      Weight container (.scrm); default $SCRAPPIE_MODEL_DIR/<model>.scrm\n"
+          "      --device=N             GPU to run on (default 0)\n", fh);
+}
+
+int main_mappy(int argc, char **argv) {
+    enum { O_MODEL = 256, O_LIC, O_MFILE, O_DEV };
+    static const struct option lo[] = {
+        {"model", 1, 0, O_MODEL}, {"backprob", 1, 0, 'b'}, {"skippen", 1, 0, 'k'}, {"localpen", 1, 0, 'l'}, {"minscore", 1, 0, 'm'},
+        {"output", 1, 0, 'o'}, {"prefix", 1, 0, 'p'}, {"rate", 1, 0, 'r'}, {"segmentation", 1, 0, 's'}, {"trim", 1, 0, 't'},
+        {"licence", 0, 0, O_LIC}, {"license", 0, 0, O_LIC}, {"model-file", 1, 0, O_MFILE}, {"device", 1, 0, O_DEV}, {"help", 0, 0, '?'},
+        {0, 0, 0, 0}};
+    /* defaults: scrappie_mappy.c:59-75 */
+    scrappie_hip_squiggle_params p = scrappie_hip_default_squiggle_params();
+    const char *model = "squiggle_r94", *model_file = NULL;
+    FILE *out = stdout;
+    int trim_start = 200, trim_end = 10, varseg_chunk = 100, device = 0, c;
+    float varseg_thresh = 0.0f;
+    char *colon;
+    optind = 1;
+    while ((c = getopt_long(argc, argv, "b:k:l:m:o:p:r:s:t:", lo, NULL)) != -1) {
+        switch (c) {
+        case O_MODEL:
+            if (!squiggle_model_ok(optarg)) { fprintf(stderr, "scrappie: Invalid squiggle model name \"%s\"\n", optarg); return EXIT_FAILURE; }
+            model = optarg;
+            break;
+        case 'b':
+            p.prob_back = (float)atof(optarg);
+            if (!(p.prob_back >= 0.0f && p.prob_back < 1.0f)) { fprintf(stderr, "scrappie: Backwards probability must be in [0, 1). Got %f\n", p.prob_back); return EXIT_FAILURE; }
+            break;
+        case 'k': p.skip_pen = (float)atof(optarg); break;
+        case 'l': p.local_pen = (float)atof(optarg); break;
+        case 'm': p.minscore = (float)atof(optarg); break;
+        case 'o':
+            out = fopen(optarg, "w");
+            if (!out) { fprintf(stderr, "scrappie: Failed to open \"%s\" for output.\n", optarg); return EXIT_FAILURE; }
+            break;
+        case 'p': break;                 /* accepted; the reference's mappy never prints it */
+        case 'r':
+            p.rate = (float)atof(optarg);
+            if (!(p.rate > 0.0f)) { fprintf(stderr, "scrappie: Rate must be positive, got %f\n", p.rate); return EXIT_FAILURE; }
+            break;
+        case 's':
+            colon = strchr(optarg, ':');
+            if (!colon) { fprintf(stderr, "scrappie: --segmentation should be of form chunk:percentile\n"); return EXIT_FAILURE; }
+            varseg_chunk = atoi(optarg); varseg_thresh = (float)(atof(colon + 1) / 100.0);
+            if (varseg_chunk < 0 || !(varseg_thresh > 0.0f && varseg_thresh < 1.0f)) { fprintf(stderr, "scrappie: --segmentation should be of form chunk:percentile\n"); return EXIT_FAILURE; }
+            break;
+        case 't':
+            colon = strchr(optarg, ':');
+            trim_start = atoi(optarg); trim_end = colon ? atoi(colon + 1) : trim_start;
+            if (trim_start < 0 || trim_end < 0) { fprintf(stderr, "scrappie: --trim wants start:end\n"); return EXIT_FAILURE; }
+            break;
+        case O_LIC: puts("Mozilla Public License 2.0 applies to the reference interface this build follows."); exit(EXIT_SUCCESS);
+        case O_MFILE: model_file = optarg; break;
+        case O_DEV: device = atoi(optarg); break;
+        default: mappy_usage(stderr); return EXIT_FAILURE;
+        }
+    }
+    if (argc - optind <= 0) { mappy_usage(stderr); return EXIT_FAILURE; }
+    if (argc - optind < 2) { fprintf(stderr, "scrappie: fast5 file is a required argument\n"); return EXIT_FAILURE; }      /* scrappie_mappy.c:152 */
+    const char *fasta = argv[optind], *fast5 = argv[optind + 1];
+    scrappie_hip_engine *e = open_model(device, model, model_file);
+    if (!e) return EXIT_FAILURE;
+
+    int rc = EXIT_FAILURE;
+    struct fa_rec *recs = NULL;
+    size_t nrec = 0;
+    raw_table rt = {0};
+    int *codes = NULL;
+    scrappie_matrix sq = NULL;
+    scrappie_hip_squiggle_result res = {0};
+    if (read_fasta(fasta, &recs, &nrec, 1) || nrec == 0 || !recs[0].seq || recs[0].n == 0) {
+        fprintf(stderr, "scrappie: Failed to open \"%s\" for input.\n\n", fasta);
+        goto done;
+    }
+    /* scrappie_mappy.c:197-204 */
+    rt = scrappie_hip_read_raw(fast5, true);
+    rt = trim_and_segment_raw(rt, (size_t)trim_start, (size_t)trim_end, (size_t)varseg_chunk, varseg_thresh);
+    if (!rt.raw) { fprintf(stderr, "scrappie: Failed to open \"%s\" for input and trim signal.\n\n", fast5); goto done; }
+    medmad_normalise_array(rt.raw + rt.start, rt.end - rt.start);
+
+    rc = EXIT_SUCCESS;                   /* from here on the reference prints what it has and succeeds */
+    codes = encode_bases_to_integers(recs[0].seq, recs[0].n, 1);
+    const int *cp = codes;
+    if (!codes || scrappie_hip_squiggle_predict_batch(e, model, &cp, &recs[0].n, 1, 0, &sq) != 0 || !sq) {
+        fprintf(stderr, "scrappie: %s\n", scrappie_hip_last_error());
+        goto done;
+    }
+    scrappie_hip_squiggle_target tg = {sq->data.f, sq->nc, sq->stride};
+    if (scrappie_hip_squiggle_match_batch(e, &rt, &tg, 1, &p, 1, 1, &res) != 0 || !res.path) {
+        fprintf(stderr, "scrappie: %s\n", scrappie_hip_last_error());
+        rc = EXIT_FAILURE;
+        goto done;
+    }
+    /* scrappie_mappy.c:215-228 */
+    fprintf(out, "# %s to %s  (score = %f)\n", fast5, fasta, res.score);
+    fprintf(out, "idx\tsignal\tpos\tbase\tcurrent\tsd\tdwell\n");
+    for (size_t i = 0; i < rt.n; i++) {
+        const int32_t pos = res.path[i];
+        if (pos >= 0) {
+            const float *col = sq->data.f + (size_t)pos * sq->stride;
+            fprintf(out, "%zu\t%3.6f\t%d\t%c\t%3.6f\t%3.6f\t%3.6f\n", i, rt.raw[i], pos, recs[0].seq[pos], col[0], expf(col[1]), expf(-col[2]));
+        } else {
+            fprintf(out, "%zu\t%3.6f\t%d\tN\tnan\tnan\tnan\n", i, (i >= rt.start && i < rt.end) ? rt.raw[i] : NAN, pos);
+        }
+    }
+done:
+    scrappie_hip_free_squiggle_results(&res, 1);
+    free_scrappie_matrix(sq);
+    free(codes);
+    free(rt.raw); free(rt.uuid);
+    free_recs(recs, nrec);
+    if (out != stdout) fclose(out);
+    scrappie_hip_engine_destroy(e);
+    return rc;
+}

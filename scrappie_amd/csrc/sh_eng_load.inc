@@ -8,6 +8,7 @@ static const HostMat *find_mat(const std::vector<std::pair<std::string, HostMat>
 }
 
 static int load_model_mem_one(scrappie_hip_engine *e, const char *name, const void *blob, size_t nbytes);
+static int sqnet_load(Model *m, const std::vector<std::pair<std::string, HostMat>> &mats);      /* sh_eng_sqnet.inc */
 extern "C" int scrappie_hip_load_model_mem(scrappie_hip_engine *e, const char *name, const void *blob, size_t nbytes) {
     const int idx = load_model_mem_one(e, name, blob, nbytes);
     if (idx < 0 || e->is_tail) return idx;
@@ -104,6 +105,14 @@ static int load_model_mem_one(scrappie_hip_engine *e, const char *name, const vo
             mtp = 3 * m->S / 16;
             if (upload(m->lp[l], make_bias_frags(*mpp, mtp))) { delete m; return -1; }
         }
+    } else if (m->arch == 4) {
+        /* the squiggle predictor (networks.c:397-565): no recurrent layers, no output layer; WL from the shapes */
+        if (sqnet_load(m, mats)) { delete m; return -1; }
+        std::lock_guard<std::mutex> lk(e->mu);
+        for (size_t i = 0; i < e->models.size(); i++)
+            if (e->models[i]->name == name) { delete e->models[i]; e->models[i] = m; return (int)i; }
+        e->models.push_back(m);
+        return (int)e->models.size() - 1;
     } else {
     if (!cw || !cb || !fw || !fb) { delete m; return set_err("model '%s': missing conv/ff matrices", name); }
     m->WL = cw->nr; m->F = cw->nc; m->NS = fw->nc; m->S = fw->nr;
@@ -243,6 +252,7 @@ extern "C" int scrappie_hip_find_model(scrappie_hip_engine *e, const char *name)
 
 static Model *get_model(scrappie_hip_engine *e, int model) {
     if (!e || model < 0 || (size_t)model >= e->models.size()) { set_err("invalid model handle %d", model); return nullptr; }
+    if (e->models[model]->arch == 4) { set_err("model '%s' predicts squiggles from sequences; it takes no signal", e->models[model]->name.c_str()); return nullptr; }
     return e->models[model];
 }
 

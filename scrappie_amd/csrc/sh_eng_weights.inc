@@ -36,6 +36,7 @@ struct Model {
     DBuf ff2W[2][2], ff2b[2];            /* raw_r94 / events: FF1/FF2 {Wf, Wb}, b (feedforward2_tanh) */
     DBuf lp[4];                          /* events: LSTM peepholes [update | forget | output] in accumulator layout */
     int nfeat = 0;                       /* events: input features per event (12), padded to F = 16 */
+    DBuf sqw;                            /* arch 4 (squiggle predictor): the weight table of k_sqnet (sh_sqnet.h); WL is its window, nothing else above is set */
     bool layer_f32[5] = {false, false, false, false, false};   /* GRU layer has a weight outside the split products' range: exact-fp32 kernels */
 };
 

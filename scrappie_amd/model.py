@@ -20,6 +20,13 @@ A model is a dict:
             i.e. one *column* of the reference's `_Mat`
   ff_W      (NS, S)   ff_b (NS,)    (transducer: stay state is the LAST row,
                                      misc/parse_rgrgr.py:127-130)
+
+A squiggle model (arch 'squiggle': sequence -> predicted squiggle, networks.c:397-565) holds instead
+  embed_W   (4, 3)            one row per base
+  conv1_W   (32, 3 WL)        conv1_b (32,)     column = tap * features + feature, unpadded
+  conv{2..5}_W (32, 32 WL)    conv{2..5}_b (32,)
+  conv6_W   (3, 32 WL)        conv6_b (3,)
+with conv_act 'tanh' and stride 1; WL is 9 (squiggle_r94, squiggle_r10) or 7 (squiggle_r94_rna).
 """
 import re
 import struct
@@ -27,7 +34,7 @@ import struct
 import numpy as np
 
 MAGIC = b"SCRMDL01"
-ARCH_ID = {"rgrgr": 0, "rnnrf": 1, "raw": 2, "events": 3}
+ARCH_ID = {"rgrgr": 0, "rnnrf": 1, "raw": 2, "events": 3, "squiggle": 4}
 ACT_ID = {"elu": 0, "tanh": 1}
 
 # name -> (arch, conv_act, winlen, nstate): shapes per SURVEY.md section 8
@@ -42,6 +49,10 @@ MODEL_SHAPES = {
     # events bi-LSTM (networks.c:146-193): no convolution, 12 input features per event
     # (3-event window x 4 features); LSTM size assumed (nanonet_events.h is not in the checkout)
     "nanonet_events": ("events", "tanh", 0, 1025),
+    # sequence -> squiggle (networks.c:397-565): window lengths of the shipped models; "nstate" is the 3 outputs
+    "squiggle_r94": ("squiggle", "tanh", 9, 3),
+    "squiggle_r94_rna": ("squiggle", "tanh", 7, 3),
+    "squiggle_r10": ("squiggle", "tanh", 9, 3),
 }
 
 MATRIX_NAMES = (["conv_W", "conv_b"]
@@ -60,11 +71,16 @@ RAW_MATRIX_NAMES = (["conv_W", "conv_b"]
 EVENTS_MATRIX_NAMES = (["lstm%d_%s" % (l, n) for l in range(4) for n in ("iW", "sW", "b", "p")]
                        + ["ff1_Wf", "ff1_Wb", "ff1_b", "ff2_Wf", "ff2_Wb", "ff2_b", "ff_W", "ff_b"])
 EVENT_FEATURES = 12
+# squiggle: embedding, conv1 (3 -> 32), conv2..5 (32 -> 32, residual), conv6 (32 -> 3)
+SQUIGGLE_MATRIX_NAMES = ["embed_W"] + ["conv%d_%s" % (l, n) for l in range(1, 7) for n in ("W", "b")]
+SQUIGGLE_EMBED, SQUIGGLE_FILTERS, SQUIGGLE_OUT = 3, 32, 3
 
 
 def matrix_names(m):
     if m["arch"] == "events":
         return EVENTS_MATRIX_NAMES
+    if m["arch"] == "squiggle":
+        return SQUIGGLE_MATRIX_NAMES
     return RAW_MATRIX_NAMES if m["arch"] == "raw" else MATRIX_NAMES
 
 
@@ -89,6 +105,17 @@ def synthetic_model(name="rgrgr_r94", seed=1, size=96, nfilter=None, winlen=None
     def b(n):
         return rng.uniform(-0.1, 0.1, size=n).astype(np.float32)
 
+    if arch == "squiggle":
+        # the embedding at the scale of the shipped one (entries of magnitude <= 1); the residual layers small enough that five of them
+        # keep the activations of order 1
+        m = {"name": name, "arch": arch, "conv_act": act, "stride": 1}
+        E, NF, NO = SQUIGGLE_EMBED, SQUIGGLE_FILTERS, SQUIGGLE_OUT
+        m["embed_W"] = rng.uniform(-1.0, 1.0, size=(4, E)).astype(np.float32)
+        for l in range(1, 7):
+            cin, cout = (E if l == 1 else NF), (NO if l == 6 else NF)
+            m["conv%d_W" % l] = u((cout, cin * winlen), cin * winlen)
+            m["conv%d_b" % l] = b(cout)
+        return m
     if arch == "events":
         m = {"name": name, "arch": arch, "conv_act": act, "stride": 1}
         for l in range(4):
@@ -162,7 +189,7 @@ def load_model(path):
     return m
 
 
-_ARRAY_RE = re.compile(r"float\s+__(\w+)\[\]\s*=\s*\{(.*?)\};", re.S)
+_ARRAY_RE = re.compile(r"float\s+__(\w+)\[\d*\]\s*=\s*\{(.*?)\};", re.S)
 _MAT_RE = re.compile(r"_Mat\s+_(\w+)\s*=\s*\{\s*\.nr\s*=\s*(\d+),\s*\.nrq\s*=\s*(\d+),"
                      r"\s*\.nc\s*=\s*(\d+),\s*\.stride\s*=\s*(\d+)", re.S)
 _STRIDE_RE = re.compile(r"const\s+int\s+conv_\w*stride\s*=\s*(\d+)")
@@ -203,7 +230,55 @@ def model_from_header(path, arch=None, conv_act="elu"):
     return m
 
 
+def squiggle_model_from_header(path):
+    """Parse a reference squiggle model header (embed_<tag>_W, conv{1..6}_<tag>_W/_b; networks.c:400-435) into a model dict.
+    There the embedding's 3 features are padded to 4, so conv1_W has nr = 4 WL - 1 rows in columns of stride 4 WL; the
+    other layers' 32 features need no padding."""
+    text = open(path).read()
+    arrays = {k: np.array([float.fromhex(t.strip()) for t in v.replace("\n", " ").split(",") if t.strip()],
+                          dtype=np.float32)
+              for k, v in _ARRAY_RE.findall(text)}
+    mats = {}
+    for nm, nr, nrq, nc, stride in _MAT_RE.findall(text):
+        nr, nc, stride = int(nr), int(nc), int(stride)
+        mats[nm] = arrays[nm][:nc * stride].reshape(nc, stride)[:, :nr]
+
+    def find(prefix, suffix):
+        ks = [k for k in mats if k.startswith(prefix) and k.endswith(suffix)]
+        if len(ks) != 1:
+            raise KeyError("header has no unique matrix %s*%s" % (prefix, suffix))
+        return mats[ks[0]]
+
+    E, NF, NO = SQUIGGLE_EMBED, SQUIGGLE_FILTERS, SQUIGGLE_OUT
+    m = {"arch": "squiggle", "conv_act": "tanh", "stride": 1}
+    em = find("embed_", "_W")
+    if em.shape != (4, E):
+        raise ValueError("%s: the embedding is %r, not 4 bases x %d features" % (path, em.shape, E))
+    m["embed_W"] = np.ascontiguousarray(em)
+    c1 = find("conv1_", "_W")                 # (32, 4 WL - 1): tap t at rows 4t .. 4t + 2
+    wl = (c1.shape[1] + 1) // 4
+    if c1.shape != (NF, 4 * wl - 1):
+        raise ValueError("%s: conv1_W is %r" % (path, c1.shape))
+    full = np.zeros((NF, 4 * wl), dtype=np.float32)
+    full[:, :4 * wl - 1] = c1
+    m["conv1_W"] = np.ascontiguousarray(full.reshape(NF, wl, 4)[:, :, :E].reshape(NF, wl * E))
+    m["conv1_b"] = find("conv1_", "_b")[0].copy()
+    for l in range(2, 7):
+        w = find("conv%d_" % l, "_W")
+        cout = NO if l == 6 else NF
+        if w.shape != (cout, NF * wl):
+            raise ValueError("%s: conv%d_W is %r, not (%d, %d)" % (path, l, w.shape, cout, NF * wl))
+        m["conv%d_W" % l] = w.copy()
+        m["conv%d_b" % l] = find("conv%d_" % l, "_b")[0].copy()
+    for st in re.findall(r"const\s+int\s+conv\d_\w*stride\s*=\s*(\d+)", text):
+        if int(st) != 1:
+            raise ValueError("%s: a convolution of stride %s" % (path, st))
+    return m
+
+
 def model_dims(m):
+    if m["arch"] == "squiggle":
+        return dict(F=SQUIGGLE_FILTERS, WL=m["conv2_W"].shape[1] // SQUIGGLE_FILTERS, S=0, NS=SQUIGGLE_OUT, stride=1)
     if m["arch"] == "events":
         return dict(F=EVENT_FEATURES, WL=0, S=m["lstm0_sW"].shape[1], NS=m["ff_W"].shape[0], stride=1)
     F, WL = m["conv_W"].shape
