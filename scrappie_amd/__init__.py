@@ -308,6 +308,22 @@ def _take_string(ptr):
     return s
 
 
+def _raw_tables(signals):
+    """The ctypes raw_table array of a batched call and what keeps its memory alive: each signal is a float32 array (its
+    whole length the window) or a `RawTable` with its window."""
+    keep = [x if isinstance(x, RawTable) else np.ascontiguousarray(x, dtype=ftype) for x in signals]
+    rts = (_RawTable * max(len(keep), 1))()
+    for i, x in enumerate(keep):
+        rts[i] = x.data() if isinstance(x, RawTable) else _RawTable(None, len(x), 0, len(x), x.ctypes.data_as(C.POINTER(C.c_float)))
+    return rts, keep
+
+
+def _scores_and_paths(out, n, length_attr):
+    """[(score, path or None)] of a batched mapping call's results; a path is `length_attr` ints long"""
+    return [(float(r.score), np.ctypeslib.as_array(r.path, shape=(getattr(r, length_attr),)).copy() if r.path else None)
+            for r in (out[i] for i in range(n))]
+
+
 # ---------------------------------------------------------------------------
 # scrappy-compatible objects (python/scrappy/__init__.py:47-273)
 # ---------------------------------------------------------------------------
@@ -1072,17 +1088,14 @@ class Engine(object):
             raise ValueError('Cannot calulate path with `viterbi==False`.')
         h = self._models[model]
         kmer_len = guess_state_properties(lib().scrappie_hip_model_states(self._h, h))[1]
-        keep = []
-        rts = (_RawTable * n)()
+        rts, keep = _raw_tables(signals)
         tgs = (_MapTarget * n)()
-        for i, (x, sq) in enumerate(zip(signals, sequences)):
-            x = np.ascontiguousarray(x, dtype=ftype)
+        for i, (x, sq) in enumerate(zip(keep[:n], sequences)):
             try:
                 codes = encode_bases(sq, kmer_len)
             except ValueError:
                 codes = np.zeros(0, dtype=np.int32)      # mapped to NaN by the library (empty sequence)
-            keep += [x, codes]
-            rts[i] = _RawTable(None, len(x), 0, len(x), x.ctypes.data_as(C.POINTER(C.c_float)))
+            keep.append(codes)
             tgs[i].seq = codes.ctypes.data_as(C.POINTER(C.c_int))
             tgs[i].seqlen = len(codes)
             b = bands if (bands is None or isinstance(bands, int)) else bands[i]
@@ -1099,19 +1112,18 @@ class Engine(object):
         out = (_MapResult * n)()
         if lib().scrappie_hip_map_batch(self._h, h, rts, tgs, n, C.byref(p), 1 if viterbi else 0, 1 if path else 0, out) != 0:
             raise RuntimeError("map_batch: " + last_error())
-        res = []
-        for i in range(n):
-            r = out[i]
-            pth = np.ctypeslib.as_array(r.path, shape=(r.nblock,)).copy() if r.path else None
-            res.append((float(r.score), pth))
+        res = _scores_and_paths(out, n, 'nblock')
         lib().scrappie_hip_free_map_results(out, n)
         return res
 
+    def _timing(self, fn, names):
+        t = (C.c_double * 3)()
+        fn(self._h, t)
+        return dict(zip(names, t))
+
     def map_timing(self):
         """the last map_to_sequence call's time (ms, summed over launch groups): network + S1, k_map, walk + results"""
-        t = (C.c_double * 3)()
-        lib().scrappie_hip_map_timing(self._h, t)
-        return dict(network_ms=t[0], map_ms=t[1], walk_ms=t[2])
+        return self._timing(lib().scrappie_hip_map_timing, ('network_ms', 'map_ms', 'walk_ms'))
 
     def match_squiggle(self, signals, squiggles, viterbi=True, path=False, rate=1.0, back_prob=0.0, local_pen=2.0,
                        skip_pen=5000.0, min_score=5.0):
@@ -1123,17 +1135,9 @@ class Engine(object):
             raise ValueError("one squiggle per signal")
         if path and not viterbi:
             raise ValueError('Cannot calulate path with `viterbi==False`.')
-        keep = []
-        rts = (_RawTable * n)()
+        rts, keep = _raw_tables(signals)
         tgs = (_SquigTarget * n)()
-        for i, (x, sq) in enumerate(zip(signals, squiggles)):
-            if isinstance(x, RawTable):
-                keep.append(x)
-                rts[i] = x.data()
-            else:
-                x = np.ascontiguousarray(x, dtype=ftype)
-                keep.append(x)
-                rts[i] = _RawTable(None, len(x), 0, len(x), x.ctypes.data_as(C.POINTER(C.c_float)))
+        for i, sq in enumerate(squiggles):
             if isinstance(sq, str):
                 _squiggle_matrix(sq)
             sq = np.ascontiguousarray(sq, dtype=ftype)
@@ -1145,11 +1149,7 @@ class Engine(object):
         out = (_SquigResult * n)()
         if lib().scrappie_hip_squiggle_match_batch(self._h, rts, tgs, n, C.byref(p), 1 if viterbi else 0, 1 if path else 0, out) != 0:
             raise RuntimeError("squiggle_match_batch: " + last_error())
-        res = []
-        for i in range(n):
-            r = out[i]
-            pth = np.ctypeslib.as_array(r.path, shape=(r.n,)).copy() if r.path else None
-            res.append((float(r.score), pth))
+        res = _scores_and_paths(out, n, 'n')
         lib().scrappie_hip_free_squiggle_results(out, n)
         return res
 
@@ -1173,9 +1173,7 @@ class Engine(object):
 
     def sqnet_timing(self):
         """the last predict_squiggle call's time (ms, summed over launches): upload, k_sqnet, download + transform"""
-        t = (C.c_double * 3)()
-        lib().scrappie_hip_sqnet_timing(self._h, t)
-        return dict(upload_ms=t[0], net_ms=t[1], download_ms=t[2])
+        return self._timing(lib().scrappie_hip_sqnet_timing, ('upload_ms', 'net_ms', 'download_ms'))
 
     def mappy(self, signals, sequences, model='squiggle_r94', rate=1.0, back_prob=0.0, local_pen=2.0, skip_pen=5000.0,
               min_score=5.0):
@@ -1195,9 +1193,7 @@ class Engine(object):
 
     def squiggle_timing(self):
         """the last match_squiggle call's time (ms, summed over launches): tables + uploads, k_squig, walk + results"""
-        t = (C.c_double * 3)()
-        lib().scrappie_hip_squiggle_timing(self._h, t)
-        return dict(tables_ms=t[0], match_ms=t[1], walk_ms=t[2])
+        return self._timing(lib().scrappie_hip_squiggle_timing, ('tables_ms', 'match_ms', 'walk_ms'))
 
     def trunk(self, signal, model='rgrgr_r94', upto=5):
         rt = RawTable(signal)

@@ -34,6 +34,8 @@
  *   sh_eng_batch.inc     helper engine for chain-bound reads, host-signal entry points, several GPUs
  *   sh_eng_debug.inc     measurement / test hooks
  *   sh_eng_surface.inc   the reference's per-read functions: one batch function per family, run by the queue or with a batch of one
+ *   sh_eng_cut.inc       what the three engines below share: a call cut into launches that fit the device (LaunchCut), per-read DP
+ *                        records through a kernel with two homes (dp_order / dp_launch / dp_collect)
  *   sh_eng_map.inc       block-based mapping of posteriors to sequences (per-read and batched)
  *   sh_eng_squig.inc     mapping of raw signals to predicted squiggles (per-read and batched)
  *   sh_eng_sqnet.inc     prediction of squiggles from base sequences (per-read and batched)
@@ -58,6 +60,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <deque>
+#include <functional>
 #include <map>
 #include <memory>
 
@@ -186,6 +189,7 @@ struct LaunchGroup {
     long long nhp = 0;            /* total blocks of real reads (hp side rows) */
     std::vector<int> order;       /* tiled index -> original read index (or -1) */
     std::vector<int> rT, rN;
+    std::vector<long long> tile_boff;     /* per tile: its first column block */
     std::vector<long long> seq_off, hp_off, bases_off;
     long long nbases_cap = 0;     /* bytes of the per-slot bases buffer (k_stitch) */
     bool dev_stitch = false;      /* bases were made on the device (k_stitch); else paths (+ side rows) come to the host */
@@ -224,6 +228,19 @@ struct BatchCoalescer : ShCoalescer<BatchReq> { BatchCoalescer() { target_pct = 
 /* the posteriors of a launch of the per-read functions in pinned memory: every caller copies its own matrix out after the engine's lock is released
  * (all at once) and counts itself off `users`; the buffer is written again only when nobody is left (sh_eng_surface.inc) */
 struct PostStage { HBuf h; DBuf d; std::atomic<int> users{0}; };
+
+/* The device side of per-read DP records run through a kernel with two homes (k_map, k_squig: score rows in LDS or in device scratch; dp_launch and
+ * dp_collect, sh_eng_cut.inc): the records in device order, traceback, scratch rows, score and final state per record, and for the walk back the
+ * records' path offsets and the paths.  h (pinned) brings scores | paths back; a family may stage its uploads in it first.  Grow-only. */
+struct DpBufs {
+    DBuf rd, tb, scr, score, final_state, path_off, paths;
+    HBuf h;
+    int ensure(size_t n, size_t rec_bytes, long long tb_words, long long scr_floats, long long path_len, size_t h_bytes = 0) {
+        return (rd.ensure(n * rec_bytes) || tb.ensure((size_t)tb_words * 4 + 16) || scr.ensure((size_t)scr_floats * 4 + 16) || score.ensure(n * 4) ||
+                final_state.ensure(n * 4) || path_off.ensure(n * 8) || paths.ensure((size_t)path_len * 4 + 16) ||
+                h.ensure(std::max(h_bytes, n * 4 + (size_t)path_len * 4))) ? -1 : 0;
+    }
+};
 
 /* fields of scrappie_hip_timing (and two figures of SH_HOST_STAMP) that a span between two profiling marks adds to: resolve_spans (sh_eng_load.inc) */
 enum SpanField { F_CONV = 0, F_AFFINE, F_GRU, F_FF, F_DECODE, F_BACKTRACE, F_TOTAL, F_FUSED, F_STITCH,
@@ -381,9 +398,9 @@ struct scrappie_hip_engine {
     PostStage post_stage[2]; unsigned post_turn = 0;     /* posterior_batch: two in turn, so that a batch seldom waits for the last one's callers */
     HBuf h_dec_in, h_dec_out; DBuf d_dec[7];             /* decode_batch: posteriors in (a lone call; the queue's members fill the queue's own), paths + scores out */
     HBuf h_crf_in, h_crf_out; DBuf d_crf[4];             /* crf_batch */
-    DBuf d_map[10]; HBuf h_map;      /* block-based mapping (sh_eng_map.inc): per-read tables, codes, bands, traceback, scratch, scores, paths, posterior */
+    DpBufs dp_map; DBuf d_map_seq, d_map_band, d_map_post;       /* block-based mapping (sh_eng_map.inc): the records' buffers; codes, bands, a per-read call's dense posterior */
     double map_ms[3] = {0, 0, 0};    /* scrappie_hip_map_batch: network + S1, k_map, k_map_walk + results, summed over the last call's launch groups */
-    DBuf d_sq[9]; HBuf h_sq;         /* squiggle matching (sh_eng_squig.inc): records, signals, tables, traceback, scratch, scores, final states, path offsets, paths */
+    DpBufs dp_sq; DBuf d_sq_sig, d_sq_tab;       /* squiggle matching (sh_eng_squig.inc): the records' buffers; signals, tables */
     double squig_ms[3] = {0, 0, 0};  /* scrappie_hip_squiggle_match_batch: tables + uploads, k_squig, k_squig_walk + results, summed over the last call's launches */
     DBuf d_sqn[2]; HBuf h_sqn;       /* squiggle prediction (sh_eng_sqnet.inc): tiles | codes, outputs */
     double sqnet_ms[3] = {0, 0, 0};  /* scrappie_hip_squiggle_predict_batch: upload, k_sqnet, download + transform, summed over the last call's launches */
@@ -520,6 +537,7 @@ extern "C" scrappie_hip_params scrappie_hip_default_params(void) {
 #include "sh_eng_batch.inc"      /* chain-bound reads on a helper engine, host-signal entry points, several GPUs */
 #include "sh_eng_debug.inc"      /* measurement / test hooks: decoder and trunk inputs, debug_option / debug_fetch / debug_stitch */
 #include "sh_eng_surface.inc"      /* the reference's per-read functions: posterior / trunk on an explicit engine, the process-default engine, decode_transducer, decode_crf; all three coalesced (sh_coalesce.h) */
+#include "sh_eng_cut.inc"      /* shared by the three below: LaunchCut (a call cut into launches), dp_order / dp_launch / dp_collect (a kernel with two homes) */
 #include "sh_eng_map.inc"      /* block-based mapping (sh_map.h): map_to_sequence_* on the process-default engine, scrappie_hip_map_batch */
 #include "sh_eng_squig.inc"      /* squiggle matching (sh_squig.h): squiggle_match_* on the process-default engine, scrappie_hip_squiggle_match_batch */
 #include "sh_eng_sqnet.inc"      /* squiggle prediction (sh_sqnet.h): squiggle_r94 and its relatives on the process-default engine, scrappie_hip_squiggle_predict_batch */

@@ -56,7 +56,6 @@ extern "C" long long scrappie_hip_debug_fetch(scrappie_hip_engine *e, const char
     if (!m) return -1;
     const size_t NH = (size_t)std::max(m->NS - 1, 0);
     const void *src = nullptr; size_t have = 0; bool host = false;
-    std::vector<long long> tb;
     const int gru_tiles = lg.gru_two ? 2 : 1;
     if (!strcmp(what, "tb")) { src = e->d_tb.p; have = (size_t)lg.ncb * NH * 16; }
     else if (!strcmp(what, "tb_end")) { src = e->d_tbend.p; have = (size_t)lg.ncb * 16 * 4; }
@@ -64,11 +63,8 @@ extern "C" long long scrappie_hip_debug_fetch(scrappie_hip_engine *e, const char
     else if (!strcmp(what, "final_score")) { src = sl.d_fscore.p; have = lg.npad * 4; }
     else if (!strcmp(what, "final_scores")) { src = e->d_vstate.p; have = lg.ntile * (NH * 16 + 32) * 4; }
     else if (!strcmp(what, "order")) { src = lg.order.data(); have = lg.npad * 4; host = true; }
-    else if (!strcmp(what, "tile_boff")) {
-        long long ncb = 0;
-        for (size_t t = 0; t < lg.ntile; t++) { tb.push_back(ncb); int mx = 0; for (int k = 0; k < 16; k++) mx = std::max(mx, lg.rT[t * 16 + k]); ncb += mx; }
-        src = tb.data(); have = tb.size() * 8; host = true;
-    } else if (!strcmp(what, "n_redo")) { static thread_local unsigned long long tot; tot = e->n_redo + e->n_redo_tail; src = &tot; have = 8; host = true; }
+    else if (!strcmp(what, "tile_boff")) { src = lg.tile_boff.data(); have = lg.ntile * 8; host = true; }
+    else if (!strcmp(what, "n_redo")) { static thread_local unsigned long long tot; tot = e->n_redo + e->n_redo_tail; src = &tot; have = 8; host = true; }
     else if (!strcmp(what, "n_tail_groups")) { src = &e->n_tail_groups; have = 8; host = true; }
     else if (!strcmp(what, "n_tail_calls")) { src = &e->n_tail_calls; have = 8; host = true; }
     else if (!strcmp(what, "n_tail_reads")) { src = &e->n_tail_reads; have = 8; host = true; }

@@ -28,7 +28,8 @@ static int build_group(scrappie_hip_engine *e, Slot &sl, Model *m, const uint64_
     const long long per_entry = (m->arch == 1) ? 1 : 5;
     std::vector<unsigned long long> sig_off(lg.npad, 0);
     std::vector<int> tile_T(lg.ntile, 0);
-    std::vector<long long> tile_boff(lg.ntile, 0);
+    std::vector<long long> &tile_boff = lg.tile_boff;
+    tile_boff.assign(lg.ntile, 0);
     long long ncb = 0, nseq = 0, nhp = 0;
     for (size_t i = 0; i < lg.npad; i++) {
         const int o = lg.order[i];

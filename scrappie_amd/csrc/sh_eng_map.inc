@@ -1,7 +1,9 @@
 /* sh_eng_map.inc -- part of scrappie_hip.hip (one translation unit, included from there in this order; not compiled alone):
  * block-based mapping of transducer posteriors to sequences (sh_map.h).  The reference's map_to_sequence_* on the
  * process-default engine (the caller's host posterior uploaded, one launch), and scrappie_hip_map_batch: the network and S1
- * of a launch group (run_pipeline to STOP_POST), k_map on the posterior where S1 left it, k_map_walk; scores and paths back. */
+ * of a launch group (run_staged to STOP_POST), k_map on the posterior where S1 left it, k_map_walk; scores and paths back.
+ * What is here is the family's own: the plan of a launch, the checks a target passes, the cost of a launch group, map_group.
+ * The cutting of a call into launch groups and the run of the records through k_map's two homes are sh_eng_cut.inc's. */
 
 /* host side of one k_map launch: the reads' tables, their codes and bands laid end to end, traceback / scratch offsets */
 struct MapPlan {
@@ -72,15 +74,8 @@ static std::atomic<uint64_t> g_map_forms[16];
 
 template <bool VIT, bool BAND, bool TILED>
 static void map_launch_k(hipStream_t s, const ShMapArgs &a, size_t n_lds, size_t n, size_t lds) {
-    const int form = (VIT ? 8 : 0) | (BAND ? 4 : 0) | (TILED ? 2 : 0);
-    if (n_lds) g_map_forms[form].fetch_add(1, std::memory_order_relaxed);
-    if (n > n_lds) g_map_forms[form | 1].fetch_add(1, std::memory_order_relaxed);
-    if (n_lds) hipLaunchKernelGGL((k_map<VIT, BAND, TILED, true>), dim3((unsigned)n_lds), dim3(SH_MAP_NTH), lds, s, a);
-    if (n > n_lds) {                     /* the reads whose rows live in scratch: the tables' tail */
-        ShMapArgs b = a;
-        b.rd += n_lds; b.score += n_lds; b.final_state += n_lds;
-        hipLaunchKernelGGL((k_map<VIT, BAND, TILED, false>), dim3((unsigned)(n - n_lds)), dim3(SH_MAP_NTH), 0, s, b);
-    }
+    dp_launch<k_map<VIT, BAND, TILED, true>, k_map<VIT, BAND, TILED, false>>(s, a, n_lds, n, SH_MAP_NTH, lds, 0,
+                                                                             g_map_forms + ((VIT ? 8 : 0) | (BAND ? 4 : 0) | (TILED ? 2 : 0)));
 }
 
 /* one plan (all banded or all unbanded) through k_map (+ k_map_walk): scores into score[], paths into paths[i] (malloc'd,
@@ -89,27 +84,21 @@ static int map_run(scrappie_hip_engine *e, MapPlan &pl, ShMapArgs a, bool vit, b
     const size_t n = pl.rd.size();
     if (n == 0) return 0;
     hipStream_t s = e->stream;
-    DBuf *d = e->d_map;          /* 0 reads, 1 codes, 2 bands, 3 traceback, 4 scratch, 5 scores, 6 final states, 7 path offsets, 8 paths */
+    DpBufs &d = e->dp_map;
     const bool walk = vit && !band && pl.path_len > 0;
-    /* device order: the reads whose rows fit LDS first (one launch), then those in scratch (another) */
-    std::vector<size_t> perm(n);
-    std::iota(perm.begin(), perm.end(), (size_t)0);
-    std::stable_partition(perm.begin(), perm.end(), [&](size_t i) { return pl.rd[i].scr < 0; });
-    size_t n_lds = 0;
-    while (n_lds < n && pl.rd[perm[n_lds]].scr < 0) n_lds++;
+    std::vector<size_t> perm;
+    const size_t n_lds = dp_order(pl.rd, perm);
     std::vector<ShMapRead> rd(n);
     std::vector<long long> poff(n);
     for (size_t k = 0; k < n; k++) { rd[k] = pl.rd[perm[k]]; poff[k] = pl.path_off[perm[k]]; }
-    if (d[0].ensure(n * sizeof(ShMapRead)) || d[1].ensure(pl.seq.size() * 4 + 16) || d[2].ensure(pl.band.size() * 4 + 16) ||
-        d[3].ensure((size_t)pl.tb_words * 4 + 16) || d[4].ensure((size_t)pl.scr_floats * 4 + 16) || d[5].ensure(n * 4) ||
-        d[6].ensure(n * 4) || d[7].ensure(n * 8) || d[8].ensure((size_t)pl.path_len * 4 + 16) ||
-        e->h_map.ensure(n * 4 + (size_t)pl.path_len * 4)) return -1;
-    HIPCHK(hipMemcpyAsync(d[0].p, rd.data(), n * sizeof(ShMapRead), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d[1].p, pl.seq.data(), pl.seq.size() * 4, hipMemcpyHostToDevice, s));
-    if (!pl.band.empty()) HIPCHK(hipMemcpyAsync(d[2].p, pl.band.data(), pl.band.size() * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d[7].p, poff.data(), n * 8, hipMemcpyHostToDevice, s));
-    a.rd = d[0].as<ShMapRead>(); a.seq = d[1].as<int>(); a.band = d[2].as<int>(); a.tb = d[3].as<unsigned>(); a.scr = d[4].as<float>();
-    a.score = d[5].as<float>(); a.final_state = d[6].as<int>();
+    if (d.ensure(n, sizeof(ShMapRead), pl.tb_words, pl.scr_floats, pl.path_len) || e->d_map_seq.ensure(pl.seq.size() * 4 + 16) ||
+        e->d_map_band.ensure(pl.band.size() * 4 + 16)) return -1;
+    HIPCHK(hipMemcpyAsync(d.rd.p, rd.data(), n * sizeof(ShMapRead), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(e->d_map_seq.p, pl.seq.data(), pl.seq.size() * 4, hipMemcpyHostToDevice, s));
+    if (!pl.band.empty()) HIPCHK(hipMemcpyAsync(e->d_map_band.p, pl.band.data(), pl.band.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d.path_off.p, poff.data(), n * 8, hipMemcpyHostToDevice, s));
+    a.rd = d.rd.as<ShMapRead>(); a.seq = e->d_map_seq.as<int>(); a.band = e->d_map_band.as<int>(); a.tb = d.tb.as<unsigned>(); a.scr = d.scr.as<float>();
+    a.score = d.score.as<float>(); a.final_state = d.final_state.as<int>();
     const auto t0 = std::chrono::steady_clock::now();
     const int k = (vit ? 4 : 0) | (band ? 2 : 0) | (tiled ? 1 : 0);
     switch (k) {
@@ -125,27 +114,17 @@ static int map_run(scrappie_hip_engine *e, MapPlan &pl, ShMapArgs a, bool vit, b
     HIPCHK(hipGetLastError());
     HIPCHK(sh_stream_wait(s));
     const auto t1 = std::chrono::steady_clock::now();
-    if (walk) {
-        hipLaunchKernelGGL(k_map_walk, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, (const ShMapRead *)d[0].p, (int)n, (const unsigned *)d[3].p,
-                           (const int *)d[6].p, (const long long *)d[7].p, d[8].as<int>());
-        HIPCHK(hipGetLastError());
-    }
-    float *hs = e->h_map.as<float>();
-    int32_t *hp = (int32_t *)(hs + n);
-    HIPCHK(hipMemcpyAsync(hs, d[5].p, n * 4, hipMemcpyDeviceToHost, s));
-    if (walk) HIPCHK(hipMemcpyAsync(hp, d[8].p, (size_t)pl.path_len * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(sh_stream_wait(s));
-    for (size_t k = 0; k < n; k++) {
-        const size_t i = perm[k];
-        score[i] = hs[k];
-        if (!paths) continue;
-        paths[i] = nullptr;
-        if (!walk || pl.path_off[i] < 0) continue;
-        const size_t nb = (size_t)pl.rd[i].nblock;
-        paths[i] = (int32_t *)malloc(nb * 4);
-        if (!paths[i]) return set_err("out of host memory");
-        memcpy(paths[i], hp + pl.path_off[i], nb * 4);
-    }
+    if (dp_collect<k_map_walk, ShMapRead>(s, d, perm, pl.path_off, pl.path_len, walk, [&](size_t i, float sc, const int32_t *p) {
+            score[i] = sc;
+            if (!paths) return 0;
+            paths[i] = nullptr;
+            if (!p) return 0;
+            const size_t nb = (size_t)pl.rd[i].nblock;
+            paths[i] = (int32_t *)malloc(nb * 4);
+            if (!paths[i]) return set_err("out of host memory");
+            memcpy(paths[i], p, nb * 4);
+            return 0;
+        })) return -1;
     if (t) {
         t[0] += std::chrono::duration<double, std::milli>(t1 - t0).count();
         t[1] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
@@ -185,7 +164,7 @@ static float map_one(const char *fn, const_scrappie_matrix lp, float stay_pen, f
     MapPlan pl;
     const bool want_path = vit && !band && path;
     plan_add(pl, 0, 0, lp->nc, seq, L, band ? lo : nullptr, band ? hi : nullptr, want_path);
-    DBuf &dpost = e->d_map[9];
+    DBuf &dpost = e->d_map_post;
     const size_t pbytes = lp->nc * lp->stride * 4;
     if (dpost.ensure(pbytes)) return NAN;
     if (hipMemcpyAsync(dpost.p, lp->data.f, pbytes, hipMemcpyHostToDevice, e->stream) != hipSuccess) { set_err("%s: upload failed", fn); return NAN; }
@@ -243,44 +222,22 @@ extern "C" int scrappie_hip_model_states(scrappie_hip_engine *e, int model) {
     return m ? m->NS : -1;
 }
 
-extern "C" void scrappie_hip_map_timing(scrappie_hip_engine *e, double out[3]) {
-    for (int k = 0; k < 3; k++) out[k] = e ? e->map_ms[k] : 0.0;
-}
+extern "C" void scrappie_hip_map_timing(scrappie_hip_engine *e, double out[3]) { timing3(e ? e->map_ms : nullptr, out); }
+extern "C" void scrappie_hip_free_map_results(scrappie_hip_map_result *r, size_t n) { free_paths(r, n); }
 
-extern "C" void scrappie_hip_free_map_results(scrappie_hip_map_result *r, size_t n) {
-    if (!r) return;
-    for (size_t i = 0; i < n; i++) { free(r[i].path); r[i].path = nullptr; }
-}
+/* what a launch group holds so far, as its cost counts it */
+struct MapLoad { size_t sumT = 0, maxT = 0, extra = 0; };
 
 /* one launch group: reads idx[0..cnt) of the call */
 static int map_group(scrappie_hip_engine *e, Model *m, const raw_table *reads, const scrappie_hip_map_target *tg, const std::vector<size_t> &idx,
-                     const scrappie_hip_params *p, bool vit, bool want_path, scrappie_hip_map_result *out, std::vector<std::string> &why) {
+                     const scrappie_hip_params *p, bool vit, bool want_path, scrappie_hip_map_result *out, LaunchCut<MapLoad> &cut) {
     std::lock_guard<std::mutex> lk(e->mu);
-    const size_t cnt = idx.size();
-    std::vector<uint64_t> off(cnt);
-    std::vector<uint32_t> len(cnt);
-    size_t total = 0;
-    for (size_t k = 0; k < cnt; k++) {
-        const raw_table &rt = reads[idx[k]];
-        off[k] = total; len[k] = (uint32_t)map_read_nsample(m, rt);
-        total += rt.end - rt.start;
-    }
-    Slot &st = e->slots[0];                /* staged in the first slot's buffers (nothing else is in flight under mu) */
-    if (st.h_sig.ensure(total * 4) || st.d_signal.ensure(total * 4)) return -1;
-    float *hs = st.h_sig.as<float>();
-    for (size_t k = 0; k < cnt; k++) { const raw_table &rt = reads[idx[k]]; memcpy(hs + off[k], rt.raw + rt.start, (rt.end - rt.start) * 4); }
-    const auto t0 = std::chrono::steady_clock::now();
-    HIPCHK(hipMemcpyAsync(st.d_signal.p, hs, total * 4, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(sh_stream_wait(e->stream));        /* (the group's prologue runs on another stream: the signals must be there first) */
+    std::vector<const raw_table *> win;
+    for (size_t r : idx) win.push_back(&reads[r]);
     RunOut ro;
-    if (run_pipeline(e, m, st.d_signal.as<float>(), off.data(), len.data(), cnt, p, STOP_POST, 5, &ro)) return -1;
-    const Slot &sl = e->current(); const LaunchGroup &lg = sl.lg;
-    std::vector<unsigned> bad(lg.npad, 0);
-    HIPCHK(hipMemcpyAsync(bad.data(), sl.d_bad.p, lg.npad * 4, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(sh_stream_wait(e->stream));
-    e->map_ms[0] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    std::vector<long long> tile_boff(lg.ntile, 0);
-    { long long ncb = 0; for (size_t t = 0; t < lg.ntile; t++) { int tt = 0; for (int b = 0; b < 16; b++) tt = std::max(tt, lg.rT[t * 16 + b]); tile_boff[t] = ncb; ncb += tt; } }
+    std::vector<unsigned> bad;
+    if (run_staged(e, m, win, p, STOP_POST, 5, &ro, bad, e->map_ms)) return -1;
+    const LaunchGroup &lg = e->current().lg;
     MapPlan plan[2];                       /* unbanded, banded */
     std::vector<size_t> who[2];
     for (size_t i = 0; i < lg.npad; i++) {
@@ -288,12 +245,12 @@ static int map_group(scrappie_hip_engine *e, Model *m, const raw_table *reads, c
         if (o < 0 || lg.rT[i] <= 0) continue;
         const size_t r = idx[(size_t)o];
         if (bad[i]) {
-            why[r] = "the read holds values outside the supported range (is the signal trimmed and med/MAD-normalised?)";
+            cut.refuse(r, "the read holds values outside the supported range (is the signal trimmed and med/MAD-normalised?)");
             continue;
         }
         const scrappie_hip_map_target &t = tg[r];
         const bool band = t.poslow != nullptr;
-        plan_add(plan[band], tile_boff[i >> 4], (int)(i & 15), (size_t)lg.rT[i], t.seq, t.seqlen, t.poslow, t.poshigh, want_path && vit && !band);
+        plan_add(plan[band], lg.tile_boff[i >> 4], (int)(i & 15), (size_t)lg.rT[i], t.seq, t.seqlen, t.poslow, t.poshigh, want_path && vit && !band);
         who[band].push_back(r);
     }
     ShMapArgs a{};
@@ -333,43 +290,28 @@ extern "C" int scrappie_hip_map_batch(scrappie_hip_engine *e, int model, const r
     for (double &x : e->map_ms) x = 0.0;
     for (size_t i = 0; i < n; i++) { out[i].score = NAN; out[i].nblock = 0; out[i].path = nullptr; }
     const bool vit = viterbi != 0, wp = want_path != 0;
-    std::vector<std::string> why(n);
-    /* launch groups in input order, bounded by reads and by device memory: the materialised posterior and the arena of the network
+    /* launch groups in input order (LaunchCut), bounded by reads and by device memory: the materialised posterior and the arena of the network
      * (bytes_per_block with the posterior: ~66 KB per column block of 16 reads for 4^5 + 1 states), plus each read's traceback */
     const size_t bpb = bytes_per_block(m, true);
     const size_t budget = e->max_launch_blocks ? e->max_launch_blocks * bpb : (size_t)(e->mem_frac * (double)e->total_mem);
-    std::vector<size_t> grp;
-    size_t sumT = 0, maxT = 0, extra = 0;
-    int rc = 0;
-    auto flush = [&]() {
-        if (grp.empty() || rc) return;
-        if (map_group(e, m, reads, targets, grp, p, vit, wp, out, why)) {
-            rc = -1;
-            const std::string keep = g_err;
-            (void)hipGetLastError();
-            (void)sh_stream_wait(e->pstream); (void)sh_stream_wait(e->stream); (void)sh_stream_wait(e->cstream);
-            set_err("%s", keep.c_str());
-        }
-        grp.clear(); sumT = maxT = extra = 0;
-    };
-    for (size_t i = 0; i < n && !rc; i++) {
+    auto cost = [&](size_t sT, size_t mT, size_t ex) { return (sT / 16 + mT + 1) * bpb + ex; };
+    LaunchCut<MapLoad> cut{e, "map_batch"};
+    cut.run = [&](const std::vector<size_t> &grp, MapLoad &) { return map_group(e, m, reads, targets, grp, p, vit, wp, out, cut); };
+    for (size_t i = 0; i < n && !cut.failed; i++) {
         const scrappie_hip_map_target &t = targets[i];
         const size_t T = map_blocks(m, map_read_nsample(m, reads[i]));
-        if (T == 0) { why[i] = "read too short for the model (or empty)"; continue; }
+        if (T == 0) { cut.refuse(i, "read too short for the model (or empty)"); continue; }
         const bool band = t.poslow != nullptr || t.poshigh != nullptr;
         if (!t.seq || map_target_ok("map_batch", (size_t)m->NS, T, t.seq, t.seqlen, t.poslow, t.poshigh, band) || (band && !t.poslow)) {
-            why[i] = t.seq ? g_err : "no sequence";
+            cut.refuse(i, t.seq ? g_err : "no sequence");
             continue;
         }
         const size_t rb = map_read_bytes(t.seqlen, T, band, vit && wp && !band);
-        auto cost = [&](size_t sT, size_t mT, size_t ex) { return (sT / 16 + mT + 1) * bpb + ex; };
-        if (cost(T, T, rb) > budget) { why[i] = "read and sequence too long for one launch group on this device"; continue; }
-        if (!grp.empty() && (grp.size() >= e->max_launch_reads || cost(sumT + T, std::max(maxT, T), extra + rb) > budget)) flush();
-        grp.push_back(i); sumT += T; maxT = std::max(maxT, T); extra += rb;
+        if (cost(T, T, rb) > budget) { cut.refuse(i, "read and sequence too long for one launch group on this device"); continue; }
+        MapLoad &g = cut.load;
+        cut.add(i, cut.who.size() < e->max_launch_reads && cost(g.sumT + T, std::max(g.maxT, T), g.extra + rb) <= budget);
+        g.sumT += T; g.maxT = std::max(g.maxT, T); g.extra += rb;
     }
-    flush();
-    if (rc) { scrappie_hip_free_map_results(out, n); for (size_t i = 0; i < n; i++) { out[i].score = NAN; out[i].nblock = 0; } return -1; }
-    for (size_t i = 0; i < n; i++)
-        if (!why[i].empty()) { set_err("map_batch: read %zu: %s", i, why[i].c_str()); break; }
-    return 0;
+    return cut.finish([&] { scrappie_hip_free_map_results(out, n); for (size_t i = 0; i < n; i++) { out[i].score = NAN; out[i].nblock = 0; } },
+                      [](size_t i, const char *why) { set_err("map_batch: read %zu: %s", i, why); });
 }

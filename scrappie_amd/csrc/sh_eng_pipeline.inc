@@ -515,3 +515,34 @@ static int run_pipeline(scrappie_hip_engine *e, Model *m, const float *d_signal,
     mark_pending(e, sl);
     return 0;
 }
+
+/* A launch group from host signals, for the callers that want something other than base calls (posterior_batch, map_group; under mu): the reads' windows
+ * laid end to end into the first slot's h_sig / d_signal (nothing else is in flight under mu), uploaded and waited for (the group's prologue runs on
+ * another stream: the signals must be there before it is enqueued), run_pipeline to `stop`, and the group's range flags back in bad[npad] (tiled order,
+ * as e->current().lg).  The reads are long enough for the model.  ms: += the time from the upload to the flags' arrival. */
+static int run_staged(scrappie_hip_engine *e, Model *m, const std::vector<const raw_table *> &win, const scrappie_hip_params *p, StopAt stop,
+                      int trunk_upto, RunOut *ro, std::vector<unsigned> &bad, double *ms = nullptr) {
+    const size_t cnt = win.size();
+    std::vector<uint64_t> off(cnt);
+    std::vector<uint32_t> len(cnt);
+    size_t total = 0;
+    for (size_t k = 0; k < cnt; k++) {
+        const size_t nf = win[k]->end - win[k]->start;
+        off[k] = total; len[k] = (uint32_t)(m->arch == 3 ? nf / (size_t)m->nfeat : nf);      /* events: raw holds [nevent][12] features */
+        total += nf;
+    }
+    Slot &st = e->slots[0];
+    if (st.h_sig.ensure(total * 4) || st.d_signal.ensure(total * 4)) return -1;
+    float *hs = st.h_sig.as<float>();
+    for (size_t k = 0; k < cnt; k++) memcpy(hs + off[k], win[k]->raw + win[k]->start, (win[k]->end - win[k]->start) * 4);
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(hipMemcpyAsync(st.d_signal.p, hs, total * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(sh_stream_wait(e->stream));
+    if (run_pipeline(e, m, st.d_signal.as<float>(), off.data(), len.data(), cnt, p, stop, trunk_upto, ro)) return -1;
+    const Slot &sl = e->current();
+    bad.assign(sl.lg.npad, 0);
+    HIPCHK(hipMemcpyAsync(bad.data(), sl.d_bad.p, sl.lg.npad * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(sh_stream_wait(e->stream));
+    if (ms) *ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return 0;
+}

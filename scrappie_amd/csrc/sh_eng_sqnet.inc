@@ -1,6 +1,7 @@
 /* sh_eng_sqnet.inc -- part of scrappie_hip.hip (one translation unit, included from there in this order; not compiled alone):
  * prediction of squiggles from base sequences (sh_sqnet.h).  scrappie_hip_squiggle_predict_batch lays the accepted sequences of a
- * call end to end and cuts them into launches that fit a share of the free device memory; a launch is one upload (tiles + codes)
+ * call end to end and cuts them into launches that fit a share of the free device memory (LaunchCut, sh_eng_cut.inc: here are only the checks a
+ * sequence passes, what it costs and how a launch is run); a launch is one upload (tiles + codes)
  * -> k_sqnet over all tiles -> one download (3 floats per position) -> transform_units on the host (libm expf, the reference's
  * expressions).  The reference's squiggle_r94 / squiggle_r94_rna / squiggle_r10 are a batch of one on the process-default engine,
  * their model found by name (scrappie_hip_register_model / SCRAPPIE_MODEL_DIR: weights are data here). */
@@ -48,9 +49,7 @@ extern "C" size_t scrappie_hip_sqnet_tile(void) { return SH_SQN_TP; }
 static std::atomic<uint64_t> g_sqnet_launches;
 extern "C" uint64_t scrappie_hip_sqnet_launch_count(void) { return g_sqnet_launches.load(std::memory_order_relaxed); }
 
-extern "C" void scrappie_hip_sqnet_timing(scrappie_hip_engine *e, double out[3]) {
-    for (int k = 0; k < 3; k++) out[k] = e ? e->sqnet_ms[k] : 0.0;
-}
+extern "C" void scrappie_hip_sqnet_timing(scrappie_hip_engine *e, double out[3]) { timing3(e ? e->sqnet_ms : nullptr, out); }
 
 /* the reference's undefined calls (layers.c:190-241: below WL - 1 columns the edge products of `convolution` read outside X; embedding asserts
  * its codes): 0, or -1 with the reason */
@@ -74,7 +73,6 @@ static size_t sqnet_seq_bytes(size_t n) { return n + n * SH_SQN_NO * 4 + ((n + S
 /* one launch over the sequences who[0 .. nw) of the call */
 static int sqnet_run(scrappie_hip_engine *e, const Model *m, const std::vector<size_t> &who, const int *const *seqs, const size_t *n, int transform_units,
                      scrappie_matrix *out) {
-    if (who.empty()) return 0;
     std::lock_guard<std::mutex> lk(e->mu);
     hipStream_t s = e->stream;
     DBuf *d = e->d_sqn;           /* 0 tiles | codes, 1 outputs */
@@ -136,52 +134,24 @@ extern "C" int scrappie_hip_squiggle_predict_batch(scrappie_hip_engine *e, const
     if (m->arch != 4) return set_err("squiggle_predict_batch: model '%s' is not a squiggle model", model);
     (void)hipSetDevice(e->device);
     { std::lock_guard<std::mutex> lk(e->mu); for (double &x : e->sqnet_ms) x = 0.0; }
-    /* what a launch may hold: half of the device memory that is free now */
-    size_t budget = e->dbg_sqnet_budget;
-    if (!budget) {
-        size_t fr = 0, tot = 0;
-        budget = hipMemGetInfo(&fr, &tot) == hipSuccess ? fr / 2 : e->total_mem / 4;
-    }
-    std::string why;
-    std::vector<size_t> who;
-    size_t bytes = 0, tiles = 0;
-    int rc = 0;
-    auto flush = [&]() {
-        if (who.empty() || rc) return;
-        if (sqnet_run(e, m, who, seqs, n, transform_units, out)) {
-            rc = -1;
-            const std::string keep = g_err;
-            (void)hipGetLastError();
-            (void)sh_stream_wait(e->stream);
-            set_err("%s", keep.c_str());
-        }
-        who.clear(); bytes = 0; tiles = 0;
-    };
-    for (size_t i = 0; i < count && !rc; i++) {
-        char msg[200];
-        if (sqnet_seq_ok("squiggle_predict_batch", seqs[i], n[i], m->WL)) {
-            if (why.empty()) { snprintf(msg, sizeof msg, "%s (sequence %zu of the call)", g_err, i); why = msg; }
-            continue;
-        }
+    const size_t budget = launch_budget(e, e->dbg_sqnet_budget);
+    struct Load { size_t bytes = 0, tiles = 0; };
+    LaunchCut<Load> cut{e, "squiggle_predict_batch"};
+    cut.run = [&](const std::vector<size_t> &who, Load &) { return sqnet_run(e, m, who, seqs, n, transform_units, out); };
+    for (size_t i = 0; i < count && !cut.failed; i++) {
+        if (sqnet_seq_ok("squiggle_predict_batch", seqs[i], n[i], m->WL)) { cut.refuse(i, g_err); continue; }
         const size_t sb = sqnet_seq_bytes(n[i]), st = (n[i] + SH_SQN_TP - 1) / SH_SQN_TP;
         if (sb > budget) {
-            if (why.empty()) {
-                snprintf(msg, sizeof msg, "squiggle_predict_batch: %zu bases need %zu bytes on the device, more than one launch may take (%zu) (sequence %zu of the call)",
-                         n[i], sb, budget, i);
-                why = msg;
-            }
+            char msg[200];
+            snprintf(msg, sizeof msg, "squiggle_predict_batch: %zu bases need %zu bytes on the device, more than one launch may take (%zu)", n[i], sb, budget);
+            cut.refuse(i, msg);
             continue;
         }
-        if (!who.empty() && (bytes + sb > budget || tiles + st > (size_t)INT32_MAX / 2)) flush();
-        who.push_back(i); bytes += sb; tiles += st;
+        cut.add(i, cut.load.bytes + sb <= budget && cut.load.tiles + st <= (size_t)INT32_MAX / 2);
+        cut.load.bytes += sb; cut.load.tiles += st;
     }
-    flush();
-    if (rc) {
-        for (size_t i = 0; i < count; i++) out[i] = free_scrappie_matrix(out[i]);
-        return -1;
-    }
-    if (!why.empty()) set_err("%s", why.c_str());
-    return 0;
+    return cut.finish([&] { for (size_t i = 0; i < count; i++) out[i] = free_scrappie_matrix(out[i]); },
+                      [](size_t i, const char *why) { set_err("%s (sequence %zu of the call)", why, i); });
 }
 
 /* ------------------------------------------------------------------ */

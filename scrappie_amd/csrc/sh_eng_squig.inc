@@ -1,18 +1,18 @@
 /* sh_eng_squig.inc -- part of scrappie_hip.hip (one translation unit, included from there in this order; not compiled alone):
  * mapping of raw signals to predicted squiggles (sh_squig.h).  scrappie_hip_squiggle_match_batch cuts a call into launches
- * whose traceback and scratch fit a share of the free device memory; a launch is tables on the host (sh_host.c) -> uploads
- * -> k_squig -> k_squig_walk -> scores and paths back.  The reference's squiggle_match_viterbi / _forward are a batch of one
- * on the process-default engine.  No network runs and no model is needed. */
+ * whose traceback and scratch fit a share of the free device memory (LaunchCut, sh_eng_cut.inc); a launch is tables on the host
+ * (sh_host.c) -> uploads -> k_squig in its two homes -> k_squig_walk -> scores and paths back (dp_order / dp_launch / dp_collect,
+ * there too).  What is here is the family's own: the plan of a launch and what a read costs, the checks a read passes, the staging of
+ * signals and tables.  The reference's squiggle_match_viterbi / _forward are a batch of one on the process-default engine.  No
+ * network runs and no model is needed. */
 
-/* host side of one launch: the reads' records, their signals and tables laid end to end, traceback / scratch offsets */
+/* host side of one launch: the reads' records (who[] of the cutter says whose), their signals and tables laid end to end, traceback / scratch offsets */
 struct SquigPlan {
     std::vector<ShSquigRead> rd;
-    std::vector<size_t> who;              /* index of each read in the call */
     std::vector<long long> path_off;      /* per read, -1: no path */
     long long sig_floats = 0, tab_floats = 0, tb_words = 0, scr_floats = 0, path_len = 0;
     size_t lds = SH_SQ_LDS_HEAD * 4;
     size_t bytes = 0;                     /* device bytes the launch holds so far */
-    void clear() { *this = SquigPlan(); }
 };
 
 static size_t squig_lds_bytes(size_t npos) { return (SH_SQ_LDS_HEAD + 2 * (2 * npos + 1) + 5 * npos + 4) * 4; }
@@ -29,7 +29,7 @@ static size_t squig_read_bytes(size_t npos, size_t nsample, bool path) {
     return b;
 }
 
-static void squig_plan_add(SquigPlan &pl, size_t who, size_t nsample, size_t npos, bool path) {
+static void squig_plan_add(SquigPlan &pl, size_t nsample, size_t npos, bool path) {
     ShSquigRead r{};
     r.nsample = (int)nsample; r.npos = (int)npos; r.ok = 1;
     r.sig = pl.sig_floats; pl.sig_floats += (long long)nsample;
@@ -42,7 +42,6 @@ static void squig_plan_add(SquigPlan &pl, size_t who, size_t nsample, size_t npo
     if (npos <= SH_SQ_LDS_MAX_POS) { r.scr = -1; pl.lds = std::max(pl.lds, squig_lds_bytes(npos)); }
     else { r.scr = pl.scr_floats; pl.scr_floats += squig_scr_floats(npos); }
     pl.rd.push_back(r);
-    pl.who.push_back(who);
     pl.bytes += squig_read_bytes(npos, nsample, path);
 }
 
@@ -53,7 +52,7 @@ static void squig_plan_add(SquigPlan &pl, size_t who, size_t nsample, size_t npo
 extern "C" long long scrappie_hip_squiggle_plan_scratch(const size_t *npos, const size_t *nsample, size_t n, long long *off) {
     SquigPlan pl;
     for (size_t i = 0; i < n; i++) {
-        squig_plan_add(pl, i, nsample[i], npos[i], false);
+        squig_plan_add(pl, nsample[i], npos[i], false);
         if (off) off[i] = pl.rd[i].scr;
     }
     return pl.scr_floats;
@@ -62,90 +61,62 @@ extern "C" long long scrappie_hip_squiggle_plan_scratch(const size_t *npos, cons
 /* launches of each k_squig form in this process: index (vit ? 2 : 0) | (scratch ? 1 : 0) */
 static std::atomic<uint64_t> g_squig_forms[4];
 
-template <bool VIT>
-static void squig_launch_k(hipStream_t s, const ShSquigArgs &a, size_t n_lds, size_t n, size_t lds) {
-    if (n_lds) g_squig_forms[VIT ? 2 : 0].fetch_add(1, std::memory_order_relaxed);
-    if (n > n_lds) g_squig_forms[(VIT ? 2 : 0) | 1].fetch_add(1, std::memory_order_relaxed);
-    if (n_lds) hipLaunchKernelGGL((k_squig<VIT, true>), dim3((unsigned)n_lds), dim3(SH_SQ_NTH), lds, s, a);
-    if (n > n_lds) {                     /* the reads whose rows live in scratch: the records' tail */
-        ShSquigArgs b = a;
-        b.rd += n_lds; b.score += n_lds; b.final_state += n_lds;
-        hipLaunchKernelGGL((k_squig<VIT, false>), dim3((unsigned)(n - n_lds)), dim3(SH_SQ_NTH), SH_SQ_LDS_HEAD * 4, s, b);
-    }
-}
-
-/* one launch: out[who] gets its score and, where the plan holds a path, its padded path (malloc'd, signal.n long) */
-static int squig_run(scrappie_hip_engine *e, SquigPlan &pl, const raw_table *reads, const scrappie_hip_squiggle_target *tg,
+/* one launch over the reads who[] of the call: out[who] gets its score and, where the plan holds a path, its padded path (malloc'd, signal.n long) */
+static int squig_run(scrappie_hip_engine *e, const std::vector<size_t> &who, SquigPlan &pl, const raw_table *reads, const scrappie_hip_squiggle_target *tg,
                      const scrappie_hip_squiggle_params *p, bool vit, scrappie_hip_squiggle_result *out) {
     const size_t n = pl.rd.size();
-    if (n == 0) return 0;
     std::lock_guard<std::mutex> lk(e->mu);
     hipStream_t s = e->stream;
-    DBuf *d = e->d_sq;           /* 0 reads, 1 signals, 2 tables, 3 traceback, 4 scratch, 5 scores, 6 final states, 7 path offsets, 8 paths */
+    DpBufs &d = e->dp_sq;
     const bool walk = vit && pl.path_len > 0;
     const auto t0 = std::chrono::steady_clock::now();
-    /* device order: the reads whose rows fit LDS first (one launch), then those in scratch (another) */
-    std::vector<size_t> perm(n);
-    std::iota(perm.begin(), perm.end(), (size_t)0);
-    std::stable_partition(perm.begin(), perm.end(), [&](size_t i) { return pl.rd[i].scr < 0; });
-    size_t n_lds = 0;
-    while (n_lds < n && pl.rd[perm[n_lds]].scr < 0) n_lds++;
+    std::vector<size_t> perm;
+    const size_t n_lds = dp_order(pl.rd, perm);
     const size_t up_floats = ((size_t)pl.sig_floats + (size_t)pl.tab_floats + 1) & ~(size_t)1;      /* (the records behind them are 8-byte aligned) */
-    if (d[0].ensure(n * sizeof(ShSquigRead)) || d[1].ensure((size_t)pl.sig_floats * 4 + 16) || d[2].ensure((size_t)pl.tab_floats * 4 + 16) ||
-        d[3].ensure((size_t)pl.tb_words * 4 + 16) || d[4].ensure((size_t)pl.scr_floats * 4 + 16) || d[5].ensure(n * 4) ||
-        d[6].ensure(n * 4) || d[7].ensure(n * 8) || d[8].ensure((size_t)pl.path_len * 4 + 16) ||
-        e->h_sq.ensure(std::max(up_floats * 4 + n * (sizeof(ShSquigRead) + 8), n * 4 + (size_t)pl.path_len * 4))) return -1;
+    if (d.ensure(n, sizeof(ShSquigRead), pl.tb_words, pl.scr_floats, pl.path_len, up_floats * 4 + n * (sizeof(ShSquigRead) + 8)) ||
+        e->d_sq_sig.ensure((size_t)pl.sig_floats * 4 + 16) || e->d_sq_tab.ensure((size_t)pl.tab_floats * 4 + 16)) return -1;
     /* staging (pinned): signals | tables | records | path offsets */
-    float *hsig = e->h_sq.as<float>(), *htab = hsig + pl.sig_floats;
+    float *hsig = d.h.as<float>(), *htab = hsig + pl.sig_floats;
     ShSquigRead *hrd = (ShSquigRead *)(hsig + up_floats);
     long long *hoff = (long long *)(hrd + n);
     float pens[2] = {0.0f, 0.0f};
     for (size_t k = 0; k < n; k++) {
         const size_t i = perm[k];
         const ShSquigRead &r = pl.rd[i];
-        const raw_table &rt = reads[pl.who[i]];
-        const scrappie_hip_squiggle_target &t = tg[pl.who[i]];
+        const raw_table &rt = reads[who[i]];
+        const scrappie_hip_squiggle_target &t = tg[who[i]];
         memcpy(hsig + r.sig, rt.raw + rt.start, (size_t)r.nsample * 4);
         sh_squiggle_tables(t.params, t.npos, t.stride, p->rate, p->prob_back, htab + r.tab, pens);
         hrd[k] = r; hoff[k] = pl.path_off[i];
     }
-    HIPCHK(hipMemcpyAsync(d[1].p, hsig, (size_t)pl.sig_floats * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d[2].p, htab, (size_t)pl.tab_floats * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d[0].p, hrd, n * sizeof(ShSquigRead), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d[7].p, hoff, n * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(e->d_sq_sig.p, hsig, (size_t)pl.sig_floats * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(e->d_sq_tab.p, htab, (size_t)pl.tab_floats * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d.rd.p, hrd, n * sizeof(ShSquigRead), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d.path_off.p, hoff, n * 8, hipMemcpyHostToDevice, s));
     HIPCHK(sh_stream_wait(s));
     ShSquigArgs a{};
-    a.rd = d[0].as<ShSquigRead>(); a.sig = d[1].as<float>(); a.tab = d[2].as<float>(); a.tb = d[3].as<unsigned>(); a.scr = d[4].as<float>();
-    a.score = d[5].as<float>(); a.final_state = d[6].as<int>();
+    a.rd = d.rd.as<ShSquigRead>(); a.sig = e->d_sq_sig.as<float>(); a.tab = e->d_sq_tab.as<float>(); a.tb = d.tb.as<unsigned>(); a.scr = d.scr.as<float>();
+    a.score = d.score.as<float>(); a.final_state = d.final_state.as<int>();
     a.move_back_pen = pens[0]; a.half_pen = pens[1];
     a.local_pen = p->local_pen; a.skip_pen = p->skip_pen; a.minscore = p->minscore;
     const auto t1 = std::chrono::steady_clock::now();
-    if (vit) squig_launch_k<true>(s, a, n_lds, n, pl.lds); else squig_launch_k<false>(s, a, n_lds, n, pl.lds);
+    if (vit) dp_launch<k_squig<true, true>, k_squig<true, false>>(s, a, n_lds, n, SH_SQ_NTH, pl.lds, SH_SQ_LDS_HEAD * 4, g_squig_forms + 2);
+    else dp_launch<k_squig<false, true>, k_squig<false, false>>(s, a, n_lds, n, SH_SQ_NTH, pl.lds, SH_SQ_LDS_HEAD * 4, g_squig_forms);
     HIPCHK(hipGetLastError());
     HIPCHK(sh_stream_wait(s));
     const auto t2 = std::chrono::steady_clock::now();
-    if (walk) {
-        hipLaunchKernelGGL(k_squig_walk, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, (const ShSquigRead *)d[0].p, (int)n, (const unsigned *)d[3].p,
-                           (const int *)d[6].p, (const long long *)d[7].p, d[8].as<int>());
-        HIPCHK(hipGetLastError());
-    }
-    float *hs = e->h_sq.as<float>();
-    int32_t *hp = (int32_t *)(hs + n);
-    HIPCHK(hipMemcpyAsync(hs, d[5].p, n * 4, hipMemcpyDeviceToHost, s));
-    if (walk) HIPCHK(hipMemcpyAsync(hp, d[8].p, (size_t)pl.path_len * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(sh_stream_wait(s));
-    for (size_t k = 0; k < n; k++) {
-        const size_t i = perm[k];
-        scrappie_hip_squiggle_result &res = out[pl.who[i]];
-        const raw_table &rt = reads[pl.who[i]];
-        res.score = hs[k];
-        res.n = rt.n;
-        if (!walk || pl.path_off[i] < 0) continue;
-        res.path = (int32_t *)malloc(std::max<size_t>(rt.n, 1) * 4);
-        if (!res.path) return set_err("out of host memory");
-        for (size_t j = 0; j < rt.n; j++) res.path[j] = -1;
-        memcpy(res.path + rt.start, hp + pl.path_off[i], (size_t)pl.rd[i].nsample * 4);
-    }
+    if (dp_collect<k_squig_walk, ShSquigRead>(s, d, perm, pl.path_off, pl.path_len, walk, [&](size_t i, float sc, const int32_t *path) {
+            scrappie_hip_squiggle_result &res = out[who[i]];
+            const raw_table &rt = reads[who[i]];
+            res.score = sc;
+            res.n = rt.n;
+            if (!path) return 0;
+            res.path = (int32_t *)malloc(std::max<size_t>(rt.n, 1) * 4);
+            if (!res.path) return set_err("out of host memory");
+            for (size_t j = 0; j < rt.n; j++) res.path[j] = -1;
+            memcpy(res.path + rt.start, path, (size_t)pl.rd[i].nsample * 4);
+            return 0;
+        })) return -1;
     const auto t3 = std::chrono::steady_clock::now();
     e->squig_ms[0] += std::chrono::duration<double, std::milli>(t1 - t0).count();
     e->squig_ms[1] += std::chrono::duration<double, std::milli>(t2 - t1).count();
@@ -184,14 +155,8 @@ extern "C" void scrappie_hip_launch_form_counts(uint64_t map_forms[16], uint64_t
     for (int k = 0; k < 4; k++) if (squig_forms) squig_forms[k] = g_squig_forms[k].load(std::memory_order_relaxed);
 }
 
-extern "C" void scrappie_hip_squiggle_timing(scrappie_hip_engine *e, double out[3]) {
-    for (int k = 0; k < 3; k++) out[k] = e ? e->squig_ms[k] : 0.0;
-}
-
-extern "C" void scrappie_hip_free_squiggle_results(scrappie_hip_squiggle_result *r, size_t n) {
-    if (!r) return;
-    for (size_t i = 0; i < n; i++) { free(r[i].path); r[i].path = nullptr; }
-}
+extern "C" void scrappie_hip_squiggle_timing(scrappie_hip_engine *e, double out[3]) { timing3(e ? e->squig_ms : nullptr, out); }
+extern "C" void scrappie_hip_free_squiggle_results(scrappie_hip_squiggle_result *r, size_t n) { free_paths(r, n); }
 
 extern "C" int scrappie_hip_squiggle_match_batch(scrappie_hip_engine *e, const raw_table *reads, const scrappie_hip_squiggle_target *targets,
                                                  size_t n, const scrappie_hip_squiggle_params *p, int viterbi, int want_path,
@@ -204,48 +169,24 @@ extern "C" int scrappie_hip_squiggle_match_batch(scrappie_hip_engine *e, const r
     (void)hipSetDevice(e->device);
     { std::lock_guard<std::mutex> lk(e->mu); for (double &x : e->squig_ms) x = 0.0; }
     const bool vit = viterbi != 0, path = vit && want_path != 0;
-    /* what a launch may hold: half of the device memory that is free now (the engine's own arena stays where it is) */
-    size_t budget = e->dbg_squig_budget;
-    if (!budget) {
-        size_t fr = 0, tot = 0;
-        budget = hipMemGetInfo(&fr, &tot) == hipSuccess ? fr / 2 : e->total_mem / 4;
-    }
-    std::vector<std::string> why(n);
-    SquigPlan pl;
-    int rc = 0;
-    auto flush = [&]() {
-        if (pl.rd.empty() || rc) return;
-        if (squig_run(e, pl, reads, targets, p, vit, out)) {
-            rc = -1;
-            const std::string keep = g_err;
-            (void)hipGetLastError();
-            (void)sh_stream_wait(e->stream);
-            set_err("%s", keep.c_str());
-        }
-        pl.clear();
-    };
-    for (size_t i = 0; i < n && !rc; i++) {
-        if (squig_read_ok("squiggle_match_batch", reads[i], targets[i])) { why[i] = g_err; continue; }
+    const size_t budget = launch_budget(e, e->dbg_squig_budget);
+    LaunchCut<SquigPlan> cut{e, "squiggle_match_batch"};          /* (the plan of the launch being assembled is the cutter's load) */
+    cut.run = [&](const std::vector<size_t> &who, SquigPlan &pl) { return squig_run(e, who, pl, reads, targets, p, vit, out); };
+    for (size_t i = 0; i < n && !cut.failed; i++) {
+        if (squig_read_ok("squiggle_match_batch", reads[i], targets[i])) { cut.refuse(i, g_err); continue; }
         const size_t ns = reads[i].end - reads[i].start, npos = targets[i].npos;
         const size_t rb = squig_read_bytes(npos, ns, path);
         if (rb > budget) {
             char msg[160];
             snprintf(msg, sizeof msg, "squiggle_match_batch: %zu samples against %zu positions need %zu bytes on the device, more than one launch may take (%zu)", ns, npos, rb, budget);
-            why[i] = msg;
+            cut.refuse(i, msg);
             continue;
         }
-        if (!pl.rd.empty() && (pl.bytes + rb > budget || pl.rd.size() >= 65535)) flush();
-        squig_plan_add(pl, i, ns, npos, path);
+        cut.add(i, cut.load.bytes + rb <= budget && cut.who.size() < 65535);
+        squig_plan_add(cut.load, ns, npos, path);
     }
-    flush();
-    if (rc) {
-        scrappie_hip_free_squiggle_results(out, n);
-        for (size_t i = 0; i < n; i++) { out[i].score = NAN; out[i].n = 0; }
-        return -1;
-    }
-    for (size_t i = 0; i < n; i++)
-        if (!why[i].empty()) { set_err("%s (read %zu of the call)", why[i].c_str(), i); break; }
-    return 0;
+    return cut.finish([&] { scrappie_hip_free_squiggle_results(out, n); for (size_t i = 0; i < n; i++) { out[i].score = NAN; out[i].n = 0; } },
+                      [](size_t i, const char *why) { set_err("%s (read %zu of the call)", why, i); });
 }
 
 /* ------------------------------------------------------------------ */

@@ -40,9 +40,7 @@ static void posterior_batch(scrappie_hip_engine *e, std::vector<PostReq *> &reqs
     std::lock_guard<std::mutex> lk(e->mu);
     PostStage *stage = &e->post_stage[e->post_turn++ & 1];
     std::vector<PostReq *> live;
-    std::vector<uint64_t> off;
-    std::vector<uint32_t> len;
-    size_t total = 0;
+    std::vector<const raw_table *> win;
     for (PostReq *r : reqs) {
         const raw_table &sg = r->sig;
         if (sg.n == 0 || !sg.raw || sg.end <= sg.start) { post_fail(r, "empty read"); continue; }
@@ -52,34 +50,19 @@ static void posterior_batch(scrappie_hip_engine *e, std::vector<PostReq *> &reqs
             else post_fail(r, "read of %zu samples is below the model minimum %zu", ns, m->min_samples);
             continue;
         }
-        live.push_back(r); off.push_back(total); len.push_back((uint32_t)ns);
-        total += nf;
+        live.push_back(r); win.push_back(&r->sig);
     }
     if (live.empty()) return;
-    auto fail_all = [&]() { for (PostReq *r : live) if (!r->src) post_fail(r, "%s", g_err); };
-    Slot &st = e->slots[0];                /* staged in the first slot's buffers (nothing else is in flight under mu) */
-    if (st.h_sig.ensure(total * 4) || st.d_signal.ensure(total * 4)) { fail_all(); return; }
-    float *hs = st.h_sig.as<float>();
-    for (size_t i = 0; i < live.size(); i++) memcpy(hs + off[i], live[i]->sig.raw + live[i]->sig.start, (live[i]->sig.end - live[i]->sig.start) * 4);
-    /* (the group's prologue -- the convolution -- runs on another stream: the signals must be there before it is enqueued) */
-    if (hipMemcpyAsync(st.d_signal.p, hs, total * 4, hipMemcpyHostToDevice, e->stream) != hipSuccess || sh_stream_wait(e->stream) != hipSuccess) {
-        set_err("upload failed: %s", hipGetErrorString(hipGetLastError())); fail_all(); return;
-    }
     scrappie_hip_params p = scrappie_hip_default_params();
     p.tempW = live[0]->tempW; p.tempb = live[0]->tempb;
     RunOut ro;
-    if (run_pipeline(e, m, st.d_signal.as<float>(), off.data(), len.data(), live.size(), &p, live[0]->stop, live[0]->upto, &ro)) { fail_all(); return; }
+    std::vector<unsigned> bad;
+    if (run_staged(e, m, win, &p, live[0]->stop, live[0]->upto, &ro, bad)) { for (PostReq *r : live) post_fail(r, "%s", g_err); return; }
     /* what is gathered: the posterior where S1 left it (finalised here for the transducers; the CRF's transitions are final), or the trunk's activations */
     const float *src = trunk ? ro.act : ro.E;
     const int nr = trunk ? ro.act_units : m->NS, nchunk = trunk ? ro.act_units / 16 : m->ff_mtiles;
     const bool tr = !trunk && m->arch != 1;
-    const Slot &sl = e->current(); const LaunchGroup &lg = sl.lg;
-    std::vector<unsigned> bad(lg.npad, 0);
-    if (hipMemcpyAsync(bad.data(), sl.d_bad.p, lg.npad * 4, hipMemcpyDeviceToHost, e->stream) != hipSuccess || sh_stream_wait(e->stream) != hipSuccess) {
-        set_err("reading the range flags failed: %s", hipGetErrorString(hipGetLastError())); fail_all(); return;
-    }
-    std::vector<long long> tile_boff(lg.ntile, 0);
-    { long long ncb = 0; for (size_t t = 0; t < lg.ntile; t++) { int tt = 0; for (int b = 0; b < 16; b++) tt = std::max(tt, lg.rT[t * 16 + b]); tile_boff[t] = ncb; ncb += tt; } }
+    const LaunchGroup &lg = e->current().lg;
     /* one staging buffer for the whole group, one synchronisation */
     std::vector<size_t> toff(lg.npad, 0);
     size_t tbytes = 0;
@@ -106,7 +89,7 @@ static void posterior_batch(scrappie_hip_engine *e, std::vector<PostReq *> &reqs
         const int T = lg.rT[i];
         const long long tot = (long long)T * nr;
         float *dst = (float *)((char *)tmp.p + toff[i]);
-        hipLaunchKernelGGL(k_gather_read, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, e->stream, src, tr ? ro.sums : nullptr, tile_boff[i >> 4], (int)(i & 15), T, nr,
+        hipLaunchKernelGGL(k_gather_read, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, e->stream, src, tr ? ro.sums : nullptr, lg.tile_boff[i >> 4], (int)(i & 15), T, nr,
                            nchunk, (int)mstride, tr ? 1 : 0, tr && r->want_log ? 1 : 0, tr ? r->min_prob : 0.f, dst);
     }
     /* one copy into pinned memory at the link's rate; the callers take their matrices out of it themselves, all at once */

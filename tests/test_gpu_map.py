@@ -377,6 +377,92 @@ def test_per_read_threads():
         assert a_s.tobytes() == t_s.tobytes() and np.array_equal(a_p, t_p)
 
 
+def _small_call(n, seed):
+    """n reads of 600 to 1000 samples with a sequence of 30 states (34 bases) each"""
+    rng = np.random.default_rng(seed)
+    sigs = [synth.medmad_normalise(synth.synthetic_signal(int(k), 500 + i)) for i, k in enumerate(rng.integers(600, 1000, n))]
+    return sigs, [_bases(34, rng) for _ in sigs]
+
+
+def _same_results(a, b, skip=()):
+    assert len(a) == len(b)
+    for i, ((sa_, pa), (sb, pb)) in enumerate(zip(a, b)):
+        if i in skip:
+            continue
+        assert np.float32(sa_).tobytes() == np.float32(sb).tobytes(), (i, sa_, sb)
+        assert (pa is None and pb is None) or np.array_equal(pa, pb), i
+
+
+def test_engine_map_cut_by_memory(eng):
+    """launch groups cut by device bytes, not by reads: a budget of 240 column blocks.  A group costs
+    (sum T / 16 + max T + 1) blocks + under one block of traceback and codes, T the reads' blocks (samples / 5):
+    T = 200, 140, [300], 198 | 200, 120, 199 | 170 -- the fourth read would make 247 and 244 -- and the read of 300 blocks
+    needs 319 alone: refused.  The others as in one uncut launch group, bit for bit."""
+    lens = [1000, 700, 1500, 990, 1000, 600, 995, 850]
+    rng = np.random.default_rng(51)
+    sigs = [synth.medmad_normalise(synth.synthetic_signal(n, 400 + i)) for i, n in enumerate(lens)]
+    seqs = [_bases(34, rng) for _ in lens]
+    assert [eng.read_blocks("rgrgr_r94", n) for n in lens] == [200, 140, 300, 198, 200, 120, 199, 170]
+    kw = dict(viterbi=True, path=True, stay_pen=0.5, skip_pen=1.0, local_pen=4.0)
+    form = (True, False, True, False)                      # Viterbi, unbanded, tiled, LDS: one launch per group
+    before = sa.launch_form_counts()["map"][form]
+    uncut = eng.map_to_sequence(sigs, seqs, **kw)
+    assert sa.launch_form_counts()["map"][form] == before + 1
+    assert all(np.isfinite(sc) and pth is not None for sc, pth in uncut)
+    eng.set_max_launch_blocks(240)
+    try:
+        cut = eng.map_to_sequence(sigs, seqs, **kw)
+        err = sa.last_error()
+    finally:
+        eng.set_max_launch_blocks(0)
+    groups = sa.launch_form_counts()["map"][form] - before - 1
+    print("launch groups under a budget of 240 blocks: %d" % groups)
+    assert groups >= 3
+    assert np.isnan(cut[2][0]) and cut[2][1] is None
+    assert "read 2" in err and "too long for one launch group" in err, err
+    _same_results(cut, uncut, skip=(2,))
+
+
+def test_engine_failed_launch_group(eng):
+    """the second of three launch groups refused (debug option fail_run): the call fails with that text and hands nothing
+    back, and the engine then gives what it gave before"""
+    sigs, seqs = _small_call(40, 61)
+    kw = dict(viterbi=True, path=True, stay_pen=0.5, skip_pen=1.0, local_pen=4.0)
+    form = (True, False, True, False)
+    eng.set_max_launch_reads(16)
+    try:
+        before = sa.launch_form_counts()["map"][form]
+        first = eng.map_to_sequence(sigs, seqs, **kw)
+        assert sa.launch_form_counts()["map"][form] - before == 3
+        assert all(np.isfinite(sc) and pth is not None for sc, pth in first)
+        eng.debug_option("fail_run", 2)
+        got = None
+        with pytest.raises(RuntimeError, match="injected failure"):
+            got = eng.map_to_sequence(sigs, seqs, **kw)
+        assert got is None
+        assert sa.launch_form_counts()["map"][form] - before == 4          # the first group ran, the second was refused, no third
+        eng.debug_option("fail_run", 0)
+        _same_results(eng.map_to_sequence(sigs, seqs, **kw), first)
+    finally:
+        eng.debug_option("fail_run", 0)
+        eng.set_max_launch_reads(16384)
+
+
+def test_debug_fetch_tile_boff(eng):
+    """the launch group's stored first column block per tile is the running sum of the tiles' longest reads"""
+    lens = [600 + 37 * i for i in range(20)]               # two tiles
+    sigs = [synth.medmad_normalise(synth.synthetic_signal(n, 700 + i)) for i, n in enumerate(lens)]
+    rng = np.random.default_rng(71)
+    assert all(np.isfinite(sc) for sc, _ in eng.map_to_sequence(sigs, [_bases(34, rng) for _ in sigs]))      # one launch group
+    order = eng.debug_fetch("order", np.int32)
+    got = eng.debug_fetch("tile_boff", np.int64)
+    assert len(order) == 32 and sorted(o for o in order if o >= 0) == list(range(20))
+    T = [eng.read_blocks("rgrgr_r94", n) for n in lens]
+    tile_T = [max(T[o] if o >= 0 else 0 for o in order[t * 16:(t + 1) * 16]) for t in range(2)]
+    assert tile_T[0] > 0 and tile_T[1] > 0
+    assert got.tolist() == [0, tile_T[0]]
+
+
 def test_every_map_form_was_launched(forms_at_start):
     """the last test of the module: each of the 16 k_map instantiations (Viterbi / forward x full / banded x dense / tiled
     x LDS / scratch) has been launched by the tests above"""

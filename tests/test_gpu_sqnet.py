@@ -117,6 +117,34 @@ def test_batch_is_bit_identical_to_per_read(name, registered, eng):
         eng.debug_option("sqnet_budget_kb", 0)
 
 
+def test_failed_launch(eng):
+    """the second of three launches refused (debug option fail_run): the call fails with that text and hands nothing back,
+    and the engine then gives what it gave before.  A sequence of 300 bases takes 3996 bytes of a launch: four to a
+    launch of 16 KB, twelve sequences in three launches."""
+    name = sorted(MODELS)[0]
+    rng = np.random.RandomState(9)
+    seqs = [rng.randint(0, 4, 300).astype(np.int32) for _ in range(12)]
+    count = sa.lib().scrappie_hip_sqnet_launch_count
+    eng.debug_option("sqnet_budget_kb", 16)
+    try:
+        before = count()
+        first = eng.predict_squiggle(seqs, model=name)
+        assert count() == before + 3
+        assert all(g is not None and g.shape == (300, 3) for g in first)
+        eng.debug_option("fail_run", 2)
+        got = None
+        with pytest.raises(RuntimeError, match="injected failure"):
+            got = eng.predict_squiggle(seqs, model=name)
+        assert got is None
+        assert count() == before + 4                       # the first launch ran, the second was refused, no third
+        eng.debug_option("fail_run", 0)
+        again = eng.predict_squiggle(seqs, model=name)
+        assert all(a is not None and a.tobytes() == g.tobytes() for a, g in zip(again, first))
+    finally:
+        eng.debug_option("fail_run", 0)
+        eng.debug_option("sqnet_budget_kb", 0)
+
+
 @pytest.mark.parametrize("name", sorted(MODELS))
 def test_tile_seams(name, registered, eng):
     """around each tile edge of a 2 TP + 1 sequence, every position equals bit for bit the same position of a run on a

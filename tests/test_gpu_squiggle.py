@@ -227,6 +227,39 @@ def test_engine_all_cases_in_one_call(eng, ref, cases):
         eng.debug_option("squiggle_budget_kb", 0)
 
 
+def test_engine_failed_launch(eng, cases):
+    """the second of several launches refused (debug option fail_run): the call fails with that text and hands nothing back,
+    and the engine then gives what it gave before"""
+    rts = []
+    for c in cases:
+        rt = sa.RawTable(c["sig"])
+        rt._rt.start, rt._rt.end = c["start"], c["end"]
+        rts.append(rt)
+    sqs = [c["params"] for c in cases]
+    lds_form = (True, False)                               # Viterbi, LDS: at most one launch of it per launch of the call
+    eng.debug_option("squiggle_budget_kb", 256)
+    try:
+        before = sa.launch_form_counts()["squig"][lds_form]
+        first = eng.match_squiggle(rts, sqs, viterbi=True, path=True)
+        launches = sa.launch_form_counts()["squig"][lds_form] - before
+        print("launches under a budget of 256 KB: at least %d" % launches)
+        assert launches >= 3
+        eng.debug_option("fail_run", 2)
+        got = None
+        with pytest.raises(RuntimeError, match="injected failure"):
+            got = eng.match_squiggle(rts, sqs, viterbi=True, path=True)
+        assert got is None
+        eng.debug_option("fail_run", 0)
+        again = eng.match_squiggle(rts, sqs, viterbi=True, path=True)
+        assert len(again) == len(first)
+        for c, (s0, p0), (s1, p1) in zip(cases, first, again):
+            assert np.float32(s0).tobytes() == np.float32(s1).tobytes(), c["name"]
+            assert (p0 is None and p1 is None) or np.array_equal(p0, p1), c["name"]
+    finally:
+        eng.debug_option("fail_run", 0)
+        eng.debug_option("squiggle_budget_kb", 0)
+
+
 def test_path_follows_the_simulated_squiggle(ref):
     params, sig, truth = synth.simulated_squiggle(400, 12)
     pens = PENS[0]
