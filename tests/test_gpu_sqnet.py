@@ -1,7 +1,13 @@
 """Squiggle prediction on the GPU (sh_sqnet.h, k_sqnet): the per-read squiggle_r94 / squiggle_r94_rna, the batched
 Engine.predict_squiggle, mappy as a composition with the squiggle matcher, and the two command lines, against the
 references and the tolerance of tests/test_sqnet_cpu.py: every output column within 4 x E32 of the float64
-restatement (E32: the float32 oracle's own distance from it)."""
+restatement (E32: the float32 oracle's own distance from it).
+
+The network tests run on the variants of tests/test_sqnet_cpu.py: the plain synthetic weights, the saturated ones (tanh
+arguments to beyond 20, as the shipped models have them) and, for the activation alone, the sweep weights under which the
+output is tanh of a known argument.  A variant goes on the engines under its model's name for the length of one test
+(`variant_loaded`); the plain weights are back afterwards."""
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -10,8 +16,9 @@ import numpy as np
 import pytest
 
 import scrappie_amd as sa
+import test_sqnet_cpu
 from scrappie_amd import model
-from test_sqnet_cpu import CLI, GPU_TOL, MODELS, ROOT, halo, references, tile, weights
+from test_sqnet_cpu import CLI, GPU_TOL_OF, MODELS, ROOT, VARIANTS, halo, references, tile, variant_weights, weights
 
 pytestmark = pytest.mark.gpu
 
@@ -50,42 +57,94 @@ def eng(model_files):
     e.close()
 
 
+@pytest.fixture(scope="module")
+def variant_files(tmp_path_factory, model_files):
+    """{(model name, variant): file}"""
+    d = tmp_path_factory.mktemp("sqnet_variants")
+    out = {}
+    for name in MODELS:
+        for variant in VARIANTS:
+            if variant == "plain":
+                out[name, variant] = model_files[name]
+            else:
+                out[name, variant] = str(d / ("%s.%s.scrm" % (name, variant)))
+                model.save_model(variant_weights(name, variant), out[name, variant])
+    return out
+
+
+@contextlib.contextmanager
+def variant_loaded(name, variant, files, eng=None):
+    """the variant's weights under the model's name, on the process-default engine and on `eng`; the plain ones afterwards"""
+    try:
+        if variant != "plain":
+            sa.register_model(name, files[name, variant])
+            if eng is not None:
+                eng.load_model(name, files[name, variant])
+        yield
+    finally:
+        if variant != "plain":
+            sa.register_model(name, files[name, "plain"])
+            if eng is not None:
+                eng.load_model(name, files[name, "plain"])
+
+
+def cases_of(variants):
+    """(model, variant) for parametrize; the plain cases keep the ids they have always had"""
+    return [pytest.param(name, v, id=name if v == "plain" else "%s-%s" % (name, v)) for v in variants for name in sorted(MODELS)]
+
+
 _per_read = {}
 
 
-def per_read(name, registered):
-    """{case name: (n, 3) float32} through the per-read function (a batch of one each), computed once"""
-    if name not in _per_read:
+def per_read(name, registered, variant="plain"):
+    """{case name: (n, 3) float32} through the per-read function (a batch of one each), computed once; the variant's weights
+    must be the registered ones (variant_loaded)"""
+    if (name, variant) not in _per_read:
         got = {}
-        for cn, (codes, r32, r64) in references(name).items():
+        for cn, (codes, r32, r64) in references(name, variant).items():
             m = sa.sequence_to_squiggle(letters(codes), model=name, rescale=False)
             mat = m.data().contents
             assert (mat.nr, mat.nrq, mat.nc, mat.stride) == (3, 1, len(codes), 4), cn
             padded = np.ctypeslib.as_array(C.cast(mat.data, C.POINTER(C.c_float)), shape=(mat.nc, 4))
             assert np.all(padded[:, 3] == 0.0), cn                         # pad lane
             got[cn] = m.data(as_numpy=True, sloika=False)
-        _per_read[name] = got
-    return _per_read[name]
+        _per_read[name, variant] = got
+    return _per_read[name, variant]
 
 
-@pytest.mark.parametrize("name", sorted(MODELS))
-def test_per_read_against_float64(name, registered):
-    worst = np.zeros(3)
-    for cn, (codes, r32, r64) in references(name).items():
-        got = per_read(name, registered)[cn]
+@pytest.mark.parametrize("name,variant", cases_of(VARIANTS))
+def test_per_read_against_float64(name, variant, registered, variant_files):
+    tol = GPU_TOL_OF[variant]
+    with variant_loaded(name, variant, variant_files):
+        got_all = per_read(name, registered, variant)
+    errs = {}
+    for cn, (codes, r32, r64) in references(name, variant).items():
+        got = got_all[cn]
         assert got.shape == (len(codes), 3) and got.dtype == np.float32, cn
-        err = np.max(np.abs(got.astype(np.float64) - r64), axis=0)
-        worst = np.maximum(worst, err)
-        print("%s %s: max |gpu - f64| per column %r" % (name, cn, tuple(float(x) for x in err)))
+        errs[cn] = np.max(np.abs(got.astype(np.float64) - r64), axis=0)
+        print("%s %s %s: max |gpu - f64| per column %r" % (name, variant, cn, tuple(float(x) for x in errs[cn])))
+    worst = np.max(list(errs.values()), axis=0)
+    print("%s %s: worst per column %r of %r allowed" % (name, variant, tuple(float(x) for x in worst), tol))
+    for cn, (codes, r32, r64) in references(name, variant).items():
         for k in range(3):
-            assert err[k] <= GPU_TOL[k], (cn, k, err[k], GPU_TOL[k])
-    print("%s: worst per column %r of %r allowed" % (name, tuple(float(x) for x in worst), GPU_TOL))
+            assert errs[cn][k] <= tol[k], (cn, k, errs[cn][k], tol[k])
+        if variant == "sweep":
+            # the output is a tanh: never beyond +-1, and exactly +-1 wherever the float32 oracle's is
+            got = got_all[cn]
+            assert np.all(np.abs(got) <= 1.0), cn
+            flat = np.abs(r32[:, 2]) == 1.0
+            assert np.count_nonzero(flat) > len(codes) // 2 and np.array_equal(got[flat, 2], r32[flat, 2]), cn
 
 
-@pytest.mark.parametrize("name", sorted(MODELS))
-def test_batch_is_bit_identical_to_per_read(name, registered, eng):
+@pytest.mark.parametrize("name,variant", cases_of(("plain", "saturated")))
+def test_batch_is_bit_identical_to_per_read(name, variant, registered, eng, variant_files):
+    with variant_loaded(name, variant, variant_files, eng):
+        _batch_is_bit_identical_to_per_read(name, variant, registered, eng)
+
+
+def _batch_is_bit_identical_to_per_read(name, variant, registered, eng):
     wl = MODELS[name][0]
-    refs = references(name)
+    refs = references(name, variant)
     names = sorted(refs)
     np.random.RandomState(5).shuffle(names)
     seqs = [refs[cn][0] for cn in names]
@@ -103,7 +162,7 @@ def test_batch_is_bit_identical_to_per_read(name, registered, eng):
         if cn is None:
             assert g is None
         else:
-            assert g is not None and g.tobytes() == per_read(name, registered)[cn].tobytes(), cn
+            assert g is not None and g.tobytes() == per_read(name, registered, variant)[cn].tobytes(), cn
     # launches cut by device memory: the same bits from several launches
     eng.debug_option("sqnet_budget_kb", 16)
     try:
@@ -145,24 +204,64 @@ def test_failed_launch(eng):
         eng.debug_option("sqnet_budget_kb", 0)
 
 
-@pytest.mark.parametrize("name", sorted(MODELS))
-def test_tile_seams(name, registered, eng):
+@pytest.mark.parametrize("name,variant", cases_of(("plain", "saturated")))
+def test_tile_seams(name, variant, registered, eng, variant_files):
     """around each tile edge of a 2 TP + 1 sequence, every position equals bit for bit the same position of a run on a
-    sub-sequence that holds its whole receptive field (and puts it at another offset of another tile)"""
-    wl, tp = MODELS[name][0], tile()
-    h = halo(wl)
-    codes = references(name)["random_%d" % (2 * tp + 1)][0]
-    full = per_read(name, registered)["random_%d" % (2 * tp + 1)]
+    sub-sequence that holds its whole receptive field (and puts it at another offset of another tile).  With the saturated
+    weights too: the halo columns are where a stale value would come in with the largest weight."""
+    with variant_loaded(name, variant, variant_files, eng):
+        _tile_seams(name, variant, registered, eng, halo(MODELS[name][0]))
+
+
+def _tile_seams(name, variant, registered, eng, h, slack=5):
+    """h: the columns of context that a compared position needs to either side; the sub-sequences keep `slack` more"""
+    tp = tile()
+    codes = references(name, variant)["random_%d" % (2 * tp + 1)][0]
+    full = per_read(name, registered, variant)["random_%d" % (2 * tp + 1)]
     subs, spans = [], []
     for seam in (tp, 2 * tp):
         lo, hi = seam - 3, min(seam + 3, len(codes))
-        a, b = lo - h - 5, min(hi + h + 5, len(codes))
+        a, b = lo - h - slack, min(hi + h + slack, len(codes))
         subs.append(codes[a:b])
         spans.append((a, lo, hi if b - hi >= h or b == len(codes) else b - h))
     got = eng.predict_squiggle(subs, model=name)
     for (a, lo, hi), g in zip(spans, got):
         assert hi - lo >= 3
         assert g[lo - a:hi - a].tobytes() == full[lo:hi].tobytes(), (a, lo, hi)
+
+
+@pytest.mark.parametrize("name", sorted(MODELS))
+def test_zero_layers_hand_their_input_through(name, registered, eng, variant_files):
+    """The sweep weights: conv2..5 are all zeros, so each adds tanh(0) to its input, and conv6 is the identity on three
+    filters.  The float32 oracle hands conv1's tanh through these five layers bit for bit (tests/test_sqnet_cpu.py,
+    test_sweep_zero_layers_hand_their_input_through_on_the_oracle, and again below).  The kernel's conv1 stage cannot be read,
+    so the same is asked of it through what follows from it: the output is then a function of one window of conv1 alone --
+    the same bits per read, batched and from cut launches at 2 TP + 1 and 5 TP + 3, and around the tile seams the same bits
+    from a sub-sequence that keeps only (WL - 1) / 2 columns of context, a sixth of what six live layers reach."""
+    wl, tp = MODELS[name][0], tile()
+    refs = references(name, "sweep")
+    m = variant_weights(name, "sweep")
+    for cn, (codes, r32, r64) in refs.items():
+        stages = []
+        test_sqnet_cpu.ref32(m, codes, stages)
+        assert r32.tobytes() == np.ascontiguousarray(stages[0][:, :3]).tobytes(), cn
+    names = sorted(refs)
+    assert set(names) == {"random_%d" % (2 * tp + 1), "random_%d" % (5 * tp + 3)}
+    with variant_loaded(name, "sweep", variant_files, eng):
+        want = per_read(name, registered, "sweep")
+        got = eng.predict_squiggle([refs[cn][0] for cn in names], model=name)
+        for cn, g in zip(names, got):
+            assert g.tobytes() == want[cn].tobytes(), cn
+        eng.debug_option("sqnet_budget_kb", 16)
+        try:
+            before = sa.lib().scrappie_hip_sqnet_launch_count()
+            cut = eng.predict_squiggle([refs[cn][0] for cn in names], model=name)
+            assert sa.lib().scrappie_hip_sqnet_launch_count() > before + 1
+            for cn, g in zip(names, cut):
+                assert g.tobytes() == want[cn].tobytes(), cn
+        finally:
+            eng.debug_option("sqnet_budget_kb", 0)
+        _tile_seams(name, "sweep", registered, eng, (wl - 1) // 2, slack=0)
 
 
 def test_rescale_is_libm_on_the_host(registered, eng):
