@@ -25,10 +25,11 @@
  *
  * The translation unit in parts (round 5; the kernels are templates in headers and are instantiated where they are launched, so
  * the engine stays ONE translation unit -- the parts are files of their own for reading, included below in this order):
- *   this file            switches, the engine's state (struct Slot: what exists once per launch group in flight), create / destroy
+ *   this file            launch_k / pick_int / pick_bool / StampBuf (how every kernel is launched), switches, the engine's state (struct Slot: what
+ *                        exists once per launch group in flight), create / destroy
  *   sh_eng_weights.inc   weights as the device wants them; the Model
  *   sh_eng_load.inc      .scrm container -> Model, settings, the ABI's planning functions
- *   sh_eng_launch.inc    launch-group construction, kernel dispatch helpers
+ *   sh_eng_launch.inc    launch-group construction; kernel dispatch helpers: a layer's sizes and switches -> the instantiation that runs
  *   sh_eng_pipeline.inc  run_pipeline: one launch group through its kernels, a function per stage
  *   sh_eng_groups.inc    run_device / collect / stitching, a call cut into launch groups
  *   sh_eng_batch.inc     helper engine for chain-bound reads, host-signal entry points, several GPUs
@@ -56,6 +57,7 @@
 #include <numeric>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 #include <chrono>
 #include <condition_variable>
@@ -76,7 +78,7 @@
 
 /* function attributes (dynamic LDS limit) are per device: remember for which devices a kernel has had its attribute set
  * (engines on several GPUs may share one process).  A real once per device: the thread that finds the attribute unset holds
- * the lock until hipFuncSetAttribute has returned (`if (auto turn = once.first()) HIPCHK(hipFuncSetAttribute(...));` -- the
+ * the lock until the call that sets it has returned (`if (auto turn = once.first()) HIPCHK(...);` in launch_k below -- the
  * turn lives to the end of the if statement), so a second engine on the same device -- the helper engine runs launch groups
  * on a host thread of its own -- cannot launch the kernel with more than 64 KB of dynamic LDS before the limit is raised. */
 struct DevOnce {
@@ -99,6 +101,60 @@ struct DevOnce {
         mu.lock();
         if (done.load(std::memory_order_acquire) & bit) { mu.unlock(); return Turn(nullptr, 0); }
         return Turn(this, bit);
+    }
+};
+
+/* The one place a kernel is launched with dynamic LDS.  K names the instantiation (`launch_k<k_gru_proj<6, 2, false>>(...)`), and every instantiation
+ * has a DevOnce of its own: attr_once<K>, which hangs on K alone, not on the types a launch passes its arguments as.  One rule for all kernels: a
+ * launch that asks for more than 48 KB raises K's limit to the device's 160 KB first, once per device and under the once's turn (above: a second engine's thread cannot launch K before the limit is up).  48 KB is the most conservative threshold
+ * the launchers ever used; those that used to set the limit at a smaller size as well no longer do, which changes nothing: the default limit covers
+ * such a launch.  Arguments are passed as given and converted where the kernel is called: a kernel's default arguments do not exist through K, so a
+ * launch spells them out.  Returns 0, or -1 through HIPCHK; the launch's own error is left to the caller's hipGetLastError, as with a plain launch. */
+template <auto K>
+static DevOnce &attr_once() { static DevOnce once; return once; }
+template <auto K, class... A>
+static int launch_k(dim3 grid, dim3 block, size_t lds, hipStream_t s, const A &...a) {
+    if (auto turn_ = attr_once<K>().first(lds > 48 * 1024))
+        HIPCHK(hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    hipLaunchKernelGGL(K, grid, block, lds, s, a...);
+    return 0;
+}
+
+/* Run-time values as template arguments.  pick_int<2, 4, 6>(v, rc, f): rc = f(int_c<V>()) for the V of the list that equals v; false (f not called,
+ * rc untouched) where none does, so that the caller words the refusal.  pick_bool(f, b...): f with std::true_type() or std::false_type() for every b,
+ * in their order; returns what f returns.  f is a generic lambda that takes the constants by value (`[&](auto nu) { return launch_k<k_gru<nu()>>(...); }`;
+ * a lambda nested in f names the value through a constexpr of f's, not through f's parameter).  Every V of the list, and both values of every b,
+ * instantiate f's body: a kernel family that uses part of a cross product leaves the rest out with `if constexpr`. */
+template <int V> using int_c = std::integral_constant<int, V>;
+template <int... Vs, class F>
+static bool pick_int(int v, int &rc, F &&f) {
+    return ((v == Vs && ((rc = f(int_c<Vs>())), true)) || ...);
+}
+template <class F>
+static int pick_bool(F &&f) { return f(); }
+template <class F, class... B>
+static int pick_bool(F &&f, bool b, B... rest) {
+    return b ? pick_bool([&](auto... c) { return f(std::true_type(), c...); }, rest...)
+             : pick_bool([&](auto... c) { return f(std::false_type(), c...); }, rest...);
+}
+
+/* Cycle stamps of an instrumented kernel form (development switches; tools/ab_stamp.sh and tools/profile_gru32.sh read the lines): a device buffer
+ * allocated on first use, and dump_on(k, ...): on the k-th call (k = 0: on every call) wait for the stream, bring `words` words back and hand them
+ * to print(const unsigned long long *).  One per stamped form, with static storage: single-threaded use, never freed. */
+struct StampBuf {
+    unsigned long long *d = nullptr;
+    int calls = 0;
+    unsigned long long *dev(size_t words) {
+        if (!d) (void)hipMalloc(&d, words * 8);
+        return d;
+    }
+    template <class P>
+    void dump_on(int k, hipStream_t s, size_t words, P &&print) {
+        if (k && ++calls != k) return;
+        (void)sh_stream_wait(s);
+        std::vector<unsigned long long> h(words);
+        (void)hipMemcpy(h.data(), d, words * 8, hipMemcpyDeviceToHost);
+        print(h.data());
     }
 };
 

@@ -77,19 +77,20 @@ static size_t dp_order(const std::vector<Rec> &rd, std::vector<size_t> &perm) {
 }
 
 /* one workgroup of nth threads per record: K_LDS over the first n_lds records with lds bytes of dynamic LDS, K_SCR over the rest with scr_lds;
- * forms[0] / forms[1] count the launches of either */
+ * forms[0] / forms[1] count the launches of either; 0, or -1 as launch_k says */
 template <auto K_LDS, auto K_SCR, class Args>
-static void dp_launch(hipStream_t s, const Args &a, size_t n_lds, size_t n, unsigned nth, size_t lds, size_t scr_lds, std::atomic<uint64_t> *forms) {
+static int dp_launch(hipStream_t s, const Args &a, size_t n_lds, size_t n, unsigned nth, size_t lds, size_t scr_lds, std::atomic<uint64_t> *forms) {
     if (n_lds) {
         forms[0].fetch_add(1, std::memory_order_relaxed);
-        hipLaunchKernelGGL(K_LDS, dim3((unsigned)n_lds), dim3(nth), lds, s, a);
+        if (launch_k<K_LDS>(dim3((unsigned)n_lds), dim3(nth), lds, s, a)) return -1;
     }
     if (n > n_lds) {                     /* the reads whose rows live in scratch: the records' tail */
         Args b = a;
         b.rd += n_lds; b.score += n_lds; b.final_state += n_lds;
         forms[1].fetch_add(1, std::memory_order_relaxed);
-        hipLaunchKernelGGL(K_SCR, dim3((unsigned)(n - n_lds)), dim3(nth), scr_lds, s, b);
+        if (launch_k<K_SCR>(dim3((unsigned)(n - n_lds)), dim3(nth), scr_lds, s, b)) return -1;
     }
+    return 0;
 }
 
 /* after the kernel: K_WALK (one thread per record) where paths are wanted, scores and paths to the host, and give(i, score, path) for every record in

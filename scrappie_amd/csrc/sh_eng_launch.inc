@@ -1,5 +1,6 @@
 /* sh_eng_launch.inc -- part of scrappie_hip.hip (one translation unit, included from there in this order; not compiled alone):
- * launch-group construction (tiles, metadata, schedules) and the kernel dispatch helpers. */
+ * launch-group construction (tiles, metadata, schedules) and the kernel dispatch helpers: which instantiation of a kernel family runs for a layer's
+ * sizes and switches, each launched through launch_k (scrappie_hip.hip). */
 
 /* ------------------------------------------------------------------ */
 /* launch-group construction                                            */
@@ -163,6 +164,9 @@ static int build_group(scrappie_hip_engine *e, Slot &sl, Model *m, const uint64_
 /* ------------------------------------------------------------------ */
 /* kernel dispatch helpers                                              */
 /* ------------------------------------------------------------------ */
+/* Every launch goes through launch_k (scrappie_hip.hip: the dynamic-LDS limit, once per device and instantiation); run-time sizes and flags become
+ * template arguments through pick_int / pick_bool, with a launch's argument list written once; the instrumented forms (STAMP = true, k_gru_conv_stamp)
+ * are named where their switch is tested and read back through a StampBuf. */
 template <int KQ>
 static int launch_affine_k(hipStream_t s, const float *in, float *out, const float *wf, const unsigned *wp, const float *bf,
                            long long ncb, int mtiles) {
@@ -170,14 +174,9 @@ static int launch_affine_k(hipStream_t s, const float *in, float *out, const flo
     long long gx = std::min<long long>((ncb + 3) / 4, 2048);
     if (gx < 1) gx = 1;
     dim3 grid((unsigned)gx, (unsigned)(mtiles / mt));
-    switch (mt) {
-    case 6: hipLaunchKernelGGL((k_affine<KQ, 6>), grid, dim3(256), 0, s, in, out, wf, wp, bf, ncb, mtiles); break;
-    case 4: hipLaunchKernelGGL((k_affine<KQ, 4>), grid, dim3(256), 0, s, in, out, wf, wp, bf, ncb, mtiles); break;
-    case 3: hipLaunchKernelGGL((k_affine<KQ, 3>), grid, dim3(256), 0, s, in, out, wf, wp, bf, ncb, mtiles); break;
-    case 2: hipLaunchKernelGGL((k_affine<KQ, 2>), grid, dim3(256), 0, s, in, out, wf, wp, bf, ncb, mtiles); break;
-    default: hipLaunchKernelGGL((k_affine<KQ, 1>), grid, dim3(256), 0, s, in, out, wf, wp, bf, ncb, mtiles); break;
-    }
-    return 0;
+    int rc = 0;
+    if (pick_int<6, 4, 3, 2, 1>(mt, rc, [&](auto m) { return launch_k<k_affine<KQ, m()>>(grid, dim3(256), 0, s, in, out, wf, wp, bf, ncb, mtiles); })) return rc;
+    return set_err("unsupported layer of %d m-tiles", mtiles);
 }
 
 template <int KQ>
@@ -185,14 +184,10 @@ static int launch_affine_lds_k(hipStream_t s, const float *in, float *out, const
                                long long ncb, int mtiles) {
     constexpr int NB = SH_AFF_NB, NTH = SH_AFF_NTH;
     const size_t lds = ((size_t)mtiles * KQ * 256 + (size_t)mtiles * 256) * 4 + 16;
-    static DevOnce attr_once;
-    if (auto turn_ = attr_once.first())
-        HIPCHK(hipFuncSetAttribute((const void *)k_affine_lds<KQ, NB, NTH>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     long long gx = std::min<long long>((ncb + (NTH / 64) * NB - 1) / ((NTH / 64) * NB), 256);
     if (gx < 1) gx = 1;
     /* column groups by fixed striding: measured 4 % faster here than the dynamic hand-out k_ff_lds uses */
-    hipLaunchKernelGGL((k_affine_lds<KQ, NB, NTH>), dim3((unsigned)gx), dim3(NTH), lds, s, in, out, wf, wp, bf, ncb, mtiles);
-    return 0;
+    return launch_k<k_affine_lds<KQ, NB, NTH>>(dim3((unsigned)gx), dim3(NTH), lds, s, in, out, wf, wp, bf, ncb, mtiles);
 }
 
 /* exact-fp32 MFMAs on the fp32 fragments whatever K: the projection of a layer whose weights are outside the split
@@ -203,46 +198,24 @@ static int launch_affine_f32_k(hipStream_t s, const float *in, float *out, const
     long long gx = std::min<long long>((ncb + 3) / 4, 2048);
     if (gx < 1) gx = 1;
     dim3 grid((unsigned)gx, (unsigned)(mtiles / mt));
-    switch (mt) {
-    case 6: hipLaunchKernelGGL((k_affine<KQ, 6, true>), grid, dim3(256), 0, s, in, out, wf, (const unsigned *)nullptr, bf, ncb, mtiles); break;
-    case 2: hipLaunchKernelGGL((k_affine<KQ, 2, true>), grid, dim3(256), 0, s, in, out, wf, (const unsigned *)nullptr, bf, ncb, mtiles); break;
-    default: hipLaunchKernelGGL((k_affine<KQ, 1, true>), grid, dim3(256), 0, s, in, out, wf, (const unsigned *)nullptr, bf, ncb, mtiles); break;
-    }
-    return 0;
+    int rc = 0;
+    if (pick_int<6, 2, 1>(mt, rc, [&](auto m) { return launch_k<k_affine<KQ, m(), true>>(grid, dim3(256), 0, s, in, out, wf, (const unsigned *)nullptr, bf, ncb, mtiles); })) return rc;
+    return set_err("unsupported layer of %d m-tiles", mtiles);
 }
 
 static int launch_affine(hipStream_t s, int K, const float *in, float *out, const float *wf, const unsigned *wp, const float *bf_nat,
                          const float *bf_acc, long long ncb, int mtiles, bool force_f32 = false) {
-    if (force_f32) {
-        switch (K / 16) {
-        case 2: return launch_affine_f32_k<2>(s, in, out, wf, bf_nat, ncb, mtiles);
-        case 4: return launch_affine_f32_k<4>(s, in, out, wf, bf_nat, ncb, mtiles);
-        case 6: return launch_affine_f32_k<6>(s, in, out, wf, bf_nat, ncb, mtiles);
-        case 8: return launch_affine_f32_k<8>(s, in, out, wf, bf_nat, ncb, mtiles);
-        default: break;            /* odd K / 16: the ordinary kernel is exact-fp32 already */
-        }
-    }
+    int rc = 0;
+    /* (odd K / 16: the ordinary kernel is exact-fp32 already) */
+    if (force_f32 && pick_int<2, 4, 6, 8>(K / 16, rc, [&](auto kq) { return launch_affine_f32_k<kq()>(s, in, out, wf, bf_nat, ncb, mtiles); })) return rc;
     if (K % 32 == 0 && (!wp || !bf_acc)) return set_err("layer weights were not cut into pieces (input size %d)", K);
     const float *bf = (K % 32 == 0) ? bf_acc : bf_nat;      /* split products start from the bias in accumulator units */
     /* big layers: LDS-resident weights, input read once */
     const size_t lds_need = ((size_t)mtiles * (K / 16) * 256 + (size_t)mtiles * 256) * 4;
-    if (mtiles >= 12 && lds_need <= 150 * 1024 && ncb >= 4096 && !tun().affine_reg) {
-        switch (K / 16) {
-        case 1: return launch_affine_lds_k<1>(s, in, out, wf, wp, bf, ncb, mtiles);
-        case 2: return launch_affine_lds_k<2>(s, in, out, wf, wp, bf, ncb, mtiles);
-        case 4: return launch_affine_lds_k<4>(s, in, out, wf, wp, bf, ncb, mtiles);
-        case 6: return launch_affine_lds_k<6>(s, in, out, wf, wp, bf, ncb, mtiles);
-        default: break;
-        }
-    }
-    switch (K / 16) {
-    case 1: return launch_affine_k<1>(s, in, out, wf, wp, bf, ncb, mtiles);
-    case 2: return launch_affine_k<2>(s, in, out, wf, wp, bf, ncb, mtiles);
-    case 4: return launch_affine_k<4>(s, in, out, wf, wp, bf, ncb, mtiles);
-    case 6: return launch_affine_k<6>(s, in, out, wf, wp, bf, ncb, mtiles);
-    case 8: return launch_affine_k<8>(s, in, out, wf, wp, bf, ncb, mtiles);
-    default: return set_err("unsupported layer input size %d (need 16, 32, 64, 96 or 128)", K);
-    }
+    if (mtiles >= 12 && lds_need <= 150 * 1024 && ncb >= 4096 && !tun().affine_reg &&
+        pick_int<1, 2, 4, 6>(K / 16, rc, [&](auto kq) { return launch_affine_lds_k<kq()>(s, in, out, wf, wp, bf, ncb, mtiles); })) return rc;
+    if (pick_int<1, 2, 4, 6, 8>(K / 16, rc, [&](auto kq) { return launch_affine_k<kq()>(s, in, out, wf, wp, bf, ncb, mtiles); })) return rc;
+    return set_err("unsupported layer input size %d (need 16, 32, 64, 96 or 128)", K);
 }
 
 template <int KQ>
@@ -252,115 +225,75 @@ static int launch_affine2_k(hipStream_t s, const float *inF, const float *inB, f
     if (gx < 1) gx = 1;
     /* S / 16 = 2, 4 or 6 m-tiles: two wave quartets per workgroup, each with half of them */
     const int mt = mtiles / 2;
-    if (mt * 2 != mtiles || mt > 3) return set_err("unsupported joining layer of %d m-tiles", mtiles);
-    dim3 grid((unsigned)gx);
-    switch (mt) {
-    case 3: hipLaunchKernelGGL((k_affine2_tanh<KQ, 3>), grid, dim3(512), 0, s, inF, inB, out, wF, wB, bf, ncb, mtiles); break;
-    case 2: hipLaunchKernelGGL((k_affine2_tanh<KQ, 2>), grid, dim3(512), 0, s, inF, inB, out, wF, wB, bf, ncb, mtiles); break;
-    default: hipLaunchKernelGGL((k_affine2_tanh<KQ, 1>), grid, dim3(512), 0, s, inF, inB, out, wF, wB, bf, ncb, mtiles); break;
-    }
-    return 0;
+    int rc = 0;
+    if (mt * 2 == mtiles &&
+        pick_int<3, 2, 1>(mt, rc, [&](auto m) { return launch_k<k_affine2_tanh<KQ, m()>>(dim3((unsigned)gx), dim3(512), 0, s, inF, inB, out, wF, wB, bf, ncb, mtiles); })) return rc;
+    return set_err("unsupported joining layer of %d m-tiles", mtiles);
 }
 
 static int launch_affine2(hipStream_t s, int K, const float *inF, const float *inB, float *out, const unsigned *wF, const unsigned *wB,
                           const float *bf, long long ncb, int mtiles) {
-    switch (K / 16) {
-    case 2: return launch_affine2_k<2>(s, inF, inB, out, wF, wB, bf, ncb, mtiles);
-    case 4: return launch_affine2_k<4>(s, inF, inB, out, wF, wB, bf, ncb, mtiles);
-    case 6: return launch_affine2_k<6>(s, inF, inB, out, wF, wB, bf, ncb, mtiles);
-    default: return set_err("unsupported bi-GRU size %d (need 32, 64 or 96)", K);
-    }
+    int rc = 0;
+    if (pick_int<2, 4, 6>(K / 16, rc, [&](auto kq) { return launch_affine2_k<kq()>(s, inF, inB, out, wF, wB, bf, ncb, mtiles); })) return rc;
+    return set_err("unsupported bi-GRU size %d (need 32, 64 or 96)", K);
 }
 
 static int launch_gru(hipStream_t s, int S, const float *xaff, float *out, const float *resid, const float *sW,
                       const float *sW2, const unsigned *sWp, const unsigned *sW2p, const ShMeta &md, int backward, size_t ntile, const ShGruLanes &lanes, int nwg,
                       bool force_f32 = false) {
+    const int NU = S / 16;
+    int rc = 0;
     /* production path: two lanes per workgroup walking the lane schedule (sh_sched.h) */
-    if (!tun().gru_single && !tun().gru_stamp && tun().gru_debug < 0 && S / 16 <= 6 && S % 32 == 0) {
+    if (!tun().gru_single && !tun().gru_stamp && tun().gru_debug < 0 && NU <= 6 && S % 32 == 0) {
         if (nwg <= 0) return 0;
         /* arrival counters of tiles cut between lanes: cleared before every launch */
         HIPCHK(hipMemsetAsync(lanes.flag, 0, (size_t)lanes.ntile * 4, s));
         dim3 lgrid((unsigned)nwg);
-        const int NU = S / 16;
-        const size_t lds = (size_t)2 * 2 * NU * 256 * 4;
         const bool stamp = tun().gru_lanes_stamp;
-        static unsigned long long *ldbg = nullptr;
-        static int lcalls = 0;
-        if (stamp && !ldbg) (void)hipMalloc(&ldbg, 4096 * 16 * 8 * 8);
         const bool f32_env = tun().gru_f32 || force_f32;
         if (!stamp && !f32_env) {                  /* production: split products */
             const size_t plds = (size_t)2 * 2 * (NU / 2) * 2 * 64 * 4 * 4;
-            switch (NU) {
-            case 2: hipLaunchKernelGGL((k_gru_split<2>), lgrid, dim3(256), plds, s, xaff, out, resid, sWp, sW2p, md, backward, lanes); break;
-            case 4: hipLaunchKernelGGL((k_gru_split<4>), lgrid, dim3(512), plds, s, xaff, out, resid, sWp, sW2p, md, backward, lanes); break;
-            default: hipLaunchKernelGGL((k_gru_split<6>), lgrid, dim3(768), plds, s, xaff, out, resid, sWp, sW2p, md, backward, lanes); break;
-            }
-            return 0;
+            if (pick_int<2, 4, 6>(NU, rc, [&](auto nu) { return launch_k<k_gru_split<nu()>>(lgrid, dim3(128 * nu()), plds, s, xaff, out, resid, sWp, sW2p, md, backward, lanes); })) return rc;
+            return set_err("unsupported GRU size %d (need 32, 64 or 96 here)", S);
         }
         /* SH_GRU_F32 / SH_GRU_LANES_STAMP: the exact-fp32 MFMA kernel (same schedule), kept as the reference the
-         * split products were measured against */
-        switch (NU) {
-        case 2: hipLaunchKernelGGL((k_gru_lanes<2, false>), lgrid, dim3(256), lds, s, xaff, out, resid, sW, sW2, md, backward, lanes, (unsigned long long *)nullptr); break;
-        case 4: hipLaunchKernelGGL((k_gru_lanes<4, false>), lgrid, dim3(512), lds, s, xaff, out, resid, sW, sW2, md, backward, lanes, (unsigned long long *)nullptr); break;
-        case 6:
+         * split products were measured against; the stamped form exists for S = 96 only */
+        const size_t lds = (size_t)2 * 2 * NU * 256 * 4;
+        static StampBuf st;
+        if (!pick_int<2, 4, 6>(NU, rc, [&](auto nu) {
 #ifdef SH_EXPERIMENTS
-            if (stamp) hipLaunchKernelGGL((k_gru_lanes<6, true>), lgrid, dim3(768), lds, s, xaff, out, resid, sW, sW2, md, backward, lanes, ldbg);
-            else
+            if constexpr (nu() == 6)
+                if (stamp) return launch_k<k_gru_lanes<6, true>>(lgrid, dim3(768), lds, s, xaff, out, resid, sW, sW2, md, backward, lanes, st.dev(4096 * 16 * 8));
 #endif
-            hipLaunchKernelGGL((k_gru_lanes<6, false>), lgrid, dim3(768), lds, s, xaff, out, resid, sW, sW2, md, backward, lanes, (unsigned long long *)nullptr);
-            break;
-        default: break;
-        }
-        if (stamp && NU == 6 && ++lcalls == 7) {
-            (void)sh_stream_wait(s);
-            std::vector<unsigned long long> h((size_t)nwg * 12 * 8);
-            (void)hipMemcpy(h.data(), ldbg, h.size() * 8, hipMemcpyDeviceToHost);
-            for (size_t g : {(size_t)nwg / 2}) for (int w = 0; w < 12; w++) {
-                unsigned long long *d = &h[(g * 12 + w) * 8];
-                fprintf(stderr, "gru lanes stamp wg %zu wave %2d: phase1 %.0f bar %.0f phase2 %.0f bar %.0f cycles/step (%llu steps)\n",
-                        g, w, d[0] / (double)d[4], d[1] / (double)d[4], d[2] / (double)d[4], d[3] / (double)d[4], d[4]);
-            }
-        }
-        return 0;
+            return launch_k<k_gru_lanes<nu(), false>>(lgrid, dim3(128 * nu()), lds, s, xaff, out, resid, sW, sW2, md, backward, lanes, (unsigned long long *)nullptr);
+            })) return set_err("unsupported GRU size %d (need 32, 64 or 96 here)", S);
+        if (stamp && NU == 6)
+            st.dump_on(7, s, (size_t)nwg * 12 * 8, [&](const unsigned long long *h) {
+                for (size_t g : {(size_t)nwg / 2}) for (int w = 0; w < 12; w++) {
+                    const unsigned long long *d = &h[(g * 12 + w) * 8];
+                    fprintf(stderr, "gru lanes stamp wg %zu wave %2d: phase1 %.0f bar %.0f phase2 %.0f bar %.0f cycles/step (%llu steps)\n",
+                            g, w, d[0] / (double)d[4], d[1] / (double)d[4], d[2] / (double)d[4], d[3] / (double)d[4], d[4]);
+                }
+            });
+        return rc;
     }
     /* other sizes, and the instrumented single-tile kernel (SH_GRU_SINGLE / SH_GRU_STAMP / SH_GRU_DEBUG) */
-    dim3 grid((unsigned)ntile);
-    const int NUx = S / 16;
     if (tun().gru_debug >= 0) backward |= tun().gru_debug << 8;
-    static unsigned long long *dbgbuf = nullptr;
-    if (tun().gru_stamp && !dbgbuf) { (void)hipMalloc(&dbgbuf, 4096 * 8 * 8 * 8); }
-    if (dbgbuf) {
-        static int calls = 0;
-        if (calls == 7) {   /* dump the stamps of an earlier launch */
-            (void)sh_stream_wait(s);
-            std::vector<unsigned long long> h(ntile * NUx * 8);
-            (void)hipMemcpy(h.data(), dbgbuf, h.size() * 8, hipMemcpyDeviceToHost);
+    static StampBuf st1;
+    unsigned long long *dbgbuf = tun().gru_stamp ? st1.dev(4096 * 8 * 8) : nullptr;
+    if (dbgbuf)         /* before the eighth launch: the stamps of an earlier one */
+        st1.dump_on(8, s, ntile * NU * 8, [&](const unsigned long long *h) {
             { unsigned long long first_end = ~0ull, mn = ~0ull, mx = 0; size_t late = 0;
-              for (size_t tl = 0; tl < ntile; tl++) { first_end = std::min(first_end, h[tl * NUx * 8 + 7]); mn = std::min(mn, h[tl * NUx * 8 + 6]); mx = std::max(mx, h[tl * NUx * 8 + 7]); }
-              for (size_t tl = 0; tl < ntile; tl++) if (h[tl * NUx * 8 + 6] >= first_end) late++;
+              for (size_t tl = 0; tl < ntile; tl++) { first_end = std::min(first_end, h[tl * NU * 8 + 7]); mn = std::min(mn, h[tl * NU * 8 + 6]); mx = std::max(mx, h[tl * NU * 8 + 7]); }
+              for (size_t tl = 0; tl < ntile; tl++) if (h[tl * NU * 8 + 6] >= first_end) late++;
               fprintf(stderr, "residency: %zu tiles, %zu started after the first one finished; span %.1f us\n", ntile, late, (mx - mn) / 100.0); }
             for (size_t tl : {size_t(0)}) for (int w = 0; w < 1; w++) {
-                unsigned long long *d = &h[(tl * NUx + w) * 8];
+                const unsigned long long *d = &h[(tl * NU + w) * 8];
                 fprintf(stderr, "stamp tile %zu wave %d: rgemm %.0f zgemm+valu %.0f bar1 %.0f gemm2+valu %.0f bar2 %.0f (cycles/step)\n", tl, w, d[0] / (double)d[5], d[1] / (double)d[5], d[2] / (double)d[5], d[3] / (double)d[5], d[4] / (double)d[5]);
             }
-        }
-        calls++;
-    }
-    const int NU = S / 16;
-    const size_t lds = 0;
-    switch (NU) {
-    case 2: hipLaunchKernelGGL((k_gru<2>), grid, dim3(128), lds, s, xaff, out, resid, sW, sW2, md, backward, dbgbuf); break;
-    case 4: hipLaunchKernelGGL((k_gru<4>), grid, dim3(256), lds, s, xaff, out, resid, sW, sW2, md, backward, dbgbuf); break;
-    case 6: hipLaunchKernelGGL((k_gru<6>), grid, dim3(384), lds, s, xaff, out, resid, sW, sW2, md, backward, dbgbuf); break;
-    case 8: {
-        static DevOnce attr_once;
-        if (auto turn_ = attr_once.first()) HIPCHK(hipFuncSetAttribute((const void *)k_gru<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((k_gru<8>), grid, dim3(512), lds, s, xaff, out, resid, sW, sW2, md, backward, dbgbuf);
-        break;
-    }
-    default: return set_err("unsupported GRU size %d (need 32, 64, 96 or 128)", S);
-    }
-    return 0;
+        });
+    if (pick_int<2, 4, 6, 8>(NU, rc, [&](auto nu) { return launch_k<k_gru<nu()>>(dim3((unsigned)ntile), dim3(64 * nu()), 0, s, xaff, out, resid, sW, sW2, md, backward, dbgbuf); })) return rc;
+    return set_err("unsupported GRU size %d (need 32, 64, 96 or 128)", S);
 }
 
 #ifndef SH_FFL_NB
@@ -383,62 +316,38 @@ static int launch_ff_lds_k(hipStream_t s, const float *in, float *E, float *sums
     constexpr int NB = SH_FFL_NB, NTH = SH_FFL_NTH;
     const int mtp = ff_mtp(KQ, mtiles);
     const size_t lds = (size_t)mtp * ((size_t)KQ * 256 + 256) * 4 + 16;
-    static DevOnce attr_once;
-    if (auto turn_ = attr_once.first()) {
-        HIPCHK(hipFuncSetAttribute((const void *)k_ff_lds<KQ, NB, NTH, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHK(hipFuncSetAttribute((const void *)k_ff_lds<KQ, NB, NTH, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
     long long gx = std::min<long long>((ncb + (NTH / 64) * NB - 1) / ((NTH / 64) * NB), ncu);
     if (gx < 1) gx = 1;
-    if (out_div != 1.0f) hipLaunchKernelGGL((k_ff_lds<KQ, NB, NTH, true>), dim3((unsigned)gx), dim3(NTH), lds, s, in, E, sums, wf, bf, ncb, mtiles, mtp, NS, in_div, out_div, (unsigned long long *)nullptr);
-    else {
-        const bool stamp = tun().ff_stamp;
-        static unsigned long long *fdbg = nullptr;
-        if (stamp && !fdbg) (void)hipMalloc(&fdbg, 16 * 8 * 8);
-        hipLaunchKernelGGL((k_ff_lds<KQ, NB, NTH, false>), dim3((unsigned)gx), dim3(NTH), lds, s, in, E, sums, wf, bf, ncb, mtiles, mtp, NS, in_div, out_div, fdbg);
-        if (stamp) {
-            (void)sh_stream_wait(s);
-            unsigned long long h[NTH / 64 * 8];
-            (void)hipMemcpy(h, fdbg, sizeof h, hipMemcpyDeviceToHost);
+    const bool dv = out_div != 1.0f;
+    const bool stamp = tun().ff_stamp && !dv;      /* cycle stamps of every launch on stderr (tuning aid): the form without the division only */
+    static StampBuf st;
+    unsigned long long *dbg = stamp ? st.dev(16 * 8) : nullptr;
+    if (pick_bool([&](auto d) { return launch_k<k_ff_lds<KQ, NB, NTH, d()>>(dim3((unsigned)gx), dim3(NTH), lds, s, in, E, sums, wf, bf, ncb, mtiles, mtp, NS, in_div, out_div, dbg); }, dv))
+        return -1;
+    if (stamp)
+        st.dump_on(0, s, NTH / 64 * 8, [](const unsigned long long *h) {
             for (int w = 0; w < NTH / 64; w++)
                 fprintf(stderr, "ff stamp wave %d: fill %llu  B-load %llu  tiles %llu  sums %llu cycles; %llu m-tiles -> %.0f cycles per m-tile\n", w, h[w * 8], h[w * 8 + 1], h[w * 8 + 2], h[w * 8 + 3], h[w * 8 + 4], (double)h[w * 8 + 2] / (double)h[w * 8 + 4]);
-        }
-    }
+        });
     return 0;
 }
 
 static int launch_ff(hipStream_t s, int S, const float *in, float *E, float *sums, const unsigned *wf, const float *bf,
                      long long ncb, int mtiles, int NS, float in_div, float out_div, int ncu) {
+    int rc = 0;
     /* large batches: weight fragments in LDS (k_ff_lds); small ones: one wave per column group streaming them from L2 */
-    if (ncb >= 8192 && !tun().ff_reg) {
-        switch (S / 16) {
-        case 2: return launch_ff_lds_k<2>(s, in, E, sums, wf, bf, ncb, mtiles, NS, in_div, out_div, ncu);
-        case 4: return launch_ff_lds_k<4>(s, in, E, sums, wf, bf, ncb, mtiles, NS, in_div, out_div, ncu);
-        case 6: return launch_ff_lds_k<6>(s, in, E, sums, wf, bf, ncb, mtiles, NS, in_div, out_div, ncu);
-        default: break;
-        }
-    }
+    if (ncb >= 8192 && !tun().ff_reg &&
+        pick_int<2, 4, 6>(S / 16, rc, [&](auto kq) { return launch_ff_lds_k<kq()>(s, in, E, sums, wf, bf, ncb, mtiles, NS, in_div, out_div, ncu); })) return rc;
     constexpr int NB = SH_FF_NB;
     const int mtp = ff_mtp(S / 16, mtiles);
-    const bool dv = out_div != 1.0f;
     const long long gx = (ncb + 4 * NB - 1) / (4 * NB);
     dim3 grid((unsigned)std::max<long long>(gx, 1));
-    switch (S / 16) {
-    case 2: if (dv) hipLaunchKernelGGL((k_ff_exp<2, NB, true>), grid, dim3(256), 0, s, in, E, sums, wf, bf, ncb, mtiles, mtp, NS, in_div, out_div);
-            else hipLaunchKernelGGL((k_ff_exp<2, NB, false>), grid, dim3(256), 0, s, in, E, sums, wf, bf, ncb, mtiles, mtp, NS, in_div, out_div);
-            break;
-    case 4: if (dv) hipLaunchKernelGGL((k_ff_exp<4, NB, true>), grid, dim3(256), 0, s, in, E, sums, wf, bf, ncb, mtiles, mtp, NS, in_div, out_div);
-            else hipLaunchKernelGGL((k_ff_exp<4, NB, false>), grid, dim3(256), 0, s, in, E, sums, wf, bf, ncb, mtiles, mtp, NS, in_div, out_div);
-            break;
-    case 6: if (dv) hipLaunchKernelGGL((k_ff_exp<6, NB, true>), grid, dim3(256), 0, s, in, E, sums, wf, bf, ncb, mtiles, mtp, NS, in_div, out_div);
-            else hipLaunchKernelGGL((k_ff_exp<6, NB, false>), grid, dim3(256), 0, s, in, E, sums, wf, bf, ncb, mtiles, mtp, NS, in_div, out_div);
-            break;
-    case 8: if (dv) hipLaunchKernelGGL((k_ff_exp<8, NB, true>), grid, dim3(256), 0, s, in, E, sums, wf, bf, ncb, mtiles, mtp, NS, in_div, out_div);
-            else hipLaunchKernelGGL((k_ff_exp<8, NB, false>), grid, dim3(256), 0, s, in, E, sums, wf, bf, ncb, mtiles, mtp, NS, in_div, out_div);
-            break;
-    default: return set_err("unsupported size %d", S);
-    }
-    return 0;
+    if (pick_int<2, 4, 6, 8>(S / 16, rc, [&](auto kq) {
+            constexpr int KQ = kq();
+            return pick_bool([&](auto dv) { return launch_k<k_ff_exp<KQ, NB, dv()>>(grid, dim3(256), 0, s, in, E, sums, wf, bf, ncb, mtiles, mtp, NS, in_div, out_div); },
+                             out_div != 1.0f);
+        })) return rc;
+    return set_err("unsupported size %d", S);
 }
 
 /* projection + recurrence in one kernel (k_gru_proj): layer input [ncb][S/16][256] -> layer output, the gate
@@ -486,37 +395,21 @@ static int launch_gru_conv(hipStream_t s, int kst, int act, float *out, const un
     HIPCHK(hipMemsetAsync(lanes.flag, 0, (size_t)lanes.ntile * 4, s));
     const size_t lds = (two ? 2 : 1) * ((size_t)4 * 3 * 2 * 64 * 4 + (size_t)2 * 3 * 6 * 256) * 4;
     dim3 grid((unsigned)nwg);
-#define CONVG1(NTv, KSTv, ACTv)                                                                                               \
-    {                                                                                                                        \
-        static DevOnce attr_once;                                                                                            \
-        if (auto turn_ = attr_once.first(lds > 48 * 1024))                                                                            \
-            HIPCHK(hipFuncSetAttribute((const void *)k_gru_conv<NTv, KSTv, ACTv>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-        hipLaunchKernelGGL((k_gru_conv<NTv, KSTv, ACTv>), grid, dim3(768), lds, s, out, iW, ib, sW, sW2, md, backward, lanes, cf); \
-    }
-#define CONVG(NTv) { if (kst == 3) { if (act) CONVG1(NTv, 3, 1) else CONVG1(NTv, 3, 0) } else { if (act) CONVG1(NTv, 5, 1) else CONVG1(NTv, 5, 0) } }
     if (tun().proj_stamp && two && kst == 3 && !act) {       /* cycle stamps of one launch on stderr (tuning aid) */
-        static unsigned long long *pdbg = nullptr;
-        static int calls = 0;
-        if (!pdbg) (void)hipMalloc(&pdbg, 1024 * 12 * 16 * 8);
-        static DevOnce once;
-        if (auto turn_ = once.first()) HIPCHK(hipFuncSetAttribute((const void *)k_gru_conv_stamp<2, 3, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        hipLaunchKernelGGL((k_gru_conv_stamp<2, 3, 0>), grid, dim3(768), lds, s, out, iW, ib, sW, sW2, md, backward, lanes, cf, pdbg);
-        if (++calls == 3) {
-            (void)sh_stream_wait(s);
-            std::vector<unsigned long long> h((size_t)nwg * 12 * 16);
-            (void)hipMemcpy(h.data(), pdbg, h.size() * 8, hipMemcpyDeviceToHost);
+        static StampBuf st;
+        if (launch_k<k_gru_conv_stamp<2, 3, 0>>(grid, dim3(768), lds, s, out, iW, ib, sW, sW2, md, backward, lanes, cf, st.dev(1024 * 12 * 16))) return -1;
+        st.dump_on(3, s, (size_t)nwg * 12 * 16, [&](const unsigned long long *h) {
             for (int w = 0; w < 12; w++) {
-                unsigned long long *d = &h[((size_t)(nwg / 2) * 12 + w) * 16];
+                const unsigned long long *d = &h[((size_t)(nwg / 2) * 12 + w) * 16];
                 fprintf(stderr, "conv-layer stamp wave %2d (%s): A %.0f bar %.0f B %.0f bar %.0f cycles per double step (%llu steps); chunk+fetch part of B (projection) / reads+MFMA issue (recurrence) %.0f\n", w,
                         w < 6 ? "recurrence" : "projection", d[0] / (double)d[4], d[1] / (double)d[4], d[2] / (double)d[4], d[3] / (double)d[4], d[4], d[5] / (double)d[4]);
             }
-        }
+        });
         return 0;
     }
-    if (two) CONVG(2) else CONVG(1)
-#undef CONVG
-#undef CONVG1
-    return 0;
+    return pick_bool([&](auto t2, auto k3, auto ac) {
+        return launch_k<k_gru_conv<t2() ? 2 : 1, k3() ? 3 : 5, ac() ? 1 : 0>>(grid, dim3(768), lds, s, out, iW, ib, sW, sW2, md, backward, lanes, cf);
+    }, two, kst == 3, act != 0);
 }
 #endif
 static int launch_gru_proj(hipStream_t s, int S, const float *in, float *out, const float *resid, const unsigned *iW, const float *ib,
@@ -533,147 +426,85 @@ static int launch_gru_proj(hipStream_t s, int S, const float *in, float *out, co
     /* residual layers: + the ring of three input columns per tile slot, wherever it fits (gru_proj_body's RLDS, the same test) */
     if (resid && SH_RESID_LDS && lds + (size_t)(two ? 2 : 1) * 3 * NU * 256 * 4 <= 160 * 1024) lds += (size_t)(two ? 2 : 1) * 3 * NU * 256 * 4;
     dim3 grid((unsigned)nwg);
-#define PROJ_LAUNCH1(NUv, NTv, RSv)                                                                                          \
-    {                                                                                                                        \
-        static DevOnce attr_once;                                                                                            \
-        if (auto turn_ = attr_once.first(lds > 48 * 1024))                                                                            \
-            HIPCHK(hipFuncSetAttribute((const void *)k_gru_proj<NUv, NTv, RSv>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-        hipLaunchKernelGGL((k_gru_proj<NUv, NTv, RSv>), grid, dim3(128 * NUv), lds, s, in, out, resid, iW, ib, sW, sW2, md, backward, lanes); \
-    }
-#define PROJ_LAUNCH1R(NUv, NTv)                                                                                              \
-    {                                                                                                                        \
-        static DevOnce attr_once;                                                                                            \
-        if (auto turn_ = attr_once.first(lds > 48 * 1024))                                                                   \
-            HIPCHK(hipFuncSetAttribute((const void *)k_gru_proj_res<NUv, NTv>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-        hipLaunchKernelGGL((k_gru_proj_res<NUv, NTv>), grid, dim3(128 * NUv), lds, s, in, out, resid, iW, ib, sW, sW2, md, backward, lanes); \
-    }
-#define PROJ_LAUNCH(NUv, NTv) { if (resid) PROJ_LAUNCH1R(NUv, NTv) else PROJ_LAUNCH1(NUv, NTv, false) }
+    unsigned long long *const no_dbg = nullptr;
+    int rc = 0;
 #ifdef SH_EXPERIMENTS
     /* S = 96, two tiles per workgroup: the form with the matrix work and the elementwise work on different waves (k_gru_mx, sh_gru_mx.h);
      * measured 6 % slower than k_gru_proj (profiles/r5_gru_mx.txt), so it runs only on SH_GRU_MX=1, and only in the experiments build */
     static const bool mx_on = [] { const char *v = getenv("SH_GRU_MX"); return v && atoi(v) != 0; }();
     if (mx_on && NU == 6 && two) {
-#define MX_LAUNCH(RSv)                                                                                                       \
-    {                                                                                                                        \
-        static DevOnce attr_once;                                                                                            \
-        if (auto turn_ = attr_once.first())                                                                                  \
-            HIPCHK(hipFuncSetAttribute((const void *)k_gru_mx<RSv>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-        hipLaunchKernelGGL((k_gru_mx<RSv>), grid, dim3(1024), lds, s, in, out, resid, iW, ib, sW, sW2, md, backward, lanes); \
-    }
         static const bool mx_stamp = getenv("SH_MX_STAMP") != nullptr;      /* cycle stamps of the seventh launch on stderr (tuning aid) */
         if (mx_stamp && !resid) {
-            static unsigned long long *mdbg = nullptr;
-            static int mcalls = 0;
-            if (!mdbg) (void)hipMalloc(&mdbg, (size_t)1024 * 16 * 10 * 8);
-            static DevOnce once;
-            if (auto turn_ = once.first()) HIPCHK(hipFuncSetAttribute((const void *)k_gru_mx<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            hipLaunchKernelGGL((k_gru_mx<false, true>), grid, dim3(1024), lds, s, in, out, resid, iW, ib, sW, sW2, md, backward, lanes, mdbg);
-            if (++mcalls == 7) {
-                (void)sh_stream_wait(s);
-                std::vector<unsigned long long> hb((size_t)nwg * 16 * 10);
-                (void)hipMemcpy(hb.data(), mdbg, hb.size() * 8, hipMemcpyDeviceToHost);
+            static StampBuf st;
+            if (launch_k<k_gru_mx<false, true>>(grid, dim3(1024), lds, s, in, out, resid, iW, ib, sW, sW2, md, backward, lanes, st.dev((size_t)1024 * 16 * 10))) return -1;
+            st.dump_on(7, s, (size_t)nwg * 16 * 10, [&](const unsigned long long *hb) {
                 for (int w = 0; w < 16; w++) {
                     const unsigned long long *d = &hb[((size_t)(nwg / 2) * 16 + w) * 10];
                     const double n = (double)std::max<unsigned long long>(d[8], 1);
                     fprintf(stderr, "mx stamp wave %2d (%s): P1 %.0f +bar %.0f | P2 %.0f +bar %.0f | P3 %.0f +bar %.0f | P4 %.0f +bar %.0f cycles per double step (%llu steps)\n", w,
                             w < 6 ? "recurrence " : w < 12 ? "projection " : "elementwise", d[0] / n, d[1] / n, d[2] / n, d[3] / n, d[4] / n, d[5] / n, d[6] / n, d[7] / n, d[8]);
                 }
-            }
+            });
             return 0;
         }
-        if (resid) MX_LAUNCH(true) else MX_LAUNCH(false)
-#undef MX_LAUNCH
+        if (pick_bool([&](auto rs) { return launch_k<k_gru_mx<rs()>>(grid, dim3(1024), lds, s, in, out, resid, iW, ib, sW, sW2, md, backward, lanes, no_dbg); }, resid != nullptr))
+            return -1;
         HIPCHK(hipGetLastError());
         return 0;
     }
-    const bool stamp = tun().proj_stamp;     /* cycle stamps of one launch on stderr (tuning aid) */
+    const bool stamp = tun().proj_stamp && NU == 6 && two && !resid;     /* cycle stamps of one launch on stderr (tuning aid) */
     const bool free_run = SH_GRU_FREE_DEFAULT ? !tun().gru_barrier : tun().gru_free;
     if (free_run) {
         /* no s_barrier in the step loop: projection team free running on a ring of three blocks (k_gru_free) */
         const size_t flds = (two ? 2 : 1) * ((size_t)4 * (NU / 2) * 2 * 64 * 4 + (size_t)3 * 3 * NU * 256) * 4 + 64;
-#define FREE_LAUNCH1(NUv, NTv, RSv, STv, DBG)                                                                                \
-    {                                                                                                                        \
-        static DevOnce attr_once;                                                                                            \
-        if (auto turn_ = attr_once.first(flds > 48 * 1024))                                                                           \
-            HIPCHK(hipFuncSetAttribute((const void *)k_gru_free<NUv, NTv, RSv, STv>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-        hipLaunchKernelGGL((k_gru_free<NUv, NTv, RSv, STv>), grid, dim3(128 * NUv), flds, s, in, out, resid, iW, ib, sW, sW2, md, backward, lanes, DBG); \
-    }
-#define FREE_LAUNCH(NUv, NTv) { if (resid) FREE_LAUNCH1(NUv, NTv, true, false, (unsigned long long *)nullptr) else FREE_LAUNCH1(NUv, NTv, false, false, (unsigned long long *)nullptr) }
-        if (stamp && NU == 6 && two && !resid) {
-            static unsigned long long *fdbg = nullptr;
-            static int fcalls = 0;
-            if (!fdbg) (void)hipMalloc(&fdbg, 1024 * 12 * 16 * 8);
-            FREE_LAUNCH1(6, 2, false, true, fdbg)
-            if (++fcalls == 7) {
-                (void)sh_stream_wait(s);
-                std::vector<unsigned long long> h((size_t)nwg * 12 * 16);
-                (void)hipMemcpy(h.data(), fdbg, h.size() * 8, hipMemcpyDeviceToHost);
+        if (stamp) {
+            static StampBuf st;
+            if (launch_k<k_gru_free<6, 2, false, true>>(grid, dim3(768), flds, s, in, out, resid, iW, ib, sW, sW2, md, backward, lanes, st.dev(1024 * 12 * 16))) return -1;
+            st.dump_on(7, s, (size_t)nwg * 12 * 16, [&](const unsigned long long *h) {
                 for (int w = 0; w < 12; w++) {
-                    unsigned long long *d = &h[((size_t)(nwg / 2) * 12 + w) * 16];
+                    const unsigned long long *d = &h[((size_t)(nwg / 2) * 12 + w) * 16];
                     if (w < 6) fprintf(stderr, "free stamp wave %2d (recurrence): work %.0f, waiting for gate inputs %.0f, for r*h of all waves %.0f, for h of all waves %.0f cycles per double step (%llu steps)\n",
                                        w, d[0] / (double)d[4], d[1] / (double)d[4], d[2] / (double)d[4], d[3] / (double)d[4], d[4]);
                     else fprintf(stderr, "free stamp wave %2d (projection): work %.0f, waiting for the column's pieces %.0f, for a free ring slot %.0f cycles per double step (%llu steps)\n",
                                  w, d[0] / (double)d[4], d[1] / (double)d[4], d[2] / (double)d[4], d[4]);
                 }
-            }
+            });
             return 0;
         }
-        if (two) {
-            switch (NU) {
-            case 2: FREE_LAUNCH(2, 2) break;
-            case 4: FREE_LAUNCH(4, 2) break;
-            default: FREE_LAUNCH(6, 2) break;
-            }
-        } else {
-            switch (NU) {
-            case 2: FREE_LAUNCH(2, 1) break;
-            case 4: FREE_LAUNCH(4, 1) break;
-            default: FREE_LAUNCH(6, 1) break;
-            }
-        }
-#undef FREE_LAUNCH1
-#undef FREE_LAUNCH
-        return 0;
+        if (pick_int<2, 4, 6>(NU, rc, [&](auto nu) {
+                constexpr int N = nu();
+                return pick_bool([&](auto t2, auto rs) {
+                    return launch_k<k_gru_free<N, t2() ? 2 : 1, rs(), false>>(grid, dim3(128 * N), flds, s, in, out, resid, iW, ib, sW, sW2, md, backward, lanes, no_dbg);
+                }, two, resid != nullptr);
+            })) return rc;
+        return set_err("unsupported GRU size %d (need 32, 64 or 96 here)", S);
     }
-    if (stamp && NU == 6 && two && !resid) {
-        static unsigned long long *pdbg = nullptr;
-        static int calls = 0;
-        if (!pdbg) (void)hipMalloc(&pdbg, 1024 * 12 * 16 * 8);
-        static DevOnce once;
-        if (auto turn_ = once.first()) HIPCHK(hipFuncSetAttribute((const void *)k_gru_proj<6, 2, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        hipLaunchKernelGGL((k_gru_proj<6, 2, false, true>), grid, dim3(768), lds, s, in, out, resid, iW, ib, sW, sW2, md, backward, lanes, pdbg);
-        if (++calls == 7) {
-            (void)sh_stream_wait(s);
-            std::vector<unsigned long long> h((size_t)nwg * 12 * 16);
-            (void)hipMemcpy(h.data(), pdbg, h.size() * 8, hipMemcpyDeviceToHost);
+    if (stamp) {
+        static StampBuf st;
+        if (launch_k<k_gru_proj<6, 2, false, true>>(grid, dim3(768), lds, s, in, out, resid, iW, ib, sW, sW2, md, backward, lanes, st.dev(1024 * 12 * 16))) return -1;
+        st.dump_on(7, s, (size_t)nwg * 12 * 16, [&](const unsigned long long *h) {
             for (int w = 0; w < 12; w++) {
-                unsigned long long *d = &h[((size_t)(nwg / 2) * 12 + w) * 16];
+                const unsigned long long *d = &h[((size_t)(nwg / 2) * 12 + w) * 16];
                 fprintf(stderr, "proj stamp wave %2d (%s): A %.0f bar %.0f B %.0f bar %.0f cycles per double step (%llu steps)", w, w < 6 ? "recurrence" : "projection",
                         d[0] / (double)d[4], d[1] / (double)d[4], d[2] / (double)d[4], d[3] / (double)d[4], d[4]);
                 if (w < 6) fprintf(stderr, "; inside B: reads+MFMA issue %.0f, logistic z %.0f, tanh+blend %.0f, store+bookkeeping %.0f, cut+publish %.0f",
                                    d[5] / (double)d[4], d[6] / (double)d[4], d[7] / (double)d[4], d[8] / (double)d[4], d[9] / (double)d[4]);
                 fprintf(stderr, "\n");
             }
-        }
+        });
         return 0;
     }
 #endif
-    if (two) {
-        switch (NU) {
-        case 2: PROJ_LAUNCH(2, 2) break;
-        case 4: PROJ_LAUNCH(4, 2) break;
-        default: PROJ_LAUNCH(6, 2) break;
-        }
-    } else {
-        switch (NU) {
-        case 2: PROJ_LAUNCH(2, 1) break;
-        case 4: PROJ_LAUNCH(4, 1) break;
-        default: PROJ_LAUNCH(6, 1) break;
-        }
-    }
-#undef PROJ_LAUNCH1
-#undef PROJ_LAUNCH
-    return 0;
+    /* residual layers have a kernel of their own (k_gru_proj_res: another register budget), without the stamps' argument */
+    if (pick_int<2, 4, 6>(NU, rc, [&](auto nu) {
+            constexpr int N = nu();
+            return pick_bool([&](auto t2) {
+                constexpr int NT = t2() ? 2 : 1;
+                if (resid) return launch_k<k_gru_proj_res<N, NT>>(grid, dim3(128 * N), lds, s, in, out, resid, iW, ib, sW, sW2, md, backward, lanes);
+                return launch_k<k_gru_proj<N, NT, false>>(grid, dim3(128 * N), lds, s, in, out, resid, iW, ib, sW, sW2, md, backward, lanes, no_dbg);
+            }, two);
+        })) return rc;
+    return set_err("unsupported GRU size %d (need 32, 64 or 96 here)", S);
 }
 
 #ifdef SH_EXPERIMENTS
@@ -686,6 +517,7 @@ static int use_gru32(const scrappie_hip_engine *e) {      /* 0: 16-read tiles; 1
     const char *v = getenv("SH_GRU32");
     return (v && atoi(v) == 2) ? 2 : (SH_GRU32_DEFAULT ? SH_GRU32_DEFAULT : 1);
 }
+static const char *const g32_role[8] = {"R0 chain", "R1 chain", "R2 chain", "C cand-proj", "G0 z/r", "G1 z/r", "G2 z/r", "L loader"};
 /* one recurrent layer of S = 96 on tiles of 32 reads (k_gru_proj32, sh_gru32.h) */
 static int launch_gru_proj32x2(hipStream_t s, const float *in, float *out, bool resid, const unsigned *iW, const float *ib, const unsigned *sW,
                                const unsigned *sW2, const ShMeta &md, int backward, const ShGruPairs &pairs, int nwg, size_t ntile) {
@@ -693,35 +525,19 @@ static int launch_gru_proj32x2(hipStream_t s, const float *in, float *out, bool 
     HIPCHK(hipMemsetAsync(pairs.flag, 0, ntile * 4, s));
     const size_t lds = (size_t)SH_G32X2_LDS_WORDS * 4;
     dim3 grid((unsigned)nwg);
-#define G32X2_LAUNCH(RSv, STv, DBG)                                                                                           \
-    {                                                                                                                        \
-        static DevOnce attr_once;                                                                                            \
-        if (auto turn_ = attr_once.first())                                                                                               \
-            HIPCHK(hipFuncSetAttribute((const void *)k_gru_proj32x2<RSv, STv>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-        hipLaunchKernelGGL((k_gru_proj32x2<RSv, STv>), grid, dim3(512), lds, s, in, out, iW, ib, sW, sW2, md, backward, pairs, DBG); \
-    }
     if (tun().gru32_stamp && !resid) {
-        static unsigned long long *pdbg = nullptr;
-        static int calls = 0;
-        if (!pdbg) (void)hipMalloc(&pdbg, 1024 * 8 * 16 * 8);
-        G32X2_LAUNCH(false, true, pdbg)
-        if (++calls == 7) {
-            (void)sh_stream_wait(s);
-            std::vector<unsigned long long> h((size_t)nwg * 8 * 16);
-            (void)hipMemcpy(h.data(), pdbg, h.size() * 8, hipMemcpyDeviceToHost);
-            static const char *role[8] = {"R0 chain", "R1 chain", "R2 chain", "C cand-proj", "G0 z/r", "G1 z/r", "G2 z/r", "L loader"};
+        static StampBuf st;
+        if (launch_k<k_gru_proj32x2<false, true>>(grid, dim3(512), lds, s, in, out, iW, ib, sW, sW2, md, backward, pairs, st.dev(1024 * 8 * 16))) return -1;
+        st.dump_on(7, s, (size_t)nwg * 8 * 16, [&](const unsigned long long *h) {
             for (int w = 0; w < 8; w++) {
-                unsigned long long *d = &h[((size_t)(nwg / 2) * 8 + w) * 16];
-                fprintf(stderr, "gru32x2 stamp wave %d (%s): work %.0f bar %.0f cycles per interval (%llu intervals = one tile-step of 32 reads each)\n", w, role[w],
+                const unsigned long long *d = &h[((size_t)(nwg / 2) * 8 + w) * 16];
+                fprintf(stderr, "gru32x2 stamp wave %d (%s): work %.0f bar %.0f cycles per interval (%llu intervals = one tile-step of 32 reads each)\n", w, g32_role[w],
                         d[0] / (double)d[4], d[1] / (double)d[4], d[4]);
             }
-        }
+        });
         return 0;
     }
-    if (resid) G32X2_LAUNCH(true, false, (unsigned long long *)nullptr)
-    else G32X2_LAUNCH(false, false, (unsigned long long *)nullptr)
-#undef G32X2_LAUNCH
-    return 0;
+    return pick_bool([&](auto rs) { return launch_k<k_gru_proj32x2<rs(), false>>(grid, dim3(512), lds, s, in, out, iW, ib, sW, sW2, md, backward, pairs, (unsigned long long *)nullptr); }, resid);
 }
 static int launch_gru_proj32(hipStream_t s, const float *in, float *out, bool resid, const unsigned *iW, const float *ib, const unsigned *sW,
                              const unsigned *sW2, const ShMeta &md, int backward, const ShGruPairs &pairs, int nwg, size_t ntile) {
@@ -729,38 +545,22 @@ static int launch_gru_proj32(hipStream_t s, const float *in, float *out, bool re
     HIPCHK(hipMemsetAsync(pairs.flag, 0, ntile * 4, s));
     const size_t lds = (size_t)SH_G32_LDS_WORDS * 4;
     dim3 grid((unsigned)nwg);
-#define G32_LAUNCH(RSv, STv, DBG)                                                                                             \
-    {                                                                                                                        \
-        static DevOnce attr_once;                                                                                            \
-        if (auto turn_ = attr_once.first())                                                                                               \
-            HIPCHK(hipFuncSetAttribute((const void *)k_gru_proj32<RSv, STv>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-        hipLaunchKernelGGL((k_gru_proj32<RSv, STv>), grid, dim3(512), lds, s, in, out, iW, ib, sW, sW2, md, backward, pairs, DBG); \
-    }
     if (tun().gru32_stamp && !resid) {       /* cycle stamps of one launch on stderr (tuning aid) */
-        static unsigned long long *pdbg = nullptr;
-        static int calls = 0;
-        if (!pdbg) (void)hipMalloc(&pdbg, 1024 * 8 * 16 * 8);
-        G32_LAUNCH(false, true, pdbg)
-        if (++calls == 7) {
-            (void)sh_stream_wait(s);
-            std::vector<unsigned long long> h((size_t)nwg * 8 * 16);
-            (void)hipMemcpy(h.data(), pdbg, h.size() * 8, hipMemcpyDeviceToHost);
-            static const char *role[8] = {"R0 chain", "R1 chain", "R2 chain", "C cand-proj", "G0 z/r", "G1 z/r", "G2 z/r", "L loader"};
+        static StampBuf st;
+        if (launch_k<k_gru_proj32<false, true>>(grid, dim3(512), lds, s, in, out, iW, ib, sW, sW2, md, backward, pairs, st.dev(1024 * 8 * 16))) return -1;
+        st.dump_on(7, s, (size_t)nwg * 8 * 16, [&](const unsigned long long *h) {
             for (int w = 0; w < 8; w++) {
-                unsigned long long *d = &h[((size_t)(nwg / 2) * 8 + w) * 16];
-                fprintf(stderr, "gru32 stamp wave %d (%s): A %.0f bar %.0f B %.0f bar %.0f cycles per step (%llu steps)", w, role[w],
+                const unsigned long long *d = &h[((size_t)(nwg / 2) * 8 + w) * 16];
+                fprintf(stderr, "gru32 stamp wave %d (%s): A %.0f bar %.0f B %.0f bar %.0f cycles per step (%llu steps)", w, g32_role[w],
                         d[0] / (double)d[4], d[1] / (double)d[4], d[2] / (double)d[4], d[3] / (double)d[4], d[4]);
                 if (w < 3) fprintf(stderr, "; A: reads+r products %.0f, logistic*h %.0f, cut+write %.0f; B: reads+candidate products %.0f, z/tanh/blend %.0f, store %.0f, cut+write %.0f",
                                    d[5] / (double)d[4], d[6] / (double)d[4], d[7] / (double)d[4], d[8] / (double)d[4], d[9] / (double)d[4], d[10] / (double)d[4], d[11] / (double)d[4]);
                 fprintf(stderr, "\n");
             }
-        }
+        });
         return 0;
     }
-    if (resid) G32_LAUNCH(true, false, (unsigned long long *)nullptr)
-    else G32_LAUNCH(false, false, (unsigned long long *)nullptr)
-#undef G32_LAUNCH
-    return 0;
+    return pick_bool([&](auto rs) { return launch_k<k_gru_proj32<rs(), false>>(grid, dim3(512), lds, s, in, out, iW, ib, sW, sW2, md, backward, pairs, (unsigned long long *)nullptr); }, resid);
 }
 
 #endif
@@ -768,14 +568,9 @@ static int launch_lstm(hipStream_t s, int S, const float *xaff, float *out, cons
                        const ShMeta &md, int backward, const ShGruLanes &lanes, int nwg) {
     if (nwg <= 0) return 0;
     HIPCHK(hipMemsetAsync(lanes.flag, 0, (size_t)lanes.ntile * 4, s));
-    dim3 grid((unsigned)nwg);
-    switch (S / 16) {
-    case 2: hipLaunchKernelGGL((k_lstm_lanes<2>), grid, dim3(256), 0, s, xaff, out, sW, pf, md, backward, lanes); break;
-    case 4: hipLaunchKernelGGL((k_lstm_lanes<4>), grid, dim3(512), 0, s, xaff, out, sW, pf, md, backward, lanes); break;
-    case 6: hipLaunchKernelGGL((k_lstm_lanes<6>), grid, dim3(768), 0, s, xaff, out, sW, pf, md, backward, lanes); break;
-    default: return set_err("unsupported LSTM size %d (need 32, 64 or 96)", S);
-    }
-    return 0;
+    int rc = 0;
+    if (pick_int<2, 4, 6>(S / 16, rc, [&](auto nu) { return launch_k<k_lstm_lanes<nu()>>(dim3((unsigned)nwg), dim3(128 * nu()), 0, s, xaff, out, sW, pf, md, backward, lanes); })) return rc;
+    return set_err("unsupported LSTM size %d (need 32, 64 or 96)", S);
 }
 
 /* projection + LSTM recurrence in one kernel (k_lstm_proj): needs the layer input as wide as the state */
@@ -785,25 +580,14 @@ static int launch_lstm_proj(hipStream_t s, int S, int I, const float *in, float 
     HIPCHK(hipMemsetAsync(lanes.flag, 0, (size_t)lanes.ntile * 4, s));
     const int NU = S / 16;
     const size_t lds = ((size_t)4 * (NU / 2) * 2 * 64 * 4 + (size_t)2 * 4 * NU * 256 + (size_t)3 * NU * 256) * 4;
-    dim3 grid((unsigned)nwg);
-#define LP_LAUNCH1(NUv, NUIv)                                                                                                \
-    {                                                                                                                        \
-        static DevOnce attr_once;                                                                                            \
-        if (auto turn_ = attr_once.first(lds > 48 * 1024))                                                                            \
-            HIPCHK(hipFuncSetAttribute((const void *)k_lstm_proj<NUv, NUIv>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-        hipLaunchKernelGGL((k_lstm_proj<NUv, NUIv>), grid, dim3(128 * NUv), lds, s, in, out, iW, ib, sW, pf, md, backward, lanes); \
-    }
-#define LP_LAUNCH(NUv) { if (I == S) LP_LAUNCH1(NUv, NUv) else LP_LAUNCH1(NUv, 1) }
     if (I != S && I != 16) return set_err("unsupported LSTM input width %d", I);
-    switch (NU) {
-    case 2: LP_LAUNCH(2) break;
-    case 4: LP_LAUNCH(4) break;
-    case 6: LP_LAUNCH(6) break;
-    default: return set_err("unsupported LSTM size %d (need 32, 64 or 96)", S);
-    }
-#undef LP_LAUNCH
-#undef LP_LAUNCH1
-    return 0;
+    int rc = 0;
+    if (pick_int<2, 4, 6>(NU, rc, [&](auto nu) {
+            constexpr int N = nu();
+            return pick_bool([&](auto wide) { return launch_k<k_lstm_proj<N, wide() ? N : 1>>(dim3((unsigned)nwg), dim3(128 * N), lds, s, in, out, iW, ib, sW, pf, md, backward, lanes); },
+                             I == S);
+        })) return rc;
+    return set_err("unsupported LSTM size %d (need 32, 64 or 96)", S);
 }
 
 static size_t viterbi_lds_bytes(int NH) {
@@ -814,40 +598,25 @@ static size_t viterbi_lds_bytes(int NH) {
 static int launch_viterbi(hipStream_t s, int NH, const ShVitArgs &a, const ShMeta &md, size_t nwg) {
     const size_t lds = viterbi_lds_bytes(NH);
     if (nwg == 0) return 0;
-    dim3 grid((unsigned)nwg);
-#define VIT_CASE1(NTH, PPT, FIN, SLIP, SK0)                                                                    \
-    {                                                                                                       \
-        static DevOnce attr_once;                                                                           \
-        if (auto turn_ = attr_once.first()) {                                                                                    \
-            HIPCHK(hipFuncSetAttribute((const void *)k_viterbi<NTH, PPT, FIN, SLIP, SK0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        }                                                                                                   \
-        hipLaunchKernelGGL((k_viterbi<NTH, PPT, FIN, SLIP, SK0>), grid, dim3(NTH), lds, s, a, md);               \
-    }
-#define VIT_CASE2(NTH, PPT, FIN, SLIP) { if (skip0) VIT_CASE1(NTH, PPT, FIN, SLIP, true) else VIT_CASE1(NTH, PPT, FIN, SLIP, false) }
-#define VIT_CASE(NTH, PPT)                                                                                     \
-    {                                                                                                       \
-        if (fin && slip) VIT_CASE2(NTH, PPT, true, true)                                                    \
-        else if (fin) VIT_CASE2(NTH, PPT, true, false)                                                      \
-        else if (slip) VIT_CASE2(NTH, PPT, false, true)                                                     \
-        else VIT_CASE2(NTH, PPT, false, false)                                                              \
-    }
     /* the log-posterior transform is compiled in (exp values + sums in, log always) or out (final log-posterior in) */
     const bool fin = a.sums != nullptr, slip = a.use_slip != 0, skip0 = a.skip_pen == 0.0f;
     if (fin && !a.want_log) return set_err("decode: exp-value input implies log output");
+    /* nth threads per workgroup, each with ppt quads of states */
+    const auto go = [&](auto nth, auto ppt) {
+        constexpr int NTH = nth(), PPT = ppt();
+        return pick_bool([&](auto fi, auto sl, auto sk) { return launch_k<k_viterbi<NTH, PPT, fi(), sl(), sk()>>(dim3((unsigned)nwg), dim3(NTH), lds, s, a, md); },
+                         fin, slip, skip0);
+    };
     switch (NH) {
-    case 64: VIT_CASE(256, 1) break;
-    case 256: VIT_CASE(256, 4) break;
+    case 64: return go(int_c<256>(), int_c<1>());
+    case 256: return go(int_c<256>(), int_c<4>());
     case 1024:
 #ifdef SH_EXPERIMENTS
-        if (getenv("SH_VIT_1024")) { VIT_CASE(1024, 4) break; }      /* sixteen waves of four quads each (four waves per SIMD at 128 VGPRs): see DESIGN.md section 5 */
+        if (getenv("SH_VIT_1024")) return go(int_c<1024>(), int_c<4>());      /* sixteen waves of four quads each (four waves per SIMD at 128 VGPRs): see DESIGN.md section 5 */
 #endif
-        VIT_CASE(512, 8) break;
+        return go(int_c<512>(), int_c<8>());
     default: return set_err("unsupported transducer state count %d (need 4^3, 4^4 or 4^5 k-mers)", NH);
     }
-#undef VIT_CASE1
-#undef VIT_CASE2
-#undef VIT_CASE
-    return 0;
 }
 
 /* S1 inside the decoder.  Two teams of waves (k_ff_viterbi_teams: an S1 producer team, a decoder team, scores updated in place) wherever
@@ -857,33 +626,15 @@ static int launch_ff_viterbi(hipStream_t s, const ShFfArgs &f, const ShVitArgs &
     const size_t lds = (size_t)SH_FV_LDS_FLOATS * 4;
     if (nwg == 0) return 0;
     dim3 grid((unsigned)nwg);
+    const bool slip = a.use_slip != 0, skip0 = a.skip_pen == 0.0f, dv = f.out_div != 1.0f || f.in_div != 1.0f;
     if (!a.use_slip && !single) {
         const size_t ldt = (size_t)SH_FVT_LDS_FLOATS * 4;
-#define FVT_CASE(SK0, DIV, NC)                                                                                    \
-    {                                                                                                             \
-        static DevOnce attr_once;                                                                                 \
-        if (auto turn_ = attr_once.first())                                                                                    \
-            HIPCHK(hipFuncSetAttribute((const void *)k_ff_viterbi_teams<SK0, DIV, NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldt)); \
-        hipLaunchKernelGGL((k_ff_viterbi_teams<SK0, DIV, NC>), grid, dim3(SH_FVT_NTH), ldt, s, f, a, md);         \
-    }
-        const bool skip0 = a.skip_pen == 0.0f, dv = f.out_div != 1.0f || f.in_div != 1.0f;
         static const bool keep_clamp = getenv("SH_FVT_KEEP_CLAMP") != nullptr;      /* (A/B switch) */
         const bool nc = f.no_clamp && !dv && !keep_clamp;
-        if (skip0) { if (dv) FVT_CASE(true, true, false) else if (nc) FVT_CASE(true, false, true) else FVT_CASE(true, false, false) }
-        else { if (dv) FVT_CASE(false, true, false) else if (nc) FVT_CASE(false, false, true) else FVT_CASE(false, false, false) }
-#undef FVT_CASE
-        return 0;
+        return pick_bool([&](auto sk, auto d, auto n) {
+            if constexpr (d() && n()) return -1;      /* never reached, nc implies !dv: the family has six forms of eight, and these two are not instantiated */
+            else return launch_k<k_ff_viterbi_teams<sk(), d(), n()>>(grid, dim3(SH_FVT_NTH), ldt, s, f, a, md);
+        }, skip0, dv, nc);
     }
-#define FV_CASE(SLIP, SK0, DIV)                                                                                   \
-    {                                                                                                             \
-        static DevOnce attr_once;                                                                                 \
-        if (auto turn_ = attr_once.first())                                                                                    \
-            HIPCHK(hipFuncSetAttribute((const void *)k_ff_viterbi<SLIP, SK0, DIV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL((k_ff_viterbi<SLIP, SK0, DIV>), grid, dim3(512), lds, s, f, a, md);                    \
-    }
-    const bool slip = a.use_slip != 0, skip0 = a.skip_pen == 0.0f, dv = f.out_div != 1.0f || f.in_div != 1.0f;
-    if (slip) { if (skip0) { if (dv) FV_CASE(true, true, true) else FV_CASE(true, true, false) } else { if (dv) FV_CASE(true, false, true) else FV_CASE(true, false, false) } }
-    else { if (skip0) { if (dv) FV_CASE(false, true, true) else FV_CASE(false, true, false) } else { if (dv) FV_CASE(false, false, true) else FV_CASE(false, false, false) } }
-#undef FV_CASE
-    return 0;
+    return pick_bool([&](auto sl, auto sk, auto d) { return launch_k<k_ff_viterbi<sl(), sk(), d()>>(grid, dim3(512), lds, s, f, a, md); }, slip, skip0, dv);
 }

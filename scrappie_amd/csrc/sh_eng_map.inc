@@ -72,12 +72,6 @@ extern "C" long long scrappie_hip_map_plan_scratch(const size_t *seqlen, const s
 /* launches of each k_map form in this process: index (vit ? 8 : 0) | (band ? 4 : 0) | (tiled ? 2 : 0) | (scratch ? 1 : 0) */
 static std::atomic<uint64_t> g_map_forms[16];
 
-template <bool VIT, bool BAND, bool TILED>
-static void map_launch_k(hipStream_t s, const ShMapArgs &a, size_t n_lds, size_t n, size_t lds) {
-    dp_launch<k_map<VIT, BAND, TILED, true>, k_map<VIT, BAND, TILED, false>>(s, a, n_lds, n, SH_MAP_NTH, lds, 0,
-                                                                             g_map_forms + ((VIT ? 8 : 0) | (BAND ? 4 : 0) | (TILED ? 2 : 0)));
-}
-
 /* one plan (all banded or all unbanded) through k_map (+ k_map_walk): scores into score[], paths into paths[i] (malloc'd,
  * only where the plan holds a path).  a: the posterior, its shape and the penalties.  t[0] += k_map, t[1] += walk + copies. */
 static int map_run(scrappie_hip_engine *e, MapPlan &pl, ShMapArgs a, bool vit, bool band, bool tiled, float *score, int32_t **paths, double *t) {
@@ -100,17 +94,10 @@ static int map_run(scrappie_hip_engine *e, MapPlan &pl, ShMapArgs a, bool vit, b
     a.rd = d.rd.as<ShMapRead>(); a.seq = e->d_map_seq.as<int>(); a.band = e->d_map_band.as<int>(); a.tb = d.tb.as<unsigned>(); a.scr = d.scr.as<float>();
     a.score = d.score.as<float>(); a.final_state = d.final_state.as<int>();
     const auto t0 = std::chrono::steady_clock::now();
-    const int k = (vit ? 4 : 0) | (band ? 2 : 0) | (tiled ? 1 : 0);
-    switch (k) {
-    case 0: map_launch_k<false, false, false>(s, a, n_lds, n, pl.lds); break;
-    case 1: map_launch_k<false, false, true>(s, a, n_lds, n, pl.lds); break;
-    case 2: map_launch_k<false, true, false>(s, a, n_lds, n, pl.lds); break;
-    case 3: map_launch_k<false, true, true>(s, a, n_lds, n, pl.lds); break;
-    case 4: map_launch_k<true, false, false>(s, a, n_lds, n, pl.lds); break;
-    case 5: map_launch_k<true, false, true>(s, a, n_lds, n, pl.lds); break;
-    case 6: map_launch_k<true, true, false>(s, a, n_lds, n, pl.lds); break;
-    default: map_launch_k<true, true, true>(s, a, n_lds, n, pl.lds); break;
-    }
+    if (pick_bool([&](auto v, auto b, auto t) {
+            return dp_launch<k_map<v(), b(), t(), true>, k_map<v(), b(), t(), false>>(s, a, n_lds, n, SH_MAP_NTH, pl.lds, 0,
+                                                                                     g_map_forms + ((v() ? 8 : 0) | (b() ? 4 : 0) | (t() ? 2 : 0)));
+        }, vit, band, tiled)) return -1;
     HIPCHK(hipGetLastError());
     HIPCHK(sh_stream_wait(s));
     const auto t1 = std::chrono::steady_clock::now();

@@ -319,8 +319,8 @@ static int stage_decode_transducer(Slot &sl, Model *m, GroupRun &c, const float 
     va.hp_side = c.hp_on ? sl.d_hp.as<float>() : nullptr; va.hp_off = mp.hp_off;
     va.dbg = nullptr;
     va.dump_final = e->dbg_dump_final ? 1 : 0;
-    static unsigned long long *vdbg = nullptr;
-    if (tun().vit_stamp) { if (!vdbg) (void)hipMalloc(&vdbg, 4096 * 16 * 8 * 8); va.dbg = vdbg; }
+    static StampBuf vst;      /* SH_VIT_STAMP: cycle stamps of every decoder launch on stderr (tuning aid) */
+    if (tun().vit_stamp) va.dbg = vst.dev(4096 * 16 * 8);
     /* more tiles than CUs: tiles are decoded in pieces that hand their state over through HBM (sh_sched.h) */
     if (e->d_vstate.ensure(std::max<size_t>(lg.ntile, 1) * ((size_t)NH * 16 + 32) * 4) || e->d_vflag.ensure(std::max<size_t>(lg.ntile, 1) * 4)) return -1;
     HIPCHK(hipMemsetAsync(e->d_vflag.p, 0, std::max<size_t>(lg.ntile, 1) * 4, s));
@@ -336,13 +336,10 @@ static int stage_decode_transducer(Slot &sl, Model *m, GroupRun &c, const float 
         va.E = nullptr; va.sums = nullptr;
         if (launch_ff_viterbi(s, fa, va, mp.md, (size_t)lg.vit_nwg, tun().fv_single || e->dbg_fv_single)) return -1;
     } else if (launch_viterbi(s, NH, va, mp.md, (size_t)lg.vit_nwg)) return -1;
-    if (va.dbg) {
-        (void)sh_stream_wait(s);
-        std::vector<unsigned long long> h((size_t)std::max(lg.vit_nwg, 1) * 16 * 8);
-        (void)hipMemcpy(h.data(), vdbg, h.size() * 8, hipMemcpyDeviceToHost);
+    if (va.dbg) vst.dump_on(0, s, (size_t)std::max(lg.vit_nwg, 1) * 16 * 8, [&](const unsigned long long *h) {
         const int nwv = (fused && !va.use_slip && !(tun().fv_single || e->dbg_fv_single)) ? 12 : 8;       /* the two-team kernel stamps twelve waves (8-11: the S1 team) */
-        for (int w = 0; w < nwv; w++) { unsigned long long *d = &h[((size_t)(lg.vit_nwg / 2) * nwv + w) * 8]; fprintf(stderr, "vit stamp wave %d: phaseB %.0f bar %.0f phaseC %.0f bar %.0f cycles/block\n", w, d[0] / (double)d[4], d[1] / (double)d[4], d[2] / (double)d[4], d[3] / (double)d[4]); }
-    }
+        for (int w = 0; w < nwv; w++) { const unsigned long long *d = &h[((size_t)(lg.vit_nwg / 2) * nwv + w) * 8]; fprintf(stderr, "vit stamp wave %d: phaseB %.0f bar %.0f phaseC %.0f bar %.0f cycles/block\n", w, d[0] / (double)d[4], d[1] / (double)d[4], d[2] / (double)d[4], d[3] / (double)d[4]); }
+    });
     if (c.pf.mark(Marks::DECODE_END, s)) return -1;
     c.pf.span(F_DECODE, Marks::S1_END, Marks::DECODE_END);
     c.stamp("decoder enqueued at");

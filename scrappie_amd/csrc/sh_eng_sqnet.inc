@@ -97,8 +97,7 @@ static int sqnet_run(scrappie_hip_engine *e, const Model *m, const std::vector<s
     a.tile = d[0].as<ShSqnetTile>(); a.code = d[0].as<unsigned char>() + tile_bytes; a.w = m->sqw.as<float>(); a.out = d[1].as<float>();
     const auto t1 = std::chrono::steady_clock::now();
     g_sqnet_launches.fetch_add(1, std::memory_order_relaxed);
-    if (m->WL == 9) hipLaunchKernelGGL(k_sqnet<9>, dim3((unsigned)ntile), dim3(SH_SQN_NTH), 0, s, a);
-    else hipLaunchKernelGGL(k_sqnet<7>, dim3((unsigned)ntile), dim3(SH_SQN_NTH), 0, s, a);
+    if (pick_bool([&](auto w9) { return launch_k<k_sqnet<w9() ? 9 : 7>>(dim3((unsigned)ntile), dim3(SH_SQN_NTH), 0, s, a); }, m->WL == 9)) return -1;
     HIPCHK(hipGetLastError());
     HIPCHK(sh_stream_wait(s));
     const auto t2 = std::chrono::steady_clock::now();

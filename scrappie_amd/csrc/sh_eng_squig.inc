@@ -100,8 +100,8 @@ static int squig_run(scrappie_hip_engine *e, const std::vector<size_t> &who, Squ
     a.move_back_pen = pens[0]; a.half_pen = pens[1];
     a.local_pen = p->local_pen; a.skip_pen = p->skip_pen; a.minscore = p->minscore;
     const auto t1 = std::chrono::steady_clock::now();
-    if (vit) dp_launch<k_squig<true, true>, k_squig<true, false>>(s, a, n_lds, n, SH_SQ_NTH, pl.lds, SH_SQ_LDS_HEAD * 4, g_squig_forms + 2);
-    else dp_launch<k_squig<false, true>, k_squig<false, false>>(s, a, n_lds, n, SH_SQ_NTH, pl.lds, SH_SQ_LDS_HEAD * 4, g_squig_forms);
+    if (pick_bool([&](auto v) { return dp_launch<k_squig<v(), true>, k_squig<v(), false>>(s, a, n_lds, n, SH_SQ_NTH, pl.lds, SH_SQ_LDS_HEAD * 4, g_squig_forms + (v() ? 2 : 0)); },
+                  vit)) return -1;
     HIPCHK(hipGetLastError());
     HIPCHK(sh_stream_wait(s));
     const auto t2 = std::chrono::steady_clock::now();

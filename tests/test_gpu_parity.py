@@ -1263,6 +1263,47 @@ def test_other_layer_sizes(eng, orc, size, nfilter, what):
     assert [key(c) for c in many] == [solo[i % 3] for i in range(40)], what
 
 
+def test_two_engines_first_launches_together(tmp_path):
+    """Two engines on one device whose first calls run at the same time, in a process of its own so that no kernel has
+    had its dynamic-LDS limit raised yet: 32 reads of 600 samples are two tiles, k_gru_proj<6, 1> asks for 60 KB and the
+    two-team decoder for its large LDS, so both threads meet in the once-per-device turn of the launcher.  A launch
+    that got ahead of the limit would fail with HIP's launch error.  Both calls equal a third, sequential one.  (The
+    threads leave a barrier together, so that their first launches overlap is likely, not certain: the test can catch a
+    broken turn only in a run where they do.)"""
+    import subprocess
+    import sys
+    mpath = str(tmp_path / "m96.scrm")
+    model.save_model(model.synthetic_model("rgrgr_r94", seed=11, size=96), mpath)
+    code = """
+import sys, threading
+sys.path.insert(0, %r)
+import scrappie_amd as sa
+from scrappie_amd import synth
+sigs = [synth.medmad_normalise(synth.synthetic_signal(600, 2100 + i)) for i in range(32)]
+engs = [sa.Engine(0), sa.Engine(0)]
+for e in engs:
+    e.load_model("m96", %r)
+key = lambda calls: [None if c is None else (c["bases"], c["score"], c["nblock"]) for c in calls]
+gate, got = threading.Barrier(2), [None, None]
+def run(k):
+    gate.wait()
+    try:
+        got[k] = key(engs[k].basecall(sigs, "m96"))
+    except Exception as ex:
+        got[k] = repr(ex)
+th = [threading.Thread(target=run, args=(k,)) for k in range(2)]
+for t in th: t.start()
+for t in th: t.join()
+want = key(engs[0].basecall(sigs, "m96"))
+assert sum(c is not None for c in want) == 32, want
+assert got[0] == want, got[0]
+assert got[1] == want, got[1]
+for e in engs: e.close()
+""" % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), mpath)
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+
+
 def test_unsupported_layer_size_fails_loudly(eng, models):
     """State widths other than 32 / 64 / 96 / 128 are refused with an error, never approximated."""
     w = model.synthetic_model("rgrgr_r94", seed=5, size=48, nstate=65)

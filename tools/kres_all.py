@@ -2,11 +2,12 @@
 """Registers / scratch / LDS of every kernel in libscrappie_hip.so, from the compiler's own
 -Rpass-analysis=kernel-resource-usage remarks (device-only compile, same flags as the Makefile).
 usage: python tools/kres_all.py [out.csv]"""
+import os
 import re
 import subprocess
 import sys
 
-CSRC = "/root/repo/scrappie_amd/csrc"
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scrappie_amd", "csrc")
 cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
        "-fno-slp-vectorize", "-I../../include", "-I.", "--cuda-device-only", "-S", "-o", "/dev/null",
        "scrappie_hip.hip", "-Rpass-analysis=kernel-resource-usage"]
