@@ -59,6 +59,27 @@
 #define SH_FVT_STAMP 0
 #endif
 #endif
+/* The end-state scan across the decoder waves as ONE 64-bit LDS maximum per read: (score, quad) packed so that the unsigned order of the keys is
+ * argmax_merge's order -- the larger score, on equal scores the lower quad.  High word: the score's bits made monotone (negative: all bits
+ * flipped; else the sign bit set), exact for everything but -0 against +0 and NaN; low word: ~quad.  Key 0 is below every score's key: the
+ * empty slot.
+ * A scanned value is never NaN (logarithms that are finite or -inf, never +inf; finite penalties; -SH_BIG) and never -0.  In round-to-nearest a + b is -0 only for
+ * (-0) + (-0) and a - b only for (-0) - (+0), so a -0 needs a -0 operand to begin with, and there is none: a log-posterior is
+ * v_log_f32(x) * ln 2 with x = e * rm + mp >= 0 -- the logarithm is negative (-inf at x = 0: a read past its end, whose moves then lose to
+ * its stay), positive, or +0 at x = 1, and a product with ln 2 > 0 keeps that; stay_v is such a value less the stay penalty, or the literal +0 of a read past its end; scores start at -SH_BIG and pstart at
+ * +0 (hold = fmaxf(-local_pen, .) may be -0, but (+0) + (-0) = +0); maxima only pick among those.  So no score, no quad maximum and, by
+ * the subtraction rule, no (maximum - local_pen) is -0, whatever the sign of a zero penalty. */
+__device__ __forceinline__ unsigned long long end_key(float v, int i) {
+    const unsigned u = __builtin_bit_cast(unsigned, v);
+    const unsigned hi = u ^ ((unsigned)((int)u >> 31) | 0x80000000u);
+    return ((unsigned long long)hi << 32) | (unsigned)~i;
+}
+__device__ __forceinline__ void end_unkey(unsigned long long k, float &v, int &i) {
+    const unsigned hi = (unsigned)(k >> 32);
+    v = __builtin_bit_cast(float, hi ^ (~(unsigned)((int)hi >> 31) | 0x80000000u));
+    i = (int)~(unsigned)k;
+}
+
 #define SH_FVT_NTH 768
 #define SH_FVT_LDS_FLOATS (1024 * 16 + 64 * 256 + 2 * 64 * 16 + 2 * 2 * 8 * 16 + 4 * 9 * 16 + 65 * 16 + 2 * 3 * 512 + 3 * 2 * 4 * 4)
 
@@ -72,8 +93,16 @@ __global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShV
     float *sc = smem;                                   /* scores, ONE buffer: quad Q of read b at (Q * 16 + b) * 4 */
     float *ring = sc + NH * 16;                         /* exp values on their way to the decoders: slot 16 p + 2 k + j = m-tile (16 p + 8 h + k) of block u + j, h = the half in flight */
     float *skk = ring + 64 * 256;                       /* skip maxima [suffix j < 64][read][value, prefix] */
-    float *redv = skk + 2 * 64 * 16;                    /* end-state scan [block of the pair][NCW][16] */
+    float *redv = skk + 2 * 64 * 16;                    /* the final argmax [NCW][16] (behind the block loop) */
     int *redi = (int *)(redv + 2 * NCW * 16);
+    typedef __attribute__((address_space(3))) unsigned long long *ldsk;
+    /* end-state scan [block of the pair][16]: end_key, the maximum over the decoder waves.  The 64 dwords of this view are redv[0 .. 63]: the two
+     * never live together -- the block loop uses redk only, the final argmax writes redv / redi only behind the loop and a __syncthreads (the region
+     * keeps the size it had as per-wave slots, [2][NCW][16] each, so the layout behind it is unchanged).  Slot order: phase B of block u reads
+     * slot par and stores the empty key 0; the next ds_max into that slot comes in phase C of block u + 1, two lds_barrier()s later; phase C of block
+     * u fills slot par ^ 1, read behind this block's closing barrier.  In front of the loop wave 0 sets both slots (a piece that starts the tile) or
+     * all lanes < 32 zero them ahead of the take-over's __syncthreads, behind which the waves ds_max their candidates into slot 0. */
+    ldsk redk = (ldsk)redv;
     float *gsum = (float *)(redi + 2 * NCW * 16);       /* row-sum groups [block & 3][NG][16] (group 8 = the stay state's exp value) */
     float *sBias = gsum + 4 * NG * 16;                  /* bias x 2^14 by state row [65 * 16] */
     unsigned *xp = (unsigned *)(sBias + 65 * 16);       /* the trunk columns of the pair in the making, as pieces [2][KS][2][64][4] */
@@ -84,6 +113,7 @@ __global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShV
     const bool decoder = wave < NCW;
     const float mp = a.min_prob, mpm1 = 1.0f - a.min_prob;
     const float lbound = (mp > 0.0f) ? 1.0e-3f - __logf(mp) : INFINITY;      /* |log-posterior| <= this */
+    const float lbgap = lbound * SH_FVT_GAP;                                  /* (exact: a power of two) */
     unsigned long long vA = 0, vB = 0, vC = 0, vD = 0, vt0 = 0, vt1 = 0;
     (void)vt0; (void)vt1;
 #undef VSTAMP
@@ -122,10 +152,12 @@ __global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShV
         if (decoder) {
 #pragma unroll
             for (int i = 0; i < PPT; i++) *(f32x4 *)(myq + SH_FVT_MT(i) * 256) = (f32x4){-SH_BIG, -SH_BIG, -SH_BIG, -SH_BIG};
-            if (lane < 16) { redv[wave * 16 + b] = -SH_BIG - a.local_pen; redi[wave * 16 + b] = 4 * wave; }
+            /* every quad holds -SH_BIG: the first one wins */
+            if (wave == 0 && lane < 16) { redk[b] = end_key(-SH_BIG - a.local_pen, 0); redk[16 + b] = 0; }
         }
     } else {
         /* the tile's earlier blocks ran on another workgroup: take over its state */
+        if (tid < 32) redk[tid] = 0;
         if (tid == 0) {
             if (!sh_wait_flag(a.flag + tile, (unsigned)ord, a.err)) __hip_atomic_store(a.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
@@ -152,7 +184,7 @@ __global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShV
             argmax_merge(bv, bi, ov, oi);
             ov = __shfl_xor(bv, 32); oi = __shfl_xor(bi, 32);
             argmax_merge(bv, bi, ov, oi);
-            if (lane < 16) { redv[wave * 16 + b] = bv; redi[wave * 16 + b] = bi; }
+            if (lane < 16) __hip_atomic_fetch_max(redk + b, end_key(bv, bi), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
     }
 
@@ -371,19 +403,19 @@ __global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShV
 
             /* ---- phase B: step maxima of my quads; skip maxima of my two suffixes; emissions out of the ring ---- */
             float sv[PPT];
-            int sr[PPT];                                    /* (phase B only: across the barrier the prefixes travel two bits each in srp) */
+            int sr[PPT];                                    /* the step move's traceback CODE, SH_TB_STEP + r4 (phase B only: across the barrier the codes travel three bits each in srp) */
 #pragma unroll
             for (int i = 0; i < PPT; i++) {
                 /* step: max over the 4 prefixes of suffix Q, the first maximum (decode.c:186-210) */
                 float v = mysrc[SH_FVT_MT(i) * 64];
-                int ri = 0;
+                int ri = (int)SH_TB_STEP;
                 if (!(SH_FVT_ABL & 2)) {
 #pragma unroll
                     for (int r = 1; r < 4; r++) {
                         const float c = mysrc[(r * 64 + SH_FVT_MT(i)) * 64];
                         const bool up = v < c;
                         v = up ? c : v;
-                        ri = up ? r : ri;
+                        ri = up ? (int)SH_TB_STEP + r : ri;
                     }
                 }
                 sv[i] = v; sr[i] = ri;
@@ -391,35 +423,33 @@ __global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShV
             }
 #pragma unroll
             for (int c = 0; c < 2; c++) {
-                /* skip into suffix j = 32 c + 4 w + q: the prefixes are r = 4 r4 + rl, lowest first (decode.c:228-251) */
+                /* skip into suffix j = 32 c + 4 w + q: the prefixes are r = 4 r4 + rl, lowest first (decode.c:228-251).  What is merged and
+                 * handed on is the move's traceback CODE, SH_TB_SKIP + r: the same order as r, and the constant rides in the shift-and-add
+                 * that forms r anyway, so phase C adds nothing per quad */
+                constexpr int KOFS = (int)SH_TB_SKIP - 4 * (int)SH_TB_STEP;
                 float v = sv[c];
-                int ri = 4 * sr[c];
+                int ri = 4 * sr[c] + KOFS;
                 if (!(SH_FVT_ABL & 2)) {
 #pragma unroll
-                    for (int rl = 1; rl < 4; rl++) argmax_merge(v, ri, sv[2 * rl + c], 4 * sr[2 * rl + c] + rl);
+                    for (int rl = 1; rl < 4; rl++) argmax_merge(v, ri, sv[2 * rl + c], 4 * sr[2 * rl + c] + (rl + KOFS));
                 }
                 *(f32x2 *)(skk + ((32 * c + 4 * cw + q) * 16 + b) * 2) = (f32x2){v, __builtin_bit_cast(float, ri)};
             }
+            static_assert(SH_TB_STEP + 3u < 8u, "a step code in three bits");
             unsigned srp = 0;
 #pragma unroll
-            for (int i = 0; i < PPT; i++) srp |= (unsigned)sr[i] << (2 * i);
+            for (int i = 0; i < PPT; i++) srp |= (unsigned)sr[i] << (3 * i);
             /* the end state's predecessor (decode.c:343-348) reads a quad of another thread: resolved here, before anything is overwritten.  ei is the
              * first QUAD that holds the maximum of (score - local_pen); the state is the first of its four that attains it */
             float ev = 0.f; int tbe_in = 0;
             if (cw == 0) {
                 int ei;
-                /* (one address register + immediate offsets; an LDS pointer by type: as a generic one these were sixteen flat loads behind
+                /* the eight waves' candidates were merged by the LDS maximum they were written with (end_key): one read instead of sixteen
+                 * and seven merges, on the wave every other one waits for at this phase's barrier.  The slot is emptied for the block after
+                 * next, whose phase C -- two barriers on -- writes it.  (An LDS pointer by type: as a generic one this is a flat load behind
                  * s_waitcnt vmcnt(0) lgkmcnt(0), i.e. behind the wave's traceback stores) */
-                typedef __attribute__((address_space(3))) const float *ldsf;
-                ldsf rv = (ldsf)(redv + b);
-                asm volatile("" : "+v"(rv));
-                ev = rv[par * NCW * 16];
-                ei = __builtin_bit_cast(int, rv[(2 + par) * NCW * 16]);
-#pragma unroll
-                for (int w = 1; w < NCW; w++) {
-                    const float ov = rv[(par * NCW + w) * 16], oif = rv[((2 + par) * NCW + w) * 16];
-                    argmax_merge(ev, ei, ov, __builtin_bit_cast(int, oif));
-                }
+                end_unkey(redk[par * 16 + b], ev, ei);
+                redk[par * 16 + b] = 0;
                 const f32x4 q4 = *(const f32x4 *)(sc + ((ei & (NQ - 1)) * 16 + b) * 4);
                 int e0 = 3;
                 e0 = (q4[2] - a.local_pen == ev) ? 2 : e0;
@@ -460,6 +490,11 @@ __global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShV
             }
             float bv = -INFINITY;
             int bi = 0x7fffffff;
+            /* the block's traceback rows: two wave-uniform bases (scalar registers), each serving four quads through the store's immediate
+             * offset (13 bits, signed: quad i of this wave lies 2048 i bytes on), and the lane as the one 32-bit vector offset */
+            typedef __attribute__((address_space(1))) unsigned *gtb;
+            gtb tb0 = (gtb)a.tb + ((cb * NQ + 4 * cw) * 16 + 1024), tb1 = tb0 + 2048;
+            asm volatile("" : "+s"(tb0), "+s"(tb1));
             /* a quad's inputs from LDS are read one quad ahead */
             f32x4 pv_n; f32x2 kk_n;
             auto q_fetch = [&](int i) {
@@ -475,7 +510,7 @@ __global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShV
                 const f32x4 pv = pv_n;
                 const float kv = kk_n[0];
                 const float krf = kk_n[1];                     /* (bit_cast straight from the vector element reads element 0: hipcc 7.2) */
-                const int kr = __builtin_bit_cast(int, krf);
+                const unsigned cskip = __builtin_bit_cast(unsigned, krf);      /* SH_TB_SKIP + r: phase B */
                 if (i + 1 < PPT) q_fetch(i + 1);
                 f32x4 l4;
 #pragma unroll
@@ -488,15 +523,20 @@ __global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShV
                     if (i == 2 * (sq >> 6) + ((sq >> 5) & 1)) hpv[k] = l4[s & 3];
                 }
                 const float svi = sv[i];
-                const unsigned cstep = SH_TB_STEP + ((srp >> (2 * i)) & 3u), cskip = SH_TB_SKIP + (unsigned)kr;
+                const unsigned cstep = (srp >> (3 * i)) & 7u;  /* SH_TB_STEP + r4: phase B */
                 const unsigned cstart = SH_TB_START;
-                unsigned codes = 0;                             /* four SH_TB_STAY */
+                unsigned codes;                                 /* four SH_TB_STAY, by the first move of state 0 */
                 f32x4 ns;
-#define SH_FVT_STATE(E)                                                                                         \
+                static_assert(SH_TB_STAY == 0u && SH_TB_STEP + 3u < 256u && SH_TB_SKIP + 15u < 256u && SH_TB_START < 256u,
+                              "SH_FVT_LT_FIRST copies all 32 bits of x (cstep, cskip, cstart or cm): every code register is zero above its low byte");
+                /* the first conditional move of a quad DEFINES `codes` (x where a < b, else four SH_TB_STAY): no register to clear first */
+#define SH_FVT_LT_FIRST(E, codes, a, b, x)                                                                      \
+                asm("v_cmp_lt_f32 vcc, %1, %2\n\tv_cndmask_b32 %0, 0, %3, vcc" : "=v"(codes) : "v"(a), "v"(b), "v"(x) : "vcc")
+#define SH_FVT_STATE(E, LT1)                                                                                    \
                 {                                                                                               \
                     float s_ = pv[E] + stay_v;                  /* stay  :180 */                                \
                     const float st = l4[E] + svi;               /* step  :214-218 */                            \
-                    SH_CODE_LT(E, codes, s_, st, cstep);                                                        \
+                    LT1(E, codes, s_, st, cstep);                                                               \
                     s_ = __builtin_fmaxf(s_, st);                                                               \
                     const float sk = SKIP0 ? l4[E] + kv : (l4[E] + kv) - a.skip_pen;   /* skip  :256-262 */     \
                     SH_CODE_LT(E, codes, s_, sk, cskip);                                                        \
@@ -514,26 +554,36 @@ __global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShV
                     m = __builtin_fmaxf(__builtin_fmaxf(svi, kv), pstart);
                     const float md = __builtin_amdgcn_fmed3f(svi, kv, pstart);
                     /* SH_FVT_GAP (sh_decode.h): 2^-21 (|l|max + |m|).  (One threshold per read and block from |pstart| >= |m| instead -- two instructions fewer
-                     * per quad -- was measured SLOWER, 10.0 against 9.7 ms: profiles/r6_decoder_issue.txt) */
-                    const unsigned long long unclear = __builtin_amdgcn_fcmpf(m - md, (lbound + __builtin_fabsf(m)) * SH_FVT_GAP, 13 /* ULE */);
+                     * per quad -- was measured SLOWER, 10.0 against 9.7 ms: profiles/r6_decoder_issue.txt)
+                     * The threshold is ONE fused multiply-add with the same bits as k_ff_viterbi's (lbound + |m|) * SH_FVT_GAP: the factor is a power
+                     * of two, so lbgap = lbound * 2^-21 is exact, |m| * 2^-21 + lbgap is exactly 2^-21 (|m| + lbound), and rounding commutes with
+                     * a power-of-two scaling while the result stays normal -- it is >= 2^-21 * 1e-3, and <= 2^-21 * 2e30 (scores are >= -SH_BIG);
+                     * lbound = +inf (min_prob = 0) gives +inf both ways */
+                    static_assert(SH_FVT_GAP == 4.76837158203125e-07f, "the fused threshold needs a power of two");
+                    const unsigned long long unclear = __builtin_amdgcn_fcmpf(m - md, __builtin_fmaf(__builtin_fabsf(m), SH_FVT_GAP, lbgap), 13 /* ULE */);
                     fast = (unclear & actmask) == 0;
                     cm = (kv == m) ? cskip : cm;
                     cm = (svi == m) ? cstep : cm;
                 }
-                if (fast) {
-#define SH_FVT_FAST(E)                                                                                          \
+                /* (expected: the one-addition path falls through and the three-move path is out of line; unhinted it was the far side of
+                 * two taken branches a quad: profiles/decoder_count.txt) */
+                if (__builtin_expect(fast, true)) {
+#define SH_FVT_FAST(E, LT1)                                                                                    \
                     {                                                                                           \
                         const float s_ = pv[E] + stay_v;        /* stay  :180 */                                \
                         const float mv = l4[E] + m;             /* the best move into the state */              \
-                        SH_CODE_LT(E, codes, s_, mv, cm);                                                       \
+                        LT1(E, codes, s_, mv, cm);                                                              \
                         ns[E] = __builtin_fmaxf(s_, mv);                                                        \
                     }
-                    SH_FVT_FAST(0) SH_FVT_FAST(1) SH_FVT_FAST(2) SH_FVT_FAST(3)
+                    SH_FVT_FAST(0, SH_FVT_LT_FIRST) SH_FVT_FAST(1, SH_CODE_LT) SH_FVT_FAST(2, SH_CODE_LT) SH_FVT_FAST(3, SH_CODE_LT)
 #undef SH_FVT_FAST
-                } else { SH_FVT_STATE(0) SH_FVT_STATE(1) SH_FVT_STATE(2) SH_FVT_STATE(3) }
+                } else { SH_FVT_STATE(0, SH_FVT_LT_FIRST) SH_FVT_STATE(1, SH_CODE_LT) SH_FVT_STATE(2, SH_CODE_LT) SH_FVT_STATE(3, SH_CODE_LT) }
 #undef SH_FVT_STATE
+#undef SH_FVT_LT_FIRST
                 *(f32x4 *)(myq + SH_FVT_MT(i) * 256) = ns;          /* in place: nobody else reads these four */
-                if (!(SH_FVT_ABL & 4)) (a.tb + (cb * NQ + QB) * 16)[tofs] = codes;   /* also for reads past their end (never read back): no branch */
+                gtb tbq = i < PPT / 2 ? tb0 : tb1;
+                asm volatile("" : "+s"(tbq));               /* (opaque per quad: seen as one base of four stores, base + lane becomes a 64-bit vector address) */
+                if (!(SH_FVT_ABL & 4)) (tbq + (512 * (i % (PPT / 2)) - 1024))[tofs] = codes;   /* (a.tb + (cb * NQ + QB) * 16)[lane]; also for reads past their end (never read back): no branch */
                 else asm volatile("" :: "v"(codes));
                 {   /* next block's end-state scan, per quad: this thread meets its quads in increasing index order,
                      * so a strict compare keeps the first maximum */
@@ -556,7 +606,7 @@ __global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShV
             }
             {
                 rows_argmax(bv, bi);
-                if (lane < 16) { redv[((par ^ 1) * NCW + wave) * 16 + b] = bv; redi[((par ^ 1) * NCW + wave) * 16 + b] = bi; }
+                if (lane < 16) __hip_atomic_fetch_max(redk + ((par ^ 1) * 16 + b), end_key(bv, bi), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
             VSTAMP(vC);
             lds_barrier();
