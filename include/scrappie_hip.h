@@ -58,6 +58,16 @@ typedef struct {
     event_t *event;
 } event_table;
 
+/* src/event_detection.h:6-21 */
+typedef struct {
+    size_t window_length1;
+    size_t window_length2;
+    float threshold1;
+    float threshold2;
+    float peak_height;
+} detector_param;
+extern const detector_param event_detection_defaults;      /* 3, 6, 1.4, 9.0, 0.2 */
+
 /* src/scrappie_matrix.h:10-16 == interface/scrappie.h:38-45.  Column-major,
  * rows padded to nrq = ceil(nr/4) 4-float vectors, stride = 4*nrq, 16-byte
  * aligned.  The `v` arm is `__m128 *` in the reference; any object pointer
@@ -126,6 +136,13 @@ scrappie_matrix nanonet_rnnrf_r94_transitions(const raw_table signal, float min_
  * 3-event window (layers.c:119, first column zero as in the reference) are host C. */
 scrappie_matrix nanonet_posterior(const event_table events, float min_prob,
                                   float tempW, float tempb, bool return_log);
+
+/* src/event_detection.c:268 -- events of rt.raw[rt.start .. rt.end): pos = state = -1, start = 0, end = n, .event malloc'd (the caller
+ * frees it).  Runs on the process-default engine as a batch of one (sh_events.h); the table is bit-identical to the reference's.  Where the
+ * reference is undefined -- no peak in the read, so that create_events reads peaks[-1]: fewer than 2 * window_length2 samples, a constant
+ * signal -- and for a NULL or empty signal, or when no engine can be made, the result is {0, 0, 0, NULL} and
+ * scrappie_hip_last_error() says why. */
+event_table detect_events(raw_table const rt, detector_param const edparam);
 
 /* src/decode.c:123 -- seq has nblock+1 entries.  Returns NAN on failure. */
 float decode_transducer(const_scrappie_matrix logpost, float stay_pen, float skip_pen,
@@ -548,6 +565,36 @@ scrappie_matrix scrappie_hip_trunk(scrappie_hip_engine *e, int model, const raw_
 int scrappie_hip_event_features(const event_table events, float *out);
 scrappie_matrix scrappie_hip_events_posterior(scrappie_hip_engine *e, int model, const float *feature3, size_t nevent,
                                               float min_prob, float tempW, float tempb, bool return_log);
+
+/* Event detection, batched (sh_eng_events.inc, kernels in sh_events.h): detect_events for every reads[i].raw[start .. end) in one call.
+ * results[i].events belongs to reads[i]: .event malloc'd (scrappie_hip_free_event_results), NULL with status 1 where the read has no
+ * peak (the reference is undefined there), status 2 where the read was refused (no signal, an empty window, more samples than one launch
+ * may hold; the first such reason is the call's error text).  p NULL: event_detection_defaults.  The reads are sorted by length and cut
+ * into launches under a sample budget (28 bytes of device scratch per sample + the signal; half of the free device memory, or the debug
+ * option "events_budget_samples").  Returns 0, or -1 with scrappie_hip_last_error() when the call as a whole fails (then every table is
+ * NULL).  A launch holds the engine's lock.  Bit-identical to scrappie_hip_detect_events_host, and so to the reference. */
+typedef struct { event_table events; int status; } scrappie_hip_event_result;
+int scrappie_hip_detect_events_batch(scrappie_hip_engine *e, const raw_table *reads, size_t n, const detector_param *p,
+                                     scrappie_hip_event_result *results);
+void scrappie_hip_free_event_results(scrappie_hip_event_result *r, size_t n);
+/* the last scrappie_hip_detect_events_batch call's time, milliseconds summed over its launches: [0] staging + upload, [1] the four
+ * kernels, [2] event tables to the host (host clock, the stream drained between the stages) */
+void scrappie_hip_event_timing(scrappie_hip_engine *e, double out[3]);
+/* samples per read of one staged tile of the serial kernels (host only): reads longer than this take several tiles */
+size_t scrappie_hip_event_tile(void);
+/* launches of scrappie_hip_detect_events_batch since the process started, all engines together (a host counter; tests) */
+uint64_t scrappie_hip_event_launch_count(void);
+/* The planner's arithmetic on the host, no device (for the tests).  Reads of nsample[i] samples laid out in this order in one launch:
+ * off[i] = the first slot of read i, which owns nsample[i] + 1 slots from there in each of the five scratch arrays (running sums and
+ * sums of squares: double; the two statistics: float; peaks: uint32; 28 bytes per slot); returns the slots of the launch. */
+long long scrappie_hip_events_plan_scratch(const size_t *nsample, size_t n, long long *off);
+/* ... and the cut of a call into launches of at most budget_slots slots: order[] takes the read indices sorted by length, longest
+ * first; starts[] the first position (in that order) of each launch; returns the number of launches (even if > cap), -1 if one read
+ * alone exceeds the budget. */
+long scrappie_hip_events_plan_launches(const size_t *nsample, size_t n, size_t budget_slots, uint32_t *order, size_t *starts, size_t cap);
+/* The host statement of detect_events (sh_host.c) on x[0 .. n): what the kernels are held against bit for bit (tests, tools; the
+ * per-read surface never falls back to it: without a device detect_events fails).  .event NULL where there is no peak.  tstat1 / tstat2 (may be NULL): n floats each, the two statistics. */
+event_table scrappie_hip_detect_events_host(const float *x, size_t n, const detector_param *p, float *tstat1, float *tstat2);
 
 /* Lane schedule of the recurrent kernel (scrappie_amd/csrc/sh_sched.h), host only:
  * how the tiles (16 reads, tile_T[i] blocks) of a launch group are cut into

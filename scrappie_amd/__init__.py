@@ -74,6 +74,27 @@ class _SquigResult(C.Structure):
     _fields_ = [("score", C.c_float), ("n", C.c_size_t), ("path", C.POINTER(C.c_int32))]
 
 
+class _Event(C.Structure):          # scrappie_structures.h:8-15
+    _fields_ = [("start", C.c_uint64), ("length", C.c_float), ("mean", C.c_float), ("stdv", C.c_float),
+                ("pos", C.c_int), ("state", C.c_int)]
+
+
+class _EventTable(C.Structure):     # scrappie_structures.h:17-22
+    _fields_ = [("n", C.c_size_t), ("start", C.c_size_t), ("end", C.c_size_t), ("event", C.POINTER(_Event))]
+
+
+class DetectorParam(C.Structure):   # event_detection.h:6-12; the defaults are event_detection_defaults
+    _fields_ = [("window_length1", C.c_size_t), ("window_length2", C.c_size_t), ("threshold1", C.c_float),
+                ("threshold2", C.c_float), ("peak_height", C.c_float)]
+
+    def __init__(self, window_length1=3, window_length2=6, threshold1=1.4, threshold2=9.0, peak_height=0.2):
+        super().__init__(window_length1, window_length2, threshold1, threshold2, peak_height)
+
+
+class _EventResult(C.Structure):
+    _fields_ = [("events", _EventTable), ("status", C.c_int)]
+
+
 class Timing(C.Structure):
     _fields_ = [("conv_ms", C.c_float), ("affine_ms", C.c_float), ("gru_ms", C.c_float),
                 ("ff_ms", C.c_float), ("decode_ms", C.c_float), ("backtrace_ms", C.c_float),
@@ -264,6 +285,22 @@ def lib():
     L.scrappie_hip_sqnet_tile.argtypes = []
     L.scrappie_hip_sqnet_launch_count.restype = C.c_uint64
     L.scrappie_hip_sqnet_launch_count.argtypes = []
+    L.detect_events.restype = _EventTable
+    L.detect_events.argtypes = [_RawTable, DetectorParam]
+    L.scrappie_hip_detect_events_host.restype = _EventTable
+    L.scrappie_hip_detect_events_host.argtypes = [C.POINTER(C.c_float), C.c_size_t, C.POINTER(DetectorParam), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.scrappie_hip_detect_events_batch.argtypes = [C.c_void_p, C.POINTER(_RawTable), C.c_size_t, C.POINTER(DetectorParam), C.POINTER(_EventResult)]
+    L.scrappie_hip_free_event_results.restype = None
+    L.scrappie_hip_free_event_results.argtypes = [C.POINTER(_EventResult), C.c_size_t]
+    L.scrappie_hip_event_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    L.scrappie_hip_event_tile.restype = C.c_size_t
+    L.scrappie_hip_event_tile.argtypes = []
+    L.scrappie_hip_event_launch_count.restype = C.c_uint64
+    L.scrappie_hip_event_launch_count.argtypes = []
+    L.scrappie_hip_events_plan_scratch.restype = C.c_longlong
+    L.scrappie_hip_events_plan_scratch.argtypes = [C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(C.c_longlong)]
+    L.scrappie_hip_events_plan_launches.restype = C.c_long
+    L.scrappie_hip_events_plan_launches.argtypes = [C.POINTER(C.c_size_t), C.c_size_t, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_size_t), C.c_size_t]
     L.scrappie_hip_launch_form_counts.restype = None
     L.scrappie_hip_launch_form_counts.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     _lib = L
@@ -418,13 +455,53 @@ _model_fn_ = {
 }
 
 
-class _Event(C.Structure):          # scrappie_structures.h:8-15
-    _fields_ = [("start", C.c_uint64), ("length", C.c_float), ("mean", C.c_float), ("stdv", C.c_float),
-                ("pos", C.c_int), ("state", C.c_int)]
+def _take_events(et):
+    """the structured array (synth.EVENT_DTYPE) of an event_table the library malloc'd, which is freed; None for no table"""
+    if not et.event:
+        return None
+    from .synth import EVENT_DTYPE
+    ev = np.frombuffer(C.string_at(et.event, et.n * C.sizeof(_Event)), dtype=EVENT_DTYPE).copy()
+    _libc.free(C.cast(et.event, C.c_void_p))
+    return ev[et.start:et.end]
 
 
-class _EventTable(C.Structure):     # scrappie_structures.h:17-22
-    _fields_ = [("n", C.c_size_t), ("start", C.c_size_t), ("end", C.c_size_t), ("event", C.POINTER(_Event))]
+def detect_events(signal, window_length1=3, window_length2=6, threshold1=1.4, threshold2=9.0, peak_height=0.2):
+    """The reference's detect_events (event_detection.c:268) on a signal in pA (a float32 array, or a `RawTable` with its
+    window), on the process-default engine: a structured array with the event_t layout (scrappie_amd.synth.EVENT_DTYPE;
+    pos = state = -1), or None where the read has no peak (the reference is undefined there; `last_error()` says so)."""
+    rts, keep = _raw_tables([signal])
+    return _take_events(lib().detect_events(rts[0], DetectorParam(window_length1, window_length2, threshold1, threshold2, peak_height)))
+
+
+def detect_events_host(signal, tstats=False, **params):
+    """The host statement of detect_events (what the kernels are held against): the event table or None; with `tstats`
+    also the two t-statistics."""
+    x = np.ascontiguousarray(signal, dtype=ftype)
+    fp = C.POINTER(C.c_float)
+    t1, t2 = np.zeros(len(x), dtype=ftype), np.zeros(len(x), dtype=ftype)
+    p = DetectorParam(**params)
+    ev = _take_events(lib().scrappie_hip_detect_events_host(x.ctypes.data_as(fp), len(x), C.byref(p), t1.ctypes.data_as(fp), t2.ctypes.data_as(fp)))
+    return (ev, t1, t2) if tstats else ev
+
+
+def plan_event_scratch(nsample):
+    """(off, total): the first scratch slot of each read of one event-detection launch of reads in this order, and the
+    slots of the launch (host arithmetic; read i owns nsample[i] + 1 slots of 28 bytes)"""
+    a = np.ascontiguousarray(nsample, dtype=np.uintp)
+    off = np.zeros(len(a), dtype=np.longlong)
+    total = lib().scrappie_hip_events_plan_scratch(a.ctypes.data_as(C.POINTER(C.c_size_t)), len(a), off.ctypes.data_as(C.POINTER(C.c_longlong)))
+    return off, int(total)
+
+
+def plan_event_launches(nsample, budget_slots):
+    """(order, starts): the reads of an event-detection call sorted by length, longest first, and the first position in
+    that order of each launch under a budget of sample slots; None where one read alone exceeds the budget"""
+    a = np.ascontiguousarray(nsample, dtype=np.uintp)
+    order = np.zeros(len(a), dtype=np.uint32)
+    starts = np.zeros(max(len(a), 1), dtype=np.uintp)
+    ng = lib().scrappie_hip_events_plan_launches(a.ctypes.data_as(C.POINTER(C.c_size_t)), len(a), budget_slots,
+                                                 order.ctypes.data_as(C.POINTER(C.c_uint32)), starts.ctypes.data_as(C.POINTER(C.c_size_t)), len(starts))
+    return None if ng < 0 else (order, starts[:ng].astype(np.int64))
 
 
 def event_features(events, start=0, end=None):
@@ -1194,6 +1271,38 @@ class Engine(object):
     def squiggle_timing(self):
         """the last match_squiggle call's time (ms, summed over launches): tables + uploads, k_squig, walk + results"""
         return self._timing(lib().scrappie_hip_squiggle_timing, ('tables_ms', 'match_ms', 'walk_ms'))
+
+    def detect_events(self, signals, window_length1=3, window_length2=6, threshold1=1.4, threshold2=9.0, peak_height=0.2):
+        """detect_events for each signal (pA; a float32 array, or a `RawTable` with its window), batched
+        (scrappie_hip_detect_events_batch): a list of structured arrays with the event_t layout
+        (scrappie_amd.synth.EVENT_DTYPE) in input order, None where a read has no peak or is refused."""
+        n = len(signals)
+        rts, keep = _raw_tables(signals)
+        p = DetectorParam(window_length1, window_length2, threshold1, threshold2, peak_height)
+        out = (_EventResult * max(n, 1))()
+        if lib().scrappie_hip_detect_events_batch(self._h, rts, n, C.byref(p), out) != 0:
+            raise RuntimeError("detect_events_batch: " + last_error())
+        return [_take_events(out[i].events) for i in range(n)]
+
+    def event_timing(self):
+        """the last detect_events call's time (ms, summed over launches): staging + upload, the kernels, tables to the host"""
+        return self._timing(lib().scrappie_hip_event_timing, ('upload_ms', 'detect_ms', 'download_ms'))
+
+    def basecall_events(self, signals, model='nanonet_events', detector=None, **params):
+        """Basecall from events, as `scrappie events` does without its dwell correction (scrappie_events.c:278-300): detect_events
+        (batched) -> event_features -> the events model's posterior -> decode_transducer -> overlapper, the last three as
+        one `basecall` of the feature matrices with the homopolymer pass off.  `signals`: pA, windows already trimmed;
+        `detector`: a dict of detect_events' parameters; `params`: fields of `Params` (min_prob, skip_pen, ...).  Returns
+        the list `basecall` returns, None where a read has no events or no call."""
+        evs = self.detect_events(signals, **(detector or {}))
+        keep = [i for i, ev in enumerate(evs) if ev is not None]
+        kw = dict(homopolymer=0)
+        kw.update(params)
+        calls = self.basecall([event_features(evs[i]).ravel() for i in keep], model, self.default_params(**kw))
+        res = [None] * len(signals)
+        for i, c in zip(keep, calls):
+            res[i] = c
+        return res
 
     def trunk(self, signal, model='rgrgr_r94', upto=5):
         rt = RawTable(signal)

@@ -35,11 +35,12 @@
  *   sh_eng_batch.inc     helper engine for chain-bound reads, host-signal entry points, several GPUs
  *   sh_eng_debug.inc     measurement / test hooks
  *   sh_eng_surface.inc   the reference's per-read functions: one batch function per family, run by the queue or with a batch of one
- *   sh_eng_cut.inc       what the three engines below share: a call cut into launches that fit the device (LaunchCut), per-read DP
+ *   sh_eng_cut.inc       what the engines below share: a call cut into launches that fit the device (LaunchCut), per-read DP
  *                        records through a kernel with two homes (dp_order / dp_launch / dp_collect)
  *   sh_eng_map.inc       block-based mapping of posteriors to sequences (per-read and batched)
  *   sh_eng_squig.inc     mapping of raw signals to predicted squiggles (per-read and batched)
  *   sh_eng_sqnet.inc     prediction of squiggles from base sequences (per-read and batched)
+ *   sh_eng_events.inc    event detection (per-read and batched; kernels in sh_events.h)
  * Separate translation units: sh_p0.hip (signal preparation, k_p0), sh_host.c / sh_fast5.c / sh_h5mini.c (host C);
  * sh_coalesce.h (the per-read functions' queue) and sh_dev.h (DBuf / HBuf: buffers that own their memory) are plain C++ headers.
  */
@@ -75,6 +76,7 @@
 #include "sh_map.h"
 #include "sh_squig.h"
 #include "sh_sqnet.h"
+#include "sh_events.h"
 
 /* function attributes (dynamic LDS limit) are per device: remember for which devices a kernel has had its attribute set
  * (engines on several GPUs may share one process).  A real once per device: the thread that finds the attribute unset holds
@@ -460,6 +462,9 @@ struct scrappie_hip_engine {
     double squig_ms[3] = {0, 0, 0};  /* scrappie_hip_squiggle_match_batch: tables + uploads, k_squig, k_squig_walk + results, summed over the last call's launches */
     DBuf d_sqn[2]; HBuf h_sqn;       /* squiggle prediction (sh_eng_sqnet.inc): tiles | codes, outputs */
     double sqnet_ms[3] = {0, 0, 0};  /* scrappie_hip_squiggle_predict_batch: upload, k_sqnet, download + transform, summed over the last call's launches */
+    DBuf d_ev_sig, d_ev_rd, d_ev_sum, d_ev_sumsq, d_ev_t1, d_ev_t2, d_ev_peaks, d_ev_np, d_ev_off, d_ev_out; HBuf h_ev, h_ev_out;      /* event detection (sh_eng_events.inc): signals, records, the five scratch arrays, peak counts, event offsets, event tables; staging */
+    double event_ms[3] = {0, 0, 0};  /* scrappie_hip_detect_events_batch: staging + upload, the kernels, tables to the host, summed over the last call's launches */
+    size_t dbg_events_budget = 0;    /* sample slots one event-detection launch may hold (debug option "events_budget_samples"; 0: from the free memory) */
     size_t dbg_sqnet_budget = 0;     /* device bytes one squiggle-predicting launch may hold (debug option "sqnet_budget_kb"; 0: half of the free memory) */
     size_t dbg_squig_budget = 0;     /* device bytes one squiggle-matching launch may hold (debug option "squiggle_budget_kb"; 0: half of the free memory) */
     std::mutex call_mu;              /* scrappie_hip_basecall_batch: one call at a time inside the engine (concurrent small calls share one: sh_eng_batch.inc) */
@@ -593,7 +598,8 @@ extern "C" scrappie_hip_params scrappie_hip_default_params(void) {
 #include "sh_eng_batch.inc"      /* chain-bound reads on a helper engine, host-signal entry points, several GPUs */
 #include "sh_eng_debug.inc"      /* measurement / test hooks: decoder and trunk inputs, debug_option / debug_fetch / debug_stitch */
 #include "sh_eng_surface.inc"      /* the reference's per-read functions: posterior / trunk on an explicit engine, the process-default engine, decode_transducer, decode_crf; all three coalesced (sh_coalesce.h) */
-#include "sh_eng_cut.inc"      /* shared by the three below: LaunchCut (a call cut into launches), dp_order / dp_launch / dp_collect (a kernel with two homes) */
+#include "sh_eng_cut.inc"      /* shared by those below: LaunchCut (a call cut into launches), dp_order / dp_launch / dp_collect (a kernel with two homes) */
 #include "sh_eng_map.inc"      /* block-based mapping (sh_map.h): map_to_sequence_* on the process-default engine, scrappie_hip_map_batch */
 #include "sh_eng_squig.inc"      /* squiggle matching (sh_squig.h): squiggle_match_* on the process-default engine, scrappie_hip_squiggle_match_batch */
 #include "sh_eng_sqnet.inc"      /* squiggle prediction (sh_sqnet.h): squiggle_r94 and its relatives on the process-default engine, scrappie_hip_squiggle_predict_batch */
+#include "sh_eng_events.inc"      /* event detection (sh_events.h): detect_events on the process-default engine, scrappie_hip_detect_events_batch */

@@ -33,6 +33,7 @@ extern "C" int scrappie_hip_debug_option(scrappie_hip_engine *e, const char *nam
     else if (!strcmp(name, "tail_free_frac")) e->dbg_tail_free_frac = value / 1000.0;      /* what the helper engine's creation takes for the device's free share (in 1/1000) */
     else if (!strcmp(name, "squiggle_budget_kb")) e->dbg_squig_budget = value > 0 ? (size_t)value << 10 : 0;      /* device bytes per squiggle-matching launch (0: from free memory) */
     else if (!strcmp(name, "sqnet_budget_kb")) e->dbg_sqnet_budget = value > 0 ? (size_t)value << 10 : 0;      /* device bytes per squiggle-predicting launch (0: from free memory) */
+    else if (!strcmp(name, "events_budget_samples")) e->dbg_events_budget = value > 0 ? (size_t)value : 0;      /* sample slots per event-detection launch (0: from free memory) */
     else return set_err("debug_option: unknown option '%s'", name);
     return 0;
 }

@@ -599,3 +599,123 @@ void sh_squiggle_tables(const float *params, size_t npos, size_t ldp, float rate
     stay_pen[0] = mean_stay_pen;
     stay_pen[nfstate - 1] = mean_stay_pen;
 }
+
+/* ------------------------------------------------------------------ */
+/* event detection (event_detection.c)                                  */
+/* ------------------------------------------------------------------ */
+/* The host statement of detect_events: what the kernels of sh_events.h are held against bit for bit, and the reference's
+ * arithmetic with its types and its order of operations kept (no contraction: -ffp-contract=off).
+ *   running sums: sequential double additions of (double)x and (double)(x * x), the product rounded to float first;
+ *   t-statistic: window sums as double differences, the first window's mean and mean square divided in double and narrowed, the
+ *     second window's in float; the pooled variance summed left to right in double, narrowed, clamped at FLT_MIN, divided by w in
+ *     float; the statistic a double division by a double square root, narrowed;
+ *   peaks: the short and the long detector walk the two statistics together, the short one masking the long one; peaks are kept
+ *     in the order they are emitted;
+ *   events: cut at the peaks from the running sums; the length of an event is (float) of an unsigned 64-bit difference, which
+ *     wraps for a pair of peaks out of order, as the reference's size_t arithmetic does. */
+#include <float.h>
+
+const detector_param event_detection_defaults = {3, 6, 1.4f, 9.0f, 0.2f};
+
+void sh_event_sums(const float *x, size_t n, double *sum, double *sumsq) {
+    sum[0] = 0.0; sumsq[0] = 0.0;
+    for (size_t i = 0; i < n; i++) {
+        const float sq = x[i] * x[i];
+        sum[i + 1] = sum[i] + (double)x[i];
+        sumsq[i + 1] = sumsq[i] + (double)sq;
+    }
+}
+
+void sh_event_tstat(const double *sum, const double *sumsq, size_t n, size_t w, float *t) {
+    for (size_t i = 0; i < n; i++) t[i] = 0.0f;
+    if (n < 2 * w || w < 2) return;
+    const float wf = (float)w;
+    for (size_t i = w; i <= n - w; i++) {
+        double sum1 = sum[i], sumsq1 = sumsq[i];
+        if (i > w) { sum1 -= sum[i - w]; sumsq1 -= sumsq[i - w]; }
+        const float sum2 = (float)(sum[i + w] - sum[i]);
+        const float sumsq2 = (float)(sumsq[i + w] - sumsq[i]);
+        const float mean1 = (float)(sum1 / (double)wf);
+        const float mean2 = sum2 / wf;
+        const float m1sq = mean1 * mean1, m2sq = mean2 * mean2, msq2 = sumsq2 / wf;
+        double cv = sumsq1 / (double)wf - (double)m1sq;
+        cv = cv + (double)msq2;
+        cv = cv - (double)m2sq;
+        const float var = fmaxf((float)cv, FLT_MIN);
+        const float dm = mean2 - mean1;
+        const float vw = var / wf;
+        t[i] = (float)(fabs((double)dm) / sqrt((double)vw));
+    }
+}
+
+typedef struct { uint64_t masked_to; int64_t peak_pos; float peak_value, threshold; uint64_t window; int valid; } sh_detector;
+
+/* peaks[] takes at most n positions; returns their number */
+size_t sh_event_peaks(const float *t1, const float *t2, size_t n, const detector_param *p, uint32_t *peaks) {
+    sh_detector d[2] = {{0, -1, FLT_MAX, p->threshold1, p->window_length1, 0}, {0, -1, FLT_MAX, p->threshold2, p->window_length2, 0}};
+    const float *sig[2] = {t1, t2};
+    const float height = p->peak_height;
+    size_t np = 0;
+    for (size_t i = 0; i < n; i++)
+        for (int k = 0; k < 2; k++) {
+            sh_detector *q = &d[k];
+            if (q->masked_to >= i) continue;
+            const float v = sig[k][i];
+            if (q->peak_pos < 0) {
+                if (v < q->peak_value) q->peak_value = v;                       /* a deeper minimum */
+                else if (v - q->peak_value > height) { q->peak_value = v; q->peak_pos = (int64_t)i; }
+            } else {
+                if (v > q->peak_value) { q->peak_value = v; q->peak_pos = (int64_t)i; }
+                if (k == 0 && q->peak_value > q->threshold) {                   /* the short detector will fire: the long one starts over behind it */
+                    d[1].masked_to = (uint64_t)q->peak_pos + q->window;
+                    d[1].peak_pos = -1; d[1].peak_value = FLT_MAX; d[1].valid = 0;
+                }
+                if (q->peak_value - v > height && q->peak_value > q->threshold) q->valid = 1;
+                if (q->valid && (uint64_t)((int64_t)i - q->peak_pos) > q->window / 2) {
+                    if (np < n) peaks[np++] = (uint32_t)q->peak_pos;      /* (a detector fires at most every other sample: np <= n; the test keeps absurd parameters inside the list too) */
+                    q->peak_pos = -1; q->peak_value = v; q->valid = 0;
+                }
+            }
+        }
+    return np;
+}
+
+event_t sh_event_make(uint64_t start, uint64_t end, const double *sum, const double *sumsq) {
+    event_t ev;
+    memset(&ev, 0, sizeof ev);            /* (the struct's tail padding too: tables are compared as bytes) */
+    ev.pos = -1; ev.state = -1;
+    ev.start = start;
+    ev.length = (float)(end - start);
+    ev.mean = (float)(sum[end] - sum[start]) / ev.length;
+    const float dsq = (float)(sumsq[end] - sumsq[start]);
+    const float msq = ev.mean * ev.mean;
+    const float var = dsq / ev.length - msq;
+    ev.stdv = sqrtf(fmaxf(var, 0.0f));
+    return ev;
+}
+
+/* detect_events on x[0 .. n): .event == NULL where no event table exists (no peak: the reference reads peaks[-1] there; no samples; out of
+ * memory).  tstat1 / tstat2 (may be NULL): n floats each, the two statistics. */
+event_table scrappie_hip_detect_events_host(const float *x, size_t n, const detector_param *param, float *tstat1, float *tstat2) {
+    event_table et = {0, 0, 0, NULL};
+    const detector_param p = param ? *param : event_detection_defaults;
+    if (!x || n == 0 || n > (size_t)UINT32_MAX - 1) return et;
+    double *sum = malloc((n + 1) * sizeof(double)), *sumsq = malloc((n + 1) * sizeof(double));
+    float *t1 = malloc(n * sizeof(float)), *t2 = malloc(n * sizeof(float));
+    uint32_t *peaks = malloc(n * sizeof(uint32_t));
+    if (sum && sumsq && t1 && t2 && peaks) {
+        sh_event_sums(x, n, sum, sumsq);
+        sh_event_tstat(sum, sumsq, n, p.window_length1, t1);
+        sh_event_tstat(sum, sumsq, n, p.window_length2, t2);
+        if (tstat1) memcpy(tstat1, t1, n * sizeof(float));
+        if (tstat2) memcpy(tstat2, t2, n * sizeof(float));
+        const size_t np = sh_event_peaks(t1, t2, n, &p, peaks);
+        if (np > 0 && (et.event = malloc((np + 1) * sizeof(event_t))) != NULL) {
+            for (size_t k = 0; k <= np; k++)
+                et.event[k] = sh_event_make(k ? peaks[k - 1] : 0, k < np ? peaks[k] : n, sum, sumsq);
+            et.n = np + 1; et.start = 0; et.end = np + 1;
+        }
+    }
+    free(peaks); free(t2); free(t1); free(sumsq); free(sum);
+    return et;
+}
