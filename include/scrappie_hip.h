@@ -149,6 +149,19 @@ float decode_transducer(const_scrappie_matrix logpost, float stay_pen, float ski
                         float local_pen, int *seq, bool allow_slip);
 /* src/decode.c:449 -- calloc'd string, caller frees; NULL if every entry is a stay */
 char *overlapper(const int *seq, size_t n, int nkmer, int *pos);
+/* src/decode.h:8-19, src/decode.c:516, :645 -- the dwell correction of homopolymer lengths, the last step of `scrappie events`: host C
+ * (sh_host.c), what the device form (sh_dwell.h) is held against.  seq and dwell have n entries; et.event[et.start .. et.end) carry
+ * pos (overlapper's) and state (1 + seq) as scrappie_events.c:308-311 sets them; basecall_len is the strlen of the plain overlapper
+ * call.  calloc'd strings as strlen sees the reference's (a call that ends inside a homopolymer ends one base short of its length,
+ * decode.c:633-635), the caller frees; NULL where the reference is undefined: no k-mer in seq, a homopolymer count that is no int. */
+typedef struct {
+    float scale;
+    float base_adj[4];
+} dwell_model;
+char *dwell_corrected_overlapper(const int *seq, const int *dwell, int n, int nkmer, const dwell_model dm);
+char *homopolymer_dwell_correction(const event_table et, const int *seq, size_t nstate, size_t basecall_len);
+/* the homo_scale homopolymer_dwell_correction uses (decode.c:666-693), NAN for an empty table */
+float scrappie_hip_dwell_scale(const event_table et, size_t basecall_len);
 /* src/decode.c:836, :895, :928 */
 float decode_crf(const_scrappie_matrix trans, int *path);
 char *crfpath_to_basecall(int const *path, size_t npos, int *pos);
@@ -547,6 +560,19 @@ int scrappie_hip_debug_option(scrappie_hip_engine *e, const char *name, int valu
 long scrappie_hip_debug_stitch(scrappie_hip_engine *e, const int *path, const float *side, size_t nblock, int nstate, int crf,
                                char *bases, size_t cap, int *pos, int *redo);
 long long scrappie_hip_debug_fetch(scrappie_hip_engine *e, const char *what, void *dst, size_t nbytes);
+/* k_stitch_dwell (sh_dwell.h: the dwell-corrected stitching of the events path on the device) on a batch of reads given on the host,
+ * for the bit-exact tests against the compiled-reference fixtures; one launch, 64 reads to a wave.  Read i: nentry[i] events, its
+ * path of nentry[i] + ntrail entries (ntrail 0 or 1; the engine runs with 1) and its nentry[i] dwells end to end in paths / dwells,
+ * prior_num[i] (the last event's length + (float)(the span of the starts)), cap[i] bytes of the device's bases buffer (rounded up to
+ * 16; scrappie_hip_dwell_capacity is what the engine reserves), the reads' reservations end to end.  bases takes that whole buffer as the
+ * device leaves it (bases_off[i]: where read i's begins; both sized by the caller from the rounded caps), lengths[i] the bases
+ * (-1: no call; 0 with redo[i] = 1: the read did not fit cap[i] and is the host's), pos (may be NULL) overlapper's pos[], laid out like
+ * paths.  Returns 0, -1 on error. */
+int scrappie_hip_debug_stitch_dwell(scrappie_hip_engine *e, const int *paths, const int *dwells, const size_t *nentry, size_t nread, int ntrail,
+                                    const float *prior_num, int nstate, const size_t *cap, char *bases, size_t bases_bytes, int *lengths, int *pos,
+                                    int *redo);
+/* bytes of bases the engine reserves for a read whose path has nentry entries when the dwell correction is on */
+size_t scrappie_hip_dwell_capacity(size_t nentry);
 
 /* Posterior of one read on a given engine/model (what the per-read surface
  * calls): HOST matrix in reference layout. */
@@ -592,6 +618,14 @@ long long scrappie_hip_events_plan_scratch(const size_t *nsample, size_t n, long
  * first; starts[] the first position (in that order) of each launch; returns the number of launches (even if > cap), -1 if one read
  * alone exceeds the budget. */
 long scrappie_hip_events_plan_launches(const size_t *nsample, size_t n, size_t budget_slots, uint32_t *order, size_t *starts, size_t cap);
+/* `scrappie events` for a batch (scrappie_events.c:271-330): batched event detection (p NULL: event_detection_defaults), the features
+ * of each read on host threads (scrappie_hip_event_features; they stay on the host: the reference studentises with rsqrtps, whose bits
+ * are the CPU's own), the launch groups of the events model `model` with the homopolymer pass off and -- dwell_correction != 0 -- the
+ * stitching in dwell mode (sh_dwell.h), the calls in input order.  reads: pA, windows already trimmed.  out[i].nblock is the number of
+ * events; a read without events or without a k-mer has no call (basecall NULL).  params NULL: scrappie_hip_default_params (its
+ * homopolymer field is ignored).  Returns 0, -1 on error (nothing is returned then). */
+int scrappie_hip_basecall_events_batch(scrappie_hip_engine *e, int model, const raw_table *reads, size_t n, const detector_param *p,
+                                       const scrappie_hip_params *params, int dwell_correction, scrappie_hip_call *out);
 /* The host statement of detect_events (sh_host.c) on x[0 .. n): what the kernels are held against bit for bit (tests, tools; the
  * per-read surface never falls back to it: without a device detect_events fails).  .event NULL where there is no peak.  tstat1 / tstat2 (may be NULL): n floats each, the two statistics. */
 event_table scrappie_hip_detect_events_host(const float *x, size_t n, const detector_param *p, float *tstat1, float *tstat2);

@@ -91,6 +91,10 @@ class DetectorParam(C.Structure):   # event_detection.h:6-12; the defaults are e
         super().__init__(window_length1, window_length2, threshold1, threshold2, peak_height)
 
 
+class DwellModel(C.Structure):      # decode.h:8-11
+    _fields_ = [("scale", C.c_float), ("base_adj", C.c_float * 4)]
+
+
 class _EventResult(C.Structure):
     _fields_ = [("events", _EventTable), ("status", C.c_int)]
 
@@ -301,6 +305,21 @@ def lib():
     L.scrappie_hip_events_plan_scratch.argtypes = [C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(C.c_longlong)]
     L.scrappie_hip_events_plan_launches.restype = C.c_long
     L.scrappie_hip_events_plan_launches.argtypes = [C.POINTER(C.c_size_t), C.c_size_t, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_size_t), C.c_size_t]
+    L.homopolymer_dwell_correction.restype = C.c_void_p
+    L.homopolymer_dwell_correction.argtypes = [_EventTable, ip, C.c_size_t, C.c_size_t]
+    L.dwell_corrected_overlapper.restype = C.c_void_p
+    L.dwell_corrected_overlapper.argtypes = [ip, ip, C.c_int, C.c_int, DwellModel]
+    L.scrappie_hip_dwell_scale.restype = C.c_float
+    L.scrappie_hip_dwell_scale.argtypes = [_EventTable, C.c_size_t]
+    L.scrappie_hip_dwell_capacity.restype = C.c_size_t
+    L.scrappie_hip_dwell_capacity.argtypes = [C.c_size_t]
+    L.scrappie_hip_debug_stitch_dwell.argtypes = [C.c_void_p, ip, ip, sp, C.c_size_t, C.c_int, fp, C.c_int, sp, C.c_void_p, C.c_size_t, ip, ip, ip]
+    L.scrappie_hip_basecall_events_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(_RawTable), C.c_size_t, C.POINTER(DetectorParam),
+                                                     C.POINTER(Params), C.c_int, C.POINTER(_Call)]
+    L.sh_dwell_stitch.restype = C.c_void_p       # (internal: the engine's host fallback, for the tests through dwell_stitch_host)
+    L.sh_dwell_stitch.argtypes = [ip, ip, C.c_int, C.c_int, C.c_int, C.c_float, ip]
+    L.scrappie_hip_read_raw.restype = _RawTable
+    L.scrappie_hip_read_raw.argtypes = [C.c_char_p, C.c_bool]
     L.scrappie_hip_launch_form_counts.restype = None
     L.scrappie_hip_launch_form_counts.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     _lib = L
@@ -520,6 +539,73 @@ def event_features(events, start=0, end=None):
     if L.scrappie_hip_event_features(et, out.ctypes.data_as(C.POINTER(C.c_float))) != 0:
         raise RuntimeError("event_features failed")
     return out
+
+
+def _event_table(events):
+    """the ctypes event_table over a structured array with the event_t layout, and the array that keeps its memory alive"""
+    ev = np.ascontiguousarray(events)
+    if ev.dtype.itemsize != C.sizeof(_Event):
+        raise ValueError("events must have the event_t layout (%d bytes per event)" % C.sizeof(_Event))
+    return _EventTable(len(ev), 0, len(ev), C.cast(ev.ctypes.data, C.POINTER(_Event))), ev
+
+
+def dwell_corrected_overlapper(path, dwell, nkmer, scale, base_adj=(0.0, 0.0, 0.0, 0.0)):
+    """decode.c:516: the k-mer stitching of `path` with every homopolymer entered behind the first k-mer given
+    round(its dwell / scale) bases; `dwell`: an int per path entry.  The string as strlen sees the reference's (a call
+    that ends inside a homopolymer is one base short of its length); None where the path has no k-mer."""
+    path = np.ascontiguousarray(path, dtype=np.int32)
+    dwell = np.ascontiguousarray(dwell, dtype=np.int32)
+    if len(path) != len(dwell):
+        raise ValueError("a dwell per path entry")
+    ip = C.POINTER(C.c_int)
+    dm = DwellModel(scale, (C.c_float * 4)(*base_adj))
+    return _take_string(lib().dwell_corrected_overlapper(path.ctypes.data_as(ip), dwell.ctypes.data_as(ip), len(path), nkmer, dm))
+
+
+def homopolymer_dwell_correction(events, path, nstate, basecall_len):
+    """decode.c:645: the dwell-corrected call of a read from its events -- annotated with `pos` (overlapper's) and
+    `state` (1 + path), as scrappie_events.c:308-311 leaves them -- its path (an entry per event) and the length of
+    its plain call.  None where the path has no k-mer."""
+    et, keep = _event_table(events)
+    path = np.ascontiguousarray(path, dtype=np.int32)
+    if len(path) < len(keep):
+        raise ValueError("a path entry per event")
+    return _take_string(lib().homopolymer_dwell_correction(et, path.ctypes.data_as(C.POINTER(C.c_int)), nstate, basecall_len))
+
+
+def dwell_scale(events, basecall_len):
+    """the homo_scale homopolymer_dwell_correction divides the dwells by (decode.c:666-693), a float32"""
+    et, keep = _event_table(events)
+    return np.float32(lib().scrappie_hip_dwell_scale(et, basecall_len))
+
+
+def dwell_stitch_host(path, dwell, nstate, prior_num):
+    """What the engine's host fallback makes of a read it holds as arrays (sh_host.c: sh_dwell_stitch): `path` has len(dwell)
+    entries, or one more (the decoder's last, without an event); returns (bases or None, overlapper's pos[])."""
+    path = np.ascontiguousarray(path, dtype=np.int32)
+    dwell = np.ascontiguousarray(dwell, dtype=np.int32)
+    if len(path) - len(dwell) not in (0, 1):
+        raise ValueError("a path of len(dwell) entries, or one more")
+    ip = C.POINTER(C.c_int)
+    pos = np.zeros(len(path), np.int32)
+    s = lib().sh_dwell_stitch(path.ctypes.data_as(ip), dwell.ctypes.data_as(ip), len(dwell), len(path) - len(dwell), nstate, float(prior_num),
+                              pos.ctypes.data_as(ip))
+    return _take_string(s), pos
+
+
+def read_raw(path, scale_to_pA=True):
+    """A read's samples from a fast5 file (or a headerless .f32 / .i16 file) as (float32 array, uuid or ''); None where it cannot be read."""
+    rt = lib().scrappie_hip_read_raw(os.fsencode(path), scale_to_pA)
+    if not rt.raw:
+        return None
+    x = np.ctypeslib.as_array(rt.raw, shape=(rt.n,)).copy()
+    _libc.free(C.cast(rt.raw, C.c_void_p))
+    return x, (rt.uuid or b"").decode()
+
+
+def dwell_capacity(nentry):
+    """bytes of bases the engine reserves for a read of `nentry` path entries when the dwell correction is on"""
+    return int(lib().scrappie_hip_dwell_capacity(nentry))
 
 
 def register_model(name, path):
@@ -1139,6 +1225,37 @@ class Engine(object):
             raise RuntimeError("debug_stitch: " + last_error())
         return (buf.value.decode() if n >= 0 else None), pos, redo.value
 
+    def debug_stitch_dwell(self, paths, dwells, prior_num, nstate=1025, cap=None, trailing=0):
+        """k_stitch_dwell (the dwell-corrected stitching of the events path) on a batch of reads given on the host, one
+        launch: paths[i] has len(dwells[i]) + trailing entries, prior_num[i] is the last event's length + the span of
+        the starts, cap[i] the bytes of the device's bases buffer read i owns (default: what the engine reserves).
+        Returns (bases, lengths, pos, redo, buffer): the call of each read (None: no call, or left to the host),
+        the lengths and flags as the device wrote them, overlapper's pos[] per read, and per read the whole of its
+        reservation as the device left it."""
+        n = len(paths)
+        nent = np.array([len(d) for d in dwells], dtype=np.uintp)
+        for pth, d in zip(paths, dwells):
+            if len(pth) != len(d) + trailing:
+                raise ValueError("a path of len(dwell) + trailing entries")
+        cap = np.array([dwell_capacity(len(pth)) for pth in paths] if cap is None else cap, dtype=np.uintp)
+        rcap = (cap + 15) // 16 * 16
+        boff = np.concatenate(([0], np.cumsum(rcap))).astype(np.int64)
+        flat_p = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int32) for x in paths]), dtype=np.int32)
+        flat_d = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int32) for x in dwells]), dtype=np.int32)
+        num = np.ascontiguousarray(prior_num, dtype=ftype)
+        buf = np.zeros(int(boff[-1]), dtype=np.uint8)
+        lengths, redo = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        pos = np.zeros(len(flat_p), np.int32)
+        ip, sp = C.POINTER(C.c_int), C.POINTER(C.c_size_t)
+        if lib().scrappie_hip_debug_stitch_dwell(self._h, flat_p.ctypes.data_as(ip), flat_d.ctypes.data_as(ip), nent.ctypes.data_as(sp), n, trailing,
+                                                 num.ctypes.data_as(C.POINTER(C.c_float)), nstate, cap.ctypes.data_as(sp), buf.ctypes.data, len(buf),
+                                                 lengths.ctypes.data_as(ip), pos.ctypes.data_as(ip), redo.ctypes.data_as(ip)) != 0:
+            raise RuntimeError("debug_stitch_dwell: " + last_error())
+        raw = [buf[boff[i]:boff[i + 1]] for i in range(n)]
+        bases = [bytes(raw[i][:lengths[i]]).decode() if lengths[i] >= 0 and not redo[i] else None for i in range(n)]
+        poff = np.concatenate(([0], np.cumsum([len(x) for x in paths])))
+        return bases, lengths, [pos[poff[i]:poff[i + 1]] for i in range(n)], redo, raw
+
     def posterior(self, signal, model='rgrgr_r94', min_prob=1e-5, tempW=1.0, tempb=1.0, log=True):
         """(T, NS) array, reference state order (stay last)."""
         rt = RawTable(signal)
@@ -1288,12 +1405,24 @@ class Engine(object):
         """the last detect_events call's time (ms, summed over launches): staging + upload, the kernels, tables to the host"""
         return self._timing(lib().scrappie_hip_event_timing, ('upload_ms', 'detect_ms', 'download_ms'))
 
-    def basecall_events(self, signals, model='nanonet_events', detector=None, **params):
-        """Basecall from events, as `scrappie events` does without its dwell correction (scrappie_events.c:278-300): detect_events
-        (batched) -> event_features -> the events model's posterior -> decode_transducer -> overlapper, the last three as
-        one `basecall` of the feature matrices with the homopolymer pass off.  `signals`: pA, windows already trimmed;
+    def basecall_events(self, signals, model='nanonet_events', detector=None, dwell=False, **params):
+        """Basecall from events, as `scrappie events` does (scrappie_events.c:278-321): detect_events (batched) -> event_features
+        -> the events model's posterior -> decode_transducer -> overlapper, the last three as one `basecall` of the feature
+        matrices with the homopolymer pass off -- and, with `dwell`, its dwell correction of homopolymer lengths, the whole as one
+        scrappie_hip_basecall_events_batch with the stitching in dwell mode.  `signals`: pA, windows already trimmed;
         `detector`: a dict of detect_events' parameters; `params`: fields of `Params` (min_prob, skip_pen, ...).  Returns
         the list `basecall` returns, None where a read has no events or no call."""
+        if dwell:
+            n = len(signals)
+            rts, keep = _raw_tables(signals)
+            dp = DetectorParam(**(detector or {}))
+            kw = dict(homopolymer=0)
+            kw.update(params)
+            p = self.default_params(**kw)
+            calls = (_Call * max(n, 1))()
+            if lib().scrappie_hip_basecall_events_batch(self._h, self._models[model], rts, n, C.byref(dp), C.byref(p), 1, calls) != 0:
+                raise RuntimeError("basecall_events_batch: " + last_error())
+            return self._unpack(calls, n, p.want_pos)
         evs = self.detect_events(signals, **(detector or {}))
         keep = [i for i, ev in enumerate(evs) if ev is not None]
         kw = dict(homopolymer=0)

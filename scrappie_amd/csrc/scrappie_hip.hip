@@ -240,7 +240,19 @@ extern "C" void sh_set_error(const char *fmt, ...) {       /* (sh_host.c: the ho
 /* ------------------------------------------------------------------ */
 /* engine                                                               */
 /* ------------------------------------------------------------------ */
+/* The dwell correction of an events launch group (sh_dwell.h): what its stage hands over beside the feature matrices (GroupArgs -> run_pipeline -> build_group).  Per read of the group, in the
+ * group's own order: where its dwells are in d_dwell, the prior's numerator, and the dwells on the host -- what the host statement needs for a read the
+ * device leaves to it; they outlive the group's collection (the call owns them). */
+struct DwellJob {
+    bool on = false;
+    const int *d_dwell = nullptr;
+    std::vector<uint64_t> off;
+    std::vector<float> num;
+    std::vector<const int *> host;
+};
+
 struct LaunchGroup {
+    DwellJob dw;                  /* events with the dwell correction on: the group's dwells (build_group takes its caller's) */
     size_t n = 0, npad = 0, ntile = 0;
     long long ncb = 0;            /* total column blocks */
     long long nseq = 0;           /* total path ints */
@@ -330,10 +342,11 @@ struct Slot {
     DBuf d_edge;                     /* k_gru_conv: where each read's convolution windows end (ShConvFuse::edge) */
     DBuf d_fscore, d_seq, d_hp;
     DBuf d_pos, d_bases, d_blen, d_redo;     /* k_stitch: pos / bases / lengths / host-decides flags */
+    DBuf d_dwmeta; HBuf h_dwmeta;            /* k_walk_dwell_out: dwell offsets, prior numerators and capacities in tiled order */
     HBuf h_meta, h_sig, h_err, h_bad, h_edge, h_seq, h_score, h_hp, h_pos, h_bases, h_blen, h_redo;
     size_t pinned_bytes() const {
         size_t tot = 0;
-        for (const HBuf *h : {&h_meta, &h_sig, &h_err, &h_bad, &h_edge, &h_seq, &h_score, &h_hp, &h_pos, &h_bases, &h_blen, &h_redo}) tot += h->cap;
+        for (const HBuf *h : {&h_meta, &h_sig, &h_err, &h_bad, &h_edge, &h_seq, &h_score, &h_hp, &h_pos, &h_bases, &h_blen, &h_redo, &h_dwmeta}) tot += h->cap;
         return tot;
     }
     bool create_events() {
@@ -407,6 +420,7 @@ struct scrappie_hip_engine {
     bool dbg_dump_final = false;     /* decoders leave every tile's final scores in d_vstate */
     int dbg_fail_run = 0;            /* k > 0: the k-th next launch group is refused (failure-path tests) */
     bool dbg_redo_all = false;       /* treat every read as one k_stitch left to the host (tests the fallback) */
+    bool dbg_dwell_tight = false;    /* dwell-mode groups reserve 16 bytes of bases a read: longer calls overflow on the device and go to the host (tests that path) */
     int dbg_gru_tiles = 0;           /* 1 / 2: tiles per workgroup of k_gru_proj whatever the schedules say (0: choose) */
     bool dbg_force_f32 = false;      /* models loaded from now on run their GRU layers on the exact-fp32 kernels (as if out of the split products' range) */
     int dbg_gru32 = -1;              /* 0 / 1: recurrent layers on 16- / 32-read tiles whatever the build's default (-1) */
@@ -602,4 +616,4 @@ extern "C" scrappie_hip_params scrappie_hip_default_params(void) {
 #include "sh_eng_map.inc"      /* block-based mapping (sh_map.h): map_to_sequence_* on the process-default engine, scrappie_hip_map_batch */
 #include "sh_eng_squig.inc"      /* squiggle matching (sh_squig.h): squiggle_match_* on the process-default engine, scrappie_hip_squiggle_match_batch */
 #include "sh_eng_sqnet.inc"      /* squiggle prediction (sh_sqnet.h): squiggle_r94 and its relatives on the process-default engine, scrappie_hip_squiggle_predict_batch */
-#include "sh_eng_events.inc"      /* event detection (sh_events.h): detect_events on the process-default engine, scrappie_hip_detect_events_batch */
+#include "sh_eng_events.inc"      /* event detection (sh_events.h): detect_events on the process-default engine, scrappie_hip_detect_events_batch; `scrappie events` for a batch (scrappie_hip_basecall_events_batch) */

@@ -767,17 +767,19 @@ int main_squiggle(int argc, char **argv) __attribute__((weak));
 int main_mappy(int argc, char **argv) __attribute__((weak));
 /* scrappie_event_table.c; weak for the same reason */
 int main_event_table(int argc, char **argv) __attribute__((weak));
+/* scrappie_events.c; weak for the same reason */
+int main_events(int argc, char **argv) __attribute__((weak));
 
 /* subcommand dispatch (src/scrappie.c:13, scrappie_subcommands.c:6): `raw`, `seqmappy`,
- * `squiggle`, `mappy` and `event_table` are part of this build */
+ * `squiggle`, `mappy`, `event_table` and `events` are part of this build */
 int main(int argc, char **argv) {
     if (argc < 2 || 0 == strcmp(argv[1], "help") || 0 == strcmp(argv[1], "--help")) {
         puts("Usage: scrappie <subcommand> [options]\n  raw        Basecall from raw signal (MI355X)\n"
              "  seqmappy   Map reads to sequences (local-global Viterbi on the posterior)\n"
              "  squiggle   Predict the squiggle of base sequences\n  mappy      Map a read's signal to the squiggle predicted for a sequence\n"
              "  event_table  Detect events and print the event table of each read\n"
-             "  version    Print version\n"
-             "The reference's other subcommand (events)\nis not part of this build.");
+             "  events     Basecall via events, with the dwell correction of homopolymer lengths\n"
+             "  version    Print version");
         return argc < 2 ? EXIT_FAILURE : EXIT_SUCCESS;
     }
     if (0 == strcmp(argv[1], "version") || 0 == strcmp(argv[1], "--version")) { puts(SCRAPPIE_HIP_VERSION); return EXIT_SUCCESS; }
@@ -786,6 +788,7 @@ int main(int argc, char **argv) {
     if (0 == strcmp(argv[1], "squiggle") && main_squiggle) return main_squiggle(argc - 1, argv + 1);
     if (0 == strcmp(argv[1], "mappy") && main_mappy) return main_mappy(argc - 1, argv + 1);
     if (0 == strcmp(argv[1], "event_table") && main_event_table) return main_event_table(argc - 1, argv + 1);
-    fprintf(stderr, "scrappie: subcommand \"%s\" is not part of this build (only `raw`, `seqmappy`, `squiggle`, `mappy` and `event_table`)\n", argv[1]);
+    if (0 == strcmp(argv[1], "events") && main_events) return main_events(argc - 1, argv + 1);
+    fprintf(stderr, "scrappie: subcommand \"%s\" is not part of this build (only `raw`, `seqmappy`, `squiggle`, `mappy`, `event_table` and `events`)\n", argv[1]);
     return EXIT_FAILURE;
 }

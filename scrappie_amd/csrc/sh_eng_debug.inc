@@ -1,5 +1,5 @@
 /* sh_eng_debug.inc -- part of scrappie_hip.hip (one translation unit, included from there in this order; not compiled alone):
- * measurement / test hooks: decoder and trunk inputs, debug_option / debug_fetch / debug_stitch. */
+ * measurement / test hooks: decoder and trunk inputs, debug_option / debug_fetch / debug_stitch / debug_stitch_dwell. */
 
 extern "C" int scrappie_hip_set_decoder_input(scrappie_hip_engine *e, const float *d_prob, const uint64_t *prob_off, size_t n_prob) {
     if (!e) return set_err("set_decoder_input: null engine");
@@ -23,6 +23,7 @@ extern "C" int scrappie_hip_debug_option(scrappie_hip_engine *e, const char *nam
     else if (!strcmp(name, "dump_final")) e->dbg_dump_final = value != 0;
     else if (!strcmp(name, "fail_run")) e->dbg_fail_run = value;
     else if (!strcmp(name, "redo_all")) e->dbg_redo_all = value != 0;
+    else if (!strcmp(name, "dwell_tight")) e->dbg_dwell_tight = value != 0;
     else if (!strcmp(name, "gru_tiles")) e->dbg_gru_tiles = value;
     else if (!strcmp(name, "force_f32_layers")) e->dbg_force_f32 = value != 0;
 #ifdef SH_EXPERIMENTS
@@ -132,6 +133,68 @@ extern "C" long scrappie_hip_debug_stitch(scrappie_hip_engine *e, const int *pat
         if (pos && !crf && hipMemcpy(pos, dpos.p, (T + 1) * 4, hipMemcpyDeviceToHost) != hipSuccess) return -2;
     }
     return len;
+}
+
+/* k_stitch_dwell on a batch of reads given on the host (test hook: the device form of the dwell correction against the compiled-reference
+ * fixtures and the host statement).  One launch, 64 reads to a wave; see include/scrappie_hip.h for the layout. */
+extern "C" int scrappie_hip_debug_stitch_dwell(scrappie_hip_engine *e, const int *paths, const int *dwells, const size_t *nentry, size_t nread, int ntrail,
+                                               const float *prior_num, int nstate, const size_t *cap, char *bases, size_t bases_bytes, int *lengths, int *pos,
+                                               int *redo) {
+    if (!e || !paths || !dwells || !nentry || !prior_num || !cap || !bases || !lengths || nread == 0 || nread > (1u << 20) || (ntrail != 0 && ntrail != 1))
+        return set_err("debug_stitch_dwell: bad argument");
+    if (nstate != 5 && nstate != 17 && nstate != 65 && nstate != 257 && nstate != 1025) return set_err("debug_stitch_dwell: %d states (4^k + 1 with k <= 5)", nstate);
+    (void)hipSetDevice(e->device);
+    std::lock_guard<std::mutex> lk(e->mu);
+    const size_t npad = (nread + 63) / 64 * 64;
+    /* per-read words: [seq_off | bases_off | dwell_off] (long long x npad each), prior_num (float x npad), nd, cap (int x npad each) */
+    std::vector<char> hm(npad * 36, 0);
+    long long *seq_off = (long long *)hm.data(), *bases_off = seq_off + npad, *dwell_off = bases_off + npad;
+    float *num = (float *)(dwell_off + npad);
+    int *nd = (int *)(num + npad), *capi = nd + npad;
+    size_t nseq = 0, ndw = 0, nb = 0;
+    for (size_t i = 0; i < nread; i++) {
+        const size_t c = (cap[i] + 15) & ~(size_t)15;
+        if (nentry[i] == 0 || nentry[i] > (1u << 28) || c == 0 || c > (1u << 30)) return set_err("debug_stitch_dwell: read %zu: %zu entries, %zu bytes", i, nentry[i], cap[i]);
+        seq_off[i] = (long long)nseq; nseq += nentry[i] + (size_t)ntrail;
+        dwell_off[i] = (long long)ndw; ndw += nentry[i];
+        bases_off[i] = (long long)nb; nb += c;
+        num[i] = prior_num[i]; nd[i] = (int)nentry[i]; capi[i] = (int)c;
+    }
+    if (nb > bases_bytes) return set_err("debug_stitch_dwell: the reservations take %zu bytes, bases holds %zu", nb, bases_bytes);
+    DBuf dmeta, dseq, ddw, dpos, dbases, dblen, dredo;      /* (freed on every way out) */
+    if (dmeta.ensure(hm.size()) || dseq.ensure(nseq * 4) || ddw.ensure(ndw * 4) || dpos.ensure(nseq * 4) || dbases.ensure(nb) ||
+        dblen.ensure(npad * 4) || dredo.ensure(npad * 4)) return -1;
+    hipStream_t s = e->stream;
+    HIPCHK(hipMemcpyAsync(dmeta.p, hm.data(), hm.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dseq.p, paths, nseq * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ddw.p, dwells, ndw * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(dbases.p, 0, nb, s));
+    HIPCHK(hipMemsetAsync(dpos.p, 0, nseq * 4, s));
+    HIPCHK(hipMemsetAsync(dredo.p, 0, npad * 4, s));
+    HIPCHK(sh_stream_wait(s));                      /* sources are pageable caller memory */
+    char *d = dmeta.as<char>();
+    ShStitchArgs sa{};
+    sa.seq = dseq.as<int>(); sa.seq_off = (const long long *)d;
+    sa.hp = nullptr; sa.hp_off = nullptr;
+    sa.pos = pos ? dpos.as<int>() : nullptr;
+    sa.bases = dbases.as<char>(); sa.bases_off = (const long long *)(d + npad * 8);
+    sa.blen = dblen.as<int>(); sa.redo = dredo.as<unsigned>();
+    sa.npad = (int)nread; sa.nstate = nstate; sa.crf = 0; sa.sstride = 1;
+    ShDwellArgs da{};
+    da.dwell = ddw.as<int>(); da.dwell_off = (const long long *)(d + npad * 16);
+    da.prior_num = (const float *)(d + npad * 24);
+    da.nd = (const int *)(d + npad * 28); da.cap = (const int *)(d + npad * 32);
+    da.ntrail = ntrail;
+    hipLaunchKernelGGL(k_stitch_dwell, dim3((unsigned)(npad / 64)), dim3(64), 0, s, sa, da);
+    HIPCHK(hipGetLastError());
+    std::vector<unsigned> hredo(nread);
+    HIPCHK(hipMemcpyAsync(lengths, dblen.p, nread * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(hredo.data(), dredo.p, nread * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(bases, dbases.p, nb, hipMemcpyDeviceToHost, s));
+    if (pos) HIPCHK(hipMemcpyAsync(pos, dpos.p, nseq * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(sh_stream_wait(s));
+    if (redo) for (size_t i = 0; i < nread; i++) redo[i] = (int)hredo[i];
+    return 0;
 }
 
 extern "C" void scrappie_hip_free_calls(scrappie_hip_call *calls, size_t n) {

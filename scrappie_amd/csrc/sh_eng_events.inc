@@ -2,7 +2,8 @@
  * event detection (sh_events.h).  scrappie_hip_detect_events_batch sorts a call's reads by length (a wave of the serial kernels holds
  * 64 reads and lasts as long as its longest), cuts them into launches under a slot budget (LaunchCut, sh_eng_cut.inc) and runs each
  * launch as signals up -> k_ev_sums -> k_ev_tstat -> k_ev_peaks -> peak counts back -> k_ev_events -> event tables back.  The
- * reference's detect_events is a batch of one on the process-default engine. */
+ * reference's detect_events is a batch of one on the process-default engine.  At the end: scrappie_hip_basecall_events_batch, `scrappie events`
+ * for a batch, with the stitching in dwell mode (sh_dwell.h). */
 
 /* host side of one launch: the reads' records in device order (who[] of the cutter says whose) */
 struct EvPlan {
@@ -201,4 +202,97 @@ extern "C" event_table detect_events(raw_table const rt, detector_param const ed
     if (scrappie_hip_detect_events_batch(e, &rt, 1, &edparam, &res)) return none;
     if (res.status == 1) set_err("detect_events: no peak in %zu samples, so no event table (the reference is undefined there)", rt.end - rt.start);
     return res.events;
+}
+
+/* ------------------------------------------------------------------ */
+/* `scrappie events` for a batch (scrappie_events.c:271-330)            */
+/* ------------------------------------------------------------------ */
+/* Detection (batched, above) -> features on host threads (sh_host.c; they stay there: the reference studentises with rsqrtps, whose bits are the
+ * CPU's own) -> the events model's launch groups, as scrappie_hip_basecall_batch cuts them, with the stitching in dwell mode (sh_dwell.h) when
+ * asked.  A group's dwells -- (int)event.length, 4 bytes an event -- ride behind its feature matrices (48 bytes an event) in the same staging
+ * buffer and the same upload; the group's DwellJob (GroupArgs) says where, in the order the length sort and the cut have given the group. */
+extern "C" int scrappie_hip_basecall_events_batch(scrappie_hip_engine *e, int model, const raw_table *reads, size_t n, const detector_param *dp,
+                                                  const scrappie_hip_params *params, int dwell_correction, scrappie_hip_call *out) {
+    if (!e || (n && (!reads || !out))) return set_err("basecall_events_batch: null argument");
+    Model *m = get_model(e, model);
+    if (!m) return -1;
+    if (m->arch != 3) return set_err("basecall_events_batch: the model is not an events model");
+    for (size_t i = 0; i < n; i++) { out[i].score = NAN; out[i].nblock = 0; out[i].basecall = nullptr; out[i].basecall_length = 0; out[i].pos = nullptr; }
+    if (n == 0) return 0;
+    std::vector<scrappie_hip_event_result> evs(n);
+    if (scrappie_hip_detect_events_batch(e, reads, n, dp, evs.data())) return -1;
+    struct FreeEvents { std::vector<scrappie_hip_event_result> &v; ~FreeEvents() { scrappie_hip_free_event_results(v.data(), v.size()); } } free_events{evs};
+    const size_t per = (size_t)m->nfeat;
+    std::vector<size_t> keep, at;      /* the reads with an event table, and where each one's events begin in the flat arrays */
+    size_t nev = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (!evs[i].events.event || evs[i].events.n == 0) continue;
+        if (evs[i].events.n > (size_t)INT32_MAX / 16) return set_err("basecall_events_batch: %zu events in read %zu", evs[i].events.n, i);
+        keep.push_back(i); at.push_back(nev); nev += evs[i].events.n;
+    }
+    const size_t nk = keep.size();
+    if (nk == 0) return 0;
+    std::vector<float> feat(nev * per), num(nk);
+    std::vector<int> dwell(dwell_correction ? nev : 0);
+    std::vector<uint32_t> len(nk);
+    std::atomic<int> feat_failed{0};
+    {
+        auto part = [&](size_t a, size_t b) {
+            for (size_t k = a; k < b; k++) {
+                const event_table &et = evs[keep[k]].events;
+                len[k] = (uint32_t)et.n;
+                if (scrappie_hip_event_features(et, feat.data() + at[k] * per)) feat_failed.store(1);
+                num[k] = sh_dwell_prior_num(et.event, et.n);
+                if (dwell_correction) for (size_t j = 0; j < et.n; j++) dwell[at[k] + j] = (int)et.event[j].length;
+            }
+        };
+        const unsigned nthr = nev > 65536 ? std::max(1u, std::min(host_threads(), 16u)) : 1u;
+        if (nthr == 1) part(0, nk);
+        else {
+            std::vector<std::thread> th;
+            const size_t step = (nk + nthr - 1) / nthr;
+            for (unsigned t = 0; t < nthr; t++) { const size_t a = t * step, b = std::min(nk, a + step); if (a < b) th.emplace_back(part, a, b); }
+            for (auto &x : th) x.join();
+        }
+    }
+    if (feat_failed.load()) return set_err("basecall_events_batch: event features failed");
+    scrappie_hip_params pp = params ? *params : scrappie_hip_default_params();
+    pp.homopolymer = 0;                          /* the posterior-mean homopolymer pass is `scrappie raw`'s */
+    (void)hipSetDevice(e->device);
+    std::lock_guard<std::mutex> lk(e->call_mu);
+    DwellJob job[2];                             /* per staging slot: build_group copies it when the group is enqueued */
+    std::vector<uint64_t> off[2];
+    std::vector<uint32_t> glen[2];
+    bool used[2] = {false, false};
+    return run_groups(e, model, m, len.data(), nk, &pp, out, [&](int k, const uint32_t *idx, size_t cnt, GroupArgs &a) {
+        Slot &st = e->slots[k];
+        if (used[k] && e->ev_ok) HIPCHK(sh_event_wait(st.up));      /* staging buffer k was last read by the upload of group g-2 */
+        off[k].resize(cnt); glen[k].resize(cnt);
+        size_t total = 0, gev = 0;
+        for (size_t i = 0; i < cnt; i++) { glen[k][i] = len[idx[i]]; off[k][i] = total; total += (size_t)glen[k][i] * per; gev += glen[k][i]; }
+        const size_t words = total + (dwell_correction ? gev : 0);
+        if (st.h_sig.ensure(std::max<size_t>(words, 1) * 4) || st.d_signal.ensure(std::max<size_t>(words, 1) * 4)) return -1;
+        float *hs = st.h_sig.as<float>();
+        for (size_t i = 0; i < cnt; i++) memcpy(hs + off[k][i], feat.data() + at[idx[i]] * per, (size_t)glen[k][i] * per * 4);
+        if (dwell_correction) {
+            int *hd = (int *)(hs + total);
+            DwellJob &j = job[k];
+            j.on = true; j.d_dwell = (const int *)(st.d_signal.as<float>() + total);
+            j.off.resize(cnt); j.num.resize(cnt); j.host.resize(cnt);
+            size_t w = 0;
+            for (size_t i = 0; i < cnt; i++) {
+                const int *src = dwell.data() + at[idx[i]];
+                memcpy(hd + w, src, (size_t)glen[k][i] * 4);
+                j.off[i] = w; j.num[i] = num[idx[i]]; j.host[i] = src;
+                w += glen[k][i];
+            }
+        }
+        hipStream_t us = e->ev_ok ? e->ustream : e->stream;
+        HIPCHK(hipMemcpyAsync(st.d_signal.p, hs, words * 4, hipMemcpyHostToDevice, us));
+        if (e->ev_ok) { HIPCHK(hipEventRecord(st.up, us)); HIPCHK(hipStreamWaitEvent(e->stream, st.up, 0)); HIPCHK(hipStreamWaitEvent(e->pstream, st.up, 0)); }
+        else HIPCHK(sh_stream_wait(e->stream));
+        used[k] = true;
+        a.d = st.d_signal.as<float>(); a.off = off[k].data(); a.len = glen[k].data(); a.dw = dwell_correction ? &job[k] : nullptr;
+        return 0;
+    }, false, keep.data());
 }

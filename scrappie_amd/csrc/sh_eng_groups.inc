@@ -4,8 +4,8 @@
 /* ------------------------------------------------------------------ */
 /* public batched surface                                               */
 /* ------------------------------------------------------------------ */
-extern "C" long scrappie_hip_run_device(scrappie_hip_engine *e, int model, const float *d_signal, const uint64_t *offsets,
-                                        const uint32_t *lengths, size_t n, const scrappie_hip_params *p) {
+static long run_device(scrappie_hip_engine *e, int model, const float *d_signal, const uint64_t *offsets, const uint32_t *lengths, size_t n,
+                       const scrappie_hip_params *p, const DwellJob *dw) {
     Model *m = get_model(e, model);
     if (!m) return -1;
     scrappie_hip_params dp = scrappie_hip_default_params();
@@ -13,17 +13,24 @@ extern "C" long scrappie_hip_run_device(scrappie_hip_engine *e, int model, const
     if (n > e->max_launch_reads) { set_err("run_device: %zu reads exceed max_launch_reads %zu", n, e->max_launch_reads); return -1; }
     if (e->dbg_fail_run > 0 && --e->dbg_fail_run == 0) { set_err("run_device: injected failure (debug option fail_run)"); return -1; }
     const HostStamp stamp;
-    if (run_pipeline(e, m, d_signal, offsets, lengths, n, p, STOP_NONE, 5, nullptr)) return -1;
+    if (run_pipeline(e, m, d_signal, offsets, lengths, n, p, STOP_NONE, 5, nullptr, dw)) return -1;
     stamp("run_device", " on the host");
     return (long)e->current().lg.ncb;
 }
+extern "C" long scrappie_hip_run_device(scrappie_hip_engine *e, int model, const float *d_signal, const uint64_t *offsets,
+                                        const uint32_t *lengths, size_t n, const scrappie_hip_params *p) {
+    return run_device(e, model, d_signal, offsets, lengths, n, p, nullptr);
+}
 
 /* D2 + D3 of one read on the host (sh_host.c): what k_stitch does on the device.  `path` (T + 1 entries) is consumed. */
-static void host_stitch_read(const Model *m, bool hp_on, const float *side, int *path, int T, bool want_pos, scrappie_hip_call &c) {
+static void host_stitch_read(const Model *m, bool hp_on, const float *side, int *path, int T, bool want_pos, scrappie_hip_call &c,
+                             const int *dwell = nullptr, float prior_num = 0.0f) {
     int *pos = (int *)calloc((size_t)T + 1, sizeof(int));
     if (!pos) { c.basecall = nullptr; c.basecall_length = 0; c.pos = nullptr; return; }
     char *bases;
-    if (m->arch != 1) {
+    if (dwell) {
+        bases = sh_dwell_stitch(path, dwell, T, 1, m->NS, prior_num, pos);          /* scrappie_events.c:300-321: one event per entry but the last */
+    } else if (m->arch != 1) {
         if (hp_on) sh_homopolymer_side(side, path, T, m->NS);                       /* scrappie_raw.c:293 */
         bases = overlapper(path, (size_t)T + 1, m->NS - 1, pos);                    /* scrappie_raw.c:303 */
     } else {
@@ -74,7 +81,8 @@ static void stitch_range(const scrappie_hip_engine *e, const Slot &sl, const Mod
         int *path = (int *)malloc(((size_t)T + 1) * sizeof(int));
         if (!path) continue;
         { const int *src = sl.h_seq.as<int>() + lg.seq_off[i]; for (int t = 0; t <= T; t++) path[t] = src[(size_t)t * SH_SEQ_STRIDE]; }
-        host_stitch_read(m, lg.hp_on, lg.hp_on ? sl.h_hp.as<float>() + lg.hp_off[i] * 5 : nullptr, path, T, p->want_pos != 0, c);
+        host_stitch_read(m, lg.hp_on, lg.hp_on ? sl.h_hp.as<float>() + lg.hp_off[i] * 5 : nullptr, path, T, p->want_pos != 0, c,
+                         lg.dw.on ? lg.dw.host[(size_t)o] : nullptr, lg.dw.on ? lg.dw.num[(size_t)o] : 0.0f);
         free(path);
     }
 }
@@ -144,7 +152,8 @@ extern "C" int scrappie_hip_collect(scrappie_hip_engine *e, const scrappie_hip_p
         const float *dsig = lg.d_signal;
         const int other_oldest = e->oldest;
         e->handover = false;
-        const int rc = run_pipeline(e, m, dsig, off.data(), len.data(), n, &pp, STOP_NONE, 5, nullptr);
+        const DwellJob dw = lg.dw;                       /* (a copy: the re-run may take this very slot) */
+        const int rc = run_pipeline(e, m, dsig, off.data(), len.data(), n, &pp, STOP_NONE, 5, nullptr, &dw);
         e->handover = true;
         if (rc) return -1;
         Slot &rs = e->current();
@@ -208,7 +217,8 @@ static int stitch_group(scrappie_hip_engine *e, Slot &sl, Model *m, const scrapp
             std::vector<float> side(lg.hp_on ? (size_t)T * 5 : 0);
             HIPCHK(hipMemcpy2D(path.data(), 4, sl.d_seq.as<int>() + lg.seq_off[i], (size_t)SH_SEQ_STRIDE * 4, 4, (size_t)T + 1, hipMemcpyDeviceToHost));
             if (lg.hp_on) HIPCHK(hipMemcpy(side.data(), sl.d_hp.as<float>() + lg.hp_off[i] * 5, (size_t)T * 5 * 4, hipMemcpyDeviceToHost));
-            host_stitch_read(m, lg.hp_on, side.data(), path.data(), T, p->want_pos != 0, out[o]);
+            host_stitch_read(m, lg.hp_on, side.data(), path.data(), T, p->want_pos != 0, out[o],
+                             lg.dw.on ? lg.dw.host[(size_t)o] : nullptr, lg.dw.on ? lg.dw.num[(size_t)o] : 0.0f);
             nredo++;
         }
         e->n_redo += nredo;
@@ -222,7 +232,7 @@ static int stitch_group(scrappie_hip_engine *e, Slot &sl, Model *m, const scrapp
  * its group with other long reads, not hold a group of short ones hostage (DESIGN.md section 7, mixed lengths).
  * stage(k, idx, cnt) makes the signals of reads idx[0..cnt) of the call available on the device and returns the
  * pointer/offset/length arrays to run them with. */
-struct GroupArgs { const float *d; const uint64_t *off; const uint32_t *len; };
+struct GroupArgs { const float *d; const uint64_t *off; const uint32_t *len; const DwellJob *dw = nullptr; };      /* (dw: events with the dwell correction, the group's dwells) */
 
 /* the last launch group of a streaming call (scrappie_hip_basecall_device_stream), still in flight when the call returned: collected by
  * the next call on the engine -- behind that call's first launch -- or by scrappie_hip_stream_flush */
@@ -285,7 +295,7 @@ static int run_groups(scrappie_hip_engine *e, int model, const Model *m, const u
         const size_t lo = starts[g], cnt = starts[g + 1] - lo;
         GroupArgs a;
         int rc = stage((int)((g + slot0) & 1), perm.data() + lo, cnt, a);
-        if (!rc && scrappie_hip_run_device(e, model, a.d, a.off, a.len, cnt, p) < 0) rc = -1;
+        if (!rc && run_device(e, model, a.d, a.off, a.len, cnt, p, a.dw) < 0) rc = -1;
         if (e->carry.live) { if (collect_carry(e)) rc = -1; }          /* the previous call's last group, behind this call's first launch */
         else if (have_prev && collect(prev)) rc = -1;
         have_prev = false;

@@ -5,13 +5,28 @@
 /* ------------------------------------------------------------------ */
 /* launch-group construction                                            */
 /* ------------------------------------------------------------------ */
-struct MetaPtrs { ShMeta md; const long long *seq_off, *hp_off, *bases_off; ShGruLanes lanes, lanes1; ShGruPairs pairs, pairs2; const ShGruSegD *vseg; };
+struct MetaPtrs { ShMeta md; const long long *seq_off, *hp_off, *bases_off; ShGruLanes lanes, lanes1; ShGruPairs pairs, pairs2; const ShGruSegD *vseg; ShDwellArgs dw; };
+
+/* Bytes of bases reserved for a read whose path has nentry entries.  Plain stitching: k of the first k-mer + at most k per later entry (k <= 5), a
+ * bound.  With the dwell correction a call has no bound of that kind: a homopolymer of hdwell samples gets round(hdwell / scale) bases, and the scale
+ * -- about the mean dwell of a step -- may come out small against one long dwell.  Over a read the homopolymers get at most sum(dwell) / scale +
+ * nentry / 2 bases (half a base of rounding each, a run owns two entries), so SH_DWELL_PER_ENTRY = 10 bytes an entry hold every read whose scale is at
+ * least 2 / 9 of its mean dwell: 5 as before, 4.5 for the dwells, 0.5 for the rounding.  A read outside that is the device's to notice (sh_dwell.h
+ * counts against the reservation before it stores) and the host's to stitch. */
+#define SH_DWELL_PER_ENTRY 10
+static long long bases_reservation(long long per_entry, long long nentry) { return (per_entry * nentry + 16 + 15) & ~15ll; }
+extern "C" size_t scrappie_hip_dwell_capacity(size_t nentry) { return (size_t)bases_reservation(SH_DWELL_PER_ENTRY, (long long)nentry); }
 
 static int build_group(scrappie_hip_engine *e, Slot &sl, Model *m, const uint64_t *offsets, const uint32_t *lengths,
-                       size_t n, bool hp_on, MetaPtrs &mp) {
+                       size_t n, bool hp_on, MetaPtrs &mp, const DwellJob *dw = nullptr) {
     LaunchGroup &lg = sl.lg;
     lg.valid = false;
     lg.n = n; lg.hp_on = hp_on;
+    lg.dw = DwellJob();
+    if (dw && dw->on) {
+        if (m->arch != 3 || dw->off.size() != n || dw->num.size() != n || dw->host.size() != n) return set_err("build_group: %zu reads, dwells of %zu", n, dw->off.size());
+        lg.dw = *dw;
+    }
     lg.ntile = (n + 15) / 16; lg.npad = lg.ntile * 16;
     const int st = m->stride;
     std::vector<int> T(n);
@@ -26,7 +41,7 @@ static int build_group(scrappie_hip_engine *e, Slot &sl, Model *m, const uint64_
     lg.seq_off.assign(lg.npad, 0); lg.hp_off.assign(lg.npad, 0); lg.bases_off.assign(lg.npad, 0);
     long long nbases = 0;
     /* bases a read can give: k of the first k-mer + at most k per later path entry (k <= 5; CRF: one per block), + 1 */
-    const long long per_entry = (m->arch == 1) ? 1 : 5;
+    const long long per_entry = (m->arch == 1) ? 1 : (lg.dw.on ? (e->dbg_dwell_tight ? 0 : SH_DWELL_PER_ENTRY) : 5);      /* (test hook: 16 bytes a read, so that calls do outgrow them) */
     std::vector<unsigned long long> sig_off(lg.npad, 0);
     std::vector<int> tile_T(lg.ntile, 0);
     std::vector<long long> &tile_boff = lg.tile_boff;
@@ -38,7 +53,7 @@ static int build_group(scrappie_hip_engine *e, Slot &sl, Model *m, const uint64_
             lg.rT[i] = T[o]; lg.rN[i] = (int)lengths[o]; sig_off[i] = offsets[o];
         }
         lg.hp_off[i] = nhp; nhp += lg.rT[i];
-        lg.bases_off[i] = nbases; nbases += lg.rT[i] ? ((per_entry * ((long long)lg.rT[i] + 1) + 16 + 15) & ~15ll) : 0;
+        lg.bases_off[i] = nbases; nbases += lg.rT[i] ? bases_reservation(per_entry, (long long)lg.rT[i] + 1) : 0;
         tile_T[i >> 4] = std::max(tile_T[i >> 4], lg.rT[i]);
     }
     for (size_t t = 0; t < lg.ntile; t++) { tile_boff[t] = ncb; ncb += tile_T[t]; }
@@ -158,6 +173,31 @@ static int build_group(scrappie_hip_engine *e, Slot &sl, Model *m, const uint64_
     mp.pairs2 = mp.pairs;
     mp.pairs2.seg = (const ShGruSegD *)(d + o_seg32b);
     mp.pairs2.lane_off = (const int *)(d + o_loff32b);
+    mp.dw = ShDwellArgs{};
+    if (lg.dw.on) {
+        /* the dwell kernel's per-read words in tiled order: [dwell_off i64][prior_num f32][cap i32], behind the metadata on the prologue stream */
+        const size_t np = lg.npad, bytes = (np * 16 + 15) & ~(size_t)15;
+        if (sl.h_dwmeta.ensure(bytes) || sl.d_dwmeta.ensure(bytes)) return -1;
+        long long *hoff = sl.h_dwmeta.as<long long>();
+        float *hnum = (float *)(hoff + np);
+        int *hcap = (int *)(hnum + np);
+        for (size_t i = 0; i < np; i++) {
+            const int o2 = lg.order[i];
+            const bool live = o2 >= 0 && lg.rT[i] > 0;
+            hoff[i] = live ? (long long)lg.dw.off[(size_t)o2] : 0;
+            hnum[i] = live ? lg.dw.num[(size_t)o2] : 0.0f;
+            hcap[i] = live ? (int)std::min<long long>(bases_reservation(per_entry, (long long)lg.rT[i] + 1), INT32_MAX & ~15) : 0;
+        }
+        if (e->ev_ok) hipLaunchKernelGGL(k_upload_words, dim3((unsigned)std::min<size_t>((bytes / 16 + 255) / 256, 64)), dim3(256), 0, ps, (const u32x4 *)sl.h_dwmeta.p, sl.d_dwmeta.as<u32x4>(), (long long)(bytes / 16));
+        else HIPCHK(hipMemcpyAsync(sl.d_dwmeta.p, sl.h_dwmeta.p, bytes, hipMemcpyHostToDevice, ps));
+        char *dd = sl.d_dwmeta.as<char>();
+        mp.dw.dwell = lg.dw.d_dwell;
+        mp.dw.dwell_off = (const long long *)dd;
+        mp.dw.prior_num = (const float *)(dd + np * 8);
+        mp.dw.cap = (const int *)(dd + np * 12);
+        mp.dw.nd = mp.md.rT;
+        mp.dw.ntrail = 1;
+    }
     return 0;
 }
 

@@ -47,6 +47,7 @@ struct GroupRun {
     const float *d_signal = nullptr; const uint64_t *offsets = nullptr; const scrappie_hip_params *p = nullptr;
     StopAt stop = STOP_NONE; int trunk_upto = 5; RunOut *ro = nullptr;
     bool transducer = false, hp_on = false;
+    const DwellJob *dw = nullptr;      /* events with the dwell correction: the group's dwells (null: plain stitching) */
     MetaPtrs mp;
     hipStream_t s = nullptr, ps = nullptr, cs = nullptr;      /* main, prologue and copy stream (all three the main stream where the engine has no events) */
     long long ncb = 0; size_t act_bytes = 0;
@@ -78,7 +79,7 @@ static int begin_group(scrappie_hip_engine *e, Model *m, const uint32_t *lengths
     if (!slp) return set_err("two launch groups are already in flight: call scrappie_hip_collect first");
     Slot &sl = *slp;
     e->cur = e->index(sl);
-    if (build_group(e, sl, m, c.offsets, lengths, n, c.hp_on, c.mp)) return -1;
+    if (build_group(e, sl, m, c.offsets, lengths, n, c.hp_on, c.mp, c.dw)) return -1;
     c.stamp("build_group");
     *slot = slp;
     *empty = sl.lg.ncb == 0;
@@ -424,12 +425,16 @@ static int stage_tail(Slot &sl, Model *m, GroupRun &c) {
         ra.d_err = sl.d_gflag.as<unsigned>() + lg.ntile; ra.h_err = sl.h_err.as<unsigned>();
         ra.npad = (int)lg.npad;
         if (c.pf.mark(Marks::STITCH_BEGIN, cs)) return -1;
+        const bool dwell = lg.dw.on && c.transducer;      /* events with the dwell correction: the stitching's other form (sh_dwell.h) */
         if (c.fold_tail) {
             ShWalkArgs wa;
             wa.tb = e->d_tb.as<unsigned>(); wa.tb_end = e->d_tbend.as<int>(); wa.final_state = e->d_fstate.as<int>();
             wa.seq_off = mp.seq_off; wa.seq = sl.d_seq.as<int>(); wa.NQ = (m->NS - 1) / 4;
-            hipLaunchKernelGGL(k_walk_stitch_out, dim3((unsigned)((lg.npad + 63) / 64)), dim3(64), 0, cs, wa, sa, ra, mp.md);
-        } else
+            if (dwell) hipLaunchKernelGGL(k_walk_dwell_out, dim3((unsigned)((lg.npad + 63) / 64)), dim3(64), 0, cs, wa, sa, mp.dw, ra, mp.md);
+            else hipLaunchKernelGGL(k_walk_stitch_out, dim3((unsigned)((lg.npad + 63) / 64)), dim3(64), 0, cs, wa, sa, ra, mp.md);
+        } else if (dwell)
+            hipLaunchKernelGGL(k_stitch_dwell, dim3((unsigned)((lg.npad + 63) / 64)), dim3(64), 0, cs, sa, mp.dw);
+        else
             hipLaunchKernelGGL(k_stitch, dim3((unsigned)((lg.npad + 63) / 64)), dim3(64), 0, cs, sa, mp.md);
         if (c.pf.mark(Marks::STITCH_END, cs)) return -1;
         c.pf.span(F_STITCH, Marks::STITCH_BEGIN, Marks::STITCH_END);
@@ -457,11 +462,11 @@ static int stage_tail(Slot &sl, Model *m, GroupRun &c) {
 
 static int run_pipeline(scrappie_hip_engine *e, Model *m, const float *d_signal, const uint64_t *offsets,
                         const uint32_t *lengths, size_t n, const scrappie_hip_params *p, StopAt stop,
-                        int trunk_upto, RunOut *ro) {
+                        int trunk_upto, RunOut *ro, const DwellJob *dw = nullptr) {
     (void)hipSetDevice(e->device);
     if (n == 0) return set_err("empty batch");
     GroupRun c;
-    c.e = e; c.d_signal = d_signal; c.offsets = offsets; c.p = p; c.stop = stop; c.trunk_upto = trunk_upto; c.ro = ro;
+    c.e = e; c.d_signal = d_signal; c.offsets = offsets; c.p = p; c.stop = stop; c.trunk_upto = trunk_upto; c.ro = ro; c.dw = dw;
     c.transducer = (m->arch != 1);
     c.hp_on = c.transducer && p->homopolymer == HOMOPOLYMER_MEAN && stop == STOP_NONE;
     c.s = e->stream; c.ps = e->ev_ok ? e->pstream : e->stream; c.cs = e->ev_ok ? e->cstream : e->stream;

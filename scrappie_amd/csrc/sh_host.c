@@ -242,6 +242,157 @@ char *crfpath_to_basecall(int const *path, size_t npos, int *pos) {
 }
 
 /* ------------------------------------------------------------------ */
+/* Dwell correction of homopolymer lengths (decode.c:511-702): the last */
+/* step of `scrappie events`.  The host statement the device form       */
+/* (sh_dwell.h) is held against, and what re-stitches a read that did   */
+/* not fit its reservation on the device.                               */
+/* ------------------------------------------------------------------ */
+static int kmer_is_homopolymer(int kmer, int klen) {
+    for (int i = 1; i < klen; i++)
+        if (((kmer >> (2 * i)) & 3) != (kmer & 3)) return 0;
+    return 1;
+}
+
+/* bases a homopolymer that was dwelt in for hdwell samples is given: a float division, then round half away from zero
+ * (decode.c:511-514).  0 where the count is no int (a scale of zero, a NaN): the reference is undefined there. */
+static int dwell_bases(int hdwell, int homo, const dwell_model *dm, int *count) {
+    const float q = roundf(((float)hdwell - dm->base_adj[homo & 3]) / dm->scale);
+    if (!(q >= 0.0f && q < 1073741824.0f)) return 0;
+    *count = (int)q;
+    return 1;
+}
+
+/* One forward walk over the path, as the reference's length pass and fill pass both are.  Returns what strlen gives on the
+ * reference's string and writes those bytes when out is not NULL; -1 where the reference is undefined (no k-mer at all, a
+ * count that is no int).  A homopolymer is entered at a k-mer behind the first only; stays and repeats of its k-mer add
+ * their dwell while it lasts; leaving it emits its bases in front of the next k-mer's.  The last homopolymer's fill starts
+ * one byte early (decode.c:633-635, on the base it repeats), so where it has bases the string ends one short of them. */
+static long dwell_walk(const int *seq, const int *dwell, int n, int nkmer, const dwell_model *dm, char *out) {
+    int klen = 0;
+    for (int x = nkmer; x > 1; x >>= 2) klen++;
+    int first = 0;
+    while (first < n && seq[first] < 0) first++;
+    if (first >= n) return -1;
+    long len = 0;
+    for (int i = klen - 1; i >= 0; i--, len++)
+        if (out) out[len] = BASES[(seq[first] >> (2 * i)) & 3];
+    int prev = seq[first], homo = -1, hdwell = 0, cnt = 0;
+    for (int k = first + 1; k < n; k++) {
+        const int cur = seq[k];
+        if (cur < 0 || cur == homo) {
+            if (homo >= 0) hdwell += dwell[k];
+            continue;
+        }
+        if (homo >= 0) {
+            if (!dwell_bases(hdwell, homo, dm, &cnt)) return -1;
+            for (int i = 0; i < cnt; i++, len++)
+                if (out) out[len] = BASES[homo & 3];
+            homo = -1;
+            hdwell = 0;
+        }
+        const int s = kmer_shift(prev, cur, nkmer);
+        for (int i = s - 1; i >= 0; i--, len++)
+            if (out) out[len] = BASES[(cur >> (2 * i)) & 3];
+        prev = cur;
+        if (kmer_is_homopolymer(cur, klen)) {
+            homo = cur;
+            hdwell = dwell[k];
+        }
+    }
+    if (homo >= 0) {
+        if (!dwell_bases(hdwell, homo, dm, &cnt)) return -1;
+        for (int i = 0; i + 1 < cnt; i++, len++)
+            if (out) out[len] = BASES[homo & 3];
+    }
+    return len;
+}
+
+char *dwell_corrected_overlapper(const int *seq, const int *dwell, int n, int nkmer, const dwell_model dm) {
+    if (!seq || !dwell || n <= 0 || nkmer < 4) return NULL;
+    const long len = dwell_walk(seq, dwell, n, nkmer, &dm, NULL);
+    if (len < 0) return NULL;
+    char *bases = calloc((size_t)len + 2, 1);
+    if (!bases) return NULL;
+    (void)dwell_walk(seq, dwell, n, nkmer, &dm, bases);
+    return bases;
+}
+
+/* decode.c:661-693: the mean dwell of the steps outside homopolymers, with the prior as one more observation.  pos / state:
+ * n ints each, `stride` bytes apart.  The sums are ints; prior + sum is a float addition, the division a double one, rounded
+ * to float once. */
+float sh_dwell_scale(const void *pos, const void *state, size_t stride, const int *dwell, int n, float prior_num, size_t basecall_len) {
+    int tot_step_dwell = 0, nstep = 0;
+    for (int ev = 0, ppos = -2, evdwell = 0, pstate = -1; ev < n; ev++) {
+        const int p = *(const int *)((const char *)pos + (size_t)ev * stride);
+        const int s = *(const int *)((const char *)state + (size_t)ev * stride);
+        if (p == ppos) { evdwell += dwell[ev]; continue; }
+        if (p == ppos + 1 && s != pstate) { tot_step_dwell += evdwell; nstep++; }
+        evdwell = dwell[ev];
+        ppos = p;
+        pstate = s;
+    }
+    const float prior_scale = prior_num / (float)basecall_len;
+    const float num = prior_scale + (float)tot_step_dwell;
+    return (float)((double)num / (1.0 + (double)nstep));
+}
+
+/* the float numerator of the prior: the last event's length + (float)(the span of the starts) (decode.c:689-692) */
+float sh_dwell_prior_num(const event_t *ev, size_t n) {
+    return ev[n - 1].length + (float)(ev[n - 1].start - ev[0].start);
+}
+
+static int *event_dwells(const event_t *ev, size_t n) {
+    int *dwell = malloc((n ? n : 1) * sizeof(int));
+    if (dwell)
+        for (size_t i = 0; i < n; i++) dwell[i] = (int)ev[i].length;
+    return dwell;
+}
+
+float scrappie_hip_dwell_scale(const event_table et, size_t basecall_len) {
+    if (!et.event || et.end <= et.start || et.end > et.n || basecall_len == 0) return NAN;
+    const event_t *ev = et.event + et.start;
+    const size_t n = et.end - et.start;
+    int *dwell = event_dwells(ev, n);
+    if (!dwell) return NAN;
+    const float scale = sh_dwell_scale(&ev[0].pos, &ev[0].state, sizeof(event_t), dwell, (int)n, sh_dwell_prior_num(ev, n), basecall_len);
+    free(dwell);
+    return scale;
+}
+
+char *homopolymer_dwell_correction(const event_table et, const int *seq, size_t nstate, size_t basecall_len) {
+    if (!et.event || !seq || et.end <= et.start || et.end > et.n || basecall_len == 0 || nstate < 5) return NULL;
+    const event_t *ev = et.event + et.start;
+    const size_t n = et.end - et.start;
+    if (n > (size_t)INT32_MAX) return NULL;
+    int *dwell = event_dwells(ev, n);
+    if (!dwell) return NULL;
+    const dwell_model dm = { sh_dwell_scale(&ev[0].pos, &ev[0].state, sizeof(event_t), dwell, (int)n, sh_dwell_prior_num(ev, n), basecall_len),
+                             { 0.0f, 0.0f, 0.0f, 0.0f } };
+    char *bases = dwell_corrected_overlapper(seq, dwell, (int)n, (int)nstate - 1, dm);
+    free(dwell);
+    return bases;
+}
+
+/* The same on a read the engine holds as arrays: a path of n + ntrail entries (the decoder's; `scrappie events` stitches its
+ * first n, one per event), n dwells, the prior's numerator.  pos_out (may be NULL): n + ntrail ints, overlapper's.  Returns the corrected call, or the plain one where the correction has none; NULL: no k-mer. */
+char *sh_dwell_stitch(const int *path, const int *dwell, int n, int ntrail, int nstate, float prior_num, int *pos_out) {
+    const size_t nall = (size_t)n + (size_t)ntrail;
+    int *pos = calloc(2 * nall + 2, sizeof(int));
+    if (!pos) return NULL;
+    int *state = pos + nall + 1;
+    char *plain = overlapper(path, nall, nstate - 1, pos);
+    if (!plain) { free(pos); return NULL; }
+    for (int i = 0; i < n; i++) state[i] = 1 + path[i];
+    const dwell_model dm = { sh_dwell_scale(pos, state, sizeof(int), dwell, n, prior_num, strlen(plain)), { 0.0f, 0.0f, 0.0f, 0.0f } };
+    char *bases = dwell_corrected_overlapper(path, dwell, n, nstate - 1, dm);
+    if (pos_out) memcpy(pos_out, pos, nall * sizeof(int));
+    free(pos);
+    if (!bases) return plain;
+    free(plain);
+    return bases;
+}
+
+/* ------------------------------------------------------------------ */
 /* D2 homopolymer correction (homopolymer.c:67-235) on a 5-row side     */
 /* buffer: side[t*5 + {0..3}] = log-posterior of the homopolymer k-mer  */
 /* of base A,C,G,T at block t, side[t*5 + 4] = stay.  Only those five   */

@@ -18,6 +18,14 @@ unsigned long sh_h5mini_zlib_fallbacks(void);      /* chunks the built-in inflat
 int sh_bounds_sane(const size_t *low, const size_t *high, size_t nblock, size_t seqlen, int verbose);
 /* squiggle matching (sh_host.c): the tables of decode.c:1055-1099 from the host's libm; tab holds 5 npos + 4 floats */
 void sh_squiggle_tables(const float *params, size_t npos, size_t ldp, float rate, float prob_back, float *tab, float pens[2]);
+/* dwell correction (sh_host.c): the scale from pos / state (n ints each, `stride` bytes apart), the prior's numerator of an event table, and
+ * the whole step on a read the engine holds as arrays (path of n + ntrail entries, n dwells; pos_out may be NULL): the corrected call, the
+ * plain one where there is no correction, NULL without a k-mer */
+float sh_dwell_scale(const void *pos, const void *state, size_t stride, const int *dwell, int n, float prior_num, size_t basecall_len);
+#ifdef SCRAPPIE_HIP_H      /* (event_t: for the files that include scrappie_hip.h first) */
+float sh_dwell_prior_num(const event_t *ev, size_t n);
+#endif
+char *sh_dwell_stitch(const int *path, const int *dwell, int n, int ntrail, int nstate, float prior_num, int *pos_out);
 #ifdef __cplusplus
 }
 #endif

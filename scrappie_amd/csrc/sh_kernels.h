@@ -330,5 +330,6 @@ struct ShMeta {
 #include "sh_decode_teams.h"
 #include "sh_crf.h"
 #include "sh_stitch.h"
+#include "sh_dwell.h"
 
 #endif /* SH_KERNELS_H */

@@ -84,6 +84,24 @@ def matrix_names(m):
     return RAW_MATRIX_NAMES if m["arch"] == "raw" else MATRIX_NAMES
 
 
+def homopolymer_cycle_model(seed=4, size=96):
+    """An events model whose calls the dwell correction of homopolymer lengths changes (tests, tools/events_call_rate.py).
+    Seeded synthetic weights decode to one k-mer and stays, which no correction touches; here the output layer's bias lifts the
+    stay and ten k-mers that form a cycle through two homopolymers (AAAAA -> AAAAC -> ... -> CCCCC -> CCCCA -> ... -> CAAAA ->
+    AAAAA) above the other states, and the input weights of the LSTM layers are four times larger, so that the features move the
+    network: the Viterbi path walks the cycle at the pace of the signal, with stays, and enters a homopolymer every few events
+    (seed 4, 96 units: synthetic reads of 250 to 2500 samples give calls of 50 to 630 bases, every one changed by the correction)."""
+    w = synthetic_model("nanonet_events", seed=seed, size=size)
+    for l in range(4):
+        w["lstm%d_iW" % l] = (w["lstm%d_iW" % l] * 4.0).astype(np.float32)
+    b = w["ff_b"].copy()
+    for kmer in ("AAAAA", "AAAAC", "AAACC", "AACCC", "ACCCC", "CCCCC", "CCCCA", "CCCAA", "CCAAA", "CAAAA"):
+        b[sum("ACGT".index(ch) * 4 ** (4 - i) for i, ch in enumerate(kmer))] += 12.0
+    b[-1] += 12.0
+    w["ff_b"] = b
+    return w
+
+
 def synthetic_model(name="rgrgr_r94", seed=1, size=96, nfilter=None, winlen=None,
                     stride=5, nstate=None, ff_scale=6.0):
     """Seeded synthetic weights, reference shapes.
