@@ -508,6 +508,37 @@ void scrappie_hip_sqnet_timing(scrappie_hip_engine *e, double out[3]);
 size_t scrappie_hip_sqnet_tile(void);
 /* launches of k_sqnet since the process started, all engines together (a host counter) */
 uint64_t scrappie_hip_sqnet_launch_count(void);
+
+/* Base probabilities of the flip-flop (CRF) models, batched (k_crf_post, sh_crf_post.h; sh_eng_crfpost.inc): the forward / backward pass of
+ * posterior_crf (src/decode.c:928) over a read's normalised transitions on the device, 8 lanes per read.  A result is the 5 x (nblock + 1)
+ * matrix posterior_crf returns -- rows A, C, G, T, stay; every column total carries the reference's extra e^0, so a column sums to less than
+ * one -- malloc'd, the caller's to free_scrappie_matrix.
+ * The per-read symbol posterior_crf (and scrappy's basecall_raw(..., with_base_probs=True) on top of it) stays the host function: it is pinned
+ * bit for bit against the compiled reference, whose log-sum-exp is libm's log1pf(expf()); the device's is the transcendental unit's, within a
+ * few ulp of a correction term of at most log 2 per step, and cannot keep that promise.  The functions below agree with it to rounding. */
+/* Host only: off[i] = float offset of read i's (nblock[i] + 1) x 5 floats in a launch's output buffer, reads end to end in this order, every
+ * start 16-byte aligned, nothing for a read without blocks; returns the floats of all of them (-1: a null argument).  Neighbouring reads are
+ * written by different workgroups and a result cannot show an overlap, so the plan is open to the tests. */
+long long scrappie_hip_crf_post_plan(const size_t *nblock, size_t n, long long *off);
+/* trans[i]: 25 rows (from state minor, to state major; ACGT-), nc >= 1 blocks, as nanonet_rnnrf_r94_transitions returns it.  The accepted
+ * matrices go up end to end: one upload, one launch of k_crf_post, one download; a call of more than 4 000 000 blocks is cut into several.
+ * A NULL or misshapen matrix gets out[i] = NULL and an error text, the others are untouched.  Returns 0, or -1 with
+ * scrappie_hip_last_error() when the call as a whole fails (out[] is then all NULL). */
+int scrappie_hip_posterior_crf_batch(scrappie_hip_engine *e, const const_scrappie_matrix *trans, size_t n, scrappie_matrix *out);
+/* scrappie_hip_basecall_batch for a CRF model (any other: -1) that returns the base probabilities as well: out[] is exactly what
+ * scrappie_hip_basecall_batch gives for the same input; probs[i] is read i's 5 x (nblock + 1) posterior, NULL where the read has no call.
+ * Inside a launch group k_crf leaves the normalised transitions on the device, k_crf_post runs behind it on the main stream, and the
+ * probabilities come back on the copy stream behind the group's calls: 20 bytes per block.  Failures as scrappie_hip_basecall_batch (a failed
+ * call returns nothing).  The call runs alone: it does not share launch groups with concurrent small calls, and keeps chain-bound reads on
+ * this engine. */
+int scrappie_hip_basecall_batch_probs(scrappie_hip_engine *e, int model, const raw_table *reads, size_t n, const scrappie_hip_params *p,
+                                      scrappie_hip_call *out, scrappie_matrix *probs);
+/* the last of the two calls above, milliseconds summed over its launch groups.  scrappie_hip_basecall_batch_probs: [0] network + k_crf,
+ * [1] k_crf_post, [2] the probabilities' transfer to the host (device events; nothing waits for them while the groups run).
+ * scrappie_hip_posterior_crf_batch: [0] staging + upload, [1] k_crf_post, [2] download + results (host clock, the stream drained between). */
+void scrappie_hip_crf_post_timing(scrappie_hip_engine *e, double out[3]);
+/* launches of k_crf_post since the process started, both forms and all engines together (a host counter) */
+uint64_t scrappie_hip_crf_post_launch_count(void);
 /* Launches of each kernel form since the process started, all engines together (the per-read functions run on the
  * process-default engine).  map_forms[(viterbi ? 8 : 0) | (banded ? 4 : 0) | (tiled ? 2 : 0) | (scratch ? 1 : 0)] for k_map,
  * squig_forms[(viterbi ? 2 : 0) | (scratch ? 1 : 0)] for k_squig; either may be NULL.  Host counters only: no device work. */

@@ -289,6 +289,15 @@ def lib():
     L.scrappie_hip_sqnet_tile.argtypes = []
     L.scrappie_hip_sqnet_launch_count.restype = C.c_uint64
     L.scrappie_hip_sqnet_launch_count.argtypes = []
+    L.scrappie_hip_crf_post_plan.restype = C.c_longlong
+    L.scrappie_hip_crf_post_plan.argtypes = [sp, C.c_size_t, C.POINTER(C.c_longlong)]
+    L.scrappie_hip_posterior_crf_batch.argtypes = [C.c_void_p, C.POINTER(PM), C.c_size_t, C.POINTER(PM)]
+    L.scrappie_hip_basecall_batch_probs.argtypes = [C.c_void_p, C.c_int, C.POINTER(_RawTable), C.c_size_t, C.POINTER(Params), C.POINTER(_Call),
+                                                    C.POINTER(PM)]
+    L.scrappie_hip_crf_post_timing.restype = None
+    L.scrappie_hip_crf_post_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    L.scrappie_hip_crf_post_launch_count.restype = C.c_uint64
+    L.scrappie_hip_crf_post_launch_count.argtypes = []
     L.detect_events.restype = _EventTable
     L.detect_events.argtypes = [_RawTable, DetectorParam]
     L.scrappie_hip_detect_events_host.restype = _EventTable
@@ -344,6 +353,15 @@ def plan_scratch(kind, sizes, counts):
     off = np.zeros(len(a), dtype=np.longlong)
     sp = C.POINTER(C.c_size_t)
     total = fn(a.ctypes.data_as(sp), b.ctypes.data_as(sp), len(a), off.ctypes.data_as(C.POINTER(C.c_longlong)))
+    return off, int(total)
+
+
+def crf_post_plan(nblocks):
+    """Where the base probabilities of one launch of reads of `nblocks` blocks lie in its output buffer (host arithmetic, no device;
+    scrappie_hip_crf_post_plan): (off, total) -- the float offset of each read's (nblock + 1) x 5 floats and the floats of all of them."""
+    a = np.ascontiguousarray(nblocks, dtype=np.uintp)
+    off = np.zeros(len(a), dtype=np.longlong)
+    total = lib().scrappie_hip_crf_post_plan(a.ctypes.data_as(C.POINTER(C.c_size_t)), len(a), off.ctypes.data_as(C.POINTER(C.c_longlong)))
     return off, int(total)
 
 
@@ -1039,7 +1057,11 @@ class Engine(object):
         lib().scrappie_hip_free_calls(calls, n)
         return out
 
-    def basecall(self, signals, model='rgrgr_r94', params=None):
+    def basecall(self, signals, model='rgrgr_r94', params=None, base_probs=False):
+        """base_probs (CRF models only): every call gains "base_probs", the (nblock + 1, 5) float32 posterior over A, C, G, T and stay
+        at every block boundary, in the orientation `basecall_raw(..., with_base_probs=True)` returns (scrappie_hip_basecall_batch_probs)."""
+        if base_probs:
+            return self._basecall_probs(signals, model, params)
         n = len(signals)
         p = params or self.default_params()
         keep = [np.ascontiguousarray(s, dtype=ftype) for s in signals]
@@ -1050,6 +1072,50 @@ class Engine(object):
         if lib().scrappie_hip_basecall_batch(self._h, self._models[model], rts, n, C.byref(p), calls) != 0:
             raise RuntimeError("basecall_batch: " + last_error())
         return self._unpack(calls, n, p.want_pos)
+
+    def _basecall_probs(self, signals, model, params):
+        h = self._models[model]
+        if lib().scrappie_hip_model_states(self._h, h) != 25:
+            raise ValueError("Base probabilities not supported for model type '{}': a CRF model is needed.".format(model))
+        n = len(signals)
+        p = params or self.default_params()
+        rts, keep = _raw_tables(signals)
+        calls = (_Call * max(n, 1))()
+        probs = (C.POINTER(_Mat) * max(n, 1))()
+        if lib().scrappie_hip_basecall_batch_probs(self._h, h, rts, n, C.byref(p), calls, probs) != 0:
+            raise RuntimeError("basecall_batch_probs: " + last_error())
+        mats = [ScrappyMatrix(probs[i]).data(as_numpy=True, sloika=False) if probs[i] else None for i in range(n)]
+        out = self._unpack(calls, n, p.want_pos)
+        for d, bp in zip(out, mats):
+            if d is not None:
+                d["base_probs"] = bp
+        return out
+
+    def posterior_crf(self, transitions):
+        """The base probabilities of each read's transitions, batched (scrappie_hip_posterior_crf_batch): `transitions` holds
+        `ScrappyMatrix` objects or (nblock, 25) arrays as `calc_post(rt, 'rnnrf_r94').data(as_numpy=True, sloika=False)` gives them;
+        returns a list of (nblock + 1, 5) float32 arrays in input order, None where a matrix is refused (`last_error()` says why)."""
+        n = len(transitions)
+        keep, ptrs = [], (C.POINTER(_Mat) * max(n, 1))()
+        for i, t in enumerate(transitions):
+            if isinstance(t, ScrappyMatrix):
+                keep.append(t)
+            else:
+                a = np.asarray(t, dtype=ftype)
+                if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] < 1:
+                    keep.append(None)       # the library refuses a null matrix
+                    continue
+                keep.append(ScrappyMatrix.from_numpy(a, sloika=False))
+            ptrs[i] = keep[-1].data()
+        out = (C.POINTER(_Mat) * max(n, 1))()
+        if lib().scrappie_hip_posterior_crf_batch(self._h, ptrs, n, out) != 0:
+            raise RuntimeError("posterior_crf_batch: " + last_error())
+        return [ScrappyMatrix(out[i]).data(as_numpy=True, sloika=False) if out[i] else None for i in range(n)]
+
+    def crf_post_timing(self):
+        """the last base-probability call's time (ms, summed over launch groups).  basecall(base_probs=True): network + k_crf, k_crf_post,
+        the probabilities' transfer; posterior_crf: staging + upload, k_crf_post, download + results"""
+        return self._timing(lib().scrappie_hip_crf_post_timing, ('network_ms', 'post_ms', 'download_ms'))
 
     # -- device-resident path (bench) ------------------------------------
     def basecall_deferred(self, signals, model='rgrgr_r94', params=None):

@@ -41,6 +41,7 @@
  *   sh_eng_squig.inc     mapping of raw signals to predicted squiggles (per-read and batched)
  *   sh_eng_sqnet.inc     prediction of squiggles from base sequences (per-read and batched)
  *   sh_eng_events.inc    event detection (per-read and batched; kernels in sh_events.h)
+ *   sh_eng_crfpost.inc   base probabilities of the flip-flop models (k_crf_post, sh_crf_post.h): inside a launch group and on host matrices
  * Separate translation units: sh_p0.hip (signal preparation, k_p0), sh_host.c / sh_fast5.c / sh_h5mini.c (host C);
  * sh_coalesce.h (the per-read functions' queue) and sh_dev.h (DBuf / HBuf: buffers that own their memory) are plain C++ headers.
  */
@@ -251,7 +252,17 @@ struct DwellJob {
     std::vector<const int *> host;
 };
 
+/* The base probabilities of a flip-flop launch group (k_crf_post, sh_eng_crfpost.inc), handed over like the dwell job: per read of the group, in the
+ * group's own order, where its matrix is to be delivered (the call owns the places). */
+struct PostJob {
+    bool on = false;
+    std::vector<scrappie_matrix *> dst;
+};
+
 struct LaunchGroup {
+    PostJob post;                 /* base probabilities wanted (build_group takes its caller's) */
+    std::vector<long long> post_off;      /* ... where each read's (T + 1) x 5 floats lie in the slot's buffer (tiled order; scrappie_hip_crf_post_plan) */
+    long long npost = 0;          /* ... and the floats of all of them */
     DwellJob dw;                  /* events with the dwell correction on: the group's dwells (build_group takes its caller's) */
     size_t n = 0, npad = 0, ntile = 0;
     long long ncb = 0;            /* total column blocks */
@@ -343,10 +354,12 @@ struct Slot {
     DBuf d_fscore, d_seq, d_hp;
     DBuf d_pos, d_bases, d_blen, d_redo;     /* k_stitch: pos / bases / lengths / host-decides flags */
     DBuf d_dwmeta; HBuf h_dwmeta;            /* k_walk_dwell_out: dwell offsets, prior numerators and capacities in tiled order */
+    DBuf d_post, d_postoff; HBuf h_post, h_postoff;      /* k_crf_post: the group's base probabilities and their offsets in tiled order */
+    hipEvent_t pev[5] = {};          /* ... and its timing marks (sh_eng_crfpost.inc; made on first use) */
     HBuf h_meta, h_sig, h_err, h_bad, h_edge, h_seq, h_score, h_hp, h_pos, h_bases, h_blen, h_redo;
     size_t pinned_bytes() const {
         size_t tot = 0;
-        for (const HBuf *h : {&h_meta, &h_sig, &h_err, &h_bad, &h_edge, &h_seq, &h_score, &h_hp, &h_pos, &h_bases, &h_blen, &h_redo, &h_dwmeta}) tot += h->cap;
+        for (const HBuf *h : {&h_meta, &h_sig, &h_err, &h_bad, &h_edge, &h_seq, &h_score, &h_hp, &h_pos, &h_bases, &h_blen, &h_redo, &h_dwmeta, &h_post, &h_postoff}) tot += h->cap;
         return tot;
     }
     bool create_events() {
@@ -357,6 +370,7 @@ struct Slot {
     }
     ~Slot() {      /* (with the engine: its device current, its streams drained) */
         for (auto &x : ev) if (x) (void)hipEventDestroy(x);
+        for (auto &x : pev) if (x) (void)hipEventDestroy(x);
         for (hipEvent_t x : {done, kdone, hdone, pdone, up}) if (x) (void)hipEventDestroy(x);
     }
 };
@@ -478,6 +492,8 @@ struct scrappie_hip_engine {
     double sqnet_ms[3] = {0, 0, 0};  /* scrappie_hip_squiggle_predict_batch: upload, k_sqnet, download + transform, summed over the last call's launches */
     DBuf d_ev_sig, d_ev_rd, d_ev_sum, d_ev_sumsq, d_ev_t1, d_ev_t2, d_ev_peaks, d_ev_np, d_ev_off, d_ev_out; HBuf h_ev, h_ev_out;      /* event detection (sh_eng_events.inc): signals, records, the five scratch arrays, peak counts, event offsets, event tables; staging */
     double event_ms[3] = {0, 0, 0};  /* scrappie_hip_detect_events_batch: staging + upload, the kernels, tables to the host, summed over the last call's launches */
+    HBuf h_cp_in, h_cp_out; DBuf d_cp_in, d_cp_out;      /* scrappie_hip_posterior_crf_batch (sh_eng_crfpost.inc): matrices + per-read words, probabilities */
+    double crf_post_ms[3] = {0, 0, 0};   /* scrappie_hip_crf_post_timing: the last call's three terms, summed over its launch groups */
     size_t dbg_events_budget = 0;    /* sample slots one event-detection launch may hold (debug option "events_budget_samples"; 0: from the free memory) */
     size_t dbg_sqnet_budget = 0;     /* device bytes one squiggle-predicting launch may hold (debug option "sqnet_budget_kb"; 0: half of the free memory) */
     size_t dbg_squig_budget = 0;     /* device bytes one squiggle-matching launch may hold (debug option "squiggle_budget_kb"; 0: half of the free memory) */
@@ -617,3 +633,4 @@ extern "C" scrappie_hip_params scrappie_hip_default_params(void) {
 #include "sh_eng_squig.inc"      /* squiggle matching (sh_squig.h): squiggle_match_* on the process-default engine, scrappie_hip_squiggle_match_batch */
 #include "sh_eng_sqnet.inc"      /* squiggle prediction (sh_sqnet.h): squiggle_r94 and its relatives on the process-default engine, scrappie_hip_squiggle_predict_batch */
 #include "sh_eng_events.inc"      /* event detection (sh_events.h): detect_events on the process-default engine, scrappie_hip_detect_events_batch; `scrappie events` for a batch (scrappie_hip_basecall_events_batch) */
+#include "sh_eng_crfpost.inc"      /* base probabilities of the flip-flop models (sh_crf_post.h): scrappie_hip_basecall_batch_probs, scrappie_hip_posterior_crf_batch */

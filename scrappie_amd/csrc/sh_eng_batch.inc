@@ -41,7 +41,9 @@ extern "C" long scrappie_hip_plan_tail(const uint32_t *lengths, size_t n, int st
     return cnt;
 }
 
-static int basecall_batch_one(scrappie_hip_engine *e, int model, const raw_table *reads, size_t n, const scrappie_hip_params *p, scrappie_hip_call *out);
+/* (probs: scrappie_hip_basecall_batch_probs -- every launch group returns its reads' base probabilities as well, sh_eng_crfpost.inc) */
+static int basecall_batch_one(scrappie_hip_engine *e, int model, const raw_table *reads, size_t n, const scrappie_hip_params *p, scrappie_hip_call *out,
+                              scrappie_matrix *probs = nullptr);
 
 /* The helper's share of the device's memory: its launch groups last as long as their longest read whatever they hold, so its rate is
  * its arena per chain.  0.3 against 0.15: a stream of 24 calls of 12 000 lognormal reads 1.19e9 against 1.10e9 samples/s
@@ -449,7 +451,7 @@ static int basecall_batch_direct(scrappie_hip_engine *e, int model, const raw_ta
 }
 
 static int basecall_batch_one(scrappie_hip_engine *e, int model, const raw_table *reads, size_t n,
-                              const scrappie_hip_params *p, scrappie_hip_call *out) {
+                              const scrappie_hip_params *p, scrappie_hip_call *out, scrappie_matrix *probs) {
     if (!e || !reads || !out) return set_err("basecall_batch: null argument");
     Model *m = get_model(e, model);
     if (!m) return -1;
@@ -464,6 +466,7 @@ static int basecall_batch_one(scrappie_hip_engine *e, int model, const raw_table
     std::vector<uint64_t> off[2];
     std::vector<uint32_t> glen[2];
     bool used[2] = {false, false};
+    PostJob job[2];                              /* per staging slot: build_group copies it when the group is enqueued */
     return run_groups(e, model, m, len.data(), n, p, out, [&](int k, const uint32_t *idx, size_t cnt, GroupArgs &a) {
         /* staging buffer k was last read by the upload of group g-2 */
         Slot &st = e->slots[k];
@@ -493,6 +496,11 @@ static int basecall_batch_one(scrappie_hip_engine *e, int model, const raw_table
         else HIPCHK(sh_stream_wait(e->stream));
         used[k] = true;
         a.d = st.d_signal.as<float>(); a.off = off[k].data(); a.len = glen[k].data();
+        if (probs) {
+            job[k].on = true; job[k].dst.resize(cnt);
+            for (size_t i = 0; i < cnt; i++) job[k].dst[i] = probs + idx[i];
+            a.pj = &job[k];
+        }
         return 0;
     });
 }

@@ -5,7 +5,7 @@
 /* public batched surface                                               */
 /* ------------------------------------------------------------------ */
 static long run_device(scrappie_hip_engine *e, int model, const float *d_signal, const uint64_t *offsets, const uint32_t *lengths, size_t n,
-                       const scrappie_hip_params *p, const DwellJob *dw) {
+                       const scrappie_hip_params *p, const DwellJob *dw, const PostJob *pj = nullptr) {
     Model *m = get_model(e, model);
     if (!m) return -1;
     scrappie_hip_params dp = scrappie_hip_default_params();
@@ -13,7 +13,7 @@ static long run_device(scrappie_hip_engine *e, int model, const float *d_signal,
     if (n > e->max_launch_reads) { set_err("run_device: %zu reads exceed max_launch_reads %zu", n, e->max_launch_reads); return -1; }
     if (e->dbg_fail_run > 0 && --e->dbg_fail_run == 0) { set_err("run_device: injected failure (debug option fail_run)"); return -1; }
     const HostStamp stamp;
-    if (run_pipeline(e, m, d_signal, offsets, lengths, n, p, STOP_NONE, 5, nullptr, dw)) return -1;
+    if (run_pipeline(e, m, d_signal, offsets, lengths, n, p, STOP_NONE, 5, nullptr, dw, pj)) return -1;
     stamp("run_device", " on the host");
     return (long)e->current().lg.ncb;
 }
@@ -88,6 +88,7 @@ static void stitch_range(const scrappie_hip_engine *e, const Slot &sl, const Mod
 }
 
 static int stitch_group(scrappie_hip_engine *e, Slot &sl, Model *m, const scrappie_hip_params *p, scrappie_hip_call *out, size_t n);
+static void crf_post_deliver(scrappie_hip_engine *e, Slot &sl, const scrappie_hip_call *out);      /* sh_eng_crfpost.inc */
 
 /* Host threads for stitching a launch group: the CPUs this process may actually use -- its affinity mask and its
  * cgroup CPU quota (a GPU box may report 256 CPUs and grant 16), shared with the other ranks of a torchrun job
@@ -153,7 +154,8 @@ extern "C" int scrappie_hip_collect(scrappie_hip_engine *e, const scrappie_hip_p
         const int other_oldest = e->oldest;
         e->handover = false;
         const DwellJob dw = lg.dw;                       /* (a copy: the re-run may take this very slot) */
-        const int rc = run_pipeline(e, m, dsig, off.data(), len.data(), n, &pp, STOP_NONE, 5, nullptr, &dw);
+        const PostJob pj = lg.post;
+        const int rc = run_pipeline(e, m, dsig, off.data(), len.data(), n, &pp, STOP_NONE, 5, nullptr, &dw, &pj);
         e->handover = true;
         if (rc) return -1;
         Slot &rs = e->current();
@@ -223,6 +225,7 @@ static int stitch_group(scrappie_hip_engine *e, Slot &sl, Model *m, const scrapp
         }
         e->n_redo += nredo;
     }
+    if (lg.post.on) crf_post_deliver(e, sl, out);
     return 0;
 }
 
@@ -232,7 +235,7 @@ static int stitch_group(scrappie_hip_engine *e, Slot &sl, Model *m, const scrapp
  * its group with other long reads, not hold a group of short ones hostage (DESIGN.md section 7, mixed lengths).
  * stage(k, idx, cnt) makes the signals of reads idx[0..cnt) of the call available on the device and returns the
  * pointer/offset/length arrays to run them with. */
-struct GroupArgs { const float *d; const uint64_t *off; const uint32_t *len; const DwellJob *dw = nullptr; };      /* (dw: events with the dwell correction, the group's dwells) */
+struct GroupArgs { const float *d; const uint64_t *off; const uint32_t *len; const DwellJob *dw = nullptr; const PostJob *pj = nullptr; };      /* (dw: events with the dwell correction, the group's dwells; pj: a flip-flop group's base probabilities) */
 
 /* the last launch group of a streaming call (scrappie_hip_basecall_device_stream), still in flight when the call returned: collected by
  * the next call on the engine -- behind that call's first launch -- or by scrappie_hip_stream_flush */
@@ -295,7 +298,7 @@ static int run_groups(scrappie_hip_engine *e, int model, const Model *m, const u
         const size_t lo = starts[g], cnt = starts[g + 1] - lo;
         GroupArgs a;
         int rc = stage((int)((g + slot0) & 1), perm.data() + lo, cnt, a);
-        if (!rc && run_device(e, model, a.d, a.off, a.len, cnt, p, a.dw) < 0) rc = -1;
+        if (!rc && run_device(e, model, a.d, a.off, a.len, cnt, p, a.dw, a.pj) < 0) rc = -1;
         if (e->carry.live) { if (collect_carry(e)) rc = -1; }          /* the previous call's last group, behind this call's first launch */
         else if (have_prev && collect(prev)) rc = -1;
         have_prev = false;

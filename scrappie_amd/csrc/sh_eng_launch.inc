@@ -18,7 +18,7 @@ static long long bases_reservation(long long per_entry, long long nentry) { retu
 extern "C" size_t scrappie_hip_dwell_capacity(size_t nentry) { return (size_t)bases_reservation(SH_DWELL_PER_ENTRY, (long long)nentry); }
 
 static int build_group(scrappie_hip_engine *e, Slot &sl, Model *m, const uint64_t *offsets, const uint32_t *lengths,
-                       size_t n, bool hp_on, MetaPtrs &mp, const DwellJob *dw = nullptr) {
+                       size_t n, bool hp_on, MetaPtrs &mp, const DwellJob *dw = nullptr, const PostJob *pj = nullptr) {
     LaunchGroup &lg = sl.lg;
     lg.valid = false;
     lg.n = n; lg.hp_on = hp_on;
@@ -26,6 +26,11 @@ static int build_group(scrappie_hip_engine *e, Slot &sl, Model *m, const uint64_
     if (dw && dw->on) {
         if (m->arch != 3 || dw->off.size() != n || dw->num.size() != n || dw->host.size() != n) return set_err("build_group: %zu reads, dwells of %zu", n, dw->off.size());
         lg.dw = *dw;
+    }
+    lg.post = PostJob(); lg.npost = 0;
+    if (pj && pj->on) {
+        if (m->arch != 1 || pj->dst.size() != n) return set_err("build_group: base probabilities of %zu reads for a group of %zu (flip-flop models only)", pj->dst.size(), n);
+        lg.post = *pj;
     }
     lg.ntile = (n + 15) / 16; lg.npad = lg.ntile * 16;
     const int st = m->stride;

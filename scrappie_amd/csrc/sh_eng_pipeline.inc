@@ -48,6 +48,7 @@ struct GroupRun {
     StopAt stop = STOP_NONE; int trunk_upto = 5; RunOut *ro = nullptr;
     bool transducer = false, hp_on = false;
     const DwellJob *dw = nullptr;      /* events with the dwell correction: the group's dwells (null: plain stitching) */
+    const PostJob *pj = nullptr;       /* flip-flop models: base probabilities wanted, and where they go (null: none) */
     MetaPtrs mp;
     hipStream_t s = nullptr, ps = nullptr, cs = nullptr;      /* main, prologue and copy stream (all three the main stream where the engine has no events) */
     long long ncb = 0; size_t act_bytes = 0;
@@ -58,6 +59,10 @@ struct GroupRun {
     Marks pf;
     HostStamp stamp;
 };
+
+static int crf_post_mark(Slot &sl, int k, hipStream_t st);
+static int crf_post_enqueue(Slot &sl, GroupRun &c);      /* sh_eng_crfpost.inc */
+static int crf_post_download(Slot &sl, GroupRun &c);
 
 static int longest_tile(const LaunchGroup &lg) {      /* sorted: the first read of a tile is its longest */
     int maxT = 0;
@@ -79,7 +84,7 @@ static int begin_group(scrappie_hip_engine *e, Model *m, const uint32_t *lengths
     if (!slp) return set_err("two launch groups are already in flight: call scrappie_hip_collect first");
     Slot &sl = *slp;
     e->cur = e->index(sl);
-    if (build_group(e, sl, m, c.offsets, lengths, n, c.hp_on, c.mp, c.dw)) return -1;
+    if (build_group(e, sl, m, c.offsets, lengths, n, c.hp_on, c.mp, c.dw, c.pj)) return -1;
     c.stamp("build_group");
     *slot = slp;
     *empty = sl.lg.ncb == 0;
@@ -365,7 +370,7 @@ static int stage_decode_transducer(Slot &sl, Model *m, GroupRun &c, const float 
 /* Stage 3, flip-flop (CRF) models: output layer + k_crf (decoder and walk back in one) */
 static int stage_decode_crf(Slot &sl, Model *m, GroupRun &c, const float *top, bool *stopped) {
     scrappie_hip_engine *e = c.e;
-    const LaunchGroup &lg = sl.lg; const MetaPtrs &mp = c.mp;
+    LaunchGroup &lg = sl.lg; const MetaPtrs &mp = c.mp;
     const hipStream_t s = c.s;
     const int S = m->S, mtiles = m->ff_mtiles;
     const long long ncb = c.ncb;
@@ -378,13 +383,16 @@ static int stage_decode_crf(Slot &sl, Model *m, GroupRun &c, const float *top, b
     /* d_tb is shared by the two slots: a transducer group in the other slot may still be walking it
      * (k_backtrace on the copy stream) */
     if (e->ev_ok && e->other(sl).pending) HIPCHK(hipStreamWaitEvent(s, e->other(sl).done, 0));
-    /* (only the posterior surface looks at the normalised transitions afterwards: the basecall path does not write them back) */
-    hipLaunchKernelGGL((c.ro || c.stop == STOP_POST) ? k_crf<true> : k_crf<false>, dim3((unsigned)(lg.npad / 16)), dim3(128), 0, s, e->d_E.as<float>(), mp.md,
+    /* (only the posterior surface and k_crf_post look at the normalised transitions afterwards: the plain basecall path does not write them back) */
+    const bool probs = lg.post.on && c.stop == STOP_NONE;
+    hipLaunchKernelGGL((c.ro || c.stop == STOP_POST || probs) ? k_crf<true> : k_crf<false>, dim3((unsigned)(lg.npad / 16)), dim3(128), 0, s, e->d_E.as<float>(), mp.md,
                        e->d_tb.as<unsigned char>(), mp.seq_off, sl.d_seq.as<int>(), sl.d_fscore.as<float>(), (int)lg.npad, SH_SEQ_STRIDE);
     if (c.pf.mark(Marks::DECODE_END, s)) return -1;
     c.pf.span(F_DECODE, Marks::S1_END, Marks::DECODE_END);
     if (c.ro) { c.ro->E = e->d_E.as<float>(); c.ro->sums = nullptr; }
     if (c.stop == STOP_POST) { HIPCHK(hipGetLastError()); *stopped = true; }
+    /* base probabilities: on the main stream, before the next group's output layer can overwrite d_E (the engine's, not the slot's) */
+    if (probs && crf_post_enqueue(sl, c)) return -1;
     return 0;
 }
 
@@ -454,6 +462,8 @@ static int stage_tail(Slot &sl, Model *m, GroupRun &c) {
         HIPCHK(hipMemcpyAsync(sl.h_err.p, sl.d_gflag.as<unsigned>() + lg.ntile, 4, hipMemcpyDeviceToHost, cs));
         HIPCHK(hipMemcpyAsync(sl.h_bad.p, sl.d_bad.p, lg.npad * 4, hipMemcpyDeviceToHost, cs));
     }
+    /* the base probabilities behind the slot's results, in front of its done event: the next group's kernels do not wait for PCIe */
+    if (lg.post.on && crf_post_download(sl, c)) return -1;
     HIPCHK(hipGetLastError());
     c.stamp("copies enqueued at");
     if (e->ev_ok) HIPCHK(hipEventRecord(sl.done, cs));
@@ -462,11 +472,11 @@ static int stage_tail(Slot &sl, Model *m, GroupRun &c) {
 
 static int run_pipeline(scrappie_hip_engine *e, Model *m, const float *d_signal, const uint64_t *offsets,
                         const uint32_t *lengths, size_t n, const scrappie_hip_params *p, StopAt stop,
-                        int trunk_upto, RunOut *ro, const DwellJob *dw = nullptr) {
+                        int trunk_upto, RunOut *ro, const DwellJob *dw = nullptr, const PostJob *pj = nullptr) {
     (void)hipSetDevice(e->device);
     if (n == 0) return set_err("empty batch");
     GroupRun c;
-    c.e = e; c.d_signal = d_signal; c.offsets = offsets; c.p = p; c.stop = stop; c.trunk_upto = trunk_upto; c.ro = ro; c.dw = dw;
+    c.e = e; c.d_signal = d_signal; c.offsets = offsets; c.p = p; c.stop = stop; c.trunk_upto = trunk_upto; c.ro = ro; c.dw = dw; c.pj = pj;
     c.transducer = (m->arch != 1);
     c.hp_on = c.transducer && p->homopolymer == HOMOPOLYMER_MEAN && stop == STOP_NONE;
     c.s = e->stream; c.ps = e->ev_ok ? e->pstream : e->stream; c.cs = e->ev_ok ? e->cstream : e->stream;
@@ -488,6 +498,7 @@ static int run_pipeline(scrappie_hip_engine *e, Model *m, const float *d_signal,
     c.pf.sl = &sl; c.pf.on = e->profiling && e->ev_ok;
     if (c.pf.on) { memset(&sl.timing, 0, sizeof sl.timing); sl.nev = 0; sl.spans.clear(); }
     if (stage_prologue(sl, m, c)) return -1;
+    if (lg.post.on && e->ev_ok && crf_post_mark(sl, 0, c.s)) return -1;      /* (PEV_MAIN: the main stream's part of the group starts here) */
     int cur = 0;
     if (stage_trunk(sl, m, c, &cur)) return -1;
     if (ro) { ro->act = c.abuf[cur]; ro->act_units = (trunk_upto == 0) ? F : S; }

@@ -481,6 +481,8 @@ int homopolymer_path(const_scrappie_matrix post, int *viterbipath,
 /* ------------------------------------------------------------------ */
 /* D5 posterior_crf (decode.c:928-1012): optional per-block state       */
 /* posterior for the CRF model; O(25 T) with libm, kept on the host.    */
+/* (Batched, on the device: k_crf_post, sh_crf_post.h; this one is the   */
+/* reference's to the bit and stays what the per-read symbol runs.)     */
 /* ------------------------------------------------------------------ */
 static inline float lse2(float x, float y) {       /* util.h:162 */
     return fmaxf(x, y) + log1pf(expf(-fabsf(x - y)));
@@ -524,6 +526,48 @@ scrappie_matrix posterior_crf(const_scrappie_matrix trans) {
         for (size_t s = 0; s < ns; s++) col[s] = expf(col[s] - tot);
     }
     free(bwd);
+    return post;
+}
+
+/* The host side of the batched posterior (k_crf_post, sh_eng_crfpost.inc): where every read's (nblock + 1) x 5 floats lie in the output buffer,
+ * the staging of a launch's matrices, a result as posterior_crf returns it.  Plain C, so that a sanitizer build can run them (tests/crf_post_asan.c). */
+long long scrappie_hip_crf_post_plan(const size_t *nblock, size_t n, long long *off) {
+    if (n && (!nblock || !off)) return -1;
+    long long tot = 0;
+    for (size_t i = 0; i < n; i++) {
+        off[i] = tot;
+        if (nblock[i]) tot += (long long)((((nblock[i] + 1) * 5) + 3) & ~(size_t)3);      /* starts stay 16-byte aligned; no blocks, no room */
+    }
+    return tot;
+}
+
+int sh_crf_post_ok(const_scrappie_matrix m) {
+    return m && m->data.f && m->nr == 25 && m->nc >= 1 && m->stride >= 25;
+}
+
+/* Matrices trans[order[0 .. n)] (all sh_crf_post_ok) end to end into dst, each with its own stride, and the per-slot words of a launch of npad = 16
+ * ntile slots (slots n .. npad - 1: no read): first float, stride, blocks; per tile its longest read.  A matrix is read as far as its last column's
+ * 25th float (a caller's own container need not be padded behind it).  Returns the floats the matrices take (an even number). */
+size_t sh_crf_post_stage(const const_scrappie_matrix *trans, const size_t *order, size_t n, size_t npad, float *dst,
+                         long long *foff, int *stride, int *T, int *tile_T) {
+    size_t at = 0;
+    for (size_t t = 0; t < npad / 16; t++) tile_T[t] = 0;
+    for (size_t k = 0; k < npad; k++) {
+        foff[k] = 0; stride[k] = 0; T[k] = 0;
+        if (k >= n) continue;
+        const_scrappie_matrix m = trans[order[k]];
+        if (dst) memcpy(dst + at, m->data.f, ((m->nc - 1) * m->stride + 25) * sizeof(float));
+        foff[k] = (long long)at; stride[k] = (int)m->stride; T[k] = (int)m->nc;
+        if (T[k] > tile_T[k / 16]) tile_T[k / 16] = T[k];
+        at += m->nc * m->stride;
+    }
+    return (at + 1) & ~(size_t)1;
+}
+
+scrappie_matrix sh_crf_post_take(const float *src, size_t nblock) {
+    scrappie_matrix post = make_scrappie_matrix(5, nblock + 1);
+    if (!post) return NULL;
+    for (size_t c = 0; c <= nblock; c++) memcpy(post->data.f + c * post->stride, src + c * 5, 5 * sizeof(float));
     return post;
 }
 

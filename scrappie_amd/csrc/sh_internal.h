@@ -26,6 +26,14 @@ float sh_dwell_scale(const void *pos, const void *state, size_t stride, const in
 float sh_dwell_prior_num(const event_t *ev, size_t n);
 #endif
 char *sh_dwell_stitch(const int *path, const int *dwell, int n, int ntrail, int nstate, float prior_num, int *pos_out);
+#ifdef SCRAPPIE_HIP_H
+/* batched CRF posterior (sh_host.c): is this a 25-row transition matrix with a block; a launch's matrices trans[order[0 .. n)] end to end into dst
+ * (NULL: sizes only) with the words of its npad slots and npad / 16 tiles, returns the floats they take; a 5 x (nblock + 1) matrix from [nblock + 1][5] */
+int sh_crf_post_ok(const_scrappie_matrix m);
+size_t sh_crf_post_stage(const const_scrappie_matrix *trans, const size_t *order, size_t n, size_t npad, float *dst,
+                         long long *foff, int *stride, int *T, int *tile_T);
+scrappie_matrix sh_crf_post_take(const float *src, size_t nblock);
+#endif
 #ifdef __cplusplus
 }
 #endif
