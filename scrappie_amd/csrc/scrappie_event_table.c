@@ -12,11 +12,8 @@
 #include <getopt.h>
 #include <stdio.h>
 #include <stdlib.h>
-#include <string.h>
 
-#include "scrappie_hip.h"
-
-int main_event_table(int argc, char **argv);
+#include "scrappie_cli.h"
 
 static void event_table_usage(FILE *fh) {
     fputs("Usage: scrappie event_table [OPTION...] fast5 [fast5 ...]\n"
@@ -37,31 +34,16 @@ int main_event_table(int argc, char **argv) {
     FILE *out = stdout;
     int trim_start = 200, trim_end = 10, varseg_chunk = 100, device = 0, c;
     float varseg_thresh = 0.0f;
-    char *tok;
+    double pct;
     optind = 1;
     while ((c = getopt_long(argc, argv, "o:t:", lo, NULL)) != -1) {
         switch (c) {
-        case 'o':
-            out = fopen(optarg, "w");
-            if (!out) { fprintf(stderr, "scrappie: Failed to open \"%s\" for output.\n", optarg); return EXIT_FAILURE; }
-            break;
-        case 't':
-            tok = strtok(optarg, ":");
-            trim_start = tok ? atoi(tok) : 0;
-            tok = strtok(NULL, ":");
-            trim_end = tok ? atoi(tok) : trim_start;
-            if (trim_start < 0 || trim_end < 0) { fprintf(stderr, "scrappie: --trim wants start:end, both >= 0\n"); return EXIT_FAILURE; }
-            break;
+        case 'o': if (!(out = cli_open_output(optarg))) return EXIT_FAILURE; break;
+        case 't': if (cli_parse_trim(optarg, &trim_start, &trim_end)) { fprintf(stderr, "scrappie: --trim wants start:end, both >= 0\n"); return EXIT_FAILURE; } break;
         case O_SEG:
-            tok = strtok(optarg, ":");
-            varseg_chunk = tok ? atoi(tok) : -1;
-            tok = strtok(NULL, ":");
-            if (!tok || varseg_chunk < 0) { fprintf(stderr, "scrappie: --segmentation should be of form chunk:percentile\n"); return EXIT_FAILURE; }
-            varseg_thresh = (float)(atof(tok) / 100.0);
-            break;
-        case O_LIC:
-            puts("Mozilla Public License, version 2.0 (see LICENCE.md of the reference distribution).");
-            return EXIT_SUCCESS;
+            if (cli_parse_segmentation(optarg, &varseg_chunk, &pct) || varseg_chunk < 0) { fprintf(stderr, "scrappie: --segmentation should be of form chunk:percentile\n"); return EXIT_FAILURE; }
+            varseg_thresh = (float)(pct / 100.0); break;
+        case O_LIC: cli_licence(); break;
         case O_DEV: device = atoi(optarg); break;
         default: event_table_usage(c == '?' && optopt == 0 ? stdout : stderr); return c == '?' && optopt == 0 ? EXIT_SUCCESS : EXIT_FAILURE;
         }
@@ -72,16 +54,7 @@ int main_event_table(int argc, char **argv) {
     raw_table *reads = calloc((size_t)nfile, sizeof *reads);
     scrappie_hip_event_result *res = calloc((size_t)nfile, sizeof *res);
     if (!reads || !res) { fprintf(stderr, "scrappie: out of memory\n"); return EXIT_FAILURE; }
-    for (int i = 0; i < nfile; i++) {
-        raw_table rt = scrappie_hip_read_raw(files[i], true);
-        if (rt.raw && varseg_chunk > 0) rt = trim_and_segment_raw(rt, (size_t)trim_start, (size_t)trim_end, (size_t)varseg_chunk, varseg_thresh);
-        else if (rt.raw) {        /* the fixed trims alone (scrappie_common.c:14-20) */
-            rt.start = (rt.n - rt.start) > (size_t)trim_start ? rt.start + (size_t)trim_start : rt.n;
-            rt.end = rt.end > (size_t)trim_end ? rt.end - (size_t)trim_end : 0;
-            if (rt.start >= rt.end) { free(rt.raw); free(rt.uuid); memset(&rt, 0, sizeof rt); }
-        }
-        reads[i] = rt;            /* (.raw NULL: the batch refuses the read, and it is warned about below) */
-    }
+    for (int i = 0; i < nfile; i++) reads[i] = cli_load_read(files[i], trim_start, trim_end, varseg_chunk, varseg_thresh, 0);      /* (.raw NULL: the batch refuses the read, and it is warned about below) */
     scrappie_hip_engine *e = scrappie_hip_engine_create(device);
     if (!e) { fprintf(stderr, "scrappie: %s\n", scrappie_hip_last_error()); return EXIT_FAILURE; }
     int rc = EXIT_SUCCESS;

@@ -12,16 +12,13 @@
  */
 #define _GNU_SOURCE
 #include <getopt.h>
-#include <libgen.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <strings.h>
 
-#include "scrappie_hip.h"
-
-int main_events(int argc, char **argv);
+#include "scrappie_cli.h"
 
 static void events_usage(FILE *fh) {
     fputs("Usage: scrappie events [OPTION...] fast5 [fast5 ...]\n"
@@ -65,7 +62,7 @@ int main_events(int argc, char **argv) {
     int dwell = 1, sam = 0, limit = 0, trim_start = 200, trim_end = 10, varseg_chunk = 100, uuid_primary = 0, device = 0, c;
     float varseg_thresh = 0.0f;
     const char *prefix = "", *model_file = NULL;
-    char *tok;
+    double pct;
     optind = 1;
     while ((c = getopt_long(argc, argv, "f:l:m:o:p:s:y:t:#:", lo, NULL)) != -1) {
         switch (c) {
@@ -76,20 +73,11 @@ int main_events(int argc, char **argv) {
             break;
         case 'l': limit = atoi(optarg); if (limit < 0) { fprintf(stderr, "scrappie: --limit wants a count >= 0\n"); return EXIT_FAILURE; } break;
         case 'm': p.min_prob = (float)atof(optarg); if (!isfinite(p.min_prob) || p.min_prob < 0.0f) { fprintf(stderr, "scrappie: --min_prob wants a probability\n"); return EXIT_FAILURE; } break;
-        case 'o':
-            out = fopen(optarg, "w");
-            if (!out) { fprintf(stderr, "scrappie: Failed to open \"%s\" for output.\n", optarg); return EXIT_FAILURE; }
-            break;
+        case 'o': if (!(out = cli_open_output(optarg))) return EXIT_FAILURE; break;
         case 'p': prefix = optarg; break;
         case 's': p.skip_pen = (float)atof(optarg); break;
         case 'y': p.stay_pen = (float)atof(optarg); break;
-        case 't':
-            tok = strtok(optarg, ":");
-            trim_start = tok ? atoi(tok) : 0;
-            tok = strtok(NULL, ":");
-            trim_end = tok ? atoi(tok) : trim_start;
-            if (trim_start < 0 || trim_end < 0) { fprintf(stderr, "scrappie: --trim wants start:end, both >= 0\n"); return EXIT_FAILURE; }
-            break;
+        case 't': if (cli_parse_trim(optarg, &trim_start, &trim_end)) { fprintf(stderr, "scrappie: --trim wants start:end, both >= 0\n"); return EXIT_FAILURE; } break;
         case '#': break;
         case O_SLIP: p.use_slip = 1; break;
         case O_NOSLIP: p.use_slip = 0; break;
@@ -100,16 +88,10 @@ int main_events(int argc, char **argv) {
         case O_LOCAL: p.local_pen = (float)atof(optarg); break;
         case O_T1: p.tempW = (float)atof(optarg); if (!(p.tempW > 0.0f) || !isfinite(p.tempW)) { fprintf(stderr, "scrappie: --temperature1 wants a factor > 0\n"); return EXIT_FAILURE; } break;
         case O_T2: p.tempb = (float)atof(optarg); if (!(p.tempb > 0.0f) || !isfinite(p.tempb)) { fprintf(stderr, "scrappie: --temperature2 wants a factor > 0\n"); return EXIT_FAILURE; } break;
-        case O_LIC:
-            puts("Mozilla Public License, version 2.0 (see LICENCE.md of the reference distribution).");
-            return EXIT_SUCCESS;
+        case O_LIC: cli_licence(); break;
         case O_SEG:
-            tok = strtok(optarg, ":");
-            varseg_chunk = tok ? atoi(tok) : -1;
-            tok = strtok(NULL, ":");
-            if (!tok || varseg_chunk < 0) { fprintf(stderr, "scrappie: --segmentation should be of form chunk:percentile\n"); return EXIT_FAILURE; }
-            varseg_thresh = (float)(atof(tok) / 100.0);
-            break;
+            if (cli_parse_segmentation(optarg, &varseg_chunk, &pct) || varseg_chunk < 0) { fprintf(stderr, "scrappie: --segmentation should be of form chunk:percentile\n"); return EXIT_FAILURE; }
+            varseg_thresh = (float)(pct / 100.0); break;
         case O_UUID: uuid_primary = 1; break;
         case O_NOUUID: uuid_primary = 0; break;
         case O_MFILE: model_file = optarg; break;
@@ -121,31 +103,16 @@ int main_events(int argc, char **argv) {
     if (nfile < 1) { events_usage(stderr); return EXIT_FAILURE; }
     if (limit > 0 && nfile > limit) nfile = limit;
     char **files = argv + optind;
-    char *mpath = NULL;
-    if (model_file) mpath = strdup(model_file);
-    else if (getenv("SCRAPPIE_MODEL_DIR") && asprintf(&mpath, "%s/nanonet_events.scrm", getenv("SCRAPPIE_MODEL_DIR")) < 0) mpath = NULL;
-    if (!mpath) { fprintf(stderr, "scrappie: no weights for model nanonet_events (weights are data, not part of this build): give --model-file or set SCRAPPIE_MODEL_DIR\n"); return EXIT_FAILURE; }
+    char *mpath = cli_model_path("nanonet_events", model_file);
+    if (!mpath) return EXIT_FAILURE;
     raw_table *reads = calloc((size_t)nfile, sizeof *reads);
     scrappie_hip_call *calls = calloc((size_t)nfile, sizeof *calls);
     if (!reads || !calls) { fprintf(stderr, "scrappie: out of memory\n"); return EXIT_FAILURE; }
-    for (int i = 0; i < nfile; i++) {
-        raw_table rt = scrappie_hip_read_raw(files[i], true);
-        if (rt.raw && varseg_chunk > 0) {
-            char *uuid = rt.uuid;            /* (trim_and_segment_raw frees the signal of a read it trims away, not its uuid) */
-            rt = trim_and_segment_raw(rt, (size_t)trim_start, (size_t)trim_end, (size_t)varseg_chunk, varseg_thresh);
-            if (!rt.raw) free(uuid);
-        } else if (rt.raw) {      /* the fixed trims alone (scrappie_common.c:14-20) */
-            rt.start = (rt.n - rt.start) > (size_t)trim_start ? rt.start + (size_t)trim_start : rt.n;
-            rt.end = rt.end > (size_t)trim_end ? rt.end - (size_t)trim_end : 0;
-            if (rt.start >= rt.end) { free(rt.raw); free(rt.uuid); memset(&rt, 0, sizeof rt); }
-        }
-        reads[i] = rt;            /* (.raw NULL: no events, no call, and the warning below) */
-    }
-    scrappie_hip_engine *e = scrappie_hip_engine_create(device);
-    if (!e) { fprintf(stderr, "scrappie: %s\n", scrappie_hip_last_error()); return EXIT_FAILURE; }
-    const int model = scrappie_hip_load_model(e, "nanonet_events", mpath);
-    if (model < 0) { fprintf(stderr, "scrappie: %s\n", scrappie_hip_last_error()); return EXIT_FAILURE; }
+    for (int i = 0; i < nfile; i++) reads[i] = cli_load_read(files[i], trim_start, trim_end, varseg_chunk, varseg_thresh, 0);      /* (.raw NULL: no events, no call, and the warning below) */
+    int model;
+    scrappie_hip_engine *e = cli_open_model(device, "nanonet_events", mpath, &model);
     free(mpath);
+    if (!e) return EXIT_FAILURE;
     /* the batch takes the reads that are there; the others keep their place in the output order */
     int nlive = 0;
     raw_table *live = calloc((size_t)nfile, sizeof *live);
@@ -162,15 +129,15 @@ int main_events(int argc, char **argv) {
         for (int i = 0; i < nfile; i++) {
             const scrappie_hip_call *res = &calls[i];
             if (!res->basecall) { fprintf(stderr, "scrappie: No basecall returned for %s\n", files[i]); continue; }
-            char *fcopy = strdup(files[i]);
-            const char *readname = basename(fcopy), *uuid = reads[i].uuid ? reads[i].uuid : "";
+            const char *uuid = reads[i].uuid ? reads[i].uuid : "";
+            char *readname = cli_record_name(files[i], NULL, 0), *id = cli_record_name(files[i], uuid, uuid_primary);
             const size_t nev = res->nblock, nbase = strlen(res->basecall);
             if (sam)
-                fprintf(out, "%s%s\t4\t*\t0\t0\t*\t*\t0\t0\t%s\t*\n", prefix, uuid_primary ? uuid : readname, res->basecall);
+                fprintf(out, "%s%s\t4\t*\t0\t0\t*\t*\t0\t0\t%s\t*\n", prefix, id, res->basecall);
             else
                 fprintf(out, ">%s%s  { \"filename\" : \"%s\", \"uuid\" : \"%s\", \"normalised_score\" : %f,  \"nevent\" : %zu,  \"sequence_length\" : %zu,  \"events_per_base\" : %f }\n%s\n",
-                        prefix, uuid_primary ? uuid : readname, readname, uuid, -res->score / nev, nev, nbase, (float)nev / (float)nbase, res->basecall);
-            free(fcopy);
+                        prefix, id, readname, uuid, -res->score / nev, nev, nbase, (float)nev / (float)nbase, res->basecall);
+            free(readname); free(id);
         }
         scrappie_hip_free_calls(calls, (size_t)nfile);
     }

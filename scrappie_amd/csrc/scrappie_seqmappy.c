@@ -11,43 +11,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <sys/types.h>
 
-#include "scrappie_hip.h"
-
-int main_seqmappy(int argc, char **argv);
-
-static int parse_pair(const char *arg, long *a, double *b_or_null, long *b_long) {
-    /* "start:end" / "chunk:percentile" */
-    char *end = NULL;
-    *a = strtol(arg, &end, 10);
-    if (!end || *end != ':') return -1;
-    if (b_long) *b_long = strtol(end + 1, NULL, 10);
-    if (b_or_null) *b_or_null = strtod(end + 1, NULL);
-    return 0;
-}
-
-/* the first record of a FASTA file, its sequence lines joined (NULL if there is none) */
-static char *read_fasta_first(const char *path, size_t *n) {
-    FILE *fh = fopen(path, "r");
-    if (!fh) return NULL;
-    char *line = NULL, *seq = NULL;
-    size_t cap = 0, len = 0, scap = 0;
-    ssize_t got;
-    int in_rec = 0;
-    while ((got = getline(&line, &cap, fh)) != -1) {
-        while (got > 0 && (line[got - 1] == '\n' || line[got - 1] == '\r')) line[--got] = '\0';
-        if (line[0] == '>') { if (in_rec) break; in_rec = 1; continue; }
-        if (!in_rec || got == 0) continue;
-        if (len + (size_t)got + 1 > scap) { scap = 2 * (len + (size_t)got + 1); seq = realloc(seq, scap); if (!seq) break; }
-        memcpy(seq + len, line, (size_t)got); len += (size_t)got; seq[len] = '\0';
-    }
-    free(line);
-    fclose(fh);
-    if (!in_rec || !seq) { free(seq); return NULL; }
-    *n = len;
-    return seq;
-}
+#include "scrappie_cli.h"
 
 static void seqmappy_usage(FILE *fh) {
     fputs("Usage: scrappie seqmappy [OPTION...] fasta fast5 [fasta fast5 ...]\n"
@@ -84,33 +49,24 @@ int main_seqmappy(int argc, char **argv) {
     int trim_start = 200, trim_end = 10, varseg_chunk = 100, device = 0;
     float varseg_thresh = 0.0f;
     const char *model = "rgrgr_r94", *model_file = NULL;
-    long a, bl;
-    double bd;
+    double pct;
     int c;
     optind = 1;
     while ((c = getopt_long(argc, argv, "l:m:o:p:s:y:t:", lo, NULL)) != -1) {
         switch (c) {
         case 'l': p.local_pen = (float)atof(optarg); break;
         case 'm': p.min_prob = (float)atof(optarg); break;
-        case 'o':
-            out = fopen(optarg, "w");
-            if (!out) { fprintf(stderr, "scrappie: Failed to open \"%s\" for output.\n", optarg); return EXIT_FAILURE; }
-            break;
+        case 'o': if (!(out = cli_open_output(optarg))) return EXIT_FAILURE; break;
         case 'p': break;                 /* accepted; the reference's seqmappy never prints it */
         case 's': p.skip_pen = (float)atof(optarg); break;
         case 'y': p.stay_pen = (float)atof(optarg); break;
-        case 't':
-            if (parse_pair(optarg, &a, NULL, &bl)) bl = a;
-            if (a < 0 || bl < 0) { fprintf(stderr, "scrappie: --trim wants start:end\n"); return EXIT_FAILURE; }
-            trim_start = (int)a; trim_end = (int)bl;
-            break;
+        case 't': if (cli_parse_trim(optarg, &trim_start, &trim_end)) { fprintf(stderr, "scrappie: --trim wants start:end\n"); return EXIT_FAILURE; } break;
         case O_SEG:
-            if (parse_pair(optarg, &a, &bd, NULL) || a < 0 || bd <= 0 || bd >= 100) { fprintf(stderr, "scrappie: --segmentation should be of form chunk:percentile\n"); return EXIT_FAILURE; }
-            varseg_chunk = (int)a; varseg_thresh = (float)(bd / 100.0);
-            break;
+            if (cli_parse_segmentation(optarg, &varseg_chunk, &pct) || varseg_chunk < 0 || pct <= 0 || pct >= 100) { fprintf(stderr, "scrappie: --segmentation should be of form chunk:percentile\n"); return EXIT_FAILURE; }
+            varseg_thresh = (float)(pct / 100.0); break;
         case O_T1: p.tempW = (float)atof(optarg); break;
         case O_T2: p.tempb = (float)atof(optarg); break;
-        case O_LIC: puts("Mozilla Public License 2.0 applies to the reference interface this build follows."); exit(EXIT_SUCCESS);
+        case O_LIC: cli_licence(); break;
         case O_MODEL:
             if (get_raw_model(optarg) == SCRAPPIE_MODEL_INVALID) { fprintf(stderr, "scrappie: Invalid model name \"%s\"\n", optarg); return EXIT_FAILURE; }
             model = optarg;
@@ -126,15 +82,9 @@ int main_seqmappy(int argc, char **argv) {
     const size_t npair = (size_t)nargs / 2;
     char **fasta = argv + optind;        /* fasta[2 i], fast5 = fasta[2 i + 1] */
 
-    scrappie_hip_engine *e = scrappie_hip_engine_create(device);
-    if (!e) { fprintf(stderr, "scrappie: %s\n", scrappie_hip_last_error()); return EXIT_FAILURE; }
-    char *mpath = NULL;
-    if (model_file) mpath = strdup(model_file);
-    else if (getenv("SCRAPPIE_MODEL_DIR")) { if (asprintf(&mpath, "%s/%s.scrm", getenv("SCRAPPIE_MODEL_DIR"), model) < 0) mpath = NULL; }
-    if (!mpath) { fprintf(stderr, "scrappie: no weights for model %s: give --model-file or set SCRAPPIE_MODEL_DIR\n", model); return EXIT_FAILURE; }
-    const int h = scrappie_hip_load_model(e, model, mpath);
-    free(mpath);
-    if (h < 0) { fprintf(stderr, "scrappie: %s\n", scrappie_hip_last_error()); return EXIT_FAILURE; }
+    int h;
+    scrappie_hip_engine *e = cli_open_model(device, model, model_file, &h);
+    if (!e) return EXIT_FAILURE;
     int nstate = scrappie_hip_model_states(e, h), klen = 0;
     for (int nk = nstate - 1; nk > 1 && nk % 4 == 0; nk /= 4) klen++;
 
@@ -145,19 +95,17 @@ int main_seqmappy(int argc, char **argv) {
     int rc = EXIT_SUCCESS;
     for (size_t i = 0; i < npair; i++) {
         const char *fa = fasta[2 * i], *f5 = fasta[2 * i + 1];
-        size_t n = 0;
-        char *seq = read_fasta_first(fa, &n);
-        if (!seq) { fprintf(stderr, "scrappie: Failed to open \"%s\" for input.\n", fa); rc = EXIT_FAILURE; continue; }
-        codes[i] = encode_bases_to_integers(seq, n, (size_t)klen);
-        free(seq);
+        struct cli_fasta *rec = NULL;       /* the first record of the file */
+        size_t nrec = 0;
+        if (cli_read_fasta(fa, &rec, &nrec, 1) || nrec == 0 || !rec[0].seq || rec[0].n == 0) { fprintf(stderr, "scrappie: Failed to open \"%s\" for input.\n", fa); cli_free_fasta(rec, nrec); rc = EXIT_FAILURE; continue; }
+        const size_t n = rec[0].n;
+        codes[i] = encode_bases_to_integers(rec[0].seq, n, (size_t)klen);
+        cli_free_fasta(rec, nrec);
         if (!codes[i]) { fprintf(stderr, "scrappie: cannot encode the sequence of \"%s\": %s\n", fa, scrappie_hip_last_error()); rc = EXIT_FAILURE; continue; }
         tg[i].seq = codes[i]; tg[i].seqlen = n - (size_t)klen + 1;
         /* scrappie_seqmappy.c:187-194 */
-        raw_table rt = scrappie_hip_read_raw(f5, true);
-        rt = trim_and_segment_raw(rt, (size_t)trim_start, (size_t)trim_end, (size_t)varseg_chunk, varseg_thresh);
-        if (!rt.raw) { fprintf(stderr, "scrappie: Failed to open \"%s\" for input and trim signal.\n", f5); rc = EXIT_FAILURE; continue; }
-        medmad_normalise_array(rt.raw + rt.start, rt.end - rt.start);
-        rts[i] = rt;
+        rts[i] = cli_load_read(f5, trim_start, trim_end, varseg_chunk, varseg_thresh, 1);
+        if (!rts[i].raw) { fprintf(stderr, "scrappie: Failed to open \"%s\" for input and trim signal.\n", f5); rc = EXIT_FAILURE; continue; }
     }
     if (scrappie_hip_map_batch(e, h, rts, tg, npair, &p, 1, 1, res) != 0) {
         fprintf(stderr, "scrappie: %s\n", scrappie_hip_last_error());

@@ -13,71 +13,11 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <sys/types.h>
 
-#include "scrappie_hip.h"
-
-int main_squiggle(int argc, char **argv);
-int main_mappy(int argc, char **argv);
-
-struct fa_rec { char *name, *seq; size_t n; };
-
-/* the records of a FASTA file appended to *recs (at most `limit` in all, 0: no limit): the name is the header up to the first
- * blank, the sequence its lines joined; -1 if the file cannot be opened */
-static int read_fasta(const char *path, struct fa_rec **recs, size_t *nrec, size_t limit) {
-    FILE *fh = fopen(path, "r");
-    if (!fh) return -1;
-    char *line = NULL;
-    size_t cap = 0, scap = 0;
-    ssize_t got;
-    struct fa_rec *cur = NULL;
-    while ((got = getline(&line, &cap, fh)) != -1) {
-        while (got > 0 && (line[got - 1] == '\n' || line[got - 1] == '\r')) line[--got] = '\0';
-        if (line[0] == '>') {
-            if (limit && *nrec >= limit) break;
-            struct fa_rec *grown = realloc(*recs, (*nrec + 1) * sizeof **recs);
-            if (!grown) break;
-            *recs = grown;
-            cur = &grown[(*nrec)++];
-            cur->name = strndup(line + 1, strcspn(line + 1, " \t"));
-            cur->seq = calloc(1, 1); cur->n = 0; scap = 1;
-            continue;
-        }
-        if (!cur || got == 0 || !cur->seq) continue;
-        if (cur->n + (size_t)got + 1 > scap) {
-            scap = 2 * (cur->n + (size_t)got + 1);
-            char *s = realloc(cur->seq, scap);
-            if (!s) break;
-            cur->seq = s;
-        }
-        memcpy(cur->seq + cur->n, line, (size_t)got); cur->n += (size_t)got; cur->seq[cur->n] = '\0';
-    }
-    free(line);
-    fclose(fh);
-    return 0;
-}
-
-static void free_recs(struct fa_rec *recs, size_t n) {
-    for (size_t i = 0; i < n; i++) { free(recs[i].name); free(recs[i].seq); }
-    free(recs);
-}
+#include "scrappie_cli.h"
 
 static int squiggle_model_ok(const char *name) {      /* scrappie_stdlib.h: get_squiggle_model */
     return !strcmp(name, "squiggle_r94") || !strcmp(name, "squiggle_r94_rna") || !strcmp(name, "squiggle_r10");
-}
-
-/* engine + model as the options name them; NULL with the reason on stderr */
-static scrappie_hip_engine *open_model(int device, const char *model, const char *model_file) {
-    char *mpath = NULL;
-    if (model_file) mpath = strdup(model_file);
-    else if (getenv("SCRAPPIE_MODEL_DIR")) { if (asprintf(&mpath, "%s/%s.scrm", getenv("SCRAPPIE_MODEL_DIR"), model) < 0) mpath = NULL; }
-    if (!mpath) { fprintf(stderr, "scrappie: no weights for model %s: give --model-file or set SCRAPPIE_MODEL_DIR\n", model); return NULL; }
-    scrappie_hip_engine *e = scrappie_hip_engine_create(device);
-    if (!e) { fprintf(stderr, "scrappie: %s\n", scrappie_hip_last_error()); free(mpath); return NULL; }
-    const int h = scrappie_hip_load_model(e, model, mpath);
-    free(mpath);
-    if (h < 0) { fprintf(stderr, "scrappie: %s\n", scrappie_hip_last_error()); scrappie_hip_engine_destroy(e); return NULL; }
-    return e;
 }
 
 static void squiggle_usage(FILE *fh) {
@@ -103,7 +43,7 @@ int main_squiggle(int argc, char **argv) {
     /* defaults: scrappie_squiggle.c:47-54 */
     const char *model = "squiggle_r94", *model_file = NULL;
     FILE *out = stdout;
-    int limit = 0, rescale = 1, device = 0, c;
+    int limit = 0, rescale = 1, device = 0, h, c;
     optind = 1;
     while ((c = getopt_long(argc, argv, "m:l:o:p:", lo, NULL)) != -1) {
         switch (c) {
@@ -115,28 +55,27 @@ int main_squiggle(int argc, char **argv) {
             limit = atoi(optarg);
             if (limit < 0) { fprintf(stderr, "scrappie: --limit wants a count\n"); return EXIT_FAILURE; }
             break;
-        case 'o':
-            out = fopen(optarg, "w");
-            if (!out) { fprintf(stderr, "scrappie: Failed to open \"%s\" for output.\n", optarg); return EXIT_FAILURE; }
-            break;
+        case 'o': if (!(out = cli_open_output(optarg))) return EXIT_FAILURE; break;
         case 'p': break;                 /* accepted; the reference's squiggle never prints it */
         case O_RESCALE: rescale = 1; break;
         case O_NORESCALE: rescale = 0; break;
-        case O_LIC: puts("Mozilla Public License 2.0 applies to the reference interface this build follows."); exit(EXIT_SUCCESS);
+        case O_LIC: cli_licence(); break;
         case O_MFILE: model_file = optarg; break;
         case O_DEV: device = atoi(optarg); break;
         default: squiggle_usage(stderr); return EXIT_FAILURE;
         }
     }
     if (argc - optind <= 0) { squiggle_usage(stderr); return EXIT_FAILURE; }
-    scrappie_hip_engine *e = open_model(device, model, model_file);
+    char *mpath = cli_model_path(model, model_file);      /* (the weights first, then the engine) */
+    scrappie_hip_engine *e = mpath ? cli_open_model(device, model, mpath, &h) : NULL;
+    free(mpath);
     if (!e) return EXIT_FAILURE;
 
-    struct fa_rec *recs = NULL;
+    struct cli_fasta *recs = NULL;
     size_t nrec = 0;
     for (int fn = optind; fn < argc; fn++) {
         if (limit > 0 && nrec >= (size_t)limit) break;
-        if (read_fasta(argv[fn], &recs, &nrec, (size_t)limit)) fprintf(stderr, "scrappie: Failed to open \"%s\" for input.\n\n", argv[fn]);
+        if (cli_read_fasta(argv[fn], &recs, &nrec, (size_t)limit)) fprintf(stderr, "scrappie: Failed to open \"%s\" for input.\n\n", argv[fn]);
     }
     int rc = EXIT_SUCCESS;
     int **codes = calloc(nrec ? nrec : 1, sizeof *codes);
@@ -163,7 +102,7 @@ int main_squiggle(int argc, char **argv) {
     }
     for (size_t i = 0; i < nrec; i++) { free(codes[i]); free_scrappie_matrix(sq[i]); }
     free(codes); free(lens); free(sq);
-    free_recs(recs, nrec);
+    cli_free_fasta(recs, nrec);
     if (out != stdout) fclose(out);
     scrappie_hip_engine_destroy(e);
     return rc;
@@ -199,9 +138,9 @@ int main_mappy(int argc, char **argv) {
     scrappie_hip_squiggle_params p = scrappie_hip_default_squiggle_params();
     const char *model = "squiggle_r94", *model_file = NULL;
     FILE *out = stdout;
-    int trim_start = 200, trim_end = 10, varseg_chunk = 100, device = 0, c;
+    int trim_start = 200, trim_end = 10, varseg_chunk = 100, device = 0, h, c;
     float varseg_thresh = 0.0f;
-    char *colon;
+    double pct;
     optind = 1;
     while ((c = getopt_long(argc, argv, "b:k:l:m:o:p:r:s:t:", lo, NULL)) != -1) {
         switch (c) {
@@ -216,27 +155,18 @@ int main_mappy(int argc, char **argv) {
         case 'k': p.skip_pen = (float)atof(optarg); break;
         case 'l': p.local_pen = (float)atof(optarg); break;
         case 'm': p.minscore = (float)atof(optarg); break;
-        case 'o':
-            out = fopen(optarg, "w");
-            if (!out) { fprintf(stderr, "scrappie: Failed to open \"%s\" for output.\n", optarg); return EXIT_FAILURE; }
-            break;
+        case 'o': if (!(out = cli_open_output(optarg))) return EXIT_FAILURE; break;
         case 'p': break;                 /* accepted; the reference's mappy never prints it */
         case 'r':
             p.rate = (float)atof(optarg);
             if (!(p.rate > 0.0f)) { fprintf(stderr, "scrappie: Rate must be positive, got %f\n", p.rate); return EXIT_FAILURE; }
             break;
         case 's':
-            colon = strchr(optarg, ':');
-            if (!colon) { fprintf(stderr, "scrappie: --segmentation should be of form chunk:percentile\n"); return EXIT_FAILURE; }
-            varseg_chunk = atoi(optarg); varseg_thresh = (float)(atof(colon + 1) / 100.0);
+            varseg_thresh = cli_parse_segmentation(optarg, &varseg_chunk, &pct) ? -1.0f : (float)(pct / 100.0);       /* (no colon: refused like a percentile out of range) */
             if (varseg_chunk < 0 || !(varseg_thresh > 0.0f && varseg_thresh < 1.0f)) { fprintf(stderr, "scrappie: --segmentation should be of form chunk:percentile\n"); return EXIT_FAILURE; }
             break;
-        case 't':
-            colon = strchr(optarg, ':');
-            trim_start = atoi(optarg); trim_end = colon ? atoi(colon + 1) : trim_start;
-            if (trim_start < 0 || trim_end < 0) { fprintf(stderr, "scrappie: --trim wants start:end\n"); return EXIT_FAILURE; }
-            break;
-        case O_LIC: puts("Mozilla Public License 2.0 applies to the reference interface this build follows."); exit(EXIT_SUCCESS);
+        case 't': if (cli_parse_trim(optarg, &trim_start, &trim_end)) { fprintf(stderr, "scrappie: --trim wants start:end\n"); return EXIT_FAILURE; } break;
+        case O_LIC: cli_licence(); break;
         case O_MFILE: model_file = optarg; break;
         case O_DEV: device = atoi(optarg); break;
         default: mappy_usage(stderr); return EXIT_FAILURE;
@@ -245,25 +175,25 @@ int main_mappy(int argc, char **argv) {
     if (argc - optind <= 0) { mappy_usage(stderr); return EXIT_FAILURE; }
     if (argc - optind < 2) { fprintf(stderr, "scrappie: fast5 file is a required argument\n"); return EXIT_FAILURE; }      /* scrappie_mappy.c:152 */
     const char *fasta = argv[optind], *fast5 = argv[optind + 1];
-    scrappie_hip_engine *e = open_model(device, model, model_file);
+    char *mpath = cli_model_path(model, model_file);      /* (the weights first, then the engine) */
+    scrappie_hip_engine *e = mpath ? cli_open_model(device, model, mpath, &h) : NULL;
+    free(mpath);
     if (!e) return EXIT_FAILURE;
 
     int rc = EXIT_FAILURE;
-    struct fa_rec *recs = NULL;
+    struct cli_fasta *recs = NULL;
     size_t nrec = 0;
     raw_table rt = {0};
     int *codes = NULL;
     scrappie_matrix sq = NULL;
     scrappie_hip_squiggle_result res = {0};
-    if (read_fasta(fasta, &recs, &nrec, 1) || nrec == 0 || !recs[0].seq || recs[0].n == 0) {
+    if (cli_read_fasta(fasta, &recs, &nrec, 1) || nrec == 0 || !recs[0].seq || recs[0].n == 0) {
         fprintf(stderr, "scrappie: Failed to open \"%s\" for input.\n\n", fasta);
         goto done;
     }
     /* scrappie_mappy.c:197-204 */
-    rt = scrappie_hip_read_raw(fast5, true);
-    rt = trim_and_segment_raw(rt, (size_t)trim_start, (size_t)trim_end, (size_t)varseg_chunk, varseg_thresh);
+    rt = cli_load_read(fast5, trim_start, trim_end, varseg_chunk, varseg_thresh, 1);
     if (!rt.raw) { fprintf(stderr, "scrappie: Failed to open \"%s\" for input and trim signal.\n\n", fast5); goto done; }
-    medmad_normalise_array(rt.raw + rt.start, rt.end - rt.start);
 
     rc = EXIT_SUCCESS;                   /* from here on the reference prints what it has and succeeds */
     codes = encode_bases_to_integers(recs[0].seq, recs[0].n, 1);
@@ -295,7 +225,7 @@ done:
     free_scrappie_matrix(sq);
     free(codes);
     free(rt.raw); free(rt.uuid);
-    free_recs(recs, nrec);
+    cli_free_fasta(recs, nrec);
     if (out != stdout) fclose(out);
     scrappie_hip_engine_destroy(e);
     return rc;

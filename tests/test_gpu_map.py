@@ -367,6 +367,45 @@ def test_seqmappy_bundled_reads(eng, ref, tmp_path):
     assert two.stdout == want[names[1]][2] + want[names[0]][2]
 
 
+def test_cli_segmentation_chunk_zero_is_the_fixed_trims(eng, tmp_path):
+    """`--segmentation 0:50` in `scrappie seqmappy` and `scrappie mappy` leaves the variance-based segmentation out, as it does in
+    `scrappie events`: the read's window is [200, n - 10), and the output is that of the same window, normalised by the Python
+    surface, through Engine.map_to_sequence / Engine.mappy"""
+    name = list(FA_SHA256)[0]
+    fa, f5 = os.path.join(READS, name + ".fa"), os.path.join(READS, "read_ch228_file118.i16")
+    seq = _fasta(name)
+    raw = sa.read_raw(f5)[0]
+    n = len(raw)
+    rt = sa.RawTable(raw, 200, n - 10).scale()
+    x = rt._data                                           # the window normalised in place, the trims as they were read
+    mfile = str(tmp_path / "rgrgr_r94.scrm")
+    model.save_model(model.synthetic_model("rgrgr_r94", seed=1), mfile)
+    (score, path), = eng.map_to_sequence([rt], [seq], viterbi=True, path=True, stay_pen=0.0, skip_pen=0.0, local_pen=4.0, min_prob=1e-5)
+    want = "# %s to %s -- score %f over %d blocks (%f per block)\nblock\tpos\n" % (f5, fa, -score, len(path), np.float32(-score) / np.float32(len(path)))
+    want += "".join("%d\t%d\n" % (i, p) for i, p in enumerate(path))
+    r = subprocess.run([CLI, "seqmappy", "--model-file", mfile, "--segmentation", "0:50", fa, f5], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    assert r.stdout == want
+
+    sfile = str(tmp_path / "squiggle_r94.scrm")
+    model.save_model(model.synthetic_model("squiggle_r94", seed=11), sfile)
+    eng.load_model("squiggle_r94", sfile)
+    (score, path), = eng.mappy([rt], [seq])
+    sq = eng.predict_squiggle([seq], model="squiggle_r94", rescale=False)[0]
+    libm = C.CDLL("libm.so.6")
+    libm.expf.restype, libm.expf.argtypes = C.c_float, [C.c_float]
+    want = ["# %s to %s  (score = %f)" % (f5, fa, score), "idx\tsignal\tpos\tbase\tcurrent\tsd\tdwell"]
+    assert len(path) == n
+    for i, p in enumerate(path):
+        if p >= 0:
+            want.append("%d\t%3.6f\t%d\t%s\t%3.6f\t%3.6f\t%3.6f" % (i, x[i], p, seq[p], sq[p, 0], libm.expf(sq[p, 1]), libm.expf(-sq[p, 2])))
+        else:
+            want.append("%d\t%3.6f\t%d\tN\tnan\tnan\tnan" % (i, x[i] if 200 <= i < n - 10 else float("nan"), p))
+    r = subprocess.run([CLI, "mappy", "--model-file", sfile, "--segmentation", "0:50", fa, f5], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    assert r.stdout.splitlines() == want
+
+
 def test_per_read_threads():
     cases = [c for c in map_cases(big=False) if c[1].shape[0] == 800][:16]
     L = sa.lib()

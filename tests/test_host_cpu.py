@@ -518,7 +518,7 @@ def test_cli_pipeline_under_thread_sanitizer(tmp_path):
     csrc = os.path.join(ROOT, "scrappie_amd", "csrc")
     exe = str(tmp_path / "scrappie_tsan")
     b = subprocess.run(["gcc", "-std=gnu11", "-O1", "-g", "-fsanitize=thread", "-pthread", "-Wno-unknown-pragmas", "-I" + os.path.join(ROOT, "include"), "-I" + csrc,
-                        os.path.join(csrc, "scrappie_raw.c"), os.path.join(ROOT, "tests", "cli_pipe_stub.c"), os.path.join(csrc, "sh_host.c"),
+                        os.path.join(csrc, "scrappie_raw.c"), os.path.join(csrc, "scrappie_cli.c"), os.path.join(ROOT, "tests", "cli_pipe_stub.c"), os.path.join(csrc, "sh_host.c"),
                         os.path.join(csrc, "sh_fast5.c"), os.path.join(csrc, "sh_h5mini.c"), os.path.join(csrc, "sh_inflate.c"), "-o", exe, "-lm", "-ldl"], capture_output=True, text=True, timeout=300)
     if b.returncode != 0 and "tsan" in (b.stderr or "").lower():
         pytest.skip("no ThreadSanitizer runtime in this toolchain")
