@@ -212,6 +212,15 @@ float squiggle_match_viterbi(const raw_table signal, float rate, const_scrappie_
                              float skip_pen, float minscore, int32_t *path_padded);
 float squiggle_match_forward(const raw_table signal, float rate, const_scrappie_matrix params, float prob_back, float local_pen,
                              float skip_pen, float minscore);
+/* The same inside a band (not in the reference; sh_squig_band.h): low[t], one int32 per sample of the window [start, end), is the
+ * first position sample t may map to and width how many: positions [low[t], min(low[t] + width, npos)).  After each sample every
+ * position and back state outside its band holds -1e30, nothing else changes: a band of low = 0 and width = npos, and any band
+ * that contains the unbanded Viterbi path, give the unbanded score and path bit for bit.  low NULL and width 0: unbanded.  A band
+ * that is not valid (0 <= low[t] <= npos - 1, low non-decreasing, width >= 1) or admits no path: NAN and an error text. */
+float squiggle_match_viterbi_banded(const raw_table signal, float rate, const_scrappie_matrix params, float prob_back, float local_pen,
+                                    float skip_pen, float minscore, const int32_t *low, size_t width, int32_t *path_padded);
+float squiggle_match_forward_banded(const raw_table signal, float rate, const_scrappie_matrix params, float prob_back, float local_pen,
+                                    float skip_pen, float minscore, const int32_t *low, size_t width);
 
 /* Prediction of a squiggle from a base sequence (src/networks.c:397, :454, :511; python/pyscrap.h:29-31).  Same signatures:
  * sequence holds n bases coded 0..3 (encode_bases_to_integers(seq, n, 1)); the result has n columns of (mean, log sd, dwell
@@ -492,6 +501,31 @@ size_t scrappie_hip_squiggle_lds_max_pos(void);
  * k_squig 2 (2 npos + 1). */
 long long scrappie_hip_map_plan_scratch(const size_t *seqlen, const size_t *nblock, size_t n, long long *off);
 long long scrappie_hip_squiggle_plan_scratch(const size_t *npos, const size_t *nsample, size_t n, long long *off);
+/* Banded squiggle matching (sh_squig_band.h).  bands[i] is read i's band as squiggle_match_viterbi_banded takes it (low: one
+ * int32 per sample of the window; it may differ from read to read), low NULL and width 0 for a read without one; bands NULL: no
+ * read has one, which is scrappie_hip_squiggle_match_batch.  Banded reads go through k_squig_band in launches of their own, the
+ * others through k_squig as ever.  A banded read costs a launch samples x width / 2 bytes of traceback and, beyond
+ * scrappie_hip_squiggle_band_lds_max_width(), 2 (2 width + 1) floats of scratch: one that is refused for its size without a band
+ * may fit with one.  An invalid band, or one that admits no path (score below -1e30 / 2): NAN, no path and an error text for that
+ * read, the others untouched.  scrappie_hip_squiggle_timing covers these calls too. */
+typedef struct { const int32_t *low; size_t width; } scrappie_hip_squiggle_band;
+int scrappie_hip_squiggle_match_banded_batch(scrappie_hip_engine *e, const raw_table *reads, const scrappie_hip_squiggle_target *targets,
+                                             const scrappie_hip_squiggle_band *bands, size_t n, const scrappie_hip_squiggle_params *p, int viterbi,
+                                             int want_path, scrappie_hip_squiggle_result *out);
+/* the diagonal band of half-width h positions: returns width = min(npos, 2 h + 1) and fills low[t] =
+ * clamp(floor(t npos / nsample) - h, 0, npos - width), t < nsample (64-bit arithmetic); low NULL: the width alone */
+size_t scrappie_hip_squiggle_diagonal_band(size_t nsample, size_t npos, size_t halfwidth, int32_t *low);
+/* the widest band whose score rows k_squig_band keeps in LDS; wider bands keep them in device scratch */
+size_t scrappie_hip_squiggle_band_lds_max_width(void);
+/* The banded planner's arithmetic on the host, no device (for the tests): banded reads laid out in this order in one launch;
+ * scr_off[i] the float offset of read i's rows (2 (2 width + 1) floats; -1: in LDS), tb_off[i] its first traceback word
+ * (nsample x 8 ceil(width / 64) words, then nsample int32 of END's source; -1 without want_path), scr_off[n] / tb_off[n] the
+ * floats / words allocated for all (arrays of n + 1, either may be NULL); width[i] > npos[i] counts as npos[i].  Returns the
+ * device bytes the launch is charged. */
+long long scrappie_hip_squiggle_band_plan(const size_t *npos, const size_t *width, const size_t *nsample, size_t n, int want_path,
+                                          long long *scr_off, long long *tb_off);
+/* launches of each k_squig_band form in this process: index (viterbi ? 2 : 0) | (scratch ? 1 : 0) */
+void scrappie_hip_squiggle_band_form_counts(uint64_t forms[4]);
 /* Squiggle prediction, batched (sh_eng_sqnet.inc): seqs[i] holds n[i] bases coded 0..3; out[i] becomes a matrix as
  * squiggle_r94 returns it (free_scrappie_matrix), predicted with `model`, a squiggle model loaded on e under that name.
  * The accepted sequences are laid end to end: one upload, one k_sqnet launch over all their tiles, one download; the call

@@ -70,6 +70,10 @@ class _SquigParams(C.Structure):
                 ("minscore", C.c_float)]
 
 
+class _SquigBand(C.Structure):
+    _fields_ = [("low", C.POINTER(C.c_int32)), ("width", C.c_size_t)]
+
+
 class _SquigResult(C.Structure):
     _fields_ = [("score", C.c_float), ("n", C.c_size_t), ("path", C.POINTER(C.c_int32))]
 
@@ -273,6 +277,22 @@ def lib():
     L.scrappie_hip_squiggle_match_batch.argtypes = [C.c_void_p, C.POINTER(_RawTable), C.POINTER(_SquigTarget), C.c_size_t,
                                                     C.POINTER(_SquigParams), C.c_int, C.c_int, C.POINTER(_SquigResult)]
     L.scrappie_hip_free_squiggle_results.argtypes = [C.POINTER(_SquigResult), C.c_size_t]
+    i32p = C.POINTER(C.c_int32)
+    L.squiggle_match_viterbi_banded.restype = C.c_float
+    L.squiggle_match_viterbi_banded.argtypes = [_RawTable, C.c_float, PM, C.c_float, C.c_float, C.c_float, C.c_float, i32p, C.c_size_t, i32p]
+    L.squiggle_match_forward_banded.restype = C.c_float
+    L.squiggle_match_forward_banded.argtypes = [_RawTable, C.c_float, PM, C.c_float, C.c_float, C.c_float, C.c_float, i32p, C.c_size_t]
+    L.scrappie_hip_squiggle_match_banded_batch.argtypes = [C.c_void_p, C.POINTER(_RawTable), C.POINTER(_SquigTarget), C.POINTER(_SquigBand),
+                                                           C.c_size_t, C.POINTER(_SquigParams), C.c_int, C.c_int, C.POINTER(_SquigResult)]
+    L.scrappie_hip_squiggle_diagonal_band.restype = C.c_size_t
+    L.scrappie_hip_squiggle_diagonal_band.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t, i32p]
+    L.scrappie_hip_squiggle_band_lds_max_width.restype = C.c_size_t
+    L.scrappie_hip_squiggle_band_lds_max_width.argtypes = []
+    L.scrappie_hip_squiggle_band_plan.restype = C.c_longlong
+    L.scrappie_hip_squiggle_band_plan.argtypes = [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_size_t, C.c_int,
+                                                  C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    L.scrappie_hip_squiggle_band_form_counts.restype = None
+    L.scrappie_hip_squiggle_band_form_counts.argtypes = [C.POINTER(C.c_uint64)]
     L.scrappie_hip_squiggle_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     L.scrappie_hip_squiggle_lds_max_pos.restype = C.c_size_t
     L.scrappie_hip_map_lds_max_seq.restype = C.c_size_t
@@ -372,6 +392,54 @@ def launch_form_counts():
     lib().scrappie_hip_launch_form_counts(m, q)
     return dict(map={(bool(k & 8), bool(k & 4), bool(k & 2), bool(k & 1)): int(m[k]) for k in range(16)},
                 squig={(bool(k & 2), bool(k & 1)): int(q[k]) for k in range(4)})
+
+
+def squiggle_band_form_counts():
+    """Launches of each k_squig_band form in this process so far (scrappie_hip_squiggle_band_form_counts):
+    {(viterbi, scratch): n}."""
+    q = (C.c_uint64 * 4)()
+    lib().scrappie_hip_squiggle_band_form_counts(q)
+    return {(bool(k & 2), bool(k & 1)): int(q[k]) for k in range(4)}
+
+
+def plan_squiggle_band(npos, width, nsample, path=True):
+    """The banded planner's layout of one launch of banded reads in this order (host arithmetic, no device;
+    scrappie_hip_squiggle_band_plan): dict(scr_off, tb_off: per read, -1 for rows in LDS / no traceback; scr_floats,
+    tb_words: what the launch allocates; bytes: what the launch is charged)."""
+    a, w, b = (np.ascontiguousarray(v, dtype=np.uintp) for v in (npos, width, nsample))
+    if not len(a) == len(w) == len(b):
+        raise ValueError("one width and one sample count per read")
+    scr, tb = np.zeros(len(a) + 1, dtype=np.longlong), np.zeros(len(a) + 1, dtype=np.longlong)
+    sp, lp = C.POINTER(C.c_size_t), C.POINTER(C.c_longlong)
+    total = lib().scrappie_hip_squiggle_band_plan(a.ctypes.data_as(sp), w.ctypes.data_as(sp), b.ctypes.data_as(sp), len(a), 1 if path else 0,
+                                                  scr.ctypes.data_as(lp), tb.ctypes.data_as(lp))
+    return dict(scr_off=scr[:-1], tb_off=tb[:-1], scr_floats=int(scr[-1]), tb_words=int(tb[-1]), bytes=int(total))
+
+
+def squiggle_diagonal_band(nsample, npos, halfwidth):
+    """(low, width) of the diagonal band of half-width `halfwidth` positions for `nsample` samples against `npos` positions
+    (scrappie_hip_squiggle_diagonal_band): width = min(npos, 2 h + 1), low[t] = clamp(t * npos // nsample - h, 0, npos - width)."""
+    if nsample < 0 or npos < 0 or halfwidth < 0:
+        raise ValueError("nsample, npos and halfwidth should not be negative")
+    low = np.zeros(nsample, dtype=np.int32)
+    width = lib().scrappie_hip_squiggle_diagonal_band(nsample, npos, halfwidth, low.ctypes.data_as(C.POINTER(C.c_int32)))
+    return low, int(width)
+
+
+def _squiggle_band(band, nsample, npos):
+    """a `band=` argument for one read of `nsample` mapped samples and `npos` positions as (low int32 array or None, width):
+    None, an int (diagonal half-width) or a (low, width) pair as given"""
+    if band is None:
+        return None, 0
+    if isinstance(band, (int, np.integer)):
+        return squiggle_diagonal_band(nsample, npos, int(band))
+    low, width = band
+    low = np.ascontiguousarray(low, dtype=np.int32)
+    if low.ndim != 1 or len(low) != nsample:
+        raise ValueError("a band's low should have one entry per mapped sample (%d)" % nsample)
+    if int(width) < 0:
+        raise ValueError("a band's width should not be negative")
+    return low, int(width)
 
 
 def _take_string(ptr):
@@ -842,35 +910,50 @@ def _squiggle_matrix(squiggle, model=None):
 
 
 def squiggle_match(rt, squiggle, rate=1.0, back_prob=0.0, local_pen=2.0, skip_pen=5000.0, min_score=5.0, viterbi=True,
-                   path=True):
+                   path=True, band=None):
     """squiggle_match_viterbi / squiggle_match_forward (decode.c:1035, :1262) on the GPU: the `RawTable` rt as it is (no
     trimming), mapped over [rt.start, rt.end), against a predicted squiggle.  Returns (score, path or None); the path has
-    rt's full length, -1 outside the window and in the START / END states."""
+    rt's full length, -1 outside the window and in the START / END states.  `band`: None, an int (the half-width in
+    positions of a diagonal band, `squiggle_diagonal_band`) or a (low, width) pair -- low[t] the first position sample t of
+    the window may map to, width how many (squiggle_match_viterbi_banded / _forward_banded)."""
     if path and not viterbi:
         raise ValueError('Cannot calulate path with `viterbi==False`.')
     if not isinstance(rt, RawTable):
         raise TypeError('`rt` should be a RawTable.')
     sq = _squiggle_matrix(squiggle)
+    i32p = C.POINTER(C.c_int32)
+    if band is not None:
+        low, width = _squiggle_band(band, max(int(rt._rt.end) - int(rt._rt.start), 0), int(sq.data().contents.nc))
+        lowp = low.ctypes.data_as(i32p) if low is not None else None
     if viterbi:
         path_data = np.zeros(rt._rt.n, dtype=np.int32)
-        score = lib().squiggle_match_viterbi(rt.data(), rate, sq.data(), back_prob, local_pen, skip_pen, min_score,
-                                             path_data.ctypes.data_as(C.POINTER(C.c_int32)))
+        if band is None:
+            score = lib().squiggle_match_viterbi(rt.data(), rate, sq.data(), back_prob, local_pen, skip_pen, min_score,
+                                                 path_data.ctypes.data_as(i32p))
+        else:
+            score = lib().squiggle_match_viterbi_banded(rt.data(), rate, sq.data(), back_prob, local_pen, skip_pen, min_score,
+                                                        lowp, width, path_data.ctypes.data_as(i32p))
     else:
         path_data = None
-        score = lib().squiggle_match_forward(rt.data(), rate, sq.data(), back_prob, local_pen, skip_pen, min_score)
+        if band is None:
+            score = lib().squiggle_match_forward(rt.data(), rate, sq.data(), back_prob, local_pen, skip_pen, min_score)
+        else:
+            score = lib().squiggle_match_forward_banded(rt.data(), rate, sq.data(), back_prob, local_pen, skip_pen, min_score, lowp, width)
     if np.isnan(score):
         raise RuntimeError('An unknown error occurred during alignment: ' + last_error())
     return score, (path_data if path else None)
 
 
-def map_signal_to_squiggle(data, squiggle, rate=1.0, back_prob=0.0, local_pen=2.0, skip_pen=5000.0, min_score=5.0, model=None):
+def map_signal_to_squiggle(data, squiggle, rate=1.0, back_prob=0.0, local_pen=2.0, skip_pen=5000.0, min_score=5.0, model=None,
+                           band=None):
     """python/scrappy/__init__.py:462-489: `squiggle` is a base sequence, predicted with the registered squiggle model
     `model`, or the predicted squiggle itself (a `ScrappyMatrix` or an (npos, 3) array); then trim -> scale ->
-    squiggle_match_viterbi.  Returns (score, path over the whole of `data`)."""
+    squiggle_match_viterbi.  Returns (score, path over the whole of `data`).  `band`: as `squiggle_match` takes it, over
+    the trimmed window."""
     sq = _squiggle_matrix(squiggle, model)
     raw = RawTable(data)
     raw.trim().scale()
-    return squiggle_match(raw, sq, rate, back_prob, local_pen, skip_pen, min_score, viterbi=True, path=True)
+    return squiggle_match(raw, sq, rate, back_prob, local_pen, skip_pen, min_score, viterbi=True, path=True, band=band)
 
 
 def plan_tail(lengths, stride, max_long_blocks=0):
@@ -1386,10 +1469,12 @@ class Engine(object):
         return self._timing(lib().scrappie_hip_map_timing, ('network_ms', 'map_ms', 'walk_ms'))
 
     def match_squiggle(self, signals, squiggles, viterbi=True, path=False, rate=1.0, back_prob=0.0, local_pen=2.0,
-                       skip_pen=5000.0, min_score=5.0):
+                       skip_pen=5000.0, min_score=5.0, band=None):
         """Each signal (trimmed, normalised float32 array, or a `RawTable` with its window) against its predicted squiggle
         (an (npos, 3) array of mean, log sd, dwell logit), batched (scrappie_hip_squiggle_match_batch).  Returns
-        [(score, path or None)] in input order; score NaN where a read cannot be mapped."""
+        [(score, path or None)] in input order; score NaN where a read cannot be mapped.  `band`: None, an int (diagonal
+        half-width in positions) or a (low, width) pair for all reads, or a list with one of these per read
+        (scrappie_hip_squiggle_match_banded_batch); score NaN too where a band is invalid or admits no path."""
         n = len(signals)
         if len(squiggles) != n:
             raise ValueError("one squiggle per signal")
@@ -1407,7 +1492,19 @@ class Engine(object):
             tgs[i] = _SquigTarget(sq.ctypes.data_as(C.POINTER(C.c_float)), sq.shape[0], sq.shape[1])
         p = _SquigParams(rate, back_prob, local_pen, skip_pen, min_score)
         out = (_SquigResult * n)()
-        if lib().scrappie_hip_squiggle_match_batch(self._h, rts, tgs, n, C.byref(p), 1 if viterbi else 0, 1 if path else 0, out) != 0:
+        if band is None:
+            rc = lib().scrappie_hip_squiggle_match_batch(self._h, rts, tgs, n, C.byref(p), 1 if viterbi else 0, 1 if path else 0, out)
+        else:
+            if isinstance(band, list) and len(band) != n:
+                raise ValueError("one band per signal")
+            bds = (_SquigBand * max(n, 1))()
+            for i in range(n):
+                low, width = _squiggle_band(band[i] if isinstance(band, list) else band,
+                                            max(int(rts[i].end) - int(rts[i].start), 0), int(tgs[i].npos))
+                keep.append(low)
+                bds[i] = _SquigBand(low.ctypes.data_as(C.POINTER(C.c_int32)) if low is not None else None, width)
+            rc = lib().scrappie_hip_squiggle_match_banded_batch(self._h, rts, tgs, bds, n, C.byref(p), 1 if viterbi else 0, 1 if path else 0, out)
+        if rc != 0:
             raise RuntimeError("squiggle_match_batch: " + last_error())
         res = _scores_and_paths(out, n, 'n')
         lib().scrappie_hip_free_squiggle_results(out, n)
@@ -1436,16 +1533,21 @@ class Engine(object):
         return self._timing(lib().scrappie_hip_sqnet_timing, ('upload_ms', 'net_ms', 'download_ms'))
 
     def mappy(self, signals, sequences, model='squiggle_r94', rate=1.0, back_prob=0.0, local_pen=2.0, skip_pen=5000.0,
-              min_score=5.0):
+              min_score=5.0, band=None):
         """Each signal (trimmed, normalised float32 array, or a `RawTable` with its window) against the squiggle predicted
         for its base sequence: one batched prediction, then one batched Viterbi match of the downloaded squiggles.
-        Returns [(score, path)] in input order; (nan, None) where a sequence or a read is refused."""
+        Returns [(score, path)] in input order; (nan, None) where a sequence or a read is refused.  `band`: as
+        `match_squiggle` takes it (`scrappie mappy --band N` is band=N)."""
         if len(signals) != len(sequences):
             raise ValueError("one sequence per signal")
         sqs = self.predict_squiggle(sequences, model=model, rescale=False)
         keep = [i for i, sq in enumerate(sqs) if sq is not None]
+        if isinstance(band, list):
+            if len(band) != len(signals):
+                raise ValueError("one band per signal")
+            band = [band[i] for i in keep]
         got = self.match_squiggle([signals[i] for i in keep], [sqs[i] for i in keep], viterbi=True, path=True, rate=rate,
-                                  back_prob=back_prob, local_pen=local_pen, skip_pen=skip_pen, min_score=min_score)
+                                  back_prob=back_prob, local_pen=local_pen, skip_pen=skip_pen, min_score=min_score, band=band)
         res = [(float("nan"), None)] * len(signals)
         for i, r in zip(keep, got):
             res[i] = r

@@ -76,6 +76,7 @@
 #include "sh_coalesce.h"
 #include "sh_map.h"
 #include "sh_squig.h"
+#include "sh_squig_band.h"
 #include "sh_sqnet.h"
 #include "sh_events.h"
 

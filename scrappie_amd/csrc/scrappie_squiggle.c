@@ -5,7 +5,8 @@
  * every FASTA file, all of them in ONE scrappie_hip_squiggle_predict_batch call, written in input order; a record the
  * network refuses (a base outside ACGT, fewer bases than the window needs) is skipped, as the reference skips a NULL
  * squiggle.  mappy: the first record's squiggle, then squiggle_match_viterbi of the read against it.  Added: --model-file /
- * --device as `scrappie raw` takes them (the weights are data: default $SCRAPPIE_MODEL_DIR/<model>.scrm).
+ * --device as `scrappie raw` takes them (the weights are data: default $SCRAPPIE_MODEL_DIR/<model>.scrm); mappy --band N, the
+ * match inside the diagonal band of half-width N positions (scrappie_hip_squiggle_diagonal_band).
  */
 #define _GNU_SOURCE
 #include <getopt.h>
@@ -124,13 +125,14 @@ static void mappy_usage(FILE *fh) {
           "  -t, --trim=start:end       Number of samples to trim, as start:end\n"
           "      --licence, --license   Print licensing information\n"
           "      --model-file=path      Weight container (.scrm); default $SCRAPPIE_MODEL_DIR/<model>.scrm\n"
-          "      --device=N             GPU to run on (default 0)\n", fh);
+          "      --device=N             GPU to run on (default 0)\n"
+          "      --band=N               Map inside the diagonal band of half-width N positions (default: no band)\n", fh);
 }
 
 int main_mappy(int argc, char **argv) {
-    enum { O_MODEL = 256, O_LIC, O_MFILE, O_DEV };
+    enum { O_MODEL = 256, O_LIC, O_MFILE, O_DEV, O_BAND };
     static const struct option lo[] = {
-        {"model", 1, 0, O_MODEL}, {"backprob", 1, 0, 'b'}, {"skippen", 1, 0, 'k'}, {"localpen", 1, 0, 'l'}, {"minscore", 1, 0, 'm'},
+        {"band", 1, 0, O_BAND}, {"model", 1, 0, O_MODEL}, {"backprob", 1, 0, 'b'}, {"skippen", 1, 0, 'k'}, {"localpen", 1, 0, 'l'}, {"minscore", 1, 0, 'm'},
         {"output", 1, 0, 'o'}, {"prefix", 1, 0, 'p'}, {"rate", 1, 0, 'r'}, {"segmentation", 1, 0, 's'}, {"trim", 1, 0, 't'},
         {"licence", 0, 0, O_LIC}, {"license", 0, 0, O_LIC}, {"model-file", 1, 0, O_MFILE}, {"device", 1, 0, O_DEV}, {"help", 0, 0, '?'},
         {0, 0, 0, 0}};
@@ -139,6 +141,7 @@ int main_mappy(int argc, char **argv) {
     const char *model = "squiggle_r94", *model_file = NULL;
     FILE *out = stdout;
     int trim_start = 200, trim_end = 10, varseg_chunk = 100, device = 0, h, c;
+    long band = -1;                      /* half-width of the diagonal band in positions; < 0: none */
     float varseg_thresh = 0.0f;
     double pct;
     optind = 1;
@@ -169,6 +172,10 @@ int main_mappy(int argc, char **argv) {
         case O_LIC: cli_licence(); break;
         case O_MFILE: model_file = optarg; break;
         case O_DEV: device = atoi(optarg); break;
+        case O_BAND:
+            band = atol(optarg);
+            if (band < 0) { fprintf(stderr, "scrappie: --band wants a half-width in positions, 0 or more\n"); return EXIT_FAILURE; }
+            break;
         default: mappy_usage(stderr); return EXIT_FAILURE;
         }
     }
@@ -187,6 +194,7 @@ int main_mappy(int argc, char **argv) {
     int *codes = NULL;
     scrappie_matrix sq = NULL;
     scrappie_hip_squiggle_result res = {0};
+    int32_t *low = NULL;
     if (cli_read_fasta(fasta, &recs, &nrec, 1) || nrec == 0 || !recs[0].seq || recs[0].n == 0) {
         fprintf(stderr, "scrappie: Failed to open \"%s\" for input.\n\n", fasta);
         goto done;
@@ -203,7 +211,14 @@ int main_mappy(int argc, char **argv) {
         goto done;
     }
     scrappie_hip_squiggle_target tg = {sq->data.f, sq->nc, sq->stride};
-    if (scrappie_hip_squiggle_match_batch(e, &rt, &tg, 1, &p, 1, 1, &res) != 0 || !res.path) {
+    scrappie_hip_squiggle_band bd = {NULL, 0};
+    if (band >= 0 && rt.end > rt.start) {
+        low = malloc((rt.end - rt.start) * sizeof *low);
+        if (!low) { fprintf(stderr, "scrappie: out of memory\n"); rc = EXIT_FAILURE; goto done; }
+        bd.low = low;
+        bd.width = scrappie_hip_squiggle_diagonal_band(rt.end - rt.start, sq->nc, (size_t)band, low);
+    }
+    if (scrappie_hip_squiggle_match_banded_batch(e, &rt, &tg, &bd, 1, &p, 1, 1, &res) != 0 || !res.path) {
         fprintf(stderr, "scrappie: %s\n", scrappie_hip_last_error());
         rc = EXIT_FAILURE;
         goto done;
@@ -224,6 +239,7 @@ done:
     scrappie_hip_free_squiggle_results(&res, 1);
     free_scrappie_matrix(sq);
     free(codes);
+    free(low);
     free(rt.raw); free(rt.uuid);
     cli_free_fasta(recs, nrec);
     if (out != stdout) fclose(out);
