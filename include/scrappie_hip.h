@@ -451,7 +451,7 @@ int scrappie_hip_collect(scrappie_hip_engine *e, const scrappie_hip_params *p,
 
 void scrappie_hip_free_calls(scrappie_hip_call *calls, size_t n);
 
-/* Block-based mapping, batched (sh_eng_map.inc): the network and S1 of a transducer model (not a CRF model) run as
+/* Block-based mapping, batched (sh_eng_map.inc): the network and S1 of a transducer model (a CRF model: see below) run as
  * for scrappie_hip_posterior, the posterior stays on the device, k_map maps every read to its target and only scores
  * and paths return.  reads[i] is mapped to targets[i]; out[i] belongs to reads[i].  seq holds state codes (as
  * encode_bases_to_integers makes them with the model's k-mer length); poslow / poshigh NULL: unbanded, else one entry
@@ -473,6 +473,45 @@ void scrappie_hip_free_map_results(scrappie_hip_map_result *r, size_t n);
 void scrappie_hip_map_timing(scrappie_hip_engine *e, double out[3]);
 /* states up to which k_map keeps its score rows and the codes in LDS; longer sequences keep the rows in device scratch */
 size_t scrappie_hip_map_lds_max_seq(void);
+
+/* Reads of a flip-flop (CRF) model mapped to base sequences (k_map_crf, sh_map_crf.h; sh_eng_map_crf.inc): decode_crf's recursion
+ * (src/decode.c:836-893) restricted to the paths that spell the sequence.  The reference has no such function; the definition is
+ * decode_crf's own: a path has nblock + 1 entries, its non-stay entries in order are exactly seq (global: all of the read, all of
+ * the sequence, no penalties), float32 as transition + previous, candidates in decode_crf's order (from-state ascending, stay last,
+ * replaced on strict >; a base wins a tie at the end).  Mapping a read to its own call returns decode_crf's score bit for bit, and
+ * its path.  The forward forms sum over the same paths (logsumexpf, util.h:162-164).
+ *
+ * scrappie_hip_map_batch with a CRF model: targets[i].seq holds base codes 0..3 and seqlen bases; poslow / poshigh, when given, hold
+ * nblock + 1 entries -- one per ENTRY of the path -- and cell index p (the bases emitted so far, 0 .. seqlen) of entry t must lie in
+ * [poslow[t], poshigh[t]) (scrappie_hip_map_crf_bounds_sane); out[i].nblock is the read's block count and out[i].path, for every
+ * read of a Viterbi call with want_path, banded or not, has nblock + 1 entries: path[t] = index of the last base emitted through
+ * entry t, -1 while none (entry t is a base exactly where path[t] > path[t - 1]).  stay_pen, skip_pen and local_pen are not used.
+ * A sequence with no admissible path (seqlen > nblock + 1, or a band that excludes them all: a score below -1e30 / 2) gets NAN and
+ * an error text, as every other read that cannot be mapped.  Launch groups are cut by the same cost model (a CRF model's posterior
+ * is its 25 transitions per block), k_map_crf runs on the transitions where k_crf left them, and scrappie_hip_map_timing covers
+ * these calls ([1] k_map_crf, [2] k_map_crf_walk + results).  Transducer models go through exactly what they went through before.
+ *
+ * The per-read symbols run on the process-default engine: trans as nanonet_rnnrf_r94_transitions returns it (25 rows, element
+ * to * 5 + from, states A C G T stay; nc >= 1 blocks), uploaded, one launch.  path: nblock + 1 entries, may be NULL.  low / high:
+ * nblock + 1 entries each.  NAN with scrappie_hip_last_error() on a null argument, a matrix that is not 25 rows with at least one
+ * block, a base code outside 0..3, a sequence longer than the limit of DESIGN.md, an invalid band, or no admissible path. */
+float map_crf_to_sequence_viterbi(const_scrappie_matrix trans, int const *seq, size_t seqlen, int *path);
+float map_crf_to_sequence_forward(const_scrappie_matrix trans, int const *seq, size_t seqlen);
+float map_crf_to_sequence_viterbi_banded(const_scrappie_matrix trans, int const *seq, size_t seqlen, size_t const *low, size_t const *high, int *path);
+float map_crf_to_sequence_forward_banded(const_scrappie_matrix trans, int const *seq, size_t seqlen, size_t const *low, size_t const *high);
+/* Host only.  A band is valid when low[0] == 0, high[nblock] == seqlen + 1, low[t] < high[t] <= seqlen + 1, both are non-decreasing
+ * and low[t] <= high[t - 1] (t = 0 .. nblock): 1, else 0 (quiet). */
+int scrappie_hip_map_crf_bounds_sane(const size_t *low, const size_t *high, size_t nblock, size_t seqlen);
+/* Host only.  The diagonal through (entry 0, cell 0) and (entry nblock, cell seqlen), halfwidth cells to either side, clamped so that
+ * the result is always valid; low and high take nblock + 1 entries each.  0, or -1 on a null or empty argument. */
+int scrappie_hip_map_crf_diagonal_band(size_t nblock, size_t seqlen, size_t halfwidth, size_t *low, size_t *high);
+/* bases up to which k_map_crf keeps its score rows and the codes in LDS; longer sequences keep the rows in device scratch */
+size_t scrappie_hip_map_crf_lds_max_seq(void);
+/* The planner's scratch arithmetic on the host, no device (for the tests): as scrappie_hip_map_plan_scratch; k_map_crf touches
+ * 4 (seqlen + 2) floats from its offset. */
+long long scrappie_hip_map_crf_plan_scratch(const size_t *seqlen, const size_t *nblock, size_t n, long long *off);
+/* launches of each k_map_crf form in this process, all engines together: index (viterbi ? 4 : 0) | (tiled ? 2 : 0) | (scratch ? 1 : 0) */
+void scrappie_hip_map_crf_form_counts(uint64_t forms[8]);
 
 /* Squiggle matching, batched (sh_eng_squig.inc): reads[i] (trimmed, normalised; mapped over [start, end)) against
  * targets[i], a predicted squiggle of npos columns of stride >= 3 floats (mean, log sd, dwell logit); out[i] belongs to

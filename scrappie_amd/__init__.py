@@ -262,6 +262,22 @@ def lib():
     for nm in ("map_to_sequence_viterbi_banded", "map_to_sequence_forward_banded"):
         getattr(L, nm).restype = C.c_float
         getattr(L, nm).argtypes = [PM, C.c_float, C.c_float, C.c_float, ip, C.c_size_t, sp, sp]
+    L.map_crf_to_sequence_viterbi.restype = C.c_float
+    L.map_crf_to_sequence_viterbi.argtypes = [PM, ip, C.c_size_t, ip]
+    L.map_crf_to_sequence_forward.restype = C.c_float
+    L.map_crf_to_sequence_forward.argtypes = [PM, ip, C.c_size_t]
+    L.map_crf_to_sequence_viterbi_banded.restype = C.c_float
+    L.map_crf_to_sequence_viterbi_banded.argtypes = [PM, ip, C.c_size_t, sp, sp, ip]
+    L.map_crf_to_sequence_forward_banded.restype = C.c_float
+    L.map_crf_to_sequence_forward_banded.argtypes = [PM, ip, C.c_size_t, sp, sp]
+    L.scrappie_hip_map_crf_bounds_sane.argtypes = [sp, sp, C.c_size_t, C.c_size_t]
+    L.scrappie_hip_map_crf_diagonal_band.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t, sp, sp]
+    L.scrappie_hip_map_crf_lds_max_seq.restype = C.c_size_t
+    L.scrappie_hip_map_crf_lds_max_seq.argtypes = []
+    L.scrappie_hip_map_crf_plan_scratch.restype = C.c_longlong
+    L.scrappie_hip_map_crf_plan_scratch.argtypes = [sp, sp, C.c_size_t, C.POINTER(C.c_longlong)]
+    L.scrappie_hip_map_crf_form_counts.restype = None
+    L.scrappie_hip_map_crf_form_counts.argtypes = [C.POINTER(C.c_uint64)]
     L.encode_bases_to_integers.restype = C.c_void_p
     L.encode_bases_to_integers.argtypes = [C.c_char_p, C.c_size_t, C.c_size_t]
     L.scrappie_hip_read_blocks.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
@@ -365,9 +381,10 @@ def last_error():
 
 def plan_scratch(kind, sizes, counts):
     """The planner's scratch layout of one launch of reads in this order (host arithmetic, no device): kind 'map' with
-    sizes = states and counts = blocks per read, or 'squig' with positions and samples.  Returns (off, total): the float
-    offset of each read's two score rows (-1: in LDS) and the floats allocated for all of them."""
-    fn = {"map": lib().scrappie_hip_map_plan_scratch, "squig": lib().scrappie_hip_squiggle_plan_scratch}[kind]
+    sizes = states and counts = blocks per read, 'squig' with positions and samples, or 'map_crf' with bases and blocks.
+    Returns (off, total): the float offset of each read's score rows (-1: in LDS) and the floats allocated for all of them."""
+    fn = {"map": lib().scrappie_hip_map_plan_scratch, "squig": lib().scrappie_hip_squiggle_plan_scratch,
+          "map_crf": lib().scrappie_hip_map_crf_plan_scratch}[kind]
     a = np.ascontiguousarray(sizes, dtype=np.uintp)
     b = np.ascontiguousarray(counts, dtype=np.uintp)
     off = np.zeros(len(a), dtype=np.longlong)
@@ -392,6 +409,14 @@ def launch_form_counts():
     lib().scrappie_hip_launch_form_counts(m, q)
     return dict(map={(bool(k & 8), bool(k & 4), bool(k & 2), bool(k & 1)): int(m[k]) for k in range(16)},
                 squig={(bool(k & 2), bool(k & 1)): int(q[k]) for k in range(4)})
+
+
+def map_crf_form_counts():
+    """Launches of each k_map_crf form in this process so far (scrappie_hip_map_crf_form_counts):
+    {(viterbi, tiled, scratch): n}."""
+    q = (C.c_uint64 * 8)()
+    lib().scrappie_hip_map_crf_form_counts(q)
+    return {(bool(k & 4), bool(k & 2), bool(k & 1)): int(q[k]) for k in range(8)}
 
 
 def squiggle_band_form_counts():
@@ -855,6 +880,61 @@ def map_post_to_sequence(post, sequence, stay_pen=0, skip_pen=0, local_pen=4.0, 
             score = func(post.data(), stay_pen, skip_pen, local_pen, p_seq, seq_len, p_lo, p_hi)
     finally:
         _libc.free(ptr)
+    if np.isnan(score):
+        raise RuntimeError('An unknown error occurred during alignment: ' + last_error())
+    return score, path_data
+
+
+def map_crf_diagonal_band(nblock, seq_len, halfwidth):
+    """(low, high) uintp arrays, nblock + 1 entries each: the diagonal band of half-width `halfwidth` cells of a read of `nblock`
+    blocks of a flip-flop (CRF) model against `seq_len` bases (scrappie_hip_map_crf_diagonal_band); always a valid band."""
+    lo, hi = np.zeros(nblock + 1, dtype=np.uintp), np.zeros(nblock + 1, dtype=np.uintp)
+    sp = C.POINTER(C.c_size_t)
+    if lib().scrappie_hip_map_crf_diagonal_band(nblock, seq_len, halfwidth, lo.ctypes.data_as(sp), hi.ctypes.data_as(sp)) != 0:
+        raise ValueError("a diagonal band needs at least one block and one base")
+    return [lo, hi]
+
+
+def map_trans_to_sequence(trans, sequence, viterbi=False, path=False, bands=None):
+    """Global alignment of a read's transitions under a flip-flop (CRF) model (a `ScrappyMatrix` of 25 rows, as
+    `calc_post(rt, model='rnnrf_r94')` gives) to a base sequence: decode_crf's recursion restricted to the paths that spell the
+    sequence, Viterbi or forward, full or banded; the DP runs on the GPU (k_map_crf).  `bands`: None, an int (half-width in
+    cells of the diagonal band) or a (low, high) pair of nblock + 1 entries each: the cells -- bases emitted so far, 0 .. len --
+    an entry of the path may be in.  Returns (score, path or None); path[t], t = 0 .. nblock, is the index of the last base
+    emitted through entry t, -1 while none."""
+    if path and not viterbi:
+        raise ValueError('Cannot calulate path with `viterbi==False`.')
+    if not isinstance(trans, ScrappyMatrix):
+        raise TypeError('`trans` should be a ScrappyMatrix.')
+    nblock, nstate = trans.shape
+    if nstate != 25:
+        raise ValueError('`trans` should hold the 25 transitions of a flip-flop (CRF) model per block.')
+    codes = encode_bases(sequence, 1).astype(np.int32)
+    seq_len = len(codes)
+    p_seq = codes.ctypes.data_as(C.POINTER(C.c_int))
+    path_data = np.zeros(nblock + 1, dtype=np.int32) if (viterbi and path) else None
+    p_path = path_data.ctypes.data_as(C.POINTER(C.c_int)) if path_data is not None else None
+    if bands is None:
+        if viterbi:
+            score = lib().map_crf_to_sequence_viterbi(trans.data(), p_seq, seq_len, p_path)
+        else:
+            score = lib().map_crf_to_sequence_forward(trans.data(), p_seq, seq_len)
+    else:
+        if isinstance(bands, (int, np.integer)):
+            bands = map_crf_diagonal_band(nblock, seq_len, int(bands))
+        elif len(bands) == 2:
+            bands = [np.ascontiguousarray(x, dtype=np.uintp) for x in bands]
+        else:
+            raise ValueError('`bands` should be `None`, an integer, or length 2.')
+        if len(bands[0]) != nblock + 1 or len(bands[1]) != nblock + 1:
+            raise ValueError('Supplied banding structure is not valid: nblock + 1 entries each.')
+        p_lo, p_hi = (x.ctypes.data_as(C.POINTER(C.c_size_t)) for x in bands)
+        if not lib().scrappie_hip_map_crf_bounds_sane(p_lo, p_hi, nblock, seq_len):
+            raise ValueError('Supplied banding structure is not valid.')
+        if viterbi:
+            score = lib().map_crf_to_sequence_viterbi_banded(trans.data(), p_seq, seq_len, p_lo, p_hi, p_path)
+        else:
+            score = lib().map_crf_to_sequence_forward_banded(trans.data(), p_seq, seq_len, p_lo, p_hi)
     if np.isnan(score):
         raise RuntimeError('An unknown error occurred during alignment: ' + last_error())
     return score, path_data
@@ -1423,14 +1503,19 @@ class Engine(object):
         network and S1 run as for `posterior`, the posterior stays on the device, only scores and paths return
         (scrappie_hip_map_batch).  `bands`: None, an int (scrappy's diagonal band, per read) or a list with a
         (low, high) pair or None per read.  Returns [(score, path or None)] in input order; score NaN where a read
-        cannot be mapped (too short, a bad sequence or band)."""
+        cannot be mapped (too short, a bad sequence or band).
+        With a flip-flop (CRF) model (`rnnrf_r94`) it is the global alignment of `map_trans_to_sequence` on the read's own
+        transitions (k_map_crf): a band holds nblock + 1 entries of cells (an int: `map_crf_diagonal_band`), a path
+        nblock + 1 entries, banded reads return one too, and the penalties are not used."""
         n = len(signals)
         if len(sequences) != n:
             raise ValueError("one sequence per signal")
         if path and not viterbi:
             raise ValueError('Cannot calulate path with `viterbi==False`.')
         h = self._models[model]
-        kmer_len = guess_state_properties(lib().scrappie_hip_model_states(self._h, h))[1]
+        nstate = lib().scrappie_hip_model_states(self._h, h)
+        crf = nstate == 25                  # the flip-flop models: 5 x 5 transitions, bases as codes of one
+        kmer_len = 1 if crf else guess_state_properties(nstate)[1]
         rts, keep = _raw_tables(signals)
         tgs = (_MapTarget * n)()
         for i, (x, sq) in enumerate(zip(keep[:n], sequences)):
@@ -1444,7 +1529,10 @@ class Engine(object):
             b = bands if (bands is None or isinstance(bands, int)) else bands[i]
             if isinstance(b, int):
                 nblock = self.read_blocks(model, len(x))
-                b = diagonal_bands(b, nblock, len(codes)) if nblock > 0 and len(codes) > 0 else None
+                if nblock <= 0 or len(codes) == 0:
+                    b = None
+                else:
+                    b = map_crf_diagonal_band(nblock, len(codes), b) if crf else diagonal_bands(b, nblock, len(codes))
             if b is not None:
                 lo, hi = (np.ascontiguousarray(v, dtype=np.uintp) for v in b)
                 keep += [lo, hi]
@@ -1455,7 +1543,10 @@ class Engine(object):
         out = (_MapResult * n)()
         if lib().scrappie_hip_map_batch(self._h, h, rts, tgs, n, C.byref(p), 1 if viterbi else 0, 1 if path else 0, out) != 0:
             raise RuntimeError("map_batch: " + last_error())
-        res = _scores_and_paths(out, n, 'nblock')
+        if crf:
+            res = [(float(r.score), np.ctypeslib.as_array(r.path, shape=(r.nblock + 1,)).copy() if r.path else None) for r in (out[i] for i in range(n))]
+        else:
+            res = _scores_and_paths(out, n, 'nblock')
         lib().scrappie_hip_free_map_results(out, n)
         return res
 

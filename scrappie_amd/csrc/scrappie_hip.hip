@@ -37,6 +37,7 @@
  *   sh_eng_surface.inc   the reference's per-read functions: one batch function per family, run by the queue or with a batch of one
  *   sh_eng_cut.inc       what the engines below share: a call cut into launches that fit the device (LaunchCut), per-read DP
  *                        records through a kernel with two homes (dp_order / dp_launch / dp_collect)
+ *   sh_eng_map_crf.inc   mapping of flip-flop (CRF) reads to base sequences (per-read; the launch group of the batched call)
  *   sh_eng_map.inc       block-based mapping of posteriors to sequences (per-read and batched)
  *   sh_eng_squig.inc     mapping of raw signals to predicted squiggles (per-read and batched)
  *   sh_eng_sqnet.inc     prediction of squiggles from base sequences (per-read and batched)
@@ -630,6 +631,7 @@ extern "C" scrappie_hip_params scrappie_hip_default_params(void) {
 #include "sh_eng_debug.inc"      /* measurement / test hooks: decoder and trunk inputs, debug_option / debug_fetch / debug_stitch */
 #include "sh_eng_surface.inc"      /* the reference's per-read functions: posterior / trunk on an explicit engine, the process-default engine, decode_transducer, decode_crf; all three coalesced (sh_coalesce.h) */
 #include "sh_eng_cut.inc"      /* shared by those below: LaunchCut (a call cut into launches), dp_order / dp_launch / dp_collect (a kernel with two homes) */
+#include "sh_eng_map_crf.inc"      /* mapping of flip-flop reads to base sequences (sh_map_crf.h): map_crf_to_sequence_* on the process-default engine, the launch group scrappie_hip_map_batch runs for a CRF model */
 #include "sh_eng_map.inc"      /* block-based mapping (sh_map.h): map_to_sequence_* on the process-default engine, scrappie_hip_map_batch */
 #include "sh_eng_squig.inc"      /* squiggle matching (sh_squig.h): squiggle_match_* on the process-default engine, scrappie_hip_squiggle_match_batch */
 #include "sh_eng_sqnet.inc"      /* squiggle prediction (sh_sqnet.h): squiggle_r94 and its relatives on the process-default engine, scrappie_hip_squiggle_predict_batch */

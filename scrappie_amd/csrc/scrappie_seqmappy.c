@@ -5,6 +5,8 @@
  * --model-file / --device as `scrappie raw` takes them, and more `fasta fast5` pairs after the first -- every pair is
  * mapped in ONE scrappie_hip_map_batch call (network, S1 and the mapping on the GPU; only scores and paths return) and
  * the records are written in argument order.  One pair prints exactly what the reference prints.
+ * --model rnnrf_r94 (a flip-flop model; the reference refuses it): the global alignment of k_map_crf, the same header
+ * line, one record per entry of the path (nblock + 1).
  */
 #define _GNU_SOURCE
 #include <getopt.h>
@@ -32,6 +34,9 @@ static void seqmappy_usage(FILE *fh) {
           "      --model=name           Raw model to use (default rgrgr_r94)\n"
           "      --model-file=path      Weight container (.scrm); default $SCRAPPIE_MODEL_DIR/<model>.scrm\n"
           "      --device=N             GPU to run on (default 0)\n"
+          "With a flip-flop (CRF) model (--model=rnnrf_r94) the read is aligned globally to the sequence under the model's own\n"
+          "transitions: the sequence is encoded with a state length of 1, the penalties are not used, and one record is\n"
+          "written per entry of the path (blocks + 1): pos is the last base emitted so far, -1 while none.\n"
           "Every (fasta, fast5) pair is mapped in one batched engine call; records are written in argument order.\n", fh);
 }
 
@@ -86,7 +91,9 @@ int main_seqmappy(int argc, char **argv) {
     scrappie_hip_engine *e = cli_open_model(device, model, model_file, &h);
     if (!e) return EXIT_FAILURE;
     int nstate = scrappie_hip_model_states(e, h), klen = 0;
-    for (int nk = nstate - 1; nk > 1 && nk % 4 == 0; nk /= 4) klen++;
+    const int crf = nstate == 25;        /* a flip-flop model (rnnrf_r94): bases as states of length 1, a path of nblock + 1 entries */
+    if (crf) klen = 1;
+    else for (int nk = nstate - 1; nk > 1 && nk % 4 == 0; nk /= 4) klen++;
 
     raw_table *rts = calloc(npair, sizeof *rts);
     scrappie_hip_map_target *tg = calloc(npair, sizeof *tg);
@@ -118,7 +125,7 @@ int main_seqmappy(int argc, char **argv) {
             const size_t nblock = res[i].nblock;
             fprintf(out, "# %s to %s -- score %f over %zu blocks (%f per block)\n", fasta[2 * i + 1], fasta[2 * i], -score, nblock, -score / nblock);
             fprintf(out, "block\tpos\n");
-            for (size_t b = 0; b < nblock; b++) fprintf(out, "%zu\t%d\n", b, res[i].path[b]);
+            for (size_t b = 0; b < nblock + (crf ? 1 : 0); b++) fprintf(out, "%zu\t%d\n", b, res[i].path[b]);
         }
     }
     scrappie_hip_free_map_results(res, npair);

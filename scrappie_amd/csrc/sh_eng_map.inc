@@ -2,6 +2,7 @@
  * block-based mapping of transducer posteriors to sequences (sh_map.h).  The reference's map_to_sequence_* on the
  * process-default engine (the caller's host posterior uploaded, one launch), and scrappie_hip_map_batch: the network and S1
  * of a launch group (run_staged to STOP_POST), k_map on the posterior where S1 left it, k_map_walk; scores and paths back.
+ * A flip-flop (CRF) model takes the same call and the same cut; its launch group is map_crf_group (sh_eng_map_crf.inc).
  * What is here is the family's own: the plan of a launch, the checks a target passes, the cost of a launch group, map_group.
  * The cutting of a call into launch groups and the run of the records through k_map's two homes are sh_eng_cut.inc's. */
 
@@ -265,8 +266,8 @@ extern "C" int scrappie_hip_map_batch(scrappie_hip_engine *e, int model, const r
     std::lock_guard<std::mutex> call(e->call_mu);
     Model *m = get_model(e, model);
     if (!m) return -1;
-    if (m->arch == 1) return set_err("map_batch: model '%s' is a CRF (flip-flop) model: block-based mapping needs a transducer posterior", m->name.c_str());
-    {   /* NS = 4^k + 1 */
+    const bool crf = m->arch == 1;      /* a flip-flop model: k_map_crf on its transitions (sh_eng_map_crf.inc) */
+    if (!crf) {   /* NS = 4^k + 1 */
         int nk = m->NS - 1;
         while (nk > 1 && nk % 4 == 0) nk /= 4;
         if (nk != 1) return set_err("map_batch: model '%s' has %d states, not 4^k + 1", m->name.c_str(), m->NS);
@@ -283,17 +284,20 @@ extern "C" int scrappie_hip_map_batch(scrappie_hip_engine *e, int model, const r
     const size_t budget = e->max_launch_blocks ? e->max_launch_blocks * bpb : (size_t)(e->mem_frac * (double)e->total_mem);
     auto cost = [&](size_t sT, size_t mT, size_t ex) { return (sT / 16 + mT + 1) * bpb + ex; };
     LaunchCut<MapLoad> cut{e, "map_batch"};
-    cut.run = [&](const std::vector<size_t> &grp, MapLoad &) { return map_group(e, m, reads, targets, grp, p, vit, wp, out, cut); };
+    cut.run = [&](const std::vector<size_t> &grp, MapLoad &) {
+        return crf ? map_crf_group(e, m, reads, targets, grp, p, vit, wp, out, cut) : map_group(e, m, reads, targets, grp, p, vit, wp, out, cut);
+    };
     for (size_t i = 0; i < n && !cut.failed; i++) {
         const scrappie_hip_map_target &t = targets[i];
         const size_t T = map_blocks(m, map_read_nsample(m, reads[i]));
         if (T == 0) { cut.refuse(i, "read too short for the model (or empty)"); continue; }
         const bool band = t.poslow != nullptr || t.poshigh != nullptr;
-        if (!t.seq || map_target_ok("map_batch", (size_t)m->NS, T, t.seq, t.seqlen, t.poslow, t.poshigh, band) || (band && !t.poslow)) {
+        if (!t.seq || (crf ? map_crf_target_ok("map_batch", T, t.seq, t.seqlen, t.poslow, t.poshigh, band)
+                           : map_target_ok("map_batch", (size_t)m->NS, T, t.seq, t.seqlen, t.poslow, t.poshigh, band)) || (band && !t.poslow)) {
             cut.refuse(i, t.seq ? g_err : "no sequence");
             continue;
         }
-        const size_t rb = map_read_bytes(t.seqlen, T, band, vit && wp && !band);
+        const size_t rb = crf ? map_crf_read_bytes(t.seqlen, T, band, vit && wp) : map_read_bytes(t.seqlen, T, band, vit && wp && !band);
         if (cost(T, T, rb) > budget) { cut.refuse(i, "read and sequence too long for one launch group on this device"); continue; }
         MapLoad &g = cut.load;
         cut.add(i, cut.who.size() < e->max_launch_reads && cost(g.sumT + T, std::max(g.maxT, T), g.extra + rb) <= budget);

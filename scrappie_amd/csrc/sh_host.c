@@ -717,6 +717,35 @@ bool are_bounds_sane(size_t const *low, size_t const *high, size_t nblock, size_
     return sh_bounds_sane(low, high, nblock, seqlen, 1) != 0;
 }
 
+/* Bands of the CRF mapping (k_map_crf, sh_map_crf.h): per ENTRY t = 0 .. nblock of the path (nblock + 1 of them) the cells
+ * [low[t], high[t]) of 0 .. seqlen, a cell being the number of bases emitted so far.  Valid: it starts at cell 0 and ends with
+ * cell seqlen, is never empty or beyond seqlen + 1, both edges non-decreasing, and every entry's lowest cell has a predecessor
+ * (itself or the cell below) in the entry before.  Quiet: 1 / 0. */
+int scrappie_hip_map_crf_bounds_sane(const size_t *low, const size_t *high, size_t nblock, size_t seqlen) {
+    if (!low || !high || nblock == 0 || seqlen == 0) return 0;
+    if (low[0] != 0 || high[nblock] != seqlen + 1) return 0;
+    for (size_t t = 0; t <= nblock; t++) {
+        if (low[t] >= high[t] || high[t] > seqlen + 1) return 0;
+        if (t == 0) continue;
+        if (low[t] < low[t - 1] || high[t] < high[t - 1] || low[t] > high[t - 1]) return 0;
+    }
+    return 1;
+}
+
+/* the diagonal through (entry 0, cell 0) and (entry nblock, cell seqlen), halfwidth cells to either side, clamped into
+ * 0 .. seqlen and, where the diagonal is steeper than the band is wide, reaching back to the entry before: always a band that
+ * scrappie_hip_map_crf_bounds_sane accepts.  low, high: nblock + 1 entries each.  0, or -1 on a null or empty argument. */
+int scrappie_hip_map_crf_diagonal_band(size_t nblock, size_t seqlen, size_t halfwidth, size_t *low, size_t *high) {
+    if (!low || !high || nblock == 0 || seqlen == 0) return -1;
+    for (size_t t = 0; t <= nblock; t++) {
+        const size_t c = (size_t)(((unsigned long long)t * (unsigned long long)seqlen) / (unsigned long long)nblock);
+        low[t] = c > halfwidth ? c - halfwidth : 0;
+        high[t] = (halfwidth >= seqlen || c + halfwidth + 1 > seqlen + 1) ? seqlen + 1 : c + halfwidth + 1;
+        if (t > 0 && low[t] > high[t - 1]) low[t] = high[t - 1];
+    }
+    return 0;
+}
+
 /* the library defines it (scrappie_hip.hip); weak, so that this file also links into the host-only builds of the tests */
 void sh_set_error(const char *fmt, ...) __attribute__((weak, format(printf, 1, 2)));
 #define SH_ERR(...) do { if (sh_set_error) sh_set_error(__VA_ARGS__); } while (0)
