@@ -474,6 +474,40 @@ void scrappie_hip_map_timing(scrappie_hip_engine *e, double out[3]);
 /* states up to which k_map keeps its score rows and the codes in LDS; longer sequences keep the rows in device scratch */
 size_t scrappie_hip_map_lds_max_seq(void);
 
+/* One read against many candidate sequences (sh_eng_map_pack.inc; k_map_pack, sh_map_pack.h): which of these barcodes, alleles,
+ * edited calls or references is this read?  The network and S1 run ONCE per read; reads[i] is mapped, unbanded, to every
+ * cands[i].cand[k], the candidates of a read packed end to end into workgroups of k_map_pack (a candidate too long for a pack
+ * takes k_map on the same resident posterior).  out[i].score[k] (malloc'd, ncand floats) belongs to cands[i].cand[k] and is the raw
+ * score map_to_sequence_viterbi / _forward give for that pair, bit for bit what scrappie_hip_map_batch gives: candidates of
+ * different lengths are compared as they are, and normalising (per block, per base, against a background) is the caller's
+ * business.  best: the index of the highest finite score, the lowest index on a tie, -1 where there is none.  With viterbi and
+ * want_path, path is the best candidate's Viterbi path (malloc'd nblock int32, -1 in START / END) from a second pass of k_map on
+ * that candidate alone while the posterior is still resident -- scrappie_hip_map_batch's path for the pair; NULL otherwise.
+ * A candidate that cannot be mapped (no or an empty sequence, a state outside the model's) gets NAN and its neighbours are scored;
+ * a candidate with poslow / poshigh set gets NAN too: bands are not part of this call.  A read that cannot run (too short, out of
+ * the operand range, over the launch budget) gets every score NAN and best -1, the other reads untouched; the first such reason is
+ * the error text.  ncand == 0 is a read with no scores.  Several reads may point at the same cand array (one set of barcodes
+ * for all): it is checked, packed and uploaded once.  A CRF model: -1 with a text.  Locks, parameters and
+ * the cut into launch groups as scrappie_hip_map_batch; scrappie_hip_map_timing covers these calls ([1] k_map_pack + k_map, [2] walk + results). */
+typedef struct { const scrappie_hip_map_target *cand; size_t ncand; } scrappie_hip_map_candidates;
+typedef struct { float *score; size_t ncand; int best; size_t nblock; int32_t *path; } scrappie_hip_map_multi_result;
+int scrappie_hip_map_multi_batch(scrappie_hip_engine *e, int model, const raw_table *reads, const scrappie_hip_map_candidates *cands,
+                                 size_t n, const scrappie_hip_params *p, int viterbi, int want_path, scrappie_hip_map_multi_result *out);
+void scrappie_hip_free_map_multi_results(scrappie_hip_map_multi_result *r, size_t n);
+/* per-read surface, process-default engine: a host log-posterior as map_to_sequence_viterbi takes it against ncand candidates,
+ * score[k] for cand[k] (NAN where that candidate cannot be mapped or is banded).  0, or -1 with the reason. */
+int scrappie_hip_map_post_multi(const_scrappie_matrix logpost, float stay_pen, float skip_pen, float local_pen,
+                                const scrappie_hip_map_target *cand, size_t ncand, int viterbi, float *score);
+/* The packing on the host, no device (sh_host.c): candidates of seqlen[k] states (seqlen[k] + 2 cells: the states, START, END) go
+ * into packs of at most pack_cells cells in input order; pack[k] the pack, cell[k] the candidate's first cell in it; pack[k] = -1
+ * where the candidate's cells exceed scrappie_hip_map_pack_max_cells() (the cells whose rows and tables fit k_map_pack's LDS) --
+ * it takes k_map.  Returns the number of packs.  The debug option "map_pack_cells" sets an engine's pack_cells (0: every candidate
+ * through k_map, one workgroup each; -1: the default; a NULL engine: the process-default engine). */
+long scrappie_hip_map_pack_plan(const size_t *seqlen, size_t ncand, size_t pack_cells, int *pack, long long *cell);
+size_t scrappie_hip_map_pack_max_cells(void);
+/* launches of each k_map_pack form in this process, all engines together: index (viterbi ? 2 : 0) | (tiled ? 1 : 0) */
+void scrappie_hip_map_pack_form_counts(uint64_t forms[4]);
+
 /* Reads of a flip-flop (CRF) model mapped to base sequences (k_map_crf, sh_map_crf.h; sh_eng_map_crf.inc): decode_crf's recursion
  * (src/decode.c:836-893) restricted to the paths that spell the sequence.  The reference has no such function; the definition is
  * decode_crf's own: a path has nblock + 1 entries, its non-stay entries in order are exactly seq (global: all of the read, all of

@@ -61,6 +61,15 @@ class _MapResult(C.Structure):
     _fields_ = [("score", C.c_float), ("nblock", C.c_size_t), ("path", C.POINTER(C.c_int32))]
 
 
+class _MapCandidates(C.Structure):
+    _fields_ = [("cand", C.POINTER(_MapTarget)), ("ncand", C.c_size_t)]
+
+
+class _MapMultiResult(C.Structure):
+    _fields_ = [("score", C.POINTER(C.c_float)), ("ncand", C.c_size_t), ("best", C.c_int), ("nblock", C.c_size_t),
+                ("path", C.POINTER(C.c_int32))]
+
+
 class _SquigTarget(C.Structure):
     _fields_ = [("params", C.POINTER(C.c_float)), ("npos", C.c_size_t), ("stride", C.c_size_t)]
 
@@ -286,6 +295,17 @@ def lib():
                                          C.POINTER(Params), C.c_int, C.c_int, C.POINTER(_MapResult)]
     L.scrappie_hip_free_map_results.argtypes = [C.POINTER(_MapResult), C.c_size_t]
     L.scrappie_hip_map_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    L.scrappie_hip_map_multi_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(_RawTable), C.POINTER(_MapCandidates), C.c_size_t,
+                                               C.POINTER(Params), C.c_int, C.c_int, C.POINTER(_MapMultiResult)]
+    L.scrappie_hip_free_map_multi_results.restype = None
+    L.scrappie_hip_free_map_multi_results.argtypes = [C.POINTER(_MapMultiResult), C.c_size_t]
+    L.scrappie_hip_map_post_multi.argtypes = [PM, C.c_float, C.c_float, C.c_float, C.POINTER(_MapTarget), C.c_size_t, C.c_int, fp]
+    L.scrappie_hip_map_pack_plan.restype = C.c_long
+    L.scrappie_hip_map_pack_plan.argtypes = [sp, C.c_size_t, C.c_size_t, ip, C.POINTER(C.c_longlong)]
+    L.scrappie_hip_map_pack_max_cells.restype = C.c_size_t
+    L.scrappie_hip_map_pack_max_cells.argtypes = []
+    L.scrappie_hip_map_pack_form_counts.restype = None
+    L.scrappie_hip_map_pack_form_counts.argtypes = [C.POINTER(C.c_uint64)]
     L.squiggle_match_viterbi.restype = C.c_float
     L.squiggle_match_viterbi.argtypes = [_RawTable, C.c_float, PM, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_int32)]
     L.squiggle_match_forward.restype = C.c_float
@@ -417,6 +437,37 @@ def map_crf_form_counts():
     q = (C.c_uint64 * 8)()
     lib().scrappie_hip_map_crf_form_counts(q)
     return {(bool(k & 4), bool(k & 2), bool(k & 1)): int(q[k]) for k in range(8)}
+
+
+def map_pack_form_counts():
+    """Launches of each k_map_pack form in this process so far (scrappie_hip_map_pack_form_counts): {(viterbi, tiled): n}."""
+    q = (C.c_uint64 * 4)()
+    lib().scrappie_hip_map_pack_form_counts(q)
+    return {(bool(k & 2), bool(k & 1)): int(q[k]) for k in range(4)}
+
+
+def map_pack_max_cells():
+    """The most cells (a candidate of L states takes L + 2) one pack of k_map_pack holds; a longer candidate takes k_map."""
+    return int(lib().scrappie_hip_map_pack_max_cells())
+
+
+def map_pack_plan(seqlens, pack_cells):
+    """The packing of candidates of `seqlens` states into packs of at most `pack_cells` cells (host arithmetic, no device;
+    scrappie_hip_map_pack_plan): (pack, cell, npack) -- each candidate's pack (-1: too long for any, it takes k_map) and its
+    first cell there."""
+    a = np.ascontiguousarray(seqlens, dtype=np.uintp)
+    pack = np.zeros(len(a), dtype=np.int32)
+    cell = np.zeros(len(a), dtype=np.longlong)
+    n = lib().scrappie_hip_map_pack_plan(a.ctypes.data_as(C.POINTER(C.c_size_t)), len(a), int(pack_cells), pack.ctypes.data_as(C.POINTER(C.c_int)),
+                                         cell.ctypes.data_as(C.POINTER(C.c_longlong)))
+    return pack, cell, int(n)
+
+
+def set_map_pack_cells(value):
+    """The debug option "map_pack_cells" of the process-default engine, the one `map_post_to_sequences` runs on: cells per pack
+    of candidates, 0: every candidate through k_map, -1: the default.  (An `Engine` has `debug_option`.)"""
+    if lib().scrappie_hip_debug_option(None, b"map_pack_cells", int(value)) != 0:
+        raise RuntimeError("debug_option: " + last_error())
 
 
 def squiggle_band_form_counts():
@@ -883,6 +934,39 @@ def map_post_to_sequence(post, sequence, stay_pen=0, skip_pen=0, local_pen=4.0, 
     if np.isnan(score):
         raise RuntimeError('An unknown error occurred during alignment: ' + last_error())
     return score, path_data
+
+
+def _map_targets(sequences, kmer_len):
+    """The ctypes scrappie_hip_map_target array of `sequences` (unbanded) and what keeps its memory alive; a sequence that
+    cannot be encoded becomes an empty one, which the library answers with NaN."""
+    tgs = (_MapTarget * max(len(sequences), 1))()
+    keep = []
+    for i, sq in enumerate(sequences):
+        try:
+            codes = encode_bases(sq, kmer_len)
+        except ValueError:
+            codes = np.zeros(0, dtype=np.int32)
+        keep.append(codes)
+        tgs[i].seq = codes.ctypes.data_as(C.POINTER(C.c_int))
+        tgs[i].seqlen = len(codes)
+    return tgs, keep
+
+
+def map_post_to_sequences(post, sequences, stay_pen=0, skip_pen=0, local_pen=4.0, viterbi=False):
+    """`map_post_to_sequence`'s score of a posterior (a `ScrappyMatrix` of log-probabilities) against each of `sequences`, in one
+    pass on the GPU: the candidates are packed into workgroups of k_map_pack (scrappie_hip_map_post_multi).  Returns a float32
+    array of raw scores, one per sequence, NaN where a sequence cannot be mapped; sequences of different lengths are compared as
+    they are."""
+    if not isinstance(post, ScrappyMatrix):
+        raise TypeError('`post` should be a ScrappyMatrix.')
+    nblock, nstate = post.shape
+    kmer_len = guess_state_properties(nstate)[1]
+    tgs, keep = _map_targets(sequences, kmer_len)
+    score = np.full(len(sequences), np.nan, dtype=np.float32)
+    if lib().scrappie_hip_map_post_multi(post.data(), stay_pen, skip_pen, local_pen, tgs, len(sequences), 1 if viterbi else 0,
+                                         score.ctypes.data_as(C.POINTER(C.c_float))) != 0:
+        raise RuntimeError('An unknown error occurred during alignment: ' + last_error())
+    return score
 
 
 def map_crf_diagonal_band(nblock, seq_len, halfwidth):
@@ -1548,6 +1632,54 @@ class Engine(object):
         else:
             res = _scores_and_paths(out, n, 'nblock')
         lib().scrappie_hip_free_map_results(out, n)
+        return res
+
+    def map_to_sequences(self, signals, candidates, model='rgrgr_r94', viterbi=True, path=False, stay_pen=0.0, skip_pen=0.0,
+                         local_pen=4.0, min_prob=1e-5, tempW=1.0, tempb=1.0):
+        """Which of these sequences is this read?  Each read (trimmed, normalised float32 signal) against every one of its
+        candidate base sequences, unbanded: the network and S1 run once per read, the candidates are packed into workgroups
+        of k_map_pack on the resident posterior (scrappie_hip_map_multi_batch).  `candidates`: a list of base strings shared
+        by every read (encoded once), or one list of strings per read.  Returns [(scores, best, path or None)] in input
+        order: the float32 raw scores as `map_to_sequence` gives them (NaN where a candidate, or the read, cannot be
+        mapped; normalising for length is the caller's business), the index of the highest (the lowest index on a tie,
+        -1: none) and, with `path`, the Viterbi path of that candidate."""
+        n = len(signals)
+        if path and not viterbi:
+            raise ValueError('Cannot calulate path with `viterbi==False`.')
+        candidates = list(candidates)
+        shared = all(isinstance(c, str) for c in candidates)
+        if not shared:
+            if any(isinstance(c, str) for c in candidates):
+                raise ValueError("`candidates`: a list of strings for every read, or one list of strings per read")
+            if len(candidates) != n:
+                raise ValueError("one list of candidates per signal")
+        h = self._models[model]
+        nstate = lib().scrappie_hip_model_states(self._h, h)
+        if nstate == 25:
+            raise RuntimeError("map_multi_batch: a flip-flop (CRF) model maps one sequence per read (map_to_sequence)")
+        kmer_len = guess_state_properties(nstate)[1]
+        rts, keep = _raw_tables(signals)
+        cds = (_MapCandidates * max(n, 1))()
+        if shared:
+            tgs, codes = _map_targets(candidates, kmer_len)
+            keep += [tgs, codes]
+            for i in range(n):
+                cds[i].cand, cds[i].ncand = tgs, len(candidates)
+        else:
+            for i, cl in enumerate(candidates):
+                tgs, codes = _map_targets(list(cl), kmer_len)
+                keep += [tgs, codes]
+                cds[i].cand, cds[i].ncand = tgs, len(cl)
+        p = self.default_params(min_prob=min_prob, tempW=tempW, tempb=tempb, stay_pen=stay_pen, skip_pen=skip_pen,
+                                local_pen=local_pen)
+        out = (_MapMultiResult * max(n, 1))()
+        if lib().scrappie_hip_map_multi_batch(self._h, h, rts, cds, n, C.byref(p), 1 if viterbi else 0, 1 if path else 0, out) != 0:
+            raise RuntimeError("map_multi_batch: " + last_error())
+        res = []
+        for r in (out[i] for i in range(n)):
+            sc = np.ctypeslib.as_array(r.score, shape=(r.ncand,)).copy() if r.ncand else np.zeros(0, dtype=np.float32)
+            res.append((sc, int(r.best), np.ctypeslib.as_array(r.path, shape=(r.nblock,)).copy() if r.path else None))
+        lib().scrappie_hip_free_map_multi_results(out, n)
         return res
 
     def _timing(self, fn, names):

@@ -39,6 +39,7 @@
  *                        records through a kernel with two homes (dp_order / dp_launch / dp_collect)
  *   sh_eng_map_crf.inc   mapping of flip-flop (CRF) reads to base sequences (per-read; the launch group of the batched call)
  *   sh_eng_map.inc       block-based mapping of posteriors to sequences (per-read and batched)
+ *   sh_eng_map_pack.inc  one read against many candidate sequences, packed into workgroups (per-read and batched)
  *   sh_eng_squig.inc     mapping of raw signals to predicted squiggles (per-read and batched)
  *   sh_eng_sqnet.inc     prediction of squiggles from base sequences (per-read and batched)
  *   sh_eng_events.inc    event detection (per-read and batched; kernels in sh_events.h)
@@ -76,6 +77,7 @@
 #include "sh_dev.h"
 #include "sh_coalesce.h"
 #include "sh_map.h"
+#include "sh_map_pack.h"
 #include "sh_squig.h"
 #include "sh_squig_band.h"
 #include "sh_sqnet.h"
@@ -487,6 +489,8 @@ struct scrappie_hip_engine {
     HBuf h_dec_in, h_dec_out; DBuf d_dec[7];             /* decode_batch: posteriors in (a lone call; the queue's members fill the queue's own), paths + scores out */
     HBuf h_crf_in, h_crf_out; DBuf d_crf[4];             /* crf_batch */
     DpBufs dp_map; DBuf d_map_seq, d_map_band, d_map_post;       /* block-based mapping (sh_eng_map.inc): the records' buffers; codes, bands, a per-read call's dense posterior */
+    DBuf d_mpk_rd, d_mpk_cell, d_mpk_first, d_mpk_score; HBuf h_mpk;      /* candidates in packs (sh_eng_map_pack.inc): the packs, their cell words and first cells, scores; scores on the host */
+    int map_pack_cells = -1;         /* cells a pack of candidates holds (debug option "map_pack_cells"; 0: every candidate through k_map, -1: the default) */
     double map_ms[3] = {0, 0, 0};    /* scrappie_hip_map_batch: network + S1, k_map, k_map_walk + results, summed over the last call's launch groups */
     DpBufs dp_sq; DBuf d_sq_sig, d_sq_tab;       /* squiggle matching (sh_eng_squig.inc): the records' buffers; signals, tables */
     double squig_ms[3] = {0, 0, 0};  /* scrappie_hip_squiggle_match_batch: tables + uploads, k_squig, k_squig_walk + results, summed over the last call's launches */
@@ -633,6 +637,7 @@ extern "C" scrappie_hip_params scrappie_hip_default_params(void) {
 #include "sh_eng_cut.inc"      /* shared by those below: LaunchCut (a call cut into launches), dp_order / dp_launch / dp_collect (a kernel with two homes) */
 #include "sh_eng_map_crf.inc"      /* mapping of flip-flop reads to base sequences (sh_map_crf.h): map_crf_to_sequence_* on the process-default engine, the launch group scrappie_hip_map_batch runs for a CRF model */
 #include "sh_eng_map.inc"      /* block-based mapping (sh_map.h): map_to_sequence_* on the process-default engine, scrappie_hip_map_batch */
+#include "sh_eng_map_pack.inc"      /* one read against many candidate sequences (sh_map_pack.h): scrappie_hip_map_multi_batch, scrappie_hip_map_post_multi */
 #include "sh_eng_squig.inc"      /* squiggle matching (sh_squig.h): squiggle_match_* on the process-default engine, scrappie_hip_squiggle_match_batch */
 #include "sh_eng_sqnet.inc"      /* squiggle prediction (sh_sqnet.h): squiggle_r94 and its relatives on the process-default engine, scrappie_hip_squiggle_predict_batch */
 #include "sh_eng_events.inc"      /* event detection (sh_events.h): detect_events on the process-default engine, scrappie_hip_detect_events_batch; `scrappie events` for a batch (scrappie_hip_basecall_events_batch) */

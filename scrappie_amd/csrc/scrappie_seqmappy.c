@@ -7,9 +7,13 @@
  * the records are written in argument order.  One pair prints exactly what the reference prints.
  * --model rnnrf_r94 (a flip-flop model; the reference refuses it): the global alignment of k_map_crf, the same header
  * line, one record per entry of the path (nblock + 1).
+ * --all-records: every record of a pair's FASTA is a candidate for the pair's read, not just the first -- all pairs in ONE
+ * scrappie_hip_map_multi_batch call (the network once per read, the candidates packed into workgroups); per pair a table of the
+ * records' scores and then the usual header and path of the best one.  Without the option nothing changes.
  */
 #define _GNU_SOURCE
 #include <getopt.h>
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -37,16 +41,77 @@ static void seqmappy_usage(FILE *fh) {
           "With a flip-flop (CRF) model (--model=rnnrf_r94) the read is aligned globally to the sequence under the model's own\n"
           "transitions: the sequence is encoded with a state length of 1, the penalties are not used, and one record is\n"
           "written per entry of the path (blocks + 1): pos is the last base emitted so far, -1 while none.\n"
-          "Every (fasta, fast5) pair is mapped in one batched engine call; records are written in argument order.\n", fh);
+          "Every (fasta, fast5) pair is mapped in one batched engine call; records are written in argument order.\n"
+          "      --all-records          Map the read to EVERY record of its fasta, not just the first: per pair a line\n"
+          "                             `# fast5 to fasta -- N records`, a table record / name / score / per_block (scores\n"
+          "                             negated, as in the header line; raw scores: records of different lengths are compared\n"
+          "                             as they are), then the header line and the path of the best record, named fasta:name.\n"
+          "                             Transducer models only.\n", fh);
+}
+
+/* --all-records: pair i's read against every record of its FASTA, all pairs in one scrappie_hip_map_multi_batch call */
+static int seqmappy_all_records(scrappie_hip_engine *e, int h, int klen, const scrappie_hip_params *p, char **fasta, size_t npair, FILE *out,
+                                int trim_start, int trim_end, int varseg_chunk, float varseg_thresh) {
+    raw_table *rts = calloc(npair, sizeof *rts);
+    scrappie_hip_map_candidates *cd = calloc(npair, sizeof *cd);
+    scrappie_hip_map_multi_result *res = calloc(npair, sizeof *res);
+    struct cli_fasta **recs = calloc(npair, sizeof *recs);
+    size_t *nrec = calloc(npair, sizeof *nrec);
+    int rc = EXIT_SUCCESS;
+    for (size_t i = 0; i < npair; i++) {
+        const char *fa = fasta[2 * i], *f5 = fasta[2 * i + 1];
+        if (cli_read_fasta(fa, &recs[i], &nrec[i], 0) || nrec[i] == 0) { fprintf(stderr, "scrappie: Failed to open \"%s\" for input.\n", fa); rc = EXIT_FAILURE; continue; }
+        scrappie_hip_map_target *tg = calloc(nrec[i], sizeof *tg);
+        for (size_t k = 0; k < nrec[i]; k++) {           /* a record that cannot be encoded stays an empty candidate: NAN in the table */
+            int *codes = recs[i][k].seq ? encode_bases_to_integers(recs[i][k].seq, recs[i][k].n, (size_t)klen) : NULL;
+            if (!codes) { fprintf(stderr, "scrappie: cannot encode record %zu of \"%s\": %s\n", k, fa, scrappie_hip_last_error()); continue; }
+            tg[k].seq = codes; tg[k].seqlen = recs[i][k].n - (size_t)klen + 1;
+        }
+        cd[i].cand = tg; cd[i].ncand = nrec[i];
+        rts[i] = cli_load_read(f5, trim_start, trim_end, varseg_chunk, varseg_thresh, 1);
+        if (!rts[i].raw) { fprintf(stderr, "scrappie: Failed to open \"%s\" for input and trim signal.\n", f5); rc = EXIT_FAILURE; cd[i].ncand = 0; }
+    }
+    if (scrappie_hip_map_multi_batch(e, h, rts, cd, npair, p, 1, 1, res) != 0) {
+        fprintf(stderr, "scrappie: %s\n", scrappie_hip_last_error());
+        rc = EXIT_FAILURE;
+    } else {
+        for (size_t i = 0; i < npair; i++) {
+            if (!rts[i].raw || !cd[i].cand) continue;
+            const char *fa = fasta[2 * i], *f5 = fasta[2 * i + 1];
+            if (res[i].best < 0 || !res[i].path) { fprintf(stderr, "scrappie: Failed to map \"%s\" to \"%s\"\n", f5, fa); rc = EXIT_FAILURE; continue; }
+            const size_t nblock = res[i].nblock;
+            fprintf(out, "# %s to %s -- %zu records\n", f5, fa, nrec[i]);
+            fprintf(out, "record\tname\tscore\tper_block\n");
+            for (size_t k = 0; k < nrec[i]; k++) {
+                const float sc = res[i].score[k];
+                if (isnan(sc)) fprintf(out, "%zu\t%s\tnan\tnan\n", k, recs[i][k].name ? recs[i][k].name : "");
+                else fprintf(out, "%zu\t%s\t%f\t%f\n", k, recs[i][k].name ? recs[i][k].name : "", -sc, -sc / nblock);
+            }
+            const size_t b = (size_t)res[i].best;
+            const float score = res[i].score[b];
+            fprintf(out, "# %s to %s:%s -- score %f over %zu blocks (%f per block)\n", f5, fa, recs[i][b].name ? recs[i][b].name : "", -score, nblock, -score / nblock);
+            fprintf(out, "block\tpos\n");
+            for (size_t t = 0; t < nblock; t++) fprintf(out, "%zu\t%d\n", t, res[i].path[t]);
+        }
+    }
+    scrappie_hip_free_map_multi_results(res, npair);
+    for (size_t i = 0; i < npair; i++) {
+        if (cd[i].cand) { for (size_t k = 0; k < nrec[i]; k++) free((void *)cd[i].cand[k].seq); free((void *)cd[i].cand); }
+        cli_free_fasta(recs[i], nrec[i]);
+        free(rts[i].raw); free(rts[i].uuid);
+    }
+    free(nrec); free(recs); free(res); free(cd); free(rts);
+    return rc;
 }
 
 int main_seqmappy(int argc, char **argv) {
-    enum { O_SEG = 256, O_T1, O_T2, O_LIC, O_MODEL, O_MFILE, O_DEV };
+    enum { O_SEG = 256, O_T1, O_T2, O_LIC, O_MODEL, O_MFILE, O_DEV, O_ALL };
     static const struct option lo[] = {
         {"localpen", 1, 0, 'l'}, {"min_prob", 1, 0, 'm'}, {"output", 1, 0, 'o'}, {"prefix", 1, 0, 'p'},
         {"segmentation", 1, 0, O_SEG}, {"skip", 1, 0, 's'}, {"stay", 1, 0, 'y'}, {"trim", 1, 0, 't'},
         {"temperature1", 1, 0, O_T1}, {"temperature2", 1, 0, O_T2}, {"licence", 0, 0, O_LIC}, {"license", 0, 0, O_LIC},
-        {"model", 1, 0, O_MODEL}, {"model-file", 1, 0, O_MFILE}, {"device", 1, 0, O_DEV}, {"help", 0, 0, '?'}, {0, 0, 0, 0}};
+        {"model", 1, 0, O_MODEL}, {"model-file", 1, 0, O_MFILE}, {"device", 1, 0, O_DEV}, {"all-records", 0, 0, O_ALL}, {"help", 0, 0, '?'}, {0, 0, 0, 0}};
+    int all_records = 0;
     /* defaults: scrappie_seqmappy.c:62-78 */
     scrappie_hip_params p = scrappie_hip_default_params();
     p.local_pen = 4.0f; p.min_prob = 1e-5f; p.stay_pen = 0.0f; p.skip_pen = 0.0f; p.tempW = 1.0f; p.tempb = 1.0f;
@@ -78,6 +143,7 @@ int main_seqmappy(int argc, char **argv) {
             break;
         case O_MFILE: model_file = optarg; break;
         case O_DEV: device = atoi(optarg); break;
+        case O_ALL: all_records = 1; break;
         default: seqmappy_usage(stderr); return EXIT_FAILURE;
         }
     }
@@ -85,6 +151,10 @@ int main_seqmappy(int argc, char **argv) {
     if (nargs <= 0) { seqmappy_usage(stderr); return EXIT_FAILURE; }
     if (nargs % 2) { fprintf(stderr, "scrappie: fast5 file is a required argument\n"); return EXIT_FAILURE; }    /* scrappie_seqmappy.c:153 */
     const size_t npair = (size_t)nargs / 2;
+    if (all_records && get_raw_model(model) == SCRAPPIE_MODEL_RNNRF_R9_4) {
+        fprintf(stderr, "scrappie: --all-records maps transducer models only; \"%s\" is a flip-flop (CRF) model\n", model);
+        return EXIT_FAILURE;
+    }
     char **fasta = argv + optind;        /* fasta[2 i], fast5 = fasta[2 i + 1] */
 
     int h;
@@ -94,6 +164,14 @@ int main_seqmappy(int argc, char **argv) {
     const int crf = nstate == 25;        /* a flip-flop model (rnnrf_r94): bases as states of length 1, a path of nblock + 1 entries */
     if (crf) klen = 1;
     else for (int nk = nstate - 1; nk > 1 && nk % 4 == 0; nk /= 4) klen++;
+    if (all_records) {
+        int rc = EXIT_FAILURE;
+        if (crf) fprintf(stderr, "scrappie: --all-records maps transducer models only; \"%s\" is a flip-flop (CRF) model\n", model);
+        else rc = seqmappy_all_records(e, h, klen, &p, fasta, npair, out, trim_start, trim_end, varseg_chunk, varseg_thresh);
+        if (out != stdout) fclose(out);
+        scrappie_hip_engine_destroy(e);
+        return rc;
+    }
 
     raw_table *rts = calloc(npair, sizeof *rts);
     scrappie_hip_map_target *tg = calloc(npair, sizeof *tg);

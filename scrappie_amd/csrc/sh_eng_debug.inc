@@ -13,9 +13,12 @@ extern "C" int scrappie_hip_set_trunk_input(scrappie_hip_engine *e, const float 
     return e->alt_trunk.set("set_trunk_input", d_trunk, trunk_off, n_trunk);
 }
 
+static scrappie_hip_engine *default_engine();      /* (sh_eng_surface.inc) */
+
 /* Test hooks.  Options: "ff_separate" (S1 and the decoder as two kernels on this engine, whatever the shape),
  * "dump_final" (the decoders leave every tile's final scores, start and end state in the hand-over buffer). */
 extern "C" int scrappie_hip_debug_option(scrappie_hip_engine *e, const char *name, int value) {
+    if (!e && name && !strcmp(name, "map_pack_cells")) e = default_engine();      /* the per-read surface's engine has no handle */
     if (!e || !name) return set_err("debug_option: null argument");
     if (e->any_pending()) return set_err("debug_option: launch groups are in flight");
     if (!strcmp(name, "ff_separate")) e->dbg_ff_separate = value != 0;
@@ -34,6 +37,7 @@ extern "C" int scrappie_hip_debug_option(scrappie_hip_engine *e, const char *nam
     else if (!strcmp(name, "tail_free_frac")) e->dbg_tail_free_frac = value / 1000.0;      /* what the helper engine's creation takes for the device's free share (in 1/1000) */
     else if (!strcmp(name, "squiggle_budget_kb")) e->dbg_squig_budget = value > 0 ? (size_t)value << 10 : 0;      /* device bytes per squiggle-matching launch (0: from free memory) */
     else if (!strcmp(name, "sqnet_budget_kb")) e->dbg_sqnet_budget = value > 0 ? (size_t)value << 10 : 0;      /* device bytes per squiggle-predicting launch (0: from free memory) */
+    else if (!strcmp(name, "map_pack_cells")) e->map_pack_cells = value < 0 ? -1 : value;      /* cells per pack of candidates (0: every candidate through k_map; -1: the default) */
     else if (!strcmp(name, "events_budget_samples")) e->dbg_events_budget = value > 0 ? (size_t)value : 0;      /* sample slots per event-detection launch (0: from free memory) */
     else return set_err("debug_option: unknown option '%s'", name);
     return 0;

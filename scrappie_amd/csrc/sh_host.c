@@ -717,6 +717,39 @@ bool are_bounds_sane(size_t const *low, size_t const *high, size_t nblock, size_
     return sh_bounds_sane(low, high, nblock, seqlen, 1) != 0;
 }
 
+/* Packs of candidates (k_map_pack, sh_map_pack.h): a candidate of L states takes L + 2 cells, a pack of ncell cells and ncand
+ * candidates two rows of floats, a word per cell and ncand + 1 first cells in LDS. */
+size_t sh_map_pack_lds_bytes(size_t ncell, size_t ncand) { return (3 * ncell + ncand + 1) * 4; }
+
+/* the most cells a pack may hold: what fits SH_MAP_LDS however the cells are shared out among candidates -- a candidate has at least
+ * 3 cells, so ncell cells hold ncell / 3 candidates at most, and the bytes only grow with ncell */
+size_t scrappie_hip_map_pack_max_cells(void) {
+    size_t c = SH_MAP_LDS / 12;
+    while (c > 0 && sh_map_pack_lds_bytes(c, c / 3) > SH_MAP_LDS) c--;
+    return c;
+}
+
+/* Candidates of seqlen[k] states into packs of at most pack_cells cells (at most scrappie_hip_map_pack_max_cells() whatever is
+ * asked for), in input order: a pack is closed when the next candidate would take it past pack_cells, so a candidate of more
+ * cells than that is alone in its pack.  pack[k]: the candidate's pack, cell[k]: its first cell there; pack[k] = -1 (cell[k] = -1)
+ * where its seqlen[k] + 2 cells exceed the most a pack may hold -- such a candidate takes k_map.  Returns the number of packs. */
+long scrappie_hip_map_pack_plan(const size_t *seqlen, size_t ncand, size_t pack_cells, int *pack, long long *cell) {
+    if (!seqlen || !pack || !cell) return 0;
+    const size_t maxc = scrappie_hip_map_pack_max_cells();
+    if (pack_cells > maxc) pack_cells = maxc;
+    long np = 0;
+    size_t used = 0;                    /* cells of the open pack, np - 1; 0: none is open */
+    for (size_t k = 0; k < ncand; k++) {
+        if (seqlen[k] > maxc - 2) { pack[k] = -1; cell[k] = -1; continue; }
+        const size_t c = seqlen[k] + 2;
+        if (used == 0 || used + c > pack_cells) { np++; used = 0; }
+        pack[k] = (int)(np - 1);
+        cell[k] = (long long)used;
+        used += c;
+    }
+    return np;
+}
+
 /* Bands of the CRF mapping (k_map_crf, sh_map_crf.h): per ENTRY t = 0 .. nblock of the path (nblock + 1 of them) the cells
  * [low[t], high[t]) of 0 .. seqlen, a cell being the number of bases emitted so far.  Valid: it starts at cell 0 and ends with
  * cell seqlen, is never empty or beyond seqlen + 1, both edges non-decreasing, and every entry's lowest cell has a predecessor

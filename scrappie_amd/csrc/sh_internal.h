@@ -16,6 +16,10 @@ int sh_zlib_inflate(unsigned char *dst, size_t cap, size_t *outlen, const unsign
 unsigned long sh_h5mini_zlib_fallbacks(void);      /* chunks the built-in inflater refused and zlib decoded (expected: 0) */
 /* block-based mapping (sh_host.c): are_bounds_sane with its warnings on or off (1 / 0: sane / not) */
 int sh_bounds_sane(const size_t *low, const size_t *high, size_t nblock, size_t seqlen, int verbose);
+/* packs of candidates (sh_host.c; k_map_pack, sh_map_pack.h): the dynamic LDS a pack of ncell cells and ncand candidates takes -- two
+ * rows and a word per cell, ncand + 1 first cells -- under the limit sh_map.h sets for the mapping kernels (the same tokens there) */
+#define SH_MAP_LDS 65536
+size_t sh_map_pack_lds_bytes(size_t ncell, size_t ncand);
 /* squiggle matching (sh_host.c): the tables of decode.c:1055-1099 from the host's libm; tab holds 5 npos + 4 floats */
 void sh_squiggle_tables(const float *params, size_t npos, size_t ldp, float rate, float prob_back, float *tab, float pens[2]);
 /* dwell correction (sh_host.c): the scale from pos / state (n ints each, `stride` bytes apart), the prior's numerator of an event table, and

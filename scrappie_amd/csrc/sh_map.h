@@ -20,7 +20,8 @@
  *
  * Viterbi arithmetic is the reference's operation for operation ((p - stay_pen) + lp, strict > in the order stay, step,
  * skip, START -> 0; END: stay, then seq -> END), and the build has -ffp-contract=off: scores and paths are bit-identical.
- * Forward uses logsumexpf as util.h:162-164 with the accurate device expf / log1pf.
+ * Forward uses logsumexpf as util.h:162-164 with the accurate device expf / log1pf.  The unbanded cell is sh_map_cell, which
+ * k_map_pack (sh_map_pack.h: several candidates of one read in one workgroup) goes through as well.
  *
  * Traceback (unbanded Viterbi): a 2-bit move code per (block, position) -- 0 stay, 1 step, 2 skip, 3 from START -- packed 16
  * to a 32-bit word from two wave ballots and written as one 16-byte store per wave and block; W = 4 ceil(L / 64) words per
@@ -31,7 +32,7 @@
 #define SH_MAP_H
 
 #define SH_MAP_NTH 256
-#define SH_MAP_LDS 65536          /* dynamic LDS per workgroup at most (the default limit: no function attribute needed) */
+#define SH_MAP_LDS 65536          /* dynamic LDS per workgroup at most (the default limit: no function attribute needed); sh_internal.h repeats it for the host C */
 #define SH_MAP_MAX_SEQ 65536      /* longest sequence mapped (states); longer: NAN and an error */
 #define SH_MAP_BIG 1.e30f         /* decode.c:8 */
 
@@ -97,6 +98,29 @@ __device__ __forceinline__ unsigned sh_spread16(unsigned x) {
     return x;
 }
 
+/* One cell of the unbanded recursion (decode.c:1448-1478, :1580-1600), shared by k_map and k_map_pack (sh_map_pack.h): p the
+ * previous block's row, i the cell in it, le the cell's posterior entry, lps the stay entry.  pos: the cell's position in its
+ * sequence, of which only 0, 1 and "2 or more" matter: from 1 on it has a left neighbour (i - 1), from 2 on two of them (i - 2),
+ * and position 0 reads START at p[start].
+ * The reference's expressions in its order -- stay, step, skip, START -- with strict > (code: the move taken) or sh_lse. */
+template <bool VIT>
+__device__ __forceinline__ float sh_map_cell(const float *p, int i, int start, int pos, float le, float lps, float stay_pen, float skip_pen,
+                                             int &code) {
+    float v = (p[i] - stay_pen) + lps;
+    if (VIT) {
+        int c = 0;
+        if (pos >= 1) { const float st = p[i - 1] + le; if (st > v) { v = st; c = 1; } }
+        if (pos >= 2) { const float sk = (p[i - 2] - skip_pen) + le; if (sk > v) { v = sk; c = 2; } }
+        if (pos == 0) { const float fs = p[start] + le; if (fs > v) { v = fs; c = 3; } }
+        code = c;
+    } else {
+        if (pos >= 1) v = sh_lse(v, p[i - 1] + le);
+        if (pos >= 2) v = sh_lse(v, (p[i - 2] - skip_pen) + le);
+        if (pos == 0) v = sh_lse(v, p[start] + le);
+    }
+    return v;
+}
+
 /* LDS: the score rows and the codes in LDS (the launch holds only reads with scr < 0); else in device scratch.  The two
  * homes are separate instantiations: a pointer never selects between LDS and global memory at run time. */
 template <bool VIT, bool BAND, bool TILED, bool LDS>
@@ -144,16 +168,7 @@ __global__ __launch_bounds__(SH_MAP_NTH) void k_map(ShMapArgs a) {
                 float v;
                 if (!BAND) {
                     const float le = lp(sq[pos]);
-                    v = (p[pos] - stay_pen) + lps;
-                    if (VIT) {
-                        if (pos >= 1) { const float st = p[pos - 1] + le; if (st > v) { v = st; code = 1; } }
-                        if (pos >= 2) { const float sk = (p[pos - 2] - skip_pen) + le; if (sk > v) { v = sk; code = 2; } }
-                        if (pos == 0) { const float fs = p[START] + le; if (fs > v) { v = fs; code = 3; } }
-                    } else {
-                        if (pos >= 1) v = sh_lse(v, p[pos - 1] + le);
-                        if (pos >= 2) v = sh_lse(v, (p[pos - 2] - skip_pen) + le);
-                        if (pos == 0) v = sh_lse(v, p[START] + le);
-                    }
+                    v = sh_map_cell<VIT>(p, pos, START, pos, le, lps, stay_pen, skip_pen, code);
                 } else if (blk == 0) {           /* decode.c:1744-1769 */
                     v = c[pos];
                     if (pos <= 2) {
