@@ -547,6 +547,50 @@ long long scrappie_hip_map_crf_plan_scratch(const size_t *seqlen, const size_t *
 /* launches of each k_map_crf form in this process, all engines together: index (viterbi ? 4 : 0) | (tiled ? 2 : 0) | (scratch ? 1 : 0) */
 void scrappie_hip_map_crf_form_counts(uint64_t forms[8]);
 
+/* Reads of a flip-flop (CRF) model mapped INTO a longer sequence (k_map_crf_local, sh_map_crf_local.h; sh_eng_map_crf_local.inc): where
+ * in this sequence does the read lie, with what score and along what path.  Cells, transitions and the block recursion are those
+ * above; the path may begin in any cell (entry 0: S[p] = 0 for p = 0 .. seqlen, B[p] = 0 for p = 1 .. seqlen, as decode_crf starts
+ * every state at 0) and end in any cell (Viterbi: the maximum over all cells of entry nblock, p ascending and B[p] before S[p], the
+ * first maximum wins; forward: logsumexpf over them).  The read spells seq[first, last): last is the end cell's p, first the start
+ * cell's p, minus one where entry 0 is a base; path[t], t = 0 .. nblock, is the index in seq of the last base emitted through
+ * entry t, first - 1 while there is none.  The all-stay path is always admissible: there is no "no path" here.  Mapping a read to
+ * flank + its own call (the bases of all nblock + 1 entries) + flank returns decode_crf's score bit for bit, and never less than
+ * map_crf_to_sequence_viterbi gives for the same pair.
+ * The sequence is cut into windows of one workgroup each (scrappie_hip_map_crf_local_plan); the Viterbi score has the same bits for
+ * every cut.  seqlen has no limit from the device's LDS; it is bounded by index width alone: 2^30 bases.
+ *
+ * scrappie_hip_map_local_batch: reads[i] (prepared as for scrappie_hip_map_batch) into targets[i] = {seq, seqlen}, base codes 0..3;
+ * several reads may point at the same seq (with the same seqlen), which is then checked and uploaded once per launch group.  A
+ * first pass scores every window of every read of a launch group in one launch; with viterbi and want_path a second launch runs the
+ * traceback on each read's best window alone, while the transitions are still resident.  out[i]: score (NAN where read or sequence
+ * cannot be mapped, with the first such reason as the error text; its neighbours are untouched), nblock, last (Viterbi; 0 for
+ * forward), first (known from the traceback only: (size_t)-1 without viterbi and want_path), path (nblock + 1 entries, malloc'd;
+ * scrappie_hip_free_map_local_results).  A transducer model is refused for the
+ * whole call (-1).  scrappie_hip_map_timing covers the call ([1] k_map_crf_local, [2] walk + results).
+ *
+ * The per-read symbols run on the process-default engine; NULL / NAN conventions as map_crf_to_sequence_*; first, last and path may
+ * each be NULL, and a call that wants neither first nor path runs the first pass alone. */
+typedef struct { const int *seq; size_t seqlen; } scrappie_hip_map_local_target;
+typedef struct { float score; size_t nblock, first, last; int32_t *path; } scrappie_hip_map_local_result;
+int scrappie_hip_map_local_batch(scrappie_hip_engine *e, int model, const raw_table *reads, const scrappie_hip_map_local_target *targets,
+                                 size_t n, const scrappie_hip_params *p, int viterbi, int want_path, scrappie_hip_map_local_result *out);
+void scrappie_hip_free_map_local_results(scrappie_hip_map_local_result *r, size_t n);
+float map_crf_to_reference_viterbi(const_scrappie_matrix trans, int const *seq, size_t seqlen, size_t *first, size_t *last, int *path);
+float map_crf_to_reference_forward(const_scrappie_matrix trans, int const *seq, size_t seqlen);
+/* Host only: the cut of seqlen + 1 cells into windows for a read of nblock blocks.  stride > 0: cells per window's owned starts; 0:
+ * one window; < 0: the default (the debug option "map_crf_local_stride" takes the same values) -- a window of stride + nblock =
+ * 2034 cells (four such workgroups are resident per compute unit) while that leaves stride >= nblock; beyond, the largest stride
+ * whose window keeps its rows in LDS (scrappie_hip_map_crf_local_max_cells); and nblock, rows in device scratch, where nblock + 1
+ * cells alone exceed that.  Window w owns the start cells [first[w], first[w] + own[w]) and holds ncell[w] cells from
+ * first[w]; home[w]: 0 LDS, 1 scratch at float offset scr_off[w] (-1 in LDS; 4 (ncell + 1) floats each) of *scr_floats in all.  Arrays
+ * may be NULL and hold cap entries.  Returns the number of windows; 0 where there is nothing to cut or seqlen exceeds 2^30. */
+long long scrappie_hip_map_crf_local_plan(size_t seqlen, size_t nblock, long stride, size_t cap, size_t *first, size_t *ncell, size_t *own,
+                                          int *home, long long *scr_off, long long *scr_floats);
+size_t scrappie_hip_map_crf_local_stride(size_t seqlen, size_t nblock, long stride);
+size_t scrappie_hip_map_crf_local_max_cells(void);
+/* launches of each k_map_crf_local form in this process, all engines together: index (viterbi ? 4 : 0) | (tiled ? 2 : 0) | (scratch ? 1 : 0) */
+void scrappie_hip_map_crf_local_form_counts(uint64_t forms[8]);
+
 /* Squiggle matching, batched (sh_eng_squig.inc): reads[i] (trimmed, normalised; mapped over [start, end)) against
  * targets[i], a predicted squiggle of npos columns of stride >= 3 floats (mean, log sd, dwell logit); out[i] belongs to
  * reads[i].  No network runs and no model is needed (the squiggles are an input here: scrappie_hip_squiggle_predict_batch

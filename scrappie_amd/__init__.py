@@ -61,6 +61,15 @@ class _MapResult(C.Structure):
     _fields_ = [("score", C.c_float), ("nblock", C.c_size_t), ("path", C.POINTER(C.c_int32))]
 
 
+class _MapLocalTarget(C.Structure):
+    _fields_ = [("seq", C.POINTER(C.c_int)), ("seqlen", C.c_size_t)]
+
+
+class _MapLocalResult(C.Structure):
+    _fields_ = [("score", C.c_float), ("nblock", C.c_size_t), ("first", C.c_size_t), ("last", C.c_size_t),
+                ("path", C.POINTER(C.c_int32))]
+
+
 class _MapCandidates(C.Structure):
     _fields_ = [("cand", C.POINTER(_MapTarget)), ("ncand", C.c_size_t)]
 
@@ -287,6 +296,23 @@ def lib():
     L.scrappie_hip_map_crf_plan_scratch.argtypes = [sp, sp, C.c_size_t, C.POINTER(C.c_longlong)]
     L.scrappie_hip_map_crf_form_counts.restype = None
     L.scrappie_hip_map_crf_form_counts.argtypes = [C.POINTER(C.c_uint64)]
+    L.map_crf_to_reference_viterbi.restype = C.c_float
+    L.map_crf_to_reference_viterbi.argtypes = [PM, ip, C.c_size_t, sp, sp, ip]
+    L.map_crf_to_reference_forward.restype = C.c_float
+    L.map_crf_to_reference_forward.argtypes = [PM, ip, C.c_size_t]
+    L.scrappie_hip_map_local_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(_RawTable), C.POINTER(_MapLocalTarget), C.c_size_t,
+                                               C.POINTER(Params), C.c_int, C.c_int, C.POINTER(_MapLocalResult)]
+    L.scrappie_hip_free_map_local_results.restype = None
+    L.scrappie_hip_free_map_local_results.argtypes = [C.POINTER(_MapLocalResult), C.c_size_t]
+    L.scrappie_hip_map_crf_local_plan.restype = C.c_longlong
+    L.scrappie_hip_map_crf_local_plan.argtypes = [C.c_size_t, C.c_size_t, C.c_long, C.c_size_t, sp, sp, sp, ip, C.POINTER(C.c_longlong),
+                                                  C.POINTER(C.c_longlong)]
+    L.scrappie_hip_map_crf_local_stride.restype = C.c_size_t
+    L.scrappie_hip_map_crf_local_stride.argtypes = [C.c_size_t, C.c_size_t, C.c_long]
+    L.scrappie_hip_map_crf_local_max_cells.restype = C.c_size_t
+    L.scrappie_hip_map_crf_local_max_cells.argtypes = []
+    L.scrappie_hip_map_crf_local_form_counts.restype = None
+    L.scrappie_hip_map_crf_local_form_counts.argtypes = [C.POINTER(C.c_uint64)]
     L.encode_bases_to_integers.restype = C.c_void_p
     L.encode_bases_to_integers.argtypes = [C.c_char_p, C.c_size_t, C.c_size_t]
     L.scrappie_hip_read_blocks.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
@@ -437,6 +463,42 @@ def map_crf_form_counts():
     q = (C.c_uint64 * 8)()
     lib().scrappie_hip_map_crf_form_counts(q)
     return {(bool(k & 4), bool(k & 2), bool(k & 1)): int(q[k]) for k in range(8)}
+
+
+def map_crf_local_form_counts():
+    """Launches of each k_map_crf_local form in this process so far (scrappie_hip_map_crf_local_form_counts):
+    {(viterbi, tiled, scratch): n}."""
+    q = (C.c_uint64 * 8)()
+    lib().scrappie_hip_map_crf_local_form_counts(q)
+    return {(bool(k & 4), bool(k & 2), bool(k & 1)): int(q[k]) for k in range(8)}
+
+
+def map_crf_local_max_cells():
+    """The most cells a window of k_map_crf_local keeps in LDS; a larger window keeps its rows in device scratch."""
+    return int(lib().scrappie_hip_map_crf_local_max_cells())
+
+
+def map_crf_local_plan(seq_len, nblock, stride=-1):
+    """The cut of the seq_len + 1 cells of a sequence into windows for a read of `nblock` blocks (host arithmetic, no device;
+    scrappie_hip_map_crf_local_plan).  `stride`: start cells per window, 0: one window, -1: the default.  Returns a dict of
+    arrays, one entry per window: first, ncell, own, home (0 LDS, 1 device scratch), scr_off (-1 in LDS), and scr_floats."""
+    Lb = lib()
+    nw = int(Lb.scrappie_hip_map_crf_local_plan(seq_len, nblock, int(stride), 0, None, None, None, None, None, None))
+    first, ncell, own = (np.zeros(nw, dtype=np.uintp) for _ in range(3))
+    home = np.zeros(nw, dtype=np.int32)
+    off = np.zeros(nw, dtype=np.longlong)
+    tot = C.c_longlong(0)
+    sp = C.POINTER(C.c_size_t)
+    Lb.scrappie_hip_map_crf_local_plan(seq_len, nblock, int(stride), nw, first.ctypes.data_as(sp), ncell.ctypes.data_as(sp), own.ctypes.data_as(sp),
+                                       home.ctypes.data_as(C.POINTER(C.c_int)), off.ctypes.data_as(C.POINTER(C.c_longlong)), C.byref(tot))
+    return dict(first=first, ncell=ncell, own=own, home=home, scr_off=off, scr_floats=int(tot.value))
+
+
+def set_map_crf_local_stride(value):
+    """The debug option "map_crf_local_stride" of the process-default engine, the one `map_trans_to_reference` runs on: start
+    cells per window, 0: one window, -1: the default.  (An `Engine` has `debug_option`.)"""
+    if lib().scrappie_hip_debug_option(None, b"map_crf_local_stride", int(value)) != 0:
+        raise RuntimeError("debug_option: " + last_error())
 
 
 def map_pack_form_counts():
@@ -1022,6 +1084,36 @@ def map_trans_to_sequence(trans, sequence, viterbi=False, path=False, bands=None
     if np.isnan(score):
         raise RuntimeError('An unknown error occurred during alignment: ' + last_error())
     return score, path_data
+
+
+def map_trans_to_reference(trans, sequence, viterbi=False, path=False):
+    """Where in `sequence` does this read lie?  A read's transitions under a flip-flop (CRF) model (a `ScrappyMatrix` of 25
+    rows, as `calc_post(rt, model='rnnrf_r94')` gives) mapped INTO a longer base sequence: the paths of `map_trans_to_sequence`
+    that begin and end anywhere in it; the DP runs on the GPU, one workgroup per window of the sequence (k_map_crf_local).
+    Returns (score, first, last, path): the read spells sequence[first:last]; path[t], t = 0 .. nblock, is the index in
+    `sequence` of the last base emitted through entry t (first - 1 while none).  Forward: (score, None, None, None); Viterbi
+    without `path`: (score, None, last, None) -- the start is known only from the traceback."""
+    if path and not viterbi:
+        raise ValueError('Cannot calulate path with `viterbi==False`.')
+    if not isinstance(trans, ScrappyMatrix):
+        raise TypeError('`trans` should be a ScrappyMatrix.')
+    nblock, nstate = trans.shape
+    if nstate != 25:
+        raise ValueError('`trans` should hold the 25 transitions of a flip-flop (CRF) model per block.')
+    codes = encode_bases(sequence, 1).astype(np.int32)
+    p_seq = codes.ctypes.data_as(C.POINTER(C.c_int))
+    if not viterbi:
+        score = lib().map_crf_to_reference_forward(trans.data(), p_seq, len(codes))
+        if np.isnan(score):
+            raise RuntimeError('An unknown error occurred during alignment: ' + last_error())
+        return score, None, None, None
+    first, last = C.c_size_t(0), C.c_size_t(0)
+    path_data = np.zeros(nblock + 1, dtype=np.int32) if path else None
+    score = lib().map_crf_to_reference_viterbi(trans.data(), p_seq, len(codes), C.byref(first) if path else None, C.byref(last),
+                                               path_data.ctypes.data_as(C.POINTER(C.c_int)) if path else None)
+    if np.isnan(score):
+        raise RuntimeError('An unknown error occurred during alignment: ' + last_error())
+    return score, (int(first.value) if path else None), int(last.value), path_data
 
 
 _squiggle_fn_ = {
@@ -1680,6 +1772,51 @@ class Engine(object):
             sc = np.ctypeslib.as_array(r.score, shape=(r.ncand,)).copy() if r.ncand else np.zeros(0, dtype=np.float32)
             res.append((sc, int(r.best), np.ctypeslib.as_array(r.path, shape=(r.nblock,)).copy() if r.path else None))
         lib().scrappie_hip_free_map_multi_results(out, n)
+        return res
+
+    def map_to_reference(self, signals, references, model='rnnrf_r94', viterbi=True, path=False, min_prob=1e-5, tempW=1.0, tempb=1.0):
+        """Where in its reference does each read lie?  Each read (trimmed, normalised float32 signal) of a flip-flop (CRF)
+        model mapped INTO a longer base sequence, batched (scrappie_hip_map_local_batch): the network runs as for
+        `posterior`, the transitions stay on the device, every window of every reference is one workgroup of
+        k_map_crf_local.  `references`: one string for all reads (encoded and uploaded once), or one per read.  Returns
+        [(score, first, last, path)] in input order as `map_trans_to_reference` gives them; score NaN (and None) where a
+        read or its reference cannot be mapped."""
+        n = len(signals)
+        if path and not viterbi:
+            raise ValueError('Cannot calulate path with `viterbi==False`.')
+        if isinstance(references, str):
+            references = [references] * n
+        elif len(references) != n:
+            raise ValueError("one reference for all signals, or one per signal")
+        h = self._models[model]
+        rts, keep = _raw_tables(signals)
+        tgs = (_MapLocalTarget * max(n, 1))()
+        enc = {}
+        for i, sq in enumerate(references):
+            if id(sq) not in enc:
+                try:
+                    enc[id(sq)] = np.ascontiguousarray(encode_bases(sq, 1), dtype=np.int32)
+                except ValueError:
+                    enc[id(sq)] = np.zeros(0, dtype=np.int32)      # mapped to NaN by the library (empty sequence)
+            codes = enc[id(sq)]
+            tgs[i].seq = codes.ctypes.data_as(C.POINTER(C.c_int))
+            tgs[i].seqlen = len(codes)
+        keep.append(enc)
+        p = self.default_params(min_prob=min_prob, tempW=tempW, tempb=tempb)
+        out = (_MapLocalResult * max(n, 1))()
+        if lib().scrappie_hip_map_local_batch(self._h, h, rts, tgs, n, C.byref(p), 1 if viterbi else 0, 1 if path else 0, out) != 0:
+            raise RuntimeError("map_local_batch: " + last_error())
+        res = []
+        for r in (out[i] for i in range(n)):
+            sc = float(r.score)
+            if np.isnan(sc):
+                res.append((sc, None, None, None))
+            elif not viterbi:
+                res.append((sc, None, None, None))
+            else:
+                pth = np.ctypeslib.as_array(r.path, shape=(r.nblock + 1,)).copy() if r.path else None
+                res.append((sc, int(r.first) if pth is not None else None, int(r.last), pth))
+        lib().scrappie_hip_free_map_local_results(out, n)
         return res
 
     def _timing(self, fn, names):

@@ -10,6 +10,10 @@
  * --all-records: every record of a pair's FASTA is a candidate for the pair's read, not just the first -- all pairs in ONE
  * scrappie_hip_map_multi_batch call (the network once per read, the candidates packed into workgroups); per pair a table of the
  * records' scores and then the usual header and path of the best one.  Without the option nothing changes.
+ * --inside (flip-flop models): the read lies somewhere INSIDE the sequence -- an amplicon, a plasmid, a chromosome arm.  All pairs
+ * in ONE scrappie_hip_map_local_batch call (k_map_crf_local: one workgroup per window of the sequence); the usual header line with
+ * `bases first..last` added -- the read spells the record's bases [first, last) -- and nblock + 1 records whose pos is in the
+ * record's coordinates (first - 1 while no base is emitted).  Without the option nothing changes.
  */
 #define _GNU_SOURCE
 #include <getopt.h>
@@ -46,7 +50,11 @@ static void seqmappy_usage(FILE *fh) {
           "                             `# fast5 to fasta -- N records`, a table record / name / score / per_block (scores\n"
           "                             negated, as in the header line; raw scores: records of different lengths are compared\n"
           "                             as they are), then the header line and the path of the best record, named fasta:name.\n"
-          "                             Transducer models only.\n", fh);
+          "                             Transducer models only.\n"
+          "      --inside               The read lies somewhere inside the sequence (a reference longer than the read): the\n"
+          "                             best local placement of the whole read.  `bases first..last` is added to the header\n"
+          "                             line -- the read spells bases [first, last) of the record -- and pos is in the\n"
+          "                             record's coordinates, first - 1 while none.  Flip-flop (CRF) models only.\n", fh);
 }
 
 /* --all-records: pair i's read against every record of its FASTA, all pairs in one scrappie_hip_map_multi_batch call */
@@ -104,14 +112,56 @@ static int seqmappy_all_records(scrappie_hip_engine *e, int h, int klen, const s
     return rc;
 }
 
+/* --inside: pair i's read into the first record of its FASTA, all pairs in one scrappie_hip_map_local_batch call */
+static int seqmappy_inside(scrappie_hip_engine *e, int h, const scrappie_hip_params *p, char **fasta, size_t npair, FILE *out,
+                           int trim_start, int trim_end, int varseg_chunk, float varseg_thresh) {
+    raw_table *rts = calloc(npair, sizeof *rts);
+    scrappie_hip_map_local_target *tg = calloc(npair, sizeof *tg);
+    scrappie_hip_map_local_result *res = calloc(npair, sizeof *res);
+    int **codes = calloc(npair, sizeof *codes);
+    int rc = EXIT_SUCCESS;
+    for (size_t i = 0; i < npair; i++) {
+        const char *fa = fasta[2 * i], *f5 = fasta[2 * i + 1];
+        struct cli_fasta *rec = NULL;       /* the first record of the file */
+        size_t nrec = 0;
+        if (cli_read_fasta(fa, &rec, &nrec, 1) || nrec == 0 || !rec[0].seq || rec[0].n == 0) { fprintf(stderr, "scrappie: Failed to open \"%s\" for input.\n", fa); cli_free_fasta(rec, nrec); rc = EXIT_FAILURE; continue; }
+        const size_t n = rec[0].n;
+        codes[i] = encode_bases_to_integers(rec[0].seq, n, 1);
+        cli_free_fasta(rec, nrec);
+        if (!codes[i]) { fprintf(stderr, "scrappie: cannot encode the sequence of \"%s\": %s\n", fa, scrappie_hip_last_error()); rc = EXIT_FAILURE; continue; }
+        tg[i].seq = codes[i]; tg[i].seqlen = n;
+        rts[i] = cli_load_read(f5, trim_start, trim_end, varseg_chunk, varseg_thresh, 1);
+        if (!rts[i].raw) { fprintf(stderr, "scrappie: Failed to open \"%s\" for input and trim signal.\n", f5); rc = EXIT_FAILURE; continue; }
+    }
+    if (scrappie_hip_map_local_batch(e, h, rts, tg, npair, p, 1, 1, res) != 0) {
+        fprintf(stderr, "scrappie: %s\n", scrappie_hip_last_error());
+        rc = EXIT_FAILURE;
+    } else {
+        for (size_t i = 0; i < npair; i++) {
+            if (!rts[i].raw || !codes[i]) continue;
+            if (!res[i].path) { fprintf(stderr, "scrappie: Failed to map \"%s\" to \"%s\"\n", fasta[2 * i + 1], fasta[2 * i]); rc = EXIT_FAILURE; continue; }
+            const float score = res[i].score;
+            const size_t nblock = res[i].nblock;
+            fprintf(out, "# %s to %s -- score %f over %zu blocks (%f per block) bases %zu..%zu\n", fasta[2 * i + 1], fasta[2 * i], -score, nblock, -score / nblock,
+                    res[i].first, res[i].last);
+            fprintf(out, "block\tpos\n");
+            for (size_t b = 0; b <= nblock; b++) fprintf(out, "%zu\t%d\n", b, res[i].path[b]);
+        }
+    }
+    scrappie_hip_free_map_local_results(res, npair);
+    for (size_t i = 0; i < npair; i++) { free(codes[i]); free(rts[i].raw); free(rts[i].uuid); }
+    free(codes); free(res); free(tg); free(rts);
+    return rc;
+}
+
 int main_seqmappy(int argc, char **argv) {
-    enum { O_SEG = 256, O_T1, O_T2, O_LIC, O_MODEL, O_MFILE, O_DEV, O_ALL };
+    enum { O_SEG = 256, O_T1, O_T2, O_LIC, O_MODEL, O_MFILE, O_DEV, O_ALL, O_INSIDE };
     static const struct option lo[] = {
         {"localpen", 1, 0, 'l'}, {"min_prob", 1, 0, 'm'}, {"output", 1, 0, 'o'}, {"prefix", 1, 0, 'p'},
         {"segmentation", 1, 0, O_SEG}, {"skip", 1, 0, 's'}, {"stay", 1, 0, 'y'}, {"trim", 1, 0, 't'},
         {"temperature1", 1, 0, O_T1}, {"temperature2", 1, 0, O_T2}, {"licence", 0, 0, O_LIC}, {"license", 0, 0, O_LIC},
-        {"model", 1, 0, O_MODEL}, {"model-file", 1, 0, O_MFILE}, {"device", 1, 0, O_DEV}, {"all-records", 0, 0, O_ALL}, {"help", 0, 0, '?'}, {0, 0, 0, 0}};
-    int all_records = 0;
+        {"model", 1, 0, O_MODEL}, {"model-file", 1, 0, O_MFILE}, {"device", 1, 0, O_DEV}, {"all-records", 0, 0, O_ALL}, {"inside", 0, 0, O_INSIDE}, {"help", 0, 0, '?'}, {0, 0, 0, 0}};
+    int all_records = 0, inside = 0;
     /* defaults: scrappie_seqmappy.c:62-78 */
     scrappie_hip_params p = scrappie_hip_default_params();
     p.local_pen = 4.0f; p.min_prob = 1e-5f; p.stay_pen = 0.0f; p.skip_pen = 0.0f; p.tempW = 1.0f; p.tempb = 1.0f;
@@ -144,6 +194,7 @@ int main_seqmappy(int argc, char **argv) {
         case O_MFILE: model_file = optarg; break;
         case O_DEV: device = atoi(optarg); break;
         case O_ALL: all_records = 1; break;
+        case O_INSIDE: inside = 1; break;
         default: seqmappy_usage(stderr); return EXIT_FAILURE;
         }
     }
@@ -151,6 +202,11 @@ int main_seqmappy(int argc, char **argv) {
     if (nargs <= 0) { seqmappy_usage(stderr); return EXIT_FAILURE; }
     if (nargs % 2) { fprintf(stderr, "scrappie: fast5 file is a required argument\n"); return EXIT_FAILURE; }    /* scrappie_seqmappy.c:153 */
     const size_t npair = (size_t)nargs / 2;
+    if (inside && all_records) { fprintf(stderr, "scrappie: --inside maps a read into the first record of its fasta; it cannot be combined with --all-records\n"); return EXIT_FAILURE; }
+    if (inside && get_raw_model(model) != SCRAPPIE_MODEL_RNNRF_R9_4) {
+        fprintf(stderr, "scrappie: --inside maps flip-flop (CRF) models only (--model=rnnrf_r94); \"%s\" is a transducer model\n", model);
+        return EXIT_FAILURE;
+    }
     if (all_records && get_raw_model(model) == SCRAPPIE_MODEL_RNNRF_R9_4) {
         fprintf(stderr, "scrappie: --all-records maps transducer models only; \"%s\" is a flip-flop (CRF) model\n", model);
         return EXIT_FAILURE;
@@ -164,6 +220,14 @@ int main_seqmappy(int argc, char **argv) {
     const int crf = nstate == 25;        /* a flip-flop model (rnnrf_r94): bases as states of length 1, a path of nblock + 1 entries */
     if (crf) klen = 1;
     else for (int nk = nstate - 1; nk > 1 && nk % 4 == 0; nk /= 4) klen++;
+    if (inside) {
+        int rc = EXIT_FAILURE;
+        if (!crf) fprintf(stderr, "scrappie: --inside maps flip-flop (CRF) models only; \"%s\" is a transducer model\n", model);
+        else rc = seqmappy_inside(e, h, &p, fasta, npair, out, trim_start, trim_end, varseg_chunk, varseg_thresh);
+        if (out != stdout) fclose(out);
+        scrappie_hip_engine_destroy(e);
+        return rc;
+    }
     if (all_records) {
         int rc = EXIT_FAILURE;
         if (crf) fprintf(stderr, "scrappie: --all-records maps transducer models only; \"%s\" is a flip-flop (CRF) model\n", model);

@@ -779,6 +779,64 @@ int scrappie_hip_map_crf_diagonal_band(size_t nblock, size_t seqlen, size_t half
     return 0;
 }
 
+/* Windows of the sequence-local CRF mapping (k_map_crf_local, sh_map_crf_local.h).  A window of ncell cells keeps two columns of
+ * transitions, four rows of ncell + 1 floats and ncell codes in LDS. */
+size_t sh_map_crf_local_lds_bytes(size_t ncell) { return (64 + 4 * (ncell + 1) + ncell) * 4; }
+
+/* the most cells a window keeps in LDS (the bytes are linear in ncell) */
+size_t scrappie_hip_map_crf_local_max_cells(void) {
+    const size_t per = sh_map_crf_local_lds_bytes(1) - sh_map_crf_local_lds_bytes(0);
+    return (SH_MAP_LDS - sh_map_crf_local_lds_bytes(0)) / per;
+}
+
+/* The stride in cells a sequence of seqlen bases and a read of nblock blocks are cut with.  stride > 0: that many cells; 0: one
+ * window; < 0: the default -- a window (stride + nblock cells) of SH_MAP_CRF_LOCAL_CELLS cells, of which four are resident per
+ * compute unit, while the window owns at least half of its cells (stride >= nblock); the largest stride whose window is
+ * LDS-resident beyond; and nblock, with the rows in device scratch, where nblock + 1 cells alone exceed the LDS home
+ * (profiles/map_crf_local_rate.txt decided between them).  Never more than the seqlen + 1 cells there are. */
+size_t scrappie_hip_map_crf_local_stride(size_t seqlen, size_t nblock, long stride) {
+    const size_t cells = seqlen + 1, maxc = scrappie_hip_map_crf_local_max_cells();
+    size_t s;
+    if (stride > 0) s = (size_t)stride;
+    else if (stride == 0) s = cells;
+    else if (nblock + 1 > maxc) s = nblock;
+    else if (2 * nblock <= SH_MAP_CRF_LOCAL_CELLS && SH_MAP_CRF_LOCAL_CELLS <= maxc) s = SH_MAP_CRF_LOCAL_CELLS - nblock;
+    else s = maxc - nblock;
+    if (s == 0) s = 1;
+    return s < cells ? s : cells;
+}
+
+/* The cut: window w owns the start cells [w s, min((w + 1) s, seqlen + 1)) and holds the cells [w s, min(w s + s - 1 + nblock,
+ * seqlen)] -- first[w], own[w] and ncell[w]; home[w]: 0 rows and codes in LDS, 1 rows in device scratch, at float offset
+ * scr_off[w] (-1 in LDS) of *scr_floats floats in all, 4 (ncell + 1) per window: whole 16-byte pieces.  Every array may be NULL;
+ * those given hold cap entries, and only the first cap windows are written.  Returns the number of windows, 0 on an empty
+ * sequence, no blocks or a sequence beyond 2^30 bases (a cell and its kind share an int32). */
+long long scrappie_hip_map_crf_local_plan(size_t seqlen, size_t nblock, long stride, size_t cap, size_t *first, size_t *ncell, size_t *own,
+                                          int *home, long long *scr_off, long long *scr_floats) {
+    if (scr_floats) *scr_floats = 0;
+    if (seqlen == 0 || nblock == 0 || seqlen > ((size_t)1 << 30) || nblock > ((size_t)1 << 30)) return 0;
+    const size_t cells = seqlen + 1, s = scrappie_hip_map_crf_local_stride(seqlen, nblock, stride);
+    const size_t nwin = (cells + s - 1) / s;
+    long long scr = 0;
+    for (size_t w = 0; w < nwin; w++) {
+        const size_t c0 = w * s;
+        const size_t left = cells - c0;                         /* cells from c0 to the end */
+        const size_t reach = s - 1 + nblock + 1;                /* cells a path that starts in the window can be in */
+        const size_t nc = reach < left ? reach : left;
+        const int scratch = sh_map_crf_local_lds_bytes(nc) > SH_MAP_LDS;
+        if (w < cap) {
+            if (first) first[w] = c0;
+            if (ncell) ncell[w] = nc;
+            if (own) own[w] = s < left ? s : left;
+            if (home) home[w] = scratch;
+            if (scr_off) scr_off[w] = scratch ? scr : -1;
+        }
+        if (scratch) scr += (long long)(4 * (nc + 1));
+    }
+    if (scr_floats) *scr_floats = scr;
+    return (long long)nwin;
+}
+
 /* the library defines it (scrappie_hip.hip); weak, so that this file also links into the host-only builds of the tests */
 void sh_set_error(const char *fmt, ...) __attribute__((weak, format(printf, 1, 2)));
 #define SH_ERR(...) do { if (sh_set_error) sh_set_error(__VA_ARGS__); } while (0)
