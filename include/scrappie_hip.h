@@ -591,6 +591,49 @@ size_t scrappie_hip_map_crf_local_max_cells(void);
 /* launches of each k_map_crf_local form in this process, all engines together: index (viterbi ? 4 : 0) | (tiled ? 2 : 0) | (scratch ? 1 : 0) */
 void scrappie_hip_map_crf_local_form_counts(uint64_t forms[8]);
 
+/* Short sequences searched INSIDE reads of a flip-flop (CRF) model (k_crf_find, sh_crf_find.h; sh_eng_crf_find.inc): does this
+ * barcode, adapter, primer or marker occur somewhere in the read, where, and which of K such motifs fits best.  Viterbi only.  A
+ * path (nblock + 1 entries over A C G T stay, as decode_crf's) is admissible for a motif m[0..L) when it has entries begin <= end,
+ * both bases, such that the non-stay entries in [begin, end] are exactly m in order; the entries before begin and behind end are
+ * free.  The score is decode_crf's sum over the best such path, so it covers the whole read: scores of motifs of different
+ * lengths compare as they are, and score - call_score <= 0 is a log-odds against the read's own call (call_score: decode_crf's
+ * score, bit for bit).  score == call_score in bits where the motif is a run of consecutive bases of the read's call, and score is
+ * never below map_crf_to_sequence_viterbi's for the same pair.  begin and end are entries of the path, 0 .. nblock (entry t lies
+ * between blocks t - 1 and t: sample t * stride of the trimmed signal).  There is no forward form: a path whose call holds the
+ * motif twice has several decompositions, and a sum would count it more than once.
+ * The motifs of a read are packed end to end into workgroups (scrappie_hip_crf_find_plan) behind the read's own five cells; a
+ * motif's score does not depend on its neighbours or on the pack size.
+ *
+ * scrappie_hip_find_batch: reads[i] (prepared as for scrappie_hip_map_batch) against motifs[i] = {cand, ncand}, base codes 0..3 in
+ * cand[k].seq; several reads may point at the same cand array, which is then checked, packed and uploaded once per launch.  out[i]:
+ * score, begin, end (malloc'd, nmotif entries each; begin and end NULL without want_pos; NAN and -1 where a motif cannot be
+ * searched: empty, not bases, banded (poslow / poshigh set), "too long for k_crf_find" -- more than
+ * scrappie_hip_crf_find_max_cells() - 9 bases; long sequences are map_to_sequence's and map_to_reference's job -- or longer than the
+ * read's nblock + 1 entries; its neighbours are scored), call_score, best (the highest finite score, the lowest index on a tie,
+ * -1: none) and nblock.  A read that cannot run (too short, out of the operand range, over the launch budget) gets every score NAN
+ * and best -1, the other reads untouched; the first such reason is the error text.  A transducer model: -1 with a text that
+ * names it.  Locks, parameters and the cut into launch groups as scrappie_hip_map_batch; all packs of all reads of a launch group
+ * go in one launch; scrappie_hip_map_timing covers the call ([1] k_crf_find, [2] results).
+ *
+ * find_crf_sequences_viterbi: the same on a host matrix (as nanonet_rnnrf_r94_transitions returns it) and the process-default
+ * engine; score[k] for motif[k], begin and end may be NULL (then positions are not carried), call_score may be NULL.  0, or -1
+ * with the reason; 0 with an error text where some motif got NAN. */
+typedef struct { float *score; int32_t *begin, *end; size_t nmotif; float call_score; int best; size_t nblock; } scrappie_hip_find_result;
+int scrappie_hip_find_batch(scrappie_hip_engine *e, int model, const raw_table *reads, const scrappie_hip_map_candidates *motifs, size_t n,
+                            const scrappie_hip_params *p, int want_pos, scrappie_hip_find_result *out);
+void scrappie_hip_free_find_results(scrappie_hip_find_result *r, size_t n);
+int find_crf_sequences_viterbi(const_scrappie_matrix trans, const scrappie_hip_map_target *motif, size_t nmotif, float *score, int32_t *begin,
+                               int32_t *end, float *call_score);
+/* Host only: motifs of seqlen[k] bases into packs of at most pack_cells cells (the debug option "crf_find_cells" sets it for an
+ * engine, -1: the default of 512; never more than scrappie_hip_crf_find_max_cells(), what the LDS holds), in input order.  A pack
+ * begins with the read's five cells, a motif of L bases takes L + 4 behind them; a pack is closed when the next motif would take it
+ * past pack_cells.  pack[k], cell[k]: the motif's pack and its first cell there; -1 for an empty motif and one whose L + 9 cells
+ * exceed the maximum.  Returns the number of packs. */
+long scrappie_hip_crf_find_plan(const size_t *seqlen, size_t nmotif, size_t pack_cells, int *pack, long long *cell);
+size_t scrappie_hip_crf_find_max_cells(void);
+/* launches of each k_crf_find form in this process, all engines together: index (positions ? 2 : 0) | (tiled ? 1 : 0) */
+void scrappie_hip_crf_find_form_counts(uint64_t forms[4]);
+
 /* Squiggle matching, batched (sh_eng_squig.inc): reads[i] (trimmed, normalised; mapped over [start, end)) against
  * targets[i], a predicted squiggle of npos columns of stride >= 3 floats (mean, log sd, dwell logit); out[i] belongs to
  * reads[i].  No network runs and no model is needed (the squiggles are an input here: scrappie_hip_squiggle_predict_batch

@@ -70,6 +70,11 @@ class _MapLocalResult(C.Structure):
                 ("path", C.POINTER(C.c_int32))]
 
 
+class _FindResult(C.Structure):
+    _fields_ = [("score", C.POINTER(C.c_float)), ("begin", C.POINTER(C.c_int32)), ("end", C.POINTER(C.c_int32)),
+                ("nmotif", C.c_size_t), ("call_score", C.c_float), ("best", C.c_int), ("nblock", C.c_size_t)]
+
+
 class _MapCandidates(C.Structure):
     _fields_ = [("cand", C.POINTER(_MapTarget)), ("ncand", C.c_size_t)]
 
@@ -313,6 +318,17 @@ def lib():
     L.scrappie_hip_map_crf_local_max_cells.argtypes = []
     L.scrappie_hip_map_crf_local_form_counts.restype = None
     L.scrappie_hip_map_crf_local_form_counts.argtypes = [C.POINTER(C.c_uint64)]
+    L.scrappie_hip_find_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(_RawTable), C.POINTER(_MapCandidates), C.c_size_t,
+                                          C.POINTER(Params), C.c_int, C.POINTER(_FindResult)]
+    L.scrappie_hip_free_find_results.restype = None
+    L.scrappie_hip_free_find_results.argtypes = [C.POINTER(_FindResult), C.c_size_t]
+    L.find_crf_sequences_viterbi.argtypes = [PM, C.POINTER(_MapTarget), C.c_size_t, fp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), fp]
+    L.scrappie_hip_crf_find_plan.restype = C.c_long
+    L.scrappie_hip_crf_find_plan.argtypes = [sp, C.c_size_t, C.c_size_t, ip, C.POINTER(C.c_longlong)]
+    L.scrappie_hip_crf_find_max_cells.restype = C.c_size_t
+    L.scrappie_hip_crf_find_max_cells.argtypes = []
+    L.scrappie_hip_crf_find_form_counts.restype = None
+    L.scrappie_hip_crf_find_form_counts.argtypes = [C.POINTER(C.c_uint64)]
     L.encode_bases_to_integers.restype = C.c_void_p
     L.encode_bases_to_integers.argtypes = [C.c_char_p, C.c_size_t, C.c_size_t]
     L.scrappie_hip_read_blocks.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
@@ -498,6 +514,38 @@ def set_map_crf_local_stride(value):
     """The debug option "map_crf_local_stride" of the process-default engine, the one `map_trans_to_reference` runs on: start
     cells per window, 0: one window, -1: the default.  (An `Engine` has `debug_option`.)"""
     if lib().scrappie_hip_debug_option(None, b"map_crf_local_stride", int(value)) != 0:
+        raise RuntimeError("debug_option: " + last_error())
+
+
+def crf_find_form_counts():
+    """Launches of each k_crf_find form in this process so far (scrappie_hip_crf_find_form_counts): {(positions, tiled): n}."""
+    q = (C.c_uint64 * 4)()
+    lib().scrappie_hip_crf_find_form_counts(q)
+    return {(bool(k & 2), bool(k & 1)): int(q[k]) for k in range(4)}
+
+
+def crf_find_max_cells():
+    """The most cells a pack of k_crf_find holds, the read's five included; a motif of L bases takes L + 4, so the longest
+    motif that can be searched has crf_find_max_cells() - 9 bases."""
+    return int(lib().scrappie_hip_crf_find_max_cells())
+
+
+def crf_find_plan(lengths, pack_cells=512):
+    """Motifs of `lengths` bases into packs of at most `pack_cells` cells, in input order (host arithmetic, no device;
+    scrappie_hip_crf_find_plan).  Returns (npack, pack, cell): per motif its pack and its first cell there, -1 where the motif
+    is empty or too long for k_crf_find."""
+    ln = np.ascontiguousarray(lengths, dtype=np.uintp)
+    pack = np.full(max(len(ln), 1), -1, dtype=np.int32)
+    cell = np.full(max(len(ln), 1), -1, dtype=np.longlong)
+    npack = int(lib().scrappie_hip_crf_find_plan(ln.ctypes.data_as(C.POINTER(C.c_size_t)), len(ln), int(pack_cells),
+                                                 pack.ctypes.data_as(C.POINTER(C.c_int)), cell.ctypes.data_as(C.POINTER(C.c_longlong))))
+    return npack, pack[:len(ln)], cell[:len(ln)]
+
+
+def set_crf_find_cells(value):
+    """The debug option "crf_find_cells" of the process-default engine, the one `find_in_trans` runs on: cells per pack of
+    motifs, -1: the default.  (An `Engine` has `debug_option`.)"""
+    if lib().scrappie_hip_debug_option(None, b"crf_find_cells", int(value)) != 0:
         raise RuntimeError("debug_option: " + last_error())
 
 
@@ -1114,6 +1162,63 @@ def map_trans_to_reference(trans, sequence, viterbi=False, path=False):
     if np.isnan(score):
         raise RuntimeError('An unknown error occurred during alignment: ' + last_error())
     return score, (int(first.value) if path else None), int(last.value), path_data
+
+
+def _motif_targets(motifs, strict):
+    """The ctypes scrappie_hip_map_target array of `motifs` (base strings, or arrays of base codes 0..3) and what keeps its memory
+    alive.  strict: an empty motif or a base outside ACGT raises ValueError; otherwise it becomes an empty motif, which the
+    library answers with NaN."""
+    tgs = (_MapTarget * max(len(motifs), 1))()
+    keep = []
+    for i, sq in enumerate(motifs):
+        try:
+            if isinstance(sq, str):
+                if len(sq) == 0:
+                    raise ValueError("an empty motif")
+                codes = np.ascontiguousarray(encode_bases(sq, 1), dtype=np.int32)
+            else:
+                codes = np.ascontiguousarray(sq, dtype=np.int32)
+                if len(codes) == 0 or codes.min() < 0 or codes.max() > 3:
+                    raise ValueError("a motif holds base codes 0..3 and at least one of them")
+        except ValueError:
+            if strict:
+                raise
+            codes = np.zeros(0, dtype=np.int32)
+        keep.append(codes)
+        tgs[i].seq = codes.ctypes.data_as(C.POINTER(C.c_int))
+        tgs[i].seqlen = len(codes)
+    return tgs, keep
+
+
+def find_in_trans(trans, motifs, positions=True):
+    """Do these short sequences occur INSIDE this read?  A read's transitions under a flip-flop (CRF) model (a `ScrappyMatrix` of
+    25 rows, as `calc_post(rt, model='rnnrf_r94')` gives) searched for each of `motifs` (base strings -- a barcode, an adapter,
+    a primer): the best path of the whole read whose bases between two entries `begin` <= `end` spell the motif exactly, the
+    entries before and behind them free; Viterbi, on the GPU, the motifs packed into workgroups (k_crf_find).  Returns
+    (scores, call_score, begins, ends): float32 scores, NaN where a motif cannot be searched (longer than the read's nblock + 1
+    entries, or than k_crf_find holds: `last_error()` says which); call_score, decode_crf's score of the read, so that
+    scores - call_score <= 0 are log-odds against the read's own call, 0 where the motif is a run of the call's bases; begins and
+    ends (int32, -1 beside a NaN; None without `positions`) are entries of the path, 0 .. nblock: entry t lies at sample
+    t * stride of the signal the transitions were computed from (stride: the model's convolution stride), so the motif covers
+    samples [begin * stride, (end + 1) * stride).  The motif is searched as given: for the other strand pass its reverse
+    complement as another motif."""
+    if not isinstance(trans, ScrappyMatrix):
+        raise TypeError('`trans` should be a ScrappyMatrix.')
+    nblock, nstate = trans.shape
+    if nstate != 25:
+        raise ValueError('`trans` should hold the 25 transitions of a flip-flop (CRF) model per block.')
+    motifs = list(motifs)
+    n = len(motifs)
+    tgs, keep = _motif_targets(motifs, True)
+    score = np.full(max(n, 1), np.nan, dtype=np.float32)
+    begin, end = (np.full(max(n, 1), -1, dtype=np.int32) for _ in range(2)) if positions else (None, None)
+    call = C.c_float(float('nan'))
+    i32 = C.POINTER(C.c_int32)
+    if lib().find_crf_sequences_viterbi(trans.data(), tgs, n, score.ctypes.data_as(C.POINTER(C.c_float)),
+                                        begin.ctypes.data_as(i32) if positions else None, end.ctypes.data_as(i32) if positions else None,
+                                        C.byref(call)) != 0:
+        raise RuntimeError('An unknown error occurred during the search: ' + last_error())
+    return score[:n], np.float32(call.value), (begin[:n] if positions else None), (end[:n] if positions else None)
 
 
 _squiggle_fn_ = {
@@ -1817,6 +1922,52 @@ class Engine(object):
                 pth = np.ctypeslib.as_array(r.path, shape=(r.nblock + 1,)).copy() if r.path else None
                 res.append((sc, int(r.first) if pth is not None else None, int(r.last), pth))
         lib().scrappie_hip_free_map_local_results(out, n)
+        return res
+
+    def find_sequences(self, signals, motifs, model='rnnrf_r94', positions=True, min_prob=1e-5, tempW=1.0, tempb=1.0):
+        """Which of these short sequences occur inside each read, and where?  Each read (trimmed, normalised float32 signal) of a
+        flip-flop (CRF) model searched for every one of its motifs, batched (scrappie_hip_find_batch): the network runs as for
+        `posterior`, the transitions stay on the device, all motifs of all reads of a launch group are packed into the
+        workgroups of one k_crf_find launch.  `motifs`: one list of base strings for all reads (encoded and uploaded once), or
+        one list per read.  Returns [(scores, call_score, best, begins, ends)] in input order, as `find_in_trans` gives them;
+        best: the index of the highest finite score (the lowest on a tie, -1: none).  A read that cannot run has every score
+        NaN and best -1.  begins and ends are entries of the path, 0 .. nblock: entry t lies at sample t * stride of the read
+        (stride: the model's convolution stride; `read_blocks` gives nblock), so the motif covers samples
+        [begin * stride, (end + 1) * stride).  A
+        motif is searched as given: pass its reverse complement as another motif for the other strand."""
+        n = len(signals)
+        motifs = list(motifs)
+        shared = all(isinstance(c, str) for c in motifs)
+        if not shared:
+            if any(isinstance(c, str) for c in motifs):
+                raise ValueError("`motifs`: a list of strings for every read, or one list of strings per read")
+            if len(motifs) != n:
+                raise ValueError("one list of motifs per signal")
+        h = self._models[model]
+        rts, keep = _raw_tables(signals)
+        cds = (_MapCandidates * max(n, 1))()
+        if shared:
+            tgs, codes = _motif_targets(motifs, False)
+            keep += [tgs, codes]
+            for i in range(n):
+                cds[i].cand, cds[i].ncand = tgs, len(motifs)
+        else:
+            for i, ml in enumerate(motifs):
+                ml = list(ml)
+                tgs, codes = _motif_targets(ml, False)
+                keep += [tgs, codes]
+                cds[i].cand, cds[i].ncand = tgs, len(ml)
+        p = self.default_params(min_prob=min_prob, tempW=tempW, tempb=tempb)
+        out = (_FindResult * max(n, 1))()
+        if lib().scrappie_hip_find_batch(self._h, h, rts, cds, n, C.byref(p), 1 if positions else 0, out) != 0:
+            raise RuntimeError("find_batch: " + last_error())
+        res = []
+        for r in (out[i] for i in range(n)):
+            k = int(r.nmotif)
+            take = lambda q, dt: (np.ctypeslib.as_array(q, shape=(k,)).copy() if k else np.zeros(0, dtype=dt))
+            res.append((take(r.score, np.float32), np.float32(r.call_score), int(r.best),
+                        take(r.begin, np.int32) if positions else None, take(r.end, np.int32) if positions else None))
+        lib().scrappie_hip_free_find_results(out, n)
         return res
 
     def _timing(self, fn, names):

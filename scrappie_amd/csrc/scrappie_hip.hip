@@ -40,6 +40,7 @@
  *   sh_eng_map_crf.inc   mapping of flip-flop (CRF) reads to base sequences (per-read; the launch group of the batched call)
  *   sh_eng_map.inc       block-based mapping of posteriors to sequences (per-read and batched)
  *   sh_eng_map_pack.inc  one read against many candidate sequences, packed into workgroups (per-read and batched)
+ *   sh_eng_crf_find.inc  short sequences searched inside flip-flop (CRF) reads, packed into workgroups (per-read and batched)
  *   sh_eng_map_crf_local.inc  flip-flop (CRF) reads mapped into a longer sequence, one workgroup per window (per-read and batched)
  *   sh_eng_squig.inc     mapping of raw signals to predicted squiggles (per-read and batched)
  *   sh_eng_sqnet.inc     prediction of squiggles from base sequences (per-read and batched)
@@ -494,6 +495,8 @@ struct scrappie_hip_engine {
     DBuf d_mpk_rd, d_mpk_cell, d_mpk_first, d_mpk_score; HBuf h_mpk;      /* candidates in packs (sh_eng_map_pack.inc): the packs, their cell words and first cells, scores; scores on the host */
     int map_pack_cells = -1;         /* cells a pack of candidates holds (debug option "map_pack_cells"; 0: every candidate through k_map, -1: the default) */
     DBuf d_mcl_rd, d_mcl_seq, d_mcl_scr, d_mcl_score, d_mcl_end, d_mcl_tb, d_mcl_poff, d_mcl_path, d_mcl_first; HBuf h_mcl;      /* sequence-local CRF mapping (sh_eng_map_crf_local.inc): windows, codes, scratch rows, scores, end cells; the second pass's traceback, path offsets, paths, firsts; results on the host */
+    DBuf d_cfd_rd, d_cfd_cell, d_cfd_score, d_cfd_pos, d_cfd_call; HBuf h_cfd;      /* motifs searched inside flip-flop reads (sh_eng_crf_find.inc): the packs, their cell words, scores, (begin, end), call scores; results on the host */
+    int crf_find_cells = -1;         /* cells a pack of motifs holds (debug option "crf_find_cells"; -1: the default) */
     int map_crf_local_stride = -1;   /* start cells a window of k_map_crf_local owns (debug option "map_crf_local_stride"; 0: one window, -1: the default) */
     double map_ms[3] = {0, 0, 0};    /* scrappie_hip_map_batch: network + S1, k_map, k_map_walk + results, summed over the last call's launch groups */
     DpBufs dp_sq; DBuf d_sq_sig, d_sq_tab;       /* squiggle matching (sh_eng_squig.inc): the records' buffers; signals, tables */
@@ -642,6 +645,7 @@ extern "C" scrappie_hip_params scrappie_hip_default_params(void) {
 #include "sh_eng_map_crf.inc"      /* mapping of flip-flop reads to base sequences (sh_map_crf.h): map_crf_to_sequence_* on the process-default engine, the launch group scrappie_hip_map_batch runs for a CRF model */
 #include "sh_eng_map.inc"      /* block-based mapping (sh_map.h): map_to_sequence_* on the process-default engine, scrappie_hip_map_batch */
 #include "sh_eng_map_pack.inc"      /* one read against many candidate sequences (sh_map_pack.h): scrappie_hip_map_multi_batch, scrappie_hip_map_post_multi */
+#include "sh_eng_crf_find.inc"      /* short sequences searched inside flip-flop reads, packed into workgroups (sh_crf_find.h): find_crf_sequences_viterbi, scrappie_hip_find_batch */
 #include "sh_eng_map_crf_local.inc"      /* flip-flop reads mapped into a longer sequence, cut into windows (sh_map_crf_local.h): map_crf_to_reference_*, scrappie_hip_map_local_batch */
 #include "sh_eng_squig.inc"      /* squiggle matching (sh_squig.h): squiggle_match_* on the process-default engine, scrappie_hip_squiggle_match_batch */
 #include "sh_eng_sqnet.inc"      /* squiggle prediction (sh_sqnet.h): squiggle_r94 and its relatives on the process-default engine, scrappie_hip_squiggle_predict_batch */

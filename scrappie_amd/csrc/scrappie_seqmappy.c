@@ -14,6 +14,9 @@
  * in ONE scrappie_hip_map_local_batch call (k_map_crf_local: one workgroup per window of the sequence); the usual header line with
  * `bases first..last` added -- the read spells the record's bases [first, last) -- and nblock + 1 records whose pos is in the
  * record's coordinates (first - 1 while no base is emitted).  Without the option nothing changes.
+ * --find (flip-flop models): every record of a pair's FASTA is a motif -- a barcode, an adapter, a primer -- searched INSIDE the
+ * pair's read.  All pairs in ONE scrappie_hip_find_batch call (k_crf_find: the motifs packed into workgroups); per pair a header
+ * line and a table record / name / score / delta / begin / end.  Without the option nothing changes.
  */
 #define _GNU_SOURCE
 #include <getopt.h>
@@ -54,7 +57,15 @@ static void seqmappy_usage(FILE *fh) {
           "      --inside               The read lies somewhere inside the sequence (a reference longer than the read): the\n"
           "                             best local placement of the whole read.  `bases first..last` is added to the header\n"
           "                             line -- the read spells bases [first, last) of the record -- and pos is in the\n"
-          "                             record's coordinates, first - 1 while none.  Flip-flop (CRF) models only.\n", fh);
+          "                             record's coordinates, first - 1 while none.  Flip-flop (CRF) models only.\n"
+          "      --find                 Search every record of the fasta (a barcode, an adapter, a primer) INSIDE the read:\n"
+          "                             per pair a line `# fast5 to fasta -- N records, call score S over B blocks, best K`\n"
+          "                             and a table record / name / score / delta / begin / end.  score: the best path of\n"
+          "                             the whole read that holds the record between entries begin and end (0 .. B; entry t\n"
+          "                             is sample t * stride of the trimmed signal), not negated; delta = score - call\n"
+          "                             score <= 0, the log-odds against the read's own call; nan where a record cannot be\n"
+          "                             searched.  A record is searched as given (no reverse complement).  Flip-flop (CRF)\n"
+          "                             models only; not with --inside or --all-records.\n", fh);
 }
 
 /* --all-records: pair i's read against every record of its FASTA, all pairs in one scrappie_hip_map_multi_batch call */
@@ -112,6 +123,55 @@ static int seqmappy_all_records(scrappie_hip_engine *e, int h, int klen, const s
     return rc;
 }
 
+/* --find: every record of pair i's FASTA searched inside pair i's read, all pairs in one scrappie_hip_find_batch call */
+static int seqmappy_find(scrappie_hip_engine *e, int h, const scrappie_hip_params *p, char **fasta, size_t npair, FILE *out,
+                         int trim_start, int trim_end, int varseg_chunk, float varseg_thresh) {
+    raw_table *rts = calloc(npair, sizeof *rts);
+    scrappie_hip_map_candidates *cd = calloc(npair, sizeof *cd);
+    scrappie_hip_find_result *res = calloc(npair, sizeof *res);
+    struct cli_fasta **recs = calloc(npair, sizeof *recs);
+    size_t *nrec = calloc(npair, sizeof *nrec);
+    int rc = EXIT_SUCCESS;
+    for (size_t i = 0; i < npair; i++) {
+        const char *fa = fasta[2 * i], *f5 = fasta[2 * i + 1];
+        if (cli_read_fasta(fa, &recs[i], &nrec[i], 0) || nrec[i] == 0) { fprintf(stderr, "scrappie: Failed to open \"%s\" for input.\n", fa); rc = EXIT_FAILURE; continue; }
+        scrappie_hip_map_target *tg = calloc(nrec[i], sizeof *tg);
+        for (size_t k = 0; k < nrec[i]; k++) {           /* a record that cannot be encoded stays an empty motif: nan in the table */
+            int *codes = recs[i][k].seq && recs[i][k].n ? encode_bases_to_integers(recs[i][k].seq, recs[i][k].n, 1) : NULL;
+            if (!codes) { fprintf(stderr, "scrappie: cannot encode record %zu of \"%s\": %s\n", k, fa, scrappie_hip_last_error()); continue; }
+            tg[k].seq = codes; tg[k].seqlen = recs[i][k].n;
+        }
+        cd[i].cand = tg; cd[i].ncand = nrec[i];
+        rts[i] = cli_load_read(f5, trim_start, trim_end, varseg_chunk, varseg_thresh, 1);
+        if (!rts[i].raw) { fprintf(stderr, "scrappie: Failed to open \"%s\" for input and trim signal.\n", f5); rc = EXIT_FAILURE; cd[i].ncand = 0; }
+    }
+    if (scrappie_hip_find_batch(e, h, rts, cd, npair, p, 1, res) != 0) {
+        fprintf(stderr, "scrappie: %s\n", scrappie_hip_last_error());
+        rc = EXIT_FAILURE;
+    } else {
+        for (size_t i = 0; i < npair; i++) {
+            if (!rts[i].raw || !cd[i].cand) continue;
+            const char *fa = fasta[2 * i], *f5 = fasta[2 * i + 1];
+            if (res[i].nblock == 0 || isnan(res[i].call_score)) { fprintf(stderr, "scrappie: Failed to search \"%s\" for \"%s\"\n", f5, fa); rc = EXIT_FAILURE; continue; }
+            fprintf(out, "# %s to %s -- %zu records, call score %f over %zu blocks, best %d\n", f5, fa, nrec[i], res[i].call_score, res[i].nblock, res[i].best);
+            fprintf(out, "record\tname\tscore\tdelta\tbegin\tend\n");
+            for (size_t k = 0; k < nrec[i]; k++) {
+                const float sc = res[i].score[k];
+                if (isnan(sc)) fprintf(out, "%zu\t%s\tnan\tnan\t-1\t-1\n", k, recs[i][k].name ? recs[i][k].name : "");
+                else fprintf(out, "%zu\t%s\t%f\t%f\t%d\t%d\n", k, recs[i][k].name ? recs[i][k].name : "", sc, sc - res[i].call_score, (int)res[i].begin[k], (int)res[i].end[k]);
+            }
+        }
+    }
+    scrappie_hip_free_find_results(res, npair);
+    for (size_t i = 0; i < npair; i++) {
+        if (cd[i].cand) { for (size_t k = 0; k < nrec[i]; k++) free((void *)cd[i].cand[k].seq); free((void *)cd[i].cand); }
+        cli_free_fasta(recs[i], nrec[i]);
+        free(rts[i].raw); free(rts[i].uuid);
+    }
+    free(nrec); free(recs); free(res); free(cd); free(rts);
+    return rc;
+}
+
 /* --inside: pair i's read into the first record of its FASTA, all pairs in one scrappie_hip_map_local_batch call */
 static int seqmappy_inside(scrappie_hip_engine *e, int h, const scrappie_hip_params *p, char **fasta, size_t npair, FILE *out,
                            int trim_start, int trim_end, int varseg_chunk, float varseg_thresh) {
@@ -155,13 +215,13 @@ static int seqmappy_inside(scrappie_hip_engine *e, int h, const scrappie_hip_par
 }
 
 int main_seqmappy(int argc, char **argv) {
-    enum { O_SEG = 256, O_T1, O_T2, O_LIC, O_MODEL, O_MFILE, O_DEV, O_ALL, O_INSIDE };
+    enum { O_SEG = 256, O_T1, O_T2, O_LIC, O_MODEL, O_MFILE, O_DEV, O_ALL, O_INSIDE, O_FIND };
     static const struct option lo[] = {
         {"localpen", 1, 0, 'l'}, {"min_prob", 1, 0, 'm'}, {"output", 1, 0, 'o'}, {"prefix", 1, 0, 'p'},
         {"segmentation", 1, 0, O_SEG}, {"skip", 1, 0, 's'}, {"stay", 1, 0, 'y'}, {"trim", 1, 0, 't'},
         {"temperature1", 1, 0, O_T1}, {"temperature2", 1, 0, O_T2}, {"licence", 0, 0, O_LIC}, {"license", 0, 0, O_LIC},
-        {"model", 1, 0, O_MODEL}, {"model-file", 1, 0, O_MFILE}, {"device", 1, 0, O_DEV}, {"all-records", 0, 0, O_ALL}, {"inside", 0, 0, O_INSIDE}, {"help", 0, 0, '?'}, {0, 0, 0, 0}};
-    int all_records = 0, inside = 0;
+        {"model", 1, 0, O_MODEL}, {"model-file", 1, 0, O_MFILE}, {"device", 1, 0, O_DEV}, {"all-records", 0, 0, O_ALL}, {"inside", 0, 0, O_INSIDE}, {"find", 0, 0, O_FIND}, {"help", 0, 0, '?'}, {0, 0, 0, 0}};
+    int all_records = 0, inside = 0, find = 0;
     /* defaults: scrappie_seqmappy.c:62-78 */
     scrappie_hip_params p = scrappie_hip_default_params();
     p.local_pen = 4.0f; p.min_prob = 1e-5f; p.stay_pen = 0.0f; p.skip_pen = 0.0f; p.tempW = 1.0f; p.tempb = 1.0f;
@@ -195,6 +255,7 @@ int main_seqmappy(int argc, char **argv) {
         case O_DEV: device = atoi(optarg); break;
         case O_ALL: all_records = 1; break;
         case O_INSIDE: inside = 1; break;
+        case O_FIND: find = 1; break;
         default: seqmappy_usage(stderr); return EXIT_FAILURE;
         }
     }
@@ -202,6 +263,12 @@ int main_seqmappy(int argc, char **argv) {
     if (nargs <= 0) { seqmappy_usage(stderr); return EXIT_FAILURE; }
     if (nargs % 2) { fprintf(stderr, "scrappie: fast5 file is a required argument\n"); return EXIT_FAILURE; }    /* scrappie_seqmappy.c:153 */
     const size_t npair = (size_t)nargs / 2;
+    if (find && inside) { fprintf(stderr, "scrappie: --find searches the records of a fasta inside the read; it cannot be combined with --inside\n"); return EXIT_FAILURE; }
+    if (find && all_records) { fprintf(stderr, "scrappie: --find searches every record of a fasta already; it cannot be combined with --all-records\n"); return EXIT_FAILURE; }
+    if (find && get_raw_model(model) != SCRAPPIE_MODEL_RNNRF_R9_4) {
+        fprintf(stderr, "scrappie: --find searches reads of flip-flop (CRF) models only (--model=rnnrf_r94); \"%s\" is a transducer model\n", model);
+        return EXIT_FAILURE;
+    }
     if (inside && all_records) { fprintf(stderr, "scrappie: --inside maps a read into the first record of its fasta; it cannot be combined with --all-records\n"); return EXIT_FAILURE; }
     if (inside && get_raw_model(model) != SCRAPPIE_MODEL_RNNRF_R9_4) {
         fprintf(stderr, "scrappie: --inside maps flip-flop (CRF) models only (--model=rnnrf_r94); \"%s\" is a transducer model\n", model);
@@ -220,6 +287,14 @@ int main_seqmappy(int argc, char **argv) {
     const int crf = nstate == 25;        /* a flip-flop model (rnnrf_r94): bases as states of length 1, a path of nblock + 1 entries */
     if (crf) klen = 1;
     else for (int nk = nstate - 1; nk > 1 && nk % 4 == 0; nk /= 4) klen++;
+    if (find) {
+        int rc = EXIT_FAILURE;
+        if (!crf) fprintf(stderr, "scrappie: --find searches reads of flip-flop (CRF) models only; \"%s\" is a transducer model\n", model);
+        else rc = seqmappy_find(e, h, &p, fasta, npair, out, trim_start, trim_end, varseg_chunk, varseg_thresh);
+        if (out != stdout) fclose(out);
+        scrappie_hip_engine_destroy(e);
+        return rc;
+    }
     if (inside) {
         int rc = EXIT_FAILURE;
         if (!crf) fprintf(stderr, "scrappie: --inside maps flip-flop (CRF) models only; \"%s\" is a transducer model\n", model);

@@ -837,6 +837,40 @@ long long scrappie_hip_map_crf_local_plan(size_t seqlen, size_t nblock, long str
     return (long long)nwin;
 }
 
+/* Packs of motifs searched inside a flip-flop read (k_crf_find, sh_crf_find.h).  A pack of ncell cells keeps two columns of
+ * transitions and, per cell and the spare slot behind them, two buffers of a value and a stay value (16 bytes) and a word (4);
+ * with positions two buffers of two payloads more (16): 20 or 36 bytes per cell. */
+size_t sh_crf_find_lds_bytes(size_t ncell, int pos) { return (64 + (pos ? 9 : 5) * (ncell + 1)) * 4; }
+
+/* the most cells a pack may hold, the read's five U cells included: what the LDS holds with positions (the bytes are linear in ncell) */
+size_t scrappie_hip_crf_find_max_cells(void) {
+    const size_t per = sh_crf_find_lds_bytes(1, 1) - sh_crf_find_lds_bytes(0, 1);
+    return (SH_MAP_LDS - sh_crf_find_lds_bytes(0, 1)) / per;
+}
+
+/* Motifs of seqlen[k] bases into packs of at most pack_cells cells (at most scrappie_hip_crf_find_max_cells() whatever is asked
+ * for), in input order.  A pack begins with the read's five U cells; a motif of L bases takes L - 1 interior cells and five V
+ * cells behind them.  A pack is closed when the next motif would take it past pack_cells, so a motif of more cells than that is
+ * alone in its pack.  pack[k]: the motif's pack, cell[k]: its first cell there (5 for the first); pack[k] = -1 (cell[k] = -1) for
+ * an empty motif and where 5 + seqlen[k] + 4 cells exceed the most a pack may hold -- such a motif is not mapped.  Returns the
+ * number of packs. */
+long scrappie_hip_crf_find_plan(const size_t *seqlen, size_t nmotif, size_t pack_cells, int *pack, long long *cell) {
+    if (!seqlen || !pack || !cell) return 0;
+    const size_t maxc = scrappie_hip_crf_find_max_cells();
+    if (pack_cells > maxc) pack_cells = maxc;
+    long np = 0;
+    size_t used = 0;                    /* cells of the open pack, np - 1; 0: none is open */
+    for (size_t k = 0; k < nmotif; k++) {
+        if (seqlen[k] == 0 || seqlen[k] > maxc - 9) { pack[k] = -1; cell[k] = -1; continue; }
+        const size_t c = seqlen[k] + 4;
+        if (used == 0 || used + c > pack_cells) { np++; used = 5; }
+        pack[k] = (int)(np - 1);
+        cell[k] = (long long)used;
+        used += c;
+    }
+    return np;
+}
+
 /* the library defines it (scrappie_hip.hip); weak, so that this file also links into the host-only builds of the tests */
 void sh_set_error(const char *fmt, ...) __attribute__((weak, format(printf, 1, 2)));
 #define SH_ERR(...) do { if (sh_set_error) sh_set_error(__VA_ARGS__); } while (0)

@@ -23,6 +23,8 @@ size_t sh_map_pack_lds_bytes(size_t ncell, size_t ncand);
 /* windows of the sequence-local CRF mapping (sh_host.c; k_map_crf_local, sh_map_crf_local.h): the dynamic LDS a window of ncell cells takes */
 size_t sh_map_crf_local_lds_bytes(size_t ncell);
 #define SH_MAP_CRF_LOCAL_CELLS 2034      /* cells of a window at the default stride: 40 952 bytes of LDS, four workgroups per compute unit (160 KB), eight chunks of 256 threads; the fastest measured (profiles/map_crf_local_rate.txt) */
+/* packs of motifs searched inside a flip-flop read (sh_host.c; k_crf_find, sh_crf_find.h): the dynamic LDS a pack of ncell cells takes, with or without positions */
+size_t sh_crf_find_lds_bytes(size_t ncell, int pos);
 /* squiggle matching (sh_host.c): the tables of decode.c:1055-1099 from the host's libm; tab holds 5 npos + 4 floats */
 void sh_squiggle_tables(const float *params, size_t npos, size_t ldp, float rate, float prob_back, float *tab, float pens[2]);
 /* dwell correction (sh_host.c): the scale from pos / state (n ints each, `stride` bytes apart), the prior's numerator of an event table, and
