@@ -646,10 +646,52 @@ def _raw_tables(signals):
     return rts, keep
 
 
-def _scores_and_paths(out, n, length_attr):
-    """[(score, path or None)] of a batched mapping call's results; a path is `length_attr` ints long"""
-    return [(float(r.score), np.ctypeslib.as_array(r.path, shape=(getattr(r, length_attr),)).copy() if r.path else None)
-            for r in (out[i] for i in range(n))]
+def _paths(rs, length_attr='nblock', more=0):
+    """The paths of a batched mapping call's results rs (a list of its ctypes structs), each an array of `length_attr` + more
+    ints; None where a result has none.  (One pass over the whole list: a call per read would show in the calls' wall time.)"""
+    as_array = np.ctypeslib.as_array
+    return [as_array(r.path, shape=(getattr(r, length_attr) + more,)).copy() if r.path else None for r in rs]
+
+
+def _scores_and_paths(out, n, length_attr, more=0):
+    """[(score, path or None)] of a batched mapping call's results"""
+    rs = [out[i] for i in range(n)]
+    return [(float(r.score), pth) for r, pth in zip(rs, _paths(rs, length_attr, more))]
+
+
+def _path_needs_viterbi(path, viterbi):
+    if path and not viterbi:
+        raise ValueError('Cannot calulate path with `viterbi==False`.')
+
+
+def _per_read_lists(lists, n, what):
+    """`lists`: one list of strings shared by all n reads, or one list of strings per read.  Returns (the lists, shared)."""
+    lists = list(lists)
+    shared = all(isinstance(c, str) for c in lists)
+    if not shared:
+        if any(isinstance(c, str) for c in lists):
+            raise ValueError("`%s`: a list of strings for every read, or one list of strings per read" % what)
+        if len(lists) != n:
+            raise ValueError("one list of %s per signal" % what)
+    return lists, shared
+
+
+def _per_read_sets(lists, shared, n, targets):
+    """The scrappie_hip_map_candidates array of n reads for what _per_read_lists returned, and what keeps its memory alive;
+    targets(list) makes (the ctypes target array, what keeps it alive) -- once for a shared list."""
+    cds = (_MapCandidates * max(n, 1))()
+    if shared:
+        made = [targets(lists)]
+        tgs, k = made[0][0], len(lists)
+        for i in range(n):
+            cds[i].cand, cds[i].ncand = tgs, k
+    else:
+        made = []
+        for i, c in enumerate(lists):
+            c = list(c)
+            made.append(targets(c))
+            cds[i].cand, cds[i].ncand = made[i][0], len(c)
+    return cds, made
 
 
 # ---------------------------------------------------------------------------
@@ -1008,8 +1050,7 @@ def map_post_to_sequence(post, sequence, stay_pen=0, skip_pen=0, local_pen=4.0, 
     """python/scrappy/__init__.py:492-578: block-based local-global alignment of a posterior (a `ScrappyMatrix` of
     log-probabilities, as from `calc_post`) to a base sequence, Viterbi or forward, full or banded; the DP runs on the
     GPU.  `bands`: None, an int (diagonal band) or a (low, high) pair.  Returns (score, path or None)."""
-    if path and not viterbi:
-        raise ValueError('Cannot calulate path with `viterbi==False`.')
+    _path_needs_viterbi(path, viterbi)
     if not isinstance(post, ScrappyMatrix):
         raise TypeError('`post` should be a ScrappyMatrix.')
     nblock, nstate = post.shape
@@ -1096,8 +1137,7 @@ def map_trans_to_sequence(trans, sequence, viterbi=False, path=False, bands=None
     cells of the diagonal band) or a (low, high) pair of nblock + 1 entries each: the cells -- bases emitted so far, 0 .. len --
     an entry of the path may be in.  Returns (score, path or None); path[t], t = 0 .. nblock, is the index of the last base
     emitted through entry t, -1 while none."""
-    if path and not viterbi:
-        raise ValueError('Cannot calulate path with `viterbi==False`.')
+    _path_needs_viterbi(path, viterbi)
     if not isinstance(trans, ScrappyMatrix):
         raise TypeError('`trans` should be a ScrappyMatrix.')
     nblock, nstate = trans.shape
@@ -1141,8 +1181,7 @@ def map_trans_to_reference(trans, sequence, viterbi=False, path=False):
     Returns (score, first, last, path): the read spells sequence[first:last]; path[t], t = 0 .. nblock, is the index in
     `sequence` of the last base emitted through entry t (first - 1 while none).  Forward: (score, None, None, None); Viterbi
     without `path`: (score, None, last, None) -- the start is known only from the traceback."""
-    if path and not viterbi:
-        raise ValueError('Cannot calulate path with `viterbi==False`.')
+    _path_needs_viterbi(path, viterbi)
     if not isinstance(trans, ScrappyMatrix):
         raise TypeError('`trans` should be a ScrappyMatrix.')
     nblock, nstate = trans.shape
@@ -1277,8 +1316,7 @@ def squiggle_match(rt, squiggle, rate=1.0, back_prob=0.0, local_pen=2.0, skip_pe
     rt's full length, -1 outside the window and in the START / END states.  `band`: None, an int (the half-width in
     positions of a diagonal band, `squiggle_diagonal_band`) or a (low, width) pair -- low[t] the first position sample t of
     the window may map to, width how many (squiggle_match_viterbi_banded / _forward_banded)."""
-    if path and not viterbi:
-        raise ValueError('Cannot calulate path with `viterbi==False`.')
+    _path_needs_viterbi(path, viterbi)
     if not isinstance(rt, RawTable):
         raise TypeError('`rt` should be a RawTable.')
     sq = _squiggle_matrix(squiggle)
@@ -1791,8 +1829,7 @@ class Engine(object):
         n = len(signals)
         if len(sequences) != n:
             raise ValueError("one sequence per signal")
-        if path and not viterbi:
-            raise ValueError('Cannot calulate path with `viterbi==False`.')
+        _path_needs_viterbi(path, viterbi)
         h = self._models[model]
         nstate = lib().scrappie_hip_model_states(self._h, h)
         crf = nstate == 25                  # the flip-flop models: 5 x 5 transitions, bases as codes of one
@@ -1824,10 +1861,7 @@ class Engine(object):
         out = (_MapResult * n)()
         if lib().scrappie_hip_map_batch(self._h, h, rts, tgs, n, C.byref(p), 1 if viterbi else 0, 1 if path else 0, out) != 0:
             raise RuntimeError("map_batch: " + last_error())
-        if crf:
-            res = [(float(r.score), np.ctypeslib.as_array(r.path, shape=(r.nblock + 1,)).copy() if r.path else None) for r in (out[i] for i in range(n))]
-        else:
-            res = _scores_and_paths(out, n, 'nblock')
+        res = _scores_and_paths(out, n, 'nblock', 1 if crf else 0)
         lib().scrappie_hip_free_map_results(out, n)
         return res
 
@@ -1841,41 +1875,26 @@ class Engine(object):
         mapped; normalising for length is the caller's business), the index of the highest (the lowest index on a tie,
         -1: none) and, with `path`, the Viterbi path of that candidate."""
         n = len(signals)
-        if path and not viterbi:
-            raise ValueError('Cannot calulate path with `viterbi==False`.')
-        candidates = list(candidates)
-        shared = all(isinstance(c, str) for c in candidates)
-        if not shared:
-            if any(isinstance(c, str) for c in candidates):
-                raise ValueError("`candidates`: a list of strings for every read, or one list of strings per read")
-            if len(candidates) != n:
-                raise ValueError("one list of candidates per signal")
+        _path_needs_viterbi(path, viterbi)
+        candidates, shared = _per_read_lists(candidates, n, 'candidates')
         h = self._models[model]
         nstate = lib().scrappie_hip_model_states(self._h, h)
         if nstate == 25:
             raise RuntimeError("map_multi_batch: a flip-flop (CRF) model maps one sequence per read (map_to_sequence)")
         kmer_len = guess_state_properties(nstate)[1]
         rts, keep = _raw_tables(signals)
-        cds = (_MapCandidates * max(n, 1))()
-        if shared:
-            tgs, codes = _map_targets(candidates, kmer_len)
-            keep += [tgs, codes]
-            for i in range(n):
-                cds[i].cand, cds[i].ncand = tgs, len(candidates)
-        else:
-            for i, cl in enumerate(candidates):
-                tgs, codes = _map_targets(list(cl), kmer_len)
-                keep += [tgs, codes]
-                cds[i].cand, cds[i].ncand = tgs, len(cl)
+        cds, kept = _per_read_sets(candidates, shared, n, lambda cl: _map_targets(cl, kmer_len))
+        keep += kept
         p = self.default_params(min_prob=min_prob, tempW=tempW, tempb=tempb, stay_pen=stay_pen, skip_pen=skip_pen,
                                 local_pen=local_pen)
         out = (_MapMultiResult * max(n, 1))()
         if lib().scrappie_hip_map_multi_batch(self._h, h, rts, cds, n, C.byref(p), 1 if viterbi else 0, 1 if path else 0, out) != 0:
             raise RuntimeError("map_multi_batch: " + last_error())
         res = []
-        for r in (out[i] for i in range(n)):
+        rs = [out[i] for i in range(n)]
+        for r, pth in zip(rs, _paths(rs)):
             sc = np.ctypeslib.as_array(r.score, shape=(r.ncand,)).copy() if r.ncand else np.zeros(0, dtype=np.float32)
-            res.append((sc, int(r.best), np.ctypeslib.as_array(r.path, shape=(r.nblock,)).copy() if r.path else None))
+            res.append((sc, int(r.best), pth))
         lib().scrappie_hip_free_map_multi_results(out, n)
         return res
 
@@ -1887,8 +1906,7 @@ class Engine(object):
         [(score, first, last, path)] in input order as `map_trans_to_reference` gives them; score NaN (and None) where a
         read or its reference cannot be mapped."""
         n = len(signals)
-        if path and not viterbi:
-            raise ValueError('Cannot calulate path with `viterbi==False`.')
+        _path_needs_viterbi(path, viterbi)
         if isinstance(references, str):
             references = [references] * n
         elif len(references) != n:
@@ -1912,14 +1930,12 @@ class Engine(object):
         if lib().scrappie_hip_map_local_batch(self._h, h, rts, tgs, n, C.byref(p), 1 if viterbi else 0, 1 if path else 0, out) != 0:
             raise RuntimeError("map_local_batch: " + last_error())
         res = []
-        for r in (out[i] for i in range(n)):
+        rs = [out[i] for i in range(n)]
+        for r, pth in zip(rs, _paths(rs, more=1)):
             sc = float(r.score)
-            if np.isnan(sc):
-                res.append((sc, None, None, None))
-            elif not viterbi:
+            if np.isnan(sc) or not viterbi:
                 res.append((sc, None, None, None))
             else:
-                pth = np.ctypeslib.as_array(r.path, shape=(r.nblock + 1,)).copy() if r.path else None
                 res.append((sc, int(r.first) if pth is not None else None, int(r.last), pth))
         lib().scrappie_hip_free_map_local_results(out, n)
         return res
@@ -1936,27 +1952,11 @@ class Engine(object):
         [begin * stride, (end + 1) * stride).  A
         motif is searched as given: pass its reverse complement as another motif for the other strand."""
         n = len(signals)
-        motifs = list(motifs)
-        shared = all(isinstance(c, str) for c in motifs)
-        if not shared:
-            if any(isinstance(c, str) for c in motifs):
-                raise ValueError("`motifs`: a list of strings for every read, or one list of strings per read")
-            if len(motifs) != n:
-                raise ValueError("one list of motifs per signal")
+        motifs, shared = _per_read_lists(motifs, n, 'motifs')
         h = self._models[model]
         rts, keep = _raw_tables(signals)
-        cds = (_MapCandidates * max(n, 1))()
-        if shared:
-            tgs, codes = _motif_targets(motifs, False)
-            keep += [tgs, codes]
-            for i in range(n):
-                cds[i].cand, cds[i].ncand = tgs, len(motifs)
-        else:
-            for i, ml in enumerate(motifs):
-                ml = list(ml)
-                tgs, codes = _motif_targets(ml, False)
-                keep += [tgs, codes]
-                cds[i].cand, cds[i].ncand = tgs, len(ml)
+        cds, kept = _per_read_sets(motifs, shared, n, lambda ml: _motif_targets(ml, False))
+        keep += kept
         p = self.default_params(min_prob=min_prob, tempW=tempW, tempb=tempb)
         out = (_FindResult * max(n, 1))()
         if lib().scrappie_hip_find_batch(self._h, h, rts, cds, n, C.byref(p), 1 if positions else 0, out) != 0:
@@ -1989,8 +1989,7 @@ class Engine(object):
         n = len(signals)
         if len(squiggles) != n:
             raise ValueError("one squiggle per signal")
-        if path and not viterbi:
-            raise ValueError('Cannot calulate path with `viterbi==False`.')
+        _path_needs_viterbi(path, viterbi)
         rts, keep = _raw_tables(signals)
         tgs = (_SquigTarget * n)()
         for i, sq in enumerate(squiggles):

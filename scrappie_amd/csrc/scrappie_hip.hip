@@ -37,6 +37,9 @@
  *   sh_eng_surface.inc   the reference's per-read functions: one batch function per family, run by the queue or with a batch of one
  *   sh_eng_cut.inc       what the engines below share: a call cut into launches that fit the device (LaunchCut), per-read DP
  *                        records through a kernel with two homes (dp_order / dp_launch / dp_collect)
+ *   sh_eng_post.inc      what the five engines on a launch group's posterior or transitions share: the batch call and its memory model
+ *                        (PostCall), the launch group's stage (post_group), one plan and runner for two homes (DpPlan / dp_run), sets of
+ *                        short sequences in packs (PackSet / PackLaunch), a host matrix's upload, the two-span timer
  *   sh_eng_map_crf.inc   mapping of flip-flop (CRF) reads to base sequences (per-read; the launch group of the batched call)
  *   sh_eng_map.inc       block-based mapping of posteriors to sequences (per-read and batched)
  *   sh_eng_map_pack.inc  one read against many candidate sequences, packed into workgroups (per-read and batched)
@@ -323,9 +326,10 @@ struct PostStage { HBuf h; DBuf d; std::atomic<int> users{0}; };
 struct DpBufs {
     DBuf rd, tb, scr, score, final_state, path_off, paths;
     HBuf h;
-    int ensure(size_t n, size_t rec_bytes, long long tb_words, long long scr_floats, long long path_len, size_t h_bytes = 0) {
-        return (rd.ensure(n * rec_bytes) || tb.ensure((size_t)tb_words * 4 + 16) || scr.ensure((size_t)scr_floats * 4 + 16) || score.ensure(n * 4) ||
-                final_state.ensure(n * 4) || path_off.ensure(n * 8) || paths.ensure((size_t)path_len * 4 + 16) ||
+    /* fs_bytes: of a record's final-state entry (an int; k_map_crf_local's end cell is an int2) */
+    int ensure(size_t n, size_t rec_bytes, long long tb_words, long long scr_floats, long long path_len, size_t h_bytes = 0, size_t fs_bytes = 4) {
+        return (rd.ensure(n * rec_bytes) || tb.ensure((size_t)tb_words * 4 + 16) || scr.ensure((size_t)scr_floats * 4 + 16) || score.ensure(n * 4 + 16) ||
+                final_state.ensure(n * fs_bytes + 16) || path_off.ensure(n * 8) || paths.ensure((size_t)path_len * 4 + 16) ||
                 h.ensure(std::max(h_bytes, n * 4 + (size_t)path_len * 4))) ? -1 : 0;
     }
 };
@@ -494,7 +498,7 @@ struct scrappie_hip_engine {
     DpBufs dp_map; DBuf d_map_seq, d_map_band, d_map_post;       /* block-based mapping (sh_eng_map.inc): the records' buffers; codes, bands, a per-read call's dense posterior */
     DBuf d_mpk_rd, d_mpk_cell, d_mpk_first, d_mpk_score; HBuf h_mpk;      /* candidates in packs (sh_eng_map_pack.inc): the packs, their cell words and first cells, scores; scores on the host */
     int map_pack_cells = -1;         /* cells a pack of candidates holds (debug option "map_pack_cells"; 0: every candidate through k_map, -1: the default) */
-    DBuf d_mcl_rd, d_mcl_seq, d_mcl_scr, d_mcl_score, d_mcl_end, d_mcl_tb, d_mcl_poff, d_mcl_path, d_mcl_first; HBuf h_mcl;      /* sequence-local CRF mapping (sh_eng_map_crf_local.inc): windows, codes, scratch rows, scores, end cells; the second pass's traceback, path offsets, paths, firsts; results on the host */
+    DpBufs dp_mcl; DBuf d_mcl_seq, d_mcl_first;      /* sequence-local CRF mapping (sh_eng_map_crf_local.inc): the windows' buffers (final state: the end cell, an int2); codes, the second pass's firsts */
     DBuf d_cfd_rd, d_cfd_cell, d_cfd_score, d_cfd_pos, d_cfd_call; HBuf h_cfd;      /* motifs searched inside flip-flop reads (sh_eng_crf_find.inc): the packs, their cell words, scores, (begin, end), call scores; results on the host */
     int crf_find_cells = -1;         /* cells a pack of motifs holds (debug option "crf_find_cells"; -1: the default) */
     int map_crf_local_stride = -1;   /* start cells a window of k_map_crf_local owns (debug option "map_crf_local_stride"; 0: one window, -1: the default) */
@@ -642,6 +646,7 @@ extern "C" scrappie_hip_params scrappie_hip_default_params(void) {
 #include "sh_eng_debug.inc"      /* measurement / test hooks: decoder and trunk inputs, debug_option / debug_fetch / debug_stitch */
 #include "sh_eng_surface.inc"      /* the reference's per-read functions: posterior / trunk on an explicit engine, the process-default engine, decode_transducer, decode_crf; all three coalesced (sh_coalesce.h) */
 #include "sh_eng_cut.inc"      /* shared by those below: LaunchCut (a call cut into launches), dp_order / dp_launch / dp_collect (a kernel with two homes) */
+#include "sh_eng_post.inc"      /* shared by the five below: PostCall (the batch call), post_group (a launch group to STOP_POST), DpPlan / dp_run, PackSet / PackLaunch, post_upload_* */
 #include "sh_eng_map_crf.inc"      /* mapping of flip-flop reads to base sequences (sh_map_crf.h): map_crf_to_sequence_* on the process-default engine, the launch group scrappie_hip_map_batch runs for a CRF model */
 #include "sh_eng_map.inc"      /* block-based mapping (sh_map.h): map_to_sequence_* on the process-default engine, scrappie_hip_map_batch */
 #include "sh_eng_map_pack.inc"      /* one read against many candidate sequences (sh_map_pack.h): scrappie_hip_map_multi_batch, scrappie_hip_map_post_multi */

@@ -1,10 +1,18 @@
 /* sh_eng_cut.inc -- part of scrappie_hip.hip (one translation unit, included from there in this order; not compiled alone):
- * what the batched engines beside the basecaller share (sh_eng_map.inc, sh_eng_squig.inc, sh_eng_sqnet.inc).  LaunchCut: a call cut into launches
+ * what the batched engines beside the basecaller share (sh_eng_map*.inc, sh_eng_crf_find.inc, sh_eng_squig.inc, sh_eng_sqnet.inc, sh_eng_events.inc;
+ * sh_eng_post.inc builds on it what the engines on a resident posterior share further).  keep_err: the way out of a failed launch.  LaunchCut: a call cut into launches
  * that fit the device, in input order, with the first refusal remembered and one way out of a failed launch.  dp_order / dp_launch / dp_collect: the
  * per-read DP records of k_map and k_squig through a kernel with two homes (score rows in LDS, or in device scratch for the reads too long for it). */
 
 /* what one launch may hold: half of the device memory that is free now (the engine's own arena stays where it is), a quarter of all of it where the
  * runtime will not say; override: the bytes a debug option has set */
+/* the way out of a failed launch: HIP's sticky error cleared, the error text as it was before that; -1 */
+static int keep_err() {
+    const std::string keep = g_err;
+    (void)hipGetLastError();
+    return set_err("%s", keep.c_str());
+}
+
 static size_t launch_budget(const scrappie_hip_engine *e, size_t override) {
     if (override) return override;
     size_t fr = 0, tot = 0;
@@ -33,10 +41,8 @@ struct LaunchCut {
         if (who.empty() || failed) return;
         if ((e->dbg_fail_run > 0 && --e->dbg_fail_run == 0) ? set_err("%s: injected failure (debug option fail_run)", fn) : run(who, load)) {
             failed = true;
-            const std::string keep = g_err;
-            (void)hipGetLastError();
+            (void)keep_err();
             (void)sh_stream_wait(e->pstream); (void)sh_stream_wait(e->stream); (void)sh_stream_wait(e->cstream);
-            set_err("%s", keep.c_str());
         }
         who.clear(); load = Load{};
     }

@@ -1,0 +1,129 @@
+"""The two paths that every engine on a launch group's posterior or transitions shares (sh_eng_post.inc): the way out of a
+failed launch, and the refusal of a read whose signal leaves the supported range -- each through every family's entry point."""
+import numpy as np
+import pytest
+
+import scrappie_amd as sa
+from scrappie_amd import model, synth
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def eng():
+    e = sa.Engine(0)
+    e.load_model("rnnrf_r94", model.synthetic_model("rnnrf_r94", seed=11))
+    e.load_model("rgrgr_r94", model.synthetic_model("rgrgr_r94", seed=1))
+    yield e
+    e.close()
+
+
+def _bases(n, rng):
+    return "".join(rng.choice(list("ACGT"), n))
+
+
+def _families():
+    """per entry point: run(engine, signals, ids) -- ids: which of the prepared sequences each read maps to, where the family
+    has one per read --, the counter of its kernel's forms, the form these calls launch and how often per launch group, and
+    whether a result is the family's empty one"""
+    rng = np.random.default_rng(83)
+    cands = [_bases(30, rng) for _ in range(3)]
+    reference = _bases(300, rng)
+    motifs = [_bases(12, rng) for _ in range(3)]
+    seqs = [_bases(30, rng) for _ in range(64)]
+    return {
+        "map_to_sequence-rnnrf_r94": dict(
+            run=lambda e, sigs, ids: e.map_to_sequence(sigs, [seqs[i] for i in ids], model="rnnrf_r94", viterbi=True, path=True),
+            counts=sa.map_crf_form_counts, form=(True, True, False), per_group=1,
+            empty=lambda r: np.isnan(r[0]) and r[1] is None),
+        "map_to_sequences-rgrgr_r94": dict(
+            run=lambda e, sigs, ids: e.map_to_sequences(sigs, cands, model="rgrgr_r94", viterbi=True, path=True),
+            counts=sa.map_pack_form_counts, form=(True, True), per_group=1,
+            empty=lambda r: len(r[0]) == 3 and np.all(np.isnan(r[0])) and r[1] == -1 and r[2] is None),
+        "map_to_reference-rnnrf_r94": dict(
+            run=lambda e, sigs, ids: e.map_to_reference(sigs, reference, model="rnnrf_r94", viterbi=True, path=True),
+            counts=sa.map_crf_local_form_counts, form=(True, True, False), per_group=2,         # both passes
+            empty=lambda r: np.isnan(r[0]) and r[1:] == (None, None, None)),
+        "find_sequences-rnnrf_r94": dict(
+            run=lambda e, sigs, ids: e.find_sequences(sigs, motifs, model="rnnrf_r94", positions=True),
+            counts=sa.crf_find_form_counts, form=(True, True), per_group=1,
+            empty=lambda r: len(r[0]) == 3 and np.all(np.isnan(r[0])) and r[2] == -1),
+        "map_to_sequence-rgrgr_r94": dict(
+            run=lambda e, sigs, ids: e.map_to_sequence(sigs, [seqs[i] for i in ids], model="rgrgr_r94", viterbi=True, path=True),
+            counts=lambda: sa.launch_form_counts()["map"], form=(True, False, True, False), per_group=1,
+            empty=lambda r: np.isnan(r[0]) and r[1] is None),
+    }
+
+
+FAMILIES = _families()
+FAILED_LAUNCH = ["map_to_sequence-rnnrf_r94", "map_to_sequences-rgrgr_r94", "map_to_reference-rnnrf_r94", "find_sequences-rnnrf_r94"]
+
+
+def _same(a, b, where=()):
+    """bit for bit: floats by their float32 bytes (NaN equals NaN), arrays by dtype, shape and bytes"""
+    if isinstance(a, (tuple, list)):
+        assert isinstance(b, (tuple, list)) and len(a) == len(b), where
+        for k, (x, y) in enumerate(zip(a, b)):
+            _same(x, y, where + (k,))
+    elif isinstance(a, np.ndarray):
+        assert isinstance(b, np.ndarray) and a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), where
+    elif isinstance(a, (float, np.floating)):
+        assert isinstance(b, (float, np.floating)) and np.float32(a).tobytes() == np.float32(b).tobytes(), (where, a, b)
+    else:
+        assert type(a) is type(b) and a == b, (where, a, b)
+
+
+@pytest.fixture(scope="module")
+def forty_reads():
+    rng = np.random.default_rng(61)
+    return [synth.medmad_normalise(synth.synthetic_signal(int(k), 500 + i)) for i, k in enumerate(rng.integers(600, 1000, 40))]
+
+
+@pytest.mark.parametrize("name", FAILED_LAUNCH)
+def test_failed_launch_group(eng, forty_reads, name):
+    """the second of three launch groups refused (debug option fail_run: on the host, before anything is uploaded): the call
+    fails with that text and hands nothing back, the third group never runs, and the engine then gives what it gave before --
+    test_gpu_map.py::test_engine_failed_launch_group for the other four entry points"""
+    fam = FAMILIES[name]
+    count = lambda: fam["counts"]()[fam["form"]]
+    g = fam["per_group"]
+    eng.set_max_launch_reads(16)
+    try:
+        before = count()
+        first = fam["run"](eng, forty_reads, range(40))
+        assert len(first) == 40 and not any(fam["empty"](r) for r in first)
+        assert count() - before == 3 * g
+        eng.debug_option("fail_run", 2)
+        got = None
+        with pytest.raises(RuntimeError, match="injected failure"):
+            got = fam["run"](eng, forty_reads, range(40))
+        assert got is None
+        assert count() - before == 4 * g           # the first group ran, the second was refused, no third
+        eng.debug_option("fail_run", 0)
+        _same(fam["run"](eng, forty_reads, range(40)), first)
+    finally:
+        eng.debug_option("fail_run", 0)
+        eng.set_max_launch_reads(16384)
+
+
+@pytest.fixture(scope="module")
+def good_and_huge():
+    good = [synth.medmad_normalise(synth.synthetic_signal(1200 + 37 * i, 900 + i)) for i in range(5)]
+    huge = (synth.synthetic_signal(2000, 91, raw_units=True) * 1000.0).astype(np.float32)
+    return good, huge
+
+
+@pytest.mark.parametrize("name", sorted(FAMILIES))
+def test_out_of_range_read_costs_only_itself(eng, good_and_huge, name):
+    """a read whose first-layer activations leave the split products' range, among five good ones of its launch group: it comes
+    back as the family's empty result and is named in the error text; its group-mates' results are those of a call without it"""
+    fam = FAMILIES[name]
+    good, huge = good_and_huge
+    alone = fam["run"](eng, good, [0, 1, 2, 3, 4])
+    assert len(alone) == 5 and not any(fam["empty"](r) for r in alone)
+    mixed = fam["run"](eng, good[:2] + [huge] + good[2:], [0, 1, 63, 2, 3, 4])
+    err = sa.last_error()
+    assert len(mixed) == 6
+    assert fam["empty"](mixed[2]), mixed[2]
+    assert "read 2" in err and "outside the supported range" in err, err
+    _same(mixed[:2] + mixed[3:], alone)
