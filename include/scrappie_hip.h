@@ -591,6 +591,54 @@ size_t scrappie_hip_map_crf_local_max_cells(void);
 /* launches of each k_map_crf_local form in this process, all engines together: index (viterbi ? 4 : 0) | (tiled ? 2 : 0) | (scratch ? 1 : 0) */
 void scrappie_hip_map_crf_local_form_counts(uint64_t forms[8]);
 
+/* Reads of a transducer model mapped INTO a longer sequence of k-mer states (k_map_local, sh_map_local.h; sh_eng_map_local.inc): where
+ * in this amplicon, plasmid or chromosome arm does the read lie.  It is map_to_sequence_viterbi / _forward (decode.c:1420-1640,
+ * unbanded) with the sequence side made local: the states are the positions 0 .. seqlen - 1, START, and one END accumulator per
+ * position; START = 0 before block 0 and everything else -1e30.  Per block, from the previous row p to c, lps the stay entry, le
+ * the entry of state seq[pos], ls = fmaxf(-local_pen, lps):
+ *   c[START] = p[START] + ls
+ *   c[pos] = (p[pos] - stay_pen) + lps, then on strict > in this order step p[pos - 1] + le (pos >= 1), skip (p[pos - 2] -
+ *            skip_pen) + le (pos >= 2), from START p[START] + le for every pos (the reference: at pos 0 only)
+ *   E'[pos] = E[pos] + ls, then p[pos] - local_pen on strict > (any position may leave for END; the reference: seqlen - 1 only)
+ * After the last block x is the first maximum of c[pos] and y the first maximum of E[pos], pos ascending; the score is
+ * fmaxf(x, y) and the path ends in a sequence cell iff x > y; START is no end state.  Forward: logsumexpf in place of every max.
+ * path[blk], nblock entries: the position in seq, -1 in START / END; first: the lowest position the path visits, last: the highest
+ * plus one -- with a k-mer model the read spells bases first .. last + k - 2 of the base string.  A path always exists, and the
+ * score is never below map_to_sequence_viterbi's for the same pair.
+ * The sequence is cut into windows of one workgroup each (scrappie_hip_map_local_plan); the Viterbi score has the same bits for
+ * every cut.  seqlen is bounded by index width alone: 2^30 states; the posterior by what a workgroup stages: 2048 states.
+ *
+ * scrappie_hip_map_post_local_batch: reads[i] (prepared as for scrappie_hip_map_batch) into targets[i] = {seq, seqlen}, state codes
+ * as encode_bases_to_integers gives them; several reads may point at the same seq (with the same seqlen), which is then checked
+ * and uploaded once per launch group.  p: min_prob, tempW, tempb and the three penalties.  Two passes as
+ * scrappie_hip_map_local_batch; out[i]: score (NAN where read or sequence cannot be mapped, with the first such reason as the error
+ * text; its neighbours are untouched), nblock, last (Viterbi; 0 for forward), first (known from the traceback only: (size_t)-1
+ * without viterbi and want_path), path (nblock entries, malloc'd; scrappie_hip_free_map_local_results).  A flip-flop (CRF) model is
+ * refused for the whole call (-1): its call is scrappie_hip_map_local_batch.  scrappie_hip_map_timing covers the call.
+ *
+ * The per-read symbols run on the process-default engine on a posterior of log-probabilities as map_to_sequence_* take it, whose
+ * columns are whole 16-byte pieces apart (scrappie matrices are); first, last and path may each be NULL, and a call that wants
+ * neither first nor path runs the first pass alone. */
+float map_to_reference_viterbi(const_scrappie_matrix logpost, float stay_pen, float skip_pen, float local_pen, int const *seq, size_t seqlen,
+                               size_t *first, size_t *last, int *path);
+float map_to_reference_forward(const_scrappie_matrix logpost, float stay_pen, float skip_pen, float local_pen, int const *seq, size_t seqlen);
+int scrappie_hip_map_post_local_batch(scrappie_hip_engine *e, int model, const raw_table *reads, const scrappie_hip_map_local_target *targets,
+                                      size_t n, const scrappie_hip_params *p, int viterbi, int want_path, scrappie_hip_map_local_result *out);
+/* Host only: the cut of seqlen positions into windows for a read of nblock blocks of a posterior of nr states.  A path advances at
+ * most reach = 2 (nblock - 1) positions.  stride > 0: entry positions per window; 0: one window; < 0: the default (the debug option
+ * "map_local_stride" takes the same values) -- while a window with stride > reach keeps its rows in LDS
+ * (scrappie_hip_map_local_max_cells(nr)): a window of stride + reach = 2798 cells (three such workgroups are resident per compute
+ * unit) where that leaves a stride of 1200 or more, the largest LDS-resident window for longer reads; and 2 nblock, rows in
+ * device scratch, beyond that.  Window w owns the entry positions [first[w], first[w] + own[w]) and holds ncell[w] cells from
+ * first[w]; home[w]: 0 LDS, 1 scratch at float offset scr_off[w] (-1 in LDS; 3 * 4 ceil(ncell / 4) floats each) of *scr_floats in
+ * all.  Arrays may be NULL and hold cap entries.  Returns the number of windows; 0 where there is nothing to cut. */
+long long scrappie_hip_map_local_plan(size_t seqlen, size_t nblock, size_t nr, long stride, size_t cap, size_t *first, size_t *ncell, size_t *own,
+                                      int *home, long long *scr_off, long long *scr_floats);
+size_t scrappie_hip_map_local_stride(size_t seqlen, size_t nblock, size_t nr, long stride);
+size_t scrappie_hip_map_local_max_cells(size_t nr);
+/* launches of each k_map_local form in this process, all engines together: index (viterbi ? 4 : 0) | (tiled ? 2 : 0) | (scratch ? 1 : 0) */
+void scrappie_hip_map_local_form_counts(uint64_t forms[8]);
+
 /* Short sequences searched INSIDE reads of a flip-flop (CRF) model (k_crf_find, sh_crf_find.h; sh_eng_crf_find.inc): does this
  * barcode, adapter, primer or marker occur somewhere in the read, where, and which of K such motifs fits best.  Viterbi only.  A
  * path (nblock + 1 entries over A C G T stay, as decode_crf's) is admissible for a motif m[0..L) when it has entries begin <= end,

@@ -318,6 +318,21 @@ def lib():
     L.scrappie_hip_map_crf_local_max_cells.argtypes = []
     L.scrappie_hip_map_crf_local_form_counts.restype = None
     L.scrappie_hip_map_crf_local_form_counts.argtypes = [C.POINTER(C.c_uint64)]
+    L.map_to_reference_viterbi.restype = C.c_float
+    L.map_to_reference_viterbi.argtypes = [PM, C.c_float, C.c_float, C.c_float, ip, C.c_size_t, sp, sp, ip]
+    L.map_to_reference_forward.restype = C.c_float
+    L.map_to_reference_forward.argtypes = [PM, C.c_float, C.c_float, C.c_float, ip, C.c_size_t]
+    L.scrappie_hip_map_post_local_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(_RawTable), C.POINTER(_MapLocalTarget), C.c_size_t,
+                                                    C.POINTER(Params), C.c_int, C.c_int, C.POINTER(_MapLocalResult)]
+    L.scrappie_hip_map_local_plan.restype = C.c_longlong
+    L.scrappie_hip_map_local_plan.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t, C.c_long, C.c_size_t, sp, sp, sp, ip, C.POINTER(C.c_longlong),
+                                              C.POINTER(C.c_longlong)]
+    L.scrappie_hip_map_local_stride.restype = C.c_size_t
+    L.scrappie_hip_map_local_stride.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t, C.c_long]
+    L.scrappie_hip_map_local_max_cells.restype = C.c_size_t
+    L.scrappie_hip_map_local_max_cells.argtypes = [C.c_size_t]
+    L.scrappie_hip_map_local_form_counts.restype = None
+    L.scrappie_hip_map_local_form_counts.argtypes = [C.POINTER(C.c_uint64)]
     L.scrappie_hip_find_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(_RawTable), C.POINTER(_MapCandidates), C.c_size_t,
                                           C.POINTER(Params), C.c_int, C.POINTER(_FindResult)]
     L.scrappie_hip_free_find_results.restype = None
@@ -514,6 +529,44 @@ def set_map_crf_local_stride(value):
     """The debug option "map_crf_local_stride" of the process-default engine, the one `map_trans_to_reference` runs on: start
     cells per window, 0: one window, -1: the default.  (An `Engine` has `debug_option`.)"""
     if lib().scrappie_hip_debug_option(None, b"map_crf_local_stride", int(value)) != 0:
+        raise RuntimeError("debug_option: " + last_error())
+
+
+def map_local_form_counts():
+    """Launches of each k_map_local form in this process so far (scrappie_hip_map_local_form_counts):
+    {(viterbi, tiled, scratch): n}."""
+    q = (C.c_uint64 * 8)()
+    lib().scrappie_hip_map_local_form_counts(q)
+    return {(bool(k & 4), bool(k & 2), bool(k & 1)): int(q[k]) for k in range(8)}
+
+
+def map_local_max_cells(nstate):
+    """The most cells a window of k_map_local keeps in LDS beside the two columns of a posterior of `nstate` states; a larger
+    window keeps its rows in device scratch."""
+    return int(lib().scrappie_hip_map_local_max_cells(nstate))
+
+
+def map_local_plan(seq_len, nblock, nstate, stride=-1):
+    """The cut of the `seq_len` positions of a sequence into windows for a read of `nblock` blocks of a posterior of `nstate`
+    states (host arithmetic, no device; scrappie_hip_map_local_plan).  `stride`: entry positions per window, 0: one window, -1:
+    the default.  Returns a dict of arrays, one entry per window: first, ncell, own, home (0 LDS, 1 device scratch), scr_off (-1
+    in LDS), and scr_floats."""
+    Lb = lib()
+    nw = int(Lb.scrappie_hip_map_local_plan(seq_len, nblock, nstate, int(stride), 0, None, None, None, None, None, None))
+    first, ncell, own = (np.zeros(nw, dtype=np.uintp) for _ in range(3))
+    home = np.zeros(nw, dtype=np.int32)
+    off = np.zeros(nw, dtype=np.longlong)
+    tot = C.c_longlong(0)
+    sp = C.POINTER(C.c_size_t)
+    Lb.scrappie_hip_map_local_plan(seq_len, nblock, nstate, int(stride), nw, first.ctypes.data_as(sp), ncell.ctypes.data_as(sp), own.ctypes.data_as(sp),
+                                   home.ctypes.data_as(C.POINTER(C.c_int)), off.ctypes.data_as(C.POINTER(C.c_longlong)), C.byref(tot))
+    return dict(first=first, ncell=ncell, own=own, home=home, scr_off=off, scr_floats=int(tot.value))
+
+
+def set_map_local_stride(value):
+    """The debug option "map_local_stride" of the process-default engine, the one `map_post_to_reference` runs on: entry
+    positions per window, 0: one window, -1: the default.  (An `Engine` has `debug_option`.)"""
+    if lib().scrappie_hip_debug_option(None, b"map_local_stride", int(value)) != 0:
         raise RuntimeError("debug_option: " + last_error())
 
 
@@ -1198,6 +1251,35 @@ def map_trans_to_reference(trans, sequence, viterbi=False, path=False):
     path_data = np.zeros(nblock + 1, dtype=np.int32) if path else None
     score = lib().map_crf_to_reference_viterbi(trans.data(), p_seq, len(codes), C.byref(first) if path else None, C.byref(last),
                                                path_data.ctypes.data_as(C.POINTER(C.c_int)) if path else None)
+    if np.isnan(score):
+        raise RuntimeError('An unknown error occurred during alignment: ' + last_error())
+    return score, (int(first.value) if path else None), int(last.value), path_data
+
+
+def map_post_to_reference(post, sequence, stay_pen=0, skip_pen=0, local_pen=4.0, viterbi=False, path=False):
+    """Where in `sequence` does this read lie?  A posterior of a transducer model (a `ScrappyMatrix` of log-probabilities, as
+    from `calc_post`) mapped INTO a longer base sequence: `map_post_to_sequence` with the sequence side made local -- the path
+    may enter the sequence from START at any position and leave it for END from any position; the DP runs on the GPU, one
+    workgroup per window of the sequence (k_map_local).  Returns (score, first, last, path): `first` is the lowest k-mer
+    position the path visits and `last` the highest plus one, so the read spells sequence[first:last + k - 1]; path[blk],
+    nblock entries, is the position or -1 in START / END.  Forward: (score, None, None, None); Viterbi without `path`:
+    (score, None, last, None) -- the start is known only from the traceback."""
+    _path_needs_viterbi(path, viterbi)
+    if not isinstance(post, ScrappyMatrix):
+        raise TypeError('`post` should be a ScrappyMatrix.')
+    nblock, nstate = post.shape
+    kmer_len = guess_state_properties(nstate)[1]
+    codes = np.ascontiguousarray(encode_bases(sequence, kmer_len), dtype=np.int32)
+    p_seq = codes.ctypes.data_as(C.POINTER(C.c_int))
+    if not viterbi:
+        score = lib().map_to_reference_forward(post.data(), stay_pen, skip_pen, local_pen, p_seq, len(codes))
+        if np.isnan(score):
+            raise RuntimeError('An unknown error occurred during alignment: ' + last_error())
+        return score, None, None, None
+    first, last = C.c_size_t(0), C.c_size_t(0)
+    path_data = np.zeros(nblock, dtype=np.int32) if path else None
+    score = lib().map_to_reference_viterbi(post.data(), stay_pen, skip_pen, local_pen, p_seq, len(codes), C.byref(first) if path else None,
+                                           C.byref(last), path_data.ctypes.data_as(C.POINTER(C.c_int)) if path else None)
     if np.isnan(score):
         raise RuntimeError('An unknown error occurred during alignment: ' + last_error())
     return score, (int(first.value) if path else None), int(last.value), path_data
@@ -1932,6 +2014,51 @@ class Engine(object):
         res = []
         rs = [out[i] for i in range(n)]
         for r, pth in zip(rs, _paths(rs, more=1)):
+            sc = float(r.score)
+            if np.isnan(sc) or not viterbi:
+                res.append((sc, None, None, None))
+            else:
+                res.append((sc, int(r.first) if pth is not None else None, int(r.last), pth))
+        lib().scrappie_hip_free_map_local_results(out, n)
+        return res
+
+    def map_to_reference_transducer(self, signals, references, model='rgrgr_r94', viterbi=True, path=False, stay_pen=0.0, skip_pen=0.0,
+                                    local_pen=4.0, min_prob=1e-5, tempW=1.0, tempb=1.0):
+        """Where in its reference does each read lie?  Each read (trimmed, normalised float32 signal) of a transducer model
+        mapped INTO a longer base sequence, batched (scrappie_hip_map_post_local_batch): the network and S1 run as for
+        `posterior`, the posterior stays on the device, every window of every reference is one workgroup of k_map_local.
+        `references`: one string for all reads (encoded with `encode_bases(ref, kmer_len)` and uploaded once), or one per
+        read.  Returns [(score, first, last, path)] in input order as `map_post_to_reference` gives them; score NaN (and
+        None) where a read or its reference cannot be mapped."""
+        n = len(signals)
+        _path_needs_viterbi(path, viterbi)
+        if isinstance(references, str):
+            references = [references] * n
+        elif len(references) != n:
+            raise ValueError("one reference for all signals, or one per signal")
+        h = self._models[model]
+        nstate = lib().scrappie_hip_model_states(self._h, h)
+        kmer_len = 1 if nstate == 25 else guess_state_properties(nstate)[1]      # (a flip-flop model: refused by the library)
+        rts, keep = _raw_tables(signals)
+        tgs = (_MapLocalTarget * max(n, 1))()
+        enc = {}
+        for i, sq in enumerate(references):
+            if id(sq) not in enc:
+                try:
+                    enc[id(sq)] = np.ascontiguousarray(encode_bases(sq, kmer_len), dtype=np.int32)
+                except ValueError:
+                    enc[id(sq)] = np.zeros(0, dtype=np.int32)      # mapped to NaN by the library (empty sequence)
+            codes = enc[id(sq)]
+            tgs[i].seq = codes.ctypes.data_as(C.POINTER(C.c_int))
+            tgs[i].seqlen = len(codes)
+        keep.append(enc)
+        p = self.default_params(min_prob=min_prob, tempW=tempW, tempb=tempb, stay_pen=stay_pen, skip_pen=skip_pen, local_pen=local_pen)
+        out = (_MapLocalResult * max(n, 1))()
+        if lib().scrappie_hip_map_post_local_batch(self._h, h, rts, tgs, n, C.byref(p), 1 if viterbi else 0, 1 if path else 0, out) != 0:
+            raise RuntimeError("map_post_local_batch: " + last_error())
+        res = []
+        rs = [out[i] for i in range(n)]
+        for r, pth in zip(rs, _paths(rs)):
             sc = float(r.score)
             if np.isnan(sc) or not viterbi:
                 res.append((sc, None, None, None))

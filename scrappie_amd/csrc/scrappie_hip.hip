@@ -45,6 +45,7 @@
  *   sh_eng_map_pack.inc  one read against many candidate sequences, packed into workgroups (per-read and batched)
  *   sh_eng_crf_find.inc  short sequences searched inside flip-flop (CRF) reads, packed into workgroups (per-read and batched)
  *   sh_eng_map_crf_local.inc  flip-flop (CRF) reads mapped into a longer sequence, one workgroup per window (per-read and batched)
+ *   sh_eng_map_local.inc      transducer reads mapped into a longer sequence, one workgroup per window, the posterior column staged in LDS (per-read and batched)
  *   sh_eng_squig.inc     mapping of raw signals to predicted squiggles (per-read and batched)
  *   sh_eng_sqnet.inc     prediction of squiggles from base sequences (per-read and batched)
  *   sh_eng_events.inc    event detection (per-read and batched; kernels in sh_events.h)
@@ -499,6 +500,8 @@ struct scrappie_hip_engine {
     DBuf d_mpk_rd, d_mpk_cell, d_mpk_first, d_mpk_score; HBuf h_mpk;      /* candidates in packs (sh_eng_map_pack.inc): the packs, their cell words and first cells, scores; scores on the host */
     int map_pack_cells = -1;         /* cells a pack of candidates holds (debug option "map_pack_cells"; 0: every candidate through k_map, -1: the default) */
     DpBufs dp_mcl; DBuf d_mcl_seq, d_mcl_first;      /* sequence-local CRF mapping (sh_eng_map_crf_local.inc): the windows' buffers (final state: the end cell, an int2); codes, the second pass's firsts */
+    DpBufs dp_ml; DBuf d_ml_seq, d_ml_lohi;      /* sequence-local transducer mapping (sh_eng_map_local.inc): the windows' buffers (final state: the end position and kind, an int2); codes, the second pass's (first, last) */
+    int map_local_stride = -1;       /* entry positions a window of k_map_local owns (debug option "map_local_stride"; 0: one window, -1: the default) */
     DBuf d_cfd_rd, d_cfd_cell, d_cfd_score, d_cfd_pos, d_cfd_call; HBuf h_cfd;      /* motifs searched inside flip-flop reads (sh_eng_crf_find.inc): the packs, their cell words, scores, (begin, end), call scores; results on the host */
     int crf_find_cells = -1;         /* cells a pack of motifs holds (debug option "crf_find_cells"; -1: the default) */
     int map_crf_local_stride = -1;   /* start cells a window of k_map_crf_local owns (debug option "map_crf_local_stride"; 0: one window, -1: the default) */
@@ -652,6 +655,7 @@ extern "C" scrappie_hip_params scrappie_hip_default_params(void) {
 #include "sh_eng_map_pack.inc"      /* one read against many candidate sequences (sh_map_pack.h): scrappie_hip_map_multi_batch, scrappie_hip_map_post_multi */
 #include "sh_eng_crf_find.inc"      /* short sequences searched inside flip-flop reads, packed into workgroups (sh_crf_find.h): find_crf_sequences_viterbi, scrappie_hip_find_batch */
 #include "sh_eng_map_crf_local.inc"      /* flip-flop reads mapped into a longer sequence, cut into windows (sh_map_crf_local.h): map_crf_to_reference_*, scrappie_hip_map_local_batch */
+#include "sh_eng_map_local.inc"      /* transducer reads mapped into a longer sequence, cut into windows (sh_map_local.h): map_to_reference_*, scrappie_hip_map_post_local_batch */
 #include "sh_eng_squig.inc"      /* squiggle matching (sh_squig.h): squiggle_match_* on the process-default engine, scrappie_hip_squiggle_match_batch */
 #include "sh_eng_sqnet.inc"      /* squiggle prediction (sh_sqnet.h): squiggle_r94 and its relatives on the process-default engine, scrappie_hip_squiggle_predict_batch */
 #include "sh_eng_events.inc"      /* event detection (sh_events.h): detect_events on the process-default engine, scrappie_hip_detect_events_batch; `scrappie events` for a batch (scrappie_hip_basecall_events_batch) */

@@ -14,6 +14,9 @@
  * in ONE scrappie_hip_map_local_batch call (k_map_crf_local: one workgroup per window of the sequence); the usual header line with
  * `bases first..last` added -- the read spells the record's bases [first, last) -- and nblock + 1 records whose pos is in the
  * record's coordinates (first - 1 while no base is emitted).  Without the option nothing changes.
+ * --within (transducer models): the same question for the default models -- all pairs in ONE scrappie_hip_map_post_local_batch call
+ * (k_map_local); the transducer output (nblock records, pos -1 in START / END) with `states first..last` added to the header line:
+ * the path visits the record's k-mers first .. last - 1.  Without the option nothing changes.
  * --find (flip-flop models): every record of a pair's FASTA is a motif -- a barcode, an adapter, a primer -- searched INSIDE the
  * pair's read.  All pairs in ONE scrappie_hip_find_batch call (k_crf_find: the motifs packed into workgroups); per pair a header
  * line and a table record / name / score / delta / begin / end.  Without the option nothing changes.
@@ -58,6 +61,13 @@ static void seqmappy_usage(FILE *fh) {
           "                             best local placement of the whole read.  `bases first..last` is added to the header\n"
           "                             line -- the read spells bases [first, last) of the record -- and pos is in the\n"
           "                             record's coordinates, first - 1 while none.  Flip-flop (CRF) models only.\n"
+          "      --within               --inside for transducer models (the default rgrgr_r94 and its relatives): the best local\n"
+          "                             placement of the read in a reference longer than it, under --stay, --skip and\n"
+          "                             --localpen.  `states first..last` is added to the header line -- the path visits the\n"
+          "                             record's k-mers first .. last - 1, so the read spells bases [first, last + k - 1) -- and\n"
+          "                             one record is written per block: pos in the record's coordinates, -1 before the read\n"
+          "                             enters the sequence and after it has left.  Not with a flip-flop (CRF) model, --inside,\n"
+          "                             --all-records or --find.\n"
           "      --find                 Search every record of the fasta (a barcode, an adapter, a primer) INSIDE the read:\n"
           "                             per pair a line `# fast5 to fasta -- N records, call score S over B blocks, best K`\n"
           "                             and a table record / name / score / delta / begin / end.  score: the best path of\n"
@@ -172,8 +182,9 @@ static int seqmappy_find(scrappie_hip_engine *e, int h, const scrappie_hip_param
     return rc;
 }
 
-/* --inside: pair i's read into the first record of its FASTA, all pairs in one scrappie_hip_map_local_batch call */
-static int seqmappy_inside(scrappie_hip_engine *e, int h, const scrappie_hip_params *p, char **fasta, size_t npair, FILE *out,
+/* --inside: pair i's read into the first record of its FASTA, all pairs in one scrappie_hip_map_local_batch call; --within (klen: the
+ * transducer model's k-mer length, 0 for --inside): the same through scrappie_hip_map_post_local_batch */
+static int seqmappy_inside(scrappie_hip_engine *e, int h, int klen, const scrappie_hip_params *p, char **fasta, size_t npair, FILE *out,
                            int trim_start, int trim_end, int varseg_chunk, float varseg_thresh) {
     raw_table *rts = calloc(npair, sizeof *rts);
     scrappie_hip_map_local_target *tg = calloc(npair, sizeof *tg);
@@ -185,15 +196,15 @@ static int seqmappy_inside(scrappie_hip_engine *e, int h, const scrappie_hip_par
         struct cli_fasta *rec = NULL;       /* the first record of the file */
         size_t nrec = 0;
         if (cli_read_fasta(fa, &rec, &nrec, 1) || nrec == 0 || !rec[0].seq || rec[0].n == 0) { fprintf(stderr, "scrappie: Failed to open \"%s\" for input.\n", fa); cli_free_fasta(rec, nrec); rc = EXIT_FAILURE; continue; }
-        const size_t n = rec[0].n;
-        codes[i] = encode_bases_to_integers(rec[0].seq, n, 1);
+        const size_t n = rec[0].n, k = klen ? (size_t)klen : 1;
+        codes[i] = encode_bases_to_integers(rec[0].seq, n, k);
         cli_free_fasta(rec, nrec);
         if (!codes[i]) { fprintf(stderr, "scrappie: cannot encode the sequence of \"%s\": %s\n", fa, scrappie_hip_last_error()); rc = EXIT_FAILURE; continue; }
-        tg[i].seq = codes[i]; tg[i].seqlen = n;
+        tg[i].seq = codes[i]; tg[i].seqlen = n - k + 1;
         rts[i] = cli_load_read(f5, trim_start, trim_end, varseg_chunk, varseg_thresh, 1);
         if (!rts[i].raw) { fprintf(stderr, "scrappie: Failed to open \"%s\" for input and trim signal.\n", f5); rc = EXIT_FAILURE; continue; }
     }
-    if (scrappie_hip_map_local_batch(e, h, rts, tg, npair, p, 1, 1, res) != 0) {
+    if ((klen ? scrappie_hip_map_post_local_batch : scrappie_hip_map_local_batch)(e, h, rts, tg, npair, p, 1, 1, res) != 0) {
         fprintf(stderr, "scrappie: %s\n", scrappie_hip_last_error());
         rc = EXIT_FAILURE;
     } else {
@@ -202,10 +213,10 @@ static int seqmappy_inside(scrappie_hip_engine *e, int h, const scrappie_hip_par
             if (!res[i].path) { fprintf(stderr, "scrappie: Failed to map \"%s\" to \"%s\"\n", fasta[2 * i + 1], fasta[2 * i]); rc = EXIT_FAILURE; continue; }
             const float score = res[i].score;
             const size_t nblock = res[i].nblock;
-            fprintf(out, "# %s to %s -- score %f over %zu blocks (%f per block) bases %zu..%zu\n", fasta[2 * i + 1], fasta[2 * i], -score, nblock, -score / nblock,
-                    res[i].first, res[i].last);
+            fprintf(out, "# %s to %s -- score %f over %zu blocks (%f per block) %s %zu..%zu\n", fasta[2 * i + 1], fasta[2 * i], -score, nblock, -score / nblock,
+                    klen ? "states" : "bases", res[i].first, res[i].last);
             fprintf(out, "block\tpos\n");
-            for (size_t b = 0; b <= nblock; b++) fprintf(out, "%zu\t%d\n", b, res[i].path[b]);
+            for (size_t b = 0; b < nblock + (klen ? 0 : 1); b++) fprintf(out, "%zu\t%d\n", b, res[i].path[b]);
         }
     }
     scrappie_hip_free_map_local_results(res, npair);
@@ -215,13 +226,13 @@ static int seqmappy_inside(scrappie_hip_engine *e, int h, const scrappie_hip_par
 }
 
 int main_seqmappy(int argc, char **argv) {
-    enum { O_SEG = 256, O_T1, O_T2, O_LIC, O_MODEL, O_MFILE, O_DEV, O_ALL, O_INSIDE, O_FIND };
+    enum { O_SEG = 256, O_T1, O_T2, O_LIC, O_MODEL, O_MFILE, O_DEV, O_ALL, O_INSIDE, O_FIND, O_WITHIN };
     static const struct option lo[] = {
         {"localpen", 1, 0, 'l'}, {"min_prob", 1, 0, 'm'}, {"output", 1, 0, 'o'}, {"prefix", 1, 0, 'p'},
         {"segmentation", 1, 0, O_SEG}, {"skip", 1, 0, 's'}, {"stay", 1, 0, 'y'}, {"trim", 1, 0, 't'},
         {"temperature1", 1, 0, O_T1}, {"temperature2", 1, 0, O_T2}, {"licence", 0, 0, O_LIC}, {"license", 0, 0, O_LIC},
-        {"model", 1, 0, O_MODEL}, {"model-file", 1, 0, O_MFILE}, {"device", 1, 0, O_DEV}, {"all-records", 0, 0, O_ALL}, {"inside", 0, 0, O_INSIDE}, {"find", 0, 0, O_FIND}, {"help", 0, 0, '?'}, {0, 0, 0, 0}};
-    int all_records = 0, inside = 0, find = 0;
+        {"model", 1, 0, O_MODEL}, {"model-file", 1, 0, O_MFILE}, {"device", 1, 0, O_DEV}, {"all-records", 0, 0, O_ALL}, {"inside", 0, 0, O_INSIDE}, {"find", 0, 0, O_FIND}, {"within", 0, 0, O_WITHIN}, {"help", 0, 0, '?'}, {0, 0, 0, 0}};
+    int all_records = 0, inside = 0, find = 0, within = 0;
     /* defaults: scrappie_seqmappy.c:62-78 */
     scrappie_hip_params p = scrappie_hip_default_params();
     p.local_pen = 4.0f; p.min_prob = 1e-5f; p.stay_pen = 0.0f; p.skip_pen = 0.0f; p.tempW = 1.0f; p.tempb = 1.0f;
@@ -256,6 +267,7 @@ int main_seqmappy(int argc, char **argv) {
         case O_ALL: all_records = 1; break;
         case O_INSIDE: inside = 1; break;
         case O_FIND: find = 1; break;
+        case O_WITHIN: within = 1; break;
         default: seqmappy_usage(stderr); return EXIT_FAILURE;
         }
     }
@@ -263,6 +275,15 @@ int main_seqmappy(int argc, char **argv) {
     if (nargs <= 0) { seqmappy_usage(stderr); return EXIT_FAILURE; }
     if (nargs % 2) { fprintf(stderr, "scrappie: fast5 file is a required argument\n"); return EXIT_FAILURE; }    /* scrappie_seqmappy.c:153 */
     const size_t npair = (size_t)nargs / 2;
+    if (within && (inside || all_records || find)) {
+        fprintf(stderr, "scrappie: --within maps a read of a transducer model into the first record of its fasta; it cannot be combined with %s\n",
+                inside ? "--inside" : all_records ? "--all-records" : "--find");
+        return EXIT_FAILURE;
+    }
+    if (within && get_raw_model(model) == SCRAPPIE_MODEL_RNNRF_R9_4) {
+        fprintf(stderr, "scrappie: --within maps transducer models only; \"%s\" is a flip-flop (CRF) model (--inside)\n", model);
+        return EXIT_FAILURE;
+    }
     if (find && inside) { fprintf(stderr, "scrappie: --find searches the records of a fasta inside the read; it cannot be combined with --inside\n"); return EXIT_FAILURE; }
     if (find && all_records) { fprintf(stderr, "scrappie: --find searches every record of a fasta already; it cannot be combined with --all-records\n"); return EXIT_FAILURE; }
     if (find && get_raw_model(model) != SCRAPPIE_MODEL_RNNRF_R9_4) {
@@ -298,7 +319,15 @@ int main_seqmappy(int argc, char **argv) {
     if (inside) {
         int rc = EXIT_FAILURE;
         if (!crf) fprintf(stderr, "scrappie: --inside maps flip-flop (CRF) models only; \"%s\" is a transducer model\n", model);
-        else rc = seqmappy_inside(e, h, &p, fasta, npair, out, trim_start, trim_end, varseg_chunk, varseg_thresh);
+        else rc = seqmappy_inside(e, h, 0, &p, fasta, npair, out, trim_start, trim_end, varseg_chunk, varseg_thresh);
+        if (out != stdout) fclose(out);
+        scrappie_hip_engine_destroy(e);
+        return rc;
+    }
+    if (within) {
+        int rc = EXIT_FAILURE;
+        if (crf) fprintf(stderr, "scrappie: --within maps transducer models only; \"%s\" is a flip-flop (CRF) model (--inside)\n", model);
+        else rc = seqmappy_inside(e, h, klen, &p, fasta, npair, out, trim_start, trim_end, varseg_chunk, varseg_thresh);
         if (out != stdout) fclose(out);
         scrappie_hip_engine_destroy(e);
         return rc;

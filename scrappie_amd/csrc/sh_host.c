@@ -837,6 +837,66 @@ long long scrappie_hip_map_crf_local_plan(size_t seqlen, size_t nblock, long str
     return (long long)nwin;
 }
 
+/* Windows of the sequence-local transducer mapping (k_map_local, sh_map_local.h).  A window keeps a head of 32 words and two
+ * columns of the posterior (nr states, rounded up to whole 16-byte pieces) in LDS; in the LDS home also two score rows, the END
+ * row and the codes, each of ncell entries rounded up to a multiple of 4. */
+size_t sh_map_local_scr_lds_bytes(size_t nr) { return (32 + 2 * ((nr + 3) & ~(size_t)3)) * 4; }
+size_t sh_map_local_lds_bytes(size_t ncell, size_t nr) { return sh_map_local_scr_lds_bytes(nr) + 4 * ((ncell + 3) & ~(size_t)3) * 4; }
+
+/* the most cells a window of a posterior of nr states keeps in LDS; 0 where the columns alone exceed it */
+size_t scrappie_hip_map_local_max_cells(size_t nr) {
+    const size_t fixed = sh_map_local_scr_lds_bytes(nr);
+    return fixed >= SH_MAP_LDS ? 0 : ((SH_MAP_LDS - fixed) / 16) & ~(size_t)3;      /* (a row is a multiple of 4 entries) */
+}
+
+/* The stride in positions a sequence of seqlen states and a read of nblock blocks are cut with.  A path that enters at a position
+ * advances at most reach = 2 (nblock - 1) positions, so a window is stride + reach cells.  stride > 0: that many; 0: one window;
+ * < 0: the default -- while a window that owns more than half of its cells (stride >= reach + 1) fits LDS: a window of
+ * SH_MAP_LOCAL_CELLS cells where that leaves it the SH_MAP_LOCAL_STRIDE entry positions it was measured with or more
+ * (profiles/map_local_rate.txt decided), the largest LDS-resident window for longer reads; and 2 nblock, with the rows in device
+ * scratch, beyond.  Never more than the seqlen positions there are. */
+size_t scrappie_hip_map_local_stride(size_t seqlen, size_t nblock, size_t nr, long stride) {
+    const size_t maxc = scrappie_hip_map_local_max_cells(nr), reach = nblock ? 2 * (nblock - 1) : 0;
+    size_t s;
+    if (stride > 0) s = (size_t)stride;
+    else if (stride == 0) s = seqlen;
+    else if (2 * reach + 1 > maxc) s = 2 * nblock;
+    else if (reach + SH_MAP_LOCAL_STRIDE <= SH_MAP_LOCAL_CELLS && SH_MAP_LOCAL_CELLS <= maxc) s = SH_MAP_LOCAL_CELLS - reach;
+    else s = maxc - reach;
+    if (s == 0) s = 1;
+    return s < seqlen ? s : seqlen;
+}
+
+/* The cut: window w owns the entry positions [w s, min((w + 1) s, seqlen)) and holds the cells [w s, min(w s + s - 1 + 2 (nblock - 1),
+ * seqlen - 1)] -- first[w], own[w] and ncell[w]; home[w]: 0 rows and codes in LDS, 1 rows in device scratch, at float offset
+ * scr_off[w] (-1 in LDS) of *scr_floats floats in all, 3 * 4 ceil(ncell / 4) per window: whole 16-byte pieces.  Every array may be
+ * NULL; those given hold cap entries, and only the first cap windows are written.  Returns the number of windows, 0 on an empty
+ * sequence, no blocks, fewer than 2 states or a sequence or read beyond 2^30. */
+long long scrappie_hip_map_local_plan(size_t seqlen, size_t nblock, size_t nr, long stride, size_t cap, size_t *first, size_t *ncell, size_t *own,
+                                      int *home, long long *scr_off, long long *scr_floats) {
+    if (scr_floats) *scr_floats = 0;
+    if (seqlen == 0 || nblock == 0 || nr < 2 || seqlen > ((size_t)1 << 30) || nblock > ((size_t)1 << 30)) return 0;
+    const size_t s = scrappie_hip_map_local_stride(seqlen, nblock, nr, stride), reach = 2 * (nblock - 1);
+    const size_t nwin = (seqlen + s - 1) / s;
+    long long scr = 0;
+    for (size_t w = 0; w < nwin; w++) {
+        const size_t c0 = w * s;
+        const size_t left = seqlen - c0;                        /* cells from c0 to the end */
+        const size_t nc = s + reach < left ? s + reach : left;  /* cells a path that enters in the window can be in */
+        const int scratch = sh_map_local_lds_bytes(nc, nr) > SH_MAP_LDS;
+        if (w < cap) {
+            if (first) first[w] = c0;
+            if (ncell) ncell[w] = nc;
+            if (own) own[w] = s < left ? s : left;
+            if (home) home[w] = scratch;
+            if (scr_off) scr_off[w] = scratch ? scr : -1;
+        }
+        if (scratch) scr += (long long)(3 * ((nc + 3) & ~(size_t)3));
+    }
+    if (scr_floats) *scr_floats = scr;
+    return (long long)nwin;
+}
+
 /* Packs of motifs searched inside a flip-flop read (k_crf_find, sh_crf_find.h).  A pack of ncell cells keeps two columns of
  * transitions and, per cell and the spare slot behind them, two buffers of a value and a stay value (16 bytes) and a word (4);
  * with positions two buffers of two payloads more (16): 20 or 36 bytes per cell. */

@@ -23,6 +23,12 @@ size_t sh_map_pack_lds_bytes(size_t ncell, size_t ncand);
 /* windows of the sequence-local CRF mapping (sh_host.c; k_map_crf_local, sh_map_crf_local.h): the dynamic LDS a window of ncell cells takes */
 size_t sh_map_crf_local_lds_bytes(size_t ncell);
 #define SH_MAP_CRF_LOCAL_CELLS 2034      /* cells of a window at the default stride: 40 952 bytes of LDS, four workgroups per compute unit (160 KB), eight chunks of 256 threads; the fastest measured (profiles/map_crf_local_rate.txt) */
+/* windows of the sequence-local transducer mapping (sh_host.c; k_map_local, sh_map_local.h): the dynamic LDS a window of ncell cells of a posterior of
+ * nr states takes in the LDS home (head, two columns, three rows and the codes), and in the scratch home (head and columns) */
+size_t sh_map_local_lds_bytes(size_t ncell, size_t nr);
+size_t sh_map_local_scr_lds_bytes(size_t nr);
+#define SH_MAP_LOCAL_CELLS 2798      /* cells of a window at the default stride: with 1025 states 53 152 bytes of LDS, three workgroups per compute unit (160 KB); the fastest measured (profiles/map_local_rate.txt) */
+#define SH_MAP_LOCAL_STRIDE 1200     /* the entry positions such a window owned where it was measured (800 blocks): a longer read, which would leave it fewer, takes the largest LDS-resident window */
 /* packs of motifs searched inside a flip-flop read (sh_host.c; k_crf_find, sh_crf_find.h): the dynamic LDS a pack of ncell cells takes, with or without positions */
 size_t sh_crf_find_lds_bytes(size_t ncell, int pos);
 /* squiggle matching (sh_host.c): the tables of decode.c:1055-1099 from the host's libm; tab holds 5 npos + 4 floats */
