@@ -547,6 +547,38 @@ long long scrappie_hip_map_crf_plan_scratch(const size_t *seqlen, const size_t *
 /* launches of each k_map_crf form in this process, all engines together: index (viterbi ? 4 : 0) | (tiled ? 2 : 0) | (scratch ? 1 : 0) */
 void scrappie_hip_map_crf_form_counts(uint64_t forms[8]);
 
+/* One read of a flip-flop (CRF) model against many candidate sequences (sh_eng_map_crf_pack.inc; k_map_crf_pack, sh_map_crf_pack.h): which of
+ * these alleles, haplotypes or references is this read, is this edit of the call better than the call?  scrappie_hip_map_multi_batch's
+ * question for the model whose score is a proper path score.  The network and k_crf run ONCE per read; reads[i] is mapped, unbanded, to every
+ * cands[i].cand[k] (base codes 0..3), the candidates of a read packed end to end into workgroups of k_map_crf_pack on the transitions where
+ * k_crf left them (a candidate of more than scrappie_hip_map_crf_pack_max_cells() - 1 bases takes k_map_crf on the same transitions).
+ * out[i].score[k] (malloc'd, ncand floats; freed by scrappie_hip_free_map_multi_results) is the score map_crf_to_sequence_viterbi / _forward
+ * give for that pair, bit for bit what scrappie_hip_map_batch gives.  best: the index of the highest finite score, the lowest index on a tie,
+ * -1 where there is none.  With viterbi and want_path, path is the best candidate's Viterbi path (malloc'd, nblock + 1 int32, as
+ * scrappie_hip_map_batch gives for that pair) from a second pass of k_map_crf on that candidate alone while the transitions are still resident;
+ * NULL otherwise.  stay_pen, skip_pen and local_pen are not used.  A candidate gets NAN, and its neighbours are scored, where it has no or an
+ * empty sequence, a code that is not a base, poslow / poshigh set ("bands are not part of this call"), or no admissible path (seqlen >
+ * nblock + 1: a score below -1e30 / 2); the first such reason is the error text.  A read that cannot run (too short, out of the operand range,
+ * over the launch budget) gets every score NAN and best -1, the other reads untouched.  ncand == 0 is a read with no scores.  Several reads
+ * may point at the same cand array: it is checked, packed and uploaded once.  A transducer model: -1 with a text that names
+ * scrappie_hip_map_multi_batch.  Locks, parameters and the cut into launch groups as scrappie_hip_map_batch with a CRF model, a read adding its
+ * candidates' tables and, with a path, the second pass on its longest candidate; scrappie_hip_map_timing covers these calls
+ * ([1] k_map_crf_pack + k_map_crf, [2] walk + results). */
+int scrappie_hip_map_crf_multi_batch(scrappie_hip_engine *e, int model, const raw_table *reads, const scrappie_hip_map_candidates *cands,
+                                     size_t n, const scrappie_hip_params *p, int viterbi, int want_path, scrappie_hip_map_multi_result *out);
+/* per-read surface, process-default engine: a host matrix as map_crf_to_sequence_viterbi takes it against ncand candidates, score[k] for cand[k]
+ * (NAN where that candidate cannot be mapped, is banded or has no admissible path; the first reason is the error text).  0, or -1 with the reason. */
+int scrappie_hip_map_trans_multi(const_scrappie_matrix trans, const scrappie_hip_map_target *cand, size_t ncand, int viterbi, float *score);
+/* The packing on the host, no device (sh_host.c): candidates of seqlen[k] bases (seqlen[k] + 1 cells: p = 0 .. seqlen bases emitted) go into
+ * packs of at most pack_cells cells in input order; pack[k] the pack, cell[k] the candidate's first cell in it; pack[k] = -1 where the
+ * candidate's cells exceed scrappie_hip_map_crf_pack_max_cells() (what k_map_crf_pack's LDS holds: 64 + 5 (cells + 1) words within 64 KB) --
+ * it takes k_map_crf and closes no pack.  Returns the number of packs.  The debug option "map_crf_pack_cells" sets an engine's pack_cells
+ * (0: every candidate through k_map_crf, one workgroup each; -1: the default; a NULL engine: the process-default engine). */
+long scrappie_hip_map_crf_pack_plan(const size_t *seqlen, size_t ncand, size_t pack_cells, int *pack, long long *cell);
+size_t scrappie_hip_map_crf_pack_max_cells(void);
+/* launches of each k_map_crf_pack form in this process, all engines together: index (viterbi ? 2 : 0) | (tiled ? 1 : 0) */
+void scrappie_hip_map_crf_pack_form_counts(uint64_t forms[4]);
+
 /* Reads of a flip-flop (CRF) model mapped INTO a longer sequence (k_map_crf_local, sh_map_crf_local.h; sh_eng_map_crf_local.inc): where
  * in this sequence does the read lie, with what score and along what path.  Cells, transitions and the block recursion are those
  * above; the path may begin in any cell (entry 0: S[p] = 0 for p = 0 .. seqlen, B[p] = 0 for p = 1 .. seqlen, as decode_crf starts

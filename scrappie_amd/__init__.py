@@ -363,6 +363,15 @@ def lib():
     L.scrappie_hip_map_pack_max_cells.argtypes = []
     L.scrappie_hip_map_pack_form_counts.restype = None
     L.scrappie_hip_map_pack_form_counts.argtypes = [C.POINTER(C.c_uint64)]
+    L.scrappie_hip_map_crf_multi_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(_RawTable), C.POINTER(_MapCandidates), C.c_size_t,
+                                                   C.POINTER(Params), C.c_int, C.c_int, C.POINTER(_MapMultiResult)]
+    L.scrappie_hip_map_trans_multi.argtypes = [PM, C.POINTER(_MapTarget), C.c_size_t, C.c_int, fp]
+    L.scrappie_hip_map_crf_pack_plan.restype = C.c_long
+    L.scrappie_hip_map_crf_pack_plan.argtypes = [sp, C.c_size_t, C.c_size_t, ip, C.POINTER(C.c_longlong)]
+    L.scrappie_hip_map_crf_pack_max_cells.restype = C.c_size_t
+    L.scrappie_hip_map_crf_pack_max_cells.argtypes = []
+    L.scrappie_hip_map_crf_pack_form_counts.restype = None
+    L.scrappie_hip_map_crf_pack_form_counts.argtypes = [C.POINTER(C.c_uint64)]
     L.squiggle_match_viterbi.restype = C.c_float
     L.squiggle_match_viterbi.argtypes = [_RawTable, C.c_float, PM, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_int32)]
     L.squiggle_match_forward.restype = C.c_float
@@ -630,6 +639,37 @@ def set_map_pack_cells(value):
     """The debug option "map_pack_cells" of the process-default engine, the one `map_post_to_sequences` runs on: cells per pack
     of candidates, 0: every candidate through k_map, -1: the default.  (An `Engine` has `debug_option`.)"""
     if lib().scrappie_hip_debug_option(None, b"map_pack_cells", int(value)) != 0:
+        raise RuntimeError("debug_option: " + last_error())
+
+
+def map_crf_pack_form_counts():
+    """Launches of each k_map_crf_pack form in this process so far (scrappie_hip_map_crf_pack_form_counts): {(viterbi, tiled): n}."""
+    q = (C.c_uint64 * 4)()
+    lib().scrappie_hip_map_crf_pack_form_counts(q)
+    return {(bool(k & 2), bool(k & 1)): int(q[k]) for k in range(4)}
+
+
+def map_crf_pack_max_cells():
+    """The most cells (a candidate of L bases takes L + 1) one pack of k_map_crf_pack holds; a longer candidate takes k_map_crf."""
+    return int(lib().scrappie_hip_map_crf_pack_max_cells())
+
+
+def map_crf_pack_plan(lengths, pack_cells):
+    """The packing of candidates of `lengths` bases into packs of at most `pack_cells` cells (host arithmetic, no device;
+    scrappie_hip_map_crf_pack_plan): (pack, cell, npack) -- each candidate's pack (-1: too long for any, it takes k_map_crf) and
+    its first cell there."""
+    a = np.ascontiguousarray(lengths, dtype=np.uintp)
+    pack = np.zeros(len(a), dtype=np.int32)
+    cell = np.zeros(len(a), dtype=np.longlong)
+    n = lib().scrappie_hip_map_crf_pack_plan(a.ctypes.data_as(C.POINTER(C.c_size_t)), len(a), int(pack_cells), pack.ctypes.data_as(C.POINTER(C.c_int)),
+                                             cell.ctypes.data_as(C.POINTER(C.c_longlong)))
+    return pack, cell, int(n)
+
+
+def set_map_crf_pack_cells(value):
+    """The debug option "map_crf_pack_cells" of the process-default engine, the one `map_trans_to_sequences` runs on: cells per
+    pack of candidates, 0: every candidate through k_map_crf, -1: the default.  (An `Engine` has `debug_option`.)"""
+    if lib().scrappie_hip_debug_option(None, b"map_crf_pack_cells", int(value)) != 0:
         raise RuntimeError("debug_option: " + last_error())
 
 
@@ -1225,6 +1265,46 @@ def map_trans_to_sequence(trans, sequence, viterbi=False, path=False, bands=None
     if np.isnan(score):
         raise RuntimeError('An unknown error occurred during alignment: ' + last_error())
     return score, path_data
+
+
+def _crf_targets(sequences):
+    """The ctypes scrappie_hip_map_target array of `sequences` (base strings, or arrays of base codes, which the library checks)
+    and what keeps its memory alive; a string that cannot be encoded becomes an empty sequence, which the library answers with
+    NaN."""
+    tgs = (_MapTarget * max(len(sequences), 1))()
+    keep = []
+    for i, sq in enumerate(sequences):
+        if isinstance(sq, str):
+            try:
+                codes = np.ascontiguousarray(encode_bases(sq, 1), dtype=np.int32) if len(sq) else np.zeros(0, dtype=np.int32)
+            except ValueError:
+                codes = np.zeros(0, dtype=np.int32)
+        else:
+            codes = np.ascontiguousarray(sq, dtype=np.int32)
+        keep.append(codes)
+        tgs[i].seq = codes.ctypes.data_as(C.POINTER(C.c_int))
+        tgs[i].seqlen = len(codes)
+    return tgs, keep
+
+
+def map_trans_to_sequences(trans, sequences, viterbi=False):
+    """`map_trans_to_sequence`'s score of a read's transitions under a flip-flop (CRF) model (a `ScrappyMatrix` of 25 rows)
+    against each of `sequences` (base strings, or arrays of base codes 0..3), unbanded, in one pass on the GPU: the candidates
+    are packed into workgroups of k_map_crf_pack (scrappie_hip_map_trans_multi).  Returns a float32 array of scores, one per
+    sequence, bit for bit what `map_trans_to_sequence` gives for it; NaN where a sequence cannot be mapped (empty, not bases,
+    more bases than the read has entries: `last_error()` names the first)."""
+    if not isinstance(trans, ScrappyMatrix):
+        raise TypeError('`trans` should be a ScrappyMatrix.')
+    nblock, nstate = trans.shape
+    if nstate != 25:
+        raise ValueError('`trans` should hold the 25 transitions of a flip-flop (CRF) model per block.')
+    sequences = list(sequences)
+    tgs, keep = _crf_targets(sequences)
+    score = np.full(len(sequences), np.nan, dtype=np.float32)
+    if lib().scrappie_hip_map_trans_multi(trans.data(), tgs, len(sequences), 1 if viterbi else 0,
+                                          score.ctypes.data_as(C.POINTER(C.c_float))) != 0:
+        raise RuntimeError('An unknown error occurred during alignment: ' + last_error())
+    return score
 
 
 def map_trans_to_reference(trans, sequence, viterbi=False, path=False):
@@ -1975,6 +2055,33 @@ class Engine(object):
         res = []
         rs = [out[i] for i in range(n)]
         for r, pth in zip(rs, _paths(rs)):
+            sc = np.ctypeslib.as_array(r.score, shape=(r.ncand,)).copy() if r.ncand else np.zeros(0, dtype=np.float32)
+            res.append((sc, int(r.best), pth))
+        lib().scrappie_hip_free_map_multi_results(out, n)
+        return res
+
+    def map_to_sequences_crf(self, signals, candidates, model='rnnrf_r94', viterbi=True, path=False, min_prob=1e-5, tempW=1.0, tempb=1.0):
+        """Which of these sequences is this read, under a flip-flop (CRF) model?  Each read (trimmed, normalised float32 signal)
+        against every one of its candidate base sequences, unbanded: the network and k_crf run once per read, the candidates
+        are packed into workgroups of k_map_crf_pack on the resident transitions (scrappie_hip_map_crf_multi_batch).
+        `candidates`: a list of base strings shared by every read (encoded once), or one list of strings per read.  Returns
+        [(scores, best, path or None)] in input order: the float32 scores as `map_to_sequence(model='rnnrf_r94')` gives them
+        (NaN where a candidate, or the read, cannot be mapped), the index of the highest (the lowest index on a tie, -1:
+        none) and, with `path`, the Viterbi path of that candidate, nblock + 1 entries."""
+        n = len(signals)
+        _path_needs_viterbi(path, viterbi)
+        candidates, shared = _per_read_lists(candidates, n, 'candidates')
+        h = self._models[model]
+        rts, keep = _raw_tables(signals)
+        cds, kept = _per_read_sets(candidates, shared, n, _crf_targets)
+        keep += kept
+        p = self.default_params(min_prob=min_prob, tempW=tempW, tempb=tempb)
+        out = (_MapMultiResult * max(n, 1))()
+        if lib().scrappie_hip_map_crf_multi_batch(self._h, h, rts, cds, n, C.byref(p), 1 if viterbi else 0, 1 if path else 0, out) != 0:
+            raise RuntimeError("map_crf_multi_batch: " + last_error())
+        res = []
+        rs = [out[i] for i in range(n)]
+        for r, pth in zip(rs, _paths(rs, more=1)):
             sc = np.ctypeslib.as_array(r.score, shape=(r.ncand,)).copy() if r.ncand else np.zeros(0, dtype=np.float32)
             res.append((sc, int(r.best), pth))
         lib().scrappie_hip_free_map_multi_results(out, n)

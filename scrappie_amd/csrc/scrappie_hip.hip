@@ -37,12 +37,13 @@
  *   sh_eng_surface.inc   the reference's per-read functions: one batch function per family, run by the queue or with a batch of one
  *   sh_eng_cut.inc       what the engines below share: a call cut into launches that fit the device (LaunchCut), per-read DP
  *                        records through a kernel with two homes (dp_order / dp_launch / dp_collect)
- *   sh_eng_post.inc      what the five engines on a launch group's posterior or transitions share: the batch call and its memory model
+ *   sh_eng_post.inc      what the engines on a launch group's posterior or transitions share: the batch call and its memory model
  *                        (PostCall), the launch group's stage (post_group), one plan and runner for two homes (DpPlan / dp_run), sets of
  *                        short sequences in packs (PackSet / PackLaunch), a host matrix's upload, the two-span timer
  *   sh_eng_map_crf.inc   mapping of flip-flop (CRF) reads to base sequences (per-read; the launch group of the batched call)
  *   sh_eng_map.inc       block-based mapping of posteriors to sequences (per-read and batched)
  *   sh_eng_map_pack.inc  one read against many candidate sequences, packed into workgroups (per-read and batched)
+ *   sh_eng_map_crf_pack.inc  one flip-flop (CRF) read against many candidate sequences, packed into workgroups (per-read and batched)
  *   sh_eng_crf_find.inc  short sequences searched inside flip-flop (CRF) reads, packed into workgroups (per-read and batched)
  *   sh_eng_map_crf_local.inc  flip-flop (CRF) reads mapped into a longer sequence, one workgroup per window (per-read and batched)
  *   sh_eng_map_local.inc      transducer reads mapped into a longer sequence, one workgroup per window, the posterior column staged in LDS (per-read and batched)
@@ -504,6 +505,8 @@ struct scrappie_hip_engine {
     int map_local_stride = -1;       /* entry positions a window of k_map_local owns (debug option "map_local_stride"; 0: one window, -1: the default) */
     DBuf d_cfd_rd, d_cfd_cell, d_cfd_score, d_cfd_pos, d_cfd_call; HBuf h_cfd;      /* motifs searched inside flip-flop reads (sh_eng_crf_find.inc): the packs, their cell words, scores, (begin, end), call scores; results on the host */
     int crf_find_cells = -1;         /* cells a pack of motifs holds (debug option "crf_find_cells"; -1: the default) */
+    DBuf d_mcp_rd, d_mcp_cell, d_mcp_score; HBuf h_mcp;      /* candidates of flip-flop reads in packs (sh_eng_map_crf_pack.inc): the packs, their cell words, scores; scores on the host */
+    int map_crf_pack_cells = -1;     /* cells a pack of candidates of a flip-flop read holds (debug option "map_crf_pack_cells"; 0: every candidate through k_map_crf, -1: the default) */
     int map_crf_local_stride = -1;   /* start cells a window of k_map_crf_local owns (debug option "map_crf_local_stride"; 0: one window, -1: the default) */
     double map_ms[3] = {0, 0, 0};    /* scrappie_hip_map_batch: network + S1, k_map, k_map_walk + results, summed over the last call's launch groups */
     DpBufs dp_sq; DBuf d_sq_sig, d_sq_tab;       /* squiggle matching (sh_eng_squig.inc): the records' buffers; signals, tables */
@@ -649,10 +652,11 @@ extern "C" scrappie_hip_params scrappie_hip_default_params(void) {
 #include "sh_eng_debug.inc"      /* measurement / test hooks: decoder and trunk inputs, debug_option / debug_fetch / debug_stitch */
 #include "sh_eng_surface.inc"      /* the reference's per-read functions: posterior / trunk on an explicit engine, the process-default engine, decode_transducer, decode_crf; all three coalesced (sh_coalesce.h) */
 #include "sh_eng_cut.inc"      /* shared by those below: LaunchCut (a call cut into launches), dp_order / dp_launch / dp_collect (a kernel with two homes) */
-#include "sh_eng_post.inc"      /* shared by the five below: PostCall (the batch call), post_group (a launch group to STOP_POST), DpPlan / dp_run, PackSet / PackLaunch, post_upload_* */
+#include "sh_eng_post.inc"      /* shared by the mapping engines below: PostCall (the batch call), post_group (a launch group to STOP_POST), DpPlan / dp_run, PackSet / PackLaunch, post_upload_* */
 #include "sh_eng_map_crf.inc"      /* mapping of flip-flop reads to base sequences (sh_map_crf.h): map_crf_to_sequence_* on the process-default engine, the launch group scrappie_hip_map_batch runs for a CRF model */
 #include "sh_eng_map.inc"      /* block-based mapping (sh_map.h): map_to_sequence_* on the process-default engine, scrappie_hip_map_batch */
 #include "sh_eng_map_pack.inc"      /* one read against many candidate sequences (sh_map_pack.h): scrappie_hip_map_multi_batch, scrappie_hip_map_post_multi */
+#include "sh_eng_map_crf_pack.inc"      /* one flip-flop read against many candidate sequences (sh_map_crf_pack.h): scrappie_hip_map_crf_multi_batch, scrappie_hip_map_trans_multi */
 #include "sh_eng_crf_find.inc"      /* short sequences searched inside flip-flop reads, packed into workgroups (sh_crf_find.h): find_crf_sequences_viterbi, scrappie_hip_find_batch */
 #include "sh_eng_map_crf_local.inc"      /* flip-flop reads mapped into a longer sequence, cut into windows (sh_map_crf_local.h): map_crf_to_reference_*, scrappie_hip_map_local_batch */
 #include "sh_eng_map_local.inc"      /* transducer reads mapped into a longer sequence, cut into windows (sh_map_local.h): map_to_reference_*, scrappie_hip_map_post_local_batch */

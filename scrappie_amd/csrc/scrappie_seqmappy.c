@@ -10,6 +10,8 @@
  * --all-records: every record of a pair's FASTA is a candidate for the pair's read, not just the first -- all pairs in ONE
  * scrappie_hip_map_multi_batch call (the network once per read, the candidates packed into workgroups); per pair a table of the
  * records' scores and then the usual header and path of the best one.  Without the option nothing changes.
+ * --each-record (flip-flop models): --all-records through scrappie_hip_map_crf_multi_batch (k_map_crf_pack); the same table, then the best
+ * record's header and path as plain seqmappy prints them for such a model (nblock + 1 records).  Without the option nothing changes.
  * --inside (flip-flop models): the read lies somewhere INSIDE the sequence -- an amplicon, a plasmid, a chromosome arm.  All pairs
  * in ONE scrappie_hip_map_local_batch call (k_map_crf_local: one workgroup per window of the sequence); the usual header line with
  * `bases first..last` added -- the read spells the record's bases [first, last) -- and nblock + 1 records whose pos is in the
@@ -75,11 +77,18 @@ static void seqmappy_usage(FILE *fh) {
           "                             is sample t * stride of the trimmed signal), not negated; delta = score - call\n"
           "                             score <= 0, the log-odds against the read's own call; nan where a record cannot be\n"
           "                             searched.  A record is searched as given (no reverse complement).  Flip-flop (CRF)\n"
-          "                             models only; not with --inside or --all-records.\n", fh);
+          "                             models only; not with --inside or --all-records.\n"
+          "      --each-record          --all-records for flip-flop (CRF) models (--model=rnnrf_r94): the read against EVERY record\n"
+          "                             of its fasta under the model's own transitions (an allele, a haplotype, a reference, an\n"
+          "                             edit of the call).  The same line `# fast5 to fasta -- N records` and table record /\n"
+          "                             name / score / per_block, then the header line and the path of the best record as plain\n"
+          "                             seqmappy prints them for this model (blocks + 1 records), named fasta:name.  Not with a\n"
+          "                             transducer model (--all-records), --all-records, --inside, --find or --within.\n", fh);
 }
 
-/* --all-records: pair i's read against every record of its FASTA, all pairs in one scrappie_hip_map_multi_batch call */
-static int seqmappy_all_records(scrappie_hip_engine *e, int h, int klen, const scrappie_hip_params *p, char **fasta, size_t npair, FILE *out,
+/* --all-records: pair i's read against every record of its FASTA, all pairs in one scrappie_hip_map_multi_batch call; --each-record (crf):
+ * the same for a flip-flop model through scrappie_hip_map_crf_multi_batch, the path of nblock + 1 entries */
+static int seqmappy_all_records(scrappie_hip_engine *e, int h, int klen, int crf, const scrappie_hip_params *p, char **fasta, size_t npair, FILE *out,
                                 int trim_start, int trim_end, int varseg_chunk, float varseg_thresh) {
     raw_table *rts = calloc(npair, sizeof *rts);
     scrappie_hip_map_candidates *cd = calloc(npair, sizeof *cd);
@@ -100,7 +109,7 @@ static int seqmappy_all_records(scrappie_hip_engine *e, int h, int klen, const s
         rts[i] = cli_load_read(f5, trim_start, trim_end, varseg_chunk, varseg_thresh, 1);
         if (!rts[i].raw) { fprintf(stderr, "scrappie: Failed to open \"%s\" for input and trim signal.\n", f5); rc = EXIT_FAILURE; cd[i].ncand = 0; }
     }
-    if (scrappie_hip_map_multi_batch(e, h, rts, cd, npair, p, 1, 1, res) != 0) {
+    if ((crf ? scrappie_hip_map_crf_multi_batch : scrappie_hip_map_multi_batch)(e, h, rts, cd, npair, p, 1, 1, res) != 0) {
         fprintf(stderr, "scrappie: %s\n", scrappie_hip_last_error());
         rc = EXIT_FAILURE;
     } else {
@@ -120,7 +129,7 @@ static int seqmappy_all_records(scrappie_hip_engine *e, int h, int klen, const s
             const float score = res[i].score[b];
             fprintf(out, "# %s to %s:%s -- score %f over %zu blocks (%f per block)\n", f5, fa, recs[i][b].name ? recs[i][b].name : "", -score, nblock, -score / nblock);
             fprintf(out, "block\tpos\n");
-            for (size_t t = 0; t < nblock; t++) fprintf(out, "%zu\t%d\n", t, res[i].path[t]);
+            for (size_t t = 0; t < nblock + (crf ? 1 : 0); t++) fprintf(out, "%zu\t%d\n", t, res[i].path[t]);
         }
     }
     scrappie_hip_free_map_multi_results(res, npair);
@@ -226,13 +235,13 @@ static int seqmappy_inside(scrappie_hip_engine *e, int h, int klen, const scrapp
 }
 
 int main_seqmappy(int argc, char **argv) {
-    enum { O_SEG = 256, O_T1, O_T2, O_LIC, O_MODEL, O_MFILE, O_DEV, O_ALL, O_INSIDE, O_FIND, O_WITHIN };
+    enum { O_SEG = 256, O_T1, O_T2, O_LIC, O_MODEL, O_MFILE, O_DEV, O_ALL, O_INSIDE, O_FIND, O_WITHIN, O_EACH };
     static const struct option lo[] = {
         {"localpen", 1, 0, 'l'}, {"min_prob", 1, 0, 'm'}, {"output", 1, 0, 'o'}, {"prefix", 1, 0, 'p'},
         {"segmentation", 1, 0, O_SEG}, {"skip", 1, 0, 's'}, {"stay", 1, 0, 'y'}, {"trim", 1, 0, 't'},
         {"temperature1", 1, 0, O_T1}, {"temperature2", 1, 0, O_T2}, {"licence", 0, 0, O_LIC}, {"license", 0, 0, O_LIC},
-        {"model", 1, 0, O_MODEL}, {"model-file", 1, 0, O_MFILE}, {"device", 1, 0, O_DEV}, {"all-records", 0, 0, O_ALL}, {"inside", 0, 0, O_INSIDE}, {"find", 0, 0, O_FIND}, {"within", 0, 0, O_WITHIN}, {"help", 0, 0, '?'}, {0, 0, 0, 0}};
-    int all_records = 0, inside = 0, find = 0, within = 0;
+        {"model", 1, 0, O_MODEL}, {"model-file", 1, 0, O_MFILE}, {"device", 1, 0, O_DEV}, {"all-records", 0, 0, O_ALL}, {"inside", 0, 0, O_INSIDE}, {"find", 0, 0, O_FIND}, {"within", 0, 0, O_WITHIN}, {"each-record", 0, 0, O_EACH},{"help", 0, 0, '?'}, {0, 0, 0, 0}};
+    int all_records = 0, inside = 0, find = 0, within = 0, each_record = 0;
     /* defaults: scrappie_seqmappy.c:62-78 */
     scrappie_hip_params p = scrappie_hip_default_params();
     p.local_pen = 4.0f; p.min_prob = 1e-5f; p.stay_pen = 0.0f; p.skip_pen = 0.0f; p.tempW = 1.0f; p.tempb = 1.0f;
@@ -268,6 +277,7 @@ int main_seqmappy(int argc, char **argv) {
         case O_INSIDE: inside = 1; break;
         case O_FIND: find = 1; break;
         case O_WITHIN: within = 1; break;
+        case O_EACH: each_record = 1; break;
         default: seqmappy_usage(stderr); return EXIT_FAILURE;
         }
     }
@@ -275,6 +285,15 @@ int main_seqmappy(int argc, char **argv) {
     if (nargs <= 0) { seqmappy_usage(stderr); return EXIT_FAILURE; }
     if (nargs % 2) { fprintf(stderr, "scrappie: fast5 file is a required argument\n"); return EXIT_FAILURE; }    /* scrappie_seqmappy.c:153 */
     const size_t npair = (size_t)nargs / 2;
+    if (each_record && (all_records || inside || find || within)) {
+        fprintf(stderr, "scrappie: --each-record maps a read of a flip-flop (CRF) model to every record of its fasta; it cannot be combined with %s\n",
+                all_records ? "--all-records" : inside ? "--inside" : find ? "--find" : "--within");
+        return EXIT_FAILURE;
+    }
+    if (each_record && get_raw_model(model) != SCRAPPIE_MODEL_RNNRF_R9_4) {
+        fprintf(stderr, "scrappie: --each-record maps flip-flop (CRF) models only (--model=rnnrf_r94); \"%s\" is a transducer model (--all-records)\n", model);
+        return EXIT_FAILURE;
+    }
     if (within && (inside || all_records || find)) {
         fprintf(stderr, "scrappie: --within maps a read of a transducer model into the first record of its fasta; it cannot be combined with %s\n",
                 inside ? "--inside" : all_records ? "--all-records" : "--find");
@@ -335,7 +354,15 @@ int main_seqmappy(int argc, char **argv) {
     if (all_records) {
         int rc = EXIT_FAILURE;
         if (crf) fprintf(stderr, "scrappie: --all-records maps transducer models only; \"%s\" is a flip-flop (CRF) model\n", model);
-        else rc = seqmappy_all_records(e, h, klen, &p, fasta, npair, out, trim_start, trim_end, varseg_chunk, varseg_thresh);
+        else rc = seqmappy_all_records(e, h, klen, 0, &p, fasta, npair, out, trim_start, trim_end, varseg_chunk, varseg_thresh);
+        if (out != stdout) fclose(out);
+        scrappie_hip_engine_destroy(e);
+        return rc;
+    }
+    if (each_record) {
+        int rc = EXIT_FAILURE;
+        if (!crf) fprintf(stderr, "scrappie: --each-record maps flip-flop (CRF) models only; \"%s\" is a transducer model (--all-records)\n", model);
+        else rc = seqmappy_all_records(e, h, 1, 1, &p, fasta, npair, out, trim_start, trim_end, varseg_chunk, varseg_thresh);
         if (out != stdout) fclose(out);
         scrappie_hip_engine_destroy(e);
         return rc;

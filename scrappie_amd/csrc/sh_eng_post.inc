@@ -1,6 +1,6 @@
 /* sh_eng_post.inc -- part of scrappie_hip.hip (one translation unit, included from there in this order; not compiled alone):
- * the host side that the engines on a launch group's resident posterior or transitions share (k_map, k_map_crf, k_map_pack, k_map_crf_local,
- * k_crf_find: sh_eng_map*.inc, sh_eng_crf_find.inc).  Per-read plumbing (Span2, post_upload_*, the base-code check, best_finite); DpPlan /
+ * the host side that the engines on a launch group's resident posterior or transitions share (k_map, k_map_crf, k_map_pack, k_map_crf_pack,
+ * k_map_crf_local, k_crf_find: sh_eng_map*.inc, sh_eng_crf_find.inc).  Per-read plumbing (Span2, post_upload_*, the base-code check, best_finite); DpPlan /
  * plan_add / dp_run: per-read records through a kernel with two homes, over a family's DpTraits; PackSet / PackSets / PackLaunch: sets of short
  * sequences packed into workgroups; PostCall: the batch call (preamble, memory model, the refusals of a read's length, the load of a launch group);
  * post_group: the network of a launch group to STOP_POST under the engine's lock, then the family's launches.  A family file keeps what is its own:

@@ -931,6 +931,38 @@ long scrappie_hip_crf_find_plan(const size_t *seqlen, size_t nmotif, size_t pack
     return np;
 }
 
+/* Packs of candidates a flip-flop read is mapped to (k_map_crf_pack, sh_map_crf_pack.h).  A pack of ncell cells keeps two columns of
+ * transitions (64 floats) and, per cell and the spare slot behind them, two buffers of a B and an S value (16 bytes) and a word (4). */
+size_t sh_map_crf_pack_lds_bytes(size_t ncell) { return (64 + 5 * (ncell + 1)) * 4; }
+
+/* the most cells a pack may hold: what SH_MAP_LDS holds (the bytes are linear in ncell) */
+size_t scrappie_hip_map_crf_pack_max_cells(void) {
+    const size_t per = sh_map_crf_pack_lds_bytes(1) - sh_map_crf_pack_lds_bytes(0);
+    return (SH_MAP_LDS - sh_map_crf_pack_lds_bytes(0)) / per;
+}
+
+/* Candidates of seqlen[k] bases into packs of at most pack_cells cells (at most scrappie_hip_map_crf_pack_max_cells() whatever is
+ * asked for), in input order: a candidate of L bases takes L + 1 cells; a pack is closed when the next candidate would take it past
+ * pack_cells, so a candidate of more cells than that is alone in its pack.  pack[k]: the candidate's pack, cell[k]: its first cell
+ * there; pack[k] = -1 (cell[k] = -1) where its seqlen[k] + 1 cells exceed the most a pack may hold -- such a candidate takes
+ * k_map_crf, and does not close the open pack.  Returns the number of packs. */
+long scrappie_hip_map_crf_pack_plan(const size_t *seqlen, size_t ncand, size_t pack_cells, int *pack, long long *cell) {
+    if (!seqlen || !pack || !cell) return 0;
+    const size_t maxc = scrappie_hip_map_crf_pack_max_cells();
+    if (pack_cells > maxc) pack_cells = maxc;
+    long np = 0;
+    size_t used = 0;                    /* cells of the open pack, np - 1; 0: none is open */
+    for (size_t k = 0; k < ncand; k++) {
+        if (seqlen[k] > maxc - 1) { pack[k] = -1; cell[k] = -1; continue; }
+        const size_t c = seqlen[k] + 1;
+        if (used == 0 || used + c > pack_cells) { np++; used = 0; }
+        pack[k] = (int)(np - 1);
+        cell[k] = (long long)used;
+        used += c;
+    }
+    return np;
+}
+
 /* the library defines it (scrappie_hip.hip); weak, so that this file also links into the host-only builds of the tests */
 void sh_set_error(const char *fmt, ...) __attribute__((weak, format(printf, 1, 2)));
 #define SH_ERR(...) do { if (sh_set_error) sh_set_error(__VA_ARGS__); } while (0)

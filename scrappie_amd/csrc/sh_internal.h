@@ -31,6 +31,8 @@ size_t sh_map_local_scr_lds_bytes(size_t nr);
 #define SH_MAP_LOCAL_STRIDE 1200     /* the entry positions such a window owned where it was measured (800 blocks): a longer read, which would leave it fewer, takes the largest LDS-resident window */
 /* packs of motifs searched inside a flip-flop read (sh_host.c; k_crf_find, sh_crf_find.h): the dynamic LDS a pack of ncell cells takes, with or without positions */
 size_t sh_crf_find_lds_bytes(size_t ncell, int pos);
+/* packs of candidates a flip-flop read is mapped to (sh_host.c; k_map_crf_pack, sh_map_crf_pack.h): the dynamic LDS a pack of ncell cells takes */
+size_t sh_map_crf_pack_lds_bytes(size_t ncell);
 /* squiggle matching (sh_host.c): the tables of decode.c:1055-1099 from the host's libm; tab holds 5 npos + 4 floats */
 void sh_squiggle_tables(const float *params, size_t npos, size_t ldp, float rate, float prob_back, float *tab, float pens[2]);
 /* dwell correction (sh_host.c): the scale from pos / state (n ints each, `stride` bytes apart), the prior's numerator of an event table, and

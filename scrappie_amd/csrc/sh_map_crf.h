@@ -80,6 +80,25 @@ template <> struct ShMapCrfView<ShCrfRef> {
     static __device__ __forceinline__ ShCrfRef::View make(const float *tr, const ShMapCrfRead &r) { return ShCrfRef::View{tr + r.trans, r.lane, r.nblock - 1}; }
 };
 
+/* One cell of block t, for k_map_crf and k_map_crf_pack (sh_map_crf_pack.h) alike: tr the block's column, tSS = tr[24], b = seq[p - 1] and
+ * bp = seq[p - 2] (any base where there is none), p the cell (k_map_crf_pack: 0, 1 or 2 for p >= 2), (B0, S0) the previous entry's cell p and
+ * (B1, S1) its cell p - 1, -SH_MAP_BIG where there is none.  vb, vs: B'[p] and S'[p]; kb, ks (Viterbi): the predecessor was the stay cell. */
+template <bool VIT>
+__device__ __forceinline__ void sh_map_crf_cell(const float *tr, float tSS, int b, int bp, int p, float B0, float S0, float B1, float S1,
+                                                float &vb, float &vs, bool &kb, bool &ks) {
+    const float bb = tr[5 * b + bp] + B1, bs = tr[5 * b + 4] + S1;
+    const float sb = tr[20 + b] + B0, ss = tSS + S0;
+    if (VIT) {
+        kb = p < 2 || bs > bb; vb = kb ? bs : bb;
+        ks = p < 1 || ss > sb; vs = ks ? ss : sb;
+    } else {
+        kb = ks = false;
+        vb = p < 2 ? bs : sh_lse(bb, bs);
+        vs = p < 1 ? ss : sh_lse(sb, ss);
+    }
+    if (p < 1) vb = -SH_MAP_BIG;                             /* there is no B[0] */
+}
+
 template <bool VIT, class LOADER, bool LDS>
 __global__ __launch_bounds__(SH_MAP_NTH) void k_map_crf(ShMapCrfArgs a) {
     extern __shared__ __attribute__((aligned(16))) float sh_mapc_lds[];
@@ -134,19 +153,9 @@ __global__ __launch_bounds__(SH_MAP_NTH) void k_map_crf(ShMapCrfArgs a) {
                 const float lB0 = pB[p0], lS0 = pS[p0], lB1 = pB[p1], lS1 = pS[p1];
                 const float B0 = in0 ? lB0 : -SH_MAP_BIG, S0 = in0 ? lS0 : -SH_MAP_BIG;
                 const float B1 = in1 ? lB1 : -SH_MAP_BIG, S1 = in1 ? lS1 : -SH_MAP_BIG;
-                const float bb = tr[5 * b + bp] + B1, bs = tr[5 * b + 4] + S1;
-                const float sb = tr[20 + b] + B0, ss = tSS + S0;
                 float vb, vs;
                 bool kb, ks;
-                if (VIT) {
-                    kb = p < 2 || bs > bb; vb = kb ? bs : bb;
-                    ks = p < 1 || ss > sb; vs = ks ? ss : sb;
-                } else {
-                    kb = ks = false;
-                    vb = p < 2 ? bs : sh_lse(bb, bs);
-                    vs = p < 1 ? ss : sh_lse(sb, ss);
-                }
-                if (p < 1) vb = -SH_MAP_BIG;                 /* there is no B[0] */
+                sh_map_crf_cell<VIT>(tr, tSS, b, bp, p, B0, S0, B1, S1, vb, vs, kb, ks);
                 const int at = valid ? p : SPARE;
                 cB[at] = vb;
                 cS[at] = vs;
