@@ -449,6 +449,7 @@ struct scrappie_hip_engine {
     bool dbg_redo_all = false;       /* treat every read as one k_stitch left to the host (tests the fallback) */
     bool dbg_dwell_tight = false;    /* dwell-mode groups reserve 16 bytes of bases a read: longer calls overflow on the device and go to the host (tests that path) */
     int dbg_gru_tiles = 0;           /* 1 / 2: tiles per workgroup of k_gru_proj whatever the schedules say (0: choose) */
+    int dbg_decoder_cus = 0;         /* n > 0: the decoder's piece schedule is made for a device of n CUs, so a launch group of a few tiles is cut into pieces (0: the device's own count) */
     bool dbg_force_f32 = false;      /* models loaded from now on run their GRU layers on the exact-fp32 kernels (as if out of the split products' range) */
     int dbg_gru32 = -1;              /* 0 / 1: recurrent layers on 16- / 32-read tiles whatever the build's default (-1) */
     /* chain-bound reads beside the rest of a call (scrappie_hip_basecall_batch): a helper engine on the same device, created on first use */

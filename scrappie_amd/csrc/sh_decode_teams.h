@@ -30,12 +30,19 @@
  *    stay  reads the thread's own state.
  * Phase C therefore reads no other thread's score: it may overwrite its own.  Ties: the step maximum keeps the lowest r4 (strict compare
  * in scan order), the skip merge the lowest r = 4 r4 + rl among equal values -- the reference's first-maximum order (Q7).
- * The end state's traceback entry, the one place that reads another thread's quad, is fetched in phase B as well.
+ * The end state's traceback entry, the one place that reads another thread's quad, is fetched in phase B as well -- by producer 3.
+ *
+ * What a block needs once per READ and not per state -- the reciprocal of the row sum, the stay state's log-posterior, the stay move, what the
+ * start state holds, and the whole end state (its predecessor, traceback entry and score) -- is the work of ONE wave, producer 3, in phase B:
+ * it publishes no trunk pieces and the S1 team stood at that barrier for 1600-1800 cycles a block.  The decoder waves read the result (16 bytes
+ * a read) at the head of phase C; none of them is special, and phase B no longer ends when wave 0 does (profiles/decoder_s1_serial.txt).
  *
  * Two LDS-only barriers per block, shared by both teams (gfx950 has no named barriers):
- *    phase B   decoders: ring -> registers, step / skip maxima      producers: (first block of a pair) the next two trunk columns -> pieces; prime the stream
- *    phase C   decoders: S2 + update in place + traceback           producers: half a pass (8 m-tiles x 2 blocks) -> ring, row sums
- * LDS: scores 64 KB + ring 64 KB + skip maxima 8 KB + bias 4 KB + trunk pieces 12 KB + sums / end-state scan 4.6 KB = 157 KB.
+ *    phase B   decoders: ring -> registers, step / skip maxima      producers: (first block of a pair) the next two trunk columns -> pieces; prime the stream;
+ *                                                                    producer 3: the per-read record, the end state (per_read)
+ *    phase C   decoders: record -> registers, S2 + update in place + traceback     producers: half a pass (8 m-tiles x 2 blocks) -> ring, row sums
+ * LDS: scores 64 KB + ring 64 KB + skip maxima 8 KB + bias 4 KB + trunk pieces 12 KB + sums / end-state scan 4.6 KB + per-read record and
+ * producer 3's parked values 0.5 KB = 157.2 KB.
  * 12 waves x <= 168 VGPRs, three waves per SIMD.  Not built for the slip move (k_ff_viterbi keeps that). */
 #ifndef SH_DECODE_TEAMS_H
 #define SH_DECODE_TEAMS_H
@@ -81,7 +88,7 @@ __device__ __forceinline__ void end_unkey(unsigned long long k, float &v, int &i
 }
 
 #define SH_FVT_NTH 768
-#define SH_FVT_LDS_FLOATS (1024 * 16 + 64 * 256 + 2 * 64 * 16 + 2 * 2 * 8 * 16 + 4 * 9 * 16 + 65 * 16 + 2 * 3 * 512 + 3 * 2 * 4 * 4)
+#define SH_FVT_LDS_FLOATS (1024 * 16 + 64 * 256 + 2 * 64 * 16 + 2 * 2 * 8 * 16 + 4 * 9 * 16 + 65 * 16 + 2 * 3 * 512 + 3 * 2 * 4 * 4 + 16 * 4 + 4 * 16)
 
 template <bool SKIP0, bool DIV, bool NOCLAMP = false>
 __global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShVitArgs a, ShMeta md) {
@@ -107,6 +114,14 @@ __global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShV
     float *sBias = gsum + 4 * NG * 16;                  /* bias x 2^14 by state row [65 * 16] */
     unsigned *xp = (unsigned *)(sBias + 65 * 16);       /* the trunk columns of the pair in the making, as pieces [2][KS][2][64][4] */
     unsigned *sStay = xp + 2 * KS * 512;                /* row 1024 of the weights as pieces [KS][2][4 k groups][4] */
+    /* the block's per-read record [16][rm, mpx, stay_v, hold]: written by producer NPW - 1 in phase B, read by every decoder thread at the head of
+     * phase C (one ds_read_b128).  One buffer: the readers of block t are through before the barrier that closes block t, the next write is behind it */
+    float *rec = (float *)(sStay + KS * 2 * 4 * 4);
+    /* what that producer keeps per read, in LDS because its registers are the weight ring's: the end state's score [16] (behind the block loop
+     * tid < 16 reads it for the final argmax), the read's block count [16] and its row offset in hp_side [16] */
+    float *pendl = rec + 16 * 4;
+    int *pT = (int *)(pendl + 16);
+    long long *phpo = (long long *)(pT + 16);
 
     const int tid = threadIdx.x, lane = tid & 63, b = lane & 15, q = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -179,13 +194,12 @@ __global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShV
                 }
             }
             pstart = vst[NH * 16 + b];
-            pend = vst[NH * 16 + 16 + b];
             float ov = __shfl_xor(bv, 16); int oi = __shfl_xor(bi, 16);
             argmax_merge(bv, bi, ov, oi);
             ov = __shfl_xor(bv, 32); oi = __shfl_xor(bi, 32);
             argmax_merge(bv, bi, ov, oi);
             if (lane < 16) __hip_atomic_fetch_max(redk + b, end_key(bv, bi), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
+        } else if (wave == NCW + NPW - 1) pend = (a.vstate + (long long)tile * (NH * 16 + 32))[NH * 16 + 16 + b];      /* the end state lives on that producer */
     }
 
     if (!decoder) {
@@ -319,6 +333,58 @@ __global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShV
                 }
             }
         };
+        /* Producer NPW - 1, phase B of block t: what a block needs once per READ, off the decoder waves -- it publishes no trunk pieces, and the S1
+         * team stands at this phase's barrier for longer than this takes.  Both inputs are complete when the phase begins: the row sums of block t
+         * (gsum[t & 3]) since phase C of block t - 1 at the latest, the end-state key of slot PAR since the barrier that closed block t - 1; the
+         * scores are overwritten only behind this phase's barrier.
+         *  - the record: S2's factor and the stay move, with t < myT applied (the operations the decoder waves did, each for itself, at the head of phase C);
+         *  - the end state (decode.c:339-348): the scan's key, the state inside its quad, the traceback entry and the score, which stays with this wave.
+         * Registers: the weight ring and the products take the wave to the cap, so nothing here lives through a half pass.  What the wave keeps
+         * per read (the end state's score, the read's block count, its row in hp_side) is parked in LDS, and every address is formed from a lane
+         * number made afresh and opaque -- hoisted out of the block loop, the addresses were spilled to scratch and reloaded in it */
+        auto per_read = [&](const int t, auto par_c) {
+            constexpr int par = decltype(par_c)::value;
+            int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+            asm volatile("" : "+v"(ln));
+            const int b = ln & 15;
+            const bool low = ln < 16;                       /* (all four rows of lanes compute, the first one stores) */
+            const int myT = pT[b];
+            float pend = pendl[b];
+            float tot = 0.0f;
+#pragma unroll
+            for (int w = 0; w < NG; w++) tot += gsum[((t & 3) * NG + w) * 16 + b];
+            const float rmf = d_rcp(tot) * mpm1;                        /* fin_log's factor; v_rcp_f32 in every consumer of the row sum: the forms keep identical bits */
+            const float stay_lp = fin_log(gsum[((t & 3) * NG + NG - 1) * 16 + b], rmf, mp);
+            const bool active = t < myT;
+            if (a.hp_side && active && low) (a.hp_side + (phpo[b] + t) * 5)[4] = stay_lp;
+            /* a read past its end keeps its scores: see k_viterbi */
+            const float rm = active ? rmf : 0.0f;
+            const float mpx = active ? mp : 0.0f;
+            const float stay_v = active ? stay_lp - a.stay_pen : 0.0f;  /* decode.c:175-176 */
+            const float stay_act = stay_lp - a.stay_pen;
+            const float hold = fmaxf(-a.local_pen, stay_act);
+            if (low) *(f32x4 *)(rec + b * 4) = (f32x4){rm, mpx, stay_v, hold};
+            /* the eight decoder waves' candidates were merged by the LDS maximum they were written with (end_key): one read.  The slot is emptied
+             * for the block after next, whose phase C -- two barriers on -- writes it.  (An LDS pointer by type: as a generic one this is a flat
+             * load behind s_waitcnt vmcnt(0) lgkmcnt(0), i.e. behind the wave's weight stream.)  ei is the first QUAD that holds the maximum of
+             * (score - local_pen); the state is the first of its four that attains it */
+            float ev; int ei;
+            end_unkey(redk[par * 16 + b], ev, ei);
+            redk[par * 16 + b] = 0;
+            const f32x4 q4 = *(const f32x4 *)(sc + ((ei & (NQ - 1)) * 16 + b) * 4);
+            int e0 = 3;
+            e0 = (q4[2] - a.local_pen == ev) ? 2 : e0;
+            e0 = (q4[1] - a.local_pen == ev) ? 1 : e0;
+            e0 = (q4[0] - a.local_pen == ev) ? 0 : e0;
+            const int tbe_in = 4 * ei + e0;
+            float nend = pend + hold;                       /* decode.c:339 */
+            const bool enter_end = ev > nend;               /* decode.c:343-348 */
+            nend = enter_end ? ev : nend;
+            if (active && low) a.tb_end[(boff + t) * 16 + b] = enter_end ? tbe_in : NH + 1;
+            if (active && low) pendl[b] = nend;
+        };
+        const bool serial = pw == NPW - 1;
+        if (serial && lane < 16) { pendl[b] = pend; pT[b] = myT; phpo[b] = hpo; }      /* (this wave's own, from here on) */
         const std::integral_constant<int, 0> H0{};
         const std::integral_constant<int, 1> H1{};
 
@@ -337,6 +403,9 @@ __global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShV
         if (a.dbg) vt0 = __builtin_readcyclecounter();
         for (int t = s0; t < s1; t += 2) {
             const bool more = (t + 2 < s1) && !(SH_FVT_ABL & 1);      /* there is a pair t + 2, t + 3 to prepare */
+            /* (per_read in FRONT of the stream's priming: behind it the wave waits with vmcnt(0) for the twelve loads to land -- the scratch registers of
+             * per_read are the ring's -- and 850 cycles later it was the last wave at this barrier: profiles/decoder_s1_serial.txt) */
+            if (serial) { per_read(t, H0); __builtin_amdgcn_sched_barrier(0); }
             if (more) { xp_publish(); w_prime(0); }         /* (the pieces of the pair before were last read two phases ago) */
             VSTAMP(vA);
             lds_barrier();
@@ -345,6 +414,7 @@ __global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShV
             VSTAMP(vC);
             lds_barrier();
             VSTAMP(vD);
+            if (serial && t + 1 < s1) { per_read(t + 1, H1); __builtin_amdgcn_sched_barrier(0); }      /* (a piece of an odd number of blocks: the decoders skip the block too) */
             if (more) w_prime(HT);
             VSTAMP(vA);
             lds_barrier();
@@ -356,7 +426,10 @@ __global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShV
             lds_barrier();
             VSTAMP(vD);
         }
-        /* the decoder team's epilogue (hand-over / final state) has two workgroup barriers either way */
+        /* the decoder team's epilogue (hand-over / final state) has two workgroup barriers either way; the end state's score goes where it is
+         * read: into the hand-over buffer (released with the decoders' part: every wave fences, then the barrier, then the flag), or stays in LDS for tid < 16 */
+        if (serial && lane < 16 && s1 < Tt) (a.vstate + (long long)tile * (NH * 16 + 32))[NH * 16 + 16 + b] = pendl[b];
+        if (s1 < Tt) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         __syncthreads();
         if (s1 >= Tt) __syncthreads();
         if (a.dbg && lane == 0) { unsigned long long *d = a.dbg + ((long long)blockIdx.x * 12 + wave) * 8; d[0] = vA; d[1] = vB; d[2] = vC; d[3] = vD; d[4] = (unsigned long long)(s1 - s0); }
@@ -439,24 +512,7 @@ __global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShV
             unsigned srp = 0;
 #pragma unroll
             for (int i = 0; i < PPT; i++) srp |= (unsigned)sr[i] << (3 * i);
-            /* the end state's predecessor (decode.c:343-348) reads a quad of another thread: resolved here, before anything is overwritten.  ei is the
-             * first QUAD that holds the maximum of (score - local_pen); the state is the first of its four that attains it */
-            float ev = 0.f; int tbe_in = 0;
-            if (cw == 0) {
-                int ei;
-                /* the eight waves' candidates were merged by the LDS maximum they were written with (end_key): one read instead of sixteen
-                 * and seven merges, on the wave every other one waits for at this phase's barrier.  The slot is emptied for the block after
-                 * next, whose phase C -- two barriers on -- writes it.  (An LDS pointer by type: as a generic one this is a flat load behind
-                 * s_waitcnt vmcnt(0) lgkmcnt(0), i.e. behind the wave's traceback stores) */
-                end_unkey(redk[par * 16 + b], ev, ei);
-                redk[par * 16 + b] = 0;
-                const f32x4 q4 = *(const f32x4 *)(sc + ((ei & (NQ - 1)) * 16 + b) * 4);
-                int e0 = 3;
-                e0 = (q4[2] - a.local_pen == ev) ? 2 : e0;
-                e0 = (q4[1] - a.local_pen == ev) ? 1 : e0;
-                e0 = (q4[0] - a.local_pen == ev) ? 0 : e0;
-                tbe_in = 4 * ei + e0;
-            }
+            /* (the end state's predecessor, the one thing that reads a quad of another thread, is resolved in this phase by producer NPW - 1: per_read) */
             /* half a pass out of the ring, behind the scans (register budget): the second half of this pair / the first half of the next */
             __builtin_amdgcn_sched_barrier(0);
             if (FIRST) drain(I0, I1, I1, I1);
@@ -466,28 +522,13 @@ __global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShV
             VSTAMP(vB);
 
             /* ---- phase C: S2 + update of my states, in place ---- */
-            float tot = 0.0f;
-#pragma unroll
-            for (int w = 0; w < NG; w++) tot += gsum[((t & 3) * NG + w) * 16 + b];
-            const float rmf = d_rcp(tot) * mpm1;                        /* fin_log's factor; v_rcp_f32 in every consumer of the row sum: the forms keep identical bits */
-            const float stay_lp = fin_log(gsum[((t & 3) * NG + NG - 1) * 16 + b], rmf, mp);
+            /* the read's S2 factor (rm, mpx: zero for a read past its end, which keeps its scores -- see k_viterbi), its stay move and what the
+             * start state holds: one record per read and block, made in phase B by producer NPW - 1 (per_read) */
+            const f32x4 rcd = *(const f32x4 *)(rec + b * 4);
+            const float rm = rcd[0], mpx = rcd[1], stay_v = rcd[2], hold = rcd[3];
             const bool active = t < myT;
             const unsigned long long actmask = __builtin_amdgcn_ballot_w64(active);
-            if (a.hp_side && active && tid < 16) (a.hp_side + (hpo + t) * 5)[4] = stay_lp;
-            /* a read past its end keeps its scores: see k_viterbi */
-            const float rm = active ? rmf : 0.0f;
-            const float mpx = active ? mp : 0.0f;
-            const float stay_v = active ? stay_lp - a.stay_pen : 0.0f;  /* decode.c:175-176 */
-            const float stay_act = stay_lp - a.stay_pen;
-            const float hold = fmaxf(-a.local_pen, stay_act);
             const float nstart = pstart + hold;                 /* decode.c:326 */
-            if (cw == 0) {
-                float nend = pend + hold;                       /* decode.c:339 */
-                const bool enter_end = ev > nend;               /* decode.c:343-348 */
-                nend = enter_end ? ev : nend;
-                if (active && tid < 16) a.tb_end[cb * 16 + b] = enter_end ? tbe_in : NH + 1;
-                if (active) pend = nend;
-            }
             float bv = -INFINITY;
             int bi = 0x7fffffff;
             /* the block's traceback rows: two wave-uniform bases (scalar registers), each serving four quads through the store's immediate
@@ -629,7 +670,7 @@ __global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShV
                 const int Q = 4 * (SH_FVT_MT(i) + cw) + q;
                 *(f32x4 *)(vst + (Q * 16 + b) * 4) = *(const f32x4 *)(myq + SH_FVT_MT(i) * 256);
             }
-            if (tid < 16) { vst[NH * 16 + b] = pstart; vst[NH * 16 + 16 + b] = pend; }
+            if (tid < 16) vst[NH * 16 + b] = pstart;            /* (the end state's score: producer NPW - 1, in front of this barrier too) */
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         __syncthreads();
@@ -655,6 +696,7 @@ __global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShV
         if (decoder && lane < 16) { redv[wave * 16 + b] = bv; redi[wave * 16 + b] = bi; }
         __syncthreads();
         if (tid < 16) {
+            pend = pendl[b];                                    /* left by producer NPW - 1 in front of the first of the two barriers */
             float ev = redv[b]; int ei = redi[b];
             for (int w = 1; w < NCW; w++) argmax_merge(ev, ei, redv[w * 16 + b], redi[w * 16 + b]);
             if (pstart > ev) { ev = pstart; ei = NH; }

@@ -101,7 +101,7 @@ static int build_group(scrappie_hip_engine *e, Slot &sl, Model *m, const uint64_
     sh_lane_schedule(pair_T.data(), pair_T.size(), e->ncu, 2, sched32b, e->handover);
     lg.gru32x2_nwg = sched32b.nwg;
     std::vector<ShGruSeg> vseg;                  /* decoder: one piece of a tile per workgroup */
-    sh_piece_schedule(tile_T.data(), lg.ntile, e->ncu, vseg, e->handover);
+    sh_piece_schedule(tile_T.data(), lg.ntile, e->dbg_decoder_cus > 0 ? e->dbg_decoder_cus : e->ncu, vseg, e->handover);
     lg.vit_nwg = (int)vseg.size();
     /* pack metadata: [sig_off u64 npad][seq_off i64 npad][hp_off i64 npad][tile_boff i64 ntile][rN i32 npad][rT i32 npad][tile_T i32 ntile] */
     const size_t b_u64 = lg.npad * 8, b_i32 = lg.npad * 4;
