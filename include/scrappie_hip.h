@@ -847,14 +847,19 @@ int scrappie_hip_set_trunk_input(scrappie_hip_engine *e, const float *d_trunk, c
  * hand-over buffer; "fail_run" = k: the k-th next launch group is refused (failure paths); "redo_all" = every read
  * takes the host fallback of k_stitch; "gru_tiles" = 1 / 2: tiles of 16 reads per workgroup of the recurrent layers
  * whatever the lane schedules say (0: the engine chooses); "decoder_cus" = n: the decoder's piece schedule is made for a device of n CUs (with
- * 2, a group of three or more tiles is cut into two pieces a tile and the pieces' hand-over runs on a small group; 0: the device's own count).
+ * 2, a group of three or more tiles is cut into two pieces a tile and the pieces' hand-over runs on a small group; 0: the device's own count) --
+ * for all three decoder forms, the two-team kernel then running one piece per workgroup like the other two; "decoder_lanes" = n: the
+ * two-team kernel's lane layout (sh_decoder_lanes) is made for a device of n CUs, so a group of a few tiles runs on n workgroups that walk
+ * several segments each and hand cut tiles over (0: the device's own count; it goes before "decoder_cus" for that kernel).
  * scrappie_hip_debug_fetch copies a buffer of the most recent transducer launch group to the
  * host: "tb" (one byte per state: [column block][state quad][read of tile][state of quad]), "tb_end" (int per
  * column block and read), "final_state" / "final_score" (per read, tiled order), "final_scores" ([tile][states x
  * 16 reads | 16 start | 16 end] floats, needs dump_final), "order" (int per tiled position: index of the read in
  * the call, -1 = padding), "tile_boff" (long long per tile: its first column block), "n_redo" (unsigned long long:
  * reads whose stitching k_stitch has left to the host since the engine was created), "gru_tiles" (int: what the group's
- * recurrent layers ran with), "decoder_pieces" (int: workgroups of the group's decoder launch, one per piece of a tile).  Returns the bytes the
+ * recurrent layers ran with), "decoder_pieces" (int: the segments of tiles the group's decoder launch ran: one per workgroup for k_viterbi and
+ * k_ff_viterbi, which own a piece of a tile each, and all the segments of the lane layout for k_ff_viterbi_teams, whose workgroups walk several),
+ * "decoder_wgs" (int: the workgroups of that launch).  Returns the bytes the
  * buffer holds (min(that, nbytes) are copied; dst may be NULL), -1 on error. */
 int scrappie_hip_debug_option(scrappie_hip_engine *e, const char *name, int value);
 /* k_stitch (homopolymer correction + k-mer stitching / crfpath_to_basecall on the device: what the batched path
@@ -951,6 +956,11 @@ long scrappie_hip_lane_schedule(const int *tile_T, size_t ntile, int ncu, int la
 /* Pieces of the Viterbi decoder's launch (scrappie_amd/csrc/sh_sched.h), host only:
  * seg takes cap rows of {tile, first block, end block, 0} in workgroup order. */
 long scrappie_hip_decoder_pieces(const int *tile_T, size_t ntile, int ncu, int *seg, size_t cap);
+/* Lane layout of the two-team decoder (k_ff_viterbi_teams; sh_decoder_lanes in sh_sched.h), host only: the tiles end to end over one
+ * lane per workgroup, nwg = min(ncu, live tiles) workgroups, cut only where a lane is full and only on even blocks.  lane_off: ncu + 1
+ * ints; seg: cap rows of {tile, first block, end block, ordinal of the segment within its tile}, each lane's segments in the order they
+ * run; capacity: M in blocks.  Returns the number of segments. */
+long scrappie_hip_decoder_lanes(const int *tile_T, size_t ntile, int ncu, int *nwg, int *capacity, int *lane_off, int *seg, size_t cap);
 
 size_t scrappie_hip_min_samples(scrappie_hip_engine *e, int model);
 int scrappie_hip_model_stride(scrappie_hip_engine *e, int model);

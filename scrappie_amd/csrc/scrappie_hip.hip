@@ -18,8 +18,8 @@
  *   a GRU layer with a weight outside the split products' operand range (|w| >= 255): k_affine<.., F32> -> k_gru_lanes (exact fp32)
  *
  * The contractions of the projection, the recurrence and S1 run as split products on the f16 matrix pipe
- * (sh_kernels.h, split_pair / split_dot): fp32 in, fp32 out, fp32 accuracy.  The recurrent kernels walk a lane schedule and
- * the decoder works on pieces of tiles (sh_sched.h).  Two launch groups can be in flight: the host stitches
+ * (sh_kernels.h, split_pair / split_dot): fp32 in, fp32 out, fp32 accuracy.  The recurrent kernels and the two-team
+ * decoder walk a lane schedule, the other decoder kernels work on pieces of tiles (sh_sched.h).  Two launch groups can be in flight: the host stitches
  * group k (homopolymer correction, k-mer overlap: sh_host.c, C) while group k+1 runs.  Only decoded paths
  * (and the 5-row homopolymer side buffer) cross PCIe.
  *
@@ -295,7 +295,11 @@ struct LaunchGroup {
     bool gru_two = false;         /* more live tiles than CUs: k_gru_proj steps two tiles per workgroup */
     int gru32_nwg = 0;            /* ... over pairs of tiles, one pair at a time per workgroup (k_gru_proj32) */
     int gru32x2_nwg = 0;          /* ... two pairs at a time per workgroup (k_gru_proj32x2) */
-    int vit_nwg = 0;              /* ... and of the Viterbi decoder */
+    int vit_nwg = 0;              /* ... and of the Viterbi decoder: pieces of tiles, one per workgroup (k_viterbi, k_ff_viterbi) */
+    int vit_lane_nwg = 0;         /* ... and its lane layout (k_ff_viterbi_teams): workgroups, */
+    int vit_lane_nseg = 0;        /* and the segments they walk */
+    int vit_launched = 0;         /* segments of the decoder launch that ran (the "decoder_pieces" debug fetch), */
+    int vit_launched_wg = 0;      /* and its workgroups ("decoder_wgs") */
     /* what the group was launched with, kept so that scrappie_hip_collect can run it again on whole tiles
      * should a state hand-over between workgroups time out */
     const float *d_signal = nullptr;
@@ -450,6 +454,7 @@ struct scrappie_hip_engine {
     bool dbg_dwell_tight = false;    /* dwell-mode groups reserve 16 bytes of bases a read: longer calls overflow on the device and go to the host (tests that path) */
     int dbg_gru_tiles = 0;           /* 1 / 2: tiles per workgroup of k_gru_proj whatever the schedules say (0: choose) */
     int dbg_decoder_cus = 0;         /* n > 0: the decoder's piece schedule is made for a device of n CUs, so a launch group of a few tiles is cut into pieces (0: the device's own count) */
+    int dbg_decoder_lanes = 0;       /* n > 0: the two-team decoder's lane layout is made for a device of n CUs, so a few tiles share n workgroups and are cut between them (0: the device's own count) */
     bool dbg_force_f32 = false;      /* models loaded from now on run their GRU layers on the exact-fp32 kernels (as if out of the split products' range) */
     int dbg_gru32 = -1;              /* 0 / 1: recurrent layers on 16- / 32-read tiles whatever the build's default (-1) */
     /* chain-bound reads beside the rest of a call (scrappie_hip_basecall_batch): a helper engine on the same device, created on first use */

@@ -29,6 +29,9 @@ struct ShVitArgs {
     unsigned long long *dbg;      /* experiment: per-wave phase cycle totals, or NULL */
     /* seg == NULL: workgroup g decodes tile g whole; else workgroup g decodes piece seg[g] (sh_sched.h) */
     const ShGruSegD *seg;
+    /* k_ff_viterbi_teams only.  Not NULL: workgroup g walks the segments seg[lane_off[g]] .. seg[lane_off[g + 1] - 1] one after the other
+     * (sh_decoder_lanes, sh_sched.h); NULL: as above */
+    const int *lane_off;
     float *vstate;                /* [ntile][NH * 16 + 32]: scores, start and end state of a tile cut between lanes */
     unsigned *flag;               /* [ntile] hand-over done */
     unsigned *err;                /* set when a hand-over never arrives */

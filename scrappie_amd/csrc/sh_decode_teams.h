@@ -43,7 +43,11 @@
  *    phase C   decoders: record -> registers, S2 + update in place + traceback     producers: half a pass (8 m-tiles x 2 blocks) -> ring, row sums
  * LDS: scores 64 KB + ring 64 KB + skip maxima 8 KB + bias 4 KB + trunk pieces 12 KB + sums / end-state scan 4.6 KB + per-read record and
  * producer 3's parked values 0.5 KB = 157.2 KB.
- * 12 waves x <= 168 VGPRs, three waves per SIMD.  Not built for the slip move (k_ff_viterbi keeps that). */
+ * 12 waves x <= 168 VGPRs, three waves per SIMD.  Not built for the slip move (k_ff_viterbi keeps that).
+ *
+ * A workgroup walks a LANE of segments of tiles (sh_decoder_lanes, sh_sched.h: tiles end to end over min(CUs, live tiles) workgroups, cut on even
+ * blocks only where a lane is full) and runs everything but the LDS set-up of the bias and the stay row once per segment; a cut tile's state
+ * crosses workgroups through the hand-over buffer and an arrival flag (profiles/decoder_lanes.txt). */
 #ifndef SH_DECODE_TEAMS_H
 #define SH_DECODE_TEAMS_H
 
@@ -91,7 +95,7 @@ __device__ __forceinline__ void end_unkey(unsigned long long k, float &v, int &i
 #define SH_FVT_LDS_FLOATS (1024 * 16 + 64 * 256 + 2 * 64 * 16 + 2 * 2 * 8 * 16 + 4 * 9 * 16 + 65 * 16 + 2 * 3 * 512 + 3 * 2 * 4 * 4 + 16 * 4 + 4 * 16)
 
 template <bool SKIP0, bool DIV, bool NOCLAMP = false>
-__global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShVitArgs a, ShMeta md) {
+__global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f_, ShVitArgs a_, ShMeta md_) {
     static_assert(!(DIV && NOCLAMP), "with temperatures the clamp stays");
     constexpr int NCW = 8, NPW = 4, PPT = 8, NQ = 256, NH = 1024, KS = 3, KQ = 6, TPP = 16, HT = 8, NG = 9, WB = SH_FVT_WBUF;
     static_assert(SH_SUM_GROUP == HT, "half a pass of a producer is one row-sum group");
@@ -123,26 +127,71 @@ __global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShV
     int *pT = (int *)(pendl + 16);
     long long *phpo = (long long *)(pT + 16);
 
-    const int tid = threadIdx.x, lane = tid & 63, b = lane & 15, q = lane >> 4;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wave_ = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    unsigned long long vA = 0, vB = 0, vC = 0, vD = 0, vt0 = 0, vt1 = 0, vP = 0, vp0 = 0;
+    unsigned vblk = 0, vseg = 0;                        /* blocks and segments this workgroup has run (stamps) */
+    (void)vt0; (void)vt1; (void)vP; (void)vp0;
+#undef VSTAMP
+#undef VSTAMP_SEG
+#undef VSTAMP_LOOP
+#if SH_FVT_STAMP
+#define VSTAMP(acc) do { if (a.dbg) { vt1 = __builtin_readcyclecounter(); acc += vt1 - vt0; vt0 = vt1; } } while (0)
+/* a segment's cost outside the block loop: from its first instruction (VSTAMP_SEG) to the barrier that opens the loop (VSTAMP_LOOP, behind vt0) */
+#define VSTAMP_SEG() do { if (a.dbg) vp0 = __builtin_readcyclecounter(); } while (0)
+#define VSTAMP_LOOP() do { if (a.dbg) vP += vt0 - vp0; } while (0)
+#else
+#define VSTAMP(acc) do { } while (0)
+#define VSTAMP_SEG() do { } while (0)
+#define VSTAMP_LOOP() do { } while (0)
+#endif
+
+    if (threadIdx.x < KS * 2 * 4 * 4) { const int j = threadIdx.x; sStay[j] = f_.wpiece[(long long)(64) * KS * 512 + (j >> 4) * 256 + ((j >> 2) & 3) * 64 + (j & 3)]; }
+    for (int j = threadIdx.x; j < 65 * 16; j += SH_FVT_NTH) sBias[j] = f_.bfrag[((j >> 4) * 64 + ((j >> 2) & 3) * 16) * 4 + (j & 3)];
+
+#define SH_FVT_MT(i) (16 * ((i) >> 1) + 8 * ((i) & 1))           /* m-tile of quad i, less the wave */
+    /* The workgroup's lane (sh_decoder_lanes, sh_sched.h): its segments of tiles, one after the other.  Everything from here to the end of the
+     * loop body is per SEGMENT, as it was per workgroup when a workgroup owned one piece of a tile: the tile's metadata, the start / end state
+     * and producer NPW - 1's parked values, the initial scores or the take-over (with its wait for the arrival flag), the S1 team's prologue
+     * P0 - P4, the block loop, and the hand-over or the final state.  Between two segments one workgroup barrier: the final state's readers
+     * (tid < 16: pendl, redv / redi) against the next segment's first LDS writes. */
+    int sgi = blockIdx.x, sge = blockIdx.x + 1;
+    if (a_.lane_off) { sgi = a_.lane_off[blockIdx.x]; sge = a_.lane_off[blockIdx.x + 1]; }
+    sgi = __builtin_amdgcn_readfirstlane(sgi); sge = __builtin_amdgcn_readfirstlane(sge);
+    for (int si = sgi; si < sge; si++) {
+    if (si > sgi) __syncthreads();
+    /* Nothing but the loop's own counters may live from one segment to the next: the block loop runs at the register cap (168 VGPRs, ~80
+     * SGPRs).  Seen as invariant over the segments, the lane's addresses, the per-thread constants and every kernel argument -- also those
+     * only the prologue and the epilogue use -- are hoisted out of this loop and held through all of it: 106 SGPRs of which 51 spilled into
+     * lanes of a VGPR, and 756 bytes of scratch a lane (24 before), reloaded inside the block loop.  So per segment the wave and lane numbers
+     * are made afresh and opaque, and the arguments are read through an opaque copy of the kernarg pointer (f, a, md in this order, each
+     * 8-byte aligned), with everything that hangs on them formed from those; the register arrays that are first written under a condition
+     * (eN, W, xr) are defined out of nothing where they are declared, or they count as carried over from the segment before. */
+    typedef const __attribute__((address_space(4))) char *kargp;
+    kargp ka = (kargp)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));
+    constexpr size_t KA_A = (sizeof(ShFfArgs) + 7) & ~(size_t)7, KA_MD = (KA_A + sizeof(ShVitArgs) + 7) & ~(size_t)7;
+    static_assert(alignof(ShFfArgs) == 8 && alignof(ShVitArgs) == 8 && alignof(ShMeta) == 8, "kernarg layout");
+    const __attribute__((address_space(4))) ShFfArgs &f = *(const __attribute__((address_space(4))) ShFfArgs *)ka;
+    const __attribute__((address_space(4))) ShVitArgs &a = *(const __attribute__((address_space(4))) ShVitArgs *)(ka + KA_A);
+    const __attribute__((address_space(4))) ShMeta &md = *(const __attribute__((address_space(4))) ShMeta *)(ka + KA_MD);
+    VSTAMP_SEG();
+    int wave = wave_;
+    asm volatile("" : "+s"(wave));
     const bool decoder = wave < NCW;
+    int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    asm volatile("" : "+v"(lane));
+    lane &= 63;                                          /* (its range known again: the lane offsets of the global accesses stay 32-bit) */
+    const int tid = wave * 64 + lane, b = lane & 15, q = lane >> 4;
     const float mp = a.min_prob, mpm1 = 1.0f - a.min_prob;
     const float lbound = (mp > 0.0f) ? 1.0e-3f - __logf(mp) : INFINITY;      /* |log-posterior| <= this */
     const float lbgap = lbound * SH_FVT_GAP;                                  /* (exact: a power of two) */
-    unsigned long long vA = 0, vB = 0, vC = 0, vD = 0, vt0 = 0, vt1 = 0;
-    (void)vt0; (void)vt1;
-#undef VSTAMP
-#if SH_FVT_STAMP
-#define VSTAMP(acc) do { if (a.dbg) { vt1 = __builtin_readcyclecounter(); acc += vt1 - vt0; vt0 = vt1; } } while (0)
-#else
-#define VSTAMP(acc) do { } while (0)
-#endif
-
-    if (tid < KS * 2 * 4 * 4) sStay[tid] = f.wpiece[(long long)(64) * KS * 512 + (tid >> 4) * 256 + ((tid >> 2) & 3) * 64 + (tid & 3)];
-    for (int j = tid; j < 65 * 16; j += SH_FVT_NTH) sBias[j] = f.bfrag[((j >> 4) * 64 + ((j >> 2) & 3) * 16) * 4 + (j & 3)];
-
-    int tile = blockIdx.x, s0 = 0, s1 = -1, ord = 0;
-    if (a.seg) { const ShGruSegD sg = a.seg[blockIdx.x]; tile = sg.tile; s0 = sg.s0; s1 = sg.s1; ord = sg.pad; }
+    /* the decoder team's quads: i = 2 rl + c, in increasing order of Q */
+    const int cw = decoder ? wave : 0;
+    float *myq = sc + cw * 256 + lane * 4;                       /* quad i of this thread: + (16 rl + 8 c) * 256 */
+    const float *mye = ring + cw * 512 + lane * 4;               /* its emissions in the ring: slot 16 rl + 2 w + j */
+    const float *mysrc = sc + cw * 64 + b * 4 + q;               /* state r4 * 256 + Q: + (r4 * 64 + 16 rl + 8 c) * 64 */
+    int tile = si, s0 = 0, s1 = -1, ord = 0;
+    if (a.seg) { const ShGruSegD sg = a.seg[si]; tile = sg.tile; s0 = sg.s0; s1 = sg.s1; ord = sg.pad; }
     tile = __builtin_amdgcn_readfirstlane(tile); s0 = __builtin_amdgcn_readfirstlane(s0); s1 = __builtin_amdgcn_readfirstlane(s1);
     const int Tt = __builtin_amdgcn_readfirstlane(md.tile_T[tile]);
     if (s1 < 0) s1 = Tt;
@@ -154,13 +203,7 @@ __global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShV
     asm volatile("" : "+v"(myT));
     const long long hpo = a.hp_side ? a.hp_off[rd] : 0;
     float pstart = 0.0f, pend = -SH_BIG;
-
-    /* the decoder team's quads: i = 2 rl + c, in increasing order of Q */
-    const int cw = decoder ? wave : 0;
-    float *myq = sc + cw * 256 + lane * 4;                       /* quad i of this thread: + (16 rl + 8 c) * 256 */
-    const float *mye = ring + cw * 512 + lane * 4;               /* its emissions in the ring: slot 16 rl + 2 w + j */
-    const float *mysrc = sc + cw * 64 + b * 4 + q;               /* state r4 * 256 + Q: + (r4 * 64 + 16 rl + 8 c) * 64 */
-#define SH_FVT_MT(i) (16 * ((i) >> 1) + 8 * ((i) & 1))           /* m-tile of quad i, less the wave */
+    vblk += (unsigned)(s1 - s0); vseg++;
 
     if (s0 == 0) {
         /* decode.c:155-159 */
@@ -215,6 +258,11 @@ __global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShV
          * offset): see k_ff_viterbi.  Tile k of a pass lands in buffer (k mod 8) mod WB: the stream is primed afresh for each half. */
         const unsigned *wmine = f.wpiece + (long long)(TPP * pw) * KS * 512;
         ShSplit W[WB][KS];
+        /* (the ring and the raw trunk columns below defined out of nothing per segment: see eN on the decoder team) */
+#pragma unroll
+        for (int k = 0; k < WB; k++)
+#pragma unroll
+            for (int ks = 0; ks < KS; ks++) asm volatile("" : "=v"(W[k][ks].p1), "=v"(W[k][ks].p2));
         const unsigned lofs = (unsigned)lane * 4u;
         typedef const __attribute__((address_space(1))) unsigned *gu32;
         typedef const __attribute__((address_space(1))) u32x4 *gu32x4;
@@ -239,6 +287,7 @@ __global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShV
         /* the trunk columns of blocks u, u + 1, k step min(pw, 2), as raw fp32 (the loads are unconditional: straight-line vmcnt accounting) ... */
         const int xks = pw < KS ? pw : KS - 1;
         f32x4 xr[2][2];
+        asm volatile("" : "=v"(xr[0][0]), "=v"(xr[0][1]), "=v"(xr[1][0]), "=v"(xr[1][1]));
         auto xraw_load = [&](int u) {
 #pragma unroll
             for (int j = 0; j < 2; j++) {
@@ -370,7 +419,12 @@ __global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShV
              * (score - local_pen); the state is the first of its four that attains it */
             float ev; int ei;
             end_unkey(redk[par * 16 + b], ev, ei);
-            redk[par * 16 + b] = 0;
+            {   /* (the empty key from two moves issued HERE: as a plain constant the 64-bit zero is made once in front of the segment loop,
+                 * shared with the slots' other resets, spilled, and reloaded from scratch in this phase) */
+                unsigned zl, zh;
+                asm volatile("v_mov_b32 %0, 0\n\tv_mov_b32 %1, 0" : "=v"(zl), "=v"(zh));
+                redk[par * 16 + b] = ((unsigned long long)zh << 32) | zl;
+            }
             const f32x4 q4 = *(const f32x4 *)(sc + ((ei & (NQ - 1)) * 16 + b) * 4);
             int e0 = 3;
             e0 = (q4[2] - a.local_pen == ev) ? 2 : e0;
@@ -401,6 +455,7 @@ __global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShV
         if (any) { s1_half(H1, s0); __builtin_amdgcn_sched_barrier(0); xraw_load(s0 + 2); }
         lds_barrier();                                      /* P4: the second half is in the ring */
         if (a.dbg) vt0 = __builtin_readcyclecounter();
+        VSTAMP_LOOP();
         for (int t = s0; t < s1; t += 2) {
             const bool more = (t + 2 < s1) && !(SH_FVT_ABL & 1);      /* there is a pair t + 2, t + 3 to prepare */
             /* (per_read in FRONT of the stream's priming: behind it the wave waits with vmcnt(0) for the twelve loads to land -- the scratch registers of
@@ -432,8 +487,7 @@ __global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShV
         if (s1 < Tt) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         __syncthreads();
         if (s1 >= Tt) __syncthreads();
-        if (a.dbg && lane == 0) { unsigned long long *d = a.dbg + ((long long)blockIdx.x * 12 + wave) * 8; d[0] = vA; d[1] = vB; d[2] = vC; d[3] = vD; d[4] = (unsigned long long)(s1 - s0); }
-        return;
+        continue;                                           /* the lane's next segment */
     }
     {
         /* ================================================================== */
@@ -443,6 +497,10 @@ __global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShV
          * first block brings the odd ones; phase B of the second block brings the NEXT pair's even quads, into the first block's registers (dead
          * by then: block u + 2 -> its even slots, block u + 3 -> its odd slots, moved over to the second block's even slots behind its phase C) */
         f32x4 eN[2][PPT];
+        /* (defined here out of nothing: what is undefined at the head of a segment is taken for the segment before's, and carried round the
+         * segment loop through scratch) */
+#pragma unroll
+        for (int i = 0; i < PPT; i++) asm volatile("" : "=v"(eN[0][i]), "=v"(eN[1][i]));
         /* half a pass out of the ring: slot 16 rl + 2 w + j -> (rl, block j) */
         auto drain = [&](auto a0, auto s0c, auto a1, auto s1c) {
             constexpr int A0 = decltype(a0)::value, S0 = decltype(s0c)::value, A1 = decltype(a1)::value, S1 = decltype(s1c)::value;
@@ -458,6 +516,7 @@ __global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShV
         lds_barrier();                                      /* P3 */
         lds_barrier();                                      /* P4 */
         if (a.dbg) vt0 = __builtin_readcyclecounter();
+        VSTAMP_LOOP();
         const unsigned tofs = (unsigned)lane;
         /* one block.  FIRST: the first block of its pair -- phase B takes the pair's second half (odd quads) out of the ring; else the first half of the next pair */
         auto block = [&](const int t, auto first_c) {
@@ -714,8 +773,11 @@ __global__ __launch_bounds__(SH_FVT_NTH) void k_ff_viterbi_teams(ShFfArgs f, ShV
             if (tid < 16) { vst[NH * 16 + b] = pstart; vst[NH * 16 + 16 + b] = pend; }
         }
     }
-    if (a.dbg && lane == 0) { unsigned long long *d = a.dbg + ((long long)blockIdx.x * 12 + wave) * 8; d[0] = vA; d[1] = vB; d[2] = vC; d[3] = vD; d[4] = (unsigned long long)(s1 - s0); }
+    }       /* the lane's segments */
+    if (a_.dbg && (threadIdx.x & 63) == 0) { unsigned long long *d = a_.dbg + ((long long)blockIdx.x * 12 + wave_) * 8; d[0] = vA; d[1] = vB; d[2] = vC; d[3] = vD; d[4] = vblk; d[5] = vP; d[6] = vseg; }
 #undef VSTAMP
+#undef VSTAMP_SEG
+#undef VSTAMP_LOOP
 #undef SH_FVT_MT
 }
 

@@ -80,7 +80,7 @@ static scrappie_hip_engine *make_helper(scrappie_hip_engine *e) {
 }
 static void sync_helper(scrappie_hip_engine *e, scrappie_hip_engine *t) {
     t->handover = e->handover; t->max_launch_reads = e->max_launch_reads; t->max_launch_blocks = e->max_launch_blocks;
-    t->dbg_ff_separate = e->dbg_ff_separate; t->dbg_fv_single = e->dbg_fv_single; t->dbg_gru32 = e->dbg_gru32; t->dbg_gru_tiles = e->dbg_gru_tiles; t->dbg_decoder_cus = e->dbg_decoder_cus; t->dbg_redo_all = e->dbg_redo_all;
+    t->dbg_ff_separate = e->dbg_ff_separate; t->dbg_fv_single = e->dbg_fv_single; t->dbg_gru32 = e->dbg_gru32; t->dbg_gru_tiles = e->dbg_gru_tiles; t->dbg_decoder_cus = e->dbg_decoder_cus; t->dbg_decoder_lanes = e->dbg_decoder_lanes; t->dbg_redo_all = e->dbg_redo_all;
     t->profiling = false;
 }
 static scrappie_hip_engine *tail_engine(scrappie_hip_engine *e) {

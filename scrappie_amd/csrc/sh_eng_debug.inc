@@ -29,6 +29,7 @@ extern "C" int scrappie_hip_debug_option(scrappie_hip_engine *e, const char *nam
     else if (!strcmp(name, "dwell_tight")) e->dbg_dwell_tight = value != 0;
     else if (!strcmp(name, "gru_tiles")) e->dbg_gru_tiles = value;
     else if (!strcmp(name, "decoder_cus")) e->dbg_decoder_cus = value > 0 ? value : 0;      /* the decoder's piece schedule believes the device has this many CUs (0: its own count) */
+    else if (!strcmp(name, "decoder_lanes")) e->dbg_decoder_lanes = value > 0 ? value : 0;  /* the two-team decoder's lane layout believes the device has this many CUs (0: its own count) */
     else if (!strcmp(name, "force_f32_layers")) e->dbg_force_f32 = value != 0;
 #ifdef SH_EXPERIMENTS
     else if (!strcmp(name, "gru32")) e->dbg_gru32 = value;
@@ -54,8 +55,9 @@ extern "C" int scrappie_hip_debug_option(scrappie_hip_engine *e, const char *nam
  * "final_scores" ([tile][states x 16 reads + 16 start + 16 end] floats; needs the dump_final option),
  * "order" (int per tiled position: index of the read in the call, -1 = padding), "tile_boff" (long long per tile),
  * "n_redo" (unsigned long long: reads k_stitch has left to the host since the engine was created), "gru_tiles" (int:
- * tiles per workgroup of the group's recurrent layers, 1 or 2), "decoder_pieces" (int: workgroups of the group's decoder launch = pieces of
- * tiles; the "decoder_cus" option cuts small groups).
+ * tiles per workgroup of the group's recurrent layers, 1 or 2), "decoder_pieces" (int: segments of tiles the group's decoder launch ran -- one per workgroup for the
+ * kernels that own a piece of a tile, all the segments its workgroups walked for the two-team kernel's lane layout; the "decoder_cus" and
+ * "decoder_lanes" options cut small groups), "decoder_wgs" (int: workgroups of that launch).
  * Returns the number of bytes the buffer holds (copies min(that, nbytes)), -1 on error. */
 extern "C" long long scrappie_hip_debug_fetch(scrappie_hip_engine *e, const char *what, void *dst, size_t nbytes) {
     if (!e || !what) return set_err("debug_fetch: null argument");
@@ -81,7 +83,8 @@ extern "C" long long scrappie_hip_debug_fetch(scrappie_hip_engine *e, const char
     else if (!strcmp(what, "n_tail_calls")) { src = &e->n_tail_calls; have = 8; host = true; }
     else if (!strcmp(what, "n_tail_reads")) { src = &e->n_tail_reads; have = 8; host = true; }
     else if (!strcmp(what, "gru_tiles")) { src = &gru_tiles; have = 4; host = true; }
-    else if (!strcmp(what, "decoder_pieces")) { src = &lg.vit_nwg; have = 4; host = true; }
+    else if (!strcmp(what, "decoder_pieces")) { src = &lg.vit_launched; have = 4; host = true; }
+    else if (!strcmp(what, "decoder_wgs")) { src = &lg.vit_launched_wg; have = 4; host = true; }
     else if (!strcmp(what, "pinned_bytes")) {      /* pinned host memory this engine holds (staging, results, metadata; both slots) */
         static thread_local unsigned long long tot;
         tot = e->slots[0].pinned_bytes() + e->slots[1].pinned_bytes();

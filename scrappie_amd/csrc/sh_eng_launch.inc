@@ -5,7 +5,7 @@
 /* ------------------------------------------------------------------ */
 /* launch-group construction                                            */
 /* ------------------------------------------------------------------ */
-struct MetaPtrs { ShMeta md; const long long *seq_off, *hp_off, *bases_off; ShGruLanes lanes, lanes1; ShGruPairs pairs, pairs2; const ShGruSegD *vseg; ShDwellArgs dw; };
+struct MetaPtrs { ShMeta md; const long long *seq_off, *hp_off, *bases_off; ShGruLanes lanes, lanes1; ShGruPairs pairs, pairs2; const ShGruSegD *vseg, *vlseg; const int *vloff; ShDwellArgs dw; };
 
 /* Bytes of bases reserved for a read whose path has nentry entries.  Plain stitching: k of the first k-mer + at most k per later entry (k <= 5), a
  * bound.  With the dwell correction a call has no bound of that kind: a homopolymer of hdwell samples gets round(hdwell / scale) bases, and the scale
@@ -100,17 +100,24 @@ static int build_group(scrappie_hip_engine *e, Slot &sl, Model *m, const uint64_
     ShGruSchedule sched32b;
     sh_lane_schedule(pair_T.data(), pair_T.size(), e->ncu, 2, sched32b, e->handover);
     lg.gru32x2_nwg = sched32b.nwg;
-    std::vector<ShGruSeg> vseg;                  /* decoder: one piece of a tile per workgroup */
+    std::vector<ShGruSeg> vseg;                  /* decoder, k_viterbi and k_ff_viterbi: one piece of a tile per workgroup */
     sh_piece_schedule(tile_T.data(), lg.ntile, e->dbg_decoder_cus > 0 ? e->dbg_decoder_cus : e->ncu, vseg, e->handover);
     lg.vit_nwg = (int)vseg.size();
+    /* k_ff_viterbi_teams: tiles end to end over one lane per workgroup, cut only where a lane is full (the "decoder_cus" debug option
+     * alone: the equal pieces the other two kernels get, a lane each) */
+    ShGruSchedule vlanes;
+    if (e->dbg_decoder_cus > 0 && e->dbg_decoder_lanes <= 0) sh_pieces_as_lanes(vseg, vlanes);
+    else sh_decoder_lanes(tile_T.data(), lg.ntile, e->dbg_decoder_lanes > 0 ? e->dbg_decoder_lanes : e->ncu, vlanes, e->handover);
+    lg.vit_lane_nwg = vlanes.nwg; lg.vit_lane_nseg = (int)vlanes.seg.size();
     /* pack metadata: [sig_off u64 npad][seq_off i64 npad][hp_off i64 npad][tile_boff i64 ntile][rN i32 npad][rT i32 npad][tile_T i32 ntile] */
     const size_t b_u64 = lg.npad * 8, b_i32 = lg.npad * 4;
     const size_t b_loff = sched.lane_off.size() * 4, b_seg = sched.seg.size() * sizeof(ShGruSeg), b_wit = sched.wg_iter.size() * 4;
-    const size_t b_vloff = 0, b_vseg = vseg.size() * sizeof(ShGruSeg);
+    const size_t b_vseg = vseg.size() * sizeof(ShGruSeg);
+    const size_t b_vloff = vlanes.lane_off.size() * 4, b_vlseg = vlanes.seg.size() * sizeof(ShGruSeg);
     const size_t b_loff1 = sched1.lane_off.size() * 4, b_seg1 = sched1.seg.size() * sizeof(ShGruSeg);
     const size_t b_loff32 = sched32.lane_off.size() * 4, b_seg32 = sched32.seg.size() * sizeof(ShGruSeg), b_pt = pair_tile.size() * 4;
     const size_t b_loff32b = sched32b.lane_off.size() * 4, b_seg32b = sched32b.seg.size() * sizeof(ShGruSeg);
-    const size_t total = 4 * b_u64 + lg.ntile * 8 + 2 * b_i32 + lg.ntile * 4 + 16 + b_seg + b_loff + b_wit + 16 + b_vseg + b_vloff + 16 + b_seg1 + b_loff1 +
+    const size_t total = 4 * b_u64 + lg.ntile * 8 + 2 * b_i32 + lg.ntile * 4 + 16 + b_seg + b_loff + b_wit + 16 + b_vseg + 16 + b_vlseg + b_vloff + 16 + b_seg1 + b_loff1 +
                          16 + b_seg32 + b_loff32 + b_pt + 16 + b_seg32b + b_loff32b;
     if (sl.h_meta.ensure(total + 16) || sl.d_meta.ensure(total + 16)) return -1;
     char *h = sl.h_meta.as<char>();
@@ -129,6 +136,9 @@ static int build_group(scrappie_hip_engine *e, Slot &sl, Model *m, const uint64_
     memcpy(h + o, sched.wg_iter.data(), b_wit); const size_t o_wit = o; o += b_wit;
     o = (o + 15) & ~(size_t)15;
     memcpy(h + o, vseg.data(), b_vseg); const size_t o_vseg = o; o += b_vseg;
+    o = (o + 15) & ~(size_t)15;
+    memcpy(h + o, vlanes.seg.data(), b_vlseg); const size_t o_vlseg = o; o += b_vlseg;
+    memcpy(h + o, vlanes.lane_off.data(), b_vloff); const size_t o_vloff = o; o += b_vloff;
     o = (o + 15) & ~(size_t)15;
     memcpy(h + o, sched1.seg.data(), b_seg1); const size_t o_seg1 = o; o += b_seg1;
     memcpy(h + o, sched1.lane_off.data(), b_loff1); const size_t o_loff1 = o; o += b_loff1;
@@ -159,6 +169,8 @@ static int build_group(scrappie_hip_engine *e, Slot &sl, Model *m, const uint64_
     mp.lanes.wg_iter = (const int *)(d + o_wit);
     mp.lanes.ntile = (int)lg.ntile;
     mp.vseg = (const ShGruSegD *)(d + o_vseg);
+    mp.vlseg = (const ShGruSegD *)(d + o_vlseg);
+    mp.vloff = (const int *)(d + o_vloff);
     if (e->d_hstate.ensure(std::max<size_t>(lg.ntile, 1) * 12 * 256 * 4) || sl.d_gflag.ensure((lg.ntile + 1) * 4)) return -1;
     mp.lanes.hstate = e->d_hstate.as<float>();
     mp.lanes.flag = sl.d_gflag.as<unsigned>();

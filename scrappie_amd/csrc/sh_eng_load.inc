@@ -351,6 +351,20 @@ extern "C" long scrappie_hip_decoder_pieces(const int *tile_T, size_t ntile, int
     return (long)v.size();
 }
 
+/* The lane layout of the two-team decoder (sh_decoder_lanes, sh_sched.h), host only: one lane per workgroup; lane_off needs ncu + 1
+ * ints, seg takes cap rows of {tile, first block, end block, ordinal of the segment within its tile}, each lane's segments in the order
+ * they run.  capacity: M in blocks.  Returns the number of segments (even if > cap). */
+extern "C" long scrappie_hip_decoder_lanes(const int *tile_T, size_t ntile, int ncu, int *nwg, int *capacity, int *lane_off, int *seg, size_t cap) {
+    if (!tile_T || ncu < 1) return -1;
+    ShGruSchedule sc;
+    sh_decoder_lanes(tile_T, ntile, ncu, sc);
+    if (nwg) *nwg = sc.nwg;
+    if (capacity) *capacity = sc.capacity;
+    if (lane_off) memcpy(lane_off, sc.lane_off.data(), sc.lane_off.size() * sizeof(int));
+    if (seg) for (size_t i = 0; i < sc.seg.size() && i < cap; i++) memcpy(seg + 4 * i, &sc.seg[i], 16);
+    return (long)sc.seg.size();
+}
+
 /* Cut a list of reads (input order kept) into launch groups of at most max_reads reads and at most
  * max_blocks column blocks (16 reads x 1 block; what the device arena is proportional to).  Tiles are
  * formed from reads sorted by length inside a group, so a group's column blocks are bounded by

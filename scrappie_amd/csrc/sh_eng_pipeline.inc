@@ -327,10 +327,15 @@ static int stage_decode_transducer(Slot &sl, Model *m, GroupRun &c, const float 
     va.dump_final = e->dbg_dump_final ? 1 : 0;
     static StampBuf vst;      /* SH_VIT_STAMP: cycle stamps of every decoder launch on stderr (tuning aid) */
     if (tun().vit_stamp) va.dbg = vst.dev(4096 * 16 * 8);
-    /* more tiles than CUs: tiles are decoded in pieces that hand their state over through HBM (sh_sched.h) */
+    /* more tiles than CUs: tiles are cut between workgroups, which hand their state over through HBM (sh_sched.h): the two-team kernel's
+     * workgroups walk a lane of segments each, the other two kernels own one piece of a tile per workgroup */
     if (e->d_vstate.ensure(std::max<size_t>(lg.ntile, 1) * ((size_t)NH * 16 + 32) * 4) || e->d_vflag.ensure(std::max<size_t>(lg.ntile, 1) * 4)) return -1;
     HIPCHK(hipMemsetAsync(e->d_vflag.p, 0, std::max<size_t>(lg.ntile, 1) * 4, s));
-    va.seg = mp.vseg;
+    va.seg = mp.vseg; va.lane_off = nullptr;
+    const bool teams = fused && !p->use_slip && !(tun().fv_single || e->dbg_fv_single);
+    if (teams) { va.seg = mp.vlseg; va.lane_off = mp.vloff; }
+    const int vit_nwg = teams ? lg.vit_lane_nwg : lg.vit_nwg;
+    lg.vit_launched = teams ? lg.vit_lane_nseg : lg.vit_nwg; lg.vit_launched_wg = vit_nwg;
     va.vstate = e->d_vstate.as<float>(); va.flag = e->d_vflag.as<unsigned>(); va.err = sl.d_gflag.as<unsigned>() + lg.ntile;
     /* the other slot's traceback walk (on the copy stream) reads the buffers this decode overwrites */
     if (e->ev_ok && e->other(sl).pending) HIPCHK(hipStreamWaitEvent(s, e->other(sl).done, 0));
@@ -340,11 +345,17 @@ static int stage_decode_transducer(Slot &sl, Model *m, GroupRun &c, const float 
         fa.in_div = p->tempW / p->tempb; fa.out_div = p->tempb;
         fa.no_clamp = (m->ff_no_clamp && !e->alt_trunk) ? 1 : 0;      /* (the trunk-input hook feeds activations that need not be gate outputs) */
         va.E = nullptr; va.sums = nullptr;
-        if (launch_ff_viterbi(s, fa, va, mp.md, (size_t)lg.vit_nwg, tun().fv_single || e->dbg_fv_single)) return -1;
-    } else if (launch_viterbi(s, NH, va, mp.md, (size_t)lg.vit_nwg)) return -1;
-    if (va.dbg) vst.dump_on(0, s, (size_t)std::max(lg.vit_nwg, 1) * 16 * 8, [&](const unsigned long long *h) {
-        const int nwv = (fused && !va.use_slip && !(tun().fv_single || e->dbg_fv_single)) ? 12 : 8;       /* the two-team kernel stamps twelve waves (8-11: the S1 team) */
-        for (int w = 0; w < nwv; w++) { const unsigned long long *d = &h[((size_t)(lg.vit_nwg / 2) * nwv + w) * 8]; fprintf(stderr, "vit stamp wave %d: phaseB %.0f bar %.0f phaseC %.0f bar %.0f cycles/block\n", w, d[0] / (double)d[4], d[1] / (double)d[4], d[2] / (double)d[4], d[3] / (double)d[4]); }
+        if (launch_ff_viterbi(s, fa, va, mp.md, (size_t)vit_nwg, !teams)) return -1;
+    } else if (launch_viterbi(s, NH, va, mp.md, (size_t)vit_nwg)) return -1;
+    if (va.dbg) vst.dump_on(0, s, (size_t)std::max(vit_nwg, 1) * 16 * 8, [&](const unsigned long long *h) {
+        const int nwv = teams ? 12 : 8;       /* the two-team kernel stamps twelve waves (8-11: the S1 team) */
+        for (int w = 0; w < nwv; w++) {
+            const unsigned long long *d = &h[((size_t)(vit_nwg / 2) * nwv + w) * 8];
+            fprintf(stderr, "vit stamp wave %d: phaseB %.0f bar %.0f phaseC %.0f bar %.0f cycles/block", w, d[0] / (double)d[4], d[1] / (double)d[4], d[2] / (double)d[4], d[3] / (double)d[4]);
+            /* the two-team kernel: what a segment costs outside the block loop, from its first instruction to the barrier that opens the loop */
+            if (teams && d[6]) fprintf(stderr, "; %llu blocks in %llu segments, prologue %.0f cycles/segment", d[4], d[6], d[5] / (double)d[6]);
+            fprintf(stderr, "\n");
+        }
     });
     if (c.pf.mark(Marks::DECODE_END, s)) return -1;
     c.pf.span(F_DECODE, Marks::S1_END, Marks::DECODE_END);

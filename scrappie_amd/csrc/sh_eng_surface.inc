@@ -373,7 +373,7 @@ static void decode_batch(scrappie_hip_engine *e, std::vector<DecReq *> &reqs, co
         va.tb = dtb.as<unsigned>(); va.tb_end = dtbe.as<int>();
         va.final_state = dfs.as<int>(); va.final_score = dfsc.as<float>();
         va.hp_side = nullptr; va.hp_off = nullptr; va.dbg = nullptr; va.dump_final = 0;
-        va.seg = nullptr; va.vstate = nullptr; va.flag = nullptr; va.err = nullptr;   /* one workgroup per read, the whole tile */
+        va.seg = nullptr; va.lane_off = nullptr; va.vstate = nullptr; va.flag = nullptr; va.err = nullptr;   /* one workgroup per read, the whole tile */
         if (launch_viterbi(s, NH, va, md, n)) break;
         /* lane 0 of every tile: the other lanes hold the same path */
         hipLaunchKernelGGL(k_backtrace_lane0, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, dtb.as<unsigned>(), dtbe.as<int>(), dfs.as<int>(), md,

@@ -13,7 +13,14 @@
  * overlap in time; the consumer still checks an arrival flag.  Lanes are
  * numbered so that the producing piece sits in the lower-numbered workgroup.
  *
- * Plain host C++ (no HIP): unit-tested on CPU through scrappie_hip_gru_schedule.
+ * The decoder's two-team kernel (k_ff_viterbi_teams) walks such a layout with one lane per
+ * workgroup: sh_decoder_lanes, the same rule counted in PAIRS of blocks, because that kernel's
+ * block loop steps two blocks at a time (a tile of 2 k - 1 blocks takes as long as one of 2 k) and
+ * a cut must fall on an even block.  The decoder's other two kernels (k_viterbi, k_ff_viterbi)
+ * own one piece of a tile per workgroup and keep the equal pieces of sh_piece_schedule below.
+ *
+ * Plain host C++ (no HIP): unit-tested on CPU through scrappie_hip_gru_schedule and
+ * scrappie_hip_decoder_lanes.
  */
 #ifndef SH_SCHED_H
 #define SH_SCHED_H
@@ -130,5 +137,37 @@ static inline void sh_piece_schedule(const int *tile_T, size_t ntile, int ncu, s
             const int s0 = std::min(T, k * len), s1 = std::min(T, (k + 1) * len);
             if (s1 > s0) seg.push_back({(int)t, s0, s1, k});          /* pad = ordinal of the piece within its tile */
         }
+}
+
+/* Decoder lanes (k_ff_viterbi_teams): tiles end to end over one lane per workgroup, min(CUs, live tiles)
+ * workgroups, by sh_lane_schedule's rule in units of block PAIRS -- a tile of T blocks costs ceil(T / 2)
+ * pair steps, the capacity is M / 2 = max(longest tile's pairs, ceil(sum of pairs / lanes)), and a cut
+ * falls between two pairs: every segment starts on an even block, and only a tile's true end is odd.
+ * out.capacity is M in blocks (even); out.seg lists each lane's segments in the order they run, with
+ * ShGruSeg.pad = the segment's ordinal within its tile (0: it starts the tile; 1: it takes the tile over
+ * from the segment that did -- M >= the longest tile, so no tile is cut twice).  A cut tile's first
+ * blocks open a lane and its last blocks close the next higher-numbered one, at least a tile's length
+ * later: the consumer's wait on the arrival flag finds it set unless workgroups start unevenly.
+ * With no more live tiles than lanes (or !allow_split) the tiles stay whole. */
+static inline void sh_decoder_lanes(const int *tile_T, size_t ntile, int ncu, ShGruSchedule &out, bool allow_split = true) {
+    std::vector<int> pairs(ntile);
+    for (size_t t = 0; t < ntile; t++) pairs[t] = tile_T[t] > 0 ? (tile_T[t] + 1) / 2 : 0;
+    sh_lane_schedule(pairs.data(), ntile, ncu, 1, out, allow_split);
+    out.capacity *= 2;
+    for (int &w : out.wg_iter) w *= 2;
+    for (ShGruSeg &sg : out.seg) {
+        sg.s0 *= 2;
+        sg.s1 = std::min(2 * sg.s1, tile_T[sg.tile]);
+        sg.pad = sg.s0 > 0 ? 1 : 0;
+    }
+}
+/* the equal pieces as a layout of one-segment lanes (the "decoder_cus" debug option: the two-team kernel cut as the other two are) */
+static inline void sh_pieces_as_lanes(const std::vector<ShGruSeg> &piece, ShGruSchedule &out) {
+    out = ShGruSchedule();
+    out.nwg = (int)piece.size();
+    out.seg = piece;
+    out.lane_off.resize(piece.size() + 1);
+    for (size_t i = 0; i <= piece.size(); i++) out.lane_off[i] = (int)i;
+    for (const ShGruSeg &sg : piece) { out.wg_iter.push_back(sg.s1 - sg.s0); out.capacity = std::max(out.capacity, sg.s1 - sg.s0); }
 }
 #endif
