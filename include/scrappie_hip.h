@@ -766,6 +766,45 @@ long long scrappie_hip_squiggle_band_plan(const size_t *npos, const size_t *widt
                                           long long *scr_off, long long *tb_off);
 /* launches of each k_squig_band form in this process: index (viterbi ? 2 : 0) | (scratch ? 1 : 0) */
 void scrappie_hip_squiggle_band_form_counts(uint64_t forms[4]);
+/* One signal against many candidate squiggles, unbanded (sh_squig_pack.h, sh_eng_squig_pack.inc): which of these squiggles does
+ * this signal fit best?  cands[i] holds read i's candidates; a cand array that several reads point at is checked, turned into
+ * tables and packed once, and uploaded once per launch.  A read's signal is uploaded once; its candidates are laid end to end
+ * into packs, every pack of every read of a launch a workgroup of one k_squig_pack launch; a candidate too long for a pack,
+ * or left alone in its pack (unless the debug option "squig_pack_lone" is 1), goes through k_squig in the same call.  out[i].score[k] (malloc'd, ncand floats) is the raw squiggle_match_viterbi / _forward
+ * score of (reads[i], cands[i].cand[k]) -- in Viterbi the bits scrappie_hip_squiggle_match_batch gives for that pair --; START
+ * and END absorb what a candidate leaves of the window, so candidates of different lengths compare as they are.  best: the
+ * highest finite score, the lowest index on a tie, -1: none.  With viterbi and want_path, path (malloc'd, n entries) is the
+ * best candidate's path_padded, from a second pass of k_squig / k_squig_walk on that pair alone.  A candidate with no params, no
+ * positions, a stride below 3 or more than the longest squiggle mapped gets NAN and its neighbours are scored; a read that
+ * fails its own checks or fits no launch gets every score NAN and best -1, the others untouched; the first such reason is the
+ * error text, the return 0.  An invalid rate or prob_back, or a failed launch, fails the call (-1, out[] freed and blanked).
+ * scrappie_hip_squiggle_timing covers these calls too. */
+typedef struct { const scrappie_hip_squiggle_target *cand; size_t ncand; } scrappie_hip_squiggle_candidates;
+typedef struct { float *score; size_t ncand; int best; size_t n; int32_t *path; } scrappie_hip_squiggle_multi_result;
+int scrappie_hip_squiggle_match_multi_batch(scrappie_hip_engine *e, const raw_table *reads, const scrappie_hip_squiggle_candidates *cands,
+                                            size_t n, const scrappie_hip_squiggle_params *p, int viterbi, int want_path,
+                                            scrappie_hip_squiggle_multi_result *out);
+void scrappie_hip_free_squiggle_multi_results(scrappie_hip_squiggle_multi_result *r, size_t n);
+/* the same for one read on the process-default engine, scores only: score[ncand]; p NULL: the defaults.  0, or -1 */
+int scrappie_hip_squiggle_match_multi(const raw_table signal, const scrappie_hip_squiggle_target *cand, size_t ncand,
+                                      const scrappie_hip_squiggle_params *p, int viterbi, float *score);
+/* The packing on the host, no device.  Candidates of npos[k] positions (a cell each) into packs of at most pack_cells cells (at
+ * most scrappie_hip_squiggle_pack_max_cells(), which follows from the LDS a cell, a candidate and an END piece take), in input
+ * order: a pack closes when the next candidate would take it past pack_cells.  pack[k]: the candidate's pack, cell[k]: its first
+ * cell there; -1 both where the candidate has more positions than a pack may hold (it takes k_squig) or none.  Returns the
+ * number of packs.  The debug option "squig_pack_cells" sets an engine's pack_cells (0: every candidate through k_squig, one
+ * workgroup each; -1: the default; a NULL engine: the process-default engine). */
+long scrappie_hip_squiggle_pack_plan(const size_t *npos, size_t ncand, size_t pack_cells, int *pack, long long *cell);
+size_t scrappie_hip_squiggle_pack_max_cells(void);
+/* pack `which` of that plan as k_squig_pack reads it: per cell of the pack wa (position in its candidate | the candidate's index
+ * in the pack << 12 | 1 << 24 position 0 | 1 << 25 position 1 | 1 << 26 position <= npos - 2) and wb (its END piece | 1 << 30 on
+ * the piece's first cell); per candidate of the call piece0[k] / npiece[k], its pieces in the pack (untouched for candidates of
+ * other packs).  A piece is a candidate's cells inside one group of 64 consecutive cells.  Any array may be NULL.  Returns the
+ * pack's pieces. */
+size_t scrappie_hip_squiggle_pack_layout(const size_t *npos, size_t ncand, const int *pack, int which, int *wa, int *wb, int *piece0,
+                                         int *npiece);
+/* launches of each k_squig_pack form in this process: index viterbi (0: forward, 1: Viterbi) */
+void scrappie_hip_squiggle_pack_form_counts(uint64_t forms[2]);
 /* Squiggle prediction, batched (sh_eng_sqnet.inc): seqs[i] holds n[i] bases coded 0..3; out[i] becomes a matrix as
  * squiggle_r94 returns it (free_scrappie_matrix), predicted with `model`, a squiggle model loaded on e under that name.
  * The accepted sequences are laid end to end: one upload, one k_sqnet launch over all their tiles, one download; the call

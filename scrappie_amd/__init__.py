@@ -101,6 +101,15 @@ class _SquigResult(C.Structure):
     _fields_ = [("score", C.c_float), ("n", C.c_size_t), ("path", C.POINTER(C.c_int32))]
 
 
+class _SquigCandidates(C.Structure):
+    _fields_ = [("cand", C.POINTER(_SquigTarget)), ("ncand", C.c_size_t)]
+
+
+class _SquigMultiResult(C.Structure):
+    _fields_ = [("score", C.POINTER(C.c_float)), ("ncand", C.c_size_t), ("best", C.c_int), ("n", C.c_size_t),
+                ("path", C.POINTER(C.c_int32))]
+
+
 class _Event(C.Structure):          # scrappie_structures.h:8-15
     _fields_ = [("start", C.c_uint64), ("length", C.c_float), ("mean", C.c_float), ("stdv", C.c_float),
                 ("pos", C.c_int), ("state", C.c_int)]
@@ -395,6 +404,21 @@ def lib():
                                                   C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     L.scrappie_hip_squiggle_band_form_counts.restype = None
     L.scrappie_hip_squiggle_band_form_counts.argtypes = [C.POINTER(C.c_uint64)]
+    L.scrappie_hip_squiggle_match_multi_batch.argtypes = [C.c_void_p, C.POINTER(_RawTable), C.POINTER(_SquigCandidates), C.c_size_t,
+                                                          C.POINTER(_SquigParams), C.c_int, C.c_int, C.POINTER(_SquigMultiResult)]
+    L.scrappie_hip_free_squiggle_multi_results.restype = None
+    L.scrappie_hip_free_squiggle_multi_results.argtypes = [C.POINTER(_SquigMultiResult), C.c_size_t]
+    L.scrappie_hip_squiggle_match_multi.argtypes = [_RawTable, C.POINTER(_SquigTarget), C.c_size_t, C.POINTER(_SquigParams), C.c_int,
+                                                    C.POINTER(C.c_float)]
+    L.scrappie_hip_squiggle_pack_plan.restype = C.c_long
+    L.scrappie_hip_squiggle_pack_plan.argtypes = [C.POINTER(C.c_size_t), C.c_size_t, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
+    L.scrappie_hip_squiggle_pack_max_cells.restype = C.c_size_t
+    L.scrappie_hip_squiggle_pack_max_cells.argtypes = []
+    L.scrappie_hip_squiggle_pack_layout.restype = C.c_size_t
+    L.scrappie_hip_squiggle_pack_layout.argtypes = [C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int),
+                                                    C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.scrappie_hip_squiggle_pack_form_counts.restype = None
+    L.scrappie_hip_squiggle_pack_form_counts.argtypes = [C.POINTER(C.c_uint64)]
     L.scrappie_hip_squiggle_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     L.scrappie_hip_squiggle_lds_max_pos.restype = C.c_size_t
     L.scrappie_hip_map_lds_max_seq.restype = C.c_size_t
@@ -640,6 +664,84 @@ def set_map_pack_cells(value):
     of candidates, 0: every candidate through k_map, -1: the default.  (An `Engine` has `debug_option`.)"""
     if lib().scrappie_hip_debug_option(None, b"map_pack_cells", int(value)) != 0:
         raise RuntimeError("debug_option: " + last_error())
+
+
+def squiggle_pack_form_counts():
+    """Launches of each k_squig_pack form in this process so far (scrappie_hip_squiggle_pack_form_counts): {viterbi: n}."""
+    q = (C.c_uint64 * 2)()
+    lib().scrappie_hip_squiggle_pack_form_counts(q)
+    return {bool(k): int(q[k]) for k in range(2)}
+
+
+def squiggle_pack_max_cells():
+    """The most cells (a candidate squiggle of npos positions takes npos) one pack of k_squig_pack holds; a longer candidate
+    takes k_squig."""
+    return int(lib().scrappie_hip_squiggle_pack_max_cells())
+
+
+def squiggle_pack_plan(npos, pack_cells):
+    """The packing of candidate squiggles of `npos` positions into packs of at most `pack_cells` cells (host arithmetic, no
+    device; scrappie_hip_squiggle_pack_plan): (pack, cell, npack) -- each candidate's pack (-1: too long for any, it takes
+    k_squig) and its first cell there."""
+    a = np.ascontiguousarray(npos, dtype=np.uintp)
+    pack = np.zeros(len(a), dtype=np.int32)
+    cell = np.zeros(len(a), dtype=np.longlong)
+    n = lib().scrappie_hip_squiggle_pack_plan(a.ctypes.data_as(C.POINTER(C.c_size_t)), len(a), int(pack_cells),
+                                              pack.ctypes.data_as(C.POINTER(C.c_int)), cell.ctypes.data_as(C.POINTER(C.c_longlong)))
+    return pack, cell, int(n)
+
+
+def squiggle_pack_layout(npos, pack, which):
+    """Pack `which` of a `squiggle_pack_plan` as k_squig_pack reads it (scrappie_hip_squiggle_pack_layout): (wa, wb, piece0,
+    npiece, pieces) -- the two words of every cell of the pack, and per candidate of the call its first END piece and how
+    many it has (-1 for the candidates of other packs)."""
+    a = np.ascontiguousarray(npos, dtype=np.uintp)
+    pk = np.ascontiguousarray(pack, dtype=np.int32)
+    ncell = int(a[pk == which].sum())
+    wa = np.zeros(max(ncell, 1), dtype=np.int32)
+    wb = np.zeros(max(ncell, 1), dtype=np.int32)
+    piece0 = np.full(max(len(a), 1), -1, dtype=np.int32)
+    npiece = np.full(max(len(a), 1), -1, dtype=np.int32)
+    ip = C.POINTER(C.c_int)
+    n = lib().scrappie_hip_squiggle_pack_layout(a.ctypes.data_as(C.POINTER(C.c_size_t)), len(a), pk.ctypes.data_as(ip), int(which),
+                                                wa.ctypes.data_as(ip), wb.ctypes.data_as(ip), piece0.ctypes.data_as(ip), npiece.ctypes.data_as(ip))
+    return wa[:ncell], wb[:ncell], piece0[:len(a)], npiece[:len(a)], int(n)
+
+
+def set_squiggle_pack_cells(value):
+    """The debug option "squig_pack_cells" of the process-default engine, the one `squiggle_match_many` runs on: cells per
+    pack of candidate squiggles, 0: every candidate through k_squig, -1: the default.  (An `Engine` has `debug_option`.)"""
+    if lib().scrappie_hip_debug_option(None, b"squig_pack_cells", int(value)) != 0:
+        raise RuntimeError("debug_option: " + last_error())
+
+
+def _squig_targets(squiggles):
+    """(the ctypes array of scrappie_hip_squiggle_target for a list of (npos, 3) arrays, what keeps its memory alive)"""
+    keep = []
+    tgs = (_SquigTarget * max(len(squiggles), 1))()
+    for i, sq in enumerate(squiggles):
+        sq = np.ascontiguousarray(sq, dtype=ftype)
+        if sq.ndim != 2 or (sq.shape[0] and sq.shape[1] < 1):
+            raise ValueError("a squiggle should be an (npos, 3) array")
+        keep.append(sq)
+        tgs[i] = _SquigTarget(sq.ctypes.data_as(C.POINTER(C.c_float)) if sq.size else None, sq.shape[0], sq.shape[1])
+    return tgs, keep
+
+
+def squiggle_match_many(rt, squiggles, rate=1.0, back_prob=0.0, local_pen=2.0, skip_pen=5000.0, min_score=5.0, viterbi=True):
+    """The `RawTable` rt as it is (no trimming), over [rt.start, rt.end), against every one of `squiggles` ((npos, 3) arrays
+    or ScrappyMatrix) in one pass on the process-default engine (scrappie_hip_squiggle_match_multi): the float32 raw
+    squiggle_match_viterbi / _forward scores, NaN where a squiggle cannot be matched."""
+    if not isinstance(rt, RawTable):
+        raise TypeError('`rt` should be a RawTable.')
+    sqs = [s.data(as_numpy=True, sloika=False) if isinstance(s, ScrappyMatrix) else s for s in squiggles]
+    tgs, keep = _squig_targets(sqs)
+    p = _SquigParams(rate, back_prob, local_pen, skip_pen, min_score)
+    score = np.full(len(sqs), np.nan, dtype=np.float32)
+    if lib().scrappie_hip_squiggle_match_multi(rt.data(), tgs, len(sqs), C.byref(p), 1 if viterbi else 0,
+                                               score.ctypes.data_as(C.POINTER(C.c_float))) != 0:
+        raise RuntimeError("squiggle_match_multi: " + last_error())
+    return score
 
 
 def map_crf_pack_form_counts():
@@ -2253,6 +2355,62 @@ class Engine(object):
         res = _scores_and_paths(out, n, 'n')
         lib().scrappie_hip_free_squiggle_results(out, n)
         return res
+
+    def match_squiggles(self, signals, candidates, viterbi=True, path=False, rate=1.0, back_prob=0.0, local_pen=2.0,
+                        skip_pen=5000.0, min_score=5.0):
+        """Which of these squiggles does this signal fit best?  Each signal (trimmed, normalised float32 array, or a
+        `RawTable` with its window) against every one of its candidate squiggles ((npos, 3) arrays), unbanded: the signal
+        is uploaded once and the candidates are packed into workgroups of k_squig_pack
+        (scrappie_hip_squiggle_match_multi_batch).  `candidates`: one list of arrays shared by every read (turned into
+        tables and uploaded once per launch), or one list of arrays per read.  Returns [(scores, best, path or None)] in
+        input order: the float32 raw scores as `match_squiggle` gives them (NaN where a candidate, or the read, cannot be
+        matched), the index of the highest (the lowest index on a tie, -1: none) and, with `path`, the Viterbi path of
+        that candidate over the whole signal."""
+        n = len(signals)
+        _path_needs_viterbi(path, viterbi)
+        candidates = list(candidates)
+        shared = all(isinstance(c, np.ndarray) and c.ndim == 2 for c in candidates)
+        if not shared and len(candidates) != n:
+            raise ValueError("one list of candidates per signal")
+        rts, keep = _raw_tables(signals)
+        cds = (_SquigCandidates * max(n, 1))()
+        if shared:
+            made = [_squig_targets(candidates)]
+            for i in range(n):
+                cds[i].cand, cds[i].ncand = made[0][0], len(candidates)
+        else:
+            made = []
+            for i, c in enumerate(candidates):
+                c = list(c)
+                made.append(_squig_targets(c))
+                cds[i].cand, cds[i].ncand = made[i][0], len(c)
+        keep += made
+        p = _SquigParams(rate, back_prob, local_pen, skip_pen, min_score)
+        out = (_SquigMultiResult * max(n, 1))()
+        if lib().scrappie_hip_squiggle_match_multi_batch(self._h, rts, cds, n, C.byref(p), 1 if viterbi else 0, 1 if path else 0, out) != 0:
+            raise RuntimeError("squiggle_match_multi_batch: " + last_error())
+        res = []
+        rs = [out[i] for i in range(n)]
+        for r, pth in zip(rs, _paths(rs, 'n')):
+            sc = np.ctypeslib.as_array(r.score, shape=(r.ncand,)).copy() if r.ncand else np.zeros(0, dtype=np.float32)
+            res.append((sc, int(r.best), pth))
+        lib().scrappie_hip_free_squiggle_multi_results(out, n)
+        return res
+
+    def mappy_multi(self, signals, sequences, model='squiggle_r94', rate=1.0, back_prob=0.0, local_pen=2.0, skip_pen=5000.0,
+                    min_score=5.0):
+        """Each signal against the squiggles predicted for its candidate base sequences: one batched prediction over the
+        DISTINCT sequences, then `match_squiggles` with paths.  `sequences`: one list of strings shared by every read, or
+        one list per read.  Returns [(scores, best, path or None)]; a sequence that is refused scores NaN."""
+        n = len(signals)
+        seqs, shared = _per_read_lists(sequences, n, 'sequences')
+        distinct = sorted(set(seqs) if shared else set(s for lst in seqs for s in lst))
+        sq = dict(zip(distinct, self.predict_squiggle(distinct, model=model, rescale=False))) if distinct else {}
+        empty = np.zeros((0, 3), dtype=ftype)
+        take = lambda lst: [sq[s] if sq[s] is not None else empty for s in lst]
+        cands = take(seqs) if shared else [take(list(lst)) for lst in seqs]
+        return self.match_squiggles(signals, cands, viterbi=True, path=True, rate=rate, back_prob=back_prob, local_pen=local_pen,
+                                    skip_pen=skip_pen, min_score=min_score)
 
     def predict_squiggle(self, sequences, model='squiggle_r94', rescale=False):
         """The predicted squiggle of each base sequence (a str over ACGT, or an int array of codes 0..3), batched

@@ -48,6 +48,7 @@
  *   sh_eng_map_crf_local.inc  flip-flop (CRF) reads mapped into a longer sequence, one workgroup per window (per-read and batched)
  *   sh_eng_map_local.inc      transducer reads mapped into a longer sequence, one workgroup per window, the posterior column staged in LDS (per-read and batched)
  *   sh_eng_squig.inc     mapping of raw signals to predicted squiggles (per-read and batched)
+ *   sh_eng_squig_pack.inc  one signal against many candidate squiggles, packed into workgroups
  *   sh_eng_sqnet.inc     prediction of squiggles from base sequences (per-read and batched)
  *   sh_eng_events.inc    event detection (per-read and batched; kernels in sh_events.h)
  *   sh_eng_crfpost.inc   base probabilities of the flip-flop models (k_crf_post, sh_crf_post.h): inside a launch group and on host matrices
@@ -88,6 +89,7 @@
 #include "sh_map_pack.h"
 #include "sh_squig.h"
 #include "sh_squig_band.h"
+#include "sh_squig_pack.h"
 #include "sh_sqnet.h"
 #include "sh_events.h"
 
@@ -516,6 +518,9 @@ struct scrappie_hip_engine {
     int map_crf_local_stride = -1;   /* start cells a window of k_map_crf_local owns (debug option "map_crf_local_stride"; 0: one window, -1: the default) */
     double map_ms[3] = {0, 0, 0};    /* scrappie_hip_map_batch: network + S1, k_map, k_map_walk + results, summed over the last call's launch groups */
     DpBufs dp_sq; DBuf d_sq_sig, d_sq_tab;       /* squiggle matching (sh_eng_squig.inc): the records' buffers; signals, tables */
+    DBuf d_sqp_rd, d_sqp_sig, d_sqp_w, d_sqp_score; HBuf h_sqp;      /* candidate squiggles in packs (sh_eng_squig_pack.inc): the packs, the reads' signals, the packs' tables and words, scores; signals and scores on the host */
+    bool squig_pack_lone = false;    /* a candidate alone in its pack runs in k_squig_pack all the same (debug option "squig_pack_lone"; default: it takes k_squig) */
+    int squig_pack_cells = -1;       /* cells a pack of candidate squiggles holds (debug option "squig_pack_cells"; 0: every candidate through k_squig, -1: the default) */
     double squig_ms[3] = {0, 0, 0};  /* scrappie_hip_squiggle_match_batch: tables + uploads, k_squig, k_squig_walk + results, summed over the last call's launches */
     DBuf d_sqn[2]; HBuf h_sqn;       /* squiggle prediction (sh_eng_sqnet.inc): tiles | codes, outputs */
     double sqnet_ms[3] = {0, 0, 0};  /* scrappie_hip_squiggle_predict_batch: upload, k_sqnet, download + transform, summed over the last call's launches */
@@ -667,6 +672,7 @@ extern "C" scrappie_hip_params scrappie_hip_default_params(void) {
 #include "sh_eng_map_crf_local.inc"      /* flip-flop reads mapped into a longer sequence, cut into windows (sh_map_crf_local.h): map_crf_to_reference_*, scrappie_hip_map_local_batch */
 #include "sh_eng_map_local.inc"      /* transducer reads mapped into a longer sequence, cut into windows (sh_map_local.h): map_to_reference_*, scrappie_hip_map_post_local_batch */
 #include "sh_eng_squig.inc"      /* squiggle matching (sh_squig.h): squiggle_match_* on the process-default engine, scrappie_hip_squiggle_match_batch */
+#include "sh_eng_squig_pack.inc"      /* one signal against many candidate squiggles (sh_squig_pack.h): scrappie_hip_squiggle_match_multi_batch, scrappie_hip_squiggle_match_multi */
 #include "sh_eng_sqnet.inc"      /* squiggle prediction (sh_sqnet.h): squiggle_r94 and its relatives on the process-default engine, scrappie_hip_squiggle_predict_batch */
 #include "sh_eng_events.inc"      /* event detection (sh_events.h): detect_events on the process-default engine, scrappie_hip_detect_events_batch; `scrappie events` for a batch (scrappie_hip_basecall_events_batch) */
 #include "sh_eng_crfpost.inc"      /* base probabilities of the flip-flop models (sh_crf_post.h): scrappie_hip_basecall_batch_probs, scrappie_hip_posterior_crf_batch */

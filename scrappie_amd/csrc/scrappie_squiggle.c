@@ -126,13 +126,81 @@ static void mappy_usage(FILE *fh) {
           "      --licence, --license   Print licensing information\n"
           "      --model-file=path      Weight container (.scrm); default $SCRAPPIE_MODEL_DIR/<model>.scrm\n"
           "      --device=N             GPU to run on (default 0)\n"
-          "      --band=N               Map inside the diagonal band of half-width N positions (default: no band)\n", fh);
+          "      --band=N               Map inside the diagonal band of half-width N positions (default: no band)\n"
+          "      --all-records          Match the read against every record of the fasta: a table of their scores, then the best\n"
+          "                             record's mapping (not with --band)\n", fh);
+}
+
+/* scrappie_mappy.c:215-228: the header line and one line per sample of the read */
+static void mappy_print(FILE *out, const char *fast5, const char *fasta, float score, const raw_table *rt, const int32_t *path, const_scrappie_matrix sq,
+                        const char *seq) {
+    fprintf(out, "# %s to %s  (score = %f)\n", fast5, fasta, score);
+    fprintf(out, "idx\tsignal\tpos\tbase\tcurrent\tsd\tdwell\n");
+    for (size_t i = 0; i < rt->n; i++) {
+        const int32_t pos = path[i];
+        if (pos >= 0) {
+            const float *col = sq->data.f + (size_t)pos * sq->stride;
+            fprintf(out, "%zu\t%3.6f\t%d\t%c\t%3.6f\t%3.6f\t%3.6f\n", i, rt->raw[i], pos, seq[pos], col[0], expf(col[1]), expf(-col[2]));
+        } else {
+            fprintf(out, "%zu\t%3.6f\t%d\tN\tnan\tnan\tnan\n", i, (i >= rt->start && i < rt->end) ? rt->raw[i] : NAN, pos);
+        }
+    }
+}
+
+/* --all-records: the read against every record of the fasta in one pass (scrappie_hip_squiggle_match_multi_batch): one batched
+ * prediction, the records' scores as a table, then the best record as plain mappy prints it */
+static int mappy_all_records(scrappie_hip_engine *e, const char *model, const char *fasta, const char *fast5, const raw_table *rt,
+                             const scrappie_hip_squiggle_params *p, FILE *out) {
+    struct cli_fasta *recs = NULL;
+    size_t nrec = 0;
+    if (cli_read_fasta(fasta, &recs, &nrec, 0) || nrec == 0) {
+        fprintf(stderr, "scrappie: Failed to open \"%s\" for input.\n\n", fasta);
+        cli_free_fasta(recs, nrec);
+        return EXIT_FAILURE;
+    }
+    int rc = EXIT_FAILURE;
+    int **codes = calloc(nrec, sizeof *codes);
+    size_t *lens = calloc(nrec, sizeof *lens);
+    scrappie_matrix *sq = calloc(nrec, sizeof *sq);
+    scrappie_hip_squiggle_target *tg = calloc(nrec, sizeof *tg);
+    scrappie_hip_squiggle_multi_result res = {0};
+    if (!codes || !lens || !sq || !tg) { fprintf(stderr, "scrappie: out of memory\n"); goto done; }
+    for (size_t k = 0; k < nrec; k++) {          /* a record that cannot be encoded is predicted as an empty sequence: refused, scored nan */
+        codes[k] = recs[k].seq && recs[k].n ? encode_bases_to_integers(recs[k].seq, recs[k].n, 1) : NULL;
+        lens[k] = codes[k] ? recs[k].n : 0;
+    }
+    if (scrappie_hip_squiggle_predict_batch(e, model, (const int *const *)codes, lens, nrec, 0, sq) != 0) {
+        fprintf(stderr, "scrappie: %s\n", scrappie_hip_last_error());
+        goto done;
+    }
+    for (size_t k = 0; k < nrec; k++)
+        if (sq[k]) { tg[k].params = sq[k]->data.f; tg[k].npos = sq[k]->nc; tg[k].stride = sq[k]->stride; }
+    const scrappie_hip_squiggle_candidates cd = {tg, nrec};
+    if (scrappie_hip_squiggle_match_multi_batch(e, rt, &cd, 1, p, 1, 1, &res) != 0 || !res.score) {
+        fprintf(stderr, "scrappie: %s\n", scrappie_hip_last_error());
+        goto done;
+    }
+    const size_t ns = rt->end > rt->start ? rt->end - rt->start : 1;
+    fprintf(out, "record\tname\tscore\tper_sample\n");
+    for (size_t k = 0; k < nrec; k++) fprintf(out, "%zu\t%s\t%f\t%f\n", k, recs[k].name ? recs[k].name : "", res.score[k], res.score[k] / (float)ns);
+    if (res.best < 0 || !res.path) {
+        fprintf(stderr, "scrappie: %s\n", scrappie_hip_last_error());
+        goto done;
+    }
+    mappy_print(out, fast5, fasta, res.score[res.best], rt, res.path, sq[res.best], recs[res.best].seq);
+    rc = EXIT_SUCCESS;
+done:
+    scrappie_hip_free_squiggle_multi_results(&res, 1);
+    for (size_t k = 0; k < nrec; k++) { if (codes) free(codes[k]); if (sq) free_scrappie_matrix(sq[k]); }
+    free(codes); free(lens); free(sq); free(tg);
+    cli_free_fasta(recs, nrec);
+    return rc;
 }
 
 int main_mappy(int argc, char **argv) {
-    enum { O_MODEL = 256, O_LIC, O_MFILE, O_DEV, O_BAND };
+    enum { O_MODEL = 256, O_LIC, O_MFILE, O_DEV, O_BAND, O_ALL };
     static const struct option lo[] = {
-        {"band", 1, 0, O_BAND}, {"model", 1, 0, O_MODEL}, {"backprob", 1, 0, 'b'}, {"skippen", 1, 0, 'k'}, {"localpen", 1, 0, 'l'}, {"minscore", 1, 0, 'm'},
+        {"all-records", 0, 0, O_ALL}, {"band", 1, 0, O_BAND}, {"model", 1, 0, O_MODEL}, {"backprob", 1, 0, 'b'}, {"skippen", 1, 0, 'k'}, {"localpen", 1, 0, 'l'}, {"minscore", 1, 0, 'm'},
         {"output", 1, 0, 'o'}, {"prefix", 1, 0, 'p'}, {"rate", 1, 0, 'r'}, {"segmentation", 1, 0, 's'}, {"trim", 1, 0, 't'},
         {"licence", 0, 0, O_LIC}, {"license", 0, 0, O_LIC}, {"model-file", 1, 0, O_MFILE}, {"device", 1, 0, O_DEV}, {"help", 0, 0, '?'},
         {0, 0, 0, 0}};
@@ -142,6 +210,7 @@ int main_mappy(int argc, char **argv) {
     FILE *out = stdout;
     int trim_start = 200, trim_end = 10, varseg_chunk = 100, device = 0, h, c;
     long band = -1;                      /* half-width of the diagonal band in positions; < 0: none */
+    int all_records = 0;
     float varseg_thresh = 0.0f;
     double pct;
     optind = 1;
@@ -172,6 +241,7 @@ int main_mappy(int argc, char **argv) {
         case O_LIC: cli_licence(); break;
         case O_MFILE: model_file = optarg; break;
         case O_DEV: device = atoi(optarg); break;
+        case O_ALL: all_records = 1; break;
         case O_BAND:
             band = atol(optarg);
             if (band < 0) { fprintf(stderr, "scrappie: --band wants a half-width in positions, 0 or more\n"); return EXIT_FAILURE; }
@@ -181,11 +251,22 @@ int main_mappy(int argc, char **argv) {
     }
     if (argc - optind <= 0) { mappy_usage(stderr); return EXIT_FAILURE; }
     if (argc - optind < 2) { fprintf(stderr, "scrappie: fast5 file is a required argument\n"); return EXIT_FAILURE; }      /* scrappie_mappy.c:152 */
+    if (all_records && band >= 0) { fprintf(stderr, "scrappie: --all-records maps without a band; it cannot be combined with --band\n"); return EXIT_FAILURE; }
     const char *fasta = argv[optind], *fast5 = argv[optind + 1];
     char *mpath = cli_model_path(model, model_file);      /* (the weights first, then the engine) */
     scrappie_hip_engine *e = mpath ? cli_open_model(device, model, mpath, &h) : NULL;
     free(mpath);
     if (!e) return EXIT_FAILURE;
+    if (all_records) {
+        raw_table art = cli_load_read(fast5, trim_start, trim_end, varseg_chunk, varseg_thresh, 1);
+        int arc = EXIT_FAILURE;
+        if (!art.raw) fprintf(stderr, "scrappie: Failed to open \"%s\" for input and trim signal.\n\n", fast5);
+        else arc = mappy_all_records(e, model, fasta, fast5, &art, &p, out);
+        free(art.raw); free(art.uuid);
+        if (out != stdout) fclose(out);
+        scrappie_hip_engine_destroy(e);
+        return arc;
+    }
 
     int rc = EXIT_FAILURE;
     struct cli_fasta *recs = NULL;
@@ -223,18 +304,7 @@ int main_mappy(int argc, char **argv) {
         rc = EXIT_FAILURE;
         goto done;
     }
-    /* scrappie_mappy.c:215-228 */
-    fprintf(out, "# %s to %s  (score = %f)\n", fast5, fasta, res.score);
-    fprintf(out, "idx\tsignal\tpos\tbase\tcurrent\tsd\tdwell\n");
-    for (size_t i = 0; i < rt.n; i++) {
-        const int32_t pos = res.path[i];
-        if (pos >= 0) {
-            const float *col = sq->data.f + (size_t)pos * sq->stride;
-            fprintf(out, "%zu\t%3.6f\t%d\t%c\t%3.6f\t%3.6f\t%3.6f\n", i, rt.raw[i], pos, recs[0].seq[pos], col[0], expf(col[1]), expf(-col[2]));
-        } else {
-            fprintf(out, "%zu\t%3.6f\t%d\tN\tnan\tnan\tnan\n", i, (i >= rt.start && i < rt.end) ? rt.raw[i] : NAN, pos);
-        }
-    }
+    mappy_print(out, fast5, fasta, res.score, &rt, res.path, sq, recs[0].seq);
 done:
     scrappie_hip_free_squiggle_results(&res, 1);
     free_scrappie_matrix(sq);

@@ -750,6 +750,84 @@ long scrappie_hip_map_pack_plan(const size_t *seqlen, size_t ncand, size_t pack_
     return np;
 }
 
+/* Packs of candidate squiggles (k_squig_pack, sh_squig_pack.h; the word counts and the cell words: sh_internal.h). */
+size_t sh_squig_pack_lds_bytes(size_t ncell, size_t ncand, size_t npiece) {
+    return (SH_SQP_CELL_WORDS * ncell + SH_SQP_CAND_WORDS * ncand + SH_SQP_PIECE_WORDS * npiece) * 4;
+}
+
+/* the most cells a pack may hold: what fits SH_SQ_LDS however the cells are shared out among candidates -- a candidate has at least
+ * one cell and a piece at least one, so ncell cells are ncell candidates and ncell pieces at most, and the bytes only grow with ncell */
+size_t scrappie_hip_squiggle_pack_max_cells(void) {
+    size_t c = SH_SQ_LDS / (SH_SQP_CELL_WORDS * 4);
+    while (c > 0 && sh_squig_pack_lds_bytes(c, c, c) > SH_SQ_LDS) c--;
+    return c <= SH_SQP_POS_MASK ? c : SH_SQP_POS_MASK;      /* (what a cell word's fields hold) */
+}
+
+/* Candidates of npos[k] positions (a cell each) into packs of at most pack_cells cells (at most scrappie_hip_squiggle_pack_max_cells()
+ * whatever is asked for), in input order: a pack is closed when the next candidate would take it past pack_cells, so a candidate of
+ * more cells than that is alone in its pack.  pack[k]: the candidate's pack, cell[k]: its first cell there; pack[k] = -1
+ * (cell[k] = -1) where npos[k] exceeds the most a pack may hold -- such a candidate takes k_squig -- or is 0.  Returns the number of
+ * packs. */
+long scrappie_hip_squiggle_pack_plan(const size_t *npos, size_t ncand, size_t pack_cells, int *pack, long long *cell) {
+    if (!npos || !pack || !cell) return 0;
+    const size_t maxc = scrappie_hip_squiggle_pack_max_cells();
+    if (pack_cells > maxc) pack_cells = maxc;
+    long np = 0;
+    size_t used = 0;                    /* cells of the open pack, np - 1; 0: none is open */
+    for (size_t k = 0; k < ncand; k++) {
+        if (npos[k] == 0 || npos[k] > maxc) { pack[k] = -1; cell[k] = -1; continue; }
+        if (used == 0 || used + npos[k] > pack_cells) { np++; used = 0; }
+        pack[k] = (int)(np - 1);
+        cell[k] = (long long)used;
+        used += npos[k];
+    }
+    return np;
+}
+
+size_t sh_squig_pack_layout(const size_t *npos, size_t ncand, int *wa, int *wb, int *piece0, int *npiece) {
+    size_t g = 0, piece = 0;
+    for (size_t k = 0; k < ncand; k++) {
+        const size_t n = npos[k];
+        if (piece0) piece0[k] = (int)piece;
+        for (size_t pos = 0; pos < n; pos++, g++) {
+            const int head = pos == 0 || g % 64 == 0;
+            if (head && pos) piece++;
+            if (wa) wa[g] = (int)pos | (int)(k << SH_SQP_CAND_SHIFT) | (pos == 0 ? SH_SQP_POS0 : 0) | (pos == 1 ? SH_SQP_POS1 : 0) | (pos + 2 <= n ? SH_SQP_RIGHT : 0);
+            if (wb) wb[g] = (int)piece | (head ? SH_SQP_HEAD : 0);
+        }
+        if (n) piece++;
+        if (npiece) npiece[k] = (int)piece - (piece0 ? piece0[k] : 0);
+    }
+    return piece;
+}
+
+/* The same for the tests, from the plan above: the candidates k with pack[k] == which, in their order, laid out as their pack holds
+ * them.  wa / wb: the pack's cell words, piece0 / npiece: per candidate OF THE CALL (untouched for those of other packs); returns the
+ * pack's pieces (0 too where memory runs out). */
+size_t scrappie_hip_squiggle_pack_layout(const size_t *npos, size_t ncand, const int *pack, int which, int *wa, int *wb, int *piece0, int *npiece) {
+    if (!npos || !pack) return 0;
+    size_t n = 0;
+    for (size_t k = 0; k < ncand; k++) n += pack[k] == which;
+    if (n == 0) return 0;
+    size_t *len = malloc(n * sizeof(size_t));
+    int *p0 = malloc(2 * n * sizeof(int));
+    size_t np = 0;
+    if (len && p0) {
+        size_t j = 0;
+        for (size_t k = 0; k < ncand; k++) if (pack[k] == which) len[j++] = npos[k];
+        np = sh_squig_pack_layout(len, n, wa, wb, p0, p0 + n);
+        j = 0;
+        for (size_t k = 0; k < ncand; k++) {
+            if (pack[k] != which) continue;
+            if (piece0) piece0[k] = p0[j];
+            if (npiece) npiece[k] = p0[n + j];
+            j++;
+        }
+    }
+    free(len); free(p0);
+    return np;
+}
+
 /* Bands of the CRF mapping (k_map_crf, sh_map_crf.h): per ENTRY t = 0 .. nblock of the path (nblock + 1 of them) the cells
  * [low[t], high[t]) of 0 .. seqlen, a cell being the number of bases emitted so far.  Valid: it starts at cell 0 and ends with
  * cell seqlen, is never empty or beyond seqlen + 1, both edges non-decreasing, and every entry's lowest cell has a predecessor

@@ -35,6 +35,32 @@ size_t sh_crf_find_lds_bytes(size_t ncell, int pos);
 size_t sh_map_crf_pack_lds_bytes(size_t ncell);
 /* squiggle matching (sh_host.c): the tables of decode.c:1055-1099 from the host's libm; tab holds 5 npos + 4 floats */
 void sh_squiggle_tables(const float *params, size_t npos, size_t ldp, float rate, float prob_back, float *tab, float pens[2]);
+/* packs of candidate squiggles of one read (sh_host.c; k_squig_pack, sh_squig_pack.h).  The limit is sh_squig.h's (the same tokens there).
+ * Per cell (a position and its back state) LDS holds 11 words: two rows of (position, back) values, loc / scale / logsc / move / stay, and the two
+ * words below; per candidate 12: first cell, npos, first piece, pieces, move and stay of START, stay of END, START's two values, END and its step and
+ * skip terms; per END piece 4: (value, origin) in two slots.
+ *   word A of a cell: its 0-based position in its candidate | its candidate's index in the pack << 12 | SH_SQP_POS0 (position 0: its left neighbour is
+ *     START), SH_SQP_POS1 (position 1: START lies two to the left), SH_SQP_RIGHT (position <= npos - 2: it has a right neighbour, is entered by its
+ *     back state's source and is an origin of END); a candidate of 1, 2 or 3 positions is the combinations these give
+ *   word B of a cell: the END piece it belongs to (index in the pack) | SH_SQP_HEAD where it is the piece's first cell
+ * A piece is a candidate's cells inside one group of 64 consecutive cells (one wave of one chunk of 256). */
+#define SH_SQ_LDS 65536
+#define SH_SQP_CELL_WORDS 11
+#define SH_SQP_CAND_WORDS 12
+#define SH_SQP_PIECE_WORDS 4
+#define SH_SQP_IN_CELL_WORDS 7       /* of those, what the host uploads per cell: the five table entries and the two words */
+#define SH_SQP_IN_CAND_WORDS 7       /* ... and per candidate: first cell, npos, first piece, pieces, move[START], stay[START], stay[END] */
+#define SH_SQP_POS_MASK 0xfff
+#define SH_SQP_CAND_SHIFT 12
+#define SH_SQP_POS0 (1 << 24)
+#define SH_SQP_POS1 (1 << 25)
+#define SH_SQP_RIGHT (1 << 26)
+#define SH_SQP_HEAD (1 << 30)
+#define SH_SQP_PIECE_MASK 0xfff
+size_t sh_squig_pack_lds_bytes(size_t ncell, size_t ncand, size_t npiece);
+/* the cell words and piece table of one pack of ncand candidates of npos[k] positions laid end to end: wa / wb [sum npos], piece0 / npiece [ncand]
+ * (any may be NULL); returns the pack's pieces */
+size_t sh_squig_pack_layout(const size_t *npos, size_t ncand, int *wa, int *wb, int *piece0, int *npiece);
 /* dwell correction (sh_host.c): the scale from pos / state (n ints each, `stride` bytes apart), the prior's numerator of an event table, and
  * the whole step on a read the engine holds as arrays (path of n + ntrail entries, n dwells; pos_out may be NULL): the corrected call, the
  * plain one where there is no correction, NULL without a k-mer */
