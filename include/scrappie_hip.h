@@ -805,6 +805,46 @@ size_t scrappie_hip_squiggle_pack_layout(const size_t *npos, size_t ncand, const
                                          int *npiece);
 /* launches of each k_squig_pack form in this process: index viterbi (0: forward, 1: Viterbi) */
 void scrappie_hip_squiggle_pack_form_counts(uint64_t forms[2]);
+/* A raw signal mapped INTO a longer reference squiggle (k_squig_local, sh_squig_local.h; sh_eng_squig_local.inc): where in the
+ * reference does this signal lie?  Not in the reference project.  The definition is squiggle_match_viterbi / _forward with the
+ * squiggle side made local: the move out of START enters at EVERY position and one END accumulator per position lets every
+ * position leave, both without a distance term; START and END still absorb samples at local_pen each; START has no step or skip
+ * of its own; the score is the best of the last row's position cells and END accumulators (Viterbi), or their log-sum.  The
+ * score is never below squiggle_match_viterbi's for local_pen >= 0, and with local_pen = 0 and a path that ends in END it is
+ * squiggle_match_viterbi's bit for bit.  The reference is cut into windows by the entry position of a path, one workgroup each; the
+ * Viterbi score has the same bits for every cut.
+ * Batched: out[i] belongs to (reads[i], targets[i]); a target that several reads point at (the same params, npos and stride) is
+ * checked once per call, goes through the table computation once per call and is uploaded once per launch.  score; n = reads[i].n;
+ * with viterbi: last = the end cell's position + 1; with viterbi and want_path also first, the lowest position on the path, and
+ * path (n entries, malloc'd; scrappie_hip_free_squiggle_local_results): positions in the reference's coordinates, -1 in START, END
+ * and outside [start, end), back states as their position.  Otherwise first = (size_t)-1, last = 0, path = NULL.  A read whose
+ * checks fail, or that fits no launch ("squiggle_budget_kb"), gets NAN and an error text, the others are untouched.  Returns 0, or
+ * -1 when the call as a whole fails (then every score is NAN).  scrappie_hip_squiggle_timing covers these calls too: [0] tables +
+ * uploads, [1] the first pass, [2] the second pass, the walk and the results. */
+typedef struct { float score; size_t first, last, n; int32_t *path; } scrappie_hip_squiggle_local_result;
+int scrappie_hip_squiggle_match_local_batch(scrappie_hip_engine *e, const raw_table *reads, const scrappie_hip_squiggle_target *targets,
+                                            size_t n, const scrappie_hip_squiggle_params *p, int viterbi, int want_path,
+                                            scrappie_hip_squiggle_local_result *out);
+void scrappie_hip_free_squiggle_local_results(scrappie_hip_squiggle_local_result *r, size_t n);
+/* the same for one read on the process-default engine, with squiggle_match_viterbi's arguments: path_padded (signal.n entries),
+ * first and last may each be NULL; NAN and an error text where squiggle_match_viterbi gives them */
+float squiggle_match_local_viterbi(const raw_table signal, float rate, const_scrappie_matrix params, float prob_back, float local_pen,
+                                   float skip_pen, float minscore, int32_t *path_padded, size_t *first, size_t *last);
+float squiggle_match_local_forward(const raw_table signal, float rate, const_scrappie_matrix params, float prob_back, float local_pen,
+                                   float skip_pen, float minscore);
+/* The cut into windows on the host, no device.  stride: entry positions per window; 0: one window; < 0: the default.  Window w owns
+ * the entry positions [w s, min((w + 1) s, npos)) (own[w] of them) and holds the cells first[w] = max(w s - 1, 0) ..
+ * min(w s + s - 1 + 2 (nsample - 1), npos - 1) (ncell[w]); home[w]: 0 rows and tables in LDS (at most
+ * scrappie_hip_squiggle_local_max_cells() cells: (16 + 10 ncell + 2) * 4 bytes within 64 KiB), 1 rows in device scratch at float
+ * offset scr_off[w] of *scr_floats in all (5 ncell per window, rounded up to a multiple of 4).  Arrays may be NULL; only the first
+ * cap windows are written.  Returns the number of windows; 0: nothing to cut.  The debug option "squig_local_stride" sets an
+ * engine's stride (a NULL engine: the process-default engine). */
+long long scrappie_hip_squiggle_local_plan(size_t npos, size_t nsample, long stride, size_t cap, size_t *first, size_t *ncell, size_t *own,
+                                           int *home, long long *scr_off, long long *scr_floats);
+size_t scrappie_hip_squiggle_local_stride(size_t npos, size_t nsample, long stride);
+size_t scrappie_hip_squiggle_local_max_cells(void);
+/* launches of each k_squig_local form in this process: index (viterbi ? 2 : 0) | (scratch ? 1 : 0) */
+void scrappie_hip_squiggle_local_form_counts(uint64_t forms[4]);
 /* Squiggle prediction, batched (sh_eng_sqnet.inc): seqs[i] holds n[i] bases coded 0..3; out[i] becomes a matrix as
  * squiggle_r94 returns it (free_scrappie_matrix), predicted with `model`, a squiggle model loaded on e under that name.
  * The accepted sequences are laid end to end: one upload, one k_sqnet launch over all their tiles, one download; the call

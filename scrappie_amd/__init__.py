@@ -101,6 +101,10 @@ class _SquigResult(C.Structure):
     _fields_ = [("score", C.c_float), ("n", C.c_size_t), ("path", C.POINTER(C.c_int32))]
 
 
+class _SquigLocalResult(C.Structure):
+    _fields_ = [("score", C.c_float), ("first", C.c_size_t), ("last", C.c_size_t), ("n", C.c_size_t), ("path", C.POINTER(C.c_int32))]
+
+
 class _SquigCandidates(C.Structure):
     _fields_ = [("cand", C.POINTER(_SquigTarget)), ("ncand", C.c_size_t)]
 
@@ -419,6 +423,24 @@ def lib():
                                                     C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.scrappie_hip_squiggle_pack_form_counts.restype = None
     L.scrappie_hip_squiggle_pack_form_counts.argtypes = [C.POINTER(C.c_uint64)]
+    L.squiggle_match_local_viterbi.restype = C.c_float
+    L.squiggle_match_local_viterbi.argtypes = [_RawTable, C.c_float, PM, C.c_float, C.c_float, C.c_float, C.c_float, i32p, C.POINTER(C.c_size_t),
+                                               C.POINTER(C.c_size_t)]
+    L.squiggle_match_local_forward.restype = C.c_float
+    L.squiggle_match_local_forward.argtypes = [_RawTable, C.c_float, PM, C.c_float, C.c_float, C.c_float, C.c_float]
+    L.scrappie_hip_squiggle_match_local_batch.argtypes = [C.c_void_p, C.POINTER(_RawTable), C.POINTER(_SquigTarget), C.c_size_t,
+                                                          C.POINTER(_SquigParams), C.c_int, C.c_int, C.POINTER(_SquigLocalResult)]
+    L.scrappie_hip_free_squiggle_local_results.restype = None
+    L.scrappie_hip_free_squiggle_local_results.argtypes = [C.POINTER(_SquigLocalResult), C.c_size_t]
+    L.scrappie_hip_squiggle_local_plan.restype = C.c_longlong
+    L.scrappie_hip_squiggle_local_plan.argtypes = [C.c_size_t, C.c_size_t, C.c_long, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                                   C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    L.scrappie_hip_squiggle_local_stride.restype = C.c_size_t
+    L.scrappie_hip_squiggle_local_stride.argtypes = [C.c_size_t, C.c_size_t, C.c_long]
+    L.scrappie_hip_squiggle_local_max_cells.restype = C.c_size_t
+    L.scrappie_hip_squiggle_local_max_cells.argtypes = []
+    L.scrappie_hip_squiggle_local_form_counts.restype = None
+    L.scrappie_hip_squiggle_local_form_counts.argtypes = [C.POINTER(C.c_uint64)]
     L.scrappie_hip_squiggle_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     L.scrappie_hip_squiggle_lds_max_pos.restype = C.c_size_t
     L.scrappie_hip_map_lds_max_seq.restype = C.c_size_t
@@ -712,6 +734,44 @@ def set_squiggle_pack_cells(value):
     """The debug option "squig_pack_cells" of the process-default engine, the one `squiggle_match_many` runs on: cells per
     pack of candidate squiggles, 0: every candidate through k_squig, -1: the default.  (An `Engine` has `debug_option`.)"""
     if lib().scrappie_hip_debug_option(None, b"squig_pack_cells", int(value)) != 0:
+        raise RuntimeError("debug_option: " + last_error())
+
+
+def squiggle_local_form_counts():
+    """Launches of each k_squig_local form in this process so far (scrappie_hip_squiggle_local_form_counts):
+    {(viterbi, scratch): n}."""
+    q = (C.c_uint64 * 4)()
+    lib().scrappie_hip_squiggle_local_form_counts(q)
+    return {(bool(k & 2), bool(k & 1)): int(q[k]) for k in range(4)}
+
+
+def squiggle_local_max_cells():
+    """The most cells a window of k_squig_local keeps in LDS (rows, END row and its slice of the tables); a larger window keeps
+    its rows in device scratch."""
+    return int(lib().scrappie_hip_squiggle_local_max_cells())
+
+
+def squiggle_local_plan(npos, nsample, stride=-1):
+    """The cut of a reference squiggle of `npos` positions into windows for a read of `nsample` samples (host arithmetic, no
+    device; scrappie_hip_squiggle_local_plan).  `stride`: entry positions per window, 0: one window, -1: the default.  Returns a
+    dict of arrays, one entry per window: first, ncell, own, home (0 LDS, 1 device scratch), scr_off (-1 in LDS), and
+    scr_floats."""
+    Lb = lib()
+    nw = int(Lb.scrappie_hip_squiggle_local_plan(npos, nsample, int(stride), 0, None, None, None, None, None, None))
+    first, ncell, own = (np.zeros(nw, dtype=np.uintp) for _ in range(3))
+    home = np.zeros(nw, dtype=np.int32)
+    off = np.zeros(nw, dtype=np.longlong)
+    tot = C.c_longlong(0)
+    sp = C.POINTER(C.c_size_t)
+    Lb.scrappie_hip_squiggle_local_plan(npos, nsample, int(stride), nw, first.ctypes.data_as(sp), ncell.ctypes.data_as(sp), own.ctypes.data_as(sp),
+                                        home.ctypes.data_as(C.POINTER(C.c_int)), off.ctypes.data_as(C.POINTER(C.c_longlong)), C.byref(tot))
+    return dict(first=first, ncell=ncell, own=own, home=home, scr_off=off, scr_floats=int(tot.value))
+
+
+def set_squiggle_local_stride(value):
+    """The debug option "squig_local_stride" of the process-default engine, the one `squiggle_match_reference` runs on: entry
+    positions per window, 0: one window, -1: the default.  (An `Engine` has `debug_option`.)"""
+    if lib().scrappie_hip_debug_option(None, b"squig_local_stride", int(value)) != 0:
         raise RuntimeError("debug_option: " + last_error())
 
 
@@ -1607,6 +1667,33 @@ def squiggle_match(rt, squiggle, rate=1.0, back_prob=0.0, local_pen=2.0, skip_pe
     return score, (path_data if path else None)
 
 
+def squiggle_match_reference(rt, squiggle, rate=1.0, back_prob=0.0, local_pen=2.0, skip_pen=5000.0, min_score=5.0, viterbi=True,
+                             path=False):
+    """Where inside a longer reference squiggle does this signal lie?  (squiggle_match_local_viterbi / _forward, k_squig_local; not
+    in the reference project.)  The `RawTable` rt as it is, mapped over [rt.start, rt.end), INTO `squiggle` (a ScrappyMatrix or an
+    (npos, 3) array): entering and leaving the squiggle is free at every position.  Returns (score, first, last, path): `last` is
+    the position the path ends in, or left the squiggle from, plus one (None without viterbi); `first`, the lowest position on
+    the path, and the path (rt's full length; positions in the squiggle's coordinates, -1 outside the window and in START / END)
+    need `path` and are None without it."""
+    _path_needs_viterbi(path, viterbi)
+    if not isinstance(rt, RawTable):
+        raise TypeError('`rt` should be a RawTable.')
+    sq = _squiggle_matrix(squiggle)
+    if viterbi:
+        path_data = np.zeros(rt._rt.n, dtype=np.int32) if path else None
+        first, last = C.c_size_t(0), C.c_size_t(0)
+        score = lib().squiggle_match_local_viterbi(rt.data(), rate, sq.data(), back_prob, local_pen, skip_pen, min_score,
+                                                   path_data.ctypes.data_as(C.POINTER(C.c_int32)) if path else None,
+                                                   C.byref(first) if path else None, C.byref(last))
+    else:
+        score = lib().squiggle_match_local_forward(rt.data(), rate, sq.data(), back_prob, local_pen, skip_pen, min_score)
+    if np.isnan(score):
+        raise RuntimeError('An unknown error occurred during alignment: ' + last_error())
+    if not viterbi:
+        return score, None, None, None
+    return score, (int(first.value) if path else None), int(last.value), path_data
+
+
 def map_signal_to_squiggle(data, squiggle, rate=1.0, back_prob=0.0, local_pen=2.0, skip_pen=5000.0, min_score=5.0, model=None,
                            band=None):
     """python/scrappy/__init__.py:462-489: `squiggle` is a base sequence, predicted with the registered squiggle model
@@ -2354,6 +2441,66 @@ class Engine(object):
             raise RuntimeError("squiggle_match_batch: " + last_error())
         res = _scores_and_paths(out, n, 'n')
         lib().scrappie_hip_free_squiggle_results(out, n)
+        return res
+
+    def match_squiggle_reference(self, signals, references, viterbi=True, path=False, rate=1.0, back_prob=0.0, local_pen=2.0,
+                                 skip_pen=5000.0, min_score=5.0):
+        """Where inside a longer reference squiggle does each signal lie?  Each signal (trimmed, normalised float32 array, or a
+        `RawTable` with its window) INTO its reference (an (npos, 3) array), batched (scrappie_hip_squiggle_match_local_batch; every
+        window of every read a workgroup of k_squig_local).  `references`: one array for all reads -- turned into tables once per
+        call and uploaded once per launch --, or a list with one per read (the same array object given twice counts once).
+        Returns [(score, first, last, path)] in input order as `squiggle_match_reference` gives them; score NaN where a read
+        cannot be mapped."""
+        n = len(signals)
+        _path_needs_viterbi(path, viterbi)
+        if isinstance(references, np.ndarray) and references.ndim == 2:
+            references = [references] * n
+        references = list(references)
+        if len(references) != n:
+            raise ValueError("one reference for all signals, or one per signal")
+        rts, keep = _raw_tables(signals)
+        tgs = (_SquigTarget * max(n, 1))()
+        made = {}
+        for i, sq in enumerate(references):
+            if id(sq) not in made:
+                a = np.ascontiguousarray(sq, dtype=ftype)
+                if a.ndim != 2 or a.shape[1] < 3:
+                    raise ValueError("a reference should be an (npos, 3) array")
+                made[id(sq)] = a
+            a = made[id(sq)]
+            tgs[i] = _SquigTarget(a.ctypes.data_as(C.POINTER(C.c_float)), a.shape[0], a.shape[1])
+        keep.append(made)
+        p = _SquigParams(rate, back_prob, local_pen, skip_pen, min_score)
+        out = (_SquigLocalResult * max(n, 1))()
+        if lib().scrappie_hip_squiggle_match_local_batch(self._h, rts, tgs, n, C.byref(p), 1 if viterbi else 0, 1 if path else 0, out) != 0:
+            raise RuntimeError("squiggle_match_local_batch: " + last_error())
+        rs = [out[i] for i in range(n)]
+        res = []
+        for r, pth in zip(rs, _paths(rs, 'n')):
+            ok = viterbi and not np.isnan(r.score)
+            res.append((float(r.score), int(r.first) if ok and pth is not None else None, int(r.last) if ok else None, pth))
+        lib().scrappie_hip_free_squiggle_local_results(out, n)
+        return res
+
+    def mappy_reference(self, signals, sequences, model='squiggle_r94', rate=1.0, back_prob=0.0, local_pen=2.0, skip_pen=5000.0,
+                        min_score=5.0):
+        """Each signal INTO the squiggle predicted for a longer base sequence: one batched prediction over the DISTINCT
+        sequences, then `match_squiggle_reference` with paths.  `sequences`: one string for all reads or one per read.  Returns
+        [(score, first, last, path)]; (nan, None, None, None) where a sequence or a read is refused."""
+        n = len(signals)
+        if isinstance(sequences, str):
+            sequences = [sequences] * n
+        sequences = list(sequences)
+        if len(sequences) != n:
+            raise ValueError("one sequence for all signals, or one per signal")
+        distinct = sorted(set(sequences))
+        sq = dict(zip(distinct, self.predict_squiggle(distinct, model=model, rescale=False))) if distinct else {}
+        keep = [i for i in range(n) if sq[sequences[i]] is not None]
+        got = self.match_squiggle_reference([signals[i] for i in keep], [sq[sequences[i]] for i in keep], viterbi=True, path=True, rate=rate,
+                                            back_prob=back_prob, local_pen=local_pen, skip_pen=skip_pen, min_score=min_score)
+        res = [(float("nan"), None, None, None)] * n
+        for i, r in zip(keep, got):
+            res[i] = r
         return res
 
     def match_squiggles(self, signals, candidates, viterbi=True, path=False, rate=1.0, back_prob=0.0, local_pen=2.0,

@@ -49,6 +49,7 @@
  *   sh_eng_map_local.inc      transducer reads mapped into a longer sequence, one workgroup per window, the posterior column staged in LDS (per-read and batched)
  *   sh_eng_squig.inc     mapping of raw signals to predicted squiggles (per-read and batched)
  *   sh_eng_squig_pack.inc  one signal against many candidate squiggles, packed into workgroups
+ *   sh_eng_squig_local.inc  raw signals mapped into a longer reference squiggle, one workgroup per window (per-read and batched)
  *   sh_eng_sqnet.inc     prediction of squiggles from base sequences (per-read and batched)
  *   sh_eng_events.inc    event detection (per-read and batched; kernels in sh_events.h)
  *   sh_eng_crfpost.inc   base probabilities of the flip-flop models (k_crf_post, sh_crf_post.h): inside a launch group and on host matrices
@@ -90,6 +91,7 @@
 #include "sh_squig.h"
 #include "sh_squig_band.h"
 #include "sh_squig_pack.h"
+#include "sh_squig_local.h"
 #include "sh_sqnet.h"
 #include "sh_events.h"
 
@@ -521,6 +523,8 @@ struct scrappie_hip_engine {
     DBuf d_sqp_rd, d_sqp_sig, d_sqp_w, d_sqp_score; HBuf h_sqp;      /* candidate squiggles in packs (sh_eng_squig_pack.inc): the packs, the reads' signals, the packs' tables and words, scores; signals and scores on the host */
     bool squig_pack_lone = false;    /* a candidate alone in its pack runs in k_squig_pack all the same (debug option "squig_pack_lone"; default: it takes k_squig) */
     int squig_pack_cells = -1;       /* cells a pack of candidate squiggles holds (debug option "squig_pack_cells"; 0: every candidate through k_squig, -1: the default) */
+    DpBufs dp_sql; DBuf d_sql_sig, d_sql_tab, d_sql_lohi; HBuf h_sql;      /* reference-local squiggle mapping (sh_eng_squig_local.inc): the windows' buffers (final state: the end position and kind, an int2); signals, tables, the second pass's (first, last); signals on the host */
+    int squig_local_stride = -1;     /* entry positions a window of k_squig_local owns (debug option "squig_local_stride"; 0: one window, -1: the default) */
     double squig_ms[3] = {0, 0, 0};  /* scrappie_hip_squiggle_match_batch: tables + uploads, k_squig, k_squig_walk + results, summed over the last call's launches */
     DBuf d_sqn[2]; HBuf h_sqn;       /* squiggle prediction (sh_eng_sqnet.inc): tiles | codes, outputs */
     double sqnet_ms[3] = {0, 0, 0};  /* scrappie_hip_squiggle_predict_batch: upload, k_sqnet, download + transform, summed over the last call's launches */
@@ -673,6 +677,7 @@ extern "C" scrappie_hip_params scrappie_hip_default_params(void) {
 #include "sh_eng_map_local.inc"      /* transducer reads mapped into a longer sequence, cut into windows (sh_map_local.h): map_to_reference_*, scrappie_hip_map_post_local_batch */
 #include "sh_eng_squig.inc"      /* squiggle matching (sh_squig.h): squiggle_match_* on the process-default engine, scrappie_hip_squiggle_match_batch */
 #include "sh_eng_squig_pack.inc"      /* one signal against many candidate squiggles (sh_squig_pack.h): scrappie_hip_squiggle_match_multi_batch, scrappie_hip_squiggle_match_multi */
+#include "sh_eng_squig_local.inc"      /* raw signals mapped into a longer reference squiggle, cut into windows (sh_squig_local.h): squiggle_match_local_*, scrappie_hip_squiggle_match_local_batch */
 #include "sh_eng_sqnet.inc"      /* squiggle prediction (sh_sqnet.h): squiggle_r94 and its relatives on the process-default engine, scrappie_hip_squiggle_predict_batch */
 #include "sh_eng_events.inc"      /* event detection (sh_events.h): detect_events on the process-default engine, scrappie_hip_detect_events_batch; `scrappie events` for a batch (scrappie_hip_basecall_events_batch) */
 #include "sh_eng_crfpost.inc"      /* base probabilities of the flip-flop models (sh_crf_post.h): scrappie_hip_basecall_batch_probs, scrappie_hip_posterior_crf_batch */

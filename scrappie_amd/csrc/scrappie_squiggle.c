@@ -128,13 +128,17 @@ static void mappy_usage(FILE *fh) {
           "      --device=N             GPU to run on (default 0)\n"
           "      --band=N               Map inside the diagonal band of half-width N positions (default: no band)\n"
           "      --all-records          Match the read against every record of the fasta: a table of their scores, then the best\n"
-          "                             record's mapping (not with --band)\n", fh);
+          "                             record's mapping (not with --band)\n"
+          "      --inside               The read lies somewhere INSIDE the (longer) sequence: entering and leaving it is free at every\n"
+          "                             position; the header gains `positions first..last` (the path lies in [first, last) of the\n"
+          "                             sequence) (not with --band or --all-records)\n", fh);
 }
 
 /* scrappie_mappy.c:215-228: the header line and one line per sample of the read */
 static void mappy_print(FILE *out, const char *fast5, const char *fasta, float score, const raw_table *rt, const int32_t *path, const_scrappie_matrix sq,
-                        const char *seq) {
-    fprintf(out, "# %s to %s  (score = %f)\n", fast5, fasta, score);
+                        const char *seq, const size_t *span) {
+    if (span) fprintf(out, "# %s to %s  (score = %f, positions %zu..%zu)\n", fast5, fasta, score, span[0], span[1]);      /* --inside */
+    else fprintf(out, "# %s to %s  (score = %f)\n", fast5, fasta, score);
     fprintf(out, "idx\tsignal\tpos\tbase\tcurrent\tsd\tdwell\n");
     for (size_t i = 0; i < rt->n; i++) {
         const int32_t pos = path[i];
@@ -187,7 +191,7 @@ static int mappy_all_records(scrappie_hip_engine *e, const char *model, const ch
         fprintf(stderr, "scrappie: %s\n", scrappie_hip_last_error());
         goto done;
     }
-    mappy_print(out, fast5, fasta, res.score[res.best], rt, res.path, sq[res.best], recs[res.best].seq);
+    mappy_print(out, fast5, fasta, res.score[res.best], rt, res.path, sq[res.best], recs[res.best].seq, NULL);
     rc = EXIT_SUCCESS;
 done:
     scrappie_hip_free_squiggle_multi_results(&res, 1);
@@ -198,9 +202,9 @@ done:
 }
 
 int main_mappy(int argc, char **argv) {
-    enum { O_MODEL = 256, O_LIC, O_MFILE, O_DEV, O_BAND, O_ALL };
+    enum { O_MODEL = 256, O_LIC, O_MFILE, O_DEV, O_BAND, O_ALL, O_INSIDE };
     static const struct option lo[] = {
-        {"all-records", 0, 0, O_ALL}, {"band", 1, 0, O_BAND}, {"model", 1, 0, O_MODEL}, {"backprob", 1, 0, 'b'}, {"skippen", 1, 0, 'k'}, {"localpen", 1, 0, 'l'}, {"minscore", 1, 0, 'm'},
+        {"all-records", 0, 0, O_ALL}, {"inside", 0, 0, O_INSIDE}, {"band", 1, 0, O_BAND}, {"model", 1, 0, O_MODEL}, {"backprob", 1, 0, 'b'}, {"skippen", 1, 0, 'k'}, {"localpen", 1, 0, 'l'}, {"minscore", 1, 0, 'm'},
         {"output", 1, 0, 'o'}, {"prefix", 1, 0, 'p'}, {"rate", 1, 0, 'r'}, {"segmentation", 1, 0, 's'}, {"trim", 1, 0, 't'},
         {"licence", 0, 0, O_LIC}, {"license", 0, 0, O_LIC}, {"model-file", 1, 0, O_MFILE}, {"device", 1, 0, O_DEV}, {"help", 0, 0, '?'},
         {0, 0, 0, 0}};
@@ -210,7 +214,7 @@ int main_mappy(int argc, char **argv) {
     FILE *out = stdout;
     int trim_start = 200, trim_end = 10, varseg_chunk = 100, device = 0, h, c;
     long band = -1;                      /* half-width of the diagonal band in positions; < 0: none */
-    int all_records = 0;
+    int all_records = 0, inside = 0;
     float varseg_thresh = 0.0f;
     double pct;
     optind = 1;
@@ -242,6 +246,7 @@ int main_mappy(int argc, char **argv) {
         case O_MFILE: model_file = optarg; break;
         case O_DEV: device = atoi(optarg); break;
         case O_ALL: all_records = 1; break;
+        case O_INSIDE: inside = 1; break;
         case O_BAND:
             band = atol(optarg);
             if (band < 0) { fprintf(stderr, "scrappie: --band wants a half-width in positions, 0 or more\n"); return EXIT_FAILURE; }
@@ -252,6 +257,7 @@ int main_mappy(int argc, char **argv) {
     if (argc - optind <= 0) { mappy_usage(stderr); return EXIT_FAILURE; }
     if (argc - optind < 2) { fprintf(stderr, "scrappie: fast5 file is a required argument\n"); return EXIT_FAILURE; }      /* scrappie_mappy.c:152 */
     if (all_records && band >= 0) { fprintf(stderr, "scrappie: --all-records maps without a band; it cannot be combined with --band\n"); return EXIT_FAILURE; }
+    if (inside && (all_records || band >= 0)) { fprintf(stderr, "scrappie: --inside maps without a band into one sequence; it cannot be combined with --band or --all-records\n"); return EXIT_FAILURE; }
     const char *fasta = argv[optind], *fast5 = argv[optind + 1];
     char *mpath = cli_model_path(model, model_file);      /* (the weights first, then the engine) */
     scrappie_hip_engine *e = mpath ? cli_open_model(device, model, mpath, &h) : NULL;
@@ -275,6 +281,7 @@ int main_mappy(int argc, char **argv) {
     int *codes = NULL;
     scrappie_matrix sq = NULL;
     scrappie_hip_squiggle_result res = {0};
+    scrappie_hip_squiggle_local_result lres = {0};
     int32_t *low = NULL;
     if (cli_read_fasta(fasta, &recs, &nrec, 1) || nrec == 0 || !recs[0].seq || recs[0].n == 0) {
         fprintf(stderr, "scrappie: Failed to open \"%s\" for input.\n\n", fasta);
@@ -292,6 +299,16 @@ int main_mappy(int argc, char **argv) {
         goto done;
     }
     scrappie_hip_squiggle_target tg = {sq->data.f, sq->nc, sq->stride};
+    if (inside) {                        /* the read somewhere inside the sequence (scrappie_hip_squiggle_match_local_batch) */
+        if (scrappie_hip_squiggle_match_local_batch(e, &rt, &tg, 1, &p, 1, 1, &lres) != 0 || !lres.path) {
+            fprintf(stderr, "scrappie: %s\n", scrappie_hip_last_error());
+            rc = EXIT_FAILURE;
+            goto done;
+        }
+        const size_t span[2] = {lres.first, lres.last};
+        mappy_print(out, fast5, fasta, lres.score, &rt, lres.path, sq, recs[0].seq, span);
+        goto done;
+    }
     scrappie_hip_squiggle_band bd = {NULL, 0};
     if (band >= 0 && rt.end > rt.start) {
         low = malloc((rt.end - rt.start) * sizeof *low);
@@ -304,9 +321,10 @@ int main_mappy(int argc, char **argv) {
         rc = EXIT_FAILURE;
         goto done;
     }
-    mappy_print(out, fast5, fasta, res.score, &rt, res.path, sq, recs[0].seq);
+    mappy_print(out, fast5, fasta, res.score, &rt, res.path, sq, recs[0].seq, NULL);
 done:
     scrappie_hip_free_squiggle_results(&res, 1);
+    scrappie_hip_free_squiggle_local_results(&lres, 1);
     free_scrappie_matrix(sq);
     free(codes);
     free(low);

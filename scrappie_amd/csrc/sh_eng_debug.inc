@@ -18,7 +18,7 @@ static scrappie_hip_engine *default_engine();      /* (sh_eng_surface.inc) */
 /* Test hooks.  Options: "ff_separate" (S1 and the decoder as two kernels on this engine, whatever the shape),
  * "dump_final" (the decoders leave every tile's final scores, start and end state in the hand-over buffer). */
 extern "C" int scrappie_hip_debug_option(scrappie_hip_engine *e, const char *name, int value) {
-    if (!e && name && (!strcmp(name, "map_pack_cells") || !strcmp(name, "map_crf_local_stride") || !strcmp(name, "map_local_stride") || !strcmp(name, "crf_find_cells") || !strcmp(name, "map_crf_pack_cells") || !strcmp(name, "squig_pack_cells") || !strcmp(name, "squig_pack_lone"))) e = default_engine();      /* the per-read surface's engine has no handle */
+    if (!e && name && (!strcmp(name, "map_pack_cells") || !strcmp(name, "map_crf_local_stride") || !strcmp(name, "map_local_stride") || !strcmp(name, "crf_find_cells") || !strcmp(name, "map_crf_pack_cells") || !strcmp(name, "squig_pack_cells") || !strcmp(name, "squig_pack_lone") || !strcmp(name, "squig_local_stride"))) e = default_engine();      /* the per-read surface's engine has no handle */
     if (!e || !name) return set_err("debug_option: null argument");
     if (e->any_pending()) return set_err("debug_option: launch groups are in flight");
     if (!strcmp(name, "ff_separate")) e->dbg_ff_separate = value != 0;
@@ -44,6 +44,7 @@ extern "C" int scrappie_hip_debug_option(scrappie_hip_engine *e, const char *nam
     else if (!strcmp(name, "map_local_stride")) e->map_local_stride = value < 0 ? -1 : value;      /* entry positions per window of k_map_local (0: one window; -1: the default) */
     else if (!strcmp(name, "crf_find_cells")) e->crf_find_cells = value < 0 ? -1 : value;      /* cells per pack of motifs of k_crf_find (-1: the default) */
     else if (!strcmp(name, "map_crf_pack_cells")) e->map_crf_pack_cells = value < 0 ? -1 : value;      /* cells per pack of candidates of k_map_crf_pack (0: every candidate through k_map_crf; -1: the default) */
+    else if (!strcmp(name, "squig_local_stride")) e->squig_local_stride = value < 0 ? -1 : value;      /* entry positions per window of k_squig_local (0: one window; -1: the default) */
     else if (!strcmp(name, "squig_pack_cells")) e->squig_pack_cells = value < 0 ? -1 : value;      /* cells per pack of candidate squiggles of k_squig_pack (0: every candidate through k_squig; -1: the default) */
     else if (!strcmp(name, "squig_pack_lone")) e->squig_pack_lone = value != 0;      /* 1: a candidate alone in its pack runs in k_squig_pack (0, the default: it takes k_squig) */
     else if (!strcmp(name, "events_budget_samples")) e->dbg_events_budget = value > 0 ? (size_t)value : 0;      /* sample slots per event-detection launch (0: from free memory) */

@@ -975,6 +975,68 @@ long long scrappie_hip_map_local_plan(size_t seqlen, size_t nblock, size_t nr, l
     return (long long)nwin;
 }
 
+/* Windows of the reference-local squiggle mapping (k_squig_local, sh_squig_local.h).  In the LDS home a window of ncell cells keeps
+ * a head of 16 words, two rows of a position and a back value per cell, the END row, and its slice of the tables: loc, scale, logsc
+ * and stay per cell and ncell + 2 move entries -- 10 words per cell and 18 beside them.  In the scratch home only the head. */
+size_t sh_squig_local_scr_lds_bytes(void) { return 16 * 4; }
+size_t sh_squig_local_lds_bytes(size_t ncell) { return (16 + 10 * ncell + 2) * 4; }
+/* the five rows of a window in device scratch, whole 16-byte pieces */
+size_t sh_squig_local_scr_floats(size_t ncell) { return (5 * ncell + 3) & ~(size_t)3; }
+
+/* the most cells a window keeps in LDS (the bytes are linear in ncell) */
+size_t scrappie_hip_squiggle_local_max_cells(void) {
+    const size_t per = sh_squig_local_lds_bytes(1) - sh_squig_local_lds_bytes(0);
+    return (SH_SQ_LDS - sh_squig_local_lds_bytes(0)) / per;
+}
+
+/* The stride in positions a reference of npos positions and a read of nsample samples are cut with.  A path that enters at a
+ * position advances at most 2 (nsample - 1) positions and reaches one cell to the left, so a window is stride + 2 (nsample - 1) + 1
+ * cells.  stride > 0: that many; 0: one window; < 0: the default -- the largest LDS-resident window while it owns at least half of
+ * its cells; SH_SQUIG_LOCAL_SCR_MUL nsample, with the rows in device scratch, beyond (profiles/squiggle_local_rate.txt decided).
+ * Never more than the npos positions there are. */
+size_t scrappie_hip_squiggle_local_stride(size_t npos, size_t nsample, long stride) {
+    const size_t maxc = scrappie_hip_squiggle_local_max_cells(), reach = nsample ? 2 * (nsample - 1) + 1 : 1;
+    size_t s;
+    if (stride > 0) s = (size_t)stride;
+    else if (stride == 0) s = npos;
+    else if (2 * reach <= maxc) s = maxc - reach;
+    else s = SH_SQUIG_LOCAL_SCR_MUL * nsample;
+    if (s == 0) s = 1;
+    return s < npos ? s : npos;
+}
+
+/* The cut: window w owns the entry positions [w s, min((w + 1) s, npos)) -- own[w] of them -- and holds the cells [max(w s - 1, 0),
+ * min(w s + s - 1 + 2 (nsample - 1), npos - 1)] -- first[w] and ncell[w]; home[w]: 0 rows and tables in LDS, 1 rows in device
+ * scratch, at float offset scr_off[w] (-1 in LDS) of *scr_floats floats in all, 5 ncell per window rounded up to whole 16-byte
+ * pieces.  Every array may be NULL; those given hold cap entries, and only the first cap windows are written.  Returns the number of
+ * windows, 0 on an empty reference, no samples or either beyond 2^30. */
+long long scrappie_hip_squiggle_local_plan(size_t npos, size_t nsample, long stride, size_t cap, size_t *first, size_t *ncell, size_t *own,
+                                           int *home, long long *scr_off, long long *scr_floats) {
+    if (scr_floats) *scr_floats = 0;
+    if (npos == 0 || nsample == 0 || npos > ((size_t)1 << 30) || nsample > ((size_t)1 << 30)) return 0;
+    const size_t s = scrappie_hip_squiggle_local_stride(npos, nsample, stride), reach = 2 * (nsample - 1);
+    const size_t nwin = (npos + s - 1) / s;
+    long long scr = 0;
+    for (size_t w = 0; w < nwin; w++) {
+        const size_t p0 = w * s;                                /* the first entry position it owns */
+        const size_t c0 = p0 ? p0 - 1 : 0;                      /* back state p0 - 1 lives in the cell to its left */
+        const size_t left = npos - p0;
+        const size_t end = s + reach < left ? p0 + s + reach : npos;      /* one past its last cell */
+        const size_t nc = end - c0;
+        const int scratch = sh_squig_local_lds_bytes(nc) > SH_SQ_LDS;
+        if (w < cap) {
+            if (first) first[w] = c0;
+            if (ncell) ncell[w] = nc;
+            if (own) own[w] = s < left ? s : left;
+            if (home) home[w] = scratch;
+            if (scr_off) scr_off[w] = scratch ? scr : -1;
+        }
+        if (scratch) scr += (long long)sh_squig_local_scr_floats(nc);
+    }
+    if (scr_floats) *scr_floats = scr;
+    return (long long)nwin;
+}
+
 /* Packs of motifs searched inside a flip-flop read (k_crf_find, sh_crf_find.h).  A pack of ncell cells keeps two columns of
  * transitions and, per cell and the spare slot behind them, two buffers of a value and a stay value (16 bytes) and a word (4);
  * with positions two buffers of two payloads more (16): 20 or 36 bytes per cell. */

@@ -45,6 +45,12 @@ void sh_squiggle_tables(const float *params, size_t npos, size_t ldp, float rate
  *   word B of a cell: the END piece it belongs to (index in the pack) | SH_SQP_HEAD where it is the piece's first cell
  * A piece is a candidate's cells inside one group of 64 consecutive cells (one wave of one chunk of 256). */
 #define SH_SQ_LDS 65536
+/* windows of the reference-local squiggle mapping (sh_host.c; k_squig_local, sh_squig_local.h): the dynamic LDS a window of ncell cells takes in the
+ * LDS home and in the scratch home, and the floats of its five rows in device scratch */
+size_t sh_squig_local_lds_bytes(size_t ncell);
+size_t sh_squig_local_scr_lds_bytes(void);
+size_t sh_squig_local_scr_floats(size_t ncell);
+#define SH_SQUIG_LOCAL_SCR_MUL 4     /* entry positions per sample a window in device scratch owns at the default stride: two thirds of its cells; the fastest windowed stride on both measured shapes (profiles/squiggle_local_rate.txt) */
 #define SH_SQP_CELL_WORDS 11
 #define SH_SQP_CAND_WORDS 12
 #define SH_SQP_PIECE_WORDS 4
