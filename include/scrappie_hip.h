@@ -714,6 +714,75 @@ size_t scrappie_hip_crf_find_max_cells(void);
 /* launches of each k_crf_find form in this process, all engines together: index (positions ? 2 : 0) | (tiled ? 1 : 0) */
 void scrappie_hip_crf_find_form_counts(uint64_t forms[4]);
 
+/* Every single-base edit of a sequence scored against a read of a flip-flop (CRF) model in one pass (sh_eng_crf_edits.inc;
+ * k_crf_edits_rows, k_crf_edits, sh_crf_edits.h): for seq[0..L) the 4 L substitutions (the L that change nothing among them), the L
+ * deletions and the 4 (L + 1) insertions, each the score map_crf_to_sequence_viterbi / _forward give for the edited sequence --
+ * from one forward sweep, one backward sweep and one combining pass instead of 9 L + 4 dynamic programmes.
+ *
+ * Definition (tests/test_crf_edits_cpu.py restates it in numpy).  trans[nblock][25], element to * 5 + from, states A C G T stay;
+ * NB = nblock, entries t = 0 .. NB, block t leads from entry t to entry t + 1; BIG = 1e30; mx(a, b): b if b > a else a (Viterbi),
+ * log(e^a + e^b) (forward), the arguments in the order written.
+ *   Forward rows, k_map_crf's cells kept for every entry: F_B[0][1] = F_S[0][0] = 0, everything else -BIG; with b = seq[p - 1]
+ *     F_B[t + 1][p] = mx(tr_t[5 b + seq[p - 2]] + F_B[t][p - 1], tr_t[5 b + 4] + F_S[t][p - 1])     (p == 1: the second term alone)
+ *     F_S[t + 1][p] = mx(tr_t[20 + b] + F_B[t][p], tr_t[24] + F_S[t][p])                           (p == 0: the second term alone)
+ *   base: F_B[NB][L] if it is >= F_S[NB][L], else F_S[NB][L] (Viterbi); their mx (forward): map_crf_to_sequence_*'s score, bit for bit.
+ *   Backward rows: G_B[NB][L] = G_S[NB][L] = 0, everything else, column L + 1 throughout, -BIG; for t descending
+ *     G_B[t][p] = mx(tr_t[5 seq[p] + seq[p - 1]] + G_B[t + 1][p + 1], tr_t[20 + seq[p - 1]] + G_S[t + 1][p])      (1 <= p)
+ *     G_S[t][p] = mx(tr_t[5 seq[p] + 4] + G_B[t + 1][p + 1], tr_t[24] + G_S[t + 1][p])              (p == L: the second terms alone)
+ *   An edit is the prefix seq[:i], perhaps a new base c, the suffix seq[j:]: a substitution at i < L (j = i + 1, sub[i][c]), a
+ *   deletion at i < L (j = i + 1, no new base, del[i]; NAN where L == 1), an insertion before i <= L (j = i, ins[i][c]).  pb = seq[i - 1]
+ *   (none: i == 0), n = seq[j] (none: j == L).  "Enter x after y from (PB, PS) at block t": mx(tr_t[5 x + y] + PB, tr_t[5 x + 4] + PS),
+ *   the second term alone where there is no y.
+ *     1. the source columns are (F_B[.][i], F_S[.][i]), F_B[.][0] = -BIG;
+ *     2. with a new base: X_B[0] = 0 if i == 0, else -BIG; X_S[0] = -BIG; X_B[t + 1] = enter c after pb from the source at t;
+ *        X_S[t + 1] = mx(tr_t[20 + c] + X_B[t], tr_t[24] + X_S[t]); X becomes the source and pb = c;
+ *     3. no n: the score is base's end rule on the source at NB;
+ *     4. else Y[0] = 0 iff nothing precedes n (a deletion at i == 0), else -BIG; Y[t] = enter n after pb from the source at t - 1;
+ *        the score is mx over t = 0 .. NB ascending of Y[t] + G_B[t][j + 1], accumulated left to right.
+ *   A score below -BIG / 2 is NAN: the edited sequence has more bases than the read has entries.  sub[i][seq[i]] is computed as any other.
+ * The join is exact: every path that spells the edited sequence is in the cell of n exactly once.  An edit's score and base are
+ * different chains of float32 additions: Viterbi scores of an edit and of map_crf_to_sequence_viterbi on the edited sequence agree to
+ * rounding, not in bits; a caller confirms the edits it chooses with scrappie_hip_map_crf_multi_batch, which is exact.
+ *
+ * scrappie_hip_map_crf_edits_batch: reads[i] (prepared as for scrappie_hip_map_batch) against targets[i] (base codes 0..3, unbanded).
+ * out[i]: base, sub (4 seqlen floats, [i][c]), del (seqlen), ins (4 (seqlen + 1), [i][c]), malloc'd, freed by
+ * scrappie_hip_free_edits_results; seqlen and nblock.  It runs as scrappie_hip_map_batch does for a CRF model: the network and k_crf
+ * once per launch group, then k_crf_edits_rows forward, k_crf_edits_rows backward and k_crf_edits on the main stream while the
+ * transitions are resident.  A read adds its three row matrices (scrappie_hip_crf_edits_row_bytes) and its results to the cut
+ * into launch groups; the debug option "crf_edits_budget_kb" bounds the row and result bytes of one launch of the three kernels
+ * (0: one launch per launch group).  A target that cannot be scored -- no or an empty sequence, a code that is not a base, poslow /
+ * poshigh set ("bands are not part of this call"), more than scrappie_hip_map_crf_lds_max_seq() bases ("too long for k_crf_edits":
+ * polishing works on windows) -- gets base and every edit NAN and the first such reason is the error text; its neighbours are
+ * scored.  A NAN edit is a result, not an error.  A transducer model: -1 with a text that names it.  viterbi 0: forward scores.
+ * scrappie_hip_map_timing covers the call ([0] network + k_crf; [1] the three launches with their copies: uploads of records and codes,
+ * the kernels, results to the host and the NAN pass over them, by the host's clock; [2] stays 0); scrappie_hip_crf_edits_timing has the
+ * kernels alone.
+ *
+ * map_crf_edits: the same on a host matrix (as nanonet_rnnrf_r94_transitions returns it) and the process-default engine, a batch
+ * of one; base, sub, del, ins may each be NULL; all are NAN, the return value 0 and the reason the error text where the sequence cannot
+ * be scored.  -1 with the reason: a null argument, not a transition matrix, a failed launch. */
+typedef struct { float base; float *sub, *del, *ins; size_t seqlen, nblock; } scrappie_hip_edits_result;
+int scrappie_hip_map_crf_edits_batch(scrappie_hip_engine *e, int model, const raw_table *reads, const scrappie_hip_map_target *targets, size_t n,
+                                     const scrappie_hip_params *p, int viterbi, scrappie_hip_edits_result *out);
+void scrappie_hip_free_edits_results(scrappie_hip_edits_result *r, size_t n);
+int map_crf_edits(const_scrappie_matrix trans, const int *seq, size_t seqlen, int viterbi, float *base, float *sub, float *del, float *ins);
+/* Host only (sh_host.c): what a launch of the three kernels keeps on the device.  pitch: floats from one entry's row to the next
+ * (seqlen + 2 rounded up to 16); row_bytes: the three row matrices of nblock + 1 entries; plan: reads in input order, rows[i] the
+ * float offset of read i's F_B in the row buffer (F_S (nblock[i] + 1) * pitch[i] floats behind it, G_B as many behind F_S), res[i]
+ * that of its results (sub [L][4], ins [L + 1][4], del [L]) in the result buffer, both multiples of 4; returns the floats of the row
+ * buffer, *res_floats (may be NULL) those of the result buffer. */
+size_t scrappie_hip_crf_edits_pitch(size_t seqlen);
+size_t scrappie_hip_crf_edits_row_bytes(size_t seqlen, size_t nblock);
+long long scrappie_hip_crf_edits_plan(const size_t *seqlen, const size_t *nblock, size_t n, int *pitch, long long *rows, long long *res,
+                                      long long *res_floats);
+/* launches of each form in this process, all engines together: k_crf_edits_rows at (viterbi ? 4 : 0) | (tiled ? 2 : 0) | (backward ? 1 : 0),
+ * k_crf_edits at 8 + ((viterbi ? 2 : 0) | (tiled ? 1 : 0)) */
+void scrappie_hip_crf_edits_form_counts(uint64_t forms[12]);
+/* the last scrappie_hip_map_crf_edits_batch call on this engine: ms[0..2] the device time of k_crf_edits_rows forward, backward and
+ * k_crf_edits (events on the main stream), summed over its launches; *launches (may be NULL): how many launches of the three it made;
+ * *row_bytes (may be NULL): the row bytes of all of them */
+void scrappie_hip_crf_edits_timing(scrappie_hip_engine *e, double ms[3], size_t *launches, size_t *row_bytes);
+
 /* Squiggle matching, batched (sh_eng_squig.inc): reads[i] (trimmed, normalised; mapped over [start, end)) against
  * targets[i], a predicted squiggle of npos columns of stride >= 3 floats (mean, log sd, dwell logit); out[i] belongs to
  * reads[i].  No network runs and no model is needed (the squiggles are an input here: scrappie_hip_squiggle_predict_batch

@@ -75,6 +75,11 @@ class _FindResult(C.Structure):
                 ("nmotif", C.c_size_t), ("call_score", C.c_float), ("best", C.c_int), ("nblock", C.c_size_t)]
 
 
+class _EditsResult(C.Structure):
+    _fields_ = [("base", C.c_float), ("sub", C.POINTER(C.c_float)), ("dele", C.POINTER(C.c_float)), ("ins", C.POINTER(C.c_float)),
+                ("seqlen", C.c_size_t), ("nblock", C.c_size_t)]
+
+
 class _MapCandidates(C.Structure):
     _fields_ = [("cand", C.POINTER(_MapTarget)), ("ncand", C.c_size_t)]
 
@@ -385,6 +390,21 @@ def lib():
     L.scrappie_hip_map_crf_pack_max_cells.argtypes = []
     L.scrappie_hip_map_crf_pack_form_counts.restype = None
     L.scrappie_hip_map_crf_pack_form_counts.argtypes = [C.POINTER(C.c_uint64)]
+    L.scrappie_hip_map_crf_edits_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(_RawTable), C.POINTER(_MapTarget), C.c_size_t,
+                                                   C.POINTER(Params), C.c_int, C.POINTER(_EditsResult)]
+    L.scrappie_hip_free_edits_results.restype = None
+    L.scrappie_hip_free_edits_results.argtypes = [C.POINTER(_EditsResult), C.c_size_t]
+    L.map_crf_edits.argtypes = [PM, ip, C.c_size_t, C.c_int, fp, fp, fp, fp]
+    L.scrappie_hip_crf_edits_pitch.restype = C.c_size_t
+    L.scrappie_hip_crf_edits_pitch.argtypes = [C.c_size_t]
+    L.scrappie_hip_crf_edits_row_bytes.restype = C.c_size_t
+    L.scrappie_hip_crf_edits_row_bytes.argtypes = [C.c_size_t, C.c_size_t]
+    L.scrappie_hip_crf_edits_plan.restype = C.c_longlong
+    L.scrappie_hip_crf_edits_plan.argtypes = [sp, sp, C.c_size_t, ip, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    L.scrappie_hip_crf_edits_form_counts.restype = None
+    L.scrappie_hip_crf_edits_form_counts.argtypes = [C.POINTER(C.c_uint64)]
+    L.scrappie_hip_crf_edits_timing.restype = None
+    L.scrappie_hip_crf_edits_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), sp, sp]
     L.squiggle_match_viterbi.restype = C.c_float
     L.squiggle_match_viterbi.argtypes = [_RawTable, C.c_float, PM, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_int32)]
     L.squiggle_match_forward.restype = C.c_float
@@ -1469,6 +1489,84 @@ def map_trans_to_sequences(trans, sequences, viterbi=False):
     return score
 
 
+def apply_edit(seq, kind, i, c=None):
+    """The sequence a single-base edit makes of `seq` (a base string, or an array of base codes 0..3): kind 'sub' puts `c` at
+    position i < L, 'del' removes position i < L, 'ins' puts `c` before position i <= L.  `c`: a base code 0..3 or one of
+    'ACGT'.  Returns what it was given, a string or an int32 array: how `map_trans_edits` and `Engine.score_edits` number their
+    results -- sub[i][c], dele[i], ins[i][c] score apply_edit(seq, 'sub' / 'del' / 'ins', i, c)."""
+    text = isinstance(seq, str)
+    codes = list(seq) if text else [int(b) for b in seq]
+    L = len(codes)
+    if kind not in ('sub', 'del', 'ins'):
+        raise ValueError("`kind` is one of 'sub', 'del', 'ins'")
+    if not 0 <= i < L + (1 if kind == 'ins' else 0):
+        raise ValueError("position %d is outside a sequence of %d bases for '%s'" % (i, L, kind))
+    if kind != 'del':
+        if isinstance(c, str):
+            if len(c) != 1 or c not in 'ACGT':
+                raise ValueError("`c` is one of 'ACGT' or a code 0..3")
+            c = c if text else 'ACGT'.index(c)
+        elif c is None or not 0 <= int(c) <= 3:
+            raise ValueError("`c` is one of 'ACGT' or a code 0..3")
+        else:
+            c = 'ACGT'[int(c)] if text else int(c)
+    out = codes[:i] + ([] if kind == 'del' else [c]) + codes[i + (0 if kind == 'ins' else 1):]
+    return ''.join(out) if text else np.array(out, dtype=np.int32)
+
+
+def crf_edits_form_counts():
+    """Launches of each form of the edit kernels in this process so far (scrappie_hip_crf_edits_form_counts):
+    {('rows', viterbi, tiled, backward): n, ('edits', viterbi, tiled): n}."""
+    q = (C.c_uint64 * 12)()
+    lib().scrappie_hip_crf_edits_form_counts(q)
+    out = {('rows', bool(k & 4), bool(k & 2), bool(k & 1)): int(q[k]) for k in range(8)}
+    out.update({('edits', bool(k & 2), bool(k & 1)): int(q[8 + k]) for k in range(4)})
+    return out
+
+
+def crf_edits_plan(seqlens, nblocks):
+    """The layout of one launch of the edit kernels over reads of `seqlens` bases and `nblocks` blocks (host arithmetic, no
+    device; scrappie_hip_crf_edits_plan): (pitch, rows, res, row_floats, res_floats) -- per read the floats from one entry's
+    row to the next, the float offset of its three row matrices (F_B, F_S, G_B, each (nblock + 1) * pitch floats) and of its
+    9 L + 4 results; the floats of the two buffers."""
+    a = np.ascontiguousarray(seqlens, dtype=np.uintp)
+    b = np.ascontiguousarray(nblocks, dtype=np.uintp)
+    if len(a) != len(b):
+        raise ValueError("one block count per sequence length")
+    pitch = np.zeros(len(a), dtype=np.int32)
+    rows, res = np.zeros(len(a), dtype=np.longlong), np.zeros(len(a), dtype=np.longlong)
+    nres = C.c_longlong(0)
+    sp, lp = C.POINTER(C.c_size_t), C.POINTER(C.c_longlong)
+    nrow = lib().scrappie_hip_crf_edits_plan(a.ctypes.data_as(sp), b.ctypes.data_as(sp), len(a), pitch.ctypes.data_as(C.POINTER(C.c_int)),
+                                             rows.ctypes.data_as(lp), res.ctypes.data_as(lp), C.byref(nres))
+    return pitch, rows, res, int(nrow), int(nres.value)
+
+
+def map_trans_edits(trans, seq, viterbi=True):
+    """Every single-base edit of `seq` (a base string, or an array of base codes 0..3) scored against a read's transitions
+    under a flip-flop (CRF) model (a `ScrappyMatrix` of 25 rows, as `calc_post(rt, model='rnnrf_r94')` gives) in one pass on
+    the GPU (map_crf_edits: a forward sweep, a backward sweep, one combining pass).  Returns (base, sub, dele, ins): base is
+    `map_trans_to_sequence`'s score of `seq` itself, bit for bit; sub (L, 4), dele (L,) and ins (L + 1, 4) are float32 arrays,
+    sub[i][c], dele[i] and ins[i][c] what `map_trans_to_sequence` gives for `apply_edit(seq, 'sub' / 'del' / 'ins', i, c)` up to
+    float32 rounding (an edit's score and base are different chains of additions: confirm chosen edits with
+    `map_trans_to_sequences`, which is exact).  NaN: the edited sequence has more bases than the read has entries, or is empty;
+    everything is NaN, and `last_error()` says why, where `seq` cannot be scored (empty, not bases, too long for k_crf_edits)."""
+    if not isinstance(trans, ScrappyMatrix):
+        raise TypeError('`trans` should be a ScrappyMatrix.')
+    nblock, nstate = trans.shape
+    if nstate != 25:
+        raise ValueError('`trans` should hold the 25 transitions of a flip-flop (CRF) model per block.')
+    tgs, keep = _crf_targets([seq])
+    L = len(keep[0])
+    base = C.c_float(float('nan'))
+    sub, dele, ins = (np.full(k, np.nan, dtype=np.float32) for k in (4 * L, max(L, 1), 4 * (L + 1)))
+    fp = C.POINTER(C.c_float)
+    if lib().map_crf_edits(trans.data(), tgs[0].seq, L, 1 if viterbi else 0, C.byref(base), sub.ctypes.data_as(fp), dele.ctypes.data_as(fp),
+                           ins.ctypes.data_as(fp)) != 0:
+        raise RuntimeError('An unknown error occurred while scoring edits: ' + last_error())
+    return np.float32(base.value), sub.reshape(L, 4), dele[:L], ins.reshape(L + 1, 4)
+
+
 def map_trans_to_reference(trans, sequence, viterbi=False, path=False):
     """Where in `sequence` does this read lie?  A read's transitions under a flip-flop (CRF) model (a `ScrappyMatrix` of 25
     rows, as `calc_post(rt, model='rnnrf_r94')` gives) mapped INTO a longer base sequence: the paths of `map_trans_to_sequence`
@@ -2392,6 +2490,49 @@ class Engine(object):
                         take(r.begin, np.int32) if positions else None, take(r.end, np.int32) if positions else None))
         lib().scrappie_hip_free_find_results(out, n)
         return res
+
+    def score_edits(self, signals, sequences, model='rnnrf_r94', viterbi=False, min_prob=1e-5, tempW=1.0, tempb=1.0):
+        """Is any single-base edit of this sequence better than the sequence?  Each read (trimmed, normalised float32 signal)
+        of a flip-flop (CRF) model against EVERY single-base edit of its sequence, batched (scrappie_hip_map_crf_edits_batch):
+        the network and k_crf run once per read; a forward sweep, a backward sweep and one combining pass score all 9 L + 4
+        edits.  `sequences`: one base string (or array of base codes) for all reads -- a window of a draft that the reads
+        cover --, or one per read.  Returns [(base, sub, dele, ins)] in input order as `map_trans_edits` gives them; with
+        `viterbi=False` the scores are log-likelihoods, so `sum(r[1] - r[0] for r in res)` over the reads of a window is the
+        log-likelihood ratio of every substitution.  A read or a sequence that cannot be scored has everything NaN
+        (`last_error()` names the first)."""
+        n = len(signals)
+        if isinstance(sequences, str) or (len(sequences) and np.ndim(sequences[0]) == 0 and not isinstance(sequences[0], str)):
+            sequences = [sequences] * n
+        sequences = list(sequences)
+        if len(sequences) != n:
+            raise ValueError("one sequence for all signals, or one sequence per signal")
+        h = self._models[model]
+        rts, keep = _raw_tables(signals)
+        made = {}
+        tgs = (_MapTarget * max(n, 1))()
+        for i, sq in enumerate(sequences):                     # a shared sequence is encoded once
+            if id(sq) not in made:
+                made[id(sq)] = _crf_targets([sq])
+            tgs[i].seq, tgs[i].seqlen = made[id(sq)][0][0].seq, made[id(sq)][0][0].seqlen
+        p = self.default_params(min_prob=min_prob, tempW=tempW, tempb=tempb)
+        out = (_EditsResult * max(n, 1))()
+        if lib().scrappie_hip_map_crf_edits_batch(self._h, h, rts, tgs, n, C.byref(p), 1 if viterbi else 0, out) != 0:
+            raise RuntimeError("map_crf_edits_batch: " + last_error())
+        res = []
+        take = lambda q, k: np.ctypeslib.as_array(q, shape=(k,)).copy() if k else np.zeros(0, dtype=np.float32)
+        for r in (out[i] for i in range(n)):
+            L = int(r.seqlen)
+            res.append((np.float32(r.base), take(r.sub, 4 * L).reshape(L, 4), take(r.dele, L), take(r.ins, 4 * (L + 1)).reshape(L + 1, 4)))
+        lib().scrappie_hip_free_edits_results(out, n)
+        return res
+
+    def crf_edits_timing(self):
+        """the last score_edits call: device ms of the forward rows, the backward rows and the combining pass, summed over its
+        launches; how many launches of the three it made and their row bytes"""
+        t = (C.c_double * 3)()
+        nl, nb = C.c_size_t(0), C.c_size_t(0)
+        lib().scrappie_hip_crf_edits_timing(self._h, t, C.byref(nl), C.byref(nb))
+        return dict(rows_forward_ms=t[0], rows_backward_ms=t[1], edits_ms=t[2], launches=int(nl.value), row_bytes=int(nb.value))
 
     def _timing(self, fn, names):
         t = (C.c_double * 3)()

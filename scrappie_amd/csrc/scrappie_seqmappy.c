@@ -22,6 +22,9 @@
  * --find (flip-flop models): every record of a pair's FASTA is a motif -- a barcode, an adapter, a primer -- searched INSIDE the
  * pair's read.  All pairs in ONE scrappie_hip_find_batch call (k_crf_find: the motifs packed into workgroups); per pair a header
  * line and a table record / name / score / delta / begin / end.  Without the option nothing changes.
+ * --edits (flip-flop models): EVERY single-base edit of the first record of a pair's FASTA scored against the pair's read.  All pairs
+ * in ONE scrappie_hip_map_crf_edits_batch call (k_crf_edits_rows, k_crf_edits); per pair a header line and one line per position:
+ * the base, then del, subA..T and insA..T as differences to the sequence's own Viterbi score.  Without the option nothing changes.
  */
 #define _GNU_SOURCE
 #include <getopt.h>
@@ -83,7 +86,16 @@ static void seqmappy_usage(FILE *fh) {
           "                             edit of the call).  The same line `# fast5 to fasta -- N records` and table record /\n"
           "                             name / score / per_block, then the header line and the path of the best record as plain\n"
           "                             seqmappy prints them for this model (blocks + 1 records), named fasta:name.  Not with a\n"
-          "                             transducer model (--all-records), --all-records, --inside, --find or --within.\n", fh);
+          "                             transducer model (--all-records), --all-records, --inside, --find or --within.\n"
+          "      --edits                Score EVERY single-base edit of the first record of the fasta against the read (Viterbi):\n"
+          "                             a line `# fast5 to fasta -- edits of L bases, score S over B blocks` (S not negated), a\n"
+          "                             line of column names, then per position i one line pos / base / del / subA subC subG subT /\n"
+          "                             insA insC insG insT: the score of the sequence without base i, with base i replaced, and\n"
+          "                             with a base inserted BEFORE base i, each as the difference to S (> 0: the edit maps better\n"
+          "                             than the sequence; nan: the edited sequence has more bases than the read has entries).\n"
+          "                             A last line `L - - - - - - insA..T`: the insertions behind the last base.  An edit's score\n"
+          "                             and S are different sums: differences of a few 1e-5 |S| are rounding; confirm an edit with\n"
+          "                             --each-record.  Flip-flop (CRF) models only; not with any of the options above.\n", fh);
 }
 
 /* --all-records: pair i's read against every record of its FASTA, all pairs in one scrappie_hip_map_multi_batch call; --each-record (crf):
@@ -191,6 +203,70 @@ static int seqmappy_find(scrappie_hip_engine *e, int h, const scrappie_hip_param
     return rc;
 }
 
+/* an edit's score as its difference to the sequence's own, "nan" where the edit has no admissible path */
+static void print_delta(FILE *out, float score, float base) {
+    if (isnan(score)) fputs("\tnan", out);
+    else fprintf(out, "\t%f", score - base);
+}
+
+/* --edits: every single-base edit of the first record of pair i's FASTA against pair i's read, all pairs in one scrappie_hip_map_crf_edits_batch call */
+static int seqmappy_edits(scrappie_hip_engine *e, int h, const scrappie_hip_params *p, char **fasta, size_t npair, FILE *out,
+                          int trim_start, int trim_end, int varseg_chunk, float varseg_thresh) {
+    /* entry m of the batch is pair who[m]: a pair whose fasta or fast5 did not load is reported here and never reaches the engine */
+    raw_table *rts = calloc(npair, sizeof *rts);
+    scrappie_hip_map_target *tg = calloc(npair, sizeof *tg);
+    scrappie_hip_edits_result *res = calloc(npair, sizeof *res);
+    int **codes = calloc(npair, sizeof *codes);
+    size_t *who = calloc(npair, sizeof *who), nb = 0;
+    int rc = EXIT_SUCCESS;
+    for (size_t j = 0; j < npair; j++) {
+        const char *fa = fasta[2 * j], *f5 = fasta[2 * j + 1];
+        struct cli_fasta *rec = NULL;       /* the first record of the file */
+        size_t nrec = 0;
+        if (cli_read_fasta(fa, &rec, &nrec, 1) || nrec == 0 || !rec[0].seq || rec[0].n == 0) { fprintf(stderr, "scrappie: Failed to open \"%s\" for input.\n", fa); cli_free_fasta(rec, nrec); rc = EXIT_FAILURE; continue; }
+        const size_t n = rec[0].n;
+        int *cd = encode_bases_to_integers(rec[0].seq, n, 1);
+        cli_free_fasta(rec, nrec);
+        if (!cd) { fprintf(stderr, "scrappie: cannot encode the sequence of \"%s\": %s\n", fa, scrappie_hip_last_error()); rc = EXIT_FAILURE; continue; }
+        const raw_table rt = cli_load_read(f5, trim_start, trim_end, varseg_chunk, varseg_thresh, 1);
+        if (!rt.raw) { fprintf(stderr, "scrappie: Failed to open \"%s\" for input and trim signal.\n", f5); free(cd); rc = EXIT_FAILURE; continue; }
+        codes[nb] = cd; tg[nb].seq = cd; tg[nb].seqlen = n; rts[nb] = rt; who[nb] = j;
+        nb++;
+    }
+    if (nb && scrappie_hip_map_crf_edits_batch(e, h, rts, tg, nb, p, 1, res) != 0) {
+        fprintf(stderr, "scrappie: %s\n", scrappie_hip_last_error());
+        rc = EXIT_FAILURE;
+    } else {
+        const size_t maxL = scrappie_hip_map_crf_lds_max_seq();
+        for (size_t i = 0; i < nb; i++) {
+            const char *fa = fasta[2 * who[i]], *f5 = fasta[2 * who[i] + 1];
+            if (isnan(res[i].base)) {        /* the engine's error text names the call's FIRST refusal only: this pair's own reason is worked out here */
+                if (tg[i].seqlen > maxL) fprintf(stderr, "scrappie: Failed to score the edits of \"%s\" for \"%s\": %zu bases are too long for --edits (at most %zu: pass a window of the sequence)\n", fa, f5, tg[i].seqlen, maxL);
+                else fprintf(stderr, "scrappie: Failed to score the edits of \"%s\" for \"%s\": the read cannot be run (too short for the model, or its signal is out of range)\n", fa, f5);
+                rc = EXIT_FAILURE;
+                continue;
+            }
+            const size_t L = res[i].seqlen;
+            const float base = res[i].base;
+            fprintf(out, "# %s to %s -- edits of %zu bases, score %f over %zu blocks\n", f5, fa, L, base, res[i].nblock);
+            fprintf(out, "pos\tbase\tdel\tsubA\tsubC\tsubG\tsubT\tinsA\tinsC\tinsG\tinsT\n");
+            for (size_t k = 0; k <= L; k++) {
+                if (k < L) {
+                    fprintf(out, "%zu\t%c", k, "ACGT"[codes[i][k]]);
+                    print_delta(out, res[i].del[k], base);
+                    for (int c = 0; c < 4; c++) print_delta(out, res[i].sub[4 * k + c], base);
+                } else fprintf(out, "%zu\t-\t-\t-\t-\t-\t-", k);
+                for (int c = 0; c < 4; c++) print_delta(out, res[i].ins[4 * k + c], base);
+                fputc('\n', out);
+            }
+        }
+    }
+    scrappie_hip_free_edits_results(res, nb);
+    for (size_t i = 0; i < nb; i++) { free(codes[i]); free(rts[i].raw); free(rts[i].uuid); }
+    free(who); free(codes); free(res); free(tg); free(rts);
+    return rc;
+}
+
 /* --inside: pair i's read into the first record of its FASTA, all pairs in one scrappie_hip_map_local_batch call; --within (klen: the
  * transducer model's k-mer length, 0 for --inside): the same through scrappie_hip_map_post_local_batch */
 static int seqmappy_inside(scrappie_hip_engine *e, int h, int klen, const scrappie_hip_params *p, char **fasta, size_t npair, FILE *out,
@@ -235,13 +311,13 @@ static int seqmappy_inside(scrappie_hip_engine *e, int h, int klen, const scrapp
 }
 
 int main_seqmappy(int argc, char **argv) {
-    enum { O_SEG = 256, O_T1, O_T2, O_LIC, O_MODEL, O_MFILE, O_DEV, O_ALL, O_INSIDE, O_FIND, O_WITHIN, O_EACH };
+    enum { O_SEG = 256, O_T1, O_T2, O_LIC, O_MODEL, O_MFILE, O_DEV, O_ALL, O_INSIDE, O_FIND, O_WITHIN, O_EACH, O_EDITS };
     static const struct option lo[] = {
         {"localpen", 1, 0, 'l'}, {"min_prob", 1, 0, 'm'}, {"output", 1, 0, 'o'}, {"prefix", 1, 0, 'p'},
         {"segmentation", 1, 0, O_SEG}, {"skip", 1, 0, 's'}, {"stay", 1, 0, 'y'}, {"trim", 1, 0, 't'},
         {"temperature1", 1, 0, O_T1}, {"temperature2", 1, 0, O_T2}, {"licence", 0, 0, O_LIC}, {"license", 0, 0, O_LIC},
-        {"model", 1, 0, O_MODEL}, {"model-file", 1, 0, O_MFILE}, {"device", 1, 0, O_DEV}, {"all-records", 0, 0, O_ALL}, {"inside", 0, 0, O_INSIDE}, {"find", 0, 0, O_FIND}, {"within", 0, 0, O_WITHIN}, {"each-record", 0, 0, O_EACH},{"help", 0, 0, '?'}, {0, 0, 0, 0}};
-    int all_records = 0, inside = 0, find = 0, within = 0, each_record = 0;
+        {"model", 1, 0, O_MODEL}, {"model-file", 1, 0, O_MFILE}, {"device", 1, 0, O_DEV}, {"all-records", 0, 0, O_ALL}, {"inside", 0, 0, O_INSIDE}, {"find", 0, 0, O_FIND}, {"within", 0, 0, O_WITHIN}, {"each-record", 0, 0, O_EACH}, {"edits", 0, 0, O_EDITS}, {"help", 0, 0, '?'}, {0, 0, 0, 0}};
+    int all_records = 0, inside = 0, find = 0, within = 0, each_record = 0, edits = 0;
     /* defaults: scrappie_seqmappy.c:62-78 */
     scrappie_hip_params p = scrappie_hip_default_params();
     p.local_pen = 4.0f; p.min_prob = 1e-5f; p.stay_pen = 0.0f; p.skip_pen = 0.0f; p.tempW = 1.0f; p.tempb = 1.0f;
@@ -278,6 +354,7 @@ int main_seqmappy(int argc, char **argv) {
         case O_FIND: find = 1; break;
         case O_WITHIN: within = 1; break;
         case O_EACH: each_record = 1; break;
+        case O_EDITS: edits = 1; break;
         default: seqmappy_usage(stderr); return EXIT_FAILURE;
         }
     }
@@ -285,6 +362,15 @@ int main_seqmappy(int argc, char **argv) {
     if (nargs <= 0) { seqmappy_usage(stderr); return EXIT_FAILURE; }
     if (nargs % 2) { fprintf(stderr, "scrappie: fast5 file is a required argument\n"); return EXIT_FAILURE; }    /* scrappie_seqmappy.c:153 */
     const size_t npair = (size_t)nargs / 2;
+    if (edits && (all_records || inside || find || within || each_record)) {
+        fprintf(stderr, "scrappie: --edits scores every single-base edit of the first record of a fasta; it cannot be combined with %s\n",
+                all_records ? "--all-records" : inside ? "--inside" : find ? "--find" : within ? "--within" : "--each-record");
+        return EXIT_FAILURE;
+    }
+    if (edits && get_raw_model(model) != SCRAPPIE_MODEL_RNNRF_R9_4) {
+        fprintf(stderr, "scrappie: --edits scores reads of flip-flop (CRF) models only (--model=rnnrf_r94); \"%s\" is a transducer model\n", model);
+        return EXIT_FAILURE;
+    }
     if (each_record && (all_records || inside || find || within)) {
         fprintf(stderr, "scrappie: --each-record maps a read of a flip-flop (CRF) model to every record of its fasta; it cannot be combined with %s\n",
                 all_records ? "--all-records" : inside ? "--inside" : find ? "--find" : "--within");
@@ -327,6 +413,14 @@ int main_seqmappy(int argc, char **argv) {
     const int crf = nstate == 25;        /* a flip-flop model (rnnrf_r94): bases as states of length 1, a path of nblock + 1 entries */
     if (crf) klen = 1;
     else for (int nk = nstate - 1; nk > 1 && nk % 4 == 0; nk /= 4) klen++;
+    if (edits) {
+        int rc = EXIT_FAILURE;
+        if (!crf) fprintf(stderr, "scrappie: --edits scores reads of flip-flop (CRF) models only; \"%s\" is a transducer model\n", model);
+        else rc = seqmappy_edits(e, h, &p, fasta, npair, out, trim_start, trim_end, varseg_chunk, varseg_thresh);
+        if (out != stdout) fclose(out);
+        scrappie_hip_engine_destroy(e);
+        return rc;
+    }
     if (find) {
         int rc = EXIT_FAILURE;
         if (!crf) fprintf(stderr, "scrappie: --find searches reads of flip-flop (CRF) models only; \"%s\" is a transducer model\n", model);

@@ -1103,6 +1103,34 @@ long scrappie_hip_map_crf_pack_plan(const size_t *seqlen, size_t ncand, size_t p
     return np;
 }
 
+/* Every single-base edit of a sequence against a flip-flop read (k_crf_edits_rows, k_crf_edits, sh_crf_edits.h): what a read of L
+ * bases and nblock blocks keeps in device memory.  Three row matrices -- F_B, F_S, G_B -- of nblock + 1 entries, an entry's row of
+ * `pitch` floats: cells 0 .. L and the slot at L + 1 that takes the stores of threads without a cell, rounded up to 16 floats, so
+ * every row starts on 64 bytes.  Results: sub [L][4], ins [L + 1][4], del [L], 9 L + 4 floats rounded up to 4. */
+size_t scrappie_hip_crf_edits_pitch(size_t seqlen) { return (seqlen + 2 + 15) / 16 * 16; }
+static size_t crf_edits_res_floats(size_t seqlen) { return (9 * seqlen + 4 + 3) / 4 * 4; }
+size_t scrappie_hip_crf_edits_row_bytes(size_t seqlen, size_t nblock) { return 3 * (nblock + 1) * scrappie_hip_crf_edits_pitch(seqlen) * 4; }
+
+/* Reads of seqlen[i] bases and nblock[i] blocks in one launch, in input order: pitch[i], rows[i] -- the float offset of read i's F_B
+ * in the launch's row buffer; F_S lies (nblock[i] + 1) * pitch[i] floats behind it and G_B as many behind F_S -- and res[i], the
+ * float offset of its results in the result buffer.  Both offsets are multiples of 4 floats (16 bytes); no two reads overlap.
+ * Returns the floats of the row buffer; *res_floats (may be NULL): those of the result buffer. */
+long long scrappie_hip_crf_edits_plan(const size_t *seqlen, const size_t *nblock, size_t n, int *pitch, long long *rows, long long *res,
+                                      long long *res_floats) {
+    if (res_floats) *res_floats = 0;
+    if (!seqlen || !nblock || !pitch || !rows || !res) return 0;
+    long long nrow = 0, nres = 0;
+    for (size_t i = 0; i < n; i++) {
+        pitch[i] = (int)scrappie_hip_crf_edits_pitch(seqlen[i]);
+        rows[i] = nrow;
+        res[i] = nres;
+        nrow += (long long)(scrappie_hip_crf_edits_row_bytes(seqlen[i], nblock[i]) / 4);
+        nres += (long long)crf_edits_res_floats(seqlen[i]);
+    }
+    if (res_floats) *res_floats = nres;
+    return nrow;
+}
+
 /* the library defines it (scrappie_hip.hip); weak, so that this file also links into the host-only builds of the tests */
 void sh_set_error(const char *fmt, ...) __attribute__((weak, format(printf, 1, 2)));
 #define SH_ERR(...) do { if (sh_set_error) sh_set_error(__VA_ARGS__); } while (0)

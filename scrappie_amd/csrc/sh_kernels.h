@@ -332,6 +332,7 @@ struct ShMeta {
 #include "sh_crf_post.h"
 #include "sh_map_crf.h"
 #include "sh_map_crf_pack.h"
+#include "sh_crf_edits.h"
 #include "sh_map_crf_local.h"
 #include "sh_map_local.h"
 #include "sh_crf_find.h"
