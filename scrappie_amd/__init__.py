@@ -563,20 +563,36 @@ def launch_form_counts():
                 squig={(bool(k & 2), bool(k & 1)): int(q[k]) for k in range(4)})
 
 
+def _form_counts(counts, nbit=3):
+    """{(a bool per bit, the highest first): n} of a *_form_counts symbol that fills 2 ** nbit counters"""
+    q = (C.c_uint64 * (1 << nbit))()
+    counts(q)
+    return {tuple(bool(k >> b & 1) for b in reversed(range(nbit))): int(q[k]) for k in range(1 << nbit)}
+
+
+def _local_plan(plan, *sizes_and_stride):
+    """A *_local_plan symbol on its leading arguments: the windows counted, then the arrays filled."""
+    nw = int(plan(*sizes_and_stride, 0, None, None, None, None, None, None))
+    first, ncell, own = (np.zeros(nw, dtype=np.uintp) for _ in range(3))
+    home = np.zeros(nw, dtype=np.int32)
+    off = np.zeros(nw, dtype=np.longlong)
+    tot = C.c_longlong(0)
+    sp = C.POINTER(C.c_size_t)
+    plan(*sizes_and_stride, nw, first.ctypes.data_as(sp), ncell.ctypes.data_as(sp), own.ctypes.data_as(sp), home.ctypes.data_as(C.POINTER(C.c_int)),
+         off.ctypes.data_as(C.POINTER(C.c_longlong)), C.byref(tot))
+    return dict(first=first, ncell=ncell, own=own, home=home, scr_off=off, scr_floats=int(tot.value))
+
+
 def map_crf_form_counts():
     """Launches of each k_map_crf form in this process so far (scrappie_hip_map_crf_form_counts):
     {(viterbi, tiled, scratch): n}."""
-    q = (C.c_uint64 * 8)()
-    lib().scrappie_hip_map_crf_form_counts(q)
-    return {(bool(k & 4), bool(k & 2), bool(k & 1)): int(q[k]) for k in range(8)}
+    return _form_counts(lib().scrappie_hip_map_crf_form_counts)
 
 
 def map_crf_local_form_counts():
     """Launches of each k_map_crf_local form in this process so far (scrappie_hip_map_crf_local_form_counts):
     {(viterbi, tiled, scratch): n}."""
-    q = (C.c_uint64 * 8)()
-    lib().scrappie_hip_map_crf_local_form_counts(q)
-    return {(bool(k & 4), bool(k & 2), bool(k & 1)): int(q[k]) for k in range(8)}
+    return _form_counts(lib().scrappie_hip_map_crf_local_form_counts)
 
 
 def map_crf_local_max_cells():
@@ -588,16 +604,7 @@ def map_crf_local_plan(seq_len, nblock, stride=-1):
     """The cut of the seq_len + 1 cells of a sequence into windows for a read of `nblock` blocks (host arithmetic, no device;
     scrappie_hip_map_crf_local_plan).  `stride`: start cells per window, 0: one window, -1: the default.  Returns a dict of
     arrays, one entry per window: first, ncell, own, home (0 LDS, 1 device scratch), scr_off (-1 in LDS), and scr_floats."""
-    Lb = lib()
-    nw = int(Lb.scrappie_hip_map_crf_local_plan(seq_len, nblock, int(stride), 0, None, None, None, None, None, None))
-    first, ncell, own = (np.zeros(nw, dtype=np.uintp) for _ in range(3))
-    home = np.zeros(nw, dtype=np.int32)
-    off = np.zeros(nw, dtype=np.longlong)
-    tot = C.c_longlong(0)
-    sp = C.POINTER(C.c_size_t)
-    Lb.scrappie_hip_map_crf_local_plan(seq_len, nblock, int(stride), nw, first.ctypes.data_as(sp), ncell.ctypes.data_as(sp), own.ctypes.data_as(sp),
-                                       home.ctypes.data_as(C.POINTER(C.c_int)), off.ctypes.data_as(C.POINTER(C.c_longlong)), C.byref(tot))
-    return dict(first=first, ncell=ncell, own=own, home=home, scr_off=off, scr_floats=int(tot.value))
+    return _local_plan(lib().scrappie_hip_map_crf_local_plan, seq_len, nblock, int(stride))
 
 
 def set_map_crf_local_stride(value):
@@ -610,9 +617,7 @@ def set_map_crf_local_stride(value):
 def map_local_form_counts():
     """Launches of each k_map_local form in this process so far (scrappie_hip_map_local_form_counts):
     {(viterbi, tiled, scratch): n}."""
-    q = (C.c_uint64 * 8)()
-    lib().scrappie_hip_map_local_form_counts(q)
-    return {(bool(k & 4), bool(k & 2), bool(k & 1)): int(q[k]) for k in range(8)}
+    return _form_counts(lib().scrappie_hip_map_local_form_counts)
 
 
 def map_local_max_cells(nstate):
@@ -626,16 +631,7 @@ def map_local_plan(seq_len, nblock, nstate, stride=-1):
     states (host arithmetic, no device; scrappie_hip_map_local_plan).  `stride`: entry positions per window, 0: one window, -1:
     the default.  Returns a dict of arrays, one entry per window: first, ncell, own, home (0 LDS, 1 device scratch), scr_off (-1
     in LDS), and scr_floats."""
-    Lb = lib()
-    nw = int(Lb.scrappie_hip_map_local_plan(seq_len, nblock, nstate, int(stride), 0, None, None, None, None, None, None))
-    first, ncell, own = (np.zeros(nw, dtype=np.uintp) for _ in range(3))
-    home = np.zeros(nw, dtype=np.int32)
-    off = np.zeros(nw, dtype=np.longlong)
-    tot = C.c_longlong(0)
-    sp = C.POINTER(C.c_size_t)
-    Lb.scrappie_hip_map_local_plan(seq_len, nblock, nstate, int(stride), nw, first.ctypes.data_as(sp), ncell.ctypes.data_as(sp), own.ctypes.data_as(sp),
-                                   home.ctypes.data_as(C.POINTER(C.c_int)), off.ctypes.data_as(C.POINTER(C.c_longlong)), C.byref(tot))
-    return dict(first=first, ncell=ncell, own=own, home=home, scr_off=off, scr_floats=int(tot.value))
+    return _local_plan(lib().scrappie_hip_map_local_plan, seq_len, nblock, nstate, int(stride))
 
 
 def set_map_local_stride(value):
@@ -760,9 +756,7 @@ def set_squiggle_pack_cells(value):
 def squiggle_local_form_counts():
     """Launches of each k_squig_local form in this process so far (scrappie_hip_squiggle_local_form_counts):
     {(viterbi, scratch): n}."""
-    q = (C.c_uint64 * 4)()
-    lib().scrappie_hip_squiggle_local_form_counts(q)
-    return {(bool(k & 2), bool(k & 1)): int(q[k]) for k in range(4)}
+    return _form_counts(lib().scrappie_hip_squiggle_local_form_counts, 2)
 
 
 def squiggle_local_max_cells():
@@ -776,16 +770,7 @@ def squiggle_local_plan(npos, nsample, stride=-1):
     device; scrappie_hip_squiggle_local_plan).  `stride`: entry positions per window, 0: one window, -1: the default.  Returns a
     dict of arrays, one entry per window: first, ncell, own, home (0 LDS, 1 device scratch), scr_off (-1 in LDS), and
     scr_floats."""
-    Lb = lib()
-    nw = int(Lb.scrappie_hip_squiggle_local_plan(npos, nsample, int(stride), 0, None, None, None, None, None, None))
-    first, ncell, own = (np.zeros(nw, dtype=np.uintp) for _ in range(3))
-    home = np.zeros(nw, dtype=np.int32)
-    off = np.zeros(nw, dtype=np.longlong)
-    tot = C.c_longlong(0)
-    sp = C.POINTER(C.c_size_t)
-    Lb.scrappie_hip_squiggle_local_plan(npos, nsample, int(stride), nw, first.ctypes.data_as(sp), ncell.ctypes.data_as(sp), own.ctypes.data_as(sp),
-                                        home.ctypes.data_as(C.POINTER(C.c_int)), off.ctypes.data_as(C.POINTER(C.c_longlong)), C.byref(tot))
-    return dict(first=first, ncell=ncell, own=own, home=home, scr_off=off, scr_floats=int(tot.value))
+    return _local_plan(lib().scrappie_hip_squiggle_local_plan, npos, nsample, int(stride))
 
 
 def set_squiggle_local_stride(value):
@@ -932,6 +917,46 @@ def _scores_and_paths(out, n, length_attr, more=0):
     """[(score, path or None)] of a batched mapping call's results"""
     rs = [out[i] for i in range(n)]
     return [(float(r.score), pth) for r, pth in zip(rs, _paths(rs, length_attr, more))]
+
+
+def _located(out, n, viterbi, length_attr='nblock', more=0):
+    """[(score, first, last, path)] of a batched reference-local call's results: first with a path only, and None for all
+    three where the score is NaN or the call summed the windows.  (One pass, as _paths.)"""
+    rs = [out[i] for i in range(n)]
+    res = []
+    for r, pth in zip(rs, _paths(rs, length_attr, more)):
+        sc = float(r.score)
+        if np.isnan(sc) or not viterbi:
+            res.append((sc, None, None, None))
+        else:
+            res.append((sc, int(r.first) if pth is not None else None, int(r.last), pth))
+    return res
+
+
+def _per_read_references(references, n):
+    """`references`: one string for all n reads, or one per read.  Returns one per read."""
+    if isinstance(references, str):
+        return [references] * n
+    if len(references) != n:
+        raise ValueError("one reference for all signals, or one per signal")
+    return references
+
+
+def _reference_targets(references, kmer_len):
+    """The _MapLocalTarget array for one reference string per read, each distinct one encoded once -- one that cannot be
+    encoded as an empty sequence, which the library maps to NaN --, and what keeps its memory alive."""
+    tgs = (_MapLocalTarget * max(len(references), 1))()
+    enc = {}
+    for i, sq in enumerate(references):
+        if id(sq) not in enc:
+            try:
+                enc[id(sq)] = np.ascontiguousarray(encode_bases(sq, kmer_len), dtype=np.int32)
+            except ValueError:
+                enc[id(sq)] = np.zeros(0, dtype=np.int32)
+        codes = enc[id(sq)]
+        tgs[i].seq = codes.ctypes.data_as(C.POINTER(C.c_int))
+        tgs[i].seqlen = len(codes)
+    return tgs, enc
 
 
 def _path_needs_viterbi(path, viterbi):
@@ -2383,36 +2408,15 @@ class Engine(object):
         read or its reference cannot be mapped."""
         n = len(signals)
         _path_needs_viterbi(path, viterbi)
-        if isinstance(references, str):
-            references = [references] * n
-        elif len(references) != n:
-            raise ValueError("one reference for all signals, or one per signal")
+        tgs, enc = _reference_targets(_per_read_references(references, n), 1)
         h = self._models[model]
         rts, keep = _raw_tables(signals)
-        tgs = (_MapLocalTarget * max(n, 1))()
-        enc = {}
-        for i, sq in enumerate(references):
-            if id(sq) not in enc:
-                try:
-                    enc[id(sq)] = np.ascontiguousarray(encode_bases(sq, 1), dtype=np.int32)
-                except ValueError:
-                    enc[id(sq)] = np.zeros(0, dtype=np.int32)      # mapped to NaN by the library (empty sequence)
-            codes = enc[id(sq)]
-            tgs[i].seq = codes.ctypes.data_as(C.POINTER(C.c_int))
-            tgs[i].seqlen = len(codes)
         keep.append(enc)
         p = self.default_params(min_prob=min_prob, tempW=tempW, tempb=tempb)
         out = (_MapLocalResult * max(n, 1))()
         if lib().scrappie_hip_map_local_batch(self._h, h, rts, tgs, n, C.byref(p), 1 if viterbi else 0, 1 if path else 0, out) != 0:
             raise RuntimeError("map_local_batch: " + last_error())
-        res = []
-        rs = [out[i] for i in range(n)]
-        for r, pth in zip(rs, _paths(rs, more=1)):
-            sc = float(r.score)
-            if np.isnan(sc) or not viterbi:
-                res.append((sc, None, None, None))
-            else:
-                res.append((sc, int(r.first) if pth is not None else None, int(r.last), pth))
+        res = _located(out, n, viterbi, more=1)
         lib().scrappie_hip_free_map_local_results(out, n)
         return res
 
@@ -2426,38 +2430,18 @@ class Engine(object):
         None) where a read or its reference cannot be mapped."""
         n = len(signals)
         _path_needs_viterbi(path, viterbi)
-        if isinstance(references, str):
-            references = [references] * n
-        elif len(references) != n:
-            raise ValueError("one reference for all signals, or one per signal")
+        references = _per_read_references(references, n)
         h = self._models[model]
         nstate = lib().scrappie_hip_model_states(self._h, h)
         kmer_len = 1 if nstate == 25 else guess_state_properties(nstate)[1]      # (a flip-flop model: refused by the library)
+        tgs, enc = _reference_targets(references, kmer_len)
         rts, keep = _raw_tables(signals)
-        tgs = (_MapLocalTarget * max(n, 1))()
-        enc = {}
-        for i, sq in enumerate(references):
-            if id(sq) not in enc:
-                try:
-                    enc[id(sq)] = np.ascontiguousarray(encode_bases(sq, kmer_len), dtype=np.int32)
-                except ValueError:
-                    enc[id(sq)] = np.zeros(0, dtype=np.int32)      # mapped to NaN by the library (empty sequence)
-            codes = enc[id(sq)]
-            tgs[i].seq = codes.ctypes.data_as(C.POINTER(C.c_int))
-            tgs[i].seqlen = len(codes)
         keep.append(enc)
         p = self.default_params(min_prob=min_prob, tempW=tempW, tempb=tempb, stay_pen=stay_pen, skip_pen=skip_pen, local_pen=local_pen)
         out = (_MapLocalResult * max(n, 1))()
         if lib().scrappie_hip_map_post_local_batch(self._h, h, rts, tgs, n, C.byref(p), 1 if viterbi else 0, 1 if path else 0, out) != 0:
             raise RuntimeError("map_post_local_batch: " + last_error())
-        res = []
-        rs = [out[i] for i in range(n)]
-        for r, pth in zip(rs, _paths(rs)):
-            sc = float(r.score)
-            if np.isnan(sc) or not viterbi:
-                res.append((sc, None, None, None))
-            else:
-                res.append((sc, int(r.first) if pth is not None else None, int(r.last), pth))
+        res = _located(out, n, viterbi)
         lib().scrappie_hip_free_map_local_results(out, n)
         return res
 
@@ -2615,11 +2599,7 @@ class Engine(object):
         out = (_SquigLocalResult * max(n, 1))()
         if lib().scrappie_hip_squiggle_match_local_batch(self._h, rts, tgs, n, C.byref(p), 1 if viterbi else 0, 1 if path else 0, out) != 0:
             raise RuntimeError("squiggle_match_local_batch: " + last_error())
-        rs = [out[i] for i in range(n)]
-        res = []
-        for r, pth in zip(rs, _paths(rs, 'n')):
-            ok = viterbi and not np.isnan(r.score)
-            res.append((float(r.score), int(r.first) if ok and pth is not None else None, int(r.last) if ok else None, pth))
+        res = _located(out, n, viterbi, 'n')
         lib().scrappie_hip_free_squiggle_local_results(out, n)
         return res
 

@@ -40,6 +40,10 @@
  *   sh_eng_post.inc      what the engines on a launch group's posterior or transitions share: the batch call and its memory model
  *                        (PostCall), the launch group's stage (post_group), one plan and runner for two homes (DpPlan / dp_run), sets of
  *                        short sequences in packs (PackSet / PackLaunch), a host matrix's upload, the two-span timer
+ *   sh_eng_win.inc       what the engines that map INTO a longer reference share: a reference cut into windows (WinCut / win_cut), both passes over
+ *                        the windows of a launch for a family's WinTraits (win_launch / win_run), the windows' forward sum (win_lse), what a read
+ *                        adds to a launch (win_read_bytes); for the two on a launch group's posterior or transitions the sequences' upload, the
+ *                        launch group's stage and the batch call (seq_win_run / seq_win_batch)
  *   sh_eng_map_crf.inc   mapping of flip-flop (CRF) reads to base sequences (per-read; the launch group of the batched call)
  *   sh_eng_map.inc       block-based mapping of posteriors to sequences (per-read and batched)
  *   sh_eng_map_pack.inc  one read against many candidate sequences, packed into workgroups (per-read and batched)
@@ -672,6 +676,7 @@ extern "C" scrappie_hip_params scrappie_hip_default_params(void) {
 #include "sh_eng_surface.inc"      /* the reference's per-read functions: posterior / trunk on an explicit engine, the process-default engine, decode_transducer, decode_crf; all three coalesced (sh_coalesce.h) */
 #include "sh_eng_cut.inc"      /* shared by those below: LaunchCut (a call cut into launches), dp_order / dp_launch / dp_collect (a kernel with two homes) */
 #include "sh_eng_post.inc"      /* shared by the mapping engines below: PostCall (the batch call), post_group (a launch group to STOP_POST), DpPlan / dp_run, PackSet / PackLaunch, post_upload_* */
+#include "sh_eng_win.inc"      /* shared by the three reference-local engines below: WinCut / win_cut, WinTraits, win_launch / win_run, win_lse, win_read_bytes; seq_win_run / seq_win_batch for the two map families */
 #include "sh_eng_map_crf.inc"      /* mapping of flip-flop reads to base sequences (sh_map_crf.h): map_crf_to_sequence_* on the process-default engine, the launch group scrappie_hip_map_batch runs for a CRF model */
 #include "sh_eng_map.inc"      /* block-based mapping (sh_map.h): map_to_sequence_* on the process-default engine, scrappie_hip_map_batch */
 #include "sh_eng_map_pack.inc"      /* one read against many candidate sequences (sh_map_pack.h): scrappie_hip_map_multi_batch, scrappie_hip_map_post_multi */

@@ -1,12 +1,12 @@
 /* sh_eng_squig_local.inc -- part of scrappie_hip.hip (one translation unit, included from there in this order; not compiled alone):
  * raw signals mapped INTO a longer reference squiggle (k_squig_local, sh_squig_local.h).  scrappie_hip_squiggle_match_local_batch cuts a
  * call into launches (LaunchCut under "squiggle_budget_kb"); every distinct reference of the call is checked and put through
- * sh_squiggle_tables once, and uploaded once per launch.  Two passes, as sh_eng_map_local.inc: every window of every read of a launch in
- * ONE k_squig_local launch (per home), scores and end states back, the host picks each read's best window (or sums them); with a path
- * wanted a second launch runs the traceback on that window alone -- it must repeat the first pass's bits or the read fails -- and
- * k_squig_local_walk returns path, first and last.  squiggle_match_local_* are a batch of one on the process-default engine.  The cut
- * of a reference into windows is host arithmetic in sh_host.c (scrappie_hip_squiggle_local_plan).  No network runs and no model is
- * needed. */
+ * sh_squiggle_tables once, and uploaded once per launch.  The two passes -- every window of every read of a launch in ONE k_squig_local launch
+ * (per home), each read's best window (or their sum), with a path wanted that window again with its traceback, which must repeat the first
+ * pass's bits or the read fails, and k_squig_local_walk for path, first and last -- are win_run's (sh_eng_win.inc).  What is here is the family's
+ * own: its form counters, its WinTraits (size formulas, planner, launch, walk), the uploads of a launch, the batch call with its cost model.
+ * squiggle_match_local_* are a batch of one on the process-default engine.  The cut of a reference into windows is host arithmetic in sh_host.c
+ * (scrappie_hip_squiggle_local_plan).  No network runs and no model is needed. */
 
 /* launches of each k_squig_local form in this process: index (vit ? 2 : 0) | (scratch ? 1 : 0) */
 static std::atomic<uint64_t> g_squig_local_forms[4];
@@ -23,113 +23,66 @@ struct SqlRef { std::string why; std::vector<float> tab; };
 /* what a launch holds so far */
 struct SqlLoad { size_t bytes = 0, nwin = 0; std::set<SqlKey> refs; };
 
-/* the four planes of moves (8 ceil(ncell / 64) words per sample) and the END plane (a quarter as many), whole 16-byte pieces */
-static long long sql_tb_words(size_t ncell, size_t nsample) { return ((long long)nsample * (long long)(10 * ((ncell + 63) / 64)) + 3) & ~3LL; }
-
-static long long sql_cut(size_t L, size_t ns, long stride, MapLocalCut *c) {
-    const long long nw = scrappie_hip_squiggle_local_plan(L, ns, stride, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-    if (!c || nw <= 0) return nw;
-    const size_t n = (size_t)nw;
-    c->first.resize(n); c->ncell.resize(n); c->own.resize(n); c->home.resize(n); c->scr.resize(n);
-    long long fl = 0;
-    return scrappie_hip_squiggle_local_plan(L, ns, stride, n, c->first.data(), c->ncell.data(), c->own.data(), c->home.data(), c->scr.data(), &fl);
-}
-
-/* device bytes one read adds to a launch, its reference's tables apart: its samples, the first pass's windows, scores, end states and scratch
- * rows; with a path the second pass's traceback and rows on its largest window, and the path */
-static size_t sql_read_bytes(size_t L, size_t ns, long stride, bool path, size_t *nwin) {
-    long long fl = 0;
-    const long long nw = scrappie_hip_squiggle_local_plan(L, ns, stride, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &fl);
-    if (nwin) *nwin = (size_t)nw;
-    size_t b = ns * 4 + (size_t)nw * (sizeof(ShSquigLocalWin) + 12) + (size_t)fl * 4 + 64;
-    if (path) {
-        const size_t s = scrappie_hip_squiggle_local_stride(L, ns, stride);
-        const size_t nc = std::min(s + 2 * (ns - 1) + 1, L);
-        b += (size_t)sql_tb_words(nc, ns) * 4 + ns * 4 + sh_squig_local_scr_floats(nc) * 4 + sizeof(ShSquigLocalWin) + 64;
+template <> struct WinTraits<ShSquigLocalWin> {
+    using Args = ShSquigLocalArgs;
+    using WalkOut = int2;                                 /* first, last */
+    static constexpr const char *name = "squiggle_match_local_batch";
+    static constexpr size_t lds_cap = SH_SQ_LDS;
+    static constexpr auto walk = k_squig_local_walk;
+    static DpBufs &bufs(scrappie_hip_engine *e) { return e->dp_sql; }
+    static DBuf &walk_out(scrappie_hip_engine *e) { return e->d_sql_lohi; }
+    static size_t lds_bytes(size_t ncell, const Args &) { return sh_squig_local_lds_bytes(ncell); }
+    static long long scr_floats(size_t ncell) { return (long long)sh_squig_local_scr_floats(ncell); }
+    /* the four planes of moves (8 ceil(ncell / 64) words per sample) and the END plane (a quarter as many), whole 16-byte pieces */
+    static long long tb_words(size_t ncell, size_t nsample) { return ((long long)nsample * (long long)(10 * ((ncell + 63) / 64)) + 3) & ~3LL; }
+    static size_t path_len(size_t nsample) { return nsample; }
+    static size_t last_of(int2 end) { return (size_t)end.x + 1; }      /* position states only move right: the path ends in, or left the reference from, its highest position */
+    static void walked(int2 w, size_t &first, size_t &last) { first = (size_t)w.x; last = (size_t)w.y; }
+    static auto plan(long stride, size_t L, size_t ns) {
+        return [=](size_t cap, size_t *first, size_t *ncell, size_t *own, int *home, long long *scr, long long *fl) {
+            return scrappie_hip_squiggle_local_plan(L, ns, stride, cap, first, ncell, own, home, scr, fl);
+        };
     }
-    return b;
-}
-
-/* one read of a launch */
-struct SqlJob {
-    size_t r;                   /* which read of the call */
-    long long sig, tab;         /* where its samples and its reference's tables lie on the device */
-    size_t ns, L;
-    const MapLocalCut *cut;
-    float score = NAN; int2 end = make_int2(0, 0);
+    static int launch(hipStream_t s, const Args &a, size_t n_lds, size_t n, size_t lds, bool vit, bool) {
+        return pick_bool([&](auto v) {
+                return dp_launch<k_squig_local<v(), true>, k_squig_local<v(), false>>(s, a, n_lds, n, SH_SQ_NTH, lds, sh_squig_local_scr_lds_bytes(), g_squig_local_forms + (v() ? 2 : 0));
+            }, vit);
+    }
 };
 
-/* the record of window w of job j; tb: its traceback's word offset, -1: none; scr_floats and lds take what it needs of its home */
-static ShSquigLocalWin sql_win(const SqlJob &j, size_t w, long long tb, long long &scr_floats, size_t &lds) {
-    const MapLocalCut &c = *j.cut;
-    ShSquigLocalWin r{};
-    r.sig = j.sig; r.tab = j.tab; r.tb = tb; r.nsample = (int)j.ns; r.npos = (int)j.L;
-    r.first = (int)c.first[w]; r.ncell = (int)c.ncell[w]; r.own = (int)c.own[w]; r.ok = 1;
-    r.own0 = w ? 1 : 0;                                  /* behind the cell kept for back state p0 - 1; window 0 has none */
-    if (c.home[w]) { r.scr = scr_floats; scr_floats += (long long)sh_squig_local_scr_floats(c.ncell[w]); }
-    else { r.scr = -1; lds = std::max(lds, sh_squig_local_lds_bytes(c.ncell[w])); }
-    return r;
+/* device bytes one read adds to a launch, its reference's tables apart: its samples and what win_read_bytes counts */
+static size_t sql_read_bytes(size_t L, size_t ns, long stride, bool path, size_t *nwin) {
+    const size_t nc2 = std::min(scrappie_hip_squiggle_local_stride(L, ns, stride) + 2 * (ns - 1) + 1, L);
+    return ns * 4 + win_read_bytes<ShSquigLocalWin>(WinTraits<ShSquigLocalWin>::plan(stride, L, ns), ns, nc2, path, nwin);
 }
 
-/* one launch of the windows wins[] through k_squig_local, in device order (dp_order: those of the LDS home first; perm[k]: which of wins[] goes
- * k-th); scores and, Viterbi, end states into dp_sql.h ([n] float, then [n] int2), which also has room for what a walk over path_len entries returns */
-static int sql_launch(scrappie_hip_engine *e, const std::vector<ShSquigLocalWin> &wins, std::vector<size_t> &perm, size_t lds, long long scr_floats,
-                      long long tb_words, long long path_len, ShSquigLocalArgs a, bool vit) {
-    hipStream_t s = e->stream;
-    DpBufs &d = e->dp_sql;
-    const size_t n = wins.size(), n_lds = dp_order(wins, perm);
-    std::vector<ShSquigLocalWin> rd;                      /* (one home only: wins[] is in device order already) */
-    if (n_lds && n_lds < n) { rd.resize(n); for (size_t k = 0; k < n; k++) rd[k] = wins[perm[k]]; }
-    if (d.ensure(n, sizeof(ShSquigLocalWin), (tb_words + 3) & ~3LL, scr_floats, path_len, n * 24 + (size_t)path_len * 4 + 16, sizeof(int2))) return -1;
-    HIPCHK(hipMemcpyAsync(d.rd.p, rd.empty() ? wins.data() : rd.data(), n * sizeof(ShSquigLocalWin), hipMemcpyHostToDevice, s));
-    a.rd = d.rd.as<ShSquigLocalWin>(); a.tb = d.tb.as<unsigned>(); a.scr = d.scr.as<float>(); a.score = d.score.as<float>(); a.final_state = d.final_state.as<int2>();
-    if (lds > SH_SQ_LDS) return set_err("squiggle_match_local_batch: a window of %zu bytes of LDS", lds);
-    if (pick_bool([&](auto v) {
-            return dp_launch<k_squig_local<v(), true>, k_squig_local<v(), false>>(s, a, n_lds, n, SH_SQ_NTH, lds, sh_squig_local_scr_lds_bytes(), g_squig_local_forms + (v() ? 2 : 0));
-        }, vit)) return -1;
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(d.h.p, d.score.p, n * 4, hipMemcpyDeviceToHost, s));
-    if (vit) HIPCHK(hipMemcpyAsync((char *)d.h.p + n * 4, d.final_state.p, n * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(sh_stream_wait(s));
-    return 0;
-}
-
-/* one launch over the reads who[] of the call */
+/* one launch over the reads who[] of the call: the references' tables and the signals up (squig_ms[0]), then both passes (win_run: squig_ms[1] from the
+ * building of the window records through the first pass, squig_ms[2] the rest).  A read whose second pass disagrees with its first is refused alone. */
 static int sql_run(scrappie_hip_engine *e, const std::vector<size_t> &who, const raw_table *reads, const scrappie_hip_squiggle_target *tg,
                    const std::map<SqlKey, SqlRef> &refs, const scrappie_hip_squiggle_params *p, bool vit, bool want_path,
                    scrappie_hip_squiggle_local_result *out, LaunchCut<SqlLoad> &cut) {
+    using T = WinTraits<ShSquigLocalWin>;
     std::lock_guard<std::mutex> lk(e->mu);
     hipStream_t s = e->stream;
-    DpBufs &d = e->dp_sql;
     const long stride = (long)e->squig_local_stride;
     const auto t0 = std::chrono::steady_clock::now();
     /* the references of the launch, each once; the signals end to end */
     std::map<SqlKey, long long> at;
     long long tab_floats = 0, sig_floats = 0;
-    std::map<std::pair<size_t, size_t>, MapLocalCut> cut_of;      /* (positions, samples): reads of one length share a reference's cut */
-    std::vector<SqlJob> jobs;
-    std::vector<size_t> job_off(who.size() + 1, 0);
-    for (size_t k = 0; k < who.size(); k++) {
-        const size_t r = who[k];
+    WinCuts cuts;
+    std::vector<WinJob> jobs;
+    std::vector<long long> sig_at, tab_at;      /* where a job's samples and its reference's tables lie on the device */
+    for (const size_t r : who) {
         const SqlKey key = sql_key(tg[r]);
         if (at.emplace(key, tab_floats).second) tab_floats += (long long)(5 * tg[r].npos + 4);
-        SqlJob j;
-        j.r = r; j.ns = reads[r].end - reads[r].start; j.L = tg[r].npos; j.sig = sig_floats; j.tab = at[key];
-        sig_floats += (long long)j.ns;
-        auto found = cut_of.find(std::make_pair(j.L, j.ns));
-        if (found == cut_of.end()) {
-            found = cut_of.emplace(std::make_pair(j.L, j.ns), MapLocalCut()).first;
-            (void)sql_cut(j.L, j.ns, stride, &found->second);
-        }
-        j.cut = &found->second;
-        if (j.cut->first.empty()) return set_err("squiggle_match_local_batch: nothing to cut (a reference of %zu positions, %zu samples)", j.L, j.ns);
-        job_off[k + 1] = job_off[k] + j.cut->first.size();
-        jobs.push_back(j);
+        const size_t ns = reads[r].end - reads[r].start, L = tg[r].npos;
+        jobs.push_back(WinJob{ns, L, cuts.get(L, ns, T::plan(stride, L, ns))});
+        sig_at.push_back(sig_floats); tab_at.push_back(at[key]);
+        sig_floats += (long long)ns;
     }
-    const size_t nj = jobs.size(), nwin = job_off[nj];
     if (e->d_sql_sig.ensure((size_t)sig_floats * 4 + 16) || e->d_sql_tab.ensure((size_t)tab_floats * 4 + 16) || e->h_sql.ensure((size_t)sig_floats * 4 + 16)) return -1;
     float *hsig = e->h_sql.as<float>();
-    for (const SqlJob &j : jobs) memcpy(hsig + j.sig, reads[j.r].raw + reads[j.r].start, j.ns * 4);
+    for (size_t k = 0; k < who.size(); k++) memcpy(hsig + sig_at[k], reads[who[k]].raw + reads[who[k]].start, jobs[k].rows * 4);
     HIPCHK(hipMemcpyAsync(e->d_sql_sig.p, hsig, (size_t)sig_floats * 4, hipMemcpyHostToDevice, s));
     for (const auto &kv : at) {
         const std::vector<float> &tab = refs.at(kv.first).tab;
@@ -140,104 +93,26 @@ static int sql_run(scrappie_hip_engine *e, const std::vector<size_t> &who, const
     a.sig = e->d_sql_sig.as<float>(); a.tab = e->d_sql_tab.as<float>();
     a.move_back_pen = logf(p->prob_back); a.half_pen = logf(0.5f);          /* sh_squiggle_tables' pens */
     a.local_pen = p->local_pen; a.skip_pen = p->skip_pen; a.minscore = p->minscore;
-    /* the first pass: window w of job k is job_off[k] + w */
-    std::vector<ShSquigLocalWin> wins;
-    std::vector<size_t> perm;
-    long long scr_floats = 0;
-    size_t lds = sh_squig_local_scr_lds_bytes();
-    wins.reserve(nwin);
-    for (size_t k = 0; k < nj; k++)
-        for (size_t w = 0; w < jobs[k].cut->first.size(); w++) wins.push_back(sql_win(jobs[k], w, -1, scr_floats, lds));
-    const auto t1 = std::chrono::steady_clock::now();
-    if (sql_launch(e, wins, perm, lds, scr_floats, 0, 0, a, vit)) return -1;
-    const auto t2 = std::chrono::steady_clock::now();
-    std::vector<float> wsc(nwin);
-    std::vector<int2> wend(vit ? nwin : 0);
-    {
-        const float *hs = d.h.as<float>();
-        const int2 *he = (const int2 *)(hs + nwin);
-        for (size_t k = 0; k < nwin; k++) { wsc[perm[k]] = hs[k]; if (vit) wend[perm[k]] = he[k]; }
-    }
-    /* per read: the highest window, the lowest on a tie; forward: sh_lse over the windows in their order */
-    std::vector<size_t> bestw(nj, 0);
-    for (size_t k = 0; k < nj; k++) {
-        const float *sc = wsc.data() + job_off[k];
-        const size_t nw = job_off[k + 1] - job_off[k];
-        SqlJob &j = jobs[k];
-        scrappie_hip_squiggle_local_result &res = out[j.r];
-        res.n = reads[j.r].n;
-        if (vit) {
-            size_t b = 0;
-            for (size_t w = 1; w < nw; w++) if (sc[w] > sc[b]) b = w;
-            bestw[k] = b;
-            j.score = sc[b];
-            j.end = wend[job_off[k] + b];
-            res.last = (size_t)j.end.x + 1;                  /* position states only move right: the path ends in, or left the reference from, its highest position */
-        } else {
-            float acc = sc[0];
-            for (size_t w = 1; w < nw; w++) acc = map_local_lse(acc, sc[w]);
-            j.score = acc;
-        }
-        res.score = j.score;
-    }
-    if (vit && want_path) {
-        /* the second pass: each read's best window alone, with its traceback; perm[k]: the job that goes k-th on the device */
-        long long tb_words = 0, scr2 = 0, path_len = 0;
-        size_t lds2 = sh_squig_local_scr_lds_bytes();
-        wins.clear();
-        for (size_t k = 0; k < nj; k++) {
-            wins.push_back(sql_win(jobs[k], bestw[k], tb_words, scr2, lds2));
-            tb_words += sql_tb_words(jobs[k].cut->ncell[bestw[k]], jobs[k].ns);
-            path_len += (long long)jobs[k].ns;
-        }
-        if (sql_launch(e, wins, perm, lds2, scr2, tb_words, path_len, a, true)) return -1;
-        std::vector<long long> poff(nj);
-        std::vector<char> bad(nj, 0);
-        long long pend = 0;
-        for (size_t k = 0; k < nj; k++) { poff[k] = pend; pend += (long long)jobs[perm[k]].ns; }
-        {
-            const float *hs = d.h.as<float>();               /* the same window again: the same bits */
-            const int2 *he = (const int2 *)(hs + nj);
-            for (size_t k = 0; k < nj; k++) {
-                const SqlJob &j = jobs[perm[k]];
-                if (memcmp(&hs[k], &j.score, 4) || he[k].x != j.end.x || he[k].y != j.end.y) {
-                    char msg[240];
-                    snprintf(msg, sizeof msg, "the second pass of a window disagrees with the first (%.9g at %d/%d, not %.9g at %d/%d)", hs[k], he[k].x, he[k].y,
-                             j.score, j.end.x, j.end.y);
-                    cut.refuse(j.r, msg);
-                    bad[k] = 1;
-                    poff[k] = -1;                            /* (not walked) */
-                }
-            }
-        }
-        if (e->d_sql_lohi.ensure(nj * 8 + 16)) return -1;
-        HIPCHK(hipMemcpyAsync(d.path_off.p, poff.data(), nj * 8, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_squig_local_walk, dim3((unsigned)((nj + 63) / 64)), dim3(64), 0, s, (const ShSquigLocalWin *)d.rd.p, (int)nj,
-                           (const unsigned *)d.tb.p, (const int2 *)d.final_state.p, (const long long *)d.path_off.p, d.paths.as<int>(),
-                           e->d_sql_lohi.as<int2>());
-        HIPCHK(hipGetLastError());
-        int32_t *hf = (int32_t *)d.h.p, *hp = hf + 2 * nj;
-        HIPCHK(hipMemcpyAsync(hf, e->d_sql_lohi.p, nj * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(hp, d.paths.p, (size_t)path_len * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(sh_stream_wait(s));
-        for (size_t k = 0; k < nj; k++) {
-            const SqlJob &j = jobs[perm[k]];
-            scrappie_hip_squiggle_local_result &res = out[j.r];
-            const raw_table &rt = reads[j.r];
-            if (bad[k]) { res = scrappie_hip_squiggle_local_result{NAN, (size_t)-1, 0, 0, nullptr}; continue; }
-            res.first = (size_t)hf[2 * k];
-            res.last = (size_t)hf[2 * k + 1];
+    e->squig_ms[0] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return win_run<ShSquigLocalWin>(e, jobs, a, vit, false, want_path, e->squig_ms + 1, Span2(),
+        [&](size_t k, size_t w) {
+            ShSquigLocalWin r{};
+            r.sig = sig_at[k]; r.tab = tab_at[k]; r.nsample = (int)jobs[k].rows; r.npos = (int)jobs[k].L;
+            r.own0 = w ? 1 : 0;                              /* behind the cell kept for back state p0 - 1; window 0 has none */
+            return r;
+        },
+        [&](size_t k, const char *why) { cut.refuse(who[k], why); return 0; },
+        [&](size_t k, float score, int2, size_t first, size_t last, const int32_t *path) {
+            const raw_table &rt = reads[who[k]];
+            scrappie_hip_squiggle_local_result &res = out[who[k]];
+            res.score = score; res.n = rt.n; res.first = first; res.last = last;
+            if (!path) return 0;
             res.path = (int32_t *)malloc(std::max<size_t>(rt.n, 1) * 4);
             if (!res.path) return set_err("out of host memory");
             for (size_t i = 0; i < rt.n; i++) res.path[i] = -1;
-            memcpy(res.path + rt.start, hp + poff[k], j.ns * 4);
-        }
-    }
-    const auto t3 = std::chrono::steady_clock::now();
-    e->squig_ms[0] += std::chrono::duration<double, std::milli>(t1 - t0).count();
-    e->squig_ms[1] += std::chrono::duration<double, std::milli>(t2 - t1).count();
-    e->squig_ms[2] += std::chrono::duration<double, std::milli>(t3 - t2).count();
-    return 0;
+            memcpy(res.path + rt.start, path, jobs[k].rows * 4);
+            return 0;
+        });
 }
 
 static void sql_blank(scrappie_hip_squiggle_local_result *r, size_t n) {

@@ -857,9 +857,38 @@ int scrappie_hip_map_crf_diagonal_band(size_t nblock, size_t seqlen, size_t half
     return 0;
 }
 
+/* The cut of a reference into windows that the three reference-local planners below share.  Of `cells` cells window w owns the s entry
+ * cells from w s on and holds reach cells more, where a path that enters it can get to -- and, back: one cell to the left of its own where
+ * it is not the first --, as far as there are cells: first[w], own[w], ncell[w].  home[w]: 0 rows in LDS, 1 (more than maxc cells) rows in
+ * device scratch, at float offset scr_off[w] (-1 in LDS) of *scr_floats floats in all, scr(ncell) per window.  Every array may be NULL;
+ * those given hold cap entries, and only the first cap windows are written.  Returns the number of windows. */
+static long long win_plan(size_t cells, size_t s, size_t reach, int back, size_t maxc, size_t (*scr_of)(size_t), size_t cap, size_t *first, size_t *ncell,
+                          size_t *own, int *home, long long *scr_off, long long *scr_floats) {
+    const size_t nwin = (cells + s - 1) / s;
+    long long scr = 0;
+    for (size_t w = 0; w < nwin; w++) {
+        const size_t p0 = w * s;                                /* the first entry cell it owns */
+        const size_t c0 = back && p0 ? p0 - 1 : p0;
+        const size_t left = cells - p0;                         /* cells from p0 to the end */
+        const size_t nc = (s + reach < left ? p0 + s + reach : cells) - c0;
+        const int scratch = nc > maxc;
+        if (w < cap) {
+            if (first) first[w] = c0;
+            if (ncell) ncell[w] = nc;
+            if (own) own[w] = s < left ? s : left;
+            if (home) home[w] = scratch;
+            if (scr_off) scr_off[w] = scratch ? scr : -1;
+        }
+        if (scratch) scr += (long long)scr_of(nc);
+    }
+    if (scr_floats) *scr_floats = scr;
+    return (long long)nwin;
+}
+
 /* Windows of the sequence-local CRF mapping (k_map_crf_local, sh_map_crf_local.h).  A window of ncell cells keeps two columns of
  * transitions, four rows of ncell + 1 floats and ncell codes in LDS. */
 size_t sh_map_crf_local_lds_bytes(size_t ncell) { return (64 + 4 * (ncell + 1) + ncell) * 4; }
+static size_t map_crf_local_scr_floats(size_t ncell) { return 4 * (ncell + 1); }      /* the four rows of a window in device scratch */
 
 /* the most cells a window keeps in LDS (the bytes are linear in ncell) */
 size_t scrappie_hip_map_crf_local_max_cells(void) {
@@ -893,26 +922,8 @@ long long scrappie_hip_map_crf_local_plan(size_t seqlen, size_t nblock, long str
                                           int *home, long long *scr_off, long long *scr_floats) {
     if (scr_floats) *scr_floats = 0;
     if (seqlen == 0 || nblock == 0 || seqlen > ((size_t)1 << 30) || nblock > ((size_t)1 << 30)) return 0;
-    const size_t cells = seqlen + 1, s = scrappie_hip_map_crf_local_stride(seqlen, nblock, stride);
-    const size_t nwin = (cells + s - 1) / s;
-    long long scr = 0;
-    for (size_t w = 0; w < nwin; w++) {
-        const size_t c0 = w * s;
-        const size_t left = cells - c0;                         /* cells from c0 to the end */
-        const size_t reach = s - 1 + nblock + 1;                /* cells a path that starts in the window can be in */
-        const size_t nc = reach < left ? reach : left;
-        const int scratch = sh_map_crf_local_lds_bytes(nc) > SH_MAP_LDS;
-        if (w < cap) {
-            if (first) first[w] = c0;
-            if (ncell) ncell[w] = nc;
-            if (own) own[w] = s < left ? s : left;
-            if (home) home[w] = scratch;
-            if (scr_off) scr_off[w] = scratch ? scr : -1;
-        }
-        if (scratch) scr += (long long)(4 * (nc + 1));
-    }
-    if (scr_floats) *scr_floats = scr;
-    return (long long)nwin;
+    return win_plan(seqlen + 1, scrappie_hip_map_crf_local_stride(seqlen, nblock, stride), nblock, 0, scrappie_hip_map_crf_local_max_cells(),
+                    map_crf_local_scr_floats, cap, first, ncell, own, home, scr_off, scr_floats);
 }
 
 /* Windows of the sequence-local transducer mapping (k_map_local, sh_map_local.h).  A window keeps a head of 32 words and two
@@ -920,6 +931,7 @@ long long scrappie_hip_map_crf_local_plan(size_t seqlen, size_t nblock, long str
  * row and the codes, each of ncell entries rounded up to a multiple of 4. */
 size_t sh_map_local_scr_lds_bytes(size_t nr) { return (32 + 2 * ((nr + 3) & ~(size_t)3)) * 4; }
 size_t sh_map_local_lds_bytes(size_t ncell, size_t nr) { return sh_map_local_scr_lds_bytes(nr) + 4 * ((ncell + 3) & ~(size_t)3) * 4; }
+static size_t map_local_scr_floats(size_t ncell) { return 3 * ((ncell + 3) & ~(size_t)3); }      /* the three rows of a window in device scratch */
 
 /* the most cells a window of a posterior of nr states keeps in LDS; 0 where the columns alone exceed it */
 size_t scrappie_hip_map_local_max_cells(size_t nr) {
@@ -954,25 +966,8 @@ long long scrappie_hip_map_local_plan(size_t seqlen, size_t nblock, size_t nr, l
                                       int *home, long long *scr_off, long long *scr_floats) {
     if (scr_floats) *scr_floats = 0;
     if (seqlen == 0 || nblock == 0 || nr < 2 || seqlen > ((size_t)1 << 30) || nblock > ((size_t)1 << 30)) return 0;
-    const size_t s = scrappie_hip_map_local_stride(seqlen, nblock, nr, stride), reach = 2 * (nblock - 1);
-    const size_t nwin = (seqlen + s - 1) / s;
-    long long scr = 0;
-    for (size_t w = 0; w < nwin; w++) {
-        const size_t c0 = w * s;
-        const size_t left = seqlen - c0;                        /* cells from c0 to the end */
-        const size_t nc = s + reach < left ? s + reach : left;  /* cells a path that enters in the window can be in */
-        const int scratch = sh_map_local_lds_bytes(nc, nr) > SH_MAP_LDS;
-        if (w < cap) {
-            if (first) first[w] = c0;
-            if (ncell) ncell[w] = nc;
-            if (own) own[w] = s < left ? s : left;
-            if (home) home[w] = scratch;
-            if (scr_off) scr_off[w] = scratch ? scr : -1;
-        }
-        if (scratch) scr += (long long)(3 * ((nc + 3) & ~(size_t)3));
-    }
-    if (scr_floats) *scr_floats = scr;
-    return (long long)nwin;
+    return win_plan(seqlen, scrappie_hip_map_local_stride(seqlen, nblock, nr, stride), 2 * (nblock - 1), 0, scrappie_hip_map_local_max_cells(nr),
+                    map_local_scr_floats, cap, first, ncell, own, home, scr_off, scr_floats);
 }
 
 /* Windows of the reference-local squiggle mapping (k_squig_local, sh_squig_local.h).  In the LDS home a window of ncell cells keeps
@@ -1014,27 +1009,8 @@ long long scrappie_hip_squiggle_local_plan(size_t npos, size_t nsample, long str
                                            int *home, long long *scr_off, long long *scr_floats) {
     if (scr_floats) *scr_floats = 0;
     if (npos == 0 || nsample == 0 || npos > ((size_t)1 << 30) || nsample > ((size_t)1 << 30)) return 0;
-    const size_t s = scrappie_hip_squiggle_local_stride(npos, nsample, stride), reach = 2 * (nsample - 1);
-    const size_t nwin = (npos + s - 1) / s;
-    long long scr = 0;
-    for (size_t w = 0; w < nwin; w++) {
-        const size_t p0 = w * s;                                /* the first entry position it owns */
-        const size_t c0 = p0 ? p0 - 1 : 0;                      /* back state p0 - 1 lives in the cell to its left */
-        const size_t left = npos - p0;
-        const size_t end = s + reach < left ? p0 + s + reach : npos;      /* one past its last cell */
-        const size_t nc = end - c0;
-        const int scratch = sh_squig_local_lds_bytes(nc) > SH_SQ_LDS;
-        if (w < cap) {
-            if (first) first[w] = c0;
-            if (ncell) ncell[w] = nc;
-            if (own) own[w] = s < left ? s : left;
-            if (home) home[w] = scratch;
-            if (scr_off) scr_off[w] = scratch ? scr : -1;
-        }
-        if (scratch) scr += (long long)sh_squig_local_scr_floats(nc);
-    }
-    if (scr_floats) *scr_floats = scr;
-    return (long long)nwin;
+    return win_plan(npos, scrappie_hip_squiggle_local_stride(npos, nsample, stride), 2 * (nsample - 1), 1 /* back state p0 - 1 lives in the cell to its left */,
+                    scrappie_hip_squiggle_local_max_cells(), sh_squig_local_scr_floats, cap, first, ncell, own, home, scr_off, scr_floats);
 }
 
 /* Packs of motifs searched inside a flip-flop read (k_crf_find, sh_crf_find.h).  A pack of ncell cells keeps two columns of

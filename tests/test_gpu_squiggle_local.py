@@ -15,7 +15,7 @@ import pytest
 import scrappie_amd as sa
 from scrappie_amd import model
 from test_squiggle_cpu import PENS, _case_inputs, call_squig, ref_squiggle_lib
-from test_squiggle_local_cpu import END_SETS, PENS4, max_cells, need_feature, np_plan, np_squiggle_local, walk_inputs
+from test_squiggle_local_cpu import END_SETS, PENS4, SCR_MUL, max_cells, need_feature, np_plan, np_squiggle_local, walk_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -146,6 +146,31 @@ def test_homes_at_the_cell_limit(eng):
     assert len({_b(g[0]) for g in got.values()}) == 1
     if info["tie_free"]:
         assert len({(g[1], g[2], g[3].tobytes()) for g in got.values()}) == 1
+
+
+def test_scratch_read_before_lds_read_in_one_call(eng):
+    """two reads into one reference of three whole scratch windows, in this order: one of so many samples that the default stride
+    puts its windows in device scratch, one of 40 whose windows live in LDS.  The second pass then runs the reads in another order
+    than the call's (LDS home first): score, first, last and path of each as of the read called alone, bit for bit"""
+    need_feature()
+    M = max_cells()
+    ns_scr, ns_lds = M // 4 + 2, 40
+    L = 3 * SCR_MUL * ns_scr
+    params, long_sig, _ = walk_inputs(L, M + 50, M + 50 + ns_scr // 2 + 2, 91)
+    same, short_sig, _ = walk_inputs(L, 2 * M + 10, 2 * M + 40, 91)
+    assert np.array_equal(params, same)
+    reads = [np.resize(long_sig, ns_scr).astype(np.float32), np.resize(short_sig, ns_lds).astype(np.float32)]
+    scr, lds = sa.squiggle_local_plan(L, ns_scr, -1), sa.squiggle_local_plan(L, ns_lds, -1)
+    assert len(scr["home"]) >= 3 and scr["home"].all() and len(lds["home"]) >= 3 and not lds["home"].any()
+    kw = _kw(PENS4[1])
+    b0 = sa.squiggle_local_form_counts()
+    together = eng.match_squiggle_reference(reads, params, viterbi=True, path=True, **kw)
+    b1 = sa.squiggle_local_form_counts()
+    assert b1[(True, False)] - b0[(True, False)] == 2 and b1[(True, True)] - b0[(True, True)] == 2, (b0, b1)      # both homes in both passes
+    alone = [eng.match_squiggle_reference([r], params, viterbi=True, path=True, **kw)[0] for r in reads]
+    for i, (got, want) in enumerate(zip(together, alone)):
+        assert np.isfinite(want[0]) and _b(got[0]) == _b(want[0]) and got[1:3] == want[1:3] and np.array_equal(got[3], want[3]), i
+        assert len(got[3]) == len(reads[i]) and got[1] == int(got[3][got[3] >= 0].min()), i
 
 
 def test_without_local_penalty_against_the_compiled_reference(eng, world):
