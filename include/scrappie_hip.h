@@ -783,6 +783,75 @@ void scrappie_hip_crf_edits_form_counts(uint64_t forms[12]);
  * *row_bytes (may be NULL): the row bytes of all of them */
 void scrappie_hip_crf_edits_timing(scrappie_hip_engine *e, double ms[3], size_t *launches, size_t *row_bytes);
 
+/* Every single-base edit of a sequence scored against a read of a TRANSDUCER model in one pass (sh_eng_map_edits.inc; k_map_edits_rows,
+ * k_map_edits, sh_map_edits.h): for the bases seq[0..L) the 4 L substitutions, the L deletions and the 4 (L + 1) insertions, numbered as
+ * above, each the score map_to_sequence_viterbi / _forward give for the k-mer states of the edited sequence -- from one forward sweep,
+ * one backward sweep and one combining pass instead of 9 L + 4 dynamic programmes.
+ *
+ * Definition (tests/test_map_edits_cpu.py restates it in numpy).  lp[t][s]: the read's log-posterior, NB blocks, nr = 4^k + 1 rows, the
+ * stay row the last; lps = lp[t][nr - 1]; penalties stay_pen, skip_pen, local_pen; BIG = 1e30; mx(a, b): b if b > a else a (Viterbi),
+ * log(e^a + e^b) (forward), the arguments in the order written; ls = mx(-local_pen, lps).  s[q] = kmer(seq[q .. q + k)), q = 0 .. n - 1,
+ * n = L - k + 1, the first base the most significant.  Entries t = 0 .. NB; block t leads from entry t to entry t + 1.
+ *   The cell rule at index q with state x, reading columns q, q - 1, q - 2 of entry t: (col[t][q] - stay_pen) + lps, then mx with the step
+ *     col[t][q - 1] + lp[t][x] (q >= 1), with the skip (col[t][q - 2] - skip_pen) + lp[t][x] (q >= 2), with FS[t] + lp[t][x] from START (q == 0).
+ *   Forward rows, map_to_sequence's cells kept for every entry: F[0][q] = -BIG; FS[0] = 0, FS[t + 1] = FS[t] + ls; F[t + 1][q] the cell rule
+ *     with state s[q].  base: map_to_sequence_*'s end rule on row NB with its END cell, bit for bit its score.
+ *   Backward rows: GE[NB] = 0, GE[t] = GE[t + 1] + ls_t; G[NB][n - 1] = 0, everything else -BIG; for t descending
+ *     G[t][q] = (lps - stay_pen) + G[t + 1][q], then mx with lp[t][s[q + 1]] + G[t + 1][q + 1] (q + 1 < n), with
+ *     (lp[t][s[q + 2]] - skip_pen) + G[t + 1][q + 2] (q + 2 < n), with -local_pen + GE[t + 1] (q == n - 1).
+ *   An edit at base i keeps the first A = max(i - k + 1, 0) states of s, puts M >= 0 new states mid[0..M) behind them and continues with the
+ *   suffix s[j0 ..] of Bn = n - j0 states; s' (n' states) are the edited sequence's.  A substitution: n' = n, j0 = min(i + 1, n); a deletion:
+ *   n' = n - 1, j0 = min(i + 1, n); an insertion before i: n' = n + 1, j0 = min(i, n).  mid = s'[A .. n' - Bn), M <= k (0 for a deletion at
+ *   i == 0), J = A + M the suffix's first index in s'.  Column idx of the edited lattice is F[.][idx] for idx < A and the edit's own
+ *   Mc[.][idx - A] otherwise.
+ *     1. Mc[0][m] = -BIG; Mc[t + 1][m] the cell rule at index A + m with state mid[m].
+ *     2. Bn == 0: E = -BIG; per block E = mx(E + ls, col[t][J - 1] - local_pen); the score is base's end rule on (col[NB][J - 1], E).
+ *     3. else per block t ascending, best = -BIG before: Y0, the arrival at index J from the step (J >= 1), then the skip (J >= 2), or from
+ *        START (J == 0), with lp[t][s[j0]] and no stay; best = mx(best, Y0 + G[t + 1][j0]); where Bn >= 2 and J >= 1 also
+ *        Y1 = (col[t][J - 1] - skip_pen) + lp[t][s[j0 + 1]], best = mx(best, Y1 + G[t + 1][j0 + 1]).
+ *   A score below -BIG / 2 is NAN (no admissible path), as is every edit that leaves fewer than k bases.  sub[i][seq[i]] is computed as any other.
+ * The join is exact: moves advance by 1 or 2, so a path reaches the suffix for the first time at exactly one block and in exactly one of its
+ * first two states; before that block it lies in prefix and middle columns, from it on in the suffix's own cells, which the edit does not touch.
+ * An edit's score and base are different chains of float32 additions: they agree to rounding, not in bits; a caller confirms the edits it
+ * chooses with scrappie_hip_map_multi_batch, which is exact.
+ *
+ * scrappie_hip_map_edits_batch: reads[i] (prepared as for scrappie_hip_map_batch) against targets[i]: seq holds BASE codes 0..3 and seqlen
+ * bases, unbanded; the engine encodes the k-mers.  out[i] as scrappie_hip_map_crf_edits_batch fills it (freed by
+ * scrappie_hip_free_edits_results); base is not turned into NAN: it is scrappie_hip_map_batch's score as it is.  It runs as
+ * scrappie_hip_map_batch does for a transducer: the network and S1 once per launch group, then k_map_edits_rows forward, k_map_edits_rows
+ * backward and k_map_edits on the main stream while the posterior is resident.  A read adds its two row matrices
+ * (scrappie_hip_map_edits_row_bytes) and its results to the cut into launch groups; the debug option "map_edits_budget_kb" bounds the row
+ * and result bytes of one launch of the three kernels (0: one launch per launch group).  A target that cannot be scored -- no or an empty
+ * sequence, fewer than k bases ("shorter than the model's k-mer"), a code that is not a base, poslow / poshigh set ("bands are not part of
+ * this call"), more than scrappie_hip_map_edits_max_bases(k) bases ("too long for k_map_edits") -- gets base and every edit NAN and the first
+ * such reason is the error text; its neighbours are scored.  A flip-flop (CRF) model: -1 with a text that names it and
+ * scrappie_hip_map_crf_edits_batch.  viterbi 0: forward scores.  scrappie_hip_map_timing covers the call ([0] network + S1; [1] the three
+ * launches with their copies; [2] stays 0); scrappie_hip_map_edits_timing has the kernels alone, as scrappie_hip_crf_edits_timing.
+ *
+ * map_post_edits: the same on a dense host log-posterior of nr = 4^k + 1 rows, k = 1 .. 5 (columns a multiple of 4 floats apart), and the
+ * process-default engine, a batch of one; base, sub, del, ins may each be NULL; all are NAN, the return value 0 and the reason the error text
+ * where the sequence cannot be scored.  -1 with the reason: a null argument, a posterior of another shape, a failed launch. */
+int scrappie_hip_map_edits_batch(scrappie_hip_engine *e, int model, const raw_table *reads, const scrappie_hip_map_target *targets, size_t n,
+                                 const scrappie_hip_params *p, int viterbi, scrappie_hip_edits_result *out);
+int map_post_edits(const_scrappie_matrix logpost, float stay_pen, float skip_pen, float local_pen, const int *seq, size_t seqlen, int viterbi,
+                   float *base, float *sub, float *del, float *ins);
+/* Host only (sh_host.c): what a launch of the three kernels keeps on the device.  pitch: floats from one entry's row to the next
+ * (n + 1 = seqlen_bases - k + 2 rounded up to 16; 0 where there are fewer than k bases); row_bytes: the two row matrices of nblock + 1
+ * entries; plan: reads in input order, rows[i] the float offset of read i's F in the row buffer (G (nblock[i] + 1) * pitch[i] floats behind
+ * it), res[i] that of its results (sub [L][4], ins [L + 1][4], del [L]) in the result buffer, both multiples of 4; returns the floats of the
+ * row buffer, *res_floats (may be NULL) those of the result buffer; -1, nothing written: k == 0 or a read of fewer than k bases.
+ * max_bases: the longest sequence scored, scrappie_hip_map_lds_max_seq() states. */
+size_t scrappie_hip_map_edits_pitch(size_t seqlen_bases, size_t k);
+size_t scrappie_hip_map_edits_row_bytes(size_t seqlen_bases, size_t k, size_t nblock);
+long long scrappie_hip_map_edits_plan(const size_t *seqlen, const size_t *nblock, size_t n, size_t k, int *pitch, long long *rows, long long *res,
+                                      long long *res_floats);
+size_t scrappie_hip_map_edits_max_bases(size_t k);
+/* launches of each form in this process, all engines together: k_map_edits_rows at (viterbi ? 4 : 0) | (tiled ? 2 : 0) | (backward ? 1 : 0),
+ * k_map_edits at 8 + ((viterbi ? 2 : 0) | (tiled ? 1 : 0)) */
+void scrappie_hip_map_edits_form_counts(uint64_t forms[12]);
+/* the last scrappie_hip_map_edits_batch call on this engine, as scrappie_hip_crf_edits_timing */
+void scrappie_hip_map_edits_timing(scrappie_hip_engine *e, double ms[3], size_t *launches, size_t *row_bytes);
+
 /* Squiggle matching, batched (sh_eng_squig.inc): reads[i] (trimmed, normalised; mapped over [start, end)) against
  * targets[i], a predicted squiggle of npos columns of stride >= 3 floats (mean, log sd, dwell logit); out[i] belongs to
  * reads[i].  No network runs and no model is needed (the squiggles are an input here: scrappie_hip_squiggle_predict_batch

@@ -405,6 +405,20 @@ def lib():
     L.scrappie_hip_crf_edits_form_counts.argtypes = [C.POINTER(C.c_uint64)]
     L.scrappie_hip_crf_edits_timing.restype = None
     L.scrappie_hip_crf_edits_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), sp, sp]
+    L.scrappie_hip_map_edits_batch.argtypes = L.scrappie_hip_map_crf_edits_batch.argtypes
+    L.map_post_edits.argtypes = [PM, C.c_float, C.c_float, C.c_float, ip, C.c_size_t, C.c_int, fp, fp, fp, fp]
+    L.scrappie_hip_map_edits_pitch.restype = C.c_size_t
+    L.scrappie_hip_map_edits_pitch.argtypes = [C.c_size_t, C.c_size_t]
+    L.scrappie_hip_map_edits_row_bytes.restype = C.c_size_t
+    L.scrappie_hip_map_edits_row_bytes.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t]
+    L.scrappie_hip_map_edits_plan.restype = C.c_longlong
+    L.scrappie_hip_map_edits_plan.argtypes = [sp, sp, C.c_size_t, C.c_size_t, ip, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    L.scrappie_hip_map_edits_max_bases.restype = C.c_size_t
+    L.scrappie_hip_map_edits_max_bases.argtypes = [C.c_size_t]
+    L.scrappie_hip_map_edits_form_counts.restype = None
+    L.scrappie_hip_map_edits_form_counts.argtypes = [C.POINTER(C.c_uint64)]
+    L.scrappie_hip_map_edits_timing.restype = None
+    L.scrappie_hip_map_edits_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), sp, sp]
     L.squiggle_match_viterbi.restype = C.c_float
     L.squiggle_match_viterbi.argtypes = [_RawTable, C.c_float, PM, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_int32)]
     L.squiggle_match_forward.restype = C.c_float
@@ -1539,21 +1553,26 @@ def apply_edit(seq, kind, i, c=None):
     return ''.join(out) if text else np.array(out, dtype=np.int32)
 
 
-def crf_edits_form_counts():
-    """Launches of each form of the edit kernels in this process so far (scrappie_hip_crf_edits_form_counts):
-    {('rows', viterbi, tiled, backward): n, ('edits', viterbi, tiled): n}."""
+def _edits_form_counts(fn):
     q = (C.c_uint64 * 12)()
-    lib().scrappie_hip_crf_edits_form_counts(q)
+    fn(q)
     out = {('rows', bool(k & 4), bool(k & 2), bool(k & 1)): int(q[k]) for k in range(8)}
     out.update({('edits', bool(k & 2), bool(k & 1)): int(q[8 + k]) for k in range(4)})
     return out
 
 
-def crf_edits_plan(seqlens, nblocks):
-    """The layout of one launch of the edit kernels over reads of `seqlens` bases and `nblocks` blocks (host arithmetic, no
-    device; scrappie_hip_crf_edits_plan): (pitch, rows, res, row_floats, res_floats) -- per read the floats from one entry's
-    row to the next, the float offset of its three row matrices (F_B, F_S, G_B, each (nblock + 1) * pitch floats) and of its
-    9 L + 4 results; the floats of the two buffers."""
+def crf_edits_form_counts():
+    """Launches of each form of the edit kernels in this process so far (scrappie_hip_crf_edits_form_counts):
+    {('rows', viterbi, tiled, backward): n, ('edits', viterbi, tiled): n}."""
+    return _edits_form_counts(lib().scrappie_hip_crf_edits_form_counts)
+
+
+def map_edits_form_counts():
+    """The same for the transducer edit kernels, k_map_edits_rows and k_map_edits (scrappie_hip_map_edits_form_counts)."""
+    return _edits_form_counts(lib().scrappie_hip_map_edits_form_counts)
+
+
+def _edits_plan(seqlens, nblocks, plan):
     a = np.ascontiguousarray(seqlens, dtype=np.uintp)
     b = np.ascontiguousarray(nblocks, dtype=np.uintp)
     if len(a) != len(b):
@@ -1562,9 +1581,52 @@ def crf_edits_plan(seqlens, nblocks):
     rows, res = np.zeros(len(a), dtype=np.longlong), np.zeros(len(a), dtype=np.longlong)
     nres = C.c_longlong(0)
     sp, lp = C.POINTER(C.c_size_t), C.POINTER(C.c_longlong)
-    nrow = lib().scrappie_hip_crf_edits_plan(a.ctypes.data_as(sp), b.ctypes.data_as(sp), len(a), pitch.ctypes.data_as(C.POINTER(C.c_int)),
-                                             rows.ctypes.data_as(lp), res.ctypes.data_as(lp), C.byref(nres))
+    nrow = plan(a.ctypes.data_as(sp), b.ctypes.data_as(sp), len(a), pitch.ctypes.data_as(C.POINTER(C.c_int)), rows.ctypes.data_as(lp),
+                res.ctypes.data_as(lp), C.byref(nres))
     return pitch, rows, res, int(nrow), int(nres.value)
+
+
+def crf_edits_plan(seqlens, nblocks):
+    """The layout of one launch of the edit kernels over reads of `seqlens` bases and `nblocks` blocks (host arithmetic, no
+    device; scrappie_hip_crf_edits_plan): (pitch, rows, res, row_floats, res_floats) -- per read the floats from one entry's
+    row to the next, the float offset of its three row matrices (F_B, F_S, G_B, each (nblock + 1) * pitch floats) and of its
+    9 L + 4 results; the floats of the two buffers."""
+    return _edits_plan(seqlens, nblocks, lib().scrappie_hip_crf_edits_plan)
+
+
+def map_edits_plan(seqlens, nblocks, kmer_len):
+    """The same for the transducer edit kernels and k-mers of `kmer_len` bases (scrappie_hip_map_edits_plan): two row matrices
+    per read, F and G, of n + 1 = L - kmer_len + 2 floats per entry rounded up to 16.  ValueError where a sequence has fewer
+    than `kmer_len` bases."""
+    out = _edits_plan(seqlens, nblocks, lambda a, b, n, *rest: lib().scrappie_hip_map_edits_plan(a, b, n, kmer_len, *rest))
+    if out[3] < 0:
+        raise ValueError("a sequence of fewer than %d bases holds no k-mer" % kmer_len)
+    return out
+
+
+def map_post_edits(post, seq, stay_pen=0, skip_pen=0, local_pen=4.0, viterbi=True):
+    """Every single-base edit of `seq` (a base string, or an array of base codes 0..3) scored against a read's posterior under a
+    transducer model (a `ScrappyMatrix` of 4^k + 1 log-probabilities per block, k = 1 .. 5, as `calc_post` gives) in one pass on
+    the GPU (map_post_edits: a forward sweep, a backward sweep, one combining pass).  Returns (base, sub, dele, ins) numbered by
+    `apply_edit` as `map_trans_edits` numbers them: base is `map_post_to_sequence`'s score of `seq` itself, bit for bit; the
+    edits are what `map_post_to_sequence` gives for the edited sequence up to float32 rounding (confirm chosen edits with
+    `map_post_to_sequences`, which is exact).  NaN: the edited sequence admits no path through the read or has fewer than k
+    bases; everything is NaN, and `last_error()` says why, where `seq` cannot be scored (empty, shorter than a k-mer, not bases,
+    too long for k_map_edits)."""
+    if not isinstance(post, ScrappyMatrix):
+        raise TypeError('`post` should be a ScrappyMatrix.')
+    nblock, nstate = post.shape
+    if nstate not in (5, 17, 65, 257, 1025):
+        raise ValueError('`post` should hold 4^k + 1 states per block, k = 1 .. 5.')
+    tgs, keep = _crf_targets([seq])
+    L = len(keep[0])
+    base = C.c_float(float('nan'))
+    sub, dele, ins = (np.full(k, np.nan, dtype=np.float32) for k in (4 * L, max(L, 1), 4 * (L + 1)))
+    fp = C.POINTER(C.c_float)
+    if lib().map_post_edits(post.data(), stay_pen, skip_pen, local_pen, tgs[0].seq, L, 1 if viterbi else 0, C.byref(base),
+                            sub.ctypes.data_as(fp), dele.ctypes.data_as(fp), ins.ctypes.data_as(fp)) != 0:
+        raise RuntimeError('An unknown error occurred while scoring edits: ' + last_error())
+    return np.float32(base.value), sub.reshape(L, 4), dele[:L], ins.reshape(L + 1, 4)
 
 
 def map_trans_edits(trans, seq, viterbi=True):
@@ -1932,6 +1994,35 @@ class Prep(object):
         t = (C.c_double * 3)()
         lib().scrappie_hip_prep_timing(self._h, slot, t)
         return {"gather_ms": t[0], "h2d_ms": t[1], "k_p0_ms": t[2]}
+
+
+def _score_edits(eng, fn, name, signals, sequences, model, viterbi, **params):
+    """one batch call of an edits engine: a shared sequence is encoded once; [(base, sub, dele, ins)]"""
+    n = len(signals)
+    if isinstance(sequences, str) or (len(sequences) and np.ndim(sequences[0]) == 0 and not isinstance(sequences[0], str)):
+        sequences = [sequences] * n
+    sequences = list(sequences)
+    if len(sequences) != n:
+        raise ValueError("one sequence for all signals, or one sequence per signal")
+    h = eng._models[model]
+    rts, keep = _raw_tables(signals)
+    made = {}
+    tgs = (_MapTarget * max(n, 1))()
+    for i, sq in enumerate(sequences):
+        if id(sq) not in made:
+            made[id(sq)] = _crf_targets([sq])
+        tgs[i].seq, tgs[i].seqlen = made[id(sq)][0][0].seq, made[id(sq)][0][0].seqlen
+    p = eng.default_params(**params)
+    out = (_EditsResult * max(n, 1))()
+    if fn(eng._h, h, rts, tgs, n, C.byref(p), 1 if viterbi else 0, out) != 0:
+        raise RuntimeError(name + ": " + last_error())
+    res = []
+    take = lambda q, k: np.ctypeslib.as_array(q, shape=(k,)).copy() if k else np.zeros(0, dtype=np.float32)
+    for r in (out[i] for i in range(n)):
+        L = int(r.seqlen)
+        res.append((np.float32(r.base), take(r.sub, 4 * L).reshape(L, 4), take(r.dele, L), take(r.ins, 4 * (L + 1)).reshape(L + 1, 4)))
+    lib().scrappie_hip_free_edits_results(out, n)
+    return res
 
 
 class Engine(object):
@@ -2484,39 +2575,34 @@ class Engine(object):
         `viterbi=False` the scores are log-likelihoods, so `sum(r[1] - r[0] for r in res)` over the reads of a window is the
         log-likelihood ratio of every substitution.  A read or a sequence that cannot be scored has everything NaN
         (`last_error()` names the first)."""
-        n = len(signals)
-        if isinstance(sequences, str) or (len(sequences) and np.ndim(sequences[0]) == 0 and not isinstance(sequences[0], str)):
-            sequences = [sequences] * n
-        sequences = list(sequences)
-        if len(sequences) != n:
-            raise ValueError("one sequence for all signals, or one sequence per signal")
-        h = self._models[model]
-        rts, keep = _raw_tables(signals)
-        made = {}
-        tgs = (_MapTarget * max(n, 1))()
-        for i, sq in enumerate(sequences):                     # a shared sequence is encoded once
-            if id(sq) not in made:
-                made[id(sq)] = _crf_targets([sq])
-            tgs[i].seq, tgs[i].seqlen = made[id(sq)][0][0].seq, made[id(sq)][0][0].seqlen
-        p = self.default_params(min_prob=min_prob, tempW=tempW, tempb=tempb)
-        out = (_EditsResult * max(n, 1))()
-        if lib().scrappie_hip_map_crf_edits_batch(self._h, h, rts, tgs, n, C.byref(p), 1 if viterbi else 0, out) != 0:
-            raise RuntimeError("map_crf_edits_batch: " + last_error())
-        res = []
-        take = lambda q, k: np.ctypeslib.as_array(q, shape=(k,)).copy() if k else np.zeros(0, dtype=np.float32)
-        for r in (out[i] for i in range(n)):
-            L = int(r.seqlen)
-            res.append((np.float32(r.base), take(r.sub, 4 * L).reshape(L, 4), take(r.dele, L), take(r.ins, 4 * (L + 1)).reshape(L + 1, 4)))
-        lib().scrappie_hip_free_edits_results(out, n)
-        return res
+        return _score_edits(self, lib().scrappie_hip_map_crf_edits_batch, "map_crf_edits_batch", signals, sequences, model, viterbi,
+                                 min_prob=min_prob, tempW=tempW, tempb=tempb)
+
+    def score_edits_transducer(self, signals, sequences, model='rgrgr_r94', viterbi=False, stay_pen=0.0, skip_pen=0.0, local_pen=4.0,
+                               min_prob=1e-5, tempW=1.0, tempb=1.0):
+        """`score_edits` for the transducer models (scrappie_hip_map_edits_batch; k_map_edits_rows, k_map_edits): each read
+        against EVERY single-base edit of its sequence under `map_to_sequence`'s lattice with these penalties -- an edit of one
+        base changes up to k consecutive k-mer states.  The network and S1 run once per read.  `sequences`: one base string (or
+        array of base codes) for all reads, or one per read.  Returns [(base, sub, dele, ins)] in input order as
+        `map_post_edits` gives them, numbered by `apply_edit`; base is `map_to_sequence`'s score of the sequence itself.  A
+        read or a sequence that cannot be scored has everything NaN (`last_error()` names the first)."""
+        return _score_edits(self, lib().scrappie_hip_map_edits_batch, "map_edits_batch", signals, sequences, model, viterbi,
+                                 min_prob=min_prob, tempW=tempW, tempb=tempb, stay_pen=stay_pen, skip_pen=skip_pen, local_pen=local_pen)
+
+    def _edits_timing(self, fn):
+        t = (C.c_double * 3)()
+        nl, nb = C.c_size_t(0), C.c_size_t(0)
+        fn(self._h, t, C.byref(nl), C.byref(nb))
+        return dict(rows_forward_ms=t[0], rows_backward_ms=t[1], edits_ms=t[2], launches=int(nl.value), row_bytes=int(nb.value))
 
     def crf_edits_timing(self):
         """the last score_edits call: device ms of the forward rows, the backward rows and the combining pass, summed over its
         launches; how many launches of the three it made and their row bytes"""
-        t = (C.c_double * 3)()
-        nl, nb = C.c_size_t(0), C.c_size_t(0)
-        lib().scrappie_hip_crf_edits_timing(self._h, t, C.byref(nl), C.byref(nb))
-        return dict(rows_forward_ms=t[0], rows_backward_ms=t[1], edits_ms=t[2], launches=int(nl.value), row_bytes=int(nb.value))
+        return self._edits_timing(lib().scrappie_hip_crf_edits_timing)
+
+    def map_edits_timing(self):
+        """the same for the last score_edits_transducer call"""
+        return self._edits_timing(lib().scrappie_hip_map_edits_timing)
 
     def _timing(self, fn, names):
         t = (C.c_double * 3)()

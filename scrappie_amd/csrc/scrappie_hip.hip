@@ -49,6 +49,7 @@
  *   sh_eng_map_pack.inc  one read against many candidate sequences, packed into workgroups (per-read and batched)
  *   sh_eng_map_crf_pack.inc  one flip-flop (CRF) read against many candidate sequences, packed into workgroups (per-read and batched)
  *   sh_eng_crf_edits.inc every single-base edit of a sequence scored against a flip-flop (CRF) read: forward rows, backward rows, one combining pass (per-read and batched)
+ *   sh_eng_map_edits.inc every single-base edit of a sequence scored against a transducer read: forward rows, backward rows, one combining pass (per-read and batched)
  *   sh_eng_crf_find.inc  short sequences searched inside flip-flop (CRF) reads, packed into workgroups (per-read and batched)
  *   sh_eng_map_crf_local.inc  flip-flop (CRF) reads mapped into a longer sequence, one workgroup per window (per-read and batched)
  *   sh_eng_map_local.inc      transducer reads mapped into a longer sequence, one workgroup per window, the posterior column staged in LDS (per-read and batched)
@@ -524,6 +525,9 @@ struct scrappie_hip_engine {
     int map_crf_pack_cells = -1;     /* cells a pack of candidates of a flip-flop read holds (debug option "map_crf_pack_cells"; 0: every candidate through k_map_crf, -1: the default) */
     DBuf d_ce_rd, d_ce_seq, d_ce_rows, d_ce_res, d_ce_base; HBuf h_ce;      /* every single-base edit of a sequence against a flip-flop read (sh_eng_crf_edits.inc): records, codes, the row matrices, results, base scores; results on the host */
     size_t dbg_crf_edits_budget = 0; /* row and result bytes one launch of the three edit kernels may hold (debug option "crf_edits_budget_kb"; 0: one launch per launch group) */
+    DBuf d_me_rd, d_me_seq, d_me_rows, d_me_res, d_me_base; HBuf h_me;      /* every single-base edit of a sequence against a transducer read (sh_eng_map_edits.inc): records, state and base codes, the row matrices, results, base scores; results on the host */
+    size_t dbg_map_edits_budget = 0; /* row and result bytes one launch of the three transducer edit kernels may hold (debug option "map_edits_budget_kb"; 0: one launch per launch group) */
+    double map_edits_ms[3] = {0, 0, 0}; size_t map_edits_launches = 0, map_edits_row_bytes = 0;      /* scrappie_hip_map_edits_timing: the last call's kernels by events, its launches and their row bytes */
     double crf_edits_ms[3] = {0, 0, 0}; size_t crf_edits_launches = 0, crf_edits_row_bytes = 0;      /* scrappie_hip_crf_edits_timing: the last call's kernels by events, its launches and their row bytes */
     int map_crf_local_stride = -1;   /* start cells a window of k_map_crf_local owns (debug option "map_crf_local_stride"; 0: one window, -1: the default) */
     double map_ms[3] = {0, 0, 0};    /* scrappie_hip_map_batch: network + S1, k_map, k_map_walk + results, summed over the last call's launch groups */
@@ -682,6 +686,7 @@ extern "C" scrappie_hip_params scrappie_hip_default_params(void) {
 #include "sh_eng_map_pack.inc"      /* one read against many candidate sequences (sh_map_pack.h): scrappie_hip_map_multi_batch, scrappie_hip_map_post_multi */
 #include "sh_eng_map_crf_pack.inc"      /* one flip-flop read against many candidate sequences (sh_map_crf_pack.h): scrappie_hip_map_crf_multi_batch, scrappie_hip_map_trans_multi */
 #include "sh_eng_crf_edits.inc"      /* every single-base edit of a sequence against a flip-flop read (sh_crf_edits.h): scrappie_hip_map_crf_edits_batch, map_crf_edits */
+#include "sh_eng_map_edits.inc"      /* every single-base edit of a sequence against a transducer read (sh_map_edits.h): scrappie_hip_map_edits_batch, map_post_edits */
 #include "sh_eng_crf_find.inc"      /* short sequences searched inside flip-flop reads, packed into workgroups (sh_crf_find.h): find_crf_sequences_viterbi, scrappie_hip_find_batch */
 #include "sh_eng_map_crf_local.inc"      /* flip-flop reads mapped into a longer sequence, cut into windows (sh_map_crf_local.h): map_crf_to_reference_*, scrappie_hip_map_local_batch */
 #include "sh_eng_map_local.inc"      /* transducer reads mapped into a longer sequence, cut into windows (sh_map_local.h): map_to_reference_*, scrappie_hip_map_post_local_batch */

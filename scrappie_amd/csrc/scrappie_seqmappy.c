@@ -25,6 +25,8 @@
  * --edits (flip-flop models): EVERY single-base edit of the first record of a pair's FASTA scored against the pair's read.  All pairs
  * in ONE scrappie_hip_map_crf_edits_batch call (k_crf_edits_rows, k_crf_edits); per pair a header line and one line per position:
  * the base, then del, subA..T and insA..T as differences to the sequence's own Viterbi score.  Without the option nothing changes.
+ * --kmer-edits (transducer models): the same table from ONE scrappie_hip_map_edits_batch call (k_map_edits_rows, k_map_edits), under
+ * --stay, --skip and --localpen.
  */
 #define _GNU_SOURCE
 #include <getopt.h>
@@ -95,7 +97,12 @@ static void seqmappy_usage(FILE *fh) {
           "                             than the sequence; nan: the edited sequence has more bases than the read has entries).\n"
           "                             A last line `L - - - - - - insA..T`: the insertions behind the last base.  An edit's score\n"
           "                             and S are different sums: differences of a few 1e-5 |S| are rounding; confirm an edit with\n"
-          "                             --each-record.  Flip-flop (CRF) models only; not with any of the options above.\n", fh);
+          "                             --each-record.  Flip-flop (CRF) models only; not with any of the options above.\n"
+          "      --kmer-edits           The table of --edits for a transducer model (the default rgrgr_r94 and its relatives), under\n"
+          "                             --stay, --skip and --localpen: an edit of one base changes up to k consecutive k-mer states\n"
+          "                             (nan: the edited sequence admits no path through the read, or has fewer than k bases).\n"
+          "                             Confirm an edit with --all-records.  Transducer models only (a flip-flop model: --edits); not\n"
+          "                             with any of the options above.\n", fh);
 }
 
 /* --all-records: pair i's read against every record of its FASTA, all pairs in one scrappie_hip_map_multi_batch call; --each-record (crf):
@@ -209,9 +216,11 @@ static void print_delta(FILE *out, float score, float base) {
     else fprintf(out, "\t%f", score - base);
 }
 
-/* --edits: every single-base edit of the first record of pair i's FASTA against pair i's read, all pairs in one scrappie_hip_map_crf_edits_batch call */
+/* --edits (klen 0) and --kmer-edits (klen: the bases of the transducer model's k-mer): every single-base edit of the first record of pair i's FASTA
+ * against pair i's read, all pairs in one scrappie_hip_map_crf_edits_batch or scrappie_hip_map_edits_batch call */
 static int seqmappy_edits(scrappie_hip_engine *e, int h, const scrappie_hip_params *p, char **fasta, size_t npair, FILE *out,
-                          int trim_start, int trim_end, int varseg_chunk, float varseg_thresh) {
+                          int trim_start, int trim_end, int varseg_chunk, float varseg_thresh, int klen) {
+    const char *const opt = klen ? "--kmer-edits" : "--edits";
     /* entry m of the batch is pair who[m]: a pair whose fasta or fast5 did not load is reported here and never reaches the engine */
     raw_table *rts = calloc(npair, sizeof *rts);
     scrappie_hip_map_target *tg = calloc(npair, sizeof *tg);
@@ -233,15 +242,16 @@ static int seqmappy_edits(scrappie_hip_engine *e, int h, const scrappie_hip_para
         codes[nb] = cd; tg[nb].seq = cd; tg[nb].seqlen = n; rts[nb] = rt; who[nb] = j;
         nb++;
     }
-    if (nb && scrappie_hip_map_crf_edits_batch(e, h, rts, tg, nb, p, 1, res) != 0) {
+    if (nb && (klen ? scrappie_hip_map_edits_batch(e, h, rts, tg, nb, p, 1, res) : scrappie_hip_map_crf_edits_batch(e, h, rts, tg, nb, p, 1, res)) != 0) {
         fprintf(stderr, "scrappie: %s\n", scrappie_hip_last_error());
         rc = EXIT_FAILURE;
     } else {
-        const size_t maxL = scrappie_hip_map_crf_lds_max_seq();
+        const size_t maxL = klen ? scrappie_hip_map_edits_max_bases((size_t)klen) : scrappie_hip_map_crf_lds_max_seq();
         for (size_t i = 0; i < nb; i++) {
             const char *fa = fasta[2 * who[i]], *f5 = fasta[2 * who[i] + 1];
             if (isnan(res[i].base)) {        /* the engine's error text names the call's FIRST refusal only: this pair's own reason is worked out here */
-                if (tg[i].seqlen > maxL) fprintf(stderr, "scrappie: Failed to score the edits of \"%s\" for \"%s\": %zu bases are too long for --edits (at most %zu: pass a window of the sequence)\n", fa, f5, tg[i].seqlen, maxL);
+                if (tg[i].seqlen > maxL) fprintf(stderr, "scrappie: Failed to score the edits of \"%s\" for \"%s\": %zu bases are too long for %s (at most %zu: pass a window of the sequence)\n", fa, f5, tg[i].seqlen, opt, maxL);
+                else if (tg[i].seqlen < (size_t)klen) fprintf(stderr, "scrappie: Failed to score the edits of \"%s\" for \"%s\": %zu bases are shorter than the model's k-mer (%d)\n", fa, f5, tg[i].seqlen, klen);
                 else fprintf(stderr, "scrappie: Failed to score the edits of \"%s\" for \"%s\": the read cannot be run (too short for the model, or its signal is out of range)\n", fa, f5);
                 rc = EXIT_FAILURE;
                 continue;
@@ -311,13 +321,13 @@ static int seqmappy_inside(scrappie_hip_engine *e, int h, int klen, const scrapp
 }
 
 int main_seqmappy(int argc, char **argv) {
-    enum { O_SEG = 256, O_T1, O_T2, O_LIC, O_MODEL, O_MFILE, O_DEV, O_ALL, O_INSIDE, O_FIND, O_WITHIN, O_EACH, O_EDITS };
+    enum { O_SEG = 256, O_T1, O_T2, O_LIC, O_MODEL, O_MFILE, O_DEV, O_ALL, O_INSIDE, O_FIND, O_WITHIN, O_EACH, O_EDITS, O_KEDITS };
     static const struct option lo[] = {
         {"localpen", 1, 0, 'l'}, {"min_prob", 1, 0, 'm'}, {"output", 1, 0, 'o'}, {"prefix", 1, 0, 'p'},
         {"segmentation", 1, 0, O_SEG}, {"skip", 1, 0, 's'}, {"stay", 1, 0, 'y'}, {"trim", 1, 0, 't'},
         {"temperature1", 1, 0, O_T1}, {"temperature2", 1, 0, O_T2}, {"licence", 0, 0, O_LIC}, {"license", 0, 0, O_LIC},
-        {"model", 1, 0, O_MODEL}, {"model-file", 1, 0, O_MFILE}, {"device", 1, 0, O_DEV}, {"all-records", 0, 0, O_ALL}, {"inside", 0, 0, O_INSIDE}, {"find", 0, 0, O_FIND}, {"within", 0, 0, O_WITHIN}, {"each-record", 0, 0, O_EACH}, {"edits", 0, 0, O_EDITS}, {"help", 0, 0, '?'}, {0, 0, 0, 0}};
-    int all_records = 0, inside = 0, find = 0, within = 0, each_record = 0, edits = 0;
+        {"model", 1, 0, O_MODEL}, {"model-file", 1, 0, O_MFILE}, {"device", 1, 0, O_DEV}, {"all-records", 0, 0, O_ALL}, {"inside", 0, 0, O_INSIDE}, {"find", 0, 0, O_FIND}, {"within", 0, 0, O_WITHIN}, {"each-record", 0, 0, O_EACH}, {"edits", 0, 0, O_EDITS}, {"kmer-edits", 0, 0, O_KEDITS}, {"help", 0, 0, '?'}, {0, 0, 0, 0}};
+    int all_records = 0, inside = 0, find = 0, within = 0, each_record = 0, edits = 0, kmer_edits = 0;
     /* defaults: scrappie_seqmappy.c:62-78 */
     scrappie_hip_params p = scrappie_hip_default_params();
     p.local_pen = 4.0f; p.min_prob = 1e-5f; p.stay_pen = 0.0f; p.skip_pen = 0.0f; p.tempW = 1.0f; p.tempb = 1.0f;
@@ -355,6 +365,7 @@ int main_seqmappy(int argc, char **argv) {
         case O_WITHIN: within = 1; break;
         case O_EACH: each_record = 1; break;
         case O_EDITS: edits = 1; break;
+        case O_KEDITS: kmer_edits = 1; break;
         default: seqmappy_usage(stderr); return EXIT_FAILURE;
         }
     }
@@ -362,6 +373,15 @@ int main_seqmappy(int argc, char **argv) {
     if (nargs <= 0) { seqmappy_usage(stderr); return EXIT_FAILURE; }
     if (nargs % 2) { fprintf(stderr, "scrappie: fast5 file is a required argument\n"); return EXIT_FAILURE; }    /* scrappie_seqmappy.c:153 */
     const size_t npair = (size_t)nargs / 2;
+    if (kmer_edits && (edits || all_records || inside || find || within || each_record)) {
+        fprintf(stderr, "scrappie: --kmer-edits scores every single-base edit of the first record of a fasta; it cannot be combined with %s\n",
+                edits ? "--edits" : all_records ? "--all-records" : inside ? "--inside" : find ? "--find" : within ? "--within" : "--each-record");
+        return EXIT_FAILURE;
+    }
+    if (kmer_edits && get_raw_model(model) == SCRAPPIE_MODEL_RNNRF_R9_4) {
+        fprintf(stderr, "scrappie: --kmer-edits scores reads of transducer models only; \"%s\" is a flip-flop (CRF) model (--edits)\n", model);
+        return EXIT_FAILURE;
+    }
     if (edits && (all_records || inside || find || within || each_record)) {
         fprintf(stderr, "scrappie: --edits scores every single-base edit of the first record of a fasta; it cannot be combined with %s\n",
                 all_records ? "--all-records" : inside ? "--inside" : find ? "--find" : within ? "--within" : "--each-record");
@@ -416,7 +436,15 @@ int main_seqmappy(int argc, char **argv) {
     if (edits) {
         int rc = EXIT_FAILURE;
         if (!crf) fprintf(stderr, "scrappie: --edits scores reads of flip-flop (CRF) models only; \"%s\" is a transducer model\n", model);
-        else rc = seqmappy_edits(e, h, &p, fasta, npair, out, trim_start, trim_end, varseg_chunk, varseg_thresh);
+        else rc = seqmappy_edits(e, h, &p, fasta, npair, out, trim_start, trim_end, varseg_chunk, varseg_thresh, 0);
+        if (out != stdout) fclose(out);
+        scrappie_hip_engine_destroy(e);
+        return rc;
+    }
+    if (kmer_edits) {
+        int rc = EXIT_FAILURE;
+        if (crf) fprintf(stderr, "scrappie: --kmer-edits scores reads of transducer models only; \"%s\" is a flip-flop (CRF) model (--edits)\n", model);
+        else rc = seqmappy_edits(e, h, &p, fasta, npair, out, trim_start, trim_end, varseg_chunk, varseg_thresh, klen);
         if (out != stdout) fclose(out);
         scrappie_hip_engine_destroy(e);
         return rc;

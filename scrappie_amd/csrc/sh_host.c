@@ -1107,6 +1107,43 @@ long long scrappie_hip_crf_edits_plan(const size_t *seqlen, const size_t *nblock
     return nrow;
 }
 
+/* Every single-base edit of a sequence against a transducer read (k_map_edits_rows, k_map_edits, sh_map_edits.h): what a read of L
+ * bases -- n = L - k + 1 states -- and nblock blocks keeps in device memory.  Two row matrices, F and G, of nblock + 1 entries, an
+ * entry's row of `pitch` floats: cells 0 .. n - 1 and slot n (FS going forward, the stores of threads without a cell going backward),
+ * rounded up to 16 floats, so every row starts on 64 bytes.  Results: sub [L][4], ins [L + 1][4], del [L], 9 L + 4 floats rounded up
+ * to 4.  Fewer than k bases hold no state: pitch and row_bytes 0, and the plan refuses. */
+size_t scrappie_hip_map_edits_pitch(size_t seqlen_bases, size_t k) {
+    return (k == 0 || seqlen_bases < k) ? 0 : (seqlen_bases - k + 1 + 1 + 15) / 16 * 16;
+}
+size_t scrappie_hip_map_edits_row_bytes(size_t seqlen_bases, size_t k, size_t nblock) {
+    return 2 * (nblock + 1) * scrappie_hip_map_edits_pitch(seqlen_bases, k) * 4;
+}
+/* the longest sequence in bases: its states and two rows stay in LDS as k_map's do (12 n + 16 bytes) */
+size_t scrappie_hip_map_edits_max_bases(size_t k) { return k == 0 ? 0 : (SH_MAP_LDS - 16) / 12 + k - 1; }
+
+/* Reads of seqlen[i] bases and nblock[i] blocks in one launch, in input order: pitch[i], rows[i] -- the float offset of read i's F in
+ * the launch's row buffer; G lies (nblock[i] + 1) * pitch[i] floats behind it -- and res[i], the float offset of its results in the
+ * result buffer.  Both offsets are multiples of 4 floats (16 bytes); no two reads overlap.  Returns the floats of the row buffer;
+ * *res_floats (may be NULL): those of the result buffer.  -1: k is 0 or a read has fewer than k bases. */
+long long scrappie_hip_map_edits_plan(const size_t *seqlen, const size_t *nblock, size_t n, size_t k, int *pitch, long long *rows, long long *res,
+                                      long long *res_floats) {
+    if (res_floats) *res_floats = 0;
+    if (!seqlen || !nblock || !pitch || !rows || !res) return 0;
+    if (k == 0) return -1;
+    for (size_t i = 0; i < n; i++)
+        if (seqlen[i] < k) return -1;
+    long long nrow = 0, nres = 0;
+    for (size_t i = 0; i < n; i++) {
+        pitch[i] = (int)scrappie_hip_map_edits_pitch(seqlen[i], k);
+        rows[i] = nrow;
+        res[i] = nres;
+        nrow += (long long)(scrappie_hip_map_edits_row_bytes(seqlen[i], k, nblock[i]) / 4);
+        nres += (long long)crf_edits_res_floats(seqlen[i]);
+    }
+    if (res_floats) *res_floats = nres;
+    return nrow;
+}
+
 /* the library defines it (scrappie_hip.hip); weak, so that this file also links into the host-only builds of the tests */
 void sh_set_error(const char *fmt, ...) __attribute__((weak, format(printf, 1, 2)));
 #define SH_ERR(...) do { if (sh_set_error) sh_set_error(__VA_ARGS__); } while (0)

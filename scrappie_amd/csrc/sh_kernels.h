@@ -335,6 +335,7 @@ struct ShMeta {
 #include "sh_crf_edits.h"
 #include "sh_map_crf_local.h"
 #include "sh_map_local.h"
+#include "sh_map_edits.h"
 #include "sh_crf_find.h"
 #include "sh_stitch.h"
 #include "sh_dwell.h"

@@ -1,0 +1,340 @@
+/* sh_map_edits.h -- part of sh_kernels.h (included from there, behind sh_map_local.h): EVERY single-base edit of a sequence scored against
+ * a read of a transducer model in one pass -- 4 L substitutions (the L that change nothing among them), L deletions, 4 (L + 1) insertions --
+ * each the score map_to_sequence_viterbi / _forward (k_map, sh_map.h) give for the k-mer states of the edited sequence.  Scores only, unbanded.
+ *
+ * The lattice is k_map's: states s[q] = kmer(seq[q .. q + k)), q = 0 .. n - 1, n = L - k + 1; START, END; stay, step, skip.  Entries
+ * t = 0 .. NB, block t leads from entry t to entry t + 1.  lps the block's stay entry, ls = mx(-local_pen, lps).
+ *     F[t][q], FS[t]    k_map's cells and START, kept for every entry;
+ *     G[t][q]           the best (forward: the sum over) continuations from cell q at entry t to the end, GE[t] END's from entry t:
+ *         GE[NB] = 0, GE[t] = GE[t + 1] + ls_t;  G[NB][n - 1] = 0, everything else -SH_MAP_BIG;
+ *         G[t][q] = (lps - stay_pen) + G[t + 1][q], then mx with lp[t][s[q + 1]] + G[t + 1][q + 1] (q + 1 < n), with
+ *         (lp[t][s[q + 2]] - skip_pen) + G[t + 1][q + 2] (q + 2 < n), with -local_pen + GE[t + 1] (q == n - 1).
+ * mx(a, b): b if b > a else a (Viterbi), sh_lse(a, b) (forward).  An edit at base i keeps the first A = max(i - k + 1, 0) states, puts M <= k
+ * new states mid[0..M) behind them -- the k-mers that hold the new base, or that close over the deleted one -- and continues with the suffix
+ * s[j0 ..] of Bn = n - j0 states; J = A + M is the suffix's first index in the edited sequence.  The edit runs its own M columns down the
+ * entries (k_map's cell rule at index A + m, reading the columns to their left: its own, or the prefix's F) and joins the suffix where a path
+ * reaches it for the FIRST time: at block t in its first state (Y0: step from J - 1, skip from J - 2, START where J == 0; no stay) or, by a
+ * skip from J - 1, in its second (Y1); from there on the path lies in cells the edit does not touch, G.  Without a suffix END's own chain and
+ * k_map's end rule close on the last column.  include/scrappie_hip.h states the whole definition; tests/test_map_edits_cpu.py restates it.
+ * The build has -ffp-contract=off; the Viterbi form holds additions and compares only.
+ *
+ * k_map_edits_rows<VIT, TILED, BACK>: k_map's unbanded LDS form -- one workgroup of SH_MAP_NTH threads per read, cell q on thread
+ * q % SH_MAP_NTH, two ping-pong rows of n + 2 floats in LDS beside the state codes, one barrier per block, a cell's posterior entries
+ * gathered through ShMapPost<TILED> -- that also stores every completed row to device memory as [entry][cell] floats, `pitch` apart.
+ * !BACK: blocks ascending through sh_map_cell<VIT>, so the rows and `base` are k_map's bits by construction; slot n of a row holds FS[t]
+ * (LDS and device memory alike), END is thread 0's.  BACK: blocks descending, the recursion above, GE a chain in every thread's registers;
+ * slot n takes the stores of threads without a cell.  The row stores are unconditional plain vector stores.  LDS is the only home of the
+ * rows: n is at most what k_map's LDS home holds.
+ *
+ * k_map_edits<VIT, TILED>: one thread per base position i = 0 .. L, consecutive lanes on consecutive i, SH_MAP_NTH positions per workgroup
+ * (grid: read x chunk of positions).  The thread walks the blocks serially.  In registers: the middle columns of its nine edits (4 x SH_ME_K
+ * for sub, as many for ins, SH_ME_K - 1 for del; slot m is index A + m, slots from M on idle), updated in place, m descending, and nine
+ * running scores; the codes of the new states as a code with base A in the new base's digit and that digit's weight.  Per block it loads
+ * F[t][A - 1], F[t][A - 2], FS[t] and G[t + 1][i .. i + 2] (coalesced, indices clamped, SH_ME_D blocks ahead).  Posterior entries come
+ * from the block's whole column in LDS, staged as k_map_local stages it (ShMapLocalCol<TILED>: every entry finalised once by the fin_post
+ * call k_map makes), SH_ME_CH blocks per barrier, double-buffered, the next chunk already in registers.  Every LDS and vector-memory operation
+ * of the block loop is unconditional: clamped indices, selects, no lane conditions.
+ * Results per read at res: sub [L][4], ins [L + 1][4], del [L] (in this order: the float4 stores stay 16-byte aligned); a score below
+ * -SH_MAP_BIG / 2: no admissible path (the host answers NAN).  All stores are plain vector stores. */
+#ifndef SH_MAP_EDITS_H
+#define SH_MAP_EDITS_H
+
+#include "sh_map_local.h"   /* sh_map.h: SH_MAP_NTH, SH_MAP_BIG, sh_lse, ShMapPost, sh_map_cell; ShMapLocalCol, SH_MAPL_PIECES */
+
+#define SH_ME_K 5                 /* middle columns an edit may have: the longest k-mer */
+#define SH_ME_CH 4                /* blocks of posterior columns staged in LDS per barrier of k_map_edits */
+#define SH_ME_D 4                 /* blocks of row values in flight per thread of k_map_edits (divides SH_ME_CH) */
+
+struct ShMapEditsRead {
+    long long post;     /* dense: float offset of the read's row 0; tiled: the read's first column block */
+    long long seq;      /* offset of the read's n state codes in seq[] */
+    long long bases;    /* offset of its L base codes in seq[] */
+    long long rows;     /* float offset of F in rows[]; G lies (nblock + 1) * pitch floats behind it */
+    long long res;      /* float offset of the read's results in res[] (a multiple of 4) */
+    int nblock, nbase;
+    int lane;           /* tiled: the read's lane in its tile (0..15) */
+    int pitch;          /* floats from one entry's row to the next (>= n + 1) */
+};
+
+struct ShMapEditsArgs {
+    const ShMapEditsRead *rd;
+    const float *post;          /* dense posterior */
+    const float *E, *sums;      /* tiled posterior */
+    long long pstride;          /* dense: floats per row (a multiple of 4, at least 4 ceil(nr / 4)) */
+    int nr;                     /* states, stay included: 4^k + 1 */
+    int nchunk;                 /* tiled: chunks of 16 states per column block */
+    int k;                      /* bases per state, 1 .. SH_ME_K */
+    float min_prob;             /* tiled: fin_post's floor */
+    float stay_pen, skip_pen, local_pen;
+    const int *seq;
+    float *rows;
+    float *res;
+    float *base;                /* [read] */
+};
+
+template <bool VIT> __device__ __forceinline__ float sh_me_mx(float a, float b) { return VIT ? (b > a ? b : a) : sh_lse(a, b); }
+/* mx(a, b) where on, else a: a select (Viterbi); forward, sh_lse with an operand so far below that it adds exactly nothing */
+template <bool VIT> __device__ __forceinline__ float sh_me_mx_if(bool on, float a, float b) {
+    return VIT ? ((on && b > a) ? b : a) : sh_lse(a, on ? b : -4.0f * SH_MAP_BIG);
+}
+
+template <bool VIT, bool TILED, bool BACK>
+__global__ __launch_bounds__(SH_MAP_NTH) void k_map_edits_rows(ShMapEditsArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float sh_me_lds[];
+    const ShMapEditsRead r = a.rd[blockIdx.x];
+    const int tid = threadIdx.x, n = r.nbase - a.k + 1, NB = r.nblock, RW = n + 2, START = n, END = n + 1, STAY = a.nr - 1;
+    const long long P = r.pitch;
+    const float stay_pen = a.stay_pen, skip_pen = a.skip_pen, local_pen = a.local_pen;
+    float *const buf0 = sh_me_lds;
+    float *const buf1 = buf0 + RW;
+    int *const sq = (int *)(sh_me_lds + 2 * RW);
+    for (int i = tid; i < n; i += SH_MAP_NTH) sq[i] = a.seq[r.seq + i];
+    float *const grow = a.rows + r.rows + (BACK ? (long long)(NB + 1) * P : 0);
+    {
+        float *const g0 = grow + (BACK ? (long long)NB * P : 0);
+        for (int i = tid; i < RW; i += SH_MAP_NTH) {         /* the first row: entry 0, or entry NB */
+            const float v = BACK ? (i == n - 1 ? 0.0f : -SH_MAP_BIG) : (i == START ? 0.0f : -SH_MAP_BIG);
+            buf0[i] = v;
+            buf1[i] = -SH_MAP_BIG;
+            g0[min(i, n)] = i <= n ? v : (BACK ? -SH_MAP_BIG : 0.0f);      /* (slot n: FS[0] = 0; backward nothing reads it) */
+        }
+    }
+    ShMapArgs ma{};
+    ma.post = a.post; ma.E = a.E; ma.sums = a.sums; ma.pstride = a.pstride; ma.nr = a.nr; ma.nchunk = a.nchunk; ma.min_prob = a.min_prob;
+    ShMapRead mr{};
+    mr.post = r.post; mr.lane = r.lane;
+    ShMapPost<TILED> lp;
+    const int nch = (n + SH_MAP_NTH) / SH_MAP_NTH;           /* chunks of the block loop: cells 0 .. n - 1 and slot n */
+    float chain = 0.0f;                                      /* FS[t] going forward, GE[t + 1] going backward: the same in every thread */
+    __syncthreads();
+    for (int step = 0; step < NB; step++) {
+        const int t = BACK ? NB - 1 - step : step;
+        const float *const p = (step & 1) ? buf1 : buf0;
+        float *const c = (step & 1) ? buf0 : buf1;
+        float *const g = grow + (long long)(BACK ? t : t + 1) * P;      /* the entry this step completes */
+        lp.block(ma, mr, t);
+        const float lps = lp(STAY);
+        const float ls = VIT ? fmaxf(-local_pen, lps) : sh_lse(-local_pen, lps);
+        for (int ch = 0; ch < nch; ch++) {
+            const int pos = ch * SH_MAP_NTH + tid, q = min(pos, n - 1), at = min(pos, n);
+            float v;
+            if (!BACK) {                                     /* k_map's unbanded cell */
+                int code;
+                const float cell = sh_map_cell<VIT>(p, q, START, q, lp(sq[q]), lps, stay_pen, skip_pen, code);
+                v = pos < n ? cell : chain + ls;             /* slot n: FS[t + 1] */
+            } else {
+                const int q1 = min(q + 1, n - 1), q2 = min(q + 2, n - 1);
+                const float le1 = lp(sq[q1]), le2 = lp(sq[q2]);
+                const float g0 = p[q], g1 = p[q1], g2 = p[q2];
+                v = (lps - stay_pen) + g0;
+                v = sh_me_mx_if<VIT>(q + 1 < n, v, le1 + g1);
+                v = sh_me_mx_if<VIT>(q + 2 < n, v, (le2 - skip_pen) + g2);
+                v = sh_me_mx_if<VIT>(q == n - 1, v, -local_pen + chain);
+            }
+            c[at] = v;
+            g[at] = v;
+        }
+        if (!BACK && tid == 0) {                             /* END, as k_map keeps it */
+            float e = p[END] + ls;
+            const float ex = p[n - 1] - local_pen;
+            if (VIT) { if (ex > e) e = ex; }
+            else e = sh_lse(e, ex);
+            c[END] = e;
+        }
+        chain = chain + ls;
+        __syncthreads();
+    }
+    if (!BACK && tid == 0) {
+        const float *const f = (NB & 1) ? buf1 : buf0;
+        const float x = f[n - 1], y = f[END];
+        a.base[blockIdx.x] = VIT ? fmaxf(x, y) : sh_lse(x, y);
+    }
+}
+
+/* the edited sequence's base at p with code 0 for the new base; kind 0 sub, 1 del, 2 ins; sq: the L bases */
+__device__ __forceinline__ int sh_me_base(int kind, int p, int i, const int *sq, int L) {
+    const int src = kind == 0 ? p : kind == 1 ? (p < i ? p : p + 1) : (p < i ? p : p - 1);
+    const int b = sq[min(max(src, 0), L - 1)];
+    return (kind != 1 && p == i) ? 0 : b;
+}
+
+/* One edit at one block: its join with the suffix (or END's chain where it has none), then its NS middle columns X, in place.
+ * fa2, fa1: the prefix's columns A - 2, A - 1 at entry t, fs START's; col: the block's posterior column; code0[m] + cw[m]: the state of slot m.
+ * le0, le1, g0, g1: the posterior entries of the suffix's first two states and G[t + 1] of them. */
+template <bool VIT, int NS>
+__device__ __forceinline__ void sh_me_edit(float (&X)[NS], float &acc, const int (&code0)[NS], const int (&cw)[NS], int cmul, int A, int M, int J, int Bn,
+                                           float fa2, float fa1, float fs, const float *col, float lps, float ls, float le0, float le1, float g0,
+                                           float g1, float stay_pen, float skip_pen, float local_pen) {
+    float c1 = fa1, c2 = fa2;                                /* columns J - 1 and J - 2 at entry t */
+#pragma unroll
+    for (int j = 1; j <= NS; j++) {
+        c1 = M == j ? X[j - 1] : c1;
+        c2 = M == j ? (j == 1 ? fa1 : X[j - 2 < 0 ? 0 : j - 2]) : c2;
+    }
+    const bool closed = Bn == 0;
+    float y0 = (J == 0 ? fs : c1) + le0;
+    y0 = sh_me_mx_if<VIT>(J >= 2, y0, (c2 - skip_pen) + le0);
+    const float a1 = closed ? acc + ls : acc, b1 = closed ? c1 - local_pen : y0 + g0;
+    acc = sh_me_mx<VIT>(a1, b1);
+    acc = sh_me_mx_if<VIT>(Bn >= 2 && J >= 1, acc, ((c1 - skip_pen) + le1) + g1);
+#pragma unroll
+    for (int m = NS - 1; m >= 0; m--) {
+        const int q = A + m;
+        const float le = col[code0[m] + cmul * cw[m]];
+        const float l1 = m == 0 ? fa1 : X[m - 1 < 0 ? 0 : m - 1];
+        const float l2 = m == 0 ? fa2 : m == 1 ? fa1 : X[m - 2 < 0 ? 0 : m - 2];
+        float v = (X[m] - stay_pen) + lps;
+        v = sh_me_mx<VIT>(v, (q >= 1 ? l1 : fs) + le);       /* the step, or from START at index 0 */
+        v = sh_me_mx_if<VIT>(q >= 2, v, (l2 - skip_pen) + le);
+        X[m] = m < M ? v : X[m];
+    }
+}
+
+/* the column J - 1 of an edit after the last block */
+template <int NS> __device__ __forceinline__ float sh_me_last(const float (&X)[NS], int M, float fa1) {
+    float c1 = fa1;
+#pragma unroll
+    for (int j = 1; j <= NS; j++) c1 = M == j ? X[j - 1] : c1;
+    return c1;
+}
+
+template <bool VIT, bool TILED>
+__global__ __launch_bounds__(SH_MAP_NTH) void k_map_edits(ShMapEditsArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float sh_me_cols[];      /* [2][SH_ME_CH][NRP] */
+    const ShMapEditsRead r = a.rd[blockIdx.x];
+    const int L = r.nbase, K = a.k, n = L - K + 1, NB = r.nblock, tid = threadIdx.x;
+    const int i0 = blockIdx.y * SH_MAP_NTH;
+    if (i0 > L) return;                                      /* (uniform) */
+    const bool mine = i0 + tid <= L;
+    const int i = min(i0 + tid, L);
+    const int NP = (a.nr + 3) >> 2, NRP = NP * 4, STAY = a.nr - 1;
+    const float stay_pen = a.stay_pen, skip_pen = a.skip_pen, local_pen = a.local_pen;
+    const long long P = r.pitch;
+    const float *const F = a.rows + r.rows, *const G = F + (long long)(NB + 1) * P;
+    /* what the three kinds share: the prefix's states, the suffix's candidates */
+    const int A = max(i - K + 1, 0);
+    const float *const FA1 = F + max(A - 1, 0), *const FA2 = F + max(A - 2, 0), *const FSp = F + n;
+    const float *const GA = G + min(i, n - 1), *const GB = G + min(i + 1, n - 1), *const GC = G + min(i + 2, n - 1);
+    const int *const st = a.seq + r.seq, *const bs = a.seq + r.bases;
+    const int sA = st[min(i, n - 1)], sB = st[min(i + 1, n - 1)], sC = st[min(i + 2, n - 1)];
+    /* sub and del: the suffix begins at min(i + 1, n); ins: at min(i, n) */
+    const int j0s = min(i + 1, n), j0i = min(i, n);
+    const int Bs = n - j0s, Bi = n - j0i;
+    const int Js = j0s, Jd = j0s - 1, Ji = j0i + 1;
+    const int Ms = Js - A, Md = max(Jd - A, 0), Mi = Ji - A;
+    int cs[SH_ME_K], ci[SH_ME_K], cd[SH_ME_K - 1], cw[SH_ME_K], zw[SH_ME_K - 1];
+#pragma unroll
+    for (int m = 0; m < SH_ME_K; m++) {
+        int vs = 0, vi = 0, vd = 0;
+#pragma unroll
+        for (int j = 0; j < SH_ME_K; j++)
+            if (j < K) {
+                vs = vs * 4 + sh_me_base(0, A + m + j, i, bs, L);
+                vd = vd * 4 + sh_me_base(1, A + m + j, i, bs, L);
+                vi = vi * 4 + sh_me_base(2, A + m + j, i, bs, L);
+            }
+        const int j = i - (A + m);                           /* where the new base stands in this k-mer */
+        cs[m] = vs; ci[m] = vi;
+        cw[m] = (j >= 0 && j < K) ? 1 << (2 * (K - 1 - j)) : 0;
+        if (m < SH_ME_K - 1) { cd[m] = vd; zw[m] = 0; }
+    }
+    ShMapLocalArgs la{};
+    la.post = a.post; la.E = a.E; la.sums = a.sums; la.pstride = a.pstride; la.nr = a.nr; la.nchunk = a.nchunk; la.min_prob = a.min_prob;
+    ShMapLocalWin lw{};
+    lw.post = r.post; lw.lane = r.lane;
+    const ShMapLocalCol<TILED> cl(la, lw);
+    int pq[SH_MAPL_PIECES];
+#pragma unroll
+    for (int k = 0; k < SH_MAPL_PIECES; k++) pq[k] = min(tid + k * SH_MAP_NTH, NP - 1);
+    float4 q[SH_ME_CH][SH_MAPL_PIECES];
+    float qs[SH_ME_CH];
+    auto fetch = [&](int c) {
+#pragma unroll
+        for (int u = 0; u < SH_ME_CH; u++) {
+            const int blk = min(c * SH_ME_CH + u, NB - 1);
+            qs[u] = cl.scale(blk);
+#pragma unroll
+            for (int k = 0; k < SH_MAPL_PIECES; k++) q[u][k] = cl.piece(blk, pq[k]);
+        }
+    };
+    auto stage = [&](int buf) {                              /* (a piece past the column's last is its last again: the same words twice) */
+#pragma unroll
+        for (int u = 0; u < SH_ME_CH; u++)
+#pragma unroll
+            for (int k = 0; k < SH_MAPL_PIECES; k++)
+                *(float4 *)(sh_me_cols + (long long)(buf * SH_ME_CH + u) * NRP + 4 * pq[k]) = cl.fin(q[u][k], qs[u]);
+    };
+    fetch(0);
+    stage(0);
+    fetch(1);
+    /* block t reads the prefix's cells of entry t and the suffix's of entry t + 1 */
+    float fa1[SH_ME_D], fa2[SH_ME_D], fs[SH_ME_D], gA[SH_ME_D], gB[SH_ME_D], gC[SH_ME_D];
+    auto rows_of = [&](int t, int d) {
+        const long long e0 = (long long)min(t, NB) * P, e1 = (long long)min(t + 1, NB) * P;
+        fa1[d] = FA1[e0]; fa2[d] = FA2[e0]; fs[d] = FSp[e0];
+        gA[d] = GA[e1]; gB[d] = GB[e1]; gC[d] = GC[e1];
+    };
+#pragma unroll
+    for (int d = 0; d < SH_ME_D; d++) rows_of(d, d);
+    float Xs[4][SH_ME_K], Xi[4][SH_ME_K], Xd[SH_ME_K - 1], sub[4], ins[4];
+    float del = -SH_MAP_BIG;
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        sub[c] = -SH_MAP_BIG;
+        ins[c] = -SH_MAP_BIG;
+#pragma unroll
+        for (int m = 0; m < SH_ME_K; m++) { Xs[c][m] = -SH_MAP_BIG; Xi[c][m] = -SH_MAP_BIG; }
+    }
+#pragma unroll
+    for (int m = 0; m < SH_ME_K - 1; m++) Xd[m] = -SH_MAP_BIG;
+    __syncthreads();
+    const int nchunk = (NB + SH_ME_CH - 1) / SH_ME_CH;
+    for (int c0 = 0; c0 < nchunk; c0++) {
+        const float *const tc = sh_me_cols + (long long)((c0 & 1) * SH_ME_CH) * NRP;
+        for (int u0 = 0; u0 < SH_ME_CH; u0 += SH_ME_D) {
+#pragma unroll
+            for (int d = 0; d < SH_ME_D; d++) {
+                const int u = u0 + d, t = c0 * SH_ME_CH + u;
+                if (t >= NB) break;                          /* (uniform) */
+                const float *const col = tc + (long long)u * NRP;
+                const float lps = col[STAY];
+                const float ls = VIT ? fmaxf(-local_pen, lps) : sh_lse(-local_pen, lps);
+                const float leA = col[sA], leB = col[sB], leC = col[sC];
+                sh_me_edit<VIT, SH_ME_K - 1>(Xd, del, cd, zw, 0, A, Md, Jd, Bs, fa2[d], fa1[d], fs[d], col, lps, ls, leB, leC, gB[d], gC[d], stay_pen,
+                                             skip_pen, local_pen);
+#pragma unroll
+                for (int c = 0; c < 4; c++) {
+                    sh_me_edit<VIT, SH_ME_K>(Xs[c], sub[c], cs, cw, c, A, Ms, Js, Bs, fa2[d], fa1[d], fs[d], col, lps, ls, leB, leC, gB[d], gC[d],
+                                             stay_pen, skip_pen, local_pen);
+                    sh_me_edit<VIT, SH_ME_K>(Xi[c], ins[c], ci, cw, c, A, Mi, Ji, Bi, fa2[d], fa1[d], fs[d], col, lps, ls, leA, leB, gA[d], gB[d],
+                                             stay_pen, skip_pen, local_pen);
+                }
+                rows_of(t + SH_ME_D, d);
+            }
+        }
+        stage((c0 + 1) & 1);                                 /* chunk c0 + 1; that buffer was read last in chunk c0 - 1, a barrier ago */
+        fetch(c0 + 2);
+        __syncthreads();
+    }
+    if (!mine) return;
+    /* no suffix: k_map's end rule on the edit's last column and END's chain */
+    const float fN = FA1[(long long)NB * P];
+    auto end = [&](float x, float y) { return VIT ? fmaxf(x, y) : sh_lse(x, y); };
+    float *const out = a.res + r.res;
+    if (Bi == 0) {
+#pragma unroll
+        for (int c = 0; c < 4; c++) ins[c] = end(sh_me_last<SH_ME_K>(Xi[c], Mi, fN), ins[c]);
+    }
+    *(float4 *)(out + 4 * (long long)L + 4 * (long long)i) = make_float4(ins[0], ins[1], ins[2], ins[3]);
+    if (i < L) {
+        if (Bs == 0) {
+#pragma unroll
+            for (int c = 0; c < 4; c++) sub[c] = end(sh_me_last<SH_ME_K>(Xs[c], Ms, fN), sub[c]);
+            del = end(sh_me_last<SH_ME_K - 1>(Xd, Md, fN), del);
+        }
+        *(float4 *)(out + 4 * (long long)i) = make_float4(sub[0], sub[1], sub[2], sub[3]);
+        out[8 * (long long)L + 4 + i] = del;
+    }
+}
+
+#endif /* SH_MAP_EDITS_H */
