@@ -48,8 +48,11 @@
  *   sh_eng_map.inc       block-based mapping of posteriors to sequences (per-read and batched)
  *   sh_eng_map_pack.inc  one read against many candidate sequences, packed into workgroups (per-read and batched)
  *   sh_eng_map_crf_pack.inc  one flip-flop (CRF) read against many candidate sequences, packed into workgroups (per-read and batched)
- *   sh_eng_crf_edits.inc every single-base edit of a sequence scored against a flip-flop (CRF) read: forward rows, backward rows, one combining pass (per-read and batched)
- *   sh_eng_map_edits.inc every single-base edit of a sequence scored against a transducer read: forward rows, backward rows, one combining pass (per-read and batched)
+ *   sh_eng_edits.inc     what the two engines that score every single-base edit of a sequence share: forward rows, backward rows and one combining
+ *                        pass per launch for a family's EditsTraits (edits_launch), the cut by a byte budget (edits_run), the per-read symbol's
+ *                        tail (edits_one), the batch call (edits_batch), the result type's release, form counts and timing
+ *   sh_eng_crf_edits.inc the EditsTraits of the flip-flop (CRF) models (k_crf_edits_rows, k_crf_edits), their checks and entry points
+ *   sh_eng_map_edits.inc the EditsTraits of the transducer models (k_map_edits_rows, k_map_edits), their checks and entry points
  *   sh_eng_crf_find.inc  short sequences searched inside flip-flop (CRF) reads, packed into workgroups (per-read and batched)
  *   sh_eng_map_crf_local.inc  flip-flop (CRF) reads mapped into a longer sequence, one workgroup per window (per-read and batched)
  *   sh_eng_map_local.inc      transducer reads mapped into a longer sequence, one workgroup per window, the posterior column staged in LDS (per-read and batched)
@@ -350,6 +353,11 @@ struct DpBufs {
     }
 };
 
+/* What an engine keeps for one family of "every single-base edit" (sh_eng_edits.inc): a launch's records, codes, row matrices, results and base scores,
+ * results | base scores on the host (grow-only); budget: row and result bytes one launch of the three kernels may hold (debug options
+ * "crf_edits_budget_kb" / "map_edits_budget_kb"; 0: one launch per launch group); the last call's kernels by events, its launches and their row bytes. */
+struct EditsState { DBuf rd, seq, rows, res, base; HBuf h; size_t budget = 0; double ms[3] = {0, 0, 0}; size_t launches = 0, row_bytes = 0; };
+
 /* fields of scrappie_hip_timing (and two figures of SH_HOST_STAMP) that a span between two profiling marks adds to: resolve_spans (sh_eng_load.inc) */
 enum SpanField { F_CONV = 0, F_AFFINE, F_GRU, F_FF, F_DECODE, F_BACKTRACE, F_TOTAL, F_FUSED, F_STITCH,
                  F_WAIT, F_LEAD,      /* how long the main stream waited for the prologue; how long before that the convolution had ended */
@@ -523,12 +531,7 @@ struct scrappie_hip_engine {
     int crf_find_cells = -1;         /* cells a pack of motifs holds (debug option "crf_find_cells"; -1: the default) */
     DBuf d_mcp_rd, d_mcp_cell, d_mcp_score; HBuf h_mcp;      /* candidates of flip-flop reads in packs (sh_eng_map_crf_pack.inc): the packs, their cell words, scores; scores on the host */
     int map_crf_pack_cells = -1;     /* cells a pack of candidates of a flip-flop read holds (debug option "map_crf_pack_cells"; 0: every candidate through k_map_crf, -1: the default) */
-    DBuf d_ce_rd, d_ce_seq, d_ce_rows, d_ce_res, d_ce_base; HBuf h_ce;      /* every single-base edit of a sequence against a flip-flop read (sh_eng_crf_edits.inc): records, codes, the row matrices, results, base scores; results on the host */
-    size_t dbg_crf_edits_budget = 0; /* row and result bytes one launch of the three edit kernels may hold (debug option "crf_edits_budget_kb"; 0: one launch per launch group) */
-    DBuf d_me_rd, d_me_seq, d_me_rows, d_me_res, d_me_base; HBuf h_me;      /* every single-base edit of a sequence against a transducer read (sh_eng_map_edits.inc): records, state and base codes, the row matrices, results, base scores; results on the host */
-    size_t dbg_map_edits_budget = 0; /* row and result bytes one launch of the three transducer edit kernels may hold (debug option "map_edits_budget_kb"; 0: one launch per launch group) */
-    double map_edits_ms[3] = {0, 0, 0}; size_t map_edits_launches = 0, map_edits_row_bytes = 0;      /* scrappie_hip_map_edits_timing: the last call's kernels by events, its launches and their row bytes */
-    double crf_edits_ms[3] = {0, 0, 0}; size_t crf_edits_launches = 0, crf_edits_row_bytes = 0;      /* scrappie_hip_crf_edits_timing: the last call's kernels by events, its launches and their row bytes */
+    EditsState crf_edits, map_edits; /* every single-base edit of a sequence against a flip-flop read and against a transducer read (sh_eng_edits.inc): one each, so that either family's timing outlives the other's calls */
     int map_crf_local_stride = -1;   /* start cells a window of k_map_crf_local owns (debug option "map_crf_local_stride"; 0: one window, -1: the default) */
     double map_ms[3] = {0, 0, 0};    /* scrappie_hip_map_batch: network + S1, k_map, k_map_walk + results, summed over the last call's launch groups */
     DpBufs dp_sq; DBuf d_sq_sig, d_sq_tab;       /* squiggle matching (sh_eng_squig.inc): the records' buffers; signals, tables */
@@ -685,6 +688,7 @@ extern "C" scrappie_hip_params scrappie_hip_default_params(void) {
 #include "sh_eng_map.inc"      /* block-based mapping (sh_map.h): map_to_sequence_* on the process-default engine, scrappie_hip_map_batch */
 #include "sh_eng_map_pack.inc"      /* one read against many candidate sequences (sh_map_pack.h): scrappie_hip_map_multi_batch, scrappie_hip_map_post_multi */
 #include "sh_eng_map_crf_pack.inc"      /* one flip-flop read against many candidate sequences (sh_map_crf_pack.h): scrappie_hip_map_crf_multi_batch, scrappie_hip_map_trans_multi */
+#include "sh_eng_edits.inc"      /* shared by the two below: EditsTraits, EditsJob, edits_launch / edits_run, edits_one, edits_batch, scrappie_hip_free_edits_results */
 #include "sh_eng_crf_edits.inc"      /* every single-base edit of a sequence against a flip-flop read (sh_crf_edits.h): scrappie_hip_map_crf_edits_batch, map_crf_edits */
 #include "sh_eng_map_edits.inc"      /* every single-base edit of a sequence against a transducer read (sh_map_edits.h): scrappie_hip_map_edits_batch, map_post_edits */
 #include "sh_eng_crf_find.inc"      /* short sequences searched inside flip-flop reads, packed into workgroups (sh_crf_find.h): find_crf_sequences_viterbi, scrappie_hip_find_batch */

@@ -47,8 +47,8 @@ extern "C" int scrappie_hip_debug_option(scrappie_hip_engine *e, const char *nam
     else if (!strcmp(name, "squig_local_stride")) e->squig_local_stride = value < 0 ? -1 : value;      /* entry positions per window of k_squig_local (0: one window; -1: the default) */
     else if (!strcmp(name, "squig_pack_cells")) e->squig_pack_cells = value < 0 ? -1 : value;      /* cells per pack of candidate squiggles of k_squig_pack (0: every candidate through k_squig; -1: the default) */
     else if (!strcmp(name, "squig_pack_lone")) e->squig_pack_lone = value != 0;      /* 1: a candidate alone in its pack runs in k_squig_pack (0, the default: it takes k_squig) */
-    else if (!strcmp(name, "crf_edits_budget_kb")) e->dbg_crf_edits_budget = value > 0 ? (size_t)value << 10 : 0;      /* row and result bytes per launch of the three edit kernels (0: one launch per launch group) */
-    else if (!strcmp(name, "map_edits_budget_kb")) e->dbg_map_edits_budget = value > 0 ? (size_t)value << 10 : 0;      /* the same for the three transducer edit kernels */
+    else if (!strcmp(name, "crf_edits_budget_kb")) e->crf_edits.budget = value > 0 ? (size_t)value << 10 : 0;      /* row and result bytes per launch of the three edit kernels (0: one launch per launch group) */
+    else if (!strcmp(name, "map_edits_budget_kb")) e->map_edits.budget = value > 0 ? (size_t)value << 10 : 0;      /* the same for the three transducer edit kernels */
     else if (!strcmp(name, "events_budget_samples")) e->dbg_events_budget = value > 0 ? (size_t)value : 0;      /* sample slots per event-detection launch (0: from free memory) */
     else return set_err("debug_option: unknown option '%s'", name);
     return 0;

@@ -1087,6 +1087,22 @@ size_t scrappie_hip_crf_edits_pitch(size_t seqlen) { return (seqlen + 2 + 15) / 
 static size_t crf_edits_res_floats(size_t seqlen) { return (9 * seqlen + 4 + 3) / 4 * 4; }
 size_t scrappie_hip_crf_edits_row_bytes(size_t seqlen, size_t nblock) { return 3 * (nblock + 1) * scrappie_hip_crf_edits_pitch(seqlen) * 4; }
 
+/* The layout that the two planners of the edit engines below share, k 0 for the flip-flop family: read i takes its pitch and row floats of
+ * its family, the reads lie one behind the other in input order in the row buffer and in the result buffer.  Returns the floats of the
+ * row buffer; *res_floats (may be NULL): those of the result buffer. */
+static long long edits_plan(const size_t *seqlen, const size_t *nblock, size_t n, size_t k, int *pitch, long long *rows, long long *res, long long *res_floats) {
+    long long nrow = 0, nres = 0;
+    for (size_t i = 0; i < n; i++) {
+        pitch[i] = (int)(k ? scrappie_hip_map_edits_pitch(seqlen[i], k) : scrappie_hip_crf_edits_pitch(seqlen[i]));
+        rows[i] = nrow;
+        res[i] = nres;
+        nrow += (long long)((k ? scrappie_hip_map_edits_row_bytes(seqlen[i], k, nblock[i]) : scrappie_hip_crf_edits_row_bytes(seqlen[i], nblock[i])) / 4);
+        nres += (long long)crf_edits_res_floats(seqlen[i]);
+    }
+    if (res_floats) *res_floats = nres;
+    return nrow;
+}
+
 /* Reads of seqlen[i] bases and nblock[i] blocks in one launch, in input order: pitch[i], rows[i] -- the float offset of read i's F_B
  * in the launch's row buffer; F_S lies (nblock[i] + 1) * pitch[i] floats behind it and G_B as many behind F_S -- and res[i], the
  * float offset of its results in the result buffer.  Both offsets are multiples of 4 floats (16 bytes); no two reads overlap.
@@ -1095,16 +1111,7 @@ long long scrappie_hip_crf_edits_plan(const size_t *seqlen, const size_t *nblock
                                       long long *res_floats) {
     if (res_floats) *res_floats = 0;
     if (!seqlen || !nblock || !pitch || !rows || !res) return 0;
-    long long nrow = 0, nres = 0;
-    for (size_t i = 0; i < n; i++) {
-        pitch[i] = (int)scrappie_hip_crf_edits_pitch(seqlen[i]);
-        rows[i] = nrow;
-        res[i] = nres;
-        nrow += (long long)(scrappie_hip_crf_edits_row_bytes(seqlen[i], nblock[i]) / 4);
-        nres += (long long)crf_edits_res_floats(seqlen[i]);
-    }
-    if (res_floats) *res_floats = nres;
-    return nrow;
+    return edits_plan(seqlen, nblock, n, 0, pitch, rows, res, res_floats);
 }
 
 /* Every single-base edit of a sequence against a transducer read (k_map_edits_rows, k_map_edits, sh_map_edits.h): what a read of L
@@ -1132,16 +1139,7 @@ long long scrappie_hip_map_edits_plan(const size_t *seqlen, const size_t *nblock
     if (k == 0) return -1;
     for (size_t i = 0; i < n; i++)
         if (seqlen[i] < k) return -1;
-    long long nrow = 0, nres = 0;
-    for (size_t i = 0; i < n; i++) {
-        pitch[i] = (int)scrappie_hip_map_edits_pitch(seqlen[i], k);
-        rows[i] = nrow;
-        res[i] = nres;
-        nrow += (long long)(scrappie_hip_map_edits_row_bytes(seqlen[i], k, nblock[i]) / 4);
-        nres += (long long)crf_edits_res_floats(seqlen[i]);
-    }
-    if (res_floats) *res_floats = nres;
-    return nrow;
+    return edits_plan(seqlen, nblock, n, k, pitch, rows, res, res_floats);
 }
 
 /* the library defines it (scrappie_hip.hip); weak, so that this file also links into the host-only builds of the tests */

@@ -1,5 +1,6 @@
 """The two paths that every engine on a launch group's posterior or transitions shares (sh_eng_post.inc): the way out of a
-failed launch, and the refusal of a read whose signal leaves the supported range -- each through every family's entry point."""
+failed launch, and the refusal of a read whose signal leaves the supported range -- each through every family's entry point.
+Last, the two edits families behind their one driver (sh_eng_edits.inc): each keeps its own counters and timing."""
 import numpy as np
 import pytest
 
@@ -127,3 +128,49 @@ def test_out_of_range_read_costs_only_itself(eng, good_and_huge, name):
     assert fam["empty"](mixed[2]), mixed[2]
     assert "read 2" in err and "outside the supported range" in err, err
     _same(mixed[:2] + mixed[3:], alone)
+
+
+def test_edits_families_keep_their_own_state(eng):
+    """the two families of "every single-base edit" run through one driver (sh_eng_edits.inc) and keep form counters, buffers,
+    budget and timing each of its own: a flip-flop call of three launches (a budget of 1 KB: every read goes alone) and a
+    transducer call of one move only their own family's counters, either's timing still reports its own last call after the
+    other's, and the results do not depend on which family ran first"""
+    rng = np.random.default_rng(97)
+    sigs = [synth.medmad_normalise(synth.synthetic_signal(n, 700 + i)) for i, n in enumerate((900, 1300, 1100))]
+    seqs = [_bases(40, rng) for _ in sigs]
+    row_bytes = sa.lib().scrappie_hip_crf_edits_row_bytes, sa.lib().scrappie_hip_map_edits_row_bytes
+    crf_rows = sum(row_bytes[0](40, len(eng.posterior(x, "rnnrf_r94"))) for x in sigs)
+    map_rows = sum(row_bytes[1](40, 5, len(eng.posterior(x, "rgrgr_r94"))) for x in sigs[:2])
+    moved = lambda now, before: {k: now[k] - before[k] for k in now if now[k] != before[k]}
+
+    def call_a():
+        crf, tr = sa.crf_edits_form_counts(), sa.map_edits_form_counts()
+        assert len(crf) == 12 and len(tr) == 12
+        eng.debug_option("crf_edits_budget_kb", 1)
+        try:
+            res = eng.score_edits(sigs, seqs, viterbi=True)
+        finally:
+            eng.debug_option("crf_edits_budget_kb", 0)
+        assert moved(sa.crf_edits_form_counts(), crf) == {("rows", True, True, False): 3, ("rows", True, True, True): 3, ("edits", True, True): 3}
+        assert moved(sa.map_edits_form_counts(), tr) == {}
+        return res
+
+    def call_b():
+        crf, tr = sa.crf_edits_form_counts(), sa.map_edits_form_counts()
+        res = eng.score_edits_transducer(sigs[:2], seqs[:2], viterbi=False)
+        assert moved(sa.map_edits_form_counts(), tr) == {("rows", False, True, False): 1, ("rows", False, True, True): 1, ("edits", False, True): 1}
+        assert moved(sa.crf_edits_form_counts(), crf) == {}
+        return res
+
+    def timing():
+        a, b = eng.crf_edits_timing(), eng.map_edits_timing()
+        assert (a["launches"], a["row_bytes"]) == (3, crf_rows), a
+        assert (b["launches"], b["row_bytes"]) == (1, map_rows), b
+
+    first = call_a(), call_b()
+    assert all(np.isfinite(r[0]) and np.any(np.isfinite(r[1])) for res in first for r in res)
+    timing()                                                # read after B: A's three launches are still the flip-flop family's last call
+    again_b = call_b()
+    again_a = call_a()
+    timing()
+    _same((again_a, again_b), first)
