@@ -783,6 +783,64 @@ void scrappie_hip_crf_edits_form_counts(uint64_t forms[12]);
  * *row_bytes (may be NULL): the row bytes of all of them */
 void scrappie_hip_crf_edits_timing(scrappie_hip_engine *e, double ms[3], size_t *launches, size_t *row_bytes);
 
+/* The same in a band (the kernels' banded forms, sh_crf_edits.h): a read that covers a window lies on a narrow diagonal of the lattice,
+ * and rows, traffic and sums are proportional to the cells visited.
+ *
+ * Definition (tests/test_crf_edits_band_cpu.py restates it in numpy).  A band is what scrappie_hip_map_batch takes for a CRF model: low,
+ * high of nblock + 1 entries, cell p (bases emitted so far, 0 .. L) of entry t admissible iff low[t] <= p < high[t]; it must pass
+ * scrappie_hip_map_crf_bounds_sane.  The definition above holds with these changes and no other:
+ *   F_B, F_S, G_B and G_S hold -BIG at every cell outside the band of its entry: F_B[0][1] = 0 only where high[0] > 1, a cell inside the
+ *   band is computed by the recursion from the masked row of the entry before (behind), a cell outside is -BIG.  Column L + 1 of G stays
+ *   -BIG throughout.  The recursions, the candidate order, mx, the end rule and the NAN rule are unchanged.
+ *   The new base's own cells X_B, X_S carry NO band: a band is given in the coordinates of the original sequence and the new cell has
+ *   none there.  sub[i][c] and ins[i][c] go on sharing X.
+ * Consequences:
+ *   Equivalence.  An edit's score is the score of the banded dynamic programme on the edited sequence in which every cell inherited from
+ *     the original -- the prefix's cells 0 .. i keep their index, the suffix's cells their index in the original -- keeps its original
+ *     cell's band and the new base's cell (i + 1 of the edited sequence) is free at every entry.
+ *   base is map_crf_to_sequence_viterbi_banded / _forward_banded's score for the same band, bit for bit.
+ *   Full band.  With low[t] = 0 and high[t] = L + 1 at every entry every output equals map_crf_edits' bit for bit, Viterbi and forward:
+ *     the banded forms run through the same cell code (sh_map_crf_cell, sh_ce_mx, sh_ce_end) in the same order.
+ *   Identity substitution.  sub[i][seq[i]] is computed as any other substitution: its cell i + 1 is the new base's and free, so it may
+ *     EXCEED base where the band binds on cell i + 1.
+ *   Ends.  A tight band can make an edit at either end NAN -- del[L - 1] where low[nblock] == L: the deletion closes on cell L - 1 of
+ *     entry nblock.  That is a result, not an error; the caller chooses the half-width.
+ * Rows on the device: an entry's row holds its band's cells alone, cell p of entry t at float p - low[t], in rows of one pitch per read:
+ * the widest entry's cells and one slot for the stores of threads without a cell, rounded up to 16 floats
+ * (scrappie_hip_crf_edits_band_pitch); three matrices of nblock + 1 such rows (scrappie_hip_crf_edits_band_row_bytes).  The score rows of
+ * k_crf_edits_rows stay in LDS by k_map_crf's formula, so the limit stays scrappie_hip_map_crf_lds_max_seq() bases.  k_crf_edits walks,
+ * per workgroup of 256 positions, only the entries at which one of its positions can be alive.
+ *
+ * scrappie_hip_map_crf_edits_banded_batch: as scrappie_hip_map_crf_edits_batch (same results, same free function, the network once per
+ * launch group, three launches); targets[i].poslow / poshigh hold nblock + 1 entries each for the read's nblock, or are both NULL: the
+ * full band, run through the unbanded forms.  A read's cost in the cut into launch groups and under "crf_edits_budget_kb" is its banded
+ * row bytes.  A band that is not valid for the read's block count (an array made for another block count is not) gets NAN for that read
+ * and the first reason as the error text; its neighbours are scored.  A transducer model: -1.  scrappie_hip_crf_edits_timing covers the
+ * call, row_bytes the bytes the launches kept.  scrappie_hip_map_crf_edits_batch itself goes on refusing bands.
+ * map_crf_edits_banded: a batch of one on a host matrix and the process-default engine, as map_crf_edits; low and high are required. */
+int scrappie_hip_map_crf_edits_banded_batch(scrappie_hip_engine *e, int model, const raw_table *reads, const scrappie_hip_map_target *targets, size_t n,
+                                            const scrappie_hip_params *p, int viterbi, scrappie_hip_edits_result *out);
+int map_crf_edits_banded(const_scrappie_matrix trans, const int *seq, size_t seqlen, const size_t *low, const size_t *high, int viterbi, float *base,
+                         float *sub, float *del, float *ins);
+/* Host only.  The band of half-width `halfwidth` cells around a Viterbi path of k_map_crf (path[t], t = 0 .. nblock: the index of the last
+ * base emitted through entry t, -1 while none): with cnt = path[t] + 1, low[t] = max(cnt - halfwidth, 0) -- and low[0] = 0 whatever the
+ * half-width, as every band begins -- and high[t] = min(cnt + halfwidth + 1, seqlen + 1); nblock + 1 entries each.  The result always
+ * passes scrappie_hip_map_crf_bounds_sane and contains the path.  0, or -1 on a null or empty argument or what is no path of that
+ * sequence: a value outside -1 .. seqlen - 1 (at entry 0: outside -1 .. 0), a step down, a step above 1, path[nblock] != seqlen - 1. */
+int scrappie_hip_map_crf_path_band(const int *path, size_t nblock, size_t seqlen, size_t halfwidth, size_t *low, size_t *high);
+/* Host only (sh_host.c), as scrappie_hip_crf_edits_pitch / _row_bytes / _plan for reads in bands: pitch, the floats of an entry's row
+ * (0: a null argument); row_bytes, the three matrices; plan, with low[i] / high[i] read i's band of nblock[i] + 1 entries (either NULL:
+ * the read has none and takes the unbanded pitch). */
+size_t scrappie_hip_crf_edits_band_pitch(const size_t *low, const size_t *high, size_t nblock);
+size_t scrappie_hip_crf_edits_band_row_bytes(const size_t *low, const size_t *high, size_t nblock);
+long long scrappie_hip_crf_edits_band_plan(const size_t *seqlen, const size_t *nblock, const size_t *const *low, const size_t *const *high, size_t n,
+                                           int *pitch, long long *rows, long long *res, long long *res_floats);
+/* launches of each banded form in this process, indexed as scrappie_hip_crf_edits_form_counts, which counts the unbanded forms alone */
+void scrappie_hip_crf_edits_band_form_counts(uint64_t forms[12]);
+/* private (scratch) bytes per lane of each banded form, as the runtime reports them for the loaded kernels, indexed as the form counts (needs
+ * a device; -1: the runtime gave no answer).  The forms are built to need none. */
+void scrappie_hip_crf_edits_band_scratch(long long bytes[12]);
+
 /* Every single-base edit of a sequence scored against a read of a TRANSDUCER model in one pass (sh_eng_map_edits.inc; k_map_edits_rows,
  * k_map_edits, sh_map_edits.h): for the bases seq[0..L) the 4 L substitutions, the L deletions and the 4 (L + 1) insertions, numbered as
  * above, each the score map_to_sequence_viterbi / _forward give for the k-mer states of the edited sequence -- from one forward sweep,

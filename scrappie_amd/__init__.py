@@ -405,6 +405,20 @@ def lib():
     L.scrappie_hip_crf_edits_form_counts.argtypes = [C.POINTER(C.c_uint64)]
     L.scrappie_hip_crf_edits_timing.restype = None
     L.scrappie_hip_crf_edits_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), sp, sp]
+    L.scrappie_hip_map_crf_edits_banded_batch.argtypes = L.scrappie_hip_map_crf_edits_batch.argtypes
+    L.map_crf_edits_banded.argtypes = [PM, ip, C.c_size_t, sp, sp, C.c_int, fp, fp, fp, fp]
+    L.scrappie_hip_map_crf_path_band.argtypes = [ip, C.c_size_t, C.c_size_t, C.c_size_t, sp, sp]
+    L.scrappie_hip_crf_edits_band_pitch.restype = C.c_size_t
+    L.scrappie_hip_crf_edits_band_pitch.argtypes = [sp, sp, C.c_size_t]
+    L.scrappie_hip_crf_edits_band_row_bytes.restype = C.c_size_t
+    L.scrappie_hip_crf_edits_band_row_bytes.argtypes = [sp, sp, C.c_size_t]
+    L.scrappie_hip_crf_edits_band_plan.restype = C.c_longlong
+    L.scrappie_hip_crf_edits_band_plan.argtypes = [sp, sp, C.POINTER(sp), C.POINTER(sp), C.c_size_t, ip, C.POINTER(C.c_longlong),
+                                                   C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    L.scrappie_hip_crf_edits_band_form_counts.restype = None
+    L.scrappie_hip_crf_edits_band_form_counts.argtypes = [C.POINTER(C.c_uint64)]
+    L.scrappie_hip_crf_edits_band_scratch.restype = None
+    L.scrappie_hip_crf_edits_band_scratch.argtypes = [C.POINTER(C.c_longlong)]
     L.scrappie_hip_map_edits_batch.argtypes = L.scrappie_hip_map_crf_edits_batch.argtypes
     L.map_post_edits.argtypes = [PM, C.c_float, C.c_float, C.c_float, ip, C.c_size_t, C.c_int, fp, fp, fp, fp]
     L.scrappie_hip_map_edits_pitch.restype = C.c_size_t
@@ -1444,6 +1458,32 @@ def map_crf_diagonal_band(nblock, seq_len, halfwidth):
     return [lo, hi]
 
 
+def map_crf_path_band(path, seq_len, halfwidth):
+    """(low, high) uintp arrays, nblock + 1 entries each: the band of half-width `halfwidth` cells around a Viterbi path of a
+    flip-flop (CRF) model, as `map_trans_to_sequence(..., viterbi=True, path=True)` and `Engine.map_to_sequence(..., path=True)`
+    return it (path[t]: the index of the last base emitted through entry t, -1 while none) against `seq_len` bases
+    (scrappie_hip_map_crf_path_band): low = max(path + 1 - halfwidth, 0), low[0] = 0, high = min(path + 2 + halfwidth,
+    seq_len + 1); always a valid band that holds the path.  ValueError where `path` is no path of such a sequence."""
+    p = np.ascontiguousarray(path, dtype=np.int32)
+    if p.ndim != 1 or len(p) < 2 or halfwidth < 0:
+        raise ValueError("a path has nblock + 1 >= 2 entries, and a half-width is not negative")
+    lo, hi = np.zeros(len(p), dtype=np.uintp), np.zeros(len(p), dtype=np.uintp)
+    sp = C.POINTER(C.c_size_t)
+    if lib().scrappie_hip_map_crf_path_band(p.ctypes.data_as(C.POINTER(C.c_int)), len(p) - 1, seq_len, int(halfwidth), lo.ctypes.data_as(sp),
+                                            hi.ctypes.data_as(sp)) != 0:
+        raise ValueError("not a path of a sequence of %d bases: entries -1 .. %d, steps of 0 or 1, the last entry %d" % (seq_len, seq_len - 1, seq_len - 1))
+    return [lo, hi]
+
+
+def _crf_band(bands, nblock, seq_len):
+    """`bands` of one read as a (low, high) pair of contiguous uintp arrays: an int is the half-width of the diagonal band"""
+    if isinstance(bands, (int, np.integer)):
+        return map_crf_diagonal_band(nblock, seq_len, int(bands))
+    if len(bands) != 2:
+        raise ValueError('`bands` should be `None`, an integer, or length 2.')
+    return [np.ascontiguousarray(x, dtype=np.uintp) for x in bands]
+
+
 def map_trans_to_sequence(trans, sequence, viterbi=False, path=False, bands=None):
     """Global alignment of a read's transitions under a flip-flop (CRF) model (a `ScrappyMatrix` of 25 rows, as
     `calc_post(rt, model='rnnrf_r94')` gives) to a base sequence: decode_crf's recursion restricted to the paths that spell the
@@ -1567,6 +1607,22 @@ def crf_edits_form_counts():
     return _edits_form_counts(lib().scrappie_hip_crf_edits_form_counts)
 
 
+def crf_edits_band_form_counts():
+    """The same for the banded forms of the edit kernels (scrappie_hip_crf_edits_band_form_counts); `crf_edits_form_counts`
+    counts the unbanded forms alone."""
+    return _edits_form_counts(lib().scrappie_hip_crf_edits_band_form_counts)
+
+
+def crf_edits_band_scratch():
+    """Private (scratch) bytes per lane of each banded form, keyed as `crf_edits_band_form_counts` keys them, as the runtime reports
+    them for the loaded kernels (scrappie_hip_crf_edits_band_scratch; needs a GPU): the forms are built to need none."""
+    q = (C.c_longlong * 12)()
+    lib().scrappie_hip_crf_edits_band_scratch(q)
+    out = {('rows', bool(k & 4), bool(k & 2), bool(k & 1)): int(q[k]) for k in range(8)}
+    out.update({('edits', bool(k & 2), bool(k & 1)): int(q[8 + k]) for k in range(4)})
+    return out
+
+
 def map_edits_form_counts():
     """The same for the transducer edit kernels, k_map_edits_rows and k_map_edits (scrappie_hip_map_edits_form_counts)."""
     return _edits_form_counts(lib().scrappie_hip_map_edits_form_counts)
@@ -1592,6 +1648,31 @@ def crf_edits_plan(seqlens, nblocks):
     row to the next, the float offset of its three row matrices (F_B, F_S, G_B, each (nblock + 1) * pitch floats) and of its
     9 L + 4 results; the floats of the two buffers."""
     return _edits_plan(seqlens, nblocks, lib().scrappie_hip_crf_edits_plan)
+
+
+def crf_edits_band_row_bytes(low, high):
+    """Device bytes of the three row matrices of a read in the band (low, high), nblock + 1 entries each
+    (scrappie_hip_crf_edits_band_row_bytes): an entry's row holds its band's cells alone."""
+    lo, hi = (np.ascontiguousarray(x, dtype=np.uintp) for x in (low, high))
+    if len(lo) != len(hi) or len(lo) < 2:
+        raise ValueError("low and high hold nblock + 1 >= 2 entries each")
+    sp = C.POINTER(C.c_size_t)
+    return int(lib().scrappie_hip_crf_edits_band_row_bytes(lo.ctypes.data_as(sp), hi.ctypes.data_as(sp), len(lo) - 1))
+
+
+def crf_edits_band_plan(seqlens, bands):
+    """`crf_edits_plan` for reads in bands (scrappie_hip_crf_edits_band_plan): `bands[i]` is read i's (low, high), nblock + 1
+    entries each -- the block count is the band's.  The pitch is that of the band's widest entry."""
+    bands = [[np.ascontiguousarray(x, dtype=np.uintp) for x in b] for b in bands]
+    if len(bands) != len(seqlens) or any(len(b) != 2 or len(b[0]) != len(b[1]) or len(b[0]) < 2 for b in bands):
+        raise ValueError("one (low, high) pair of nblock + 1 >= 2 entries each per sequence length")
+    sp = C.POINTER(C.c_size_t)
+    n = len(bands)
+    lo, hi = (sp * max(n, 1))(), (sp * max(n, 1))()
+    for i, b in enumerate(bands):
+        lo[i], hi[i] = b[0].ctypes.data_as(sp), b[1].ctypes.data_as(sp)
+    return _edits_plan(seqlens, [len(b[0]) - 1 for b in bands],
+                       lambda a, nb, cnt, *rest: lib().scrappie_hip_crf_edits_band_plan(a, nb, lo, hi, cnt, *rest))
 
 
 def map_edits_plan(seqlens, nblocks, kmer_len):
@@ -1629,7 +1710,7 @@ def map_post_edits(post, seq, stay_pen=0, skip_pen=0, local_pen=4.0, viterbi=Tru
     return np.float32(base.value), sub.reshape(L, 4), dele[:L], ins.reshape(L + 1, 4)
 
 
-def map_trans_edits(trans, seq, viterbi=True):
+def map_trans_edits(trans, seq, viterbi=True, bands=None):
     """Every single-base edit of `seq` (a base string, or an array of base codes 0..3) scored against a read's transitions
     under a flip-flop (CRF) model (a `ScrappyMatrix` of 25 rows, as `calc_post(rt, model='rnnrf_r94')` gives) in one pass on
     the GPU (map_crf_edits: a forward sweep, a backward sweep, one combining pass).  Returns (base, sub, dele, ins): base is
@@ -1637,7 +1718,11 @@ def map_trans_edits(trans, seq, viterbi=True):
     sub[i][c], dele[i] and ins[i][c] what `map_trans_to_sequence` gives for `apply_edit(seq, 'sub' / 'del' / 'ins', i, c)` up to
     float32 rounding (an edit's score and base are different chains of additions: confirm chosen edits with
     `map_trans_to_sequences`, which is exact).  NaN: the edited sequence has more bases than the read has entries, or is empty;
-    everything is NaN, and `last_error()` says why, where `seq` cannot be scored (empty, not bases, too long for k_crf_edits)."""
+    everything is NaN, and `last_error()` says why, where `seq` cannot be scored (empty, not bases, too long for k_crf_edits).
+    `bands`: None, an int (half-width in cells of the diagonal band, as `map_trans_to_sequence` reads it) or a (low, high) pair of
+    nblock + 1 entries each, from `map_crf_path_band` for one: the edits are scored inside the band (map_crf_edits_banded) --
+    every cell of the original sequence keeps its band, the new base's own cell is free; base is then
+    `map_trans_to_sequence(..., bands=bands)`'s score; a band that is not valid is a ValueError."""
     if not isinstance(trans, ScrappyMatrix):
         raise TypeError('`trans` should be a ScrappyMatrix.')
     nblock, nstate = trans.shape
@@ -1648,8 +1733,19 @@ def map_trans_edits(trans, seq, viterbi=True):
     base = C.c_float(float('nan'))
     sub, dele, ins = (np.full(k, np.nan, dtype=np.float32) for k in (4 * L, max(L, 1), 4 * (L + 1)))
     fp = C.POINTER(C.c_float)
-    if lib().map_crf_edits(trans.data(), tgs[0].seq, L, 1 if viterbi else 0, C.byref(base), sub.ctypes.data_as(fp), dele.ctypes.data_as(fp),
-                           ins.ctypes.data_as(fp)) != 0:
+    if bands is not None and L > 0:
+        lo, hi = _crf_band(bands, nblock, L)
+        if len(lo) != nblock + 1 or len(hi) != nblock + 1:
+            raise ValueError('Supplied banding structure is not valid: nblock + 1 entries each.')
+        p_lo, p_hi = (x.ctypes.data_as(C.POINTER(C.c_size_t)) for x in (lo, hi))
+        if not lib().scrappie_hip_map_crf_bounds_sane(p_lo, p_hi, nblock, L):
+            raise ValueError('Supplied banding structure is not valid.')
+        rc = lib().map_crf_edits_banded(trans.data(), tgs[0].seq, L, p_lo, p_hi, 1 if viterbi else 0, C.byref(base), sub.ctypes.data_as(fp),
+                                        dele.ctypes.data_as(fp), ins.ctypes.data_as(fp))
+    else:
+        rc = lib().map_crf_edits(trans.data(), tgs[0].seq, L, 1 if viterbi else 0, C.byref(base), sub.ctypes.data_as(fp), dele.ctypes.data_as(fp),
+                                 ins.ctypes.data_as(fp))
+    if rc != 0:
         raise RuntimeError('An unknown error occurred while scoring edits: ' + last_error())
     return np.float32(base.value), sub.reshape(L, 4), dele[:L], ins.reshape(L + 1, 4)
 
@@ -1996,8 +2092,10 @@ class Prep(object):
         return {"gather_ms": t[0], "h2d_ms": t[1], "k_p0_ms": t[2]}
 
 
-def _score_edits(eng, fn, name, signals, sequences, model, viterbi, **params):
-    """one batch call of an edits engine: a shared sequence is encoded once; [(base, sub, dele, ins)]"""
+def _score_edits(eng, fn, name, signals, sequences, model, viterbi, bands=None, **params):
+    """one batch call of an edits engine: a shared sequence is encoded once; [(base, sub, dele, ins)].  `bands` (flip-flop models):
+    None, or per read None, an int or a (low, high) pair; the library reads nblock + 1 entries of each array, so a pair of any
+    other length goes in as nblock + 1 entries of an empty band, which it refuses for that read."""
     n = len(signals)
     if isinstance(sequences, str) or (len(sequences) and np.ndim(sequences[0]) == 0 and not isinstance(sequences[0], str)):
         sequences = [sequences] * n
@@ -2012,6 +2110,17 @@ def _score_edits(eng, fn, name, signals, sequences, model, viterbi, **params):
         if id(sq) not in made:
             made[id(sq)] = _crf_targets([sq])
         tgs[i].seq, tgs[i].seqlen = made[id(sq)][0][0].seq, made[id(sq)][0][0].seqlen
+    if bands is not None:
+        for i, b in enumerate(bands):
+            nblock, L = eng.read_blocks(model, len(keep[i])), int(tgs[i].seqlen)
+            if b is None or nblock <= 0 or L == 0:          # (a read too short or an empty sequence is refused by the library as it is)
+                continue
+            lo, hi = _crf_band(b, nblock, L)
+            if len(lo) != nblock + 1 or len(hi) != nblock + 1:
+                lo, hi = np.zeros(nblock + 1, dtype=np.uintp), np.zeros(nblock + 1, dtype=np.uintp)
+            keep += [lo, hi]
+            tgs[i].poslow = lo.ctypes.data_as(C.POINTER(C.c_size_t))
+            tgs[i].poshigh = hi.ctypes.data_as(C.POINTER(C.c_size_t))
     p = eng.default_params(**params)
     out = (_EditsResult * max(n, 1))()
     if fn(eng._h, h, rts, tgs, n, C.byref(p), 1 if viterbi else 0, out) != 0:
@@ -2566,7 +2675,22 @@ class Engine(object):
         lib().scrappie_hip_free_find_results(out, n)
         return res
 
-    def score_edits(self, signals, sequences, model='rnnrf_r94', viterbi=False, min_prob=1e-5, tempW=1.0, tempb=1.0):
+    @staticmethod
+    def _bands_per_read(bands, n):
+        """`bands` of score_edits as a list of None, an int or a (low, high) pair per read"""
+        if isinstance(bands, (int, np.integer)):
+            return [int(bands)] * n
+        bands = list(bands)
+        # an edge of a band: a sequence of numbers (a per-read entry is None, an int, or a pair of such sequences); decided from the
+        # first element alone, so that a ragged pair never reaches numpy
+        one = lambda b: b is not None and not isinstance(b, (int, np.integer)) and len(b) > 0 and isinstance(b[0], (int, float, np.number))
+        if len(bands) == 2 and one(bands[0]) and one(bands[1]):             # one (low, high) pair for all reads
+            return [bands] * n
+        if len(bands) != n:
+            raise ValueError("`bands`: None, an int, a (low, high) pair, or one of these per signal")
+        return bands
+
+    def score_edits(self, signals, sequences, model='rnnrf_r94', viterbi=False, min_prob=1e-5, tempW=1.0, tempb=1.0, bands=None):
         """Is any single-base edit of this sequence better than the sequence?  Each read (trimmed, normalised float32 signal)
         of a flip-flop (CRF) model against EVERY single-base edit of its sequence, batched (scrappie_hip_map_crf_edits_batch):
         the network and k_crf run once per read; a forward sweep, a backward sweep and one combining pass score all 9 L + 4
@@ -2574,9 +2698,18 @@ class Engine(object):
         cover --, or one per read.  Returns [(base, sub, dele, ins)] in input order as `map_trans_edits` gives them; with
         `viterbi=False` the scores are log-likelihoods, so `sum(r[1] - r[0] for r in res)` over the reads of a window is the
         log-likelihood ratio of every substitution.  A read or a sequence that cannot be scored has everything NaN
-        (`last_error()` names the first)."""
-        return _score_edits(self, lib().scrappie_hip_map_crf_edits_batch, "map_crf_edits_batch", signals, sequences, model, viterbi,
-                                 min_prob=min_prob, tempW=tempW, tempb=tempb)
+        (`last_error()` names the first).
+        `bands`: None (exactly the call above), an int (the diagonal band of that half-width per read, `map_crf_diagonal_band`),
+        a (low, high) pair of nblock + 1 entries each for all reads, or a list with None, an int or such a pair per read --
+        `map_crf_path_band(path, len(seq), halfwidth)` on the paths of `map_to_sequence(..., path=True)` makes them.  The edits
+        are then scored inside the bands (scrappie_hip_map_crf_edits_banded_batch): rows, traffic and time go with the cells in
+        the band; a read with None takes the unbanded kernels; a band that is not valid for its read (or not of nblock + 1
+        entries) leaves that read NaN."""
+        if bands is None:
+            return _score_edits(self, lib().scrappie_hip_map_crf_edits_batch, "map_crf_edits_batch", signals, sequences, model, viterbi,
+                                     min_prob=min_prob, tempW=tempW, tempb=tempb)
+        return _score_edits(self, lib().scrappie_hip_map_crf_edits_banded_batch, "map_crf_edits_banded_batch", signals, sequences, model, viterbi,
+                            bands=Engine._bands_per_read(bands, len(signals)), min_prob=min_prob, tempW=tempW, tempb=tempb)
 
     def score_edits_transducer(self, signals, sequences, model='rgrgr_r94', viterbi=False, stay_pen=0.0, skip_pen=0.0, local_pen=4.0,
                                min_prob=1e-5, tempW=1.0, tempb=1.0):

@@ -25,6 +25,8 @@
  * --edits (flip-flop models): EVERY single-base edit of the first record of a pair's FASTA scored against the pair's read.  All pairs
  * in ONE scrappie_hip_map_crf_edits_batch call (k_crf_edits_rows, k_crf_edits); per pair a header line and one line per position:
  * the base, then del, subA..T and insA..T as differences to the sequence's own Viterbi score.  Without the option nothing changes.
+ * --edits --band N: each read mapped to its record with the path first (scrappie_hip_map_batch), then the same table from ONE
+ * scrappie_hip_map_crf_edits_banded_batch call in the bands of half-width N around those paths.  Without --band nothing changes.
  * --kmer-edits (transducer models): the same table from ONE scrappie_hip_map_edits_batch call (k_map_edits_rows, k_map_edits), under
  * --stay, --skip and --localpen.
  */
@@ -98,6 +100,11 @@ static void seqmappy_usage(FILE *fh) {
           "                             A last line `L - - - - - - insA..T`: the insertions behind the last base.  An edit's score\n"
           "                             and S are different sums: differences of a few 1e-5 |S| are rounding; confirm an edit with\n"
           "                             --each-record.  Flip-flop (CRF) models only; not with any of the options above.\n"
+          "      --band=N               With --edits: map the read to the record first and score the edits inside the band of N cells\n"
+          "                             to either side of that path -- a cell of the sequence keeps its band, the edit's own new base\n"
+          "                             is free; S is the score inside the band.  The same table for a fraction of the cells; nan\n"
+          "                             also where the band leaves an edit no path (a small N at either end of the sequence).  A read\n"
+          "                             that cannot be mapped to the record has no path to band around: reported, not scored.\n"
           "      --kmer-edits           The table of --edits for a transducer model (the default rgrgr_r94 and its relatives), under\n"
           "                             --stay, --skip and --localpen: an edit of one base changes up to k consecutive k-mer states\n"
           "                             (nan: the edited sequence admits no path through the read, or has fewer than k bases).\n"
@@ -216,11 +223,38 @@ static void print_delta(FILE *out, float score, float base) {
     else fprintf(out, "\t%f", score - base);
 }
 
+/* --edits --band: the nb reads mapped to their sequences with the path in one scrappie_hip_map_batch call (k_map_crf), and around each path the band
+ * of that half-width (scrappie_hip_map_crf_path_band) as the target's poslow / poshigh.  Returns the 2 nb arrays to free -- low and high of entry m at
+ * [2 m], [2 m + 1]; a pair that cannot be mapped keeps no band (poslow stays NULL), and the caller reports it as not scored --, NULL where the call failed
+ * (scrappie_hip_last_error() says why). */
+static size_t **seqmappy_path_bands(scrappie_hip_engine *e, int h, const scrappie_hip_params *p, const raw_table *rts, scrappie_hip_map_target *tg,
+                                    size_t nb, size_t halfwidth) {
+    scrappie_hip_map_result *mp = calloc(nb, sizeof *mp);
+    size_t **bands = calloc(2 * nb, sizeof *bands);
+    if (!mp || !bands || scrappie_hip_map_batch(e, h, rts, tg, nb, p, 1, 1, mp) != 0) {
+        free(mp); free(bands);              /* (a failed call has released its results) */
+        return NULL;
+    }
+    for (size_t i = 0; i < nb; i++) {
+        if (!mp[i].path) continue;
+        size_t *lo = malloc((mp[i].nblock + 1) * sizeof *lo), *hi = malloc((mp[i].nblock + 1) * sizeof *hi);
+        if (lo && hi && scrappie_hip_map_crf_path_band(mp[i].path, mp[i].nblock, tg[i].seqlen, halfwidth, lo, hi) == 0) {
+            bands[2 * i] = lo; bands[2 * i + 1] = hi;
+            tg[i].poslow = lo; tg[i].poshigh = hi;
+        } else { free(lo); free(hi); }
+    }
+    scrappie_hip_free_map_results(mp, nb);
+    free(mp);
+    return bands;
+}
+
 /* --edits (klen 0) and --kmer-edits (klen: the bases of the transducer model's k-mer): every single-base edit of the first record of pair i's FASTA
- * against pair i's read, all pairs in one scrappie_hip_map_crf_edits_batch or scrappie_hip_map_edits_batch call */
+ * against pair i's read, all pairs in one scrappie_hip_map_crf_edits_batch or scrappie_hip_map_edits_batch call; band >= 0 (--band): the flip-flop
+ * table from scrappie_hip_map_crf_edits_banded_batch in the bands of that half-width around the reads' Viterbi paths */
 static int seqmappy_edits(scrappie_hip_engine *e, int h, const scrappie_hip_params *p, char **fasta, size_t npair, FILE *out,
-                          int trim_start, int trim_end, int varseg_chunk, float varseg_thresh, int klen) {
+                          int trim_start, int trim_end, int varseg_chunk, float varseg_thresh, int klen, long band) {
     const char *const opt = klen ? "--kmer-edits" : "--edits";
+    size_t **bands = NULL;                  /* --band (band >= 0): low and high of entry m at bands[2 m], bands[2 m + 1] */
     /* entry m of the batch is pair who[m]: a pair whose fasta or fast5 did not load is reported here and never reaches the engine */
     raw_table *rts = calloc(npair, sizeof *rts);
     scrappie_hip_map_target *tg = calloc(npair, sizeof *tg);
@@ -242,7 +276,12 @@ static int seqmappy_edits(scrappie_hip_engine *e, int h, const scrappie_hip_para
         codes[nb] = cd; tg[nb].seq = cd; tg[nb].seqlen = n; rts[nb] = rt; who[nb] = j;
         nb++;
     }
-    if (nb && (klen ? scrappie_hip_map_edits_batch(e, h, rts, tg, nb, p, 1, res) : scrappie_hip_map_crf_edits_batch(e, h, rts, tg, nb, p, 1, res)) != 0) {
+    int failed = 0;                         /* a batch call failed as a whole: its text is the engine's */
+    if (nb && band >= 0 && !(bands = seqmappy_path_bands(e, h, p, rts, tg, nb, (size_t)band))) failed = 1;
+    if (nb && !failed)
+        failed = (klen ? scrappie_hip_map_edits_batch(e, h, rts, tg, nb, p, 1, res) :
+                  band >= 0 ? scrappie_hip_map_crf_edits_banded_batch(e, h, rts, tg, nb, p, 1, res) : scrappie_hip_map_crf_edits_batch(e, h, rts, tg, nb, p, 1, res)) != 0;
+    if (failed) {
         fprintf(stderr, "scrappie: %s\n", scrappie_hip_last_error());
         rc = EXIT_FAILURE;
     } else {
@@ -253,6 +292,11 @@ static int seqmappy_edits(scrappie_hip_engine *e, int h, const scrappie_hip_para
                 if (tg[i].seqlen > maxL) fprintf(stderr, "scrappie: Failed to score the edits of \"%s\" for \"%s\": %zu bases are too long for %s (at most %zu: pass a window of the sequence)\n", fa, f5, tg[i].seqlen, opt, maxL);
                 else if (tg[i].seqlen < (size_t)klen) fprintf(stderr, "scrappie: Failed to score the edits of \"%s\" for \"%s\": %zu bases are shorter than the model's k-mer (%d)\n", fa, f5, tg[i].seqlen, klen);
                 else fprintf(stderr, "scrappie: Failed to score the edits of \"%s\" for \"%s\": the read cannot be run (too short for the model, or its signal is out of range)\n", fa, f5);
+                rc = EXIT_FAILURE;
+                continue;
+            }
+            if (band >= 0 && !tg[i].poslow) {   /* no path to build the band around: what the call scored for it is unbanded, and is not printed as --band's */
+                fprintf(stderr, "scrappie: Failed to score the edits of \"%s\" for \"%s\" in a band: the read cannot be mapped to the sequence (no admissible path), so there is no path for --band; not scored\n", fa, f5);
                 rc = EXIT_FAILURE;
                 continue;
             }
@@ -273,7 +317,8 @@ static int seqmappy_edits(scrappie_hip_engine *e, int h, const scrappie_hip_para
     }
     scrappie_hip_free_edits_results(res, nb);
     for (size_t i = 0; i < nb; i++) { free(codes[i]); free(rts[i].raw); free(rts[i].uuid); }
-    free(who); free(codes); free(res); free(tg); free(rts);
+    for (size_t i = 0; bands && i < 2 * nb; i++) free(bands[i]);
+    free(bands); free(who); free(codes); free(res); free(tg); free(rts);
     return rc;
 }
 
@@ -321,13 +366,14 @@ static int seqmappy_inside(scrappie_hip_engine *e, int h, int klen, const scrapp
 }
 
 int main_seqmappy(int argc, char **argv) {
-    enum { O_SEG = 256, O_T1, O_T2, O_LIC, O_MODEL, O_MFILE, O_DEV, O_ALL, O_INSIDE, O_FIND, O_WITHIN, O_EACH, O_EDITS, O_KEDITS };
+    enum { O_SEG = 256, O_T1, O_T2, O_LIC, O_MODEL, O_MFILE, O_DEV, O_ALL, O_INSIDE, O_FIND, O_WITHIN, O_EACH, O_EDITS, O_KEDITS, O_BAND };
     static const struct option lo[] = {
         {"localpen", 1, 0, 'l'}, {"min_prob", 1, 0, 'm'}, {"output", 1, 0, 'o'}, {"prefix", 1, 0, 'p'},
         {"segmentation", 1, 0, O_SEG}, {"skip", 1, 0, 's'}, {"stay", 1, 0, 'y'}, {"trim", 1, 0, 't'},
         {"temperature1", 1, 0, O_T1}, {"temperature2", 1, 0, O_T2}, {"licence", 0, 0, O_LIC}, {"license", 0, 0, O_LIC},
-        {"model", 1, 0, O_MODEL}, {"model-file", 1, 0, O_MFILE}, {"device", 1, 0, O_DEV}, {"all-records", 0, 0, O_ALL}, {"inside", 0, 0, O_INSIDE}, {"find", 0, 0, O_FIND}, {"within", 0, 0, O_WITHIN}, {"each-record", 0, 0, O_EACH}, {"edits", 0, 0, O_EDITS}, {"kmer-edits", 0, 0, O_KEDITS}, {"help", 0, 0, '?'}, {0, 0, 0, 0}};
+        {"model", 1, 0, O_MODEL}, {"model-file", 1, 0, O_MFILE}, {"device", 1, 0, O_DEV}, {"all-records", 0, 0, O_ALL}, {"inside", 0, 0, O_INSIDE}, {"find", 0, 0, O_FIND}, {"within", 0, 0, O_WITHIN}, {"each-record", 0, 0, O_EACH}, {"edits", 0, 0, O_EDITS}, {"kmer-edits", 0, 0, O_KEDITS}, {"band", 1, 0, O_BAND}, {"help", 0, 0, '?'}, {0, 0, 0, 0}};
     int all_records = 0, inside = 0, find = 0, within = 0, each_record = 0, edits = 0, kmer_edits = 0;
+    long band = -1;                         /* --band: the half-width in cells; -1: no band */
     /* defaults: scrappie_seqmappy.c:62-78 */
     scrappie_hip_params p = scrappie_hip_default_params();
     p.local_pen = 4.0f; p.min_prob = 1e-5f; p.stay_pen = 0.0f; p.skip_pen = 0.0f; p.tempW = 1.0f; p.tempb = 1.0f;
@@ -366,6 +412,12 @@ int main_seqmappy(int argc, char **argv) {
         case O_EACH: each_record = 1; break;
         case O_EDITS: edits = 1; break;
         case O_KEDITS: kmer_edits = 1; break;
+        case O_BAND: {
+            char *end = NULL;
+            band = strtol(optarg, &end, 10);
+            if (end == optarg || *end || band < 0) { fprintf(stderr, "scrappie: --band wants a half-width in cells, 0 or more\n"); return EXIT_FAILURE; }
+            break;
+        }
         default: seqmappy_usage(stderr); return EXIT_FAILURE;
         }
     }
@@ -373,6 +425,7 @@ int main_seqmappy(int argc, char **argv) {
     if (nargs <= 0) { seqmappy_usage(stderr); return EXIT_FAILURE; }
     if (nargs % 2) { fprintf(stderr, "scrappie: fast5 file is a required argument\n"); return EXIT_FAILURE; }    /* scrappie_seqmappy.c:153 */
     const size_t npair = (size_t)nargs / 2;
+    if (band >= 0 && !edits) { fprintf(stderr, "scrappie: --band is the band of --edits; it needs --edits\n"); return EXIT_FAILURE; }
     if (kmer_edits && (edits || all_records || inside || find || within || each_record)) {
         fprintf(stderr, "scrappie: --kmer-edits scores every single-base edit of the first record of a fasta; it cannot be combined with %s\n",
                 edits ? "--edits" : all_records ? "--all-records" : inside ? "--inside" : find ? "--find" : within ? "--within" : "--each-record");
@@ -436,7 +489,7 @@ int main_seqmappy(int argc, char **argv) {
     if (edits) {
         int rc = EXIT_FAILURE;
         if (!crf) fprintf(stderr, "scrappie: --edits scores reads of flip-flop (CRF) models only; \"%s\" is a transducer model\n", model);
-        else rc = seqmappy_edits(e, h, &p, fasta, npair, out, trim_start, trim_end, varseg_chunk, varseg_thresh, 0);
+        else rc = seqmappy_edits(e, h, &p, fasta, npair, out, trim_start, trim_end, varseg_chunk, varseg_thresh, 0, band);
         if (out != stdout) fclose(out);
         scrappie_hip_engine_destroy(e);
         return rc;
@@ -444,7 +497,7 @@ int main_seqmappy(int argc, char **argv) {
     if (kmer_edits) {
         int rc = EXIT_FAILURE;
         if (crf) fprintf(stderr, "scrappie: --kmer-edits scores reads of transducer models only; \"%s\" is a flip-flop (CRF) model (--edits)\n", model);
-        else rc = seqmappy_edits(e, h, &p, fasta, npair, out, trim_start, trim_end, varseg_chunk, varseg_thresh, klen);
+        else rc = seqmappy_edits(e, h, &p, fasta, npair, out, trim_start, trim_end, varseg_chunk, varseg_thresh, klen, -1);
         if (out != stdout) fclose(out);
         scrappie_hip_engine_destroy(e);
         return rc;

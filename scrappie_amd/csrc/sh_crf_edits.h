@@ -1,6 +1,7 @@
 /* sh_crf_edits.h -- part of sh_kernels.h (included from there, behind sh_map_crf_pack.h): EVERY single-base edit of a sequence scored
  * against a read of a flip-flop (CRF) model in one pass -- 3 L substitutions (and the L that change nothing), L deletions, 4 (L + 1)
- * insertions: what a polisher or a variant caller asks of a window.  Scores only, unbanded.
+ * insertions: what a polisher or a variant caller asks of a window.  Scores only; unbanded, or (the BAND instantiations, at the end of
+ * this comment) inside a band of k_map_crf's kind.
  *
  * The lattice is k_map_crf's (sh_map_crf.h states it): after entry t a path is in B[p] (entry t was base seq[p - 1]) or S[p] (a stay),
  * p bases emitted.  Every admissible path is in B[p] exactly once, at the entry that emits base p, so a path score splits there:
@@ -31,7 +32,15 @@
  * ahead, and keeps in registers the four X columns -- sub[i][c] and ins[i][c] share them -- and its nine running scores.  The 25
  * transitions of a block come from LDS, SH_CE_CH blocks staged per barrier, the next chunk already in registers.
  * Results per read at res: sub [L][4], ins [L + 1][4], del [L] (in this order: the float4 stores stay 16-byte aligned); a score
- * below -SH_MAP_BIG / 2: no admissible path (the host answers NAN).  All stores are plain vector stores. */
+ * below -SH_MAP_BIG / 2: no admissible path (the host answers NAN).  All stores are plain vector stores.
+ *
+ * BAND = true (ShCrfEditsBandRead: low and high of nblock + 1 int32 each behind the codes; include/scrappie_hip.h states the definition): F and G
+ * hold -SH_MAP_BIG outside the band of their entry, the new base's cells X carry none.  The rows kernel runs k_map_crf's banded loop -- per entry
+ * the cells from the 64-cell group of low on, the previous row read under the previous entry's band, nothing ever cleared -- and stores an
+ * entry's band alone: cell p of entry t at float p - low[t] of its row, the row's last slot (pitch - 1, never a cell: pitch > the widest entry)
+ * for the threads without one.  The combining kernel indexes the rows the same way (the index clamped into the row, -SH_MAP_BIG selected outside
+ * the band) and walks only the blocks at which one of its workgroup's positions can be alive.  With the full band both run the unbanded
+ * arithmetic operand for operand: the same bits.  The instantiations with BAND = false are the code they were. */
 #ifndef SH_CRF_EDITS_H
 #define SH_CRF_EDITS_H
 
@@ -59,6 +68,22 @@ struct ShCrfEditsArgs {
     float *base;                /* [read] */
 };
 
+/* A read in a band: the cells [low[t], high[t]) of entry t, as k_map_crf takes them (nblock + 1 int32 each, in seq[] behind the codes).  An entry's
+ * row holds its band's cells alone, cell p at float p - low[t], and the slot at pitch - 1 takes the stores of threads without a cell: pitch is
+ * the widest entry's cells and that slot rounded up to 16 (scrappie_hip_crf_edits_band_pitch). */
+struct ShCrfEditsBandRead : ShCrfEditsRead {
+    long long band;     /* offset in seq[] of low; high the next nblock + 1 */
+};
+
+struct ShCrfEditsBandArgs {
+    const ShCrfEditsBandRead *rd;
+    const float *trans;
+    const int *seq;             /* codes and bands */
+    float *rows;
+    float *res;
+    float *base;
+};
+
 template <bool VIT> __device__ __forceinline__ float sh_ce_mx(float a, float b) { return VIT ? (b > a ? b : a) : sh_lse(a, b); }
 template <bool VIT> __device__ __forceinline__ float sh_ce_end(float x, float y) { return VIT ? (x >= y ? x : y) : sh_lse(x, y); }
 
@@ -69,10 +94,12 @@ __device__ __forceinline__ auto sh_ce_view(const float *tr, const ShCrfEditsRead
     return ShMapCrfView<LOADER>::make(tr, m);
 }
 
-template <bool VIT, class LOADER, bool BACK>
-__global__ __launch_bounds__(SH_MAP_NTH) void k_crf_edits_rows(ShCrfEditsArgs a) {
+template <bool BAND> using ShCrfEditsArgsOf = std::conditional_t<BAND, ShCrfEditsBandArgs, ShCrfEditsArgs>;
+
+template <bool VIT, class LOADER, bool BACK, bool BAND = false>
+__global__ __launch_bounds__(SH_MAP_NTH) void k_crf_edits_rows(ShCrfEditsArgsOf<BAND> a) {
     extern __shared__ __attribute__((aligned(16))) float sh_ce_lds[];
-    const ShCrfEditsRead r = a.rd[blockIdx.x];
+    const auto r = a.rd[blockIdx.x];
     const int tid = threadIdx.x, L = r.seqlen, NB = r.nblock, RW = L + 2, SPARE = L + 1;
     const long long P = r.pitch, M = (long long)(NB + 1) * P;
     float *const trb = sh_ce_lds;                            /* [2][32] */
@@ -81,16 +108,25 @@ __global__ __launch_bounds__(SH_MAP_NTH) void k_crf_edits_rows(ShCrfEditsArgs a)
     int *const sq = (int *)(sh_ce_lds + SH_MAPC_HEAD + 4 * RW);
     for (int i = tid; i < L; i += SH_MAP_NTH) sq[i] = a.seq[r.seq + i];
     float *const gB = a.rows + r.rows + (BACK ? 2 * M : 0), *const gS = gB + M;      /* (BACK: gS is not used) */
-    const int nch = (L + SH_MAP_NTH) / SH_MAP_NTH;           /* chunks of the block loop: cells 0 .. L */
+    const int nch = (L + SH_MAP_NTH) / SH_MAP_NTH;           /* chunks of the block loop: cells 0 .. L (BAND: per entry, below) */
+    /* BAND: the band of the entry a step reads (lo_p, hi_p) and of the one it completes (lo_c, hi_c), as k_map_crf keeps them */
+    const int *blo = nullptr, *bhi = nullptr;
+    int lo_p = 0, hi_p = L + 1, lo_c = 0, hi_c = L + 1;
+    auto entry = [&](int k) { return min(max(BACK ? NB - 1 - k : k + 1, 0), NB); };      /* the entry that step k completes */
+    if constexpr (BAND) {
+        blo = a.seq + r.band; bhi = blo + (NB + 1);
+        lo_p = blo[BACK ? NB : 0]; hi_p = bhi[BACK ? NB : 0];
+        lo_c = blo[entry(0)]; hi_c = bhi[entry(0)];
+    }
     {
         float *const g0 = gB + (BACK ? (long long)NB * P : 0);
-        for (int p = tid; p <= L; p += SH_MAP_NTH) {         /* the first row: entry 0, or entry NB */
+        for (int p = (BAND ? lo_p : 0) + tid; p < (BAND ? hi_p : L + 1); p += SH_MAP_NTH) {      /* the first row: entry 0, or entry NB */
             const float b = BACK ? (p == L ? 0.0f : -SH_MAP_BIG) : (p == 1 ? 0.0f : -SH_MAP_BIG);
             const float s = BACK ? (p == L ? 0.0f : -SH_MAP_BIG) : (p == 0 ? 0.0f : -SH_MAP_BIG);
             buf0[p] = b;
             buf0[RW + p] = s;
-            g0[p] = b;
-            if (!BACK) g0[M + p] = s;
+            g0[BAND ? p - lo_p : p] = b;
+            if (!BACK) g0[M + (BAND ? p - lo_p : p)] = s;
         }
     }
     const auto v = sh_ce_view<LOADER>(a.trans, r);
@@ -111,7 +147,47 @@ __global__ __launch_bounds__(SH_MAP_NTH) void k_crf_edits_rows(ShCrfEditsArgs a)
             float *const cB = (k & 1) ? buf0 : buf1, *const cS = cB + RW;
             const float *const tr = trb + (k & 1) * 32;
             const float tSS = tr[24];
-            for (int ch = 0; ch < nch; ch++) {
+            if constexpr (BAND) {                            /* k_map_crf's banded loop: the band's cells alone, from the 64-cell group of lo_c on */
+                const int en = entry(k + 1);
+                const int lo_n = blo[en], hi_n = bhi[en];    /* asked for before the barrier */
+                const int base = lo_c & ~63;
+                const int nchb = (hi_c - base + SH_MAP_NTH - 1) / SH_MAP_NTH;
+                for (int ch = 0; ch < nchb; ch++) {
+                    const int p = base + ch * SH_MAP_NTH + tid;
+                    const bool valid = p >= lo_c && p < hi_c;
+                    const int b = sq[min(max(p - 1, 0), L - 1)];            /* seq[p - 1] */
+                    const bool in0 = p >= lo_p && p < hi_p;                 /* cell p of the entry read */
+                    float vb, vs;
+                    if (!BACK) {
+                        const int p0 = min(p, L), p1 = min(max(p - 1, 0), L);
+                        const int bp = sq[min(max(p - 2, 0), L - 1)];
+                        const bool in1 = p - 1 >= lo_p && p - 1 < hi_p;
+                        const float lB0 = pB[p0], lS0 = pS[p0], lB1 = pB[p1], lS1 = pS[p1];
+                        const float B0 = in0 ? lB0 : -SH_MAP_BIG, S0 = in0 ? lS0 : -SH_MAP_BIG;
+                        const float B1 = in1 ? lB1 : -SH_MAP_BIG, S1 = in1 ? lS1 : -SH_MAP_BIG;
+                        bool kb, ks;
+                        sh_map_crf_cell<VIT>(tr, tSS, b, bp, p, B0, S0, B1, S1, vb, vs, kb, ks);
+                    } else {
+                        const int nx = sq[min(p, L - 1)];
+                        const bool inx = p + 1 >= lo_p && p + 1 < hi_p;     /* cell p + 1 of the entry read (never L + 1: hi_p <= L + 1) */
+                        const float lB = pB[min(p + 1, L)], lS = pS[min(p, L)];
+                        const float nB = inx ? lB : -SH_MAP_BIG, nS = in0 ? lS : -SH_MAP_BIG;
+                        const float mvB = tr[5 * nx + b] + nB, stB = tr[20 + b] + nS;
+                        const float mvS = tr[5 * nx + 4] + nB, stS = tSS + nS;
+                        vb = p < L ? sh_ce_mx<VIT>(mvB, stB) : stB;
+                        vs = p < L ? sh_ce_mx<VIT>(mvS, stS) : stS;
+                        if (p < 1) vb = -SH_MAP_BIG;
+                    }
+                    const int at = valid ? p : SPARE;
+                    const long long gat = valid ? (long long)(p - lo_c) : P - 1;       /* the row holds the band's cells; its last slot is no cell's */
+                    cB[at] = vb;
+                    cS[at] = vs;
+                    gB[row + gat] = vb;
+                    if (!BACK) gS[row + gat] = vs;
+                }
+                lo_p = lo_c; hi_p = hi_c; lo_c = lo_n; hi_c = hi_n;
+            }
+            for (int ch = 0; !BAND && ch < nch; ch++) {      /* without a band: cells 0 .. L */
                 const int p = ch * SH_MAP_NTH + tid;
                 const bool valid = p <= L;
                 const int b = sq[min(max(p - 1, 0), L - 1)];            /* seq[p - 1] */
@@ -151,18 +227,43 @@ __global__ __launch_bounds__(SH_MAP_NTH) void k_crf_edits_rows(ShCrfEditsArgs a)
     }
 }
 
-template <bool VIT, class LOADER>
-__global__ __launch_bounds__(SH_MAP_NTH) void k_crf_edits(ShCrfEditsArgs a) {
+template <bool VIT, class LOADER, bool BAND = false>
+__global__ __launch_bounds__(SH_MAP_NTH) void k_crf_edits(ShCrfEditsArgsOf<BAND> a) {
     __shared__ float trs[2][SH_CE_CH * 32];
-    const ShCrfEditsRead r = a.rd[blockIdx.x];
+    const auto r = a.rd[blockIdx.x];
     const int L = r.seqlen, NB = r.nblock, tid = threadIdx.x;
     const int i0 = blockIdx.y * SH_MAP_NTH;
     if (i0 > L) return;                                      /* (uniform) */
     const bool mine = i0 + tid <= L;
     const int i = min(i0 + tid, L);
     const long long P = r.pitch, M = (long long)(NB + 1) * P;
-    const float *const FB = a.rows + r.rows + i, *const FS = FB + M;
-    const float *const G1 = a.rows + r.rows + 2 * M + min(i + 1, L), *const G2 = a.rows + r.rows + 2 * M + min(i + 2, L);
+    /* BAND: the rows hold the band's cells (cell p of entry t at p - low[t]); FB and G1 = G2 are the matrices' starts, the cell goes into the index.
+     * The workgroup walks blocks T0 .. T1 - 1 alone: before entry T0 -- the first whose band reaches its first position's cell, high[T0] > i0 -- every
+     * source cell of its positions is outside the band and X, the sums and the maxima hold nothing admissible; from entry T1 on -- the last whose
+     * band still holds the cell two behind its last position, low[T1] <= min(i0 + SH_MAP_NTH + 1, L): the furthest G a position joins -- nothing joins.
+     * With the end rule (positions L - 1 and L) that cell is L and T1 = NB. */
+    const int *blo = nullptr, *bhi = nullptr;
+    int T0 = 0, T1 = NB;
+    if constexpr (BAND) {
+        __shared__ int cnt[2];
+        blo = a.seq + r.band; bhi = blo + (NB + 1);
+        if (tid < 2) cnt[tid] = 0;
+        __syncthreads();
+        const int c1 = min(i0 + SH_MAP_NTH + 1, L);
+        int below = 0, reach = 0;
+        for (int t = tid; t <= NB; t += SH_MAP_NTH) { below += bhi[t] <= i0; reach += blo[t] <= c1; }      /* both edges are non-decreasing: prefixes */
+        if (below) atomicAdd(&cnt[0], below);
+        if (reach) atomicAdd(&cnt[1], reach);
+        __syncthreads();
+        T0 = cnt[0]; T1 = cnt[1] - 1;                        /* high[NB] = L + 1 > i0: T0 <= NB; low[0] = 0: T1 >= 0 */
+    }
+    const float *const FB = a.rows + r.rows + (BAND ? 0 : i), *const FS = FB + M;
+    const float *const G1 = a.rows + r.rows + 2 * M + (BAND ? 0 : min(i + 1, L)), *const G2 = a.rows + r.rows + 2 * M + (BAND ? 0 : min(i + 2, L));
+    /* BAND: cell c of entry e from the matrix at m; outside the band -SH_MAP_BIG, the index clamped into the row */
+    auto cell = [&](const float *m, int e, int c, int lo, int hi) {
+        const float x = m[(long long)e * P + min(max(c - lo, 0), (int)P - 1)];
+        return c >= lo && c < hi ? x : -SH_MAP_BIG;
+    };
     const int *const sq = a.seq + r.seq;
     const bool hp = i >= 1;                                  /* a base precedes position i */
     const int pb = sq[max(i - 1, 0)], n0 = sq[min(i, L - 1)], n1 = sq[min(i + 1, L - 1)];
@@ -172,7 +273,7 @@ __global__ __launch_bounds__(SH_MAP_NTH) void k_crf_edits(ShCrfEditsArgs a) {
     float q[NQ];
     auto fetch = [&](int c) {
 #pragma unroll
-        for (int m = 0; m < NQ; m++) q[m] = v.col(c * SH_CE_CH + srow + m * (SH_MAP_NTH / 32))[slot];
+        for (int m = 0; m < NQ; m++) q[m] = v.col((BAND ? T0 : 0) + c * SH_CE_CH + srow + m * (SH_MAP_NTH / 32))[slot];
     };
     auto stage = [&](int buf) {
 #pragma unroll
@@ -184,12 +285,25 @@ __global__ __launch_bounds__(SH_MAP_NTH) void k_crf_edits(ShCrfEditsArgs a) {
     /* block t reads the prefix's cells of entry t and the suffix's of entry t + 1 */
     float fb[SH_CE_D], fs[SH_CE_D], g1[SH_CE_D], g2[SH_CE_D];
     auto rows_of = [&](int t, int d) {
-        const long long e0 = (long long)min(t, NB) * P, e1 = (long long)min(t + 1, NB) * P;
-        fb[d] = FB[e0]; fs[d] = FS[e0]; g1[d] = G1[e1]; g2[d] = G2[e1];
+        if constexpr (BAND) {
+            const int t0 = min(t, NB), t1 = min(t + 1, NB);
+            const int l0 = blo[t0], h0 = bhi[t0], l1 = blo[t1], h1 = bhi[t1];
+            fb[d] = cell(FB, t0, i, l0, h0); fs[d] = cell(FS, t0, i, l0, h0);
+            g1[d] = cell(G1, t1, min(i + 1, L), l1, h1); g2[d] = cell(G2, t1, min(i + 2, L), l1, h1);
+        } else {
+            const long long e0 = (long long)min(t, NB) * P, e1 = (long long)min(t + 1, NB) * P;
+            fb[d] = FB[e0]; fs[d] = FS[e0]; g1[d] = G1[e1]; g2[d] = G2[e1];
+        }
     };
-    const float g10 = G1[0], g20 = G2[0];
+    float g10, g20;                                          /* G_B[T0][i + 1], G_B[T0][i + 2] */
+    if constexpr (BAND) {
+        const int l = blo[min(T0, NB)], h = bhi[min(T0, NB)];
+        g10 = cell(G1, min(T0, NB), min(i + 1, L), l, h); g20 = cell(G2, min(T0, NB), min(i + 2, L), l, h);
+    } else {
+        g10 = G1[0]; g20 = G2[0];
+    }
 #pragma unroll
-    for (int d = 0; d < SH_CE_D; d++) rows_of(d, d);
+    for (int d = 0; d < SH_CE_D; d++) rows_of(T0 + d, d);
     float XB[4], XS[4], sub[4], ins[4];
     float del = (i == 0 ? 0.0f : -SH_MAP_BIG) + g20;         /* entry 0 is the suffix's first base only where nothing precedes it */
 #pragma unroll
@@ -200,14 +314,14 @@ __global__ __launch_bounds__(SH_MAP_NTH) void k_crf_edits(ShCrfEditsArgs a) {
         ins[c] = -SH_MAP_BIG + g10;
     }
     __syncthreads();
-    const int nchunk = (NB + SH_CE_CH - 1) / SH_CE_CH;
+    const int nchunk = BAND ? (max(T1 - T0, 0) + SH_CE_CH - 1) / SH_CE_CH : (NB + SH_CE_CH - 1) / SH_CE_CH;
     for (int c0 = 0; c0 < nchunk; c0++) {
         const float *const tc = trs[c0 & 1];
         for (int u0 = 0; u0 < SH_CE_CH; u0 += SH_CE_D) {
 #pragma unroll
             for (int d = 0; d < SH_CE_D; d++) {
-                const int u = u0 + d, t = c0 * SH_CE_CH + u;
-                if (t >= NB) break;                          /* (uniform) */
+                const int u = u0 + d, t = (BAND ? T0 : 0) + c0 * SH_CE_CH + u;
+                if (t >= (BAND ? T1 : NB)) break;            /* (uniform) */
                 const float *const tr = tc + u * 32;
                 const float tSS = tr[24], e1 = tr[5 * n1 + 4], e0 = tr[5 * n0 + 4];
                 const float dB = tr[5 * n1 + pb] + fb[d], dS = e1 + fs[d];
@@ -243,8 +357,13 @@ __global__ __launch_bounds__(SH_MAP_NTH) void k_crf_edits(ShCrfEditsArgs a) {
         if (i == L - 1) {
 #pragma unroll
             for (int c = 0; c < 4; c++) sub[c] = sh_ce_end<VIT>(XB[c], XS[c]);
-            const long long eN = (long long)NB * P;
-            del = sh_ce_end<VIT>(FB[eN], FS[eN]);
+            if constexpr (BAND) {
+                const int l = blo[NB], h = bhi[NB];
+                del = sh_ce_end<VIT>(cell(FB, NB, i, l, h), cell(FS, NB, i, l, h));
+            } else {
+                const long long eN = (long long)NB * P;
+                del = sh_ce_end<VIT>(FB[eN], FS[eN]);
+            }
         }
         *(float4 *)(out + 4 * (long long)i) = make_float4(sub[0], sub[1], sub[2], sub[3]);
         out[8 * (long long)L + 4 + i] = del;

@@ -7,12 +7,13 @@
  * type's release; form counts and timing.  A family says what is its own in an EditsTraits. */
 
 /* What a family says of its record Rec: Args, its kernels' arguments; name, as its error texts begin; state(e), the EditsState of the engine it uses;
- * plan(L, nblock, n, a, pitch, rows, res, res_floats), its planner of the ABI (below 0: refused); read_bytes(L, nblock, a), the device bytes a read
- * adds to a launch: rows, results, codes, its record and base score; fill(r, j, codes, a): the record's own fields and what the read appends to
+ * plan(jobs, L, nblock, n, a, pitch, rows, res, res_floats), its planner of the ABI on the n jobs' lengths and block counts (below 0: refused);
+ * read_bytes(j, a), the device bytes job j adds to a launch: rows, results, codes, its record and base score; fill(r, j, codes, a): the record's own fields and what the read appends to
  * codes; lds_rows(maxL, a) and lds_edits(a), the dynamic LDS of the two kernels, and lds_err(rows, edits), its text where either is too much;
  * launch_rows / launch_edits: launch_k on its kernels' forms; base_as_is: the base score goes out as the kernel wrote it (else through the "no
  * admissible path" rule); del_from(a): the fewest bases a deletion leaves something of; target_why(t, a): why a target cannot be scored, empty: it
- * can; model_ok(m) and args(m, p, ro): the batch call's check of the model and its kernels' arguments on what the network left. */
+ * can; read_why(t, nblock, a): the same once the read's block count is known; model_ok(m) and args(m, p, ro): the batch call's check of the model and
+ * its kernels' arguments on what the network left; run(e, jobs, a, vit, tiled, budget, t): the jobs of a launch group through edits_run. */
 template <class Rec> struct EditsTraits;
 
 /* launches of each form in this process: the rows kernel at (vit ? 4 : 0) | (tiled ? 2 : 0) | (back ? 1 : 0), the combining one at 8 + ((vit ? 2 : 0) | (tiled ? 1 : 0)) */
@@ -28,7 +29,7 @@ static void edits_timing(const EditsState &d, double ms[3], size_t *launches, si
 }
 
 /* one read of a launch: where its posterior or transitions are (as plan_add takes them), its sequence, and where its results go (NAN already; any may be NULL) */
-struct EditsJob { long long at; int lane; size_t nblock; const int *seq; size_t L; float *base, *sub, *del, *ins; };
+struct EditsJob { long long at; int lane; size_t nblock; const int *seq; size_t L; float *base, *sub, *del, *ins; const size_t *lo, *hi; /* its band, or NULL */ };
 
 /* jobs[j0, j1) as one launch of the three kernels (under mu, on the main stream).  a: what the kernels take of the caller. */
 template <class Rec>
@@ -43,7 +44,7 @@ static int edits_launch(scrappie_hip_engine *e, const std::vector<EditsJob> &job
     size_t maxL = 0;
     for (size_t k = 0; k < n; k++) { Ls[k] = jobs[j0 + k].L; NBs[k] = jobs[j0 + k].nblock; maxL = std::max(maxL, Ls[k]); }
     long long nres = 0;
-    const long long nrow = T::plan(Ls.data(), NBs.data(), n, a, pitch.data(), rows.data(), res.data(), &nres);
+    const long long nrow = T::plan(jobs.data() + j0, Ls.data(), NBs.data(), n, a, pitch.data(), rows.data(), res.data(), &nres);
     if (nrow < 0) return set_err("%s: a sequence shorter than the k-mer reached the launch", T::name);
     std::vector<Rec> rd(n);
     for (size_t k = 0; k < n; k++) {
@@ -111,7 +112,7 @@ static int edits_run(scrappie_hip_engine *e, const std::vector<EditsJob> &jobs, 
     Span2 span;
     size_t j0 = 0, bytes = 0;
     for (size_t j = 0; j < jobs.size(); j++) {
-        const size_t b = EditsTraits<Rec>::read_bytes(jobs[j].L, jobs[j].nblock, a);
+        const size_t b = EditsTraits<Rec>::read_bytes(jobs[j], a);
         if (budget && j > j0 && bytes + b > budget) {
             if (edits_launch<Rec>(e, jobs, j0, j, a, vit, tiled)) return -1;
             j0 = j; bytes = 0;
@@ -188,9 +189,9 @@ static int edits_batch(const char *fn, scrappie_hip_engine *e, int model, const 
             for (const PostRead &q : rd) {
                 scrappie_hip_edits_result &r = out[q.r];
                 r.nblock = q.nblock;
-                jobs.push_back(EditsJob{q.boff, q.lane, q.nblock, targets[q.r].seq, targets[q.r].seqlen, &r.base, r.sub, r.del, r.ins});
+                jobs.push_back(EditsJob{q.boff, q.lane, q.nblock, targets[q.r].seq, targets[q.r].seqlen, &r.base, r.sub, r.del, r.ins, targets[q.r].poslow, targets[q.r].poshigh});
             }
-            return edits_run<Rec>(e, jobs, T::args(m, c.p, ro), vit, true, d.budget, e->map_ms + 1);
+            return T::run(e, jobs, T::args(m, c.p, ro), vit, true, d.budget, e->map_ms + 1);
         });
     };
     const typename T::Args a = T::args(m, c.p, RunOut());   /* (what the checks and the byte count read of it does not depend on the launch group) */
@@ -199,7 +200,10 @@ static int edits_batch(const char *fn, scrappie_hip_engine *e, int model, const 
         if (!why.empty()) { cut.refuse(i, why.c_str()); continue; }
         const size_t nb = c.blocks(cut, i, reads[i]);
         if (nb == 0) continue;
-        c.add(cut, i, nb, T::read_bytes(targets[i].seqlen, nb, a), "read and sequence too long for one launch group on this device");
+        const std::string why_nb = T::read_why(targets[i], nb, a);
+        if (!why_nb.empty()) { cut.refuse(i, why_nb.c_str()); continue; }
+        const EditsJob j{0, 0, nb, targets[i].seq, targets[i].seqlen, nullptr, nullptr, nullptr, nullptr, targets[i].poslow, targets[i].poshigh};
+        c.add(cut, i, nb, T::read_bytes(j, a), "read and sequence too long for one launch group on this device");
     }
     return c.finish(cut, [&] { edits_blank(out, n); });
 }

@@ -22,11 +22,15 @@ template <> struct EditsTraits<ShMapEditsRead> {
     static constexpr bool base_as_is = true;                 /* k_map's score as it is */
     static EditsState &state(scrappie_hip_engine *e) { return e->map_edits; }
     static size_t del_from(const Args &a) { return (size_t)a.k + 1; }      /* (a deletion from k bases leaves no state) */
-    static long long plan(const size_t *L, const size_t *nblock, size_t n, const Args &a, int *pitch, long long *rows, long long *res, long long *res_floats) {
+    static long long plan(const EditsJob *, const size_t *L, const size_t *nblock, size_t n, const Args &a, int *pitch, long long *rows, long long *res, long long *res_floats) {
         return scrappie_hip_map_edits_plan(L, nblock, n, (size_t)a.k, pitch, rows, res, res_floats);
     }
-    static size_t read_bytes(size_t L, size_t nblock, const Args &a) {
-        return scrappie_hip_map_edits_row_bytes(L, (size_t)a.k, nblock) + (9 * L + 8) * 4 + 2 * L * 4 + sizeof(ShMapEditsRead) + 64;
+    static size_t read_bytes(const EditsJob &j, const Args &a) {
+        return scrappie_hip_map_edits_row_bytes(j.L, (size_t)a.k, j.nblock) + (9 * j.L + 8) * 4 + 2 * j.L * 4 + sizeof(ShMapEditsRead) + 64;
+    }
+    static std::string read_why(const scrappie_hip_map_target &, size_t, const Args &) { return std::string(); }
+    static int run(scrappie_hip_engine *e, const std::vector<EditsJob> &jobs, const Args &a, bool vit, bool tiled, size_t budget, double *t) {
+        return edits_run<ShMapEditsRead>(e, jobs, a, vit, tiled, budget, t);
     }
     static void fill(ShMapEditsRead &r, const EditsJob &j, std::vector<int> &codes, const Args &a) {
         const size_t K = (size_t)a.k;

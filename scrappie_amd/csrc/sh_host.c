@@ -1114,6 +1114,63 @@ long long scrappie_hip_crf_edits_plan(const size_t *seqlen, const size_t *nblock
     return edits_plan(seqlen, nblock, n, 0, pitch, rows, res, res_floats);
 }
 
+/* The same in a band (low, high: nblock + 1 entries each, as scrappie_hip_map_crf_bounds_sane takes them): an entry's row holds its band's
+ * cells alone, cell p of entry t at float p - low[t], and the row's last slot takes the stores of threads without a cell.  One pitch per read:
+ * the widest entry's cells and that slot, rounded up to 16 floats.  An entry that is empty or the wrong way round counts as one cell (the
+ * engine refuses such a band before it plans). */
+size_t scrappie_hip_crf_edits_band_pitch(const size_t *low, const size_t *high, size_t nblock) {
+    size_t w = 1;
+    if (!low || !high) return 0;
+    for (size_t t = 0; t <= nblock; t++)
+        if (high[t] > low[t] && high[t] - low[t] > w) w = high[t] - low[t];
+    return (w + 1 + 15) / 16 * 16;
+}
+size_t scrappie_hip_crf_edits_band_row_bytes(const size_t *low, const size_t *high, size_t nblock) {
+    return 3 * (nblock + 1) * scrappie_hip_crf_edits_band_pitch(low, high, nblock) * 4;
+}
+
+/* scrappie_hip_crf_edits_plan for reads in bands: read i has the band low[i], high[i] (nblock[i] + 1 entries each); where either is NULL the read
+ * has no band and takes the unbanded pitch and rows.  Everything else as there. */
+long long scrappie_hip_crf_edits_band_plan(const size_t *seqlen, const size_t *nblock, const size_t *const *low, const size_t *const *high, size_t n,
+                                           int *pitch, long long *rows, long long *res, long long *res_floats) {
+    long long nrow = 0, nres = 0;
+    if (res_floats) *res_floats = 0;
+    if (!seqlen || !nblock || !low || !high || !pitch || !rows || !res) return 0;
+    for (size_t i = 0; i < n; i++) {
+        const int band = low[i] && high[i];
+        const size_t p = band ? scrappie_hip_crf_edits_band_pitch(low[i], high[i], nblock[i]) : scrappie_hip_crf_edits_pitch(seqlen[i]);
+        pitch[i] = (int)p;
+        rows[i] = nrow;
+        res[i] = nres;
+        nrow += (long long)(3 * (nblock[i] + 1) * p);
+        nres += (long long)crf_edits_res_floats(seqlen[i]);
+    }
+    if (res_floats) *res_floats = nres;
+    return nrow;
+}
+
+/* The band around a Viterbi path of k_map_crf: path[t], t = 0 .. nblock, the index of the last base emitted through entry t (-1: none), so
+ * cnt = path[t] + 1 is the path's cell; low[t] = max(cnt - halfwidth, 0), high[t] = min(cnt + halfwidth + 1, seqlen + 1), and low[0] = 0
+ * whatever the half-width (a path whose entry 0 is a base is in cell 1 there; a band begins at cell 0).  A path moves by 0 or 1 per entry,
+ * begins in cell 0 or 1 and ends in cell seqlen, so both edges are non-decreasing, high[nblock] = seqlen + 1 and
+ * low[t] <= cnt[t - 1] + 1 - halfwidth <= high[t - 1]: always a band that scrappie_hip_map_crf_bounds_sane accepts.  -1 on a null or empty
+ * argument or what is no path of that sequence: a value outside -1 .. seqlen - 1 (entry 0: outside -1 .. 0), a step down or above 1,
+ * path[nblock] != seqlen - 1. */
+int scrappie_hip_map_crf_path_band(const int *path, size_t nblock, size_t seqlen, size_t halfwidth, size_t *low, size_t *high) {
+    if (!path || !low || !high || nblock == 0 || seqlen == 0) return -1;
+    for (size_t t = 0; t <= nblock; t++) {
+        if (path[t] < -1 || (long long)path[t] > (long long)seqlen - 1) return -1;
+        if (t > 0 && (path[t] < path[t - 1] || path[t] - path[t - 1] > 1)) return -1;
+    }
+    if (path[0] > 0 || (size_t)(path[nblock] + 1) != seqlen) return -1;
+    for (size_t t = 0; t <= nblock; t++) {
+        const size_t cnt = (size_t)(path[t] + 1);
+        low[t] = (t > 0 && cnt > halfwidth) ? cnt - halfwidth : 0;
+        high[t] = (halfwidth >= seqlen || cnt + halfwidth + 1 > seqlen + 1) ? seqlen + 1 : cnt + halfwidth + 1;
+    }
+    return 0;
+}
+
 /* Every single-base edit of a sequence against a transducer read (k_map_edits_rows, k_map_edits, sh_map_edits.h): what a read of L
  * bases -- n = L - k + 1 states -- and nblock blocks keeps in device memory.  Two row matrices, F and G, of nblock + 1 entries, an
  * entry's row of `pitch` floats: cells 0 .. n - 1 and slot n (FS going forward, the stores of threads without a cell going backward),
