@@ -611,6 +611,21 @@ def _local_plan(plan, *sizes_and_stride):
     return dict(first=first, ncell=ncell, own=own, home=home, scr_off=off, scr_floats=int(tot.value))
 
 
+def _set_default_engine_option(name, value):
+    """A debug option of the process-default engine, the one the per-read functions run on (an `Engine` has `debug_option`)."""
+    if lib().scrappie_hip_debug_option(None, name.encode(), int(value)) != 0:
+        raise RuntimeError("debug_option: " + last_error())
+
+
+def _pack_plan(plan, lengths, pack_cells):
+    """A *_pack_plan symbol (or scrappie_hip_crf_find_plan) on the members' lengths: (pack, cell, npack)."""
+    a = np.ascontiguousarray(lengths, dtype=np.uintp)
+    pack = np.full(max(len(a), 1), -1, dtype=np.int32)
+    cell = np.full(max(len(a), 1), -1, dtype=np.longlong)
+    n = plan(a.ctypes.data_as(C.POINTER(C.c_size_t)), len(a), int(pack_cells), pack.ctypes.data_as(C.POINTER(C.c_int)), cell.ctypes.data_as(C.POINTER(C.c_longlong)))
+    return pack[:len(a)], cell[:len(a)], int(n)
+
+
 def map_crf_form_counts():
     """Launches of each k_map_crf form in this process so far (scrappie_hip_map_crf_form_counts):
     {(viterbi, tiled, scratch): n}."""
@@ -638,8 +653,7 @@ def map_crf_local_plan(seq_len, nblock, stride=-1):
 def set_map_crf_local_stride(value):
     """The debug option "map_crf_local_stride" of the process-default engine, the one `map_trans_to_reference` runs on: start
     cells per window, 0: one window, -1: the default.  (An `Engine` has `debug_option`.)"""
-    if lib().scrappie_hip_debug_option(None, b"map_crf_local_stride", int(value)) != 0:
-        raise RuntimeError("debug_option: " + last_error())
+    _set_default_engine_option("map_crf_local_stride", value)
 
 
 def map_local_form_counts():
@@ -665,15 +679,12 @@ def map_local_plan(seq_len, nblock, nstate, stride=-1):
 def set_map_local_stride(value):
     """The debug option "map_local_stride" of the process-default engine, the one `map_post_to_reference` runs on: entry
     positions per window, 0: one window, -1: the default.  (An `Engine` has `debug_option`.)"""
-    if lib().scrappie_hip_debug_option(None, b"map_local_stride", int(value)) != 0:
-        raise RuntimeError("debug_option: " + last_error())
+    _set_default_engine_option("map_local_stride", value)
 
 
 def crf_find_form_counts():
     """Launches of each k_crf_find form in this process so far (scrappie_hip_crf_find_form_counts): {(positions, tiled): n}."""
-    q = (C.c_uint64 * 4)()
-    lib().scrappie_hip_crf_find_form_counts(q)
-    return {(bool(k & 2), bool(k & 1)): int(q[k]) for k in range(4)}
+    return _form_counts(lib().scrappie_hip_crf_find_form_counts, 2)
 
 
 def crf_find_max_cells():
@@ -686,26 +697,19 @@ def crf_find_plan(lengths, pack_cells=512):
     """Motifs of `lengths` bases into packs of at most `pack_cells` cells, in input order (host arithmetic, no device;
     scrappie_hip_crf_find_plan).  Returns (npack, pack, cell): per motif its pack and its first cell there, -1 where the motif
     is empty or too long for k_crf_find."""
-    ln = np.ascontiguousarray(lengths, dtype=np.uintp)
-    pack = np.full(max(len(ln), 1), -1, dtype=np.int32)
-    cell = np.full(max(len(ln), 1), -1, dtype=np.longlong)
-    npack = int(lib().scrappie_hip_crf_find_plan(ln.ctypes.data_as(C.POINTER(C.c_size_t)), len(ln), int(pack_cells),
-                                                 pack.ctypes.data_as(C.POINTER(C.c_int)), cell.ctypes.data_as(C.POINTER(C.c_longlong))))
-    return npack, pack[:len(ln)], cell[:len(ln)]
+    pack, cell, npack = _pack_plan(lib().scrappie_hip_crf_find_plan, lengths, pack_cells)
+    return npack, pack, cell
 
 
 def set_crf_find_cells(value):
     """The debug option "crf_find_cells" of the process-default engine, the one `find_in_trans` runs on: cells per pack of
     motifs, -1: the default.  (An `Engine` has `debug_option`.)"""
-    if lib().scrappie_hip_debug_option(None, b"crf_find_cells", int(value)) != 0:
-        raise RuntimeError("debug_option: " + last_error())
+    _set_default_engine_option("crf_find_cells", value)
 
 
 def map_pack_form_counts():
     """Launches of each k_map_pack form in this process so far (scrappie_hip_map_pack_form_counts): {(viterbi, tiled): n}."""
-    q = (C.c_uint64 * 4)()
-    lib().scrappie_hip_map_pack_form_counts(q)
-    return {(bool(k & 2), bool(k & 1)): int(q[k]) for k in range(4)}
+    return _form_counts(lib().scrappie_hip_map_pack_form_counts, 2)
 
 
 def map_pack_max_cells():
@@ -717,19 +721,13 @@ def map_pack_plan(seqlens, pack_cells):
     """The packing of candidates of `seqlens` states into packs of at most `pack_cells` cells (host arithmetic, no device;
     scrappie_hip_map_pack_plan): (pack, cell, npack) -- each candidate's pack (-1: too long for any, it takes k_map) and its
     first cell there."""
-    a = np.ascontiguousarray(seqlens, dtype=np.uintp)
-    pack = np.zeros(len(a), dtype=np.int32)
-    cell = np.zeros(len(a), dtype=np.longlong)
-    n = lib().scrappie_hip_map_pack_plan(a.ctypes.data_as(C.POINTER(C.c_size_t)), len(a), int(pack_cells), pack.ctypes.data_as(C.POINTER(C.c_int)),
-                                         cell.ctypes.data_as(C.POINTER(C.c_longlong)))
-    return pack, cell, int(n)
+    return _pack_plan(lib().scrappie_hip_map_pack_plan, seqlens, pack_cells)
 
 
 def set_map_pack_cells(value):
     """The debug option "map_pack_cells" of the process-default engine, the one `map_post_to_sequences` runs on: cells per pack
     of candidates, 0: every candidate through k_map, -1: the default.  (An `Engine` has `debug_option`.)"""
-    if lib().scrappie_hip_debug_option(None, b"map_pack_cells", int(value)) != 0:
-        raise RuntimeError("debug_option: " + last_error())
+    _set_default_engine_option("map_pack_cells", value)
 
 
 def squiggle_pack_form_counts():
@@ -749,12 +747,7 @@ def squiggle_pack_plan(npos, pack_cells):
     """The packing of candidate squiggles of `npos` positions into packs of at most `pack_cells` cells (host arithmetic, no
     device; scrappie_hip_squiggle_pack_plan): (pack, cell, npack) -- each candidate's pack (-1: too long for any, it takes
     k_squig) and its first cell there."""
-    a = np.ascontiguousarray(npos, dtype=np.uintp)
-    pack = np.zeros(len(a), dtype=np.int32)
-    cell = np.zeros(len(a), dtype=np.longlong)
-    n = lib().scrappie_hip_squiggle_pack_plan(a.ctypes.data_as(C.POINTER(C.c_size_t)), len(a), int(pack_cells),
-                                              pack.ctypes.data_as(C.POINTER(C.c_int)), cell.ctypes.data_as(C.POINTER(C.c_longlong)))
-    return pack, cell, int(n)
+    return _pack_plan(lib().scrappie_hip_squiggle_pack_plan, npos, pack_cells)
 
 
 def squiggle_pack_layout(npos, pack, which):
@@ -777,8 +770,7 @@ def squiggle_pack_layout(npos, pack, which):
 def set_squiggle_pack_cells(value):
     """The debug option "squig_pack_cells" of the process-default engine, the one `squiggle_match_many` runs on: cells per
     pack of candidate squiggles, 0: every candidate through k_squig, -1: the default.  (An `Engine` has `debug_option`.)"""
-    if lib().scrappie_hip_debug_option(None, b"squig_pack_cells", int(value)) != 0:
-        raise RuntimeError("debug_option: " + last_error())
+    _set_default_engine_option("squig_pack_cells", value)
 
 
 def squiggle_local_form_counts():
@@ -804,8 +796,7 @@ def squiggle_local_plan(npos, nsample, stride=-1):
 def set_squiggle_local_stride(value):
     """The debug option "squig_local_stride" of the process-default engine, the one `squiggle_match_reference` runs on: entry
     positions per window, 0: one window, -1: the default.  (An `Engine` has `debug_option`.)"""
-    if lib().scrappie_hip_debug_option(None, b"squig_local_stride", int(value)) != 0:
-        raise RuntimeError("debug_option: " + last_error())
+    _set_default_engine_option("squig_local_stride", value)
 
 
 def _squig_targets(squiggles):
@@ -839,9 +830,7 @@ def squiggle_match_many(rt, squiggles, rate=1.0, back_prob=0.0, local_pen=2.0, s
 
 def map_crf_pack_form_counts():
     """Launches of each k_map_crf_pack form in this process so far (scrappie_hip_map_crf_pack_form_counts): {(viterbi, tiled): n}."""
-    q = (C.c_uint64 * 4)()
-    lib().scrappie_hip_map_crf_pack_form_counts(q)
-    return {(bool(k & 2), bool(k & 1)): int(q[k]) for k in range(4)}
+    return _form_counts(lib().scrappie_hip_map_crf_pack_form_counts, 2)
 
 
 def map_crf_pack_max_cells():
@@ -853,27 +842,19 @@ def map_crf_pack_plan(lengths, pack_cells):
     """The packing of candidates of `lengths` bases into packs of at most `pack_cells` cells (host arithmetic, no device;
     scrappie_hip_map_crf_pack_plan): (pack, cell, npack) -- each candidate's pack (-1: too long for any, it takes k_map_crf) and
     its first cell there."""
-    a = np.ascontiguousarray(lengths, dtype=np.uintp)
-    pack = np.zeros(len(a), dtype=np.int32)
-    cell = np.zeros(len(a), dtype=np.longlong)
-    n = lib().scrappie_hip_map_crf_pack_plan(a.ctypes.data_as(C.POINTER(C.c_size_t)), len(a), int(pack_cells), pack.ctypes.data_as(C.POINTER(C.c_int)),
-                                             cell.ctypes.data_as(C.POINTER(C.c_longlong)))
-    return pack, cell, int(n)
+    return _pack_plan(lib().scrappie_hip_map_crf_pack_plan, lengths, pack_cells)
 
 
 def set_map_crf_pack_cells(value):
     """The debug option "map_crf_pack_cells" of the process-default engine, the one `map_trans_to_sequences` runs on: cells per
     pack of candidates, 0: every candidate through k_map_crf, -1: the default.  (An `Engine` has `debug_option`.)"""
-    if lib().scrappie_hip_debug_option(None, b"map_crf_pack_cells", int(value)) != 0:
-        raise RuntimeError("debug_option: " + last_error())
+    _set_default_engine_option("map_crf_pack_cells", value)
 
 
 def squiggle_band_form_counts():
     """Launches of each k_squig_band form in this process so far (scrappie_hip_squiggle_band_form_counts):
     {(viterbi, scratch): n}."""
-    q = (C.c_uint64 * 4)()
-    lib().scrappie_hip_squiggle_band_form_counts(q)
-    return {(bool(k & 2), bool(k & 1)): int(q[k]) for k in range(4)}
+    return _form_counts(lib().scrappie_hip_squiggle_band_form_counts, 2)
 
 
 def plan_squiggle_band(npos, width, nsample, path=True):
@@ -2548,25 +2529,35 @@ class Engine(object):
         order: the float32 raw scores as `map_to_sequence` gives them (NaN where a candidate, or the read, cannot be
         mapped; normalising for length is the caller's business), the index of the highest (the lowest index on a tie,
         -1: none) and, with `path`, the Viterbi path of that candidate."""
+        def targets():
+            nstate = lib().scrappie_hip_model_states(self._h, self._models[model])
+            if nstate == 25:
+                raise RuntimeError("map_multi_batch: a flip-flop (CRF) model maps one sequence per read (map_to_sequence)")
+            kmer_len = guess_state_properties(nstate)[1]
+            return lambda cl: _map_targets(cl, kmer_len)
+        return Engine._map_multi(self, "map_multi_batch", lib().scrappie_hip_map_multi_batch, signals, candidates, model, targets,
+                                 dict(min_prob=min_prob, tempW=tempW, tempb=tempb, stay_pen=stay_pen, skip_pen=skip_pen, local_pen=local_pen),
+                                 viterbi, path, 0)
+
+    def _map_multi(self, fn_name, symbol, signals, candidates, model, targets, params, viterbi, path, more):
+        """A *_multi_batch symbol on the reads and their candidates.  The argument checks come before anything touches the engine:
+        `targets()` gives how a list of candidates becomes map targets, `params` are `default_params`' keywords; `more`: the
+        entries a path has beyond the read's blocks."""
         n = len(signals)
         _path_needs_viterbi(path, viterbi)
         candidates, shared = _per_read_lists(candidates, n, 'candidates')
         h = self._models[model]
-        nstate = lib().scrappie_hip_model_states(self._h, h)
-        if nstate == 25:
-            raise RuntimeError("map_multi_batch: a flip-flop (CRF) model maps one sequence per read (map_to_sequence)")
-        kmer_len = guess_state_properties(nstate)[1]
+        encode = targets()
         rts, keep = _raw_tables(signals)
-        cds, kept = _per_read_sets(candidates, shared, n, lambda cl: _map_targets(cl, kmer_len))
+        cds, kept = _per_read_sets(candidates, shared, n, encode)
         keep += kept
-        p = self.default_params(min_prob=min_prob, tempW=tempW, tempb=tempb, stay_pen=stay_pen, skip_pen=skip_pen,
-                                local_pen=local_pen)
+        p = self.default_params(**params)
         out = (_MapMultiResult * max(n, 1))()
-        if lib().scrappie_hip_map_multi_batch(self._h, h, rts, cds, n, C.byref(p), 1 if viterbi else 0, 1 if path else 0, out) != 0:
-            raise RuntimeError("map_multi_batch: " + last_error())
+        if symbol(self._h, h, rts, cds, n, C.byref(p), 1 if viterbi else 0, 1 if path else 0, out) != 0:
+            raise RuntimeError(fn_name + ": " + last_error())
         res = []
         rs = [out[i] for i in range(n)]
-        for r, pth in zip(rs, _paths(rs)):
+        for r, pth in zip(rs, _paths(rs, more=more)):
             sc = np.ctypeslib.as_array(r.score, shape=(r.ncand,)).copy() if r.ncand else np.zeros(0, dtype=np.float32)
             res.append((sc, int(r.best), pth))
         lib().scrappie_hip_free_map_multi_results(out, n)
@@ -2580,24 +2571,8 @@ class Engine(object):
         [(scores, best, path or None)] in input order: the float32 scores as `map_to_sequence(model='rnnrf_r94')` gives them
         (NaN where a candidate, or the read, cannot be mapped), the index of the highest (the lowest index on a tie, -1:
         none) and, with `path`, the Viterbi path of that candidate, nblock + 1 entries."""
-        n = len(signals)
-        _path_needs_viterbi(path, viterbi)
-        candidates, shared = _per_read_lists(candidates, n, 'candidates')
-        h = self._models[model]
-        rts, keep = _raw_tables(signals)
-        cds, kept = _per_read_sets(candidates, shared, n, _crf_targets)
-        keep += kept
-        p = self.default_params(min_prob=min_prob, tempW=tempW, tempb=tempb)
-        out = (_MapMultiResult * max(n, 1))()
-        if lib().scrappie_hip_map_crf_multi_batch(self._h, h, rts, cds, n, C.byref(p), 1 if viterbi else 0, 1 if path else 0, out) != 0:
-            raise RuntimeError("map_crf_multi_batch: " + last_error())
-        res = []
-        rs = [out[i] for i in range(n)]
-        for r, pth in zip(rs, _paths(rs, more=1)):
-            sc = np.ctypeslib.as_array(r.score, shape=(r.ncand,)).copy() if r.ncand else np.zeros(0, dtype=np.float32)
-            res.append((sc, int(r.best), pth))
-        lib().scrappie_hip_free_map_multi_results(out, n)
-        return res
+        return Engine._map_multi(self, "map_crf_multi_batch", lib().scrappie_hip_map_crf_multi_batch, signals, candidates, model,
+                                 lambda: _crf_targets, dict(min_prob=min_prob, tempW=tempW, tempb=tempb), viterbi, path, 1)
 
     def map_to_reference(self, signals, references, model='rnnrf_r94', viterbi=True, path=False, min_prob=1e-5, tempW=1.0, tempb=1.0):
         """Where in its reference does each read lie?  Each read (trimmed, normalised float32 signal) of a flip-flop (CRF)

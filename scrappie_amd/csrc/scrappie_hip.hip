@@ -46,8 +46,11 @@
  *                        launch group's stage and the batch call (seq_win_run / seq_win_batch)
  *   sh_eng_map_crf.inc   mapping of flip-flop (CRF) reads to base sequences (per-read; the launch group of the batched call)
  *   sh_eng_map.inc       block-based mapping of posteriors to sequences (per-read and batched)
- *   sh_eng_map_pack.inc  one read against many candidate sequences, packed into workgroups (per-read and batched)
- *   sh_eng_map_crf_pack.inc  one flip-flop (CRF) read against many candidate sequences, packed into workgroups (per-read and batched)
+ *   sh_eng_cands.inc     what the two engines that score one read against many candidate sequences packed into workgroups share: the set of a cand
+ *                        array (cand_set_build), its packs and the left-over candidates of a launch (cand_run), the launch group with its second
+ *                        pass and the batch call (cand_group / cand_batch), the per-read symbol's tail (cand_one), the result type's release, form counts
+ *   sh_eng_map_pack.inc  the CandTraits of the transducer models (k_map_pack), their checks and entry points
+ *   sh_eng_map_crf_pack.inc  the CandTraits of the flip-flop (CRF) models (k_map_crf_pack), their checks and entry points
  *   sh_eng_edits.inc     what the two engines that score every single-base edit of a sequence share: forward rows, backward rows and one combining
  *                        pass per launch for a family's EditsTraits (edits_launch), the cut by a byte budget (edits_run), the per-read symbol's
  *                        tail (edits_one), the batch call (edits_batch), the result type's release, form counts and timing
@@ -358,6 +361,11 @@ struct DpBufs {
  * "crf_edits_budget_kb" / "map_edits_budget_kb"; 0: one launch per launch group); the last call's kernels by events, its launches and their row bytes. */
 struct EditsState { DBuf rd, seq, rows, res, base; HBuf h; size_t budget = 0; double ms[3] = {0, 0, 0}; size_t launches = 0, row_bytes = 0; };
 
+/* What an engine keeps for one family of candidates in packs (sh_eng_cands.inc): a launch's pack records, their cell words, first cells (k_map_pack's alone) and
+ * scores, scores on the host (grow-only); cells: what a pack holds (debug options "map_pack_cells" / "map_crf_pack_cells"; 0: every candidate through the
+ * per-candidate kernel, -1: the family's default). */
+struct PackState { DBuf rd, cell, first, score; HBuf h; int cells = -1; };
+
 /* fields of scrappie_hip_timing (and two figures of SH_HOST_STAMP) that a span between two profiling marks adds to: resolve_spans (sh_eng_load.inc) */
 enum SpanField { F_CONV = 0, F_AFFINE, F_GRU, F_FF, F_DECODE, F_BACKTRACE, F_TOTAL, F_FUSED, F_STITCH,
                  F_WAIT, F_LEAD,      /* how long the main stream waited for the prologue; how long before that the convolution had ended */
@@ -522,15 +530,12 @@ struct scrappie_hip_engine {
     HBuf h_dec_in, h_dec_out; DBuf d_dec[7];             /* decode_batch: posteriors in (a lone call; the queue's members fill the queue's own), paths + scores out */
     HBuf h_crf_in, h_crf_out; DBuf d_crf[4];             /* crf_batch */
     DpBufs dp_map; DBuf d_map_seq, d_map_band, d_map_post;       /* block-based mapping (sh_eng_map.inc): the records' buffers; codes, bands, a per-read call's dense posterior */
-    DBuf d_mpk_rd, d_mpk_cell, d_mpk_first, d_mpk_score; HBuf h_mpk;      /* candidates in packs (sh_eng_map_pack.inc): the packs, their cell words and first cells, scores; scores on the host */
-    int map_pack_cells = -1;         /* cells a pack of candidates holds (debug option "map_pack_cells"; 0: every candidate through k_map, -1: the default) */
+    PackState map_pack, map_crf_pack;      /* candidates in packs, of transducer reads (k_map_pack) and of flip-flop reads (k_map_crf_pack): sh_eng_cands.inc */
     DpBufs dp_mcl; DBuf d_mcl_seq, d_mcl_first;      /* sequence-local CRF mapping (sh_eng_map_crf_local.inc): the windows' buffers (final state: the end cell, an int2); codes, the second pass's firsts */
     DpBufs dp_ml; DBuf d_ml_seq, d_ml_lohi;      /* sequence-local transducer mapping (sh_eng_map_local.inc): the windows' buffers (final state: the end position and kind, an int2); codes, the second pass's (first, last) */
     int map_local_stride = -1;       /* entry positions a window of k_map_local owns (debug option "map_local_stride"; 0: one window, -1: the default) */
     DBuf d_cfd_rd, d_cfd_cell, d_cfd_score, d_cfd_pos, d_cfd_call; HBuf h_cfd;      /* motifs searched inside flip-flop reads (sh_eng_crf_find.inc): the packs, their cell words, scores, (begin, end), call scores; results on the host */
     int crf_find_cells = -1;         /* cells a pack of motifs holds (debug option "crf_find_cells"; -1: the default) */
-    DBuf d_mcp_rd, d_mcp_cell, d_mcp_score; HBuf h_mcp;      /* candidates of flip-flop reads in packs (sh_eng_map_crf_pack.inc): the packs, their cell words, scores; scores on the host */
-    int map_crf_pack_cells = -1;     /* cells a pack of candidates of a flip-flop read holds (debug option "map_crf_pack_cells"; 0: every candidate through k_map_crf, -1: the default) */
     EditsState crf_edits, map_edits; /* every single-base edit of a sequence against a flip-flop read and against a transducer read (sh_eng_edits.inc): one each, so that either family's timing outlives the other's calls */
     int map_crf_local_stride = -1;   /* start cells a window of k_map_crf_local owns (debug option "map_crf_local_stride"; 0: one window, -1: the default) */
     double map_ms[3] = {0, 0, 0};    /* scrappie_hip_map_batch: network + S1, k_map, k_map_walk + results, summed over the last call's launch groups */
@@ -686,6 +691,7 @@ extern "C" scrappie_hip_params scrappie_hip_default_params(void) {
 #include "sh_eng_win.inc"      /* shared by the three reference-local engines below: WinCut / win_cut, WinTraits, win_launch / win_run, win_lse, win_read_bytes; seq_win_run / seq_win_batch for the two map families */
 #include "sh_eng_map_crf.inc"      /* mapping of flip-flop reads to base sequences (sh_map_crf.h): map_crf_to_sequence_* on the process-default engine, the launch group scrappie_hip_map_batch runs for a CRF model */
 #include "sh_eng_map.inc"      /* block-based mapping (sh_map.h): map_to_sequence_* on the process-default engine, scrappie_hip_map_batch */
+#include "sh_eng_cands.inc"      /* shared by the two below: CandTraits, CandSet / cand_set_build, CandJob, cand_run, cand_one, cand_group / cand_batch, scrappie_hip_free_map_multi_results */
 #include "sh_eng_map_pack.inc"      /* one read against many candidate sequences (sh_map_pack.h): scrappie_hip_map_multi_batch, scrappie_hip_map_post_multi */
 #include "sh_eng_map_crf_pack.inc"      /* one flip-flop read against many candidate sequences (sh_map_crf_pack.h): scrappie_hip_map_crf_multi_batch, scrappie_hip_map_trans_multi */
 #include "sh_eng_edits.inc"      /* shared by the two below: EditsTraits, EditsJob, edits_launch / edits_run, edits_one, edits_batch, scrappie_hip_free_edits_results */

@@ -39,11 +39,11 @@ extern "C" int scrappie_hip_debug_option(scrappie_hip_engine *e, const char *nam
     else if (!strcmp(name, "tail_free_frac")) e->dbg_tail_free_frac = value / 1000.0;      /* what the helper engine's creation takes for the device's free share (in 1/1000) */
     else if (!strcmp(name, "squiggle_budget_kb")) e->dbg_squig_budget = value > 0 ? (size_t)value << 10 : 0;      /* device bytes per squiggle-matching launch (0: from free memory) */
     else if (!strcmp(name, "sqnet_budget_kb")) e->dbg_sqnet_budget = value > 0 ? (size_t)value << 10 : 0;      /* device bytes per squiggle-predicting launch (0: from free memory) */
-    else if (!strcmp(name, "map_pack_cells")) e->map_pack_cells = value < 0 ? -1 : value;      /* cells per pack of candidates (0: every candidate through k_map; -1: the default) */
+    else if (!strcmp(name, "map_pack_cells")) e->map_pack.cells = value < 0 ? -1 : value;      /* cells per pack of candidates (0: every candidate through k_map; -1: the default) */
     else if (!strcmp(name, "map_crf_local_stride")) e->map_crf_local_stride = value < 0 ? -1 : value;      /* start cells per window of k_map_crf_local (0: one window; -1: the default) */
     else if (!strcmp(name, "map_local_stride")) e->map_local_stride = value < 0 ? -1 : value;      /* entry positions per window of k_map_local (0: one window; -1: the default) */
     else if (!strcmp(name, "crf_find_cells")) e->crf_find_cells = value < 0 ? -1 : value;      /* cells per pack of motifs of k_crf_find (-1: the default) */
-    else if (!strcmp(name, "map_crf_pack_cells")) e->map_crf_pack_cells = value < 0 ? -1 : value;      /* cells per pack of candidates of k_map_crf_pack (0: every candidate through k_map_crf; -1: the default) */
+    else if (!strcmp(name, "map_crf_pack_cells")) e->map_crf_pack.cells = value < 0 ? -1 : value;      /* cells per pack of candidates of k_map_crf_pack (0: every candidate through k_map_crf; -1: the default) */
     else if (!strcmp(name, "squig_local_stride")) e->squig_local_stride = value < 0 ? -1 : value;      /* entry positions per window of k_squig_local (0: one window; -1: the default) */
     else if (!strcmp(name, "squig_pack_cells")) e->squig_pack_cells = value < 0 ? -1 : value;      /* cells per pack of candidate squiggles of k_squig_pack (0: every candidate through k_squig; -1: the default) */
     else if (!strcmp(name, "squig_pack_lone")) e->squig_pack_lone = value != 0;      /* 1: a candidate alone in its pack runs in k_squig_pack (0, the default: it takes k_squig) */

@@ -165,25 +165,29 @@ static int dp_run(scrappie_hip_engine *e, DpPlan<Rec> &pl, typename DpTraits<Rec
 /* sets of short sequences packed into workgroups                       */
 /* ------------------------------------------------------------------ */
 /* One cand array of a call as every read that points at it sees it: checked, packed and laid out as its kernel reads it, once.  A family derives
- * its set from this and fills it (how a candidate or motif becomes cell words is its own). */
-struct PackSet {
-    const scrappie_hip_map_target *cand = nullptr;
+ * its set from this and fills it (how a candidate or motif becomes cell words is its own).  PackSet: of block-mapping targets. */
+struct PackSpan { size_t cell, first, at, ncell, nitem; };       /* where a pack's cell words, its first cells and its members begin in cellw / firsts / packed */
+template <class Target_>
+struct PackSetOf {
+    using Target = Target_;
+    using Pack = PackSpan;
+    const Target *cand = nullptr;
     size_t n = 0;
     std::string why;                          /* why its first member that cannot be run cannot */
-    struct Pack { size_t cell, first, at, ncell, nitem; };       /* where its cell words, its first cells and its members begin in cellw / firsts / packed */
     std::vector<Pack> packs;
     std::vector<int> cellw, firsts;           /* (firsts: k_map_pack's alone) */
     std::vector<size_t> packed;               /* the members in pack order */
     size_t bytes = 0;                         /* device bytes a read of this set adds to a launch */
 };
+using PackSet = PackSetOf<scrappie_hip_map_target>;
 
 /* the sets of a call, one per distinct (cand, n), built on first sight; of[i]: read i's */
 template <class Set>
 struct PackSets {
-    std::map<std::pair<const scrappie_hip_map_target *, size_t>, std::unique_ptr<Set>> sets;
+    std::map<std::pair<const typename Set::Target *, size_t>, std::unique_ptr<Set>> sets;
     std::vector<const Set *> of;
     template <class Build>
-    const Set *get(const scrappie_hip_map_target *cand, size_t n, Build &&build) {
+    const Set *get(const typename Set::Target *cand, size_t n, Build &&build) {
         std::unique_ptr<Set> &cs = sets[std::make_pair(cand, n)];
         if (!cs) { cs.reset(new Set()); build(*cs); }
         return cs.get();

@@ -4,8 +4,8 @@
  * launch uploaded once (PackLaunch, sh_eng_post.inc), every pack of every read a workgroup of one k_squig_pack launch, the candidates too long for
  * a pack through k_squig on the same call (squig_run, sh_eng_squig.inc), scores back; with a path wanted, a second pass of squig_run on each
  * read's best candidate alone, so the path is scrappie_hip_squiggle_match_batch's by construction.  The packing itself is host arithmetic in
- * sh_host.c (scrappie_hip_squiggle_pack_plan, sh_squig_pack_layout).  No network runs, so nothing of PostCall / post_group applies; PackSets is
- * keyed on block-mapping targets, so the sets of a call are kept in a map of this file's own. */
+ * sh_host.c (scrappie_hip_squiggle_pack_plan, sh_squig_pack_layout).  No network runs, so nothing of PostCall / post_group applies; the sets of a
+ * call are PackSets' (sh_eng_post.inc). */
 
 #define SH_SQUIG_PACK_CELLS 512       /* cells a pack holds unless the debug option "squig_pack_cells" says otherwise: the fastest on 24 barcodes of 40 positions, 12.4 % ahead of 256 (profiles/squiggle_pack_rate.txt) */
 
@@ -15,20 +15,13 @@ extern "C" void scrappie_hip_squiggle_pack_form_counts(uint64_t forms[2]) {
     for (int k = 0; k < 2; k++) if (forms) forms[k] = g_squig_pack_forms[k].load(std::memory_order_relaxed);
 }
 
-/* one cand array of a call as every read that points at it sees it: checked, through sh_squiggle_tables and packed as k_squig_pack reads it, once
- * (the fields PackLaunch lays out are PackSet's; firsts stays empty) */
-struct SquigCandSet {
-    const scrappie_hip_squiggle_target *cand = nullptr;
-    size_t n = 0;
-    std::string why;                          /* why its first member that cannot be run cannot */
-    std::vector<PackSet::Pack> packs;
+/* a PackSet (sh_eng_post.inc) of candidate squiggles: checked, through sh_squiggle_tables and packed as k_squig_pack reads it, once; cellw holds per
+ * pack 7 ncell + 7 ncand words (sh_internal.h), floats as their bits; firsts stays empty; bytes: the read's samples apart */
+struct SquigCandSet : PackSetOf<scrappie_hip_squiggle_target> {
     std::vector<int> npiece;                  /* per pack */
-    std::vector<int> cellw, firsts;           /* per pack 7 ncell + 7 ncand words (sh_internal.h), floats as their bits */
-    std::vector<size_t> packed;               /* the members in pack order */
     std::vector<size_t> over;                 /* the candidates that take k_squig */
     size_t maxpos = 0;                        /* the longest candidate that can be matched */
     size_t lds = 0;                           /* dynamic LDS of its largest pack */
-    size_t bytes = 0;                         /* device bytes a read of this set adds to a launch, its samples apart */
 };
 
 static int squig_cand_ok(const char *fn, const scrappie_hip_squiggle_target &t) {
@@ -252,8 +245,9 @@ extern "C" int scrappie_hip_squiggle_match_multi_batch(scrappie_hip_engine *e, c
     { std::lock_guard<std::mutex> lk(e->mu); for (double &x : e->squig_ms) x = 0.0; }
     const bool vit = viterbi != 0, path = vit && want_path != 0;
     /* the candidates: one set per distinct cand array of the call */
-    std::map<std::pair<const scrappie_hip_squiggle_target *, size_t>, std::unique_ptr<SquigCandSet>> sets;
-    std::vector<const SquigCandSet *> setof(n, nullptr);
+    PackSets<SquigCandSet> sets;
+    std::vector<const SquigCandSet *> &setof = sets.of;
+    setof.assign(n, nullptr);
     for (size_t i = 0; i < n; i++) {
         const size_t nc = cands[i].ncand;
         out[i].score = (float *)malloc(std::max<size_t>(nc, 1) * sizeof(float));
@@ -261,9 +255,7 @@ extern "C" int scrappie_hip_squiggle_match_multi_batch(scrappie_hip_engine *e, c
         std::fill(out[i].score, out[i].score + nc, NAN);
         out[i].ncand = nc;
         if (!nc || !cands[i].cand) continue;
-        std::unique_ptr<SquigCandSet> &cs = sets[std::make_pair(cands[i].cand, nc)];
-        if (!cs) { cs.reset(new SquigCandSet()); squig_cand_set_build(*cs, fn, cands[i].cand, nc, p, squig_pack_cells(e), e->squig_pack_lone); }
-        setof[i] = cs.get();
+        setof[i] = sets.get(cands[i].cand, nc, [&](SquigCandSet &cs) { squig_cand_set_build(cs, fn, cands[i].cand, nc, p, squig_pack_cells(e), e->squig_pack_lone); });
     }
     /* a read is charged for its signal (once for the packs, once per candidate left to k_squig), its set's tables, pack records and scores, the
      * scratch rows of the candidates left to k_squig and, with a path, the second pass on its longest candidate */

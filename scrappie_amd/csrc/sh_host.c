@@ -717,6 +717,24 @@ bool are_bounds_sane(size_t const *low, size_t const *high, size_t nblock, size_
     return sh_bounds_sane(low, high, nblock, seqlen, 1) != 0;
 }
 
+/* The loop the four pack planners below share: member k of len[k] + per cells, in input order, into packs that open with `open` cells and hold
+ * at most pack_cells (at most maxc whatever is asked for); -1 entries where a member fits no pack or, with `empty`, has no length. */
+static long pack_plan(const size_t *len, size_t n, size_t pack_cells, size_t maxc, size_t per, size_t open, int empty, int *pack, long long *cell) {
+    if (!len || !pack || !cell) return 0;
+    if (pack_cells > maxc) pack_cells = maxc;
+    long np = 0;
+    size_t used = 0;                    /* cells of the open pack, np - 1; 0: none is open */
+    for (size_t k = 0; k < n; k++) {
+        if ((empty && len[k] == 0) || len[k] > maxc - per - open) { pack[k] = -1; cell[k] = -1; continue; }
+        const size_t c = len[k] + per;
+        if (used == 0 || used + c > pack_cells) { np++; used = open; }
+        pack[k] = (int)(np - 1);
+        cell[k] = (long long)used;
+        used += c;
+    }
+    return np;
+}
+
 /* Packs of candidates (k_map_pack, sh_map_pack.h): a candidate of L states takes L + 2 cells, a pack of ncell cells and ncand
  * candidates two rows of floats, a word per cell and ncand + 1 first cells in LDS. */
 size_t sh_map_pack_lds_bytes(size_t ncell, size_t ncand) { return (3 * ncell + ncand + 1) * 4; }
@@ -734,20 +752,7 @@ size_t scrappie_hip_map_pack_max_cells(void) {
  * cells than that is alone in its pack.  pack[k]: the candidate's pack, cell[k]: its first cell there; pack[k] = -1 (cell[k] = -1)
  * where its seqlen[k] + 2 cells exceed the most a pack may hold -- such a candidate takes k_map.  Returns the number of packs. */
 long scrappie_hip_map_pack_plan(const size_t *seqlen, size_t ncand, size_t pack_cells, int *pack, long long *cell) {
-    if (!seqlen || !pack || !cell) return 0;
-    const size_t maxc = scrappie_hip_map_pack_max_cells();
-    if (pack_cells > maxc) pack_cells = maxc;
-    long np = 0;
-    size_t used = 0;                    /* cells of the open pack, np - 1; 0: none is open */
-    for (size_t k = 0; k < ncand; k++) {
-        if (seqlen[k] > maxc - 2) { pack[k] = -1; cell[k] = -1; continue; }
-        const size_t c = seqlen[k] + 2;
-        if (used == 0 || used + c > pack_cells) { np++; used = 0; }
-        pack[k] = (int)(np - 1);
-        cell[k] = (long long)used;
-        used += c;
-    }
-    return np;
+    return pack_plan(seqlen, ncand, pack_cells, scrappie_hip_map_pack_max_cells(), 2, 0, 0, pack, cell);
 }
 
 /* Packs of candidate squiggles (k_squig_pack, sh_squig_pack.h; the word counts and the cell words: sh_internal.h). */
@@ -769,19 +774,7 @@ size_t scrappie_hip_squiggle_pack_max_cells(void) {
  * (cell[k] = -1) where npos[k] exceeds the most a pack may hold -- such a candidate takes k_squig -- or is 0.  Returns the number of
  * packs. */
 long scrappie_hip_squiggle_pack_plan(const size_t *npos, size_t ncand, size_t pack_cells, int *pack, long long *cell) {
-    if (!npos || !pack || !cell) return 0;
-    const size_t maxc = scrappie_hip_squiggle_pack_max_cells();
-    if (pack_cells > maxc) pack_cells = maxc;
-    long np = 0;
-    size_t used = 0;                    /* cells of the open pack, np - 1; 0: none is open */
-    for (size_t k = 0; k < ncand; k++) {
-        if (npos[k] == 0 || npos[k] > maxc) { pack[k] = -1; cell[k] = -1; continue; }
-        if (used == 0 || used + npos[k] > pack_cells) { np++; used = 0; }
-        pack[k] = (int)(np - 1);
-        cell[k] = (long long)used;
-        used += npos[k];
-    }
-    return np;
+    return pack_plan(npos, ncand, pack_cells, scrappie_hip_squiggle_pack_max_cells(), 0, 0, 1, pack, cell);
 }
 
 size_t sh_squig_pack_layout(const size_t *npos, size_t ncand, int *wa, int *wb, int *piece0, int *npiece) {
@@ -1031,20 +1024,7 @@ size_t scrappie_hip_crf_find_max_cells(void) {
  * an empty motif and where 5 + seqlen[k] + 4 cells exceed the most a pack may hold -- such a motif is not mapped.  Returns the
  * number of packs. */
 long scrappie_hip_crf_find_plan(const size_t *seqlen, size_t nmotif, size_t pack_cells, int *pack, long long *cell) {
-    if (!seqlen || !pack || !cell) return 0;
-    const size_t maxc = scrappie_hip_crf_find_max_cells();
-    if (pack_cells > maxc) pack_cells = maxc;
-    long np = 0;
-    size_t used = 0;                    /* cells of the open pack, np - 1; 0: none is open */
-    for (size_t k = 0; k < nmotif; k++) {
-        if (seqlen[k] == 0 || seqlen[k] > maxc - 9) { pack[k] = -1; cell[k] = -1; continue; }
-        const size_t c = seqlen[k] + 4;
-        if (used == 0 || used + c > pack_cells) { np++; used = 5; }
-        pack[k] = (int)(np - 1);
-        cell[k] = (long long)used;
-        used += c;
-    }
-    return np;
+    return pack_plan(seqlen, nmotif, pack_cells, scrappie_hip_crf_find_max_cells(), 4, 5, 1, pack, cell);
 }
 
 /* Packs of candidates a flip-flop read is mapped to (k_map_crf_pack, sh_map_crf_pack.h).  A pack of ncell cells keeps two columns of
@@ -1063,20 +1043,7 @@ size_t scrappie_hip_map_crf_pack_max_cells(void) {
  * there; pack[k] = -1 (cell[k] = -1) where its seqlen[k] + 1 cells exceed the most a pack may hold -- such a candidate takes
  * k_map_crf, and does not close the open pack.  Returns the number of packs. */
 long scrappie_hip_map_crf_pack_plan(const size_t *seqlen, size_t ncand, size_t pack_cells, int *pack, long long *cell) {
-    if (!seqlen || !pack || !cell) return 0;
-    const size_t maxc = scrappie_hip_map_crf_pack_max_cells();
-    if (pack_cells > maxc) pack_cells = maxc;
-    long np = 0;
-    size_t used = 0;                    /* cells of the open pack, np - 1; 0: none is open */
-    for (size_t k = 0; k < ncand; k++) {
-        if (seqlen[k] > maxc - 1) { pack[k] = -1; cell[k] = -1; continue; }
-        const size_t c = seqlen[k] + 1;
-        if (used == 0 || used + c > pack_cells) { np++; used = 0; }
-        pack[k] = (int)(np - 1);
-        cell[k] = (long long)used;
-        used += c;
-    }
-    return np;
+    return pack_plan(seqlen, ncand, pack_cells, scrappie_hip_map_crf_pack_max_cells(), 1, 0, 0, pack, cell);
 }
 
 /* Every single-base edit of a sequence against a flip-flop read (k_crf_edits_rows, k_crf_edits, sh_crf_edits.h): what a read of L

@@ -1,6 +1,7 @@
 """The two paths that every engine on a launch group's posterior or transitions shares (sh_eng_post.inc): the way out of a
 failed launch, and the refusal of a read whose signal leaves the supported range -- each through every family's entry point.
-Last, the two edits families behind their one driver (sh_eng_edits.inc): each keeps its own counters and timing."""
+Last, the two edits families behind their one driver (sh_eng_edits.inc): each keeps its own counters and timing; and the two
+candidate-pack families behind theirs (sh_eng_cands.inc): each keeps its own counters, buffers and pack size."""
 import numpy as np
 import pytest
 
@@ -41,6 +42,10 @@ def _families():
             run=lambda e, sigs, ids: e.map_to_sequences(sigs, cands, model="rgrgr_r94", viterbi=True, path=True),
             counts=sa.map_pack_form_counts, form=(True, True), per_group=1,
             empty=lambda r: len(r[0]) == 3 and np.all(np.isnan(r[0])) and r[1] == -1 and r[2] is None),
+        "map_to_sequences_crf-rnnrf_r94": dict(
+            run=lambda e, sigs, ids: e.map_to_sequences_crf(sigs, cands, model="rnnrf_r94", viterbi=True, path=True),
+            counts=sa.map_crf_pack_form_counts, form=(True, True), per_group=1,
+            empty=lambda r: len(r[0]) == 3 and np.all(np.isnan(r[0])) and r[1] == -1 and r[2] is None),
         "map_to_reference-rnnrf_r94": dict(
             run=lambda e, sigs, ids: e.map_to_reference(sigs, reference, model="rnnrf_r94", viterbi=True, path=True),
             counts=sa.map_crf_local_form_counts, form=(True, True, False), per_group=2,         # both passes
@@ -57,7 +62,8 @@ def _families():
 
 
 FAMILIES = _families()
-FAILED_LAUNCH = ["map_to_sequence-rnnrf_r94", "map_to_sequences-rgrgr_r94", "map_to_reference-rnnrf_r94", "find_sequences-rnnrf_r94"]
+FAILED_LAUNCH = ["map_to_sequence-rnnrf_r94", "map_to_sequences-rgrgr_r94", "map_to_sequences_crf-rnnrf_r94", "map_to_reference-rnnrf_r94",
+                 "find_sequences-rnnrf_r94"]
 
 
 def _same(a, b, where=()):
@@ -174,3 +180,46 @@ def test_edits_families_keep_their_own_state(eng):
     again_a = call_a()
     timing()
     _same((again_a, again_b), first)
+
+
+def test_pack_families_keep_their_own_state(eng):
+    """the two families of "one read against many candidates" run through one driver (sh_eng_cands.inc) and keep form counters,
+    buffers and pack size each of its own: a transducer call in packs of 64 cells (a candidate of 30 bases is 26 states and
+    28 cells, so the four make two packs of one launch) moves only its own counter; a flip-flop call with every candidate through
+    k_map_crf (map_crf_pack_cells 0) moves neither; the flip-flop call in packs moves only its own and gives the bits of the call
+    without packs; and the results do not depend on which family ran first.  All with the second pass for the path."""
+    rng = np.random.default_rng(89)
+    sigs = [synth.medmad_normalise(synth.synthetic_signal(n, 800 + i)) for i, n in enumerate((900, 1300, 1100))]
+    cands = [_bases(30, rng) for _ in range(4)]
+    moved = lambda now, before: {k: now[k] - before[k] for k in now if now[k] != before[k]}
+
+    def call(run, option, cells, own, other, launches):
+        before = own(), other()
+        assert len(before[0]) == 4 and len(before[1]) == 4
+        eng.debug_option(option, cells)
+        try:
+            res = run(sigs, cands, viterbi=True, path=True)
+        finally:
+            eng.debug_option(option, -1)
+        assert moved(own(), before[0]) == ({(True, True): launches} if launches else {})
+        assert moved(other(), before[1]) == {}
+        return res
+
+    tr, crf = sa.map_pack_form_counts, sa.map_crf_pack_form_counts
+    call_a = lambda: call(eng.map_to_sequences, "map_pack_cells", 64, tr, crf, 1)
+    call_b = lambda: call(eng.map_to_sequences_crf, "map_crf_pack_cells", 0, crf, tr, 0)
+    call_c = lambda: call(eng.map_to_sequences_crf, "map_crf_pack_cells", -1, crf, tr, 1)
+    try:
+        first = call_a(), call_b(), call_c()
+        _same(first[2], first[1])
+        for res in first:
+            assert len(res) == 3
+            for scores, best, path in res:
+                assert len(scores) == 4 and np.all(np.isfinite(scores)) and 0 <= best < 4 and path is not None
+        again_c = call_c()
+        again_b = call_b()
+        again_a = call_a()
+        _same((again_a, again_b, again_c), first)
+    finally:
+        eng.debug_option("map_pack_cells", -1)
+        eng.debug_option("map_crf_pack_cells", -1)
