@@ -910,6 +910,75 @@ void scrappie_hip_map_edits_form_counts(uint64_t forms[12]);
 /* the last scrappie_hip_map_edits_batch call on this engine, as scrappie_hip_crf_edits_timing */
 void scrappie_hip_map_edits_timing(scrappie_hip_engine *e, double ms[3], size_t *launches, size_t *row_bytes);
 
+/* The same in a band (the kernels' banded forms, sh_map_edits.h): a read that covers a window lies on a narrow diagonal of the lattice, and rows,
+ * traffic and sums are proportional to the cells visited.
+ *
+ * Definition (tests/test_map_edits_band_cpu.py restates it in numpy).  A band is what map_to_sequence_viterbi_banded / _forward_banded take: low,
+ * high of nblock entries over the n = L - k + 1 states, valid iff are_bounds_sane(low, high, nblock, n).  Block t leads from entry t to entry
+ * t + 1; cell q of entry t + 1 is admissible iff low[t] <= q < high[t].  Entry 0 has no cells, as above; START and END carry no band.  The
+ * definition of scrappie_hip_map_edits_batch holds with these changes and no other:
+ *   Rows.  F[t + 1][q] is the cell rule on the row of entry t where the cell is admissible and -BIG where it is not.  FS, the END chain, the end
+ *     rule and base read those masked rows and are otherwise unchanged.  G[NB][n - 1] = 0 only where that cell is admissible.  G[t][q] for t >= 1
+ *     is the unbanded recursion on the masked row of entry t + 1, and -BIG where cell q of entry t (band entry t - 1) is not admissible.  G[0]
+ *     is never read.
+ *   The edit's own M <= k middle columns Mc carry NO band: a band is given in the coordinates of the original sequence, and the new states have
+ *     none there.
+ *   The NAN rule and the sharing of the prefix's loads among the edits of a position are unchanged.
+ * Consequences:
+ *   Equivalence.  An edit's score is the score of the masked dynamic programme on the edited sequence in which cells idx < A keep the band of the
+ *     original cell idx, the suffix's cells keep the band of their original index j0 + (idx - J), and the M middle cells are free at every entry.
+ *   Full band.  With low[t] = 0 and high[t] = n at every block every output equals map_post_edits' bit for bit, Viterbi and forward: the banded
+ *     forms run the same operations (sh_me_mx, sh_me_mx_if, sh_lse) on the same operands in the same order.
+ *   A Viterbi band that contains the unbanded Viterbi path: base has the unbanded base's bits.
+ *   base is NOT map_to_sequence_viterbi_banded / _forward_banded's score.  The reference's banded functions keep stale cells outside the band and
+ *     assign two cells in block 0 from no source (sh_map.h describes it; k_map's banded form reproduces it literally and stays as it is); an edit
+ *     cannot be defined on top of that.  The edits use the clean masked programme above.
+ *   Identity substitution.  sub[i][seq[i]] is computed as any other substitution: its middle cells are free, so it may EXCEED base where the band
+ *     binds on them.
+ *   Ends.  A tight band can make edits at either end NAN -- the last positions where low[nblock - 1] == n: they close on cell n - 1 of entry
+ *     nblock.  That is a result, not an error; the caller chooses the half-width.
+ * Rows on the device: an entry's row holds its band's cells alone, cell q of entry t + 1 at float q - low[t], in rows of one pitch per read: the
+ * widest entry's cells and one slot -- FS in the forward matrix, the stores of threads without a cell in the backward one -- rounded up to 16
+ * floats (scrappie_hip_map_edits_band_pitch); two matrices of nblock + 1 such rows (scrappie_hip_map_edits_band_row_bytes).  The score rows of
+ * k_map_edits_rows stay in LDS by k_map's formula, so the limit stays scrappie_hip_map_edits_max_bases(k).  k_map_edits walks, per workgroup of 64
+ * or 256 positions (the default per form is the faster measured; the debug option "map_edits_band_width": 0 the default, 64, 256), only the blocks
+ * at which one of its positions can have an admissible prefix source or a join.
+ *
+ * scrappie_hip_map_edits_banded_batch: as scrappie_hip_map_edits_batch (same results, same free function, the network once per launch group,
+ * three launches); targets[i].poslow / poshigh hold nblock entries each for the read's nblock, or are both NULL: no band, run through the
+ * unbanded forms in a launch of their own.  One of the two alone: "a band needs both poslow and poshigh".  A read's cost in the cut into launch
+ * groups and under "map_edits_budget_kb" is its banded row bytes.  A band that is not valid for the read's block count and n (an array made for
+ * another block count is not) gets NAN for that read and the first reason as the error text; its neighbours are scored.  A flip-flop (CRF)
+ * model: -1.  scrappie_hip_map_edits_timing covers the call, row_bytes the bytes the launches kept.  scrappie_hip_map_edits_batch itself goes on
+ * refusing bands.
+ * map_post_edits_banded: a batch of one on a dense host log-posterior and the process-default engine, as map_post_edits; low and high are
+ * required. */
+int scrappie_hip_map_edits_banded_batch(scrappie_hip_engine *e, int model, const raw_table *reads, const scrappie_hip_map_target *targets, size_t n,
+                                        const scrappie_hip_params *p, int viterbi, scrappie_hip_edits_result *out);
+int map_post_edits_banded(const_scrappie_matrix logpost, float stay_pen, float skip_pen, float local_pen, const int *seq, size_t seqlen,
+                          const size_t *low, const size_t *high, int viterbi, float *base, float *sub, float *del, float *ins);
+/* Host only.  The band of half-width `halfwidth` states around a Viterbi path of k_map (path[t], t = 0 .. nblock - 1, as scrappie_hip_map_batch
+ * and map_to_sequence_viterbi return it: the state after block t, -1 in START and END): with p[t] the position -- 0 over the leading START
+ * entries, nstate - 1 over the trailing END entries -- low[t] = max(p - halfwidth, 0), high[t] = min(p + halfwidth + 1, nstate); low[0] = 0 and
+ * high[nblock - 1] = nstate are forced; nblock entries each.  For every path it accepts the result passes are_bounds_sane and contains the path.
+ * 0, or -1: a null or empty argument; halfwidth < 1 (a skip moves two states, so a half-width of 0 cannot pass are_bounds_sane); what is no path
+ * of such a sequence -- a value outside -1 .. nstate - 1, a step down or above 2, a -1 between positions, no position at all, a first position
+ * other than 0, a last other than nstate - 1. */
+int scrappie_hip_map_path_band(const int *path, size_t nblock, size_t nstate, size_t halfwidth, size_t *low, size_t *high);
+/* Host only (sh_host.c), as scrappie_hip_map_edits_pitch / _row_bytes / _plan for reads in bands: pitch, the floats of an entry's row (0: a null
+ * argument); row_bytes, the two matrices; plan, with low[i] / high[i] read i's band of nblock[i] entries (either NULL: the read has none and takes
+ * the unbanded pitch). */
+size_t scrappie_hip_map_edits_band_pitch(const size_t *low, const size_t *high, size_t nblock);
+size_t scrappie_hip_map_edits_band_row_bytes(const size_t *low, const size_t *high, size_t nblock);
+long long scrappie_hip_map_edits_band_plan(const size_t *seqlen, const size_t *nblock, const size_t *const *low, const size_t *const *high, size_t n,
+                                           size_t k, int *pitch, long long *rows, long long *res, long long *res_floats);
+/* launches of each banded form in this process: [0 .. 8) k_map_edits_rows indexed as scrappie_hip_map_edits_form_counts (which counts the unbanded
+ * forms alone), [8 .. 12) k_map_edits at 256 positions per workgroup and [12 .. 16) at 64, each at (viterbi ? 2 : 0) | (tiled ? 1 : 0) */
+void scrappie_hip_map_edits_band_form_counts(uint64_t forms[16]);
+/* private (scratch) bytes per lane of each banded form, as the runtime reports them for the loaded kernels, indexed as the form counts (needs a
+ * device; -1: the runtime gave no answer).  The forms are built to need none. */
+void scrappie_hip_map_edits_band_scratch(long long bytes[16]);
+
 /* Squiggle matching, batched (sh_eng_squig.inc): reads[i] (trimmed, normalised; mapped over [start, end)) against
  * targets[i], a predicted squiggle of npos columns of stride >= 3 floats (mean, log sd, dwell logit); out[i] belongs to
  * reads[i].  No network runs and no model is needed (the squiggles are an input here: scrappie_hip_squiggle_predict_batch

@@ -421,6 +421,20 @@ def lib():
     L.scrappie_hip_crf_edits_band_scratch.argtypes = [C.POINTER(C.c_longlong)]
     L.scrappie_hip_map_edits_batch.argtypes = L.scrappie_hip_map_crf_edits_batch.argtypes
     L.map_post_edits.argtypes = [PM, C.c_float, C.c_float, C.c_float, ip, C.c_size_t, C.c_int, fp, fp, fp, fp]
+    L.scrappie_hip_map_edits_banded_batch.argtypes = L.scrappie_hip_map_crf_edits_batch.argtypes
+    L.map_post_edits_banded.argtypes = [PM, C.c_float, C.c_float, C.c_float, ip, C.c_size_t, sp, sp, C.c_int, fp, fp, fp, fp]
+    L.scrappie_hip_map_path_band.argtypes = [ip, C.c_size_t, C.c_size_t, C.c_size_t, sp, sp]
+    L.scrappie_hip_map_edits_band_pitch.restype = C.c_size_t
+    L.scrappie_hip_map_edits_band_pitch.argtypes = [sp, sp, C.c_size_t]
+    L.scrappie_hip_map_edits_band_row_bytes.restype = C.c_size_t
+    L.scrappie_hip_map_edits_band_row_bytes.argtypes = [sp, sp, C.c_size_t]
+    L.scrappie_hip_map_edits_band_plan.restype = C.c_longlong
+    L.scrappie_hip_map_edits_band_plan.argtypes = [sp, sp, C.POINTER(sp), C.POINTER(sp), C.c_size_t, C.c_size_t, ip, C.POINTER(C.c_longlong),
+                                                   C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    L.scrappie_hip_map_edits_band_form_counts.restype = None
+    L.scrappie_hip_map_edits_band_form_counts.argtypes = [C.POINTER(C.c_uint64)]
+    L.scrappie_hip_map_edits_band_scratch.restype = None
+    L.scrappie_hip_map_edits_band_scratch.argtypes = [C.POINTER(C.c_longlong)]
     L.scrappie_hip_map_edits_pitch.restype = C.c_size_t
     L.scrappie_hip_map_edits_pitch.argtypes = [C.c_size_t, C.c_size_t]
     L.scrappie_hip_map_edits_row_bytes.restype = C.c_size_t
@@ -1456,6 +1470,33 @@ def map_crf_path_band(path, seq_len, halfwidth):
     return [lo, hi]
 
 
+def map_path_band(path, nstate, halfwidth):
+    """(low, high) uintp arrays, nblock entries each: the band of half-width `halfwidth` >= 1 states around a Viterbi path of a
+    transducer model, as `map_post_to_sequence(..., viterbi=True, path=True)` and `Engine.map_to_sequence(..., path=True)` return
+    it (path[t]: the state after block t, -1 in START and END) against `nstate` = len(seq) - k + 1 k-mer states
+    (scrappie_hip_map_path_band): with p the position -- 0 over the leading -1s, nstate - 1 over the trailing ones --
+    low = max(p - halfwidth, 0), high = min(p + halfwidth + 1, nstate), low[0] = 0, high[-1] = nstate; always a band that
+    `are_bounds_sane` accepts and that holds the path.  ValueError where `path` is no path of such a sequence or halfwidth < 1."""
+    p = np.ascontiguousarray(path, dtype=np.int32)
+    if p.ndim != 1 or len(p) < 1 or halfwidth < 1 or nstate < 1:
+        raise ValueError("a path has nblock >= 1 entries, a sequence at least one state, and a half-width is at least 1")
+    lo, hi = np.zeros(len(p), dtype=np.uintp), np.zeros(len(p), dtype=np.uintp)
+    sp = C.POINTER(C.c_size_t)
+    if lib().scrappie_hip_map_path_band(p.ctypes.data_as(C.POINTER(C.c_int)), len(p), int(nstate), int(halfwidth), lo.ctypes.data_as(sp),
+                                        hi.ctypes.data_as(sp)) != 0:
+        raise ValueError("not a path of a sequence of %d states: -1s, then 0 .. %d in steps of 0, 1 or 2, then -1s" % (nstate, nstate - 1))
+    return [lo, hi]
+
+
+def _map_band(bands, nblock, nstate):
+    """`bands` of one transducer read as a (low, high) pair of contiguous uintp arrays: an int is scrappy's `diagonal_bands`"""
+    if isinstance(bands, (int, np.integer)):
+        return diagonal_bands(int(bands), nblock, nstate)
+    if len(bands) != 2:
+        raise ValueError('`bands` should be `None`, an integer, or length 2.')
+    return [np.ascontiguousarray(x, dtype=np.uintp) for x in bands]
+
+
 def _crf_band(bands, nblock, seq_len):
     """`bands` of one read as a (low, high) pair of contiguous uintp arrays: an int is the half-width of the diagonal band"""
     if isinstance(bands, (int, np.integer)):
@@ -1609,6 +1650,30 @@ def map_edits_form_counts():
     return _edits_form_counts(lib().scrappie_hip_map_edits_form_counts)
 
 
+def _map_edits_band_forms(q):
+    out = {('rows', bool(k & 4), bool(k & 2), bool(k & 1)): int(q[k]) for k in range(8)}
+    for j, w in enumerate((256, 64)):
+        out.update({('edits', bool(k & 2), bool(k & 1), w): int(q[8 + 4 * j + k]) for k in range(4)})
+    return out
+
+
+def map_edits_band_form_counts():
+    """Launches of each banded form of the transducer edit kernels in this process so far (scrappie_hip_map_edits_band_form_counts):
+    {('rows', viterbi, tiled, backward): n, ('edits', viterbi, tiled, width): n}, width 256 or 64 positions per workgroup;
+    `map_edits_form_counts` counts the unbanded forms alone."""
+    q = (C.c_uint64 * 16)()
+    lib().scrappie_hip_map_edits_band_form_counts(q)
+    return _map_edits_band_forms(q)
+
+
+def map_edits_band_scratch():
+    """Private (scratch) bytes per lane of each banded form, keyed as `map_edits_band_form_counts` keys them, as the runtime reports
+    them for the loaded kernels (scrappie_hip_map_edits_band_scratch; needs a GPU): the forms are built to need none."""
+    q = (C.c_longlong * 16)()
+    lib().scrappie_hip_map_edits_band_scratch(q)
+    return _map_edits_band_forms(q)
+
+
 def _edits_plan(seqlens, nblocks, plan):
     a = np.ascontiguousarray(seqlens, dtype=np.uintp)
     b = np.ascontiguousarray(nblocks, dtype=np.uintp)
@@ -1666,7 +1731,37 @@ def map_edits_plan(seqlens, nblocks, kmer_len):
     return out
 
 
-def map_post_edits(post, seq, stay_pen=0, skip_pen=0, local_pen=4.0, viterbi=True):
+def map_edits_band_row_bytes(low, high):
+    """Device bytes of the two row matrices of a transducer read in the band (low, high), nblock entries each
+    (scrappie_hip_map_edits_band_row_bytes): an entry's row holds its band's cells alone."""
+    lo, hi = (np.ascontiguousarray(x, dtype=np.uintp) for x in (low, high))
+    if len(lo) != len(hi) or len(lo) < 1:
+        raise ValueError("low and high hold nblock >= 1 entries each")
+    sp = C.POINTER(C.c_size_t)
+    return int(lib().scrappie_hip_map_edits_band_row_bytes(lo.ctypes.data_as(sp), hi.ctypes.data_as(sp), len(lo)))
+
+
+def map_edits_band_plan(seqlens, bands, kmer_len):
+    """`map_edits_plan` for reads in bands (scrappie_hip_map_edits_band_plan): `bands[i]` is read i's (low, high), nblock entries
+    each -- the block count is the band's --, or (nblock, None) for a read without a band, which takes the unbanded pitch.  The
+    pitch of a read in a band is that of the band's widest entry."""
+    bands = [b if b[1] is None else [np.ascontiguousarray(x, dtype=np.uintp) for x in b] for b in bands]
+    if len(bands) != len(seqlens) or any(len(b) != 2 or (b[1] is not None and (len(b[0]) != len(b[1]) or len(b[0]) < 1)) for b in bands):
+        raise ValueError("one (low, high) pair of nblock >= 1 entries each, or (nblock, None), per sequence length")
+    sp = C.POINTER(C.c_size_t)
+    n = len(bands)
+    lo, hi = (sp * max(n, 1))(), (sp * max(n, 1))()
+    for i, b in enumerate(bands):
+        if b[1] is not None:
+            lo[i], hi[i] = b[0].ctypes.data_as(sp), b[1].ctypes.data_as(sp)
+    out = _edits_plan(seqlens, [int(b[0]) if b[1] is None else len(b[0]) for b in bands],
+                      lambda a, nb, cnt, *rest: lib().scrappie_hip_map_edits_band_plan(a, nb, lo, hi, cnt, kmer_len, *rest))
+    if out[3] < 0:
+        raise ValueError("a sequence of fewer than %d bases holds no k-mer" % kmer_len)
+    return out
+
+
+def map_post_edits(post, seq, stay_pen=0, skip_pen=0, local_pen=4.0, viterbi=True, bands=None):
     """Every single-base edit of `seq` (a base string, or an array of base codes 0..3) scored against a read's posterior under a
     transducer model (a `ScrappyMatrix` of 4^k + 1 log-probabilities per block, k = 1 .. 5, as `calc_post` gives) in one pass on
     the GPU (map_post_edits: a forward sweep, a backward sweep, one combining pass).  Returns (base, sub, dele, ins) numbered by
@@ -1674,7 +1769,12 @@ def map_post_edits(post, seq, stay_pen=0, skip_pen=0, local_pen=4.0, viterbi=Tru
     edits are what `map_post_to_sequence` gives for the edited sequence up to float32 rounding (confirm chosen edits with
     `map_post_to_sequences`, which is exact).  NaN: the edited sequence admits no path through the read or has fewer than k
     bases; everything is NaN, and `last_error()` says why, where `seq` cannot be scored (empty, shorter than a k-mer, not bases,
-    too long for k_map_edits)."""
+    too long for k_map_edits).
+    `bands`: None, an int (scrappy's `diagonal_bands` over the n = len(seq) - k + 1 states, as `map_post_to_sequence` reads it) or a
+    (low, high) pair of nblock entries each, from `map_path_band` for one: the edits are scored inside the band
+    (map_post_edits_banded) -- every state of the original sequence keeps its band, the edit's own new states are free; base is then
+    the score of the masked programme, which is NOT `map_post_to_sequence(..., bands=bands)`'s (that keeps the reference's stale
+    cells); a band that is not valid is a ValueError."""
     if not isinstance(post, ScrappyMatrix):
         raise TypeError('`post` should be a ScrappyMatrix.')
     nblock, nstate = post.shape
@@ -1685,8 +1785,21 @@ def map_post_edits(post, seq, stay_pen=0, skip_pen=0, local_pen=4.0, viterbi=Tru
     base = C.c_float(float('nan'))
     sub, dele, ins = (np.full(k, np.nan, dtype=np.float32) for k in (4 * L, max(L, 1), 4 * (L + 1)))
     fp = C.POINTER(C.c_float)
-    if lib().map_post_edits(post.data(), stay_pen, skip_pen, local_pen, tgs[0].seq, L, 1 if viterbi else 0, C.byref(base),
-                            sub.ctypes.data_as(fp), dele.ctypes.data_as(fp), ins.ctypes.data_as(fp)) != 0:
+    kmer_len = guess_state_properties(nstate)[1]
+    if bands is not None and L >= kmer_len:
+        n = L - kmer_len + 1
+        lo, hi = _map_band(bands, nblock, n)
+        if len(lo) != nblock or len(hi) != nblock:
+            raise ValueError('Supplied banding structure is not valid: nblock entries each.')
+        p_lo, p_hi = (x.ctypes.data_as(C.POINTER(C.c_size_t)) for x in (lo, hi))
+        if not lib().are_bounds_sane(p_lo, p_hi, nblock, n):
+            raise ValueError('Supplied banding structure is not valid.')
+        rc = lib().map_post_edits_banded(post.data(), stay_pen, skip_pen, local_pen, tgs[0].seq, L, p_lo, p_hi, 1 if viterbi else 0, C.byref(base),
+                                         sub.ctypes.data_as(fp), dele.ctypes.data_as(fp), ins.ctypes.data_as(fp))
+    else:
+        rc = lib().map_post_edits(post.data(), stay_pen, skip_pen, local_pen, tgs[0].seq, L, 1 if viterbi else 0, C.byref(base),
+                                  sub.ctypes.data_as(fp), dele.ctypes.data_as(fp), ins.ctypes.data_as(fp))
+    if rc != 0:
         raise RuntimeError('An unknown error occurred while scoring edits: ' + last_error())
     return np.float32(base.value), sub.reshape(L, 4), dele[:L], ins.reshape(L + 1, 4)
 
@@ -2073,10 +2186,11 @@ class Prep(object):
         return {"gather_ms": t[0], "h2d_ms": t[1], "k_p0_ms": t[2]}
 
 
-def _score_edits(eng, fn, name, signals, sequences, model, viterbi, bands=None, **params):
-    """one batch call of an edits engine: a shared sequence is encoded once; [(base, sub, dele, ins)].  `bands` (flip-flop models):
-    None, or per read None, an int or a (low, high) pair; the library reads nblock + 1 entries of each array, so a pair of any
-    other length goes in as nblock + 1 entries of an empty band, which it refuses for that read."""
+def _score_edits(eng, fn, name, signals, sequences, model, viterbi, bands=None, kmer_len=0, **params):
+    """one batch call of an edits engine: a shared sequence is encoded once; [(base, sub, dele, ins)].  `bands`: None, or per read
+    None, an int or a (low, high) pair; the library reads nblock + 1 entries of each array (a transducer model, `kmer_len` -1 -- the
+    model's own, asked of the engine once the arguments have passed --: nblock entries, over the L - kmer_len + 1 states), so a pair
+    of any other length goes in as that many entries of an empty band, which it refuses for that read."""
     n = len(signals)
     if isinstance(sequences, str) or (len(sequences) and np.ndim(sequences[0]) == 0 and not isinstance(sequences[0], str)):
         sequences = [sequences] * n
@@ -2084,6 +2198,9 @@ def _score_edits(eng, fn, name, signals, sequences, model, viterbi, bands=None, 
     if len(sequences) != n:
         raise ValueError("one sequence for all signals, or one sequence per signal")
     h = eng._models[model]
+    if kmer_len < 0:
+        nstate = lib().scrappie_hip_model_states(eng._h, h)
+        kmer_len = 1 if nstate == 25 else guess_state_properties(nstate)[1]      # (a flip-flop model: refused by the library)
     rts, keep = _raw_tables(signals)
     made = {}
     tgs = (_MapTarget * max(n, 1))()
@@ -2094,11 +2211,12 @@ def _score_edits(eng, fn, name, signals, sequences, model, viterbi, bands=None, 
     if bands is not None:
         for i, b in enumerate(bands):
             nblock, L = eng.read_blocks(model, len(keep[i])), int(tgs[i].seqlen)
-            if b is None or nblock <= 0 or L == 0:          # (a read too short or an empty sequence is refused by the library as it is)
+            if b is None or nblock <= 0 or L == 0 or L < kmer_len:      # (a read too short or a sequence that holds nothing is refused by the library as it is)
                 continue
-            lo, hi = _crf_band(b, nblock, L)
-            if len(lo) != nblock + 1 or len(hi) != nblock + 1:
-                lo, hi = np.zeros(nblock + 1, dtype=np.uintp), np.zeros(nblock + 1, dtype=np.uintp)
+            nent = nblock if kmer_len else nblock + 1
+            lo, hi = _map_band(b, nblock, L - kmer_len + 1) if kmer_len else _crf_band(b, nblock, L)
+            if len(lo) != nent or len(hi) != nent:
+                lo, hi = np.zeros(nent, dtype=np.uintp), np.zeros(nent, dtype=np.uintp)
             keep += [lo, hi]
             tgs[i].poslow = lo.ctypes.data_as(C.POINTER(C.c_size_t))
             tgs[i].poshigh = hi.ctypes.data_as(C.POINTER(C.c_size_t))
@@ -2687,15 +2805,24 @@ class Engine(object):
                             bands=Engine._bands_per_read(bands, len(signals)), min_prob=min_prob, tempW=tempW, tempb=tempb)
 
     def score_edits_transducer(self, signals, sequences, model='rgrgr_r94', viterbi=False, stay_pen=0.0, skip_pen=0.0, local_pen=4.0,
-                               min_prob=1e-5, tempW=1.0, tempb=1.0):
+                               min_prob=1e-5, tempW=1.0, tempb=1.0, bands=None):
         """`score_edits` for the transducer models (scrappie_hip_map_edits_batch; k_map_edits_rows, k_map_edits): each read
         against EVERY single-base edit of its sequence under `map_to_sequence`'s lattice with these penalties -- an edit of one
         base changes up to k consecutive k-mer states.  The network and S1 run once per read.  `sequences`: one base string (or
         array of base codes) for all reads, or one per read.  Returns [(base, sub, dele, ins)] in input order as
         `map_post_edits` gives them, numbered by `apply_edit`; base is `map_to_sequence`'s score of the sequence itself.  A
-        read or a sequence that cannot be scored has everything NaN (`last_error()` names the first)."""
-        return _score_edits(self, lib().scrappie_hip_map_edits_batch, "map_edits_batch", signals, sequences, model, viterbi,
-                                 min_prob=min_prob, tempW=tempW, tempb=tempb, stay_pen=stay_pen, skip_pen=skip_pen, local_pen=local_pen)
+        read or a sequence that cannot be scored has everything NaN (`last_error()` names the first).
+        `bands`: None (exactly the call above), an int (scrappy's `diagonal_bands` for the read's block count and the n = L - k + 1
+        states), a (low, high) pair of nblock entries each for all reads, or a list with None, an int or such a pair per read --
+        `map_path_band(path, n, halfwidth)` on the paths of `map_to_sequence(..., path=True)` makes them.  The edits are then
+        scored inside the bands (scrappie_hip_map_edits_banded_batch): rows, traffic and time go with the cells in the band; a read
+        with None takes the unbanded kernels; a band that is not valid for its read (or not of nblock entries) leaves that read
+        NaN.  base is then the masked programme's score, not `map_to_sequence(..., bands=...)`'s."""
+        pen = dict(min_prob=min_prob, tempW=tempW, tempb=tempb, stay_pen=stay_pen, skip_pen=skip_pen, local_pen=local_pen)
+        if bands is None:
+            return _score_edits(self, lib().scrappie_hip_map_edits_batch, "map_edits_batch", signals, sequences, model, viterbi, **pen)
+        return _score_edits(self, lib().scrappie_hip_map_edits_banded_batch, "map_edits_banded_batch", signals, sequences, model, viterbi,
+                            bands=Engine._bands_per_read(bands, len(signals)), kmer_len=-1, **pen)
 
     def _edits_timing(self, fn):
         t = (C.c_double * 3)()

@@ -537,6 +537,7 @@ struct scrappie_hip_engine {
     DBuf d_cfd_rd, d_cfd_cell, d_cfd_score, d_cfd_pos, d_cfd_call; HBuf h_cfd;      /* motifs searched inside flip-flop reads (sh_eng_crf_find.inc): the packs, their cell words, scores, (begin, end), call scores; results on the host */
     int crf_find_cells = -1;         /* cells a pack of motifs holds (debug option "crf_find_cells"; -1: the default) */
     EditsState crf_edits, map_edits; /* every single-base edit of a sequence against a flip-flop read and against a transducer read (sh_eng_edits.inc): one each, so that either family's timing outlives the other's calls */
+    int map_edits_band_width = 0;    /* positions per workgroup of the banded k_map_edits: 64 or 256; 0: the default of the form (debug option "map_edits_band_width") */
     int map_crf_local_stride = -1;   /* start cells a window of k_map_crf_local owns (debug option "map_crf_local_stride"; 0: one window, -1: the default) */
     double map_ms[3] = {0, 0, 0};    /* scrappie_hip_map_batch: network + S1, k_map, k_map_walk + results, summed over the last call's launch groups */
     DpBufs dp_sq; DBuf d_sq_sig, d_sq_tab;       /* squiggle matching (sh_eng_squig.inc): the records' buffers; signals, tables */

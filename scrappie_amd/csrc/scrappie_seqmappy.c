@@ -29,6 +29,8 @@
  * scrappie_hip_map_crf_edits_banded_batch call in the bands of half-width N around those paths.  Without --band nothing changes.
  * --kmer-edits (transducer models): the same table from ONE scrappie_hip_map_edits_batch call (k_map_edits_rows, k_map_edits), under
  * --stay, --skip and --localpen.
+ * --kmer-edits --band N (N >= 1): each read mapped to the record's k-mer states with the path first (scrappie_hip_map_batch), then the same
+ * table from ONE scrappie_hip_map_edits_banded_batch call in the bands of half-width N states around those paths.
  */
 #define _GNU_SOURCE
 #include <getopt.h>
@@ -109,7 +111,9 @@ static void seqmappy_usage(FILE *fh) {
           "                             --stay, --skip and --localpen: an edit of one base changes up to k consecutive k-mer states\n"
           "                             (nan: the edited sequence admits no path through the read, or has fewer than k bases).\n"
           "                             Confirm an edit with --all-records.  Transducer models only (a flip-flop model: --edits); not\n"
-          "                             with any of the options above.\n", fh);
+          "                             with any of the options above.\n"
+          "                             --kmer-edits --band=N (N >= 1): as --edits --band, in the band of N k-mer states to either side\n"
+          "                             of the read's path through the record's states; S is the score of the masked programme.\n", fh);
 }
 
 /* --all-records: pair i's read against every record of its FASTA, all pairs in one scrappie_hip_map_multi_batch call; --each-record (crf):
@@ -248,9 +252,48 @@ static size_t **seqmappy_path_bands(scrappie_hip_engine *e, int h, const scrappi
     return bands;
 }
 
+/* --kmer-edits --band: the same for a transducer model of k-mers of klen bases.  The reads are mapped to the k-mer states of their sequences
+ * (scrappie_hip_map_batch, k_map: a path of nblock entries), the band of that half-width in states goes around each path
+ * (scrappie_hip_map_path_band) and becomes poslow / poshigh of the target tg[i], whose sequence stays the BASES.  A sequence shorter than a k-mer is
+ * mapped as an empty one: it gets no band and the edits call refuses it by its own rule. */
+static size_t **seqmappy_kmer_path_bands(scrappie_hip_engine *e, int h, const scrappie_hip_params *p, const raw_table *rts, scrappie_hip_map_target *tg,
+                                         size_t nb, size_t halfwidth, int klen) {
+    scrappie_hip_map_result *mp = calloc(nb, sizeof *mp);
+    scrappie_hip_map_target *st = calloc(nb, sizeof *st);
+    int **states = calloc(nb, sizeof *states);
+    size_t **bands = calloc(2 * nb, sizeof *bands);
+    int ok = mp && st && states && bands;
+    for (size_t i = 0; ok && i < nb; i++) {
+        if (tg[i].seqlen < (size_t)klen) continue;
+        const size_t ns = tg[i].seqlen - (size_t)klen + 1;
+        if (!(states[i] = malloc(ns * sizeof **states))) { ok = 0; break; }
+        for (size_t q = 0; q < ns; q++) {                    /* the first base the most significant (encode_bases_to_integers) */
+            int code = 0;
+            for (int j = 0; j < klen; j++) code = code * 4 + tg[i].seq[q + (size_t)j];
+            states[i][q] = code;
+        }
+        st[i].seq = states[i]; st[i].seqlen = ns;
+    }
+    if (ok && scrappie_hip_map_batch(e, h, rts, st, nb, p, 1, 1, mp) != 0) ok = 0;      /* (a failed call has released its results) */
+    for (size_t i = 0; ok && i < nb; i++) {
+        if (!mp[i].path || !st[i].seqlen) continue;
+        size_t *lo = malloc(mp[i].nblock * sizeof *lo), *hi = malloc(mp[i].nblock * sizeof *hi);
+        if (lo && hi && scrappie_hip_map_path_band(mp[i].path, mp[i].nblock, st[i].seqlen, halfwidth, lo, hi) == 0) {
+            bands[2 * i] = lo; bands[2 * i + 1] = hi;
+            tg[i].poslow = lo; tg[i].poshigh = hi;
+        } else { free(lo); free(hi); }
+    }
+    if (ok) scrappie_hip_free_map_results(mp, nb);
+    for (size_t i = 0; states && i < nb; i++) free(states[i]);
+    free(states); free(st); free(mp);
+    if (!ok) { free(bands); return NULL; }
+    return bands;
+}
+
 /* --edits (klen 0) and --kmer-edits (klen: the bases of the transducer model's k-mer): every single-base edit of the first record of pair i's FASTA
  * against pair i's read, all pairs in one scrappie_hip_map_crf_edits_batch or scrappie_hip_map_edits_batch call; band >= 0 (--band): the flip-flop
- * table from scrappie_hip_map_crf_edits_banded_batch in the bands of that half-width around the reads' Viterbi paths */
+ * table from scrappie_hip_map_crf_edits_banded_batch, the transducer one from scrappie_hip_map_edits_banded_batch, in the bands of that half-width
+ * around the reads' Viterbi paths */
 static int seqmappy_edits(scrappie_hip_engine *e, int h, const scrappie_hip_params *p, char **fasta, size_t npair, FILE *out,
                           int trim_start, int trim_end, int varseg_chunk, float varseg_thresh, int klen, long band) {
     const char *const opt = klen ? "--kmer-edits" : "--edits";
@@ -277,9 +320,9 @@ static int seqmappy_edits(scrappie_hip_engine *e, int h, const scrappie_hip_para
         nb++;
     }
     int failed = 0;                         /* a batch call failed as a whole: its text is the engine's */
-    if (nb && band >= 0 && !(bands = seqmappy_path_bands(e, h, p, rts, tg, nb, (size_t)band))) failed = 1;
+    if (nb && band >= 0 && !(bands = klen ? seqmappy_kmer_path_bands(e, h, p, rts, tg, nb, (size_t)band, klen) : seqmappy_path_bands(e, h, p, rts, tg, nb, (size_t)band))) failed = 1;
     if (nb && !failed)
-        failed = (klen ? scrappie_hip_map_edits_batch(e, h, rts, tg, nb, p, 1, res) :
+        failed = (klen ? (band >= 0 ? scrappie_hip_map_edits_banded_batch(e, h, rts, tg, nb, p, 1, res) : scrappie_hip_map_edits_batch(e, h, rts, tg, nb, p, 1, res)) :
                   band >= 0 ? scrappie_hip_map_crf_edits_banded_batch(e, h, rts, tg, nb, p, 1, res) : scrappie_hip_map_crf_edits_batch(e, h, rts, tg, nb, p, 1, res)) != 0;
     if (failed) {
         fprintf(stderr, "scrappie: %s\n", scrappie_hip_last_error());
@@ -425,7 +468,11 @@ int main_seqmappy(int argc, char **argv) {
     if (nargs <= 0) { seqmappy_usage(stderr); return EXIT_FAILURE; }
     if (nargs % 2) { fprintf(stderr, "scrappie: fast5 file is a required argument\n"); return EXIT_FAILURE; }    /* scrappie_seqmappy.c:153 */
     const size_t npair = (size_t)nargs / 2;
-    if (band >= 0 && !edits) { fprintf(stderr, "scrappie: --band is the band of --edits; it needs --edits\n"); return EXIT_FAILURE; }
+    if (band >= 0 && !edits && !kmer_edits) { fprintf(stderr, "scrappie: --band is the band of --edits (a transducer model: of --kmer-edits); it needs --edits\n"); return EXIT_FAILURE; }
+    if (band == 0 && kmer_edits) {
+        fprintf(stderr, "scrappie: --kmer-edits --band wants a half-width of at least 1 state: a skip moves two states, so a half-width of 0 cannot hold a path\n");
+        return EXIT_FAILURE;
+    }
     if (kmer_edits && (edits || all_records || inside || find || within || each_record)) {
         fprintf(stderr, "scrappie: --kmer-edits scores every single-base edit of the first record of a fasta; it cannot be combined with %s\n",
                 edits ? "--edits" : all_records ? "--all-records" : inside ? "--inside" : find ? "--find" : within ? "--within" : "--each-record");
@@ -497,7 +544,7 @@ int main_seqmappy(int argc, char **argv) {
     if (kmer_edits) {
         int rc = EXIT_FAILURE;
         if (crf) fprintf(stderr, "scrappie: --kmer-edits scores reads of transducer models only; \"%s\" is a flip-flop (CRF) model (--edits)\n", model);
-        else rc = seqmappy_edits(e, h, &p, fasta, npair, out, trim_start, trim_end, varseg_chunk, varseg_thresh, klen, -1);
+        else rc = seqmappy_edits(e, h, &p, fasta, npair, out, trim_start, trim_end, varseg_chunk, varseg_thresh, klen, band);
         if (out != stdout) fclose(out);
         scrappie_hip_engine_destroy(e);
         return rc;

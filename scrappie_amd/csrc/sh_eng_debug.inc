@@ -18,7 +18,7 @@ static scrappie_hip_engine *default_engine();      /* (sh_eng_surface.inc) */
 /* Test hooks.  Options: "ff_separate" (S1 and the decoder as two kernels on this engine, whatever the shape),
  * "dump_final" (the decoders leave every tile's final scores, start and end state in the hand-over buffer). */
 extern "C" int scrappie_hip_debug_option(scrappie_hip_engine *e, const char *name, int value) {
-    if (!e && name && (!strcmp(name, "map_pack_cells") || !strcmp(name, "map_crf_local_stride") || !strcmp(name, "map_local_stride") || !strcmp(name, "crf_find_cells") || !strcmp(name, "map_crf_pack_cells") || !strcmp(name, "squig_pack_cells") || !strcmp(name, "squig_pack_lone") || !strcmp(name, "squig_local_stride"))) e = default_engine();      /* the per-read surface's engine has no handle */
+    if (!e && name && (!strcmp(name, "map_pack_cells") || !strcmp(name, "map_crf_local_stride") || !strcmp(name, "map_local_stride") || !strcmp(name, "crf_find_cells") || !strcmp(name, "map_crf_pack_cells") || !strcmp(name, "squig_pack_cells") || !strcmp(name, "squig_pack_lone") || !strcmp(name, "squig_local_stride") || !strcmp(name, "map_edits_band_width"))) e = default_engine();      /* the per-read surface's engine has no handle */
     if (!e || !name) return set_err("debug_option: null argument");
     if (e->any_pending()) return set_err("debug_option: launch groups are in flight");
     if (!strcmp(name, "ff_separate")) e->dbg_ff_separate = value != 0;
@@ -49,6 +49,10 @@ extern "C" int scrappie_hip_debug_option(scrappie_hip_engine *e, const char *nam
     else if (!strcmp(name, "squig_pack_lone")) e->squig_pack_lone = value != 0;      /* 1: a candidate alone in its pack runs in k_squig_pack (0, the default: it takes k_squig) */
     else if (!strcmp(name, "crf_edits_budget_kb")) e->crf_edits.budget = value > 0 ? (size_t)value << 10 : 0;      /* row and result bytes per launch of the three edit kernels (0: one launch per launch group) */
     else if (!strcmp(name, "map_edits_budget_kb")) e->map_edits.budget = value > 0 ? (size_t)value << 10 : 0;      /* the same for the three transducer edit kernels */
+    else if (!strcmp(name, "map_edits_band_width")) {        /* positions per workgroup of the banded k_map_edits: 64 or 256 (0: the default of the form) */
+        if (value != 0 && value != 64 && value != 256) return set_err("debug_option: map_edits_band_width is 0 (the default), 64 or 256");
+        e->map_edits_band_width = value;
+    }
     else if (!strcmp(name, "events_budget_samples")) e->dbg_events_budget = value > 0 ? (size_t)value : 0;      /* sample slots per event-detection launch (0: from free memory) */
     else return set_err("debug_option: unknown option '%s'", name);
     return 0;

@@ -1166,6 +1166,73 @@ long long scrappie_hip_map_edits_plan(const size_t *seqlen, const size_t *nblock
     return edits_plan(seqlen, nblock, n, k, pitch, rows, res, res_floats);
 }
 
+/* The same in a band (low, high: nblock entries each, as are_bounds_sane takes them; cell q of entry t + 1 admissible iff low[t] <= q < high[t]):
+ * an entry's row holds its band's cells alone, cell q of entry t + 1 at float q - low[t], and the row's last slot holds FS (forward) or takes the
+ * stores of threads without a cell (backward).  One pitch per read: the widest entry's cells and that slot, rounded up to 16 floats.  An entry that
+ * is empty or the wrong way round counts as one cell (the engine refuses a band that is not sane before it plans).  0: a null argument. */
+size_t scrappie_hip_map_edits_band_pitch(const size_t *low, const size_t *high, size_t nblock) {
+    size_t w = 1;
+    if (!low || !high) return 0;
+    for (size_t t = 0; t < nblock; t++)
+        if (high[t] > low[t] && high[t] - low[t] > w) w = high[t] - low[t];
+    return (w + 1 + 15) / 16 * 16;
+}
+size_t scrappie_hip_map_edits_band_row_bytes(const size_t *low, const size_t *high, size_t nblock) {
+    return 2 * (nblock + 1) * scrappie_hip_map_edits_band_pitch(low, high, nblock) * 4;
+}
+
+/* scrappie_hip_map_edits_plan for reads in bands: read i has the band low[i], high[i] (nblock[i] entries each); where either is NULL the read has
+ * no band and takes the unbanded pitch and rows.  Everything else as there. */
+long long scrappie_hip_map_edits_band_plan(const size_t *seqlen, const size_t *nblock, const size_t *const *low, const size_t *const *high, size_t n,
+                                           size_t k, int *pitch, long long *rows, long long *res, long long *res_floats) {
+    long long nrow = 0, nres = 0;
+    if (res_floats) *res_floats = 0;
+    if (!seqlen || !nblock || !low || !high || !pitch || !rows || !res) return 0;
+    if (k == 0) return -1;
+    for (size_t i = 0; i < n; i++)
+        if (seqlen[i] < k) return -1;
+    for (size_t i = 0; i < n; i++) {
+        const int band = low[i] && high[i];
+        const size_t p = band ? scrappie_hip_map_edits_band_pitch(low[i], high[i], nblock[i]) : scrappie_hip_map_edits_pitch(seqlen[i], k);
+        pitch[i] = (int)p;
+        rows[i] = nrow;
+        res[i] = nres;
+        nrow += (long long)(2 * (nblock[i] + 1) * p);
+        nres += (long long)crf_edits_res_floats(seqlen[i]);
+    }
+    if (res_floats) *res_floats = nres;
+    return nrow;
+}
+
+/* The band around a Viterbi path of k_map: path[t], t = 0 .. nblock - 1, the state after block t (0 .. nstate - 1; -1 in START and in END).  p[t] is
+ * the path's position: 0 over the leading START entries, nstate - 1 over the trailing END entries; low[t] = max(p - halfwidth, 0), high[t] =
+ * min(p + halfwidth + 1, nstate), and low[0] = 0, high[nblock - 1] = nstate whatever the path.  A path moves by 0, 1 or 2 states per block, so with
+ * halfwidth >= 1 low[t] <= p[t - 1] + 2 - halfwidth <= high[t - 1] and both edges are non-decreasing: always a band that are_bounds_sane accepts,
+ * and the path is inside it.  -1: a null or empty argument, halfwidth < 1 (a skip moves two states: a half-width of 0 cannot hold it), or what is
+ * no path of such a sequence -- a value outside -1 .. nstate - 1, a step down or above 2, a -1 between positions, no position at all, a first
+ * position other than 0 (START enters state 0 alone), a last other than nstate - 1. */
+int scrappie_hip_map_path_band(const int *path, size_t nblock, size_t nstate, size_t halfwidth, size_t *low, size_t *high) {
+    if (!path || !low || !high || nblock == 0 || nstate == 0 || halfwidth < 1) return -1;
+    size_t first = nblock, last = 0;
+    for (size_t t = 0; t < nblock; t++) {
+        if (path[t] < -1 || (long long)path[t] > (long long)nstate - 1) return -1;
+        if (path[t] >= 0) { if (first == nblock) first = t; last = t; }
+    }
+    if (first == nblock || path[first] != 0 || (size_t)path[last] != nstate - 1) return -1;
+    for (size_t t = first; t <= last; t++) {
+        if (path[t] < 0) return -1;
+        if (t > first && (path[t] < path[t - 1] || path[t] - path[t - 1] > 2)) return -1;
+    }
+    for (size_t t = 0; t < nblock; t++) {
+        const size_t p = t < first ? 0 : t > last ? nstate - 1 : (size_t)path[t];
+        low[t] = p > halfwidth ? p - halfwidth : 0;
+        high[t] = (halfwidth >= nstate || p + halfwidth + 1 > nstate) ? nstate : p + halfwidth + 1;
+    }
+    low[0] = 0;
+    high[nblock - 1] = nstate;
+    return 0;
+}
+
 /* the library defines it (scrappie_hip.hip); weak, so that this file also links into the host-only builds of the tests */
 void sh_set_error(const char *fmt, ...) __attribute__((weak, format(printf, 1, 2)));
 #define SH_ERR(...) do { if (sh_set_error) sh_set_error(__VA_ARGS__); } while (0)

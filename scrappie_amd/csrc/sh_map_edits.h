@@ -56,8 +56,8 @@ struct ShMapEditsRead {
     int pitch;          /* floats from one entry's row to the next (>= n + 1) */
 };
 
-struct ShMapEditsArgs {
-    const ShMapEditsRead *rd;
+template <class Rec> struct ShMapEditsArgsT {
+    const Rec *rd;
     const float *post;          /* dense posterior */
     const float *E, *sums;      /* tiled posterior */
     long long pstride;          /* dense: floats per row (a multiple of 4, at least 4 ceil(nr / 4)) */
@@ -71,6 +71,27 @@ struct ShMapEditsArgs {
     float *res;
     float *base;                /* [read] */
 };
+using ShMapEditsArgs = ShMapEditsArgsT<ShMapEditsRead>;
+
+/* A read in a band: low and high of nblock int32 each, as map_to_sequence_*_banded take them (in seq[] behind the codes): cell q of entry t + 1 is
+ * admissible iff low[t] <= q < high[t]; entry 0 has no cells.  An entry's row holds its band's cells alone, cell q of entry t + 1 at float q - low[t],
+ * and the slot at pitch - 1 holds FS (forward) or takes the stores of threads without a cell (backward): pitch is the widest entry's cells and that
+ * slot rounded up to 16 (scrappie_hip_map_edits_band_pitch). */
+struct ShMapEditsBandRead : ShMapEditsRead {
+    long long band;     /* offset in seq[] of low; high the next nblock */
+};
+struct ShMapEditsBandArgs : ShMapEditsArgsT<ShMapEditsBandRead> {
+    int width;          /* host only: the positions per workgroup of k_map_edits this launch takes (64 or 256) */
+};
+template <bool BAND> using ShMapEditsArgsOf = std::conditional_t<BAND, ShMapEditsBandArgs, ShMapEditsArgs>;
+
+/* the band of entry e of a read of NB blocks: [lo, hi); entry 0 has none */
+__device__ __forceinline__ void sh_me_band(const int *blo, int NB, int e, int &lo, int &hi) {
+    const int j = min(max(e - 1, 0), NB - 1);
+    lo = blo[j];
+    const int h = blo[NB + j];
+    hi = e >= 1 ? h : lo;
+}
 
 template <bool VIT> __device__ __forceinline__ float sh_me_mx(float a, float b) { return VIT ? (b > a ? b : a) : sh_lse(a, b); }
 /* mx(a, b) where on, else a: a select (Viterbi); forward, sh_lse with an operand so far below that it adds exactly nothing */
@@ -78,10 +99,10 @@ template <bool VIT> __device__ __forceinline__ float sh_me_mx_if(bool on, float 
     return VIT ? ((on && b > a) ? b : a) : sh_lse(a, on ? b : -4.0f * SH_MAP_BIG);
 }
 
-template <bool VIT, bool TILED, bool BACK>
-__global__ __launch_bounds__(SH_MAP_NTH) void k_map_edits_rows(ShMapEditsArgs a) {
+template <bool VIT, bool TILED, bool BACK, bool BAND = false>
+__global__ __launch_bounds__(SH_MAP_NTH) void k_map_edits_rows(ShMapEditsArgsOf<BAND> a) {
     extern __shared__ __attribute__((aligned(16))) float sh_me_lds[];
-    const ShMapEditsRead r = a.rd[blockIdx.x];
+    const auto r = a.rd[blockIdx.x];
     const int tid = threadIdx.x, n = r.nbase - a.k + 1, NB = r.nblock, RW = n + 2, START = n, END = n + 1, STAY = a.nr - 1;
     const long long P = r.pitch;
     const float stay_pen = a.stay_pen, skip_pen = a.skip_pen, local_pen = a.local_pen;
@@ -90,7 +111,21 @@ __global__ __launch_bounds__(SH_MAP_NTH) void k_map_edits_rows(ShMapEditsArgs a)
     int *const sq = (int *)(sh_me_lds + 2 * RW);
     for (int i = tid; i < n; i += SH_MAP_NTH) sq[i] = a.seq[r.seq + i];
     float *const grow = a.rows + r.rows + (BACK ? (long long)(NB + 1) * P : 0);
-    {
+    /* BAND: the band of the entry a step reads (lo_p, hi_p) and of the one it completes (lo_c, hi_c) */
+    const int *blo = nullptr;
+    int lo_p = 0, hi_p = 0, lo_c = 0, hi_c = 0;
+    if constexpr (BAND) {
+        blo = a.seq + r.band;
+        sh_me_band(blo, NB, BACK ? NB : 0, lo_p, hi_p);
+        sh_me_band(blo, NB, BACK ? NB - 1 : 1, lo_c, hi_c);
+        float *const g0 = grow + (BACK ? (long long)NB * P : 0);
+        for (int i = tid; i < RW; i += SH_MAP_NTH) {         /* the first row: entry 0 (no cells), or entry NB (cell n - 1 where it is admissible) */
+            buf0[i] = BACK ? ((i == n - 1 && i >= lo_p && i < hi_p) ? 0.0f : -SH_MAP_BIG) : (i == START ? 0.0f : -SH_MAP_BIG);
+            buf1[i] = -SH_MAP_BIG;
+        }
+        for (int i = tid; i < (int)P; i += SH_MAP_NTH)       /* (the slot at P - 1: FS[0] = 0; backward nothing reads it) */
+            g0[i] = BACK ? ((lo_p + i == n - 1 && lo_p + i < hi_p) ? 0.0f : -SH_MAP_BIG) : (i == (int)P - 1 ? 0.0f : -SH_MAP_BIG);
+    } else {
         float *const g0 = grow + (BACK ? (long long)NB * P : 0);
         for (int i = tid; i < RW; i += SH_MAP_NTH) {         /* the first row: entry 0, or entry NB */
             const float v = BACK ? (i == n - 1 ? 0.0f : -SH_MAP_BIG) : (i == START ? 0.0f : -SH_MAP_BIG);
@@ -115,7 +150,49 @@ __global__ __launch_bounds__(SH_MAP_NTH) void k_map_edits_rows(ShMapEditsArgs a)
         lp.block(ma, mr, t);
         const float lps = lp(STAY);
         const float ls = VIT ? fmaxf(-local_pen, lps) : sh_lse(-local_pen, lps);
-        for (int ch = 0; ch < nch; ch++) {
+        if constexpr (BAND) {                                /* the band's cells alone, from the 64-cell group of lo_c on, and at least one thread without a cell */
+            int lo_n, hi_n;
+            sh_me_band(blo, NB, BACK ? max(t - 1, 0) : min(t + 2, NB), lo_n, hi_n);      /* asked for before the barrier */
+            const int base = lo_c & ~63;
+            const int nchb = (hi_c - base + SH_MAP_NTH) / SH_MAP_NTH;
+            auto in_p = [&](int x) { return x >= lo_p && x < hi_p; };      /* cell x of the entry read */
+            for (int ch = 0; ch < nchb; ch++) {
+                const int pos = base + ch * SH_MAP_NTH + tid, q = min(pos, n - 1);
+                const bool valid = pos >= lo_c && pos < hi_c;
+                float v;
+                if (!BACK) {                                 /* k_map's unbanded cell on the masked row */
+                    const float l0 = p[q], l1 = p[max(q - 1, 0)], l2 = p[max(q - 2, 0)], ps = p[START];
+                    const float p0 = in_p(q) ? l0 : -SH_MAP_BIG, p1 = in_p(q - 1) ? l1 : -SH_MAP_BIG, p2 = in_p(q - 2) ? l2 : -SH_MAP_BIG;
+                    const float le = lp(sq[q]);
+                    float cell = (p0 - stay_pen) + lps;
+                    cell = sh_me_mx_if<VIT>(q >= 1, cell, p1 + le);
+                    cell = sh_me_mx_if<VIT>(q >= 2, cell, (p2 - skip_pen) + le);
+                    cell = sh_me_mx_if<VIT>(q == 0, cell, ps + le);
+                    v = valid ? cell : chain + ls;           /* the slot: FS[t + 1] */
+                } else {
+                    const int q1 = min(q + 1, n - 1), q2 = min(q + 2, n - 1);
+                    const float le1 = lp(sq[q1]), le2 = lp(sq[q2]);
+                    const float l0 = p[q], l1 = p[q1], l2 = p[q2];
+                    const float g0 = in_p(q) ? l0 : -SH_MAP_BIG, g1 = in_p(q1) ? l1 : -SH_MAP_BIG, g2 = in_p(q2) ? l2 : -SH_MAP_BIG;
+                    v = (lps - stay_pen) + g0;
+                    v = sh_me_mx_if<VIT>(q + 1 < n, v, le1 + g1);
+                    v = sh_me_mx_if<VIT>(q + 2 < n, v, (le2 - skip_pen) + g2);
+                    v = sh_me_mx_if<VIT>(q == n - 1, v, -local_pen + chain);
+                }
+                c[valid ? pos : n] = v;
+                g[valid ? (long long)(pos - lo_c) : P - 1] = v;      /* the row holds the band's cells; its last slot is no cell's */
+            }
+            if (!BACK && tid == 0) {                         /* END, reading cell n - 1 under its band */
+                float e = p[END] + ls;
+                const float pl = p[n - 1];
+                const float ex = (in_p(n - 1) ? pl : -SH_MAP_BIG) - local_pen;
+                if (VIT) { if (ex > e) e = ex; }
+                else e = sh_lse(e, ex);
+                c[END] = e;
+            }
+            lo_p = lo_c; hi_p = hi_c; lo_c = lo_n; hi_c = hi_n;
+        }
+        for (int ch = 0; !BAND && ch < nch; ch++) {
             const int pos = ch * SH_MAP_NTH + tid, q = min(pos, n - 1), at = min(pos, n);
             float v;
             if (!BACK) {                                     /* k_map's unbanded cell */
@@ -134,7 +211,7 @@ __global__ __launch_bounds__(SH_MAP_NTH) void k_map_edits_rows(ShMapEditsArgs a)
             c[at] = v;
             g[at] = v;
         }
-        if (!BACK && tid == 0) {                             /* END, as k_map keeps it */
+        if (!BAND && !BACK && tid == 0) {                    /* END, as k_map keeps it */
             float e = p[END] + ls;
             const float ex = p[n - 1] - local_pen;
             if (VIT) { if (ex > e) e = ex; }
@@ -146,7 +223,8 @@ __global__ __launch_bounds__(SH_MAP_NTH) void k_map_edits_rows(ShMapEditsArgs a)
     }
     if (!BACK && tid == 0) {
         const float *const f = (NB & 1) ? buf1 : buf0;
-        const float x = f[n - 1], y = f[END];
+        const float fx = f[n - 1], y = f[END];
+        const float x = (!BAND || (n - 1 >= lo_p && n - 1 < hi_p)) ? fx : -SH_MAP_BIG;      /* (BAND: entry NB's band) */
         a.base[blockIdx.x] = VIT ? fmaxf(x, y) : sh_lse(x, y);
     }
 }
@@ -198,12 +276,14 @@ template <int NS> __device__ __forceinline__ float sh_me_last(const float (&X)[N
     return c1;
 }
 
-template <bool VIT, bool TILED>
-__global__ __launch_bounds__(SH_MAP_NTH) void k_map_edits(ShMapEditsArgs a) {
+template <bool VIT, bool TILED, bool BAND = false, int W = SH_MAP_NTH>
+__global__ __launch_bounds__(W) void k_map_edits(ShMapEditsArgsOf<BAND> a) {
     extern __shared__ __attribute__((aligned(16))) float sh_me_cols[];      /* [2][SH_ME_CH][NRP] */
-    const ShMapEditsRead r = a.rd[blockIdx.x];
+    constexpr int NPC = ((1 << (2 * SH_ME_K - 2)) + 1 + W - 1) / W;         /* 16-byte pieces of a column per thread: 4^SH_ME_K + 1 states at most */
+    static_assert(W == SH_MAP_NTH ? NPC == SH_MAPL_PIECES : true, "a workgroup of SH_MAP_NTH stages as k_map_local does");
+    const auto r = a.rd[blockIdx.x];
     const int L = r.nbase, K = a.k, n = L - K + 1, NB = r.nblock, tid = threadIdx.x;
-    const int i0 = blockIdx.y * SH_MAP_NTH;
+    const int i0 = blockIdx.y * W;
     if (i0 > L) return;                                      /* (uniform) */
     const bool mine = i0 + tid <= L;
     const int i = min(i0 + tid, L);
@@ -211,10 +291,37 @@ __global__ __launch_bounds__(SH_MAP_NTH) void k_map_edits(ShMapEditsArgs a) {
     const float stay_pen = a.stay_pen, skip_pen = a.skip_pen, local_pen = a.local_pen;
     const long long P = r.pitch;
     const float *const F = a.rows + r.rows, *const G = F + (long long)(NB + 1) * P;
+    /* BAND: the workgroup walks blocks T0 .. T1 - 1 alone.  Before block T0 -- entry T0 the first whose band reaches the lowest cell a position of
+     * the workgroup takes a prefix value from, max(A(i0) - 2, 0): high[T0 - 1] > it; 0 where a position enters from START (i0 < K) -- every source is
+     * -SH_MAP_BIG: the middle columns and the running scores stay what they were set to.  From block T1 on -- low[T1] above the furthest cell a position
+     * joins, min(i1 + 2, n - 1) -- every G is -SH_MAP_BIG and nothing joins; NB where a position closes by END's chain (i1 >= n - 1).  Both edges
+     * are non-decreasing: two counts over the band. */
+    const int *blo = nullptr;
+    int T0 = 0, T1 = NB;
+    if constexpr (BAND) {
+        __shared__ int cnt[2];
+        blo = a.seq + r.band;
+        if (tid < 2) cnt[tid] = 0;
+        __syncthreads();
+        const int i1 = min(i0 + W - 1, L);
+        const int cmin = max(max(i0 - K + 1, 0) - 2, 0), cmax = min(i1 + 2, n - 1);
+        int below = 0, reach = 0;
+        for (int t = tid; t < NB; t += W) { below += blo[NB + t] <= cmin; reach += blo[t] <= cmax; }
+        if (below) atomicAdd(&cnt[0], below);
+        if (reach) atomicAdd(&cnt[1], reach);
+        __syncthreads();
+        T0 = i0 < K ? 0 : min(cnt[0] + 1, NB);
+        T1 = i1 >= n - 1 ? NB : cnt[1];
+    }
     /* what the three kinds share: the prefix's states, the suffix's candidates */
     const int A = max(i - K + 1, 0);
     const float *const FA1 = F + max(A - 1, 0), *const FA2 = F + max(A - 2, 0), *const FSp = F + n;
     const float *const GA = G + min(i, n - 1), *const GB = G + min(i + 1, n - 1), *const GC = G + min(i + 2, n - 1);
+    /* BAND: cell c of entry e from the matrix at m; outside the band -SH_MAP_BIG, the index clamped into the row */
+    auto cell = [&](const float *m, int e, int c, int lo, int hi) {
+        const float x = m[(long long)e * P + min(max(c - lo, 0), (int)P - 1)];
+        return c >= lo && c < hi ? x : -SH_MAP_BIG;
+    };
     const int *const st = a.seq + r.seq, *const bs = a.seq + r.bases;
     const int sA = st[min(i, n - 1)], sB = st[min(i + 1, n - 1)], sC = st[min(i + 2, n - 1)];
     /* sub and del: the suffix begins at min(i + 1, n); ins: at min(i, n) */
@@ -243,25 +350,25 @@ __global__ __launch_bounds__(SH_MAP_NTH) void k_map_edits(ShMapEditsArgs a) {
     ShMapLocalWin lw{};
     lw.post = r.post; lw.lane = r.lane;
     const ShMapLocalCol<TILED> cl(la, lw);
-    int pq[SH_MAPL_PIECES];
+    int pq[NPC];
 #pragma unroll
-    for (int k = 0; k < SH_MAPL_PIECES; k++) pq[k] = min(tid + k * SH_MAP_NTH, NP - 1);
-    float4 q[SH_ME_CH][SH_MAPL_PIECES];
+    for (int k = 0; k < NPC; k++) pq[k] = min(tid + k * W, NP - 1);
+    float4 q[SH_ME_CH][NPC];
     float qs[SH_ME_CH];
     auto fetch = [&](int c) {
 #pragma unroll
         for (int u = 0; u < SH_ME_CH; u++) {
-            const int blk = min(c * SH_ME_CH + u, NB - 1);
+            const int blk = min((BAND ? T0 : 0) + c * SH_ME_CH + u, NB - 1);
             qs[u] = cl.scale(blk);
 #pragma unroll
-            for (int k = 0; k < SH_MAPL_PIECES; k++) q[u][k] = cl.piece(blk, pq[k]);
+            for (int k = 0; k < NPC; k++) q[u][k] = cl.piece(blk, pq[k]);
         }
     };
     auto stage = [&](int buf) {                              /* (a piece past the column's last is its last again: the same words twice) */
 #pragma unroll
         for (int u = 0; u < SH_ME_CH; u++)
 #pragma unroll
-            for (int k = 0; k < SH_MAPL_PIECES; k++)
+            for (int k = 0; k < NPC; k++)
                 *(float4 *)(sh_me_cols + (long long)(buf * SH_ME_CH + u) * NRP + 4 * pq[k]) = cl.fin(q[u][k], qs[u]);
     };
     fetch(0);
@@ -270,12 +377,21 @@ __global__ __launch_bounds__(SH_MAP_NTH) void k_map_edits(ShMapEditsArgs a) {
     /* block t reads the prefix's cells of entry t and the suffix's of entry t + 1 */
     float fa1[SH_ME_D], fa2[SH_ME_D], fs[SH_ME_D], gA[SH_ME_D], gB[SH_ME_D], gC[SH_ME_D];
     auto rows_of = [&](int t, int d) {
-        const long long e0 = (long long)min(t, NB) * P, e1 = (long long)min(t + 1, NB) * P;
-        fa1[d] = FA1[e0]; fa2[d] = FA2[e0]; fs[d] = FSp[e0];
-        gA[d] = GA[e1]; gB[d] = GB[e1]; gC[d] = GC[e1];
+        if constexpr (BAND) {
+            const int t0 = min(t, NB), t1 = min(t + 1, NB);
+            int l0, h0, l1, h1;
+            sh_me_band(blo, NB, t0, l0, h0);
+            sh_me_band(blo, NB, t1, l1, h1);
+            fa1[d] = cell(F, t0, max(A - 1, 0), l0, h0); fa2[d] = cell(F, t0, max(A - 2, 0), l0, h0); fs[d] = F[(long long)t0 * P + (P - 1)];
+            gA[d] = cell(G, t1, min(i, n - 1), l1, h1); gB[d] = cell(G, t1, min(i + 1, n - 1), l1, h1); gC[d] = cell(G, t1, min(i + 2, n - 1), l1, h1);
+        } else {
+            const long long e0 = (long long)min(t, NB) * P, e1 = (long long)min(t + 1, NB) * P;
+            fa1[d] = FA1[e0]; fa2[d] = FA2[e0]; fs[d] = FSp[e0];
+            gA[d] = GA[e1]; gB[d] = GB[e1]; gC[d] = GC[e1];
+        }
     };
 #pragma unroll
-    for (int d = 0; d < SH_ME_D; d++) rows_of(d, d);
+    for (int d = 0; d < SH_ME_D; d++) rows_of((BAND ? T0 : 0) + d, d);
     float Xs[4][SH_ME_K], Xi[4][SH_ME_K], Xd[SH_ME_K - 1], sub[4], ins[4];
     float del = -SH_MAP_BIG;
 #pragma unroll
@@ -288,14 +404,14 @@ __global__ __launch_bounds__(SH_MAP_NTH) void k_map_edits(ShMapEditsArgs a) {
 #pragma unroll
     for (int m = 0; m < SH_ME_K - 1; m++) Xd[m] = -SH_MAP_BIG;
     __syncthreads();
-    const int nchunk = (NB + SH_ME_CH - 1) / SH_ME_CH;
+    const int nchunk = BAND ? (max(T1 - T0, 0) + SH_ME_CH - 1) / SH_ME_CH : (NB + SH_ME_CH - 1) / SH_ME_CH;
     for (int c0 = 0; c0 < nchunk; c0++) {
         const float *const tc = sh_me_cols + (long long)((c0 & 1) * SH_ME_CH) * NRP;
         for (int u0 = 0; u0 < SH_ME_CH; u0 += SH_ME_D) {
 #pragma unroll
             for (int d = 0; d < SH_ME_D; d++) {
-                const int u = u0 + d, t = c0 * SH_ME_CH + u;
-                if (t >= NB) break;                          /* (uniform) */
+                const int u = u0 + d, t = (BAND ? T0 : 0) + c0 * SH_ME_CH + u;
+                if (t >= (BAND ? T1 : NB)) break;            /* (uniform) */
                 const float *const col = tc + (long long)u * NRP;
                 const float lps = col[STAY];
                 const float ls = VIT ? fmaxf(-local_pen, lps) : sh_lse(-local_pen, lps);
@@ -318,7 +434,12 @@ __global__ __launch_bounds__(SH_MAP_NTH) void k_map_edits(ShMapEditsArgs a) {
     }
     if (!mine) return;
     /* no suffix: k_map's end rule on the edit's last column and END's chain */
-    const float fN = FA1[(long long)NB * P];
+    float fN;
+    if constexpr (BAND) {
+        int l, h;
+        sh_me_band(blo, NB, NB, l, h);
+        fN = cell(F, NB, max(A - 1, 0), l, h);
+    } else fN = FA1[(long long)NB * P];
     auto end = [&](float x, float y) { return VIT ? fmaxf(x, y) : sh_lse(x, y); };
     float *const out = a.res + r.res;
     if (Bi == 0) {
