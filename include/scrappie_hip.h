@@ -1227,6 +1227,10 @@ long long scrappie_hip_debug_fetch(scrappie_hip_engine *e, const char *what, voi
 int scrappie_hip_debug_stitch_dwell(scrappie_hip_engine *e, const int *paths, const int *dwells, const size_t *nentry, size_t nread, int ntrail,
                                     const float *prior_num, int nstate, const size_t *cap, char *bases, size_t bases_bytes, int *lengths, int *pos,
                                     int *redo);
+/* The cut of the split products (sh_kernels.h: split8, which every kernel's activations go through) on n values given on the host, for
+ * the bit-exact test of the device's cut against its definition: p1[i] = fp16(64 x[i]), p2[i] = fp16(64 x[i] - p1[i]), as fp16 bit
+ * patterns (n each).  Values are taken in groups of eight, the last group filled with zeros.  Returns 0, -1 on error. */
+int scrappie_hip_debug_split(scrappie_hip_engine *e, const float *x, size_t n, uint16_t *p1, uint16_t *p2);
 /* bytes of bases the engine reserves for a read whose path has nentry entries when the dwell correction is on */
 size_t scrappie_hip_dwell_capacity(size_t nentry);
 

@@ -2531,6 +2531,17 @@ class Engine(object):
             raise RuntimeError("debug_fetch: " + last_error())
         return buf.view(dtype)
 
+    def debug_split(self, x):
+        """The two fp16 pieces of every value of x as the kernels cut them (scrappie_hip_debug_split): (p1, p2), uint16 bit patterns."""
+        x = np.ascontiguousarray(x, dtype=ftype).ravel()
+        p1, p2 = np.zeros(x.size, np.uint16), np.zeros(x.size, np.uint16)
+        fn = lib().scrappie_hip_debug_split
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        if fn(self._h, x.ctypes.data, x.size, p1.ctypes.data, p2.ctypes.data) != 0:
+            raise RuntimeError("debug_split: " + last_error())
+        return p1, p2
+
     def debug_stitch(self, path, side=None, nstate=1025, crf=False):
         """k_stitch on one read given on the host: (bases or None, pos, redo)."""
         path = np.ascontiguousarray(path, dtype=np.int32)

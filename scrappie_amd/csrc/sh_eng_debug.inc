@@ -1,5 +1,5 @@
 /* sh_eng_debug.inc -- part of scrappie_hip.hip (one translation unit, included from there in this order; not compiled alone):
- * measurement / test hooks: decoder and trunk inputs, debug_option / debug_fetch / debug_stitch / debug_stitch_dwell. */
+ * measurement / test hooks: decoder and trunk inputs, debug_option / debug_fetch / debug_stitch / debug_stitch_dwell / debug_split. */
 
 extern "C" int scrappie_hip_set_decoder_input(scrappie_hip_engine *e, const float *d_prob, const uint64_t *prob_off, size_t n_prob) {
     if (!e) return set_err("set_decoder_input: null engine");
@@ -217,6 +217,36 @@ extern "C" int scrappie_hip_debug_stitch_dwell(scrappie_hip_engine *e, const int
     if (pos) HIPCHK(hipMemcpyAsync(pos, dpos.p, nseq * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(sh_stream_wait(s));
     if (redo) for (size_t i = 0; i < nread; i++) redo[i] = (int)hredo[i];
+    return 0;
+}
+
+/* split8 (sh_kernels.h: the cut every split product's activations go through) on consecutive groups of eight values */
+__global__ void k_debug_split(const float *x, unsigned *p1, unsigned *p2, size_t ngroup) {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= ngroup) return;
+    const ShSplit sp = split8(*(const f32x4 *)(x + g * 8), *(const f32x4 *)(x + g * 8 + 4));
+    *(u32x4 *)(p1 + g * 4) = __builtin_bit_cast(u32x4, sp.p1);
+    *(u32x4 *)(p2 + g * 4) = __builtin_bit_cast(u32x4, sp.p2);
+}
+
+/* The two fp16 pieces of n values given on the host, as the kernels cut them (test hook: the device's cut against its
+ * definition, bit for bit).  p1 and p2 take n fp16 bit patterns each.  Returns 0, -1 on error. */
+extern "C" int scrappie_hip_debug_split(scrappie_hip_engine *e, const float *x, size_t n, uint16_t *p1, uint16_t *p2) {
+    if (!e || !x || !p1 || !p2 || n == 0 || n > ((size_t)1 << 30)) return set_err("debug_split: bad argument");
+    (void)hipSetDevice(e->device);
+    std::lock_guard<std::mutex> lk(e->mu);
+    const size_t ngroup = (n + 7) / 8, npad = ngroup * 8;      /* the last group is filled with zeros */
+    DBuf dx, d1, d2;      /* (freed on every way out) */
+    if (dx.ensure(npad * 4) || d1.ensure(npad * 2) || d2.ensure(npad * 2)) return -1;
+    hipStream_t s = e->stream;
+    HIPCHK(hipMemsetAsync(dx.p, 0, npad * 4, s));
+    HIPCHK(hipMemcpyAsync(dx.p, x, n * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(sh_stream_wait(s));                      /* the source is pageable caller memory */
+    hipLaunchKernelGGL(k_debug_split, dim3((unsigned)((ngroup + 255) / 256)), dim3(256), 0, s, dx.as<float>(), d1.as<unsigned>(), d2.as<unsigned>(), ngroup);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(p1, d1.p, n * 2, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(p2, d2.p, n * 2, hipMemcpyDeviceToHost, s));
+    HIPCHK(sh_stream_wait(s));
     return 0;
 }
 

@@ -76,7 +76,7 @@ __device__ __forceinline__ float d_rcp(float x) {
 __device__ __forceinline__ float d_logistic(float x) { return d_rcp(1.0f + d_exp(-x)); }
 __device__ __forceinline__ float d_tanh(float x) {
     const float y = d_logistic(x + x);
-    return (y + y) - 1.0f;
+    return __builtin_fmaf(y, 2.0f, -1.0f);      /* (y + y) - 1: 2 y is exact, so both round 2 y - 1 once -- the same bits in one instruction */
 }
 /* the same operations on four values as vector arithmetic, which the compiler lowers to packed f32 VALU
  * (v_pk_mul_f32 / v_pk_add_f32: two lanes per instruction, identical IEEE results) whether or not the SLP
@@ -103,8 +103,10 @@ __device__ __forceinline__ f32x4 d_logistic4(f32x4 x) {
     return y;
 }
 __device__ __forceinline__ f32x4 d_tanh4(f32x4 x) {
-    const f32x4 y = d_logistic4(x + x);
-    return (y + y) - 1.0f;
+    f32x4 y = d_logistic4(x + x);
+#pragma unroll
+    for (int k = 0; k < 4; k++) y[k] = __builtin_fmaf(y[k], 2.0f, -1.0f);      /* as d_tanh; four v_fma_f32 instead of two packed additions and four additions */
+    return y;
 }
 __device__ __forceinline__ float d_elu(float x) { return (x >= 0.0f) ? x : (d_exp(x) - 1.0f); }
 __device__ __forceinline__ float d_lse(float x, float y) {   /* util.h:162 */
@@ -195,11 +197,22 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 #define SH_ACT_LIMIT 1000.0f
 #define SH_OINV (1.0f / SH_OSCALE)
 struct ShSplit { f16x8 p1, p2; };
+/* The cut of two values: xs = 64 x (exact unless x is an fp32 subnormal), p1 = fp16(xs) by v_cvt_pk_f16_f32 (round to
+ * nearest even), p2 = fp16(xs - p1).  The definition goes through fp32 -- fp16(xs - (float)p1) -- where the subtraction is
+ * exact (p1 is xs rounded to 11 bits: the residual has at most 13 significant bits and lies on xs's grid), so it rounds
+ * once, in the conversion.  What runs is one mixed-precision fused multiply-add per value that reads p1's half as its
+ * addend and rounds xs * 1.0 - p1 once to fp16, v_fma_mixlo_f16 into the low half of w2 and v_fma_mixhi_f16 into the high
+ * half (it leaves the low half alone: the second statement is tied to the first's destination): the same exact value
+ * rounded once by the same rule, so the same bits, signed zeros included (an exact zero is +0 both ways), and
+ * v_fma_mix* honours the fp16 / fp32 denormal modes like the conversions.  5 VALU instructions per pair against 8 (no
+ * v_cvt_f32_f16, its SDWA form for the high half, v_sub_f32, or second v_cvt_pk_f16_f32: profiles/split_cut_mix.txt).
+ * hipcc does not select the two from C, hence asm; not volatile, so the scheduler still places them among the MFMAs.
+ * tests/test_gpu_split_cut.py holds the device to the definition. */
 __device__ __forceinline__ void split_pair(float x, float y, unsigned &w1, unsigned &w2) {
     const float xs = x * SH_ASCALE, ys = y * SH_ASCALE;
-    const f16x2 h = __builtin_convertvector((f32x2){xs, ys}, f16x2);               /* round to nearest even */
-    w1 = __builtin_bit_cast(unsigned, h);
-    w2 = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){xs - (float)h[0], ys - (float)h[1]}, f16x2));
+    w1 = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){xs, ys}, f16x2));               /* round to nearest even */
+    asm("v_fma_mixlo_f16 %0, %1, 1.0, -%2 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(w2) : "v"(xs), "v"(w1));
+    asm("v_fma_mixhi_f16 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(w2) : "v"(ys), "v"(w1));
 }
 __device__ __forceinline__ ShSplit split8(f32x4 lo, f32x4 hi) {
     unsigned w1[4], w2[4];
@@ -292,7 +305,9 @@ __device__ __forceinline__ f32x4 d_tanh4_acc(f32x4 a) {
     t = 1.0f + t;
 #pragma unroll
     for (int k = 0; k < 4; k++) t[k] = d_rcp(t[k]);
-    return (t + t) - 1.0f;
+#pragma unroll
+    for (int k = 0; k < 4; k++) t[k] = __builtin_fmaf(t[k], 2.0f, -1.0f);      /* as d_tanh */
+    return t;
 #else
     return d_tanh4(a * SH_OINV);
 #endif

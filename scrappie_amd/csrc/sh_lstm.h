@@ -117,7 +117,12 @@ __global__ __launch_bounds__(128 * NU) void k_lstm_lanes(const float *__restrict
             if (!sh_wait_flag(L.flag + tile, (unsigned)NU, L.flag + L.ntile) && lane == 0)      /* give up loudly instead of hanging the device */
                 __hip_atomic_store(L.flag + L.ntile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            const float *hs = L.hstate + ((long long)tile * 2 * NU + u) * 256 + lane * 4;       /* [h | c] */
+            /* the lane's offset made opaque here and at the hand-over below: seen as invariant, L.hstate + 4 lane is formed once in front of the step
+             * loop and held through it as a 64-bit pair -- two registers NU = 6 does not have under its cap of 168 (they went to scratch, with the reload
+             * inside the step loop); formed where a segment ends instead, one v_lshl_add_u64 per segment */
+            int lofs = lane * 4;
+            asm volatile("" : "+v"(lofs));
+            const float *hs = L.hstate + ((long long)tile * 2 * NU + u) * 256 + lofs;       /* [h | c] */
 #pragma unroll
             for (int k = 0; k < 4; k++) {
                 h[k] = __hip_atomic_load(hs + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -195,7 +200,9 @@ __global__ __launch_bounds__(128 * NU) void k_lstm_lanes(const float *__restrict
         s++;
         if (s == s1) {                                       /* segment done */
             if (s1 < Tt) {                                   /* the tile continues on another lane */
-                float *hs = L.hstate + ((long long)tile * 2 * NU + u) * 256 + lane * 4;
+                int lofs = lane * 4;
+                asm volatile("" : "+v"(lofs));               /* (see take_over) */
+                float *hs = L.hstate + ((long long)tile * 2 * NU + u) * 256 + lofs;
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
                     __hip_atomic_store(hs + k, h[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
