@@ -1231,6 +1231,24 @@ int scrappie_hip_debug_stitch_dwell(scrappie_hip_engine *e, const int *paths, co
  * the bit-exact test of the device's cut against its definition: p1[i] = fp16(64 x[i]), p2[i] = fp16(64 x[i] - p1[i]), as fp16 bit
  * patterns (n each).  Values are taken in groups of eight, the last group filled with zeros.  Returns 0, -1 on error. */
 int scrappie_hip_debug_split(scrappie_hip_engine *e, const float *x, size_t n, uint16_t *p1, uint16_t *p2);
+/* One activation form of the kernels (sh_kernels.h) on n values given on the host, in one kernel, for the tests that hold the forms to each
+ * other bit for bit and to float64 where network weights do not reach: deep saturation, the clamp of the exponential, signed zeros,
+ * subnormals.  The *_ACC forms take their argument as the split products leave it, in accumulator units: 2^14 x (exact in fp32).  Values
+ * are taken in groups of four, the last group filled with zeros.  Returns 0, -1 on error. */
+enum {
+    SH_GATE_LOGISTIC = 0,           /* d_logistic */
+    SH_GATE_TANH = 1,               /* d_tanh */
+    SH_GATE_LOGISTIC4 = 2,          /* d_logistic4 */
+    SH_GATE_TANH4 = 3,              /* d_tanh4 */
+    SH_GATE_LOGISTIC4_ACC = 4,      /* d_logistic4_acc */
+    SH_GATE_TANH4_ACC = 5,          /* d_tanh4_acc */
+    SH_GATE_EXP = 6,                /* d_exp */
+    SH_GATE_EXP_ACC = 7,            /* d_exp_acc */
+    SH_GATE_EXP_ACC_INRANGE = 8,    /* d_exp_acc_inrange: only for |x| < 88 */
+    SH_GATE_ELU = 9,                /* d_elu */
+    SH_GATE_NFORM = 10
+};
+int scrappie_hip_debug_gates(scrappie_hip_engine *e, int which, const float *x, size_t n, float *out);
 /* bytes of bases the engine reserves for a read whose path has nentry entries when the dwell correction is on */
 size_t scrappie_hip_dwell_capacity(size_t nentry);
 

@@ -2542,6 +2542,23 @@ class Engine(object):
             raise RuntimeError("debug_split: " + last_error())
         return p1, p2
 
+    GATE_FORMS = ("d_logistic", "d_tanh", "d_logistic4", "d_tanh4", "d_logistic4_acc", "d_tanh4_acc", "d_exp", "d_exp_acc",
+                  "d_exp_acc_inrange", "d_elu")        # scrappie_hip.h: SH_GATE_*
+
+    def debug_gates(self, which, x):
+        """One activation form of the kernels (a name of GATE_FORMS) on every value of x, as float32 (scrappie_hip_debug_gates).
+        The *_acc forms are given 2^14 x, formed here in float32 (exact), as the split products hand it to them."""
+        x = np.ascontiguousarray(x, dtype=ftype).ravel()
+        if which.endswith("_acc") or which.endswith("_acc_inrange"):
+            x = x * ftype(16384.0)
+        out = np.zeros(x.size, ftype)
+        fn = lib().scrappie_hip_debug_gates
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+        if fn(self._h, self.GATE_FORMS.index(which), x.ctypes.data, x.size, out.ctypes.data) != 0:
+            raise RuntimeError("debug_gates: " + last_error())
+        return out
+
     def debug_stitch(self, path, side=None, nstate=1025, crf=False):
         """k_stitch on one read given on the host: (bases or None, pos, redo)."""
         path = np.ascontiguousarray(path, dtype=np.int32)

@@ -1,5 +1,5 @@
 /* sh_eng_debug.inc -- part of scrappie_hip.hip (one translation unit, included from there in this order; not compiled alone):
- * measurement / test hooks: decoder and trunk inputs, debug_option / debug_fetch / debug_stitch / debug_stitch_dwell / debug_split. */
+ * measurement / test hooks: decoder and trunk inputs, debug_option / debug_fetch / debug_stitch / debug_stitch_dwell / debug_split / debug_gates. */
 
 extern "C" int scrappie_hip_set_decoder_input(scrappie_hip_engine *e, const float *d_prob, const uint64_t *prob_off, size_t n_prob) {
     if (!e) return set_err("set_decoder_input: null engine");
@@ -246,6 +246,65 @@ extern "C" int scrappie_hip_debug_split(scrappie_hip_engine *e, const float *x, 
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(p1, d1.p, n * 2, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(p2, d2.p, n * 2, hipMemcpyDeviceToHost, s));
+    HIPCHK(sh_stream_wait(s));
+    return 0;
+}
+
+/* one of the activation forms of sh_kernels.h on consecutive groups of four values (`which`: scrappie_hip.h, SH_GATE_*) */
+__global__ void k_debug_gates(int which, const float *x, float *y, size_t ngroup) {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= ngroup) return;
+    const f32x4 v = *(const f32x4 *)(x + g * 4);
+    f32x4 r = v;
+    switch (which) {
+    case SH_GATE_LOGISTIC:
+#pragma unroll
+        for (int k = 0; k < 4; k++) r[k] = d_logistic(v[k]);
+        break;
+    case SH_GATE_TANH:
+#pragma unroll
+        for (int k = 0; k < 4; k++) r[k] = d_tanh(v[k]);
+        break;
+    case SH_GATE_LOGISTIC4: r = d_logistic4(v); break;
+    case SH_GATE_TANH4: r = d_tanh4(v); break;
+    case SH_GATE_LOGISTIC4_ACC: r = d_logistic4_acc(v); break;
+    case SH_GATE_TANH4_ACC: r = d_tanh4_acc(v); break;
+    case SH_GATE_EXP:
+#pragma unroll
+        for (int k = 0; k < 4; k++) r[k] = d_exp(v[k]);
+        break;
+    case SH_GATE_EXP_ACC:
+#pragma unroll
+        for (int k = 0; k < 4; k++) r[k] = d_exp_acc(v[k]);
+        break;
+    case SH_GATE_EXP_ACC_INRANGE:
+#pragma unroll
+        for (int k = 0; k < 4; k++) r[k] = d_exp_acc_inrange(v[k]);
+        break;
+    default:
+#pragma unroll
+        for (int k = 0; k < 4; k++) r[k] = d_elu(v[k]);
+        break;
+    }
+    *(f32x4 *)(y + g * 4) = r;
+}
+
+/* One activation form of the kernels on n values given on the host (test hook: the forms against each other bit for bit, and against
+ * float64, outside the range network weights reach).  The _ACC forms take their argument in accumulator units (2^14 x).  Returns 0, -1 on error. */
+extern "C" int scrappie_hip_debug_gates(scrappie_hip_engine *e, int which, const float *x, size_t n, float *out) {
+    if (!e || !x || !out || n == 0 || n > ((size_t)1 << 30) || which < 0 || which >= SH_GATE_NFORM) return set_err("debug_gates: bad argument");
+    (void)hipSetDevice(e->device);
+    std::lock_guard<std::mutex> lk(e->mu);
+    const size_t ngroup = (n + 3) / 4, npad = ngroup * 4;      /* the last group is filled with zeros */
+    DBuf dx, dy;      /* (freed on every way out) */
+    if (dx.ensure(npad * 4) || dy.ensure(npad * 4)) return -1;
+    hipStream_t s = e->stream;
+    HIPCHK(hipMemsetAsync(dx.p, 0, npad * 4, s));
+    HIPCHK(hipMemcpyAsync(dx.p, x, n * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(sh_stream_wait(s));                      /* the source is pageable caller memory */
+    hipLaunchKernelGGL(k_debug_gates, dim3((unsigned)((ngroup + 255) / 256)), dim3(256), 0, s, which, dx.as<float>(), dy.as<float>(), ngroup);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, dy.p, n * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(sh_stream_wait(s));
     return 0;
 }
