@@ -1615,63 +1615,51 @@ def apply_edit(seq, kind, i, c=None):
     return ''.join(out) if text else np.array(out, dtype=np.int32)
 
 
-def _edits_form_counts(fn):
-    q = (C.c_uint64 * 12)()
+def _edits_forms(fn, ctype=C.c_uint64, widths=(None,)):
+    """a table of the ABI over the forms of the edit kernels (counts, or scratch bytes) as a dict: eight rows forms, then four combining
+    forms per width of `widths` (None: the one width, which the key leaves out)"""
+    q = (ctype * (8 + 4 * len(widths)))()
     fn(q)
     out = {('rows', bool(k & 4), bool(k & 2), bool(k & 1)): int(q[k]) for k in range(8)}
-    out.update({('edits', bool(k & 2), bool(k & 1)): int(q[8 + k]) for k in range(4)})
+    for j, w in enumerate(widths):
+        out.update({('edits', bool(k & 2), bool(k & 1)) + (() if w is None else (w,)): int(q[8 + 4 * j + k]) for k in range(4)})
     return out
 
 
 def crf_edits_form_counts():
     """Launches of each form of the edit kernels in this process so far (scrappie_hip_crf_edits_form_counts):
     {('rows', viterbi, tiled, backward): n, ('edits', viterbi, tiled): n}."""
-    return _edits_form_counts(lib().scrappie_hip_crf_edits_form_counts)
+    return _edits_forms(lib().scrappie_hip_crf_edits_form_counts)
 
 
 def crf_edits_band_form_counts():
     """The same for the banded forms of the edit kernels (scrappie_hip_crf_edits_band_form_counts); `crf_edits_form_counts`
     counts the unbanded forms alone."""
-    return _edits_form_counts(lib().scrappie_hip_crf_edits_band_form_counts)
+    return _edits_forms(lib().scrappie_hip_crf_edits_band_form_counts)
 
 
 def crf_edits_band_scratch():
     """Private (scratch) bytes per lane of each banded form, keyed as `crf_edits_band_form_counts` keys them, as the runtime reports
     them for the loaded kernels (scrappie_hip_crf_edits_band_scratch; needs a GPU): the forms are built to need none."""
-    q = (C.c_longlong * 12)()
-    lib().scrappie_hip_crf_edits_band_scratch(q)
-    out = {('rows', bool(k & 4), bool(k & 2), bool(k & 1)): int(q[k]) for k in range(8)}
-    out.update({('edits', bool(k & 2), bool(k & 1)): int(q[8 + k]) for k in range(4)})
-    return out
+    return _edits_forms(lib().scrappie_hip_crf_edits_band_scratch, C.c_longlong)
 
 
 def map_edits_form_counts():
     """The same for the transducer edit kernels, k_map_edits_rows and k_map_edits (scrappie_hip_map_edits_form_counts)."""
-    return _edits_form_counts(lib().scrappie_hip_map_edits_form_counts)
-
-
-def _map_edits_band_forms(q):
-    out = {('rows', bool(k & 4), bool(k & 2), bool(k & 1)): int(q[k]) for k in range(8)}
-    for j, w in enumerate((256, 64)):
-        out.update({('edits', bool(k & 2), bool(k & 1), w): int(q[8 + 4 * j + k]) for k in range(4)})
-    return out
+    return _edits_forms(lib().scrappie_hip_map_edits_form_counts)
 
 
 def map_edits_band_form_counts():
     """Launches of each banded form of the transducer edit kernels in this process so far (scrappie_hip_map_edits_band_form_counts):
     {('rows', viterbi, tiled, backward): n, ('edits', viterbi, tiled, width): n}, width 256 or 64 positions per workgroup;
     `map_edits_form_counts` counts the unbanded forms alone."""
-    q = (C.c_uint64 * 16)()
-    lib().scrappie_hip_map_edits_band_form_counts(q)
-    return _map_edits_band_forms(q)
+    return _edits_forms(lib().scrappie_hip_map_edits_band_form_counts, widths=(256, 64))
 
 
 def map_edits_band_scratch():
     """Private (scratch) bytes per lane of each banded form, keyed as `map_edits_band_form_counts` keys them, as the runtime reports
     them for the loaded kernels (scrappie_hip_map_edits_band_scratch; needs a GPU): the forms are built to need none."""
-    q = (C.c_longlong * 16)()
-    lib().scrappie_hip_map_edits_band_scratch(q)
-    return _map_edits_band_forms(q)
+    return _edits_forms(lib().scrappie_hip_map_edits_band_scratch, C.c_longlong, (256, 64))
 
 
 def _edits_plan(seqlens, nblocks, plan):
@@ -1696,29 +1684,43 @@ def crf_edits_plan(seqlens, nblocks):
     return _edits_plan(seqlens, nblocks, lib().scrappie_hip_crf_edits_plan)
 
 
+def _edits_band_row_bytes(fn, low, high, extra, what):
+    """a read's row bytes in the band (low, high) of nblock + `extra` entries each"""
+    lo, hi = (np.ascontiguousarray(x, dtype=np.uintp) for x in (low, high))
+    if len(lo) != len(hi) or len(lo) < 1 + extra:
+        raise ValueError("low and high hold %s entries each" % what)
+    sp = C.POINTER(C.c_size_t)
+    return int(fn(lo.ctypes.data_as(sp), hi.ctypes.data_as(sp), len(lo) - extra))
+
+
+def _edits_band_plan(plan, seqlens, bands, extra, what, kmer_len=None, bandless=False):
+    """`_edits_plan` for reads in bands of nblock + `extra` entries each; `bandless`: (nblock, None) is a read without a band"""
+    bands = [b if bandless and b[1] is None else [np.ascontiguousarray(x, dtype=np.uintp) for x in b] for b in bands]
+    if len(bands) != len(seqlens) or any(len(b) != 2 or (b[1] is not None and (len(b[0]) != len(b[1]) or len(b[0]) < 1 + extra)) for b in bands):
+        raise ValueError("one (low, high) pair of %s entries each%s per sequence length" % (what, ", or (nblock, None)," if bandless else ""))
+    sp = C.POINTER(C.c_size_t)
+    n = len(bands)
+    lo, hi = (sp * max(n, 1))(), (sp * max(n, 1))()
+    for i, b in enumerate(bands):
+        if b[1] is not None:
+            lo[i], hi[i] = b[0].ctypes.data_as(sp), b[1].ctypes.data_as(sp)
+    k = () if kmer_len is None else (kmer_len,)
+    out = _edits_plan(seqlens, [int(b[0]) if b[1] is None else len(b[0]) - extra for b in bands], lambda a, nb, cnt, *rest: plan(a, nb, lo, hi, cnt, *k, *rest))
+    if out[3] < 0:
+        raise ValueError("a sequence of fewer than %d bases holds no k-mer" % kmer_len)
+    return out
+
+
 def crf_edits_band_row_bytes(low, high):
     """Device bytes of the three row matrices of a read in the band (low, high), nblock + 1 entries each
     (scrappie_hip_crf_edits_band_row_bytes): an entry's row holds its band's cells alone."""
-    lo, hi = (np.ascontiguousarray(x, dtype=np.uintp) for x in (low, high))
-    if len(lo) != len(hi) or len(lo) < 2:
-        raise ValueError("low and high hold nblock + 1 >= 2 entries each")
-    sp = C.POINTER(C.c_size_t)
-    return int(lib().scrappie_hip_crf_edits_band_row_bytes(lo.ctypes.data_as(sp), hi.ctypes.data_as(sp), len(lo) - 1))
+    return _edits_band_row_bytes(lib().scrappie_hip_crf_edits_band_row_bytes, low, high, 1, "nblock + 1 >= 2")
 
 
 def crf_edits_band_plan(seqlens, bands):
     """`crf_edits_plan` for reads in bands (scrappie_hip_crf_edits_band_plan): `bands[i]` is read i's (low, high), nblock + 1
     entries each -- the block count is the band's.  The pitch is that of the band's widest entry."""
-    bands = [[np.ascontiguousarray(x, dtype=np.uintp) for x in b] for b in bands]
-    if len(bands) != len(seqlens) or any(len(b) != 2 or len(b[0]) != len(b[1]) or len(b[0]) < 2 for b in bands):
-        raise ValueError("one (low, high) pair of nblock + 1 >= 2 entries each per sequence length")
-    sp = C.POINTER(C.c_size_t)
-    n = len(bands)
-    lo, hi = (sp * max(n, 1))(), (sp * max(n, 1))()
-    for i, b in enumerate(bands):
-        lo[i], hi[i] = b[0].ctypes.data_as(sp), b[1].ctypes.data_as(sp)
-    return _edits_plan(seqlens, [len(b[0]) - 1 for b in bands],
-                       lambda a, nb, cnt, *rest: lib().scrappie_hip_crf_edits_band_plan(a, nb, lo, hi, cnt, *rest))
+    return _edits_band_plan(lib().scrappie_hip_crf_edits_band_plan, seqlens, bands, 1, "nblock + 1 >= 2")
 
 
 def map_edits_plan(seqlens, nblocks, kmer_len):
@@ -1734,31 +1736,37 @@ def map_edits_plan(seqlens, nblocks, kmer_len):
 def map_edits_band_row_bytes(low, high):
     """Device bytes of the two row matrices of a transducer read in the band (low, high), nblock entries each
     (scrappie_hip_map_edits_band_row_bytes): an entry's row holds its band's cells alone."""
-    lo, hi = (np.ascontiguousarray(x, dtype=np.uintp) for x in (low, high))
-    if len(lo) != len(hi) or len(lo) < 1:
-        raise ValueError("low and high hold nblock >= 1 entries each")
-    sp = C.POINTER(C.c_size_t)
-    return int(lib().scrappie_hip_map_edits_band_row_bytes(lo.ctypes.data_as(sp), hi.ctypes.data_as(sp), len(lo)))
+    return _edits_band_row_bytes(lib().scrappie_hip_map_edits_band_row_bytes, low, high, 0, "nblock >= 1")
 
 
 def map_edits_band_plan(seqlens, bands, kmer_len):
     """`map_edits_plan` for reads in bands (scrappie_hip_map_edits_band_plan): `bands[i]` is read i's (low, high), nblock entries
     each -- the block count is the band's --, or (nblock, None) for a read without a band, which takes the unbanded pitch.  The
     pitch of a read in a band is that of the band's widest entry."""
-    bands = [b if b[1] is None else [np.ascontiguousarray(x, dtype=np.uintp) for x in b] for b in bands]
-    if len(bands) != len(seqlens) or any(len(b) != 2 or (b[1] is not None and (len(b[0]) != len(b[1]) or len(b[0]) < 1)) for b in bands):
-        raise ValueError("one (low, high) pair of nblock >= 1 entries each, or (nblock, None), per sequence length")
-    sp = C.POINTER(C.c_size_t)
-    n = len(bands)
-    lo, hi = (sp * max(n, 1))(), (sp * max(n, 1))()
-    for i, b in enumerate(bands):
-        if b[1] is not None:
-            lo[i], hi[i] = b[0].ctypes.data_as(sp), b[1].ctypes.data_as(sp)
-    out = _edits_plan(seqlens, [int(b[0]) if b[1] is None else len(b[0]) for b in bands],
-                      lambda a, nb, cnt, *rest: lib().scrappie_hip_map_edits_band_plan(a, nb, lo, hi, cnt, kmer_len, *rest))
-    if out[3] < 0:
-        raise ValueError("a sequence of fewer than %d bases holds no k-mer" % kmer_len)
-    return out
+    return _edits_band_plan(lib().scrappie_hip_map_edits_band_plan, seqlens, bands, 0, "nblock >= 1", kmer_len, True)
+
+
+def _one_edits(seq, band, call):
+    """what `map_post_edits` and `map_trans_edits` share once the matrix is checked: the results allocated, band(L) -- None for the
+    call without a band, else `_one_band`'s -- handed to call(band, seq, L, base, sub, dele, ins); (base, sub, dele, ins)"""
+    tgs, keep = _crf_targets([seq])
+    L = len(keep[0])
+    base = C.c_float(float('nan'))
+    sub, dele, ins = (np.full(k, np.nan, dtype=np.float32) for k in (4 * L, max(L, 1), 4 * (L + 1)))
+    fp = C.POINTER(C.c_float)
+    if call(band(L), tgs[0].seq, L, C.byref(base), sub.ctypes.data_as(fp), dele.ctypes.data_as(fp), ins.ctypes.data_as(fp)) != 0:
+        raise RuntimeError('An unknown error occurred while scoring edits: ' + last_error())
+    return np.float32(base.value), sub.reshape(L, 4), dele[:L], ins.reshape(L + 1, 4)
+
+
+def _one_band(lo, hi, entries, what, sane):
+    """the band of a per-read edits call as pointers, checked: `entries` entries each, and sane(p_lo, p_hi)"""
+    if len(lo) != entries or len(hi) != entries:
+        raise ValueError('Supplied banding structure is not valid: %s entries each.' % what)
+    p = tuple(x.ctypes.data_as(C.POINTER(C.c_size_t)) for x in (lo, hi))
+    if not sane(*p):
+        raise ValueError('Supplied banding structure is not valid.')
+    return p + (lo, hi)      # (the arrays live as long as their pointers)
 
 
 def map_post_edits(post, seq, stay_pen=0, skip_pen=0, local_pen=4.0, viterbi=True, bands=None):
@@ -1780,28 +1788,19 @@ def map_post_edits(post, seq, stay_pen=0, skip_pen=0, local_pen=4.0, viterbi=Tru
     nblock, nstate = post.shape
     if nstate not in (5, 17, 65, 257, 1025):
         raise ValueError('`post` should hold 4^k + 1 states per block, k = 1 .. 5.')
-    tgs, keep = _crf_targets([seq])
-    L = len(keep[0])
-    base = C.c_float(float('nan'))
-    sub, dele, ins = (np.full(k, np.nan, dtype=np.float32) for k in (4 * L, max(L, 1), 4 * (L + 1)))
-    fp = C.POINTER(C.c_float)
     kmer_len = guess_state_properties(nstate)[1]
-    if bands is not None and L >= kmer_len:
+
+    def band(L):
+        if bands is None or L < kmer_len:
+            return None
         n = L - kmer_len + 1
-        lo, hi = _map_band(bands, nblock, n)
-        if len(lo) != nblock or len(hi) != nblock:
-            raise ValueError('Supplied banding structure is not valid: nblock entries each.')
-        p_lo, p_hi = (x.ctypes.data_as(C.POINTER(C.c_size_t)) for x in (lo, hi))
-        if not lib().are_bounds_sane(p_lo, p_hi, nblock, n):
-            raise ValueError('Supplied banding structure is not valid.')
-        rc = lib().map_post_edits_banded(post.data(), stay_pen, skip_pen, local_pen, tgs[0].seq, L, p_lo, p_hi, 1 if viterbi else 0, C.byref(base),
-                                         sub.ctypes.data_as(fp), dele.ctypes.data_as(fp), ins.ctypes.data_as(fp))
-    else:
-        rc = lib().map_post_edits(post.data(), stay_pen, skip_pen, local_pen, tgs[0].seq, L, 1 if viterbi else 0, C.byref(base),
-                                  sub.ctypes.data_as(fp), dele.ctypes.data_as(fp), ins.ctypes.data_as(fp))
-    if rc != 0:
-        raise RuntimeError('An unknown error occurred while scoring edits: ' + last_error())
-    return np.float32(base.value), sub.reshape(L, 4), dele[:L], ins.reshape(L + 1, 4)
+        return _one_band(*_map_band(bands, nblock, n), nblock, 'nblock', lambda lo, hi: lib().are_bounds_sane(lo, hi, nblock, n))
+
+    def call(b, seq, L, *out):
+        if b is None:
+            return lib().map_post_edits(post.data(), stay_pen, skip_pen, local_pen, seq, L, 1 if viterbi else 0, *out)
+        return lib().map_post_edits_banded(post.data(), stay_pen, skip_pen, local_pen, seq, L, b[0], b[1], 1 if viterbi else 0, *out)
+    return _one_edits(seq, band, call)
 
 
 def map_trans_edits(trans, seq, viterbi=True, bands=None):
@@ -1822,26 +1821,17 @@ def map_trans_edits(trans, seq, viterbi=True, bands=None):
     nblock, nstate = trans.shape
     if nstate != 25:
         raise ValueError('`trans` should hold the 25 transitions of a flip-flop (CRF) model per block.')
-    tgs, keep = _crf_targets([seq])
-    L = len(keep[0])
-    base = C.c_float(float('nan'))
-    sub, dele, ins = (np.full(k, np.nan, dtype=np.float32) for k in (4 * L, max(L, 1), 4 * (L + 1)))
-    fp = C.POINTER(C.c_float)
-    if bands is not None and L > 0:
-        lo, hi = _crf_band(bands, nblock, L)
-        if len(lo) != nblock + 1 or len(hi) != nblock + 1:
-            raise ValueError('Supplied banding structure is not valid: nblock + 1 entries each.')
-        p_lo, p_hi = (x.ctypes.data_as(C.POINTER(C.c_size_t)) for x in (lo, hi))
-        if not lib().scrappie_hip_map_crf_bounds_sane(p_lo, p_hi, nblock, L):
-            raise ValueError('Supplied banding structure is not valid.')
-        rc = lib().map_crf_edits_banded(trans.data(), tgs[0].seq, L, p_lo, p_hi, 1 if viterbi else 0, C.byref(base), sub.ctypes.data_as(fp),
-                                        dele.ctypes.data_as(fp), ins.ctypes.data_as(fp))
-    else:
-        rc = lib().map_crf_edits(trans.data(), tgs[0].seq, L, 1 if viterbi else 0, C.byref(base), sub.ctypes.data_as(fp), dele.ctypes.data_as(fp),
-                                 ins.ctypes.data_as(fp))
-    if rc != 0:
-        raise RuntimeError('An unknown error occurred while scoring edits: ' + last_error())
-    return np.float32(base.value), sub.reshape(L, 4), dele[:L], ins.reshape(L + 1, 4)
+
+    def band(L):
+        if bands is None or L == 0:
+            return None
+        return _one_band(*_crf_band(bands, nblock, L), nblock + 1, 'nblock + 1', lambda lo, hi: lib().scrappie_hip_map_crf_bounds_sane(lo, hi, nblock, L))
+
+    def call(b, seq, L, *out):
+        if b is None:
+            return lib().map_crf_edits(trans.data(), seq, L, 1 if viterbi else 0, *out)
+        return lib().map_crf_edits_banded(trans.data(), seq, L, b[0], b[1], 1 if viterbi else 0, *out)
+    return _one_edits(seq, band, call)
 
 
 def map_trans_to_reference(trans, sequence, viterbi=False, path=False):

@@ -35,12 +35,13 @@
  * below -SH_MAP_BIG / 2: no admissible path (the host answers NAN).  All stores are plain vector stores.
  *
  * BAND = true (ShCrfEditsBandRead: low and high of nblock + 1 int32 each behind the codes; include/scrappie_hip.h states the definition): F and G
- * hold -SH_MAP_BIG outside the band of their entry, the new base's cells X carry none.  The rows kernel runs k_map_crf's banded loop -- per entry
- * the cells from the 64-cell group of low on, the previous row read under the previous entry's band, nothing ever cleared -- and stores an
- * entry's band alone: cell p of entry t at float p - low[t] of its row, the row's last slot (pitch - 1, never a cell: pitch > the widest entry)
+ * hold -SH_MAP_BIG outside the band of their entry, the new base's cells X carry none.  The rows kernel has ONE block loop, k_map_crf's -- per
+ * entry the cells from the 64-cell group of low on, the previous row read under the previous entry's band, nothing ever cleared; without a band
+ * the bounds are the constants 0 and L + 1 and BAND decides the bounds, the first chunk's base and the row index of the global store alone -- and
+ * in a band stores an entry's band alone: cell p of entry t at float p - low[t] of its row, the row's last slot (pitch - 1, never a cell: pitch > the widest entry)
  * for the threads without one.  The combining kernel indexes the rows the same way (the index clamped into the row, -SH_MAP_BIG selected outside
  * the band) and walks only the blocks at which one of its workgroup's positions can be alive.  With the full band both run the unbanded
- * arithmetic operand for operand: the same bits.  The instantiations with BAND = false are the code they were. */
+ * arithmetic operand for operand: the same bits.  The combining kernel's BAND differences are a few `if constexpr` lines. */
 #ifndef SH_CRF_EDITS_H
 #define SH_CRF_EDITS_H
 
@@ -59,14 +60,15 @@ struct ShCrfEditsRead {
     int pitch;          /* floats from one entry's row to the next (>= seqlen + 2) */
 };
 
-struct ShCrfEditsArgs {
-    const ShCrfEditsRead *rd;
+template <class Rec> struct ShCrfEditsArgsT {
+    const Rec *rd;
     const float *trans;         /* d_E, or the uploaded matrices */
-    const int *seq;
+    const int *seq;             /* codes, and behind them the bands */
     float *rows;
     float *res;
     float *base;                /* [read] */
 };
+using ShCrfEditsArgs = ShCrfEditsArgsT<ShCrfEditsRead>;
 
 /* A read in a band: the cells [low[t], high[t]) of entry t, as k_map_crf takes them (nblock + 1 int32 each, in seq[] behind the codes).  An entry's
  * row holds its band's cells alone, cell p at float p - low[t], and the slot at pitch - 1 takes the stores of threads without a cell: pitch is
@@ -74,15 +76,7 @@ struct ShCrfEditsArgs {
 struct ShCrfEditsBandRead : ShCrfEditsRead {
     long long band;     /* offset in seq[] of low; high the next nblock + 1 */
 };
-
-struct ShCrfEditsBandArgs {
-    const ShCrfEditsBandRead *rd;
-    const float *trans;
-    const int *seq;             /* codes and bands */
-    float *rows;
-    float *res;
-    float *base;
-};
+using ShCrfEditsBandArgs = ShCrfEditsArgsT<ShCrfEditsBandRead>;
 
 template <bool VIT> __device__ __forceinline__ float sh_ce_mx(float a, float b) { return VIT ? (b > a ? b : a) : sh_lse(a, b); }
 template <bool VIT> __device__ __forceinline__ float sh_ce_end(float x, float y) { return VIT ? (x >= y ? x : y) : sh_lse(x, y); }
@@ -108,7 +102,6 @@ __global__ __launch_bounds__(SH_MAP_NTH) void k_crf_edits_rows(ShCrfEditsArgsOf<
     int *const sq = (int *)(sh_ce_lds + SH_MAPC_HEAD + 4 * RW);
     for (int i = tid; i < L; i += SH_MAP_NTH) sq[i] = a.seq[r.seq + i];
     float *const gB = a.rows + r.rows + (BACK ? 2 * M : 0), *const gS = gB + M;      /* (BACK: gS is not used) */
-    const int nch = (L + SH_MAP_NTH) / SH_MAP_NTH;           /* chunks of the block loop: cells 0 .. L (BAND: per entry, below) */
     /* BAND: the band of the entry a step reads (lo_p, hi_p) and of the one it completes (lo_c, hi_c), as k_map_crf keeps them */
     const int *blo = nullptr, *bhi = nullptr;
     int lo_p = 0, hi_p = L + 1, lo_c = 0, hi_c = L + 1;
@@ -147,55 +140,23 @@ __global__ __launch_bounds__(SH_MAP_NTH) void k_crf_edits_rows(ShCrfEditsArgsOf<
             float *const cB = (k & 1) ? buf0 : buf1, *const cS = cB + RW;
             const float *const tr = trb + (k & 1) * 32;
             const float tSS = tr[24];
-            if constexpr (BAND) {                            /* k_map_crf's banded loop: the band's cells alone, from the 64-cell group of lo_c on */
-                const int en = entry(k + 1);
-                const int lo_n = blo[en], hi_n = bhi[en];    /* asked for before the barrier */
-                const int base = lo_c & ~63;
-                const int nchb = (hi_c - base + SH_MAP_NTH - 1) / SH_MAP_NTH;
-                for (int ch = 0; ch < nchb; ch++) {
-                    const int p = base + ch * SH_MAP_NTH + tid;
-                    const bool valid = p >= lo_c && p < hi_c;
-                    const int b = sq[min(max(p - 1, 0), L - 1)];            /* seq[p - 1] */
-                    const bool in0 = p >= lo_p && p < hi_p;                 /* cell p of the entry read */
-                    float vb, vs;
-                    if (!BACK) {
-                        const int p0 = min(p, L), p1 = min(max(p - 1, 0), L);
-                        const int bp = sq[min(max(p - 2, 0), L - 1)];
-                        const bool in1 = p - 1 >= lo_p && p - 1 < hi_p;
-                        const float lB0 = pB[p0], lS0 = pS[p0], lB1 = pB[p1], lS1 = pS[p1];
-                        const float B0 = in0 ? lB0 : -SH_MAP_BIG, S0 = in0 ? lS0 : -SH_MAP_BIG;
-                        const float B1 = in1 ? lB1 : -SH_MAP_BIG, S1 = in1 ? lS1 : -SH_MAP_BIG;
-                        bool kb, ks;
-                        sh_map_crf_cell<VIT>(tr, tSS, b, bp, p, B0, S0, B1, S1, vb, vs, kb, ks);
-                    } else {
-                        const int nx = sq[min(p, L - 1)];
-                        const bool inx = p + 1 >= lo_p && p + 1 < hi_p;     /* cell p + 1 of the entry read (never L + 1: hi_p <= L + 1) */
-                        const float lB = pB[min(p + 1, L)], lS = pS[min(p, L)];
-                        const float nB = inx ? lB : -SH_MAP_BIG, nS = in0 ? lS : -SH_MAP_BIG;
-                        const float mvB = tr[5 * nx + b] + nB, stB = tr[20 + b] + nS;
-                        const float mvS = tr[5 * nx + 4] + nB, stS = tSS + nS;
-                        vb = p < L ? sh_ce_mx<VIT>(mvB, stB) : stB;
-                        vs = p < L ? sh_ce_mx<VIT>(mvS, stS) : stS;
-                        if (p < 1) vb = -SH_MAP_BIG;
-                    }
-                    const int at = valid ? p : SPARE;
-                    const long long gat = valid ? (long long)(p - lo_c) : P - 1;       /* the row holds the band's cells; its last slot is no cell's */
-                    cB[at] = vb;
-                    cS[at] = vs;
-                    gB[row + gat] = vb;
-                    if (!BACK) gS[row + gat] = vs;
-                }
-                lo_p = lo_c; hi_p = hi_c; lo_c = lo_n; hi_c = hi_n;
-            }
-            for (int ch = 0; !BAND && ch < nch; ch++) {      /* without a band: cells 0 .. L */
-                const int p = ch * SH_MAP_NTH + tid;
-                const bool valid = p <= L;
+            /* k_map_crf's loop: the band's cells alone, from the 64-cell group of lo_c on; without a band the bounds are 0 and L + 1, constants: cells 0 .. L */
+            int lo_n = 0, hi_n = L + 1;
+            if constexpr (BAND) { const int en = entry(k + 1); lo_n = blo[en]; hi_n = bhi[en]; }      /* asked for before the barrier */
+            const int base = lo_c & ~63;
+            const int nchb = (hi_c - base + SH_MAP_NTH - 1) / SH_MAP_NTH;
+            for (int ch = 0; ch < nchb; ch++) {
+                const int p = base + ch * SH_MAP_NTH + tid;
+                const bool valid = p >= lo_c && p < hi_c;
                 const int b = sq[min(max(p - 1, 0), L - 1)];            /* seq[p - 1] */
+                /* what is read is masked by the band of the entry read: forward as k_map_crf does, without a band too; the recursion back needs no mask then */
+                constexpr bool FREE = !BAND && BACK;
+                const bool in0 = FREE || (p >= lo_p && p < hi_p);       /* cell p of the entry read */
                 float vb, vs;
-                if (!BACK) {                                 /* k_map_crf's unbanded cell */
+                if (!BACK) {                                 /* k_map_crf's cell */
                     const int p0 = min(p, L), p1 = min(max(p - 1, 0), L);
                     const int bp = sq[min(max(p - 2, 0), L - 1)];
-                    const bool in0 = p <= L, in1 = p >= 1 && p - 1 <= L;
+                    const bool in1 = p - 1 >= lo_p && p - 1 <= hi_p - 1;    /* cell p - 1 (in these words the block loop without a band compiles to the code it was: profiles/edits_band_layer_refactor.txt, section 2) */
                     const float lB0 = pB[p0], lS0 = pS[p0], lB1 = pB[p1], lS1 = pS[p1];
                     const float B0 = in0 ? lB0 : -SH_MAP_BIG, S0 = in0 ? lS0 : -SH_MAP_BIG;
                     const float B1 = in1 ? lB1 : -SH_MAP_BIG, S1 = in1 ? lS1 : -SH_MAP_BIG;
@@ -203,7 +164,9 @@ __global__ __launch_bounds__(SH_MAP_NTH) void k_crf_edits_rows(ShCrfEditsArgsOf<
                     sh_map_crf_cell<VIT>(tr, tSS, b, bp, p, B0, S0, B1, S1, vb, vs, kb, ks);
                 } else {
                     const int nx = sq[min(p, L - 1)];        /* seq[p]: the next base, where p < L */
-                    const float nB = pB[min(p + 1, L)], nS = pS[min(p, L)];
+                    const bool inx = FREE || (p + 1 >= lo_p && p + 1 < hi_p);      /* cell p + 1 of the entry read (never L + 1: hi_p <= L + 1) */
+                    const float lB = pB[min(p + 1, L)], lS = pS[min(p, L)];
+                    const float nB = inx ? lB : -SH_MAP_BIG, nS = in0 ? lS : -SH_MAP_BIG;
                     const float mvB = tr[5 * nx + b] + nB, stB = tr[20 + b] + nS;
                     const float mvS = tr[5 * nx + 4] + nB, stS = tSS + nS;
                     vb = p < L ? sh_ce_mx<VIT>(mvB, stB) : stB;
@@ -211,11 +174,13 @@ __global__ __launch_bounds__(SH_MAP_NTH) void k_crf_edits_rows(ShCrfEditsArgsOf<
                     if (p < 1) vb = -SH_MAP_BIG;             /* there is no B[0] */
                 }
                 const int at = valid ? p : SPARE;
+                const long long gat = !BAND ? (long long)at : valid ? (long long)(p - lo_c) : P - 1;      /* BAND: the row holds the band's cells; its last slot is no cell's */
                 cB[at] = vb;
                 cS[at] = vs;
-                gB[row + at] = vb;
-                if (!BACK) gS[row + at] = vs;
+                gB[row + gat] = vb;
+                if (!BACK) gS[row + gat] = vs;
             }
+            if constexpr (BAND) { lo_p = lo_c; hi_p = hi_c; lo_c = lo_n; hi_c = hi_n; }
             if (tid < 32) trb[((k + 1) & 1) * 32 + tid] = q[d];     /* step k + 1's column; read last in step k - 1, a barrier ago */
             q[d] = v.col(blk(k + 1 + SH_MAPC_D))[slot];
             __syncthreads();

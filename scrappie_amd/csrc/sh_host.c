@@ -1054,16 +1054,31 @@ size_t scrappie_hip_crf_edits_pitch(size_t seqlen) { return (seqlen + 2 + 15) / 
 static size_t crf_edits_res_floats(size_t seqlen) { return (9 * seqlen + 4 + 3) / 4 * 4; }
 size_t scrappie_hip_crf_edits_row_bytes(size_t seqlen, size_t nblock) { return 3 * (nblock + 1) * scrappie_hip_crf_edits_pitch(seqlen) * 4; }
 
-/* The layout that the two planners of the edit engines below share, k 0 for the flip-flop family: read i takes its pitch and row floats of
- * its family, the reads lie one behind the other in input order in the row buffer and in the result buffer.  Returns the floats of the
- * row buffer; *res_floats (may be NULL): those of the result buffer. */
-static long long edits_plan(const size_t *seqlen, const size_t *nblock, size_t n, size_t k, int *pitch, long long *rows, long long *res, long long *res_floats) {
+/* The pitch of a read in a band of `entries` entries: an entry's row holds its band's cells alone and a last slot that is no cell's; one pitch per
+ * read, the widest entry's cells and that slot rounded up to 16 floats.  An entry that is empty or the wrong way round counts as one cell (the
+ * engines refuse such a band before they plan).  0: a null argument. */
+static size_t edits_band_pitch(const size_t *low, const size_t *high, size_t entries) {
+    size_t w = 1;
+    if (!low || !high) return 0;
+    for (size_t t = 0; t < entries; t++)
+        if (high[t] > low[t] && high[t] - low[t] > w) w = high[t] - low[t];
+    return (w + 1 + 15) / 16 * 16;
+}
+
+/* The layout that the four planners of the edit engines below share, k 0 for the flip-flop family (three row matrices, bands of nblock + 1
+ * entries; else two, of nblock): read i takes its family's pitch -- where low and high are given and neither of low[i], high[i] is NULL, its
+ * band's -- and nblock[i] + 1 rows of it per matrix; the reads lie one behind the other in input order in the row buffer and in the result
+ * buffer.  Returns the floats of the row buffer; *res_floats (may be NULL): those of the result buffer. */
+static long long edits_plan(const size_t *seqlen, const size_t *nblock, const size_t *const *low, const size_t *const *high, size_t n, size_t k, int *pitch,
+                            long long *rows, long long *res, long long *res_floats) {
     long long nrow = 0, nres = 0;
     for (size_t i = 0; i < n; i++) {
-        pitch[i] = (int)(k ? scrappie_hip_map_edits_pitch(seqlen[i], k) : scrappie_hip_crf_edits_pitch(seqlen[i]));
+        const size_t p = low && high && low[i] && high[i] ? edits_band_pitch(low[i], high[i], k ? nblock[i] : nblock[i] + 1)
+                         : k ? scrappie_hip_map_edits_pitch(seqlen[i], k) : scrappie_hip_crf_edits_pitch(seqlen[i]);
+        pitch[i] = (int)p;
         rows[i] = nrow;
         res[i] = nres;
-        nrow += (long long)((k ? scrappie_hip_map_edits_row_bytes(seqlen[i], k, nblock[i]) : scrappie_hip_crf_edits_row_bytes(seqlen[i], nblock[i])) / 4);
+        nrow += (long long)((k ? 2 : 3) * (nblock[i] + 1) * p);
         nres += (long long)crf_edits_res_floats(seqlen[i]);
     }
     if (res_floats) *res_floats = nres;
@@ -1078,20 +1093,12 @@ long long scrappie_hip_crf_edits_plan(const size_t *seqlen, const size_t *nblock
                                       long long *res_floats) {
     if (res_floats) *res_floats = 0;
     if (!seqlen || !nblock || !pitch || !rows || !res) return 0;
-    return edits_plan(seqlen, nblock, n, 0, pitch, rows, res, res_floats);
+    return edits_plan(seqlen, nblock, NULL, NULL, n, 0, pitch, rows, res, res_floats);
 }
 
 /* The same in a band (low, high: nblock + 1 entries each, as scrappie_hip_map_crf_bounds_sane takes them): an entry's row holds its band's
- * cells alone, cell p of entry t at float p - low[t], and the row's last slot takes the stores of threads without a cell.  One pitch per read:
- * the widest entry's cells and that slot, rounded up to 16 floats.  An entry that is empty or the wrong way round counts as one cell (the
- * engine refuses such a band before it plans). */
-size_t scrappie_hip_crf_edits_band_pitch(const size_t *low, const size_t *high, size_t nblock) {
-    size_t w = 1;
-    if (!low || !high) return 0;
-    for (size_t t = 0; t <= nblock; t++)
-        if (high[t] > low[t] && high[t] - low[t] > w) w = high[t] - low[t];
-    return (w + 1 + 15) / 16 * 16;
-}
+ * cells alone, cell p of entry t at float p - low[t], and the row's last slot takes the stores of threads without a cell (edits_band_pitch). */
+size_t scrappie_hip_crf_edits_band_pitch(const size_t *low, const size_t *high, size_t nblock) { return edits_band_pitch(low, high, nblock + 1); }
 size_t scrappie_hip_crf_edits_band_row_bytes(const size_t *low, const size_t *high, size_t nblock) {
     return 3 * (nblock + 1) * scrappie_hip_crf_edits_band_pitch(low, high, nblock) * 4;
 }
@@ -1100,20 +1107,9 @@ size_t scrappie_hip_crf_edits_band_row_bytes(const size_t *low, const size_t *hi
  * has no band and takes the unbanded pitch and rows.  Everything else as there. */
 long long scrappie_hip_crf_edits_band_plan(const size_t *seqlen, const size_t *nblock, const size_t *const *low, const size_t *const *high, size_t n,
                                            int *pitch, long long *rows, long long *res, long long *res_floats) {
-    long long nrow = 0, nres = 0;
     if (res_floats) *res_floats = 0;
     if (!seqlen || !nblock || !low || !high || !pitch || !rows || !res) return 0;
-    for (size_t i = 0; i < n; i++) {
-        const int band = low[i] && high[i];
-        const size_t p = band ? scrappie_hip_crf_edits_band_pitch(low[i], high[i], nblock[i]) : scrappie_hip_crf_edits_pitch(seqlen[i]);
-        pitch[i] = (int)p;
-        rows[i] = nrow;
-        res[i] = nres;
-        nrow += (long long)(3 * (nblock[i] + 1) * p);
-        nres += (long long)crf_edits_res_floats(seqlen[i]);
-    }
-    if (res_floats) *res_floats = nres;
-    return nrow;
+    return edits_plan(seqlen, nblock, low, high, n, 0, pitch, rows, res, res_floats);
 }
 
 /* The band around a Viterbi path of k_map_crf: path[t], t = 0 .. nblock, the index of the last base emitted through entry t (-1: none), so
@@ -1163,20 +1159,13 @@ long long scrappie_hip_map_edits_plan(const size_t *seqlen, const size_t *nblock
     if (k == 0) return -1;
     for (size_t i = 0; i < n; i++)
         if (seqlen[i] < k) return -1;
-    return edits_plan(seqlen, nblock, n, k, pitch, rows, res, res_floats);
+    return edits_plan(seqlen, nblock, NULL, NULL, n, k, pitch, rows, res, res_floats);
 }
 
 /* The same in a band (low, high: nblock entries each, as are_bounds_sane takes them; cell q of entry t + 1 admissible iff low[t] <= q < high[t]):
  * an entry's row holds its band's cells alone, cell q of entry t + 1 at float q - low[t], and the row's last slot holds FS (forward) or takes the
- * stores of threads without a cell (backward).  One pitch per read: the widest entry's cells and that slot, rounded up to 16 floats.  An entry that
- * is empty or the wrong way round counts as one cell (the engine refuses a band that is not sane before it plans).  0: a null argument. */
-size_t scrappie_hip_map_edits_band_pitch(const size_t *low, const size_t *high, size_t nblock) {
-    size_t w = 1;
-    if (!low || !high) return 0;
-    for (size_t t = 0; t < nblock; t++)
-        if (high[t] > low[t] && high[t] - low[t] > w) w = high[t] - low[t];
-    return (w + 1 + 15) / 16 * 16;
-}
+ * stores of threads without a cell (backward) (edits_band_pitch).  0: a null argument. */
+size_t scrappie_hip_map_edits_band_pitch(const size_t *low, const size_t *high, size_t nblock) { return edits_band_pitch(low, high, nblock); }
 size_t scrappie_hip_map_edits_band_row_bytes(const size_t *low, const size_t *high, size_t nblock) {
     return 2 * (nblock + 1) * scrappie_hip_map_edits_band_pitch(low, high, nblock) * 4;
 }
@@ -1185,23 +1174,12 @@ size_t scrappie_hip_map_edits_band_row_bytes(const size_t *low, const size_t *hi
  * no band and takes the unbanded pitch and rows.  Everything else as there. */
 long long scrappie_hip_map_edits_band_plan(const size_t *seqlen, const size_t *nblock, const size_t *const *low, const size_t *const *high, size_t n,
                                            size_t k, int *pitch, long long *rows, long long *res, long long *res_floats) {
-    long long nrow = 0, nres = 0;
     if (res_floats) *res_floats = 0;
     if (!seqlen || !nblock || !low || !high || !pitch || !rows || !res) return 0;
     if (k == 0) return -1;
     for (size_t i = 0; i < n; i++)
         if (seqlen[i] < k) return -1;
-    for (size_t i = 0; i < n; i++) {
-        const int band = low[i] && high[i];
-        const size_t p = band ? scrappie_hip_map_edits_band_pitch(low[i], high[i], nblock[i]) : scrappie_hip_map_edits_pitch(seqlen[i], k);
-        pitch[i] = (int)p;
-        rows[i] = nrow;
-        res[i] = nres;
-        nrow += (long long)(2 * (nblock[i] + 1) * p);
-        nres += (long long)crf_edits_res_floats(seqlen[i]);
-    }
-    if (res_floats) *res_floats = nres;
-    return nrow;
+    return edits_plan(seqlen, nblock, low, high, n, k, pitch, rows, res, res_floats);
 }
 
 /* The band around a Viterbi path of k_map: path[t], t = 0 .. nblock - 1, the state after block t (0 .. nstate - 1; -1 in START and in END).  p[t] is

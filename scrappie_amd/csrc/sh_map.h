@@ -102,9 +102,10 @@ __device__ __forceinline__ unsigned sh_spread16(unsigned x) {
  * previous block's row, i the cell in it, le the cell's posterior entry, lps the stay entry.  pos: the cell's position in its
  * sequence, of which only 0, 1 and "2 or more" matter: from 1 on it has a left neighbour (i - 1), from 2 on two of them (i - 2),
  * and position 0 reads START at p[start].
- * The reference's expressions in its order -- stay, step, skip, START -- with strict > (code: the move taken) or sh_lse. */
-template <bool VIT>
-__device__ __forceinline__ float sh_map_cell(const float *p, int i, int start, int pos, float le, float lps, float stay_pen, float skip_pen,
+ * The reference's expressions in its order -- stay, step, skip, START -- with strict > (code: the move taken) or sh_lse.  Row: a pointer, or
+ * what answers p[i] as one does (k_map_edits_rows reads the row under a band: ShMapEditsRow, sh_map_edits.h). */
+template <bool VIT, class Row>
+__device__ __forceinline__ float sh_map_cell(const Row p, int i, int start, int pos, float le, float lps, float stay_pen, float skip_pen,
                                              int &code) {
     float v = (p[i] - stay_pen) + lps;
     if (VIT) {

@@ -1,6 +1,7 @@
 /* sh_map_edits.h -- part of sh_kernels.h (included from there, behind sh_map_local.h): EVERY single-base edit of a sequence scored against
  * a read of a transducer model in one pass -- 4 L substitutions (the L that change nothing among them), L deletions, 4 (L + 1) insertions --
- * each the score map_to_sequence_viterbi / _forward (k_map, sh_map.h) give for the k-mer states of the edited sequence.  Scores only, unbanded.
+ * each the score map_to_sequence_viterbi / _forward (k_map, sh_map.h) give for the k-mer states of the edited sequence.  Scores only; unbanded, or
+ * (the BAND instantiations, at the end of this comment) inside a band of map_to_sequence_*_banded's kind.
  *
  * The lattice is k_map's: states s[q] = kmer(seq[q .. q + k)), q = 0 .. n - 1, n = L - k + 1; START, END; stay, step, skip.  Entries
  * t = 0 .. NB, block t leads from entry t to entry t + 1.  lps the block's stay entry, ls = mx(-local_pen, lps).
@@ -35,7 +36,14 @@
  * call k_map makes), SH_ME_CH blocks per barrier, double-buffered, the next chunk already in registers.  Every LDS and vector-memory operation
  * of the block loop is unconditional: clamped indices, selects, no lane conditions.
  * Results per read at res: sub [L][4], ins [L + 1][4], del [L] (in this order: the float4 stores stay 16-byte aligned); a score below
- * -SH_MAP_BIG / 2: no admissible path (the host answers NAN).  All stores are plain vector stores. */
+ * -SH_MAP_BIG / 2: no admissible path (the host answers NAN).  All stores are plain vector stores.
+ *
+ * BAND = true (ShMapEditsBandRead, below): F and G hold -SH_MAP_BIG outside the band of their entry and an entry's row holds its band's cells alone.
+ * The rows kernel has ONE block loop for both forms -- per entry the cells from the 64-cell group of low on and at least one thread without a
+ * cell, the previous row read under the previous entry's band (forward: sh_map_cell on a ShMapEditsRow, whose reads of the cells to the left and
+ * of START sit under its position tests, as in k_map) -- whose bounds without a band are the
+ * constants 0 and n; BAND decides the bounds, the first chunk's base and the row index of the global store alone.  k_map_edits: a few
+ * `if constexpr` lines. */
 #ifndef SH_MAP_EDITS_H
 #define SH_MAP_EDITS_H
 
@@ -84,6 +92,13 @@ struct ShMapEditsBandArgs : ShMapEditsArgsT<ShMapEditsBandRead> {
     int width;          /* host only: the positions per workgroup of k_map_edits this launch takes (64 or 256) */
 };
 template <bool BAND> using ShMapEditsArgsOf = std::conditional_t<BAND, ShMapEditsBandArgs, ShMapEditsArgs>;
+/* what the kernels take of the caller, from one form's arguments to the other's: the one place the fields are copied (the launch sets the rest) */
+template <class To, class From> static To sh_map_edits_args_as(const From &u) {
+    To a{};
+    a.post = u.post; a.E = u.E; a.sums = u.sums; a.pstride = u.pstride; a.nr = u.nr; a.nchunk = u.nchunk; a.k = u.k; a.min_prob = u.min_prob;
+    a.stay_pen = u.stay_pen; a.skip_pen = u.skip_pen; a.local_pen = u.local_pen;
+    return a;
+}
 
 /* the band of entry e of a read of NB blocks: [lo, hi); entry 0 has none */
 __device__ __forceinline__ void sh_me_band(const int *blo, int NB, int e, int &lo, int &hi) {
@@ -99,6 +114,17 @@ template <bool VIT> __device__ __forceinline__ float sh_me_mx_if(bool on, float 
     return VIT ? ((on && b > a) ? b : a) : sh_lse(a, on ? b : -4.0f * SH_MAP_BIG);
 }
 
+/* a row of n cells under the band [lo, hi) of its entry, as sh_map_cell reads one: a cell outside the band is -SH_MAP_BIG; the slots from n on
+ * (START, END) and, without a band, everything as they stand */
+template <bool BAND> struct ShMapEditsRow {
+    const float *p;
+    int lo, hi, n;
+    __device__ __forceinline__ float operator[](int x) const {
+        const float l = p[x];
+        return (!BAND || x >= n || (x >= lo && x < hi)) ? l : -SH_MAP_BIG;
+    }
+};
+
 template <bool VIT, bool TILED, bool BACK, bool BAND = false>
 __global__ __launch_bounds__(SH_MAP_NTH) void k_map_edits_rows(ShMapEditsArgsOf<BAND> a) {
     extern __shared__ __attribute__((aligned(16))) float sh_me_lds[];
@@ -113,7 +139,7 @@ __global__ __launch_bounds__(SH_MAP_NTH) void k_map_edits_rows(ShMapEditsArgsOf<
     float *const grow = a.rows + r.rows + (BACK ? (long long)(NB + 1) * P : 0);
     /* BAND: the band of the entry a step reads (lo_p, hi_p) and of the one it completes (lo_c, hi_c) */
     const int *blo = nullptr;
-    int lo_p = 0, hi_p = 0, lo_c = 0, hi_c = 0;
+    int lo_p = 0, hi_p = n, lo_c = 0, hi_c = n;
     if constexpr (BAND) {
         blo = a.seq + r.band;
         sh_me_band(blo, NB, BACK ? NB : 0, lo_p, hi_p);
@@ -139,7 +165,6 @@ __global__ __launch_bounds__(SH_MAP_NTH) void k_map_edits_rows(ShMapEditsArgsOf<
     ShMapRead mr{};
     mr.post = r.post; mr.lane = r.lane;
     ShMapPost<TILED> lp;
-    const int nch = (n + SH_MAP_NTH) / SH_MAP_NTH;           /* chunks of the block loop: cells 0 .. n - 1 and slot n */
     float chain = 0.0f;                                      /* FS[t] going forward, GE[t + 1] going backward: the same in every thread */
     __syncthreads();
     for (int step = 0; step < NB; step++) {
@@ -150,74 +175,43 @@ __global__ __launch_bounds__(SH_MAP_NTH) void k_map_edits_rows(ShMapEditsArgsOf<
         lp.block(ma, mr, t);
         const float lps = lp(STAY);
         const float ls = VIT ? fmaxf(-local_pen, lps) : sh_lse(-local_pen, lps);
-        if constexpr (BAND) {                                /* the band's cells alone, from the 64-cell group of lo_c on, and at least one thread without a cell */
-            int lo_n, hi_n;
-            sh_me_band(blo, NB, BACK ? max(t - 1, 0) : min(t + 2, NB), lo_n, hi_n);      /* asked for before the barrier */
-            const int base = lo_c & ~63;
-            const int nchb = (hi_c - base + SH_MAP_NTH) / SH_MAP_NTH;
-            auto in_p = [&](int x) { return x >= lo_p && x < hi_p; };      /* cell x of the entry read */
-            for (int ch = 0; ch < nchb; ch++) {
-                const int pos = base + ch * SH_MAP_NTH + tid, q = min(pos, n - 1);
-                const bool valid = pos >= lo_c && pos < hi_c;
-                float v;
-                if (!BACK) {                                 /* k_map's unbanded cell on the masked row */
-                    const float l0 = p[q], l1 = p[max(q - 1, 0)], l2 = p[max(q - 2, 0)], ps = p[START];
-                    const float p0 = in_p(q) ? l0 : -SH_MAP_BIG, p1 = in_p(q - 1) ? l1 : -SH_MAP_BIG, p2 = in_p(q - 2) ? l2 : -SH_MAP_BIG;
-                    const float le = lp(sq[q]);
-                    float cell = (p0 - stay_pen) + lps;
-                    cell = sh_me_mx_if<VIT>(q >= 1, cell, p1 + le);
-                    cell = sh_me_mx_if<VIT>(q >= 2, cell, (p2 - skip_pen) + le);
-                    cell = sh_me_mx_if<VIT>(q == 0, cell, ps + le);
-                    v = valid ? cell : chain + ls;           /* the slot: FS[t + 1] */
-                } else {
-                    const int q1 = min(q + 1, n - 1), q2 = min(q + 2, n - 1);
-                    const float le1 = lp(sq[q1]), le2 = lp(sq[q2]);
-                    const float l0 = p[q], l1 = p[q1], l2 = p[q2];
-                    const float g0 = in_p(q) ? l0 : -SH_MAP_BIG, g1 = in_p(q1) ? l1 : -SH_MAP_BIG, g2 = in_p(q2) ? l2 : -SH_MAP_BIG;
-                    v = (lps - stay_pen) + g0;
-                    v = sh_me_mx_if<VIT>(q + 1 < n, v, le1 + g1);
-                    v = sh_me_mx_if<VIT>(q + 2 < n, v, (le2 - skip_pen) + g2);
-                    v = sh_me_mx_if<VIT>(q == n - 1, v, -local_pen + chain);
-                }
-                c[valid ? pos : n] = v;
-                g[valid ? (long long)(pos - lo_c) : P - 1] = v;      /* the row holds the band's cells; its last slot is no cell's */
-            }
-            if (!BACK && tid == 0) {                         /* END, reading cell n - 1 under its band */
-                float e = p[END] + ls;
-                const float pl = p[n - 1];
-                const float ex = (in_p(n - 1) ? pl : -SH_MAP_BIG) - local_pen;
-                if (VIT) { if (ex > e) e = ex; }
-                else e = sh_lse(e, ex);
-                c[END] = e;
-            }
-            lo_p = lo_c; hi_p = hi_c; lo_c = lo_n; hi_c = hi_n;
-        }
-        for (int ch = 0; !BAND && ch < nch; ch++) {
-            const int pos = ch * SH_MAP_NTH + tid, q = min(pos, n - 1), at = min(pos, n);
+        /* the band's cells alone, from the 64-cell group of lo_c on, and at least one thread without a cell; without a band the bounds are 0 and n,
+         * constants: cells 0 .. n - 1 and slot n */
+        int lo_n = 0, hi_n = n;
+        if constexpr (BAND) sh_me_band(blo, NB, BACK ? max(t - 1, 0) : min(t + 2, NB), lo_n, hi_n);      /* asked for before the barrier */
+        const int base = lo_c & ~63;
+        const int nchb = (hi_c - base + SH_MAP_NTH) / SH_MAP_NTH;
+        auto in_p = [&](int x) { return !BAND || (x >= lo_p && x < hi_p); };      /* cell x of the entry read */
+        for (int ch = 0; ch < nchb; ch++) {
+            const int pos = base + ch * SH_MAP_NTH + tid, q = min(pos, n - 1);
+            const bool valid = pos >= lo_c && pos < hi_c;
             float v;
-            if (!BACK) {                                     /* k_map's unbanded cell */
+            if (!BACK) {                                     /* k_map's unbanded cell on the masked row */
                 int code;
-                const float cell = sh_map_cell<VIT>(p, q, START, q, lp(sq[q]), lps, stay_pen, skip_pen, code);
-                v = pos < n ? cell : chain + ls;             /* slot n: FS[t + 1] */
+                const float cell = sh_map_cell<VIT>(ShMapEditsRow<BAND>{p, lo_p, hi_p, n}, q, START, q, lp(sq[q]), lps, stay_pen, skip_pen, code);
+                v = valid ? cell : chain + ls;               /* the slot: FS[t + 1] */
             } else {
                 const int q1 = min(q + 1, n - 1), q2 = min(q + 2, n - 1);
                 const float le1 = lp(sq[q1]), le2 = lp(sq[q2]);
-                const float g0 = p[q], g1 = p[q1], g2 = p[q2];
+                const float l0 = p[q], l1 = p[q1], l2 = p[q2];
+                const float g0 = in_p(q) ? l0 : -SH_MAP_BIG, g1 = in_p(q1) ? l1 : -SH_MAP_BIG, g2 = in_p(q2) ? l2 : -SH_MAP_BIG;
                 v = (lps - stay_pen) + g0;
                 v = sh_me_mx_if<VIT>(q + 1 < n, v, le1 + g1);
                 v = sh_me_mx_if<VIT>(q + 2 < n, v, (le2 - skip_pen) + g2);
                 v = sh_me_mx_if<VIT>(q == n - 1, v, -local_pen + chain);
             }
-            c[at] = v;
-            g[at] = v;
+            c[valid ? pos : n] = v;
+            g[!BAND ? (long long)min(pos, n) : valid ? (long long)(pos - lo_c) : P - 1] = v;      /* BAND: the row holds the band's cells; its last slot is no cell's */
         }
-        if (!BAND && !BACK && tid == 0) {                    /* END, as k_map keeps it */
+        if (!BACK && tid == 0) {                             /* END, as k_map keeps it, reading cell n - 1 under its band */
             float e = p[END] + ls;
-            const float ex = p[n - 1] - local_pen;
+            const float pl = p[n - 1];
+            const float ex = (in_p(n - 1) ? pl : -SH_MAP_BIG) - local_pen;
             if (VIT) { if (ex > e) e = ex; }
             else e = sh_lse(e, ex);
             c[END] = e;
         }
+        if constexpr (BAND) { lo_p = lo_c; hi_p = hi_c; lo_c = lo_n; hi_c = hi_n; }
         chain = chain + ls;
         __syncthreads();
     }

@@ -182,6 +182,58 @@ def test_edits_families_keep_their_own_state(eng):
     _same((again_a, again_b), first)
 
 
+def test_banded_edits_families_keep_their_own_state(eng):
+    """the same for the banded calls, whose forms are the band layer's of the one driver (EditsForm, sh_eng_edits.inc): a call of
+    either family with bands of half-width 8 around the reads' paths, the second read without a band, under a budget of 1 KB (every
+    read goes alone) moves the banded counters of its own family by the two reads in bands and the unbanded ones by the read
+    without -- the transducer family's at 64 positions per workgroup, none at 256 --, and no counter of the other family; either's
+    timing still reports its own last call (three launches, the row bytes of two bands and one full matrix) after the other's, and
+    the results do not depend on which family ran first"""
+    rng = np.random.default_rng(97)
+    sigs = [synth.medmad_normalise(synth.synthetic_signal(n, 700 + i)) for i, n in enumerate((900, 1300, 1100))]
+    seqs = [_bases(40, rng) for _ in sigs]
+    crf_bands = [sa.map_crf_path_band(path, 40, 8) for sc, path in eng.map_to_sequence(sigs, seqs, model="rnnrf_r94", viterbi=True, path=True)]
+    map_bands = [sa.map_path_band(path, 40 - 5 + 1, 8) for sc, path in eng.map_to_sequence(sigs, seqs, model="rgrgr_r94", viterbi=True, path=True)]
+    crf_bands[1] = map_bands[1] = None
+    crf_rows = sa.crf_edits_band_row_bytes(*crf_bands[0]) + sa.crf_edits_band_row_bytes(*crf_bands[2]) + \
+        sa.lib().scrappie_hip_crf_edits_row_bytes(40, len(eng.posterior(sigs[1], "rnnrf_r94")))
+    map_rows = sa.map_edits_band_row_bytes(*map_bands[0]) + sa.map_edits_band_row_bytes(*map_bands[2]) + \
+        sa.lib().scrappie_hip_map_edits_row_bytes(40, 5, len(eng.posterior(sigs[1], "rgrgr_r94")))
+    counters = dict(crf=sa.crf_edits_form_counts, crf_band=sa.crf_edits_band_form_counts, tr=sa.map_edits_form_counts, tr_band=sa.map_edits_band_form_counts)
+    moved = lambda now, before: {k: now[k] - before[k] for k in now if now[k] != before[k]}
+
+    def call(option, run, vit, expect):
+        before = {k: f() for k, f in counters.items()}
+        assert [len(before[k]) for k in ("crf", "crf_band", "tr", "tr_band")] == [12, 12, 12, 16]
+        eng.debug_option(option, 1)
+        try:
+            res = run(vit)
+        finally:
+            eng.debug_option(option, 0)
+        for k, f in counters.items():
+            assert moved(f(), before[k]) == expect.get(k, {}), k
+        return res
+
+    forms = lambda vit, n, *width: {("rows", vit, True, False): n, ("rows", vit, True, True): n, ("edits", vit, True) + width: n}
+    call_a = lambda: call("crf_edits_budget_kb", lambda vit: eng.score_edits(sigs, seqs, viterbi=vit, bands=crf_bands), True,
+                          dict(crf_band=forms(True, 2), crf=forms(True, 1)))
+    call_b = lambda: call("map_edits_budget_kb", lambda vit: eng.score_edits_transducer(sigs, seqs, viterbi=vit, bands=map_bands), False,
+                          dict(tr_band=forms(False, 2, 64), tr=forms(False, 1)))
+
+    def timing():
+        a, b = eng.crf_edits_timing(), eng.map_edits_timing()
+        assert (a["launches"], a["row_bytes"]) == (3, crf_rows), a
+        assert (b["launches"], b["row_bytes"]) == (3, map_rows), b
+
+    first = call_a(), call_b()
+    assert all(np.isfinite(r[0]) and np.any(np.isfinite(r[1])) for res in first for r in res)
+    timing()                                                # read after B: A's three launches are still the flip-flop family's last call
+    again_b = call_b()
+    again_a = call_a()
+    timing()
+    _same((again_a, again_b), first)
+
+
 def test_pack_families_keep_their_own_state(eng):
     """the two families of "one read against many candidates" run through one driver (sh_eng_cands.inc) and keep form counters,
     buffers and pack size each of its own: a transducer call in packs of 64 cells (a candidate of 30 bases is 26 states and
